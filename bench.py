@@ -21,6 +21,12 @@ frac_plain_launches (an event pair around K plain launches of the same call queu
 fixed cost, no host launch latency). The cpu_baseline leg times the CPU oracle (the C port of
 the reference algorithm) on a bounded sample of the same workload, rank 0 at N = 1 only.
 
+A plain run sets up, warms up, times the K steps and prints the line: value, ms_per_step and the roofline figures of the timed
+region itself. Everything else -- the device self-test, the chain-equals-single-launch check and the single-launch / plain-launch
+timings, the N > 1 shard re-check, the f64-reward and beyond-LLC step legs, beam, evaluation, rollouts and the CPU baselines --
+runs only with --full (the --no-* switches pick among those legs). --dump-outputs DIR writes what the timed path's last step
+computed (a fixed seeded sample of rank 0's boards, f32 / f64 .npy) so that two builds can be compared output for output.
+
 One JSON line on stdout (rank 0).
 """
 import argparse
@@ -42,6 +48,7 @@ HBM_PEAK_GBS = 8000.0        # MI355X_MICROARCH.md: 8.0 TB/s spec
 BEAM_GAMES, BEAM_WIDTH, BEAM_DEPTH = 4096, 20, 30
 BEAM_BYTES_PER_EXPANSION = 29    # "HBM-resident-beam" accounting (parent 16 B / 4 children + child 16 + score 8 + root action 1)
 SIMDS_PER_CU = 4                 # MI355X_MICROARCH.md; the CU count and the clock come from the device properties
+DUMP_SAMPLE = 1 << 18            # boards in the --dump-outputs sample: ~23 MB of .npy files in all (the limit is 64 MB)
 
 
 def parse():
@@ -61,7 +68,14 @@ def parse():
     ap.add_argument("--no-extra", action="store_true", help="skip the HBM-resident and f64-reward step legs")
     ap.add_argument("--cpu-seconds", type=float, default=8.0)
     ap.add_argument("--dry-launch", action="store_true", help="print the multi-GPU child command as JSON and exit")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: self-test, chain / single-launch checks and timings, the other legs, CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the timed path's last-step outputs (seeded sample of rank 0's boards) as DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def _free_port():
@@ -188,6 +202,23 @@ def timed_replay(graph, ev0, ev1, eager, reps=1):
     return best
 
 
+def dump_outputs(path, out, scores, reward, flags, id_base):
+    """--dump-outputs: what a caller of the timed path receives from its last step -- the next boards, the running scores (summed
+    over the K timed steps), the f32 rewards and the flags -- for a fixed seeded sample of the shard's boards (ascending ids, in
+    board_ids), as f32 / f64 .npy files (exact: cells, flags and scores are small integers)."""
+    import numpy as np
+    n = out.shape[0]
+    idx = np.sort(np.random.default_rng(SEED).choice(n, size=min(DUMP_SAMPLE, n), replace=False))
+    arrays = {"board_ids": (idx + id_base).astype(np.float64),
+              "boards": out.cpu().numpy()[idx].astype(np.float32),
+              "scores": scores.cpu().numpy().view(np.uint32)[idx].astype(np.float64),
+              "reward": reward.cpu().numpy()[idx].astype(np.float32),
+              "flags": flags.cpu().numpy()[idx].astype(np.float32)}
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def beam_roots(ops, n, id_base, dev):
     """half the roots reached by 200 moves of seeded self-play under a greedy fast-evaluation policy (a
     width-1, depth-1 beam decision is exactly that: every valid move, its spawn, _fast_evaluate, best one), auto-reset on;
@@ -236,7 +267,8 @@ def main():
     if os.environ.get("G2048_BENCH_FAIL_RANK") == str(rank):       # tests/test_bench_launch.py: a rank that dies while the others wait
         raise RuntimeError("injected failure on rank %d (G2048_BENCH_FAIL_RANK)" % rank)
     _lib.lib()
-    assert ops.selftest(dev) == 0, "device self-test failed"
+    if args.full:
+        assert ops.selftest(dev) == 0, "device self-test failed"
 
     n = BOARDS_PER_GPU
     id_base = rank * n
@@ -287,13 +319,14 @@ def main():
     graph = ev0 = ev1 = None
     if not args.no_graph and len(sc) == 1:
         graph, ev0, ev1 = graph_of(k_steps, dev)
-    # untimed: the first replay pays the graph's one-time upload, and ~20 ms of load bring the clocks to steady state
+    # untimed: the first replay pays the graph's one-time upload, and ~20 ms of load bring the clocks to steady state (without a
+    # graph in passes of at most 20 steps, so that a large K does not add another K untimed steps to the run)
     t_warm = time.perf_counter()
     while time.perf_counter() - t_warm < 0.02:
         if graph is not None:
             graph.replay()
         else:
-            k_steps()
+            steps_in_chains(W, min(K, 20))
         torch.cuda.synchronize()
 
     # ---- timed region: exactly K steps -------------------------------------------------
@@ -320,6 +353,8 @@ def main():
     outer_ms = o0.elapsed_time(o1)
     per_rank_s = gdist.gather_floats(elapsed, dev)  # every rank's own K-step time, in rank order
     elapsed = gdist.max_over_ranks(elapsed, dev)    # ... and the job's time is the slowest rank's
+    if args.dump_outputs and rank == 0:             # before anything below launches into `scores` again
+        dump_outputs(args.dump_outputs, out, scores, reward, flags, id_base)
 
     # ---- final metrics reduction: all-gather of per-board scores (config 5), timed separately
     gather_ms = None
@@ -333,8 +368,8 @@ def main():
         assert gathered.numel() == world * n and bool((gathered[rank * n:(rank + 1) * n] == scores).all())
         m = gdist.reduce_metrics(ops.metrics(out, scores, flags))
         assert int(m[0].item()) == world * n
-        if rank == 0:
-            # the gathered vector must equal what ONE GPU computes for the same global ids: rank 0 re-runs the K timed
+        if rank == 0 and args.full:
+            # (--full) the gathered vector must equal what ONE GPU computes for the same global ids: rank 0 re-runs the K timed
             # steps of every other shard (same seed, step indices and id_base = shard start) and compares
             # (into buffers of its own: this rank's out / reward / flags still have to pass the chains check below)
             vb, va = torch.empty_like(boards), torch.empty_like(actions)
@@ -349,9 +384,9 @@ def main():
                 assert bool((gathered[r * n:(r + 1) * n] == vs).all()), "shard %d differs from the 1-GPU result" % r
             del vb, va, vo, vs, vr, vf
 
-    # ---- the chain form must BE the single launch: the same K steps, one launch each, into buffers of their own
+    # ---- (--full) the chain form must BE the single launch: the same K steps, one launch each, into buffers of their own
     chains_equal = None
-    if len(sc) > 1:
+    if len(sc) > 1 and args.full:
         vo, vs, vr, vf = torch.empty_like(out), torch.zeros_like(scores), torch.empty_like(reward), torch.empty_like(flags)
         for t in range(K):
             ops.step(boards, actions, vs, SEED, W + t, id_base, out=vo, reward=vr, flags=vf)
@@ -360,13 +395,13 @@ def main():
         assert chains_equal, "the %d-chain step differs from the single launch" % len(sc)
         del vo, vs, vr, vf
 
-    # ---- the single-launch form beside it (rounds 1-4's headline): one hipGraph of K launches of all 1,048,576 boards, the same
+    # ---- (--full) the single-launch form beside it (rounds 1-4's headline): one hipGraph of K launches of all 1,048,576 boards, the same
     # event-pair definition (a replay from an idle stream), mean of three
     def k_single():
         for t in range(K):
             one_step(W + t)
     single_s = None
-    if len(sc) > 1:
+    if len(sc) > 1 and args.full:
         gs, _, _ = (None, None, None) if args.no_graph else graph_of(k_single, dev)
         reads = []
         for _ in range(4):
@@ -392,22 +427,6 @@ def main():
     timing = ("HIP event pair on the launch stream around the timed region's own K steps (one chain: one hipGraph replay unless "
               "--no-graph; several chains: plain launches on the chains' streams, the pair spans fork and join), / K -- the definition "
               "roofline.frac keeps across rounds")
-    # plain launches: the same g2048_step call of the timed region (same buffers, same arguments), K times behind K untimed
-    # ones through a prepared call (ops.PreparedStep, ~4 us of host time per launch, so the GPU queue never runs dry)
-    prepared = ops.PreparedStep(boards, actions, scores, SEED, id_base, out=out, reward=reward, flags=flags)
-    sp = torch.cuda.current_stream(dev).cuda_stream
-    plain = []
-    for _ in range(3):
-        q0, q1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        for t in range(K):
-            prepared(W + t, sp)
-        q0.record()
-        for t in range(K):
-            prepared(W + t, sp)
-        q1.record()
-        torch.cuda.synchronize()
-        plain.append(q0.elapsed_time(q1) * 1e-3 / K)
-    plain_s, plain_mean_s = min(plain), sum(plain) / len(plain)
     # ---- roofline: algorithmic bytes per launch / average launch duration over the timed region ----
     achieved = n * STEP_BYTES_F32 / kernel_s / 1e9
     traffic = traffic_src = None
@@ -456,15 +475,33 @@ def main():
                      "frac_wall": n * STEP_BYTES_F32 / (elapsed / K) / 1e9 / HBM_PEAK_GBS,
                      "algorithmic_bytes_per_launch": n * STEP_BYTES_F32, "algorithmic_bytes_per_step": n * STEP_BYTES_F32, "timing": timing,
                      "chains_equal_single_launch": chains_equal,
-                     "single_launch": {"kernel_us": (single_s if single_s is not None else kernel_s) * 1e6,
-                                       "frac": n * STEP_BYTES_F32 / (single_s if single_s is not None else kernel_s) / 1e9 / HBM_PEAK_GBS,
-                                       "frac_plain_launches": n * STEP_BYTES_F32 / plain_s / 1e9 / HBM_PEAK_GBS,
-                                       "kernel_us_plain_launches": plain_s * 1e6, "kernel_us_plain_launches_mean_of_3": plain_mean_s * 1e6,
-                                       "timing": "one hipGraph of K launches of all 1,048,576 boards, event pair around a replay from an idle "
-                                                 "stream / K, mean of three (rounds 3-4's roofline.frac: 0.447-0.456); plain launches: K "
-                                                 "launches queued behind K untimed ones, best / mean of three"},
                      "note": "LLC-resident working set at this size; what binds is VALU issue (valu_issue below), not memory"},
     }
+    if args.full:
+        # plain launches: the same g2048_step call of the timed region (same buffers, same arguments), K times behind K untimed
+        # ones through a prepared call (ops.PreparedStep, ~4 us of host time per launch, so the GPU queue never runs dry)
+        prepared = ops.PreparedStep(boards, actions, scores, SEED, id_base, out=out, reward=reward, flags=flags)
+        sp = torch.cuda.current_stream(dev).cuda_stream
+        plain = []
+        for _ in range(3):
+            q0, q1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            for t in range(K):
+                prepared(W + t, sp)
+            q0.record()
+            for t in range(K):
+                prepared(W + t, sp)
+            q1.record()
+            torch.cuda.synchronize()
+            plain.append(q0.elapsed_time(q1) * 1e-3 / K)
+        plain_s, plain_mean_s = min(plain), sum(plain) / len(plain)
+        result["roofline"]["single_launch"] = {
+            "kernel_us": (single_s if single_s is not None else kernel_s) * 1e6,
+            "frac": n * STEP_BYTES_F32 / (single_s if single_s is not None else kernel_s) / 1e9 / HBM_PEAK_GBS,
+            "frac_plain_launches": n * STEP_BYTES_F32 / plain_s / 1e9 / HBM_PEAK_GBS,
+            "kernel_us_plain_launches": plain_s * 1e6, "kernel_us_plain_launches_mean_of_3": plain_mean_s * 1e6,
+            "timing": "one hipGraph of K launches of all 1,048,576 boards, event pair around a replay from an idle "
+                      "stream / K, mean of three (rounds 3-4's roofline.frac: 0.447-0.456); plain launches: K "
+                      "launches queued behind K untimed ones, best / mean of three"}
     # what really binds the step kernel: VALU issue. Instructions per step from the recorded SQ_INSTS_VALU pass, the issue-cycle
     # model of tools/isa_cost.py, and the counter's own busy time: SQ_ACTIVE_INST_VALU (quad-cycles) x 4 / (SIMDs x clock)
     if pmc_extra.get("valu_wave_instructions_per_launch"):
@@ -502,7 +539,7 @@ def main():
         result["backend_control"] = planes["control"]
         if planes.get("data_note"):
             result["backend_note"] = "RCCL data plane unavailable, staged through the host over gloo: " + planes["data_note"]
-        result["gathered_equals_single_gpu"] = True        # asserted above on rank 0
+        result["gathered_equals_single_gpu"] = True if args.full else None     # asserted above on rank 0 (--full only)
         # what the scaling curve is read against: every rank's own K-step time, their spread, and the recorded N = 1 figure
         result["per_rank_ms_per_step"] = [t / K * 1e3 for t in per_rank_s]
         result["slowest_over_fastest_rank"] = max(per_rank_s) / min(per_rank_s)
@@ -513,7 +550,7 @@ def main():
             if ref1.get("value"):
                 result["single_gpu_reference"]["this_run_per_gpu_over_it"] = result["per_gpu_value"] / ref1["value"]
 
-    # ---- the other legs. With one rank a failure in any of them fails the run, as it should. With several ranks the headline
+    # ---- the other legs (--full only). With one rank a failure in any of them fails the run, as it should. With several ranks the headline
     # figures above are what the scaling curve needs: a leg that raises (or a collective in it that times out: g2048/dist.py
     # bounds every wait) is recorded in the line as optional_legs_error and the line is still printed.
     def _optional_legs():
@@ -961,9 +998,9 @@ def main():
                 assert np.array_equal(a.cpu().numpy(), oa) and np.array_equal(e.cpu().numpy().astype(np.uint32), oe), \
                     "GPU beam != oracle"
 
-    if world == 1:
+    if args.full and world == 1:
         _optional_legs()
-    else:
+    elif args.full:
         try:
             _optional_legs()
         except Exception as exc:            # noqa: BLE001

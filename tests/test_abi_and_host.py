@@ -197,19 +197,30 @@ def test_product_never_imports_oracle():
                 assert "hostsim_" not in src and "__HIP_DEVICE_COMPILE__" not in src, f        # no host emulation inside
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/agents"), reason="needs the reference checkout (build container only)")
-def test_drop_in_import_layout_with_reference_behind():
+def test_drop_in_import_layout_with_reference_behind(tmp_path):
     """PYTHONPATH=<package dir>:<reference>: the two replaced modules come from here, the rest of the reference's
-    packages (agents.ppo_agent, which train.py imports) still resolve -- checked in a clean interpreter."""
+    packages (agents.ppo_agent, which train.py imports) still resolve -- checked in a clean interpreter, against a stand-in
+    checkout with the reference's package layout whose two replaced modules refuse to be imported."""
     import subprocess
     import sys
+    ref = tmp_path / "reference"
+    shadowed = "raise ImportError('the reference copy was imported instead of the drop-in')\n"
+    for rel, text in {"agents/__init__.py": "from agents.ppo_agent import PPOAgent\n",
+                      "agents/ppo_agent.py": "class PPOAgent:\n    pass\n",
+                      "agents/beam_search_agent.py": shadowed,
+                      "environment/__init__.py": "from environment.game_2048 import Game2048Env\n",
+                      "environment/game_2048.py": shadowed,
+                      "utils/__init__.py": "",
+                      "utils/visualization.py": ""}.items():
+        (ref / rel).parent.mkdir(parents=True, exist_ok=True)
+        (ref / rel).write_text(text)
     code = ("import agents.beam_search_agent as b, environment.game_2048 as e, agents.ppo_agent as p, utils.visualization;"
             "print(b.__file__); print(e.__file__); print(p.__file__)")
-    env = dict(os.environ, PYTHONPATH=PKG + os.pathsep + "/root/reference")
+    env = dict(os.environ, PYTHONPATH=PKG + os.pathsep + str(ref))
     out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=env, timeout=300)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = out.stdout.strip().splitlines()[-3:]
-    assert lines[0].startswith(PKG) and lines[1].startswith(PKG) and lines[2].startswith("/root/reference")
+    assert lines[0].startswith(PKG) and lines[1].startswith(PKG) and lines[2].startswith(str(ref))
 
 
 def test_round4_entry_points_validate_without_device(built):

@@ -55,3 +55,33 @@ def test_parent_relays_child_and_never_imports_torch(tmp_path):
     lines = out.strip().splitlines()
     assert lines[0] == "child ran"
     assert json.loads(lines[-1]) == {"rc": 7, "torch": False}
+
+
+def test_steps_must_be_positive():
+    out = subprocess.run([sys.executable, BENCH, "--steps", "0", "--dry-launch"], env=_clean_env(), capture_output=True, text=True)
+    assert out.returncode == 2 and "--steps" in out.stderr
+
+
+def test_dump_outputs_is_a_fixed_exact_sample(tmp_path):
+    """--dump-outputs: the same boards of the shard on every run (ids ascending), every array f32 or f64 with the values exact,
+    at most 64 MB in all."""
+    import numpy as np
+    import torch
+    import bench
+    n, id_base = 1 << 20, 3 << 20
+    g = torch.Generator().manual_seed(1)
+    out = torch.randint(0, 18, (n, 16), dtype=torch.uint8, generator=g)
+    scores = torch.randint(-2 ** 31, 2 ** 31 - 1, (n,), dtype=torch.int32, generator=g)
+    reward = torch.rand(n, generator=g) * 4096
+    flags = torch.randint(0, 256, (n,), dtype=torch.uint8, generator=g)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), out, scores, reward, flags, id_base)
+    a = {f[:-4]: np.load(str(tmp_path / "a" / f)) for f in os.listdir(str(tmp_path / "a"))}
+    b = {f[:-4]: np.load(str(tmp_path / "b" / f)) for f in os.listdir(str(tmp_path / "b"))}
+    assert set(a) == set(b) == {"board_ids", "boards", "scores", "reward", "flags"}
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    assert all(x.dtype in (np.float32, np.float64) for x in a.values()) and sum(x.nbytes for x in a.values()) <= 64 << 20
+    ids = a["board_ids"].astype(np.int64) - id_base
+    assert len(ids) == bench.DUMP_SAMPLE and np.all(np.diff(ids) > 0) and 0 <= ids[0] and ids[-1] < n
+    assert np.array_equal(a["boards"], out.numpy()[ids]) and np.array_equal(a["reward"], reward.numpy()[ids])
+    assert np.array_equal(a["scores"], scores.numpy().view(np.uint32)[ids]) and np.array_equal(a["flags"], flags.numpy()[ids])

@@ -1,6 +1,7 @@
-"""The driver's bench line: `python bench.py --gpus 1 --steps K --warmup W` prints ONE JSON line whose `roofline` and
+"""The driver's bench line: `python bench.py --gpus 1 --steps K --warmup W --full` prints ONE JSON line whose `roofline` and
 `cpu_baseline` objects carry BOTH halves of BASELINE.json's metric (batched env.step board-steps/s + beam node-expansions/s at
-width 20 / depth 30) as scalars -- the driver's record keeps those two objects -- and whose last key repeats the headline."""
+width 20 / depth 30) as scalars -- the driver's record keeps those two objects -- and whose last key repeats the headline.
+Without --full the line holds the headline alone, and --dump-outputs writes what the timed steps computed."""
 import json
 import os
 import subprocess
@@ -15,7 +16,7 @@ pytestmark = pytest.mark.gpu
 
 def test_bench_line_carries_both_halves_of_the_metric():
     out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5",
-                          "--no-extra", "--cpu-seconds", "2"], capture_output=True, text=True, timeout=900)
+                          "--no-extra", "--cpu-seconds", "2", "--full"], capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, "exactly one JSON line on stdout"
@@ -52,3 +53,37 @@ def test_bench_line_carries_both_halves_of_the_metric():
     assert cb["beam_one_thread_value"] > 1e5 and cb["config1_drop_in_steps_per_s"] > 100 and cb["config1_reference_style_python_steps_per_s"] > 100
     assert list(r)[-1] == "headline" and r["headline"]["beam_expansions_per_s"] == r["beam"]["value"]
     assert r["headline"]["board_steps_per_s"] == r["value"] and r["headline"]["evaluation_seconds"] == r["evaluation"]["seconds"]
+
+
+def test_plain_line_is_the_headline_and_dumps_the_last_step(tmp_path, oracle):
+    """A plain run: the headline without the legs that take runs of their own; --steps sets the timed steps; --dump-outputs holds
+    what the last timed step computed for the sampled boards: the oracle's next boards, rewards and flags of step W + K - 1, and
+    the scores summed over the K timed steps."""
+    import numpy as np
+    K, W, n = 3, 2, 1048576
+    d = tmp_path / "dump"
+    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", str(K), "--warmup", str(W),
+                          "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, "exactly one JSON line on stdout"
+    r = json.loads(lines[0])
+    assert r["metric"] == "board-steps/sec (batched env.step)" and r["unit"] == "board-steps/s" and r["higher_is_better"] is True
+    assert r["steps"] == K and r["warmup"] == W and r["dtype"].startswith("u8 ")
+    assert abs(r["value"] - n / (r["ms_per_step"] * 1e-3)) / r["value"] < 1e-6
+    for k in ("beam", "evaluation", "rollout", "rollout_random", "roofline_f64_reward", "roofline_hbm_resident", "cpu_baseline",
+              "cpu_baseline_python"):
+        assert k not in r, k
+    assert "single_launch" not in r["roofline"] and r["roofline"]["chains_equal_single_launch"] is None
+    got = {f[:-4]: np.load(str(d / f)) for f in os.listdir(str(d))}
+    assert set(got) == {"board_ids", "boards", "scores", "reward", "flags"}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values()) and sum(a.nbytes for a in got.values()) <= 64 << 20
+    ids = got["board_ids"].astype(np.int64)
+    assert len(ids) == 1 << 18 and np.all(np.diff(ids) > 0) and ids[-1] < n
+    hb, ha = oracle.synth_boards(n, seed=0x2048), oracle.synth_actions(n, seed=0x2048, step_index=0)
+    hs = np.zeros(n, np.uint32)
+    for t in range(W, W + K):
+        bo, hs, ro, fo = oracle.step_batch(hb, ha, hs, seed=0x2048, step_index=t)
+    assert np.array_equal(got["boards"], bo[ids].astype(np.float32)) and np.array_equal(got["scores"], hs[ids].astype(np.float64))
+    assert np.array_equal(got["reward"], ro[ids].astype(np.float32), equal_nan=True)
+    assert np.array_equal(got["flags"], fo[ids].astype(np.float32))

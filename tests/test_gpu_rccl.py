@@ -163,8 +163,8 @@ def test_bench_two_ranks_on_one_card_fall_back_from_rccl_and_still_report():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "G2048_DIST_BACKEND"):
         env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "1", "--no-beam",
-                          "--no-rollout", "--no-extra", "--no-cpu-baseline", "--no-evaluation"], env=env, capture_output=True, text=True,
-                         timeout=400)
+                          "--no-rollout", "--no-extra", "--no-cpu-baseline", "--no-evaluation", "--full"], env=env, capture_output=True,
+                         text=True, timeout=400)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 2 and line["n_ranks_seen"] == 2 and line["gathered_equals_single_gpu"] is True

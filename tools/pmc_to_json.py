@@ -68,7 +68,7 @@ def main():
 
     # ---- the kept text files
     with open(os.path.join(PROF, "%s_pmc_step_beam_play_rollout.txt" % TAG), "w") as o:
-        o.write("# Round %s PMC passes (tools/profile_round.sh %s): separate rocprofv3 --pmc passes over `python3 bench.py --steps 20 --warmup 5 --chains 1`\n"
+        o.write("# Round %s PMC passes (tools/profile_round.sh %s): separate rocprofv3 --pmc passes over `python3 bench.py --steps 20 --warmup 5 --full --chains 1`\n"
                 "# (FETCH_SIZE; WRITE_SIZE; SQ_*: counters are per dispatch, so the one-launch-per-step form) and over `python3 tools/rollout_rate.py 65536`\n"
                 "# (config 4's rollout_step_kernel). FETCH_SIZE / WRITE_SIZE in KB; gfx950: FETCH_SIZE x2 for wide coalesced reads (MI355X_MICROARCH.md).\n"
                 "# SQ_WAVE_CYCLES / SQ_WAIT_* / SQ_ACTIVE_* in quad-cycles summed over waves. Reduced to profiles/pmc_*.json by tools/pmc_to_json.py.\n" % (str(int(TAG[1:])), TAG))
@@ -79,7 +79,7 @@ def main():
             keep = [ln for ln in body.splitlines() if "at::native" not in ln and "__amd_rocclr" not in ln and "Cijk_" not in ln and "attn_fwd" not in ln]
             o.write("\n## %s\n%s\n" % (title, "\n".join(keep).replace("(anonymous namespace)::", "")))
     with open(os.path.join(PROF, "%s_bench_kernel_trace_stats.txt" % TAG), "w") as o:
-        o.write("# rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 20 --warmup 5   (round %s closing build; tools/profile_round.sh %s, pass kt)\n"
+        o.write("# rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 20 --warmup 5 --full   (round %s closing build; tools/profile_round.sh %s, pass kt)\n"
                 "# The headline step of this run is the two-chain form: the tracer's per-launch host cost slows the host-paced launches (its own bench line:\n"
                 "# profiles/%s_bench_under_tracer.json), so what the trace is good for is the per-kernel durations and the single-launch figure\n"
                 "# (step_kernel<false,false,1,256> at grid 1048576), which the untraced run's roofline.single_launch reproduces.\n\n" % (str(int(TAG[1:])), TAG, TAG))

@@ -13,7 +13,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out
 TAG=${1:-r05}
 cd /tmp && export TMPDIR=/tmp
-B="python3 $ROOT/bench.py --steps 20 --warmup 5"
+B="python3 $ROOT/bench.py --steps 20 --warmup 5 --full"
 R="python3 $ROOT/tools/rollout_rate.py 65536"
 SQ="SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU SQ_WAIT_ANY SQ_WAIT_INST_ANY"
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_${TAG}_kt -- $B > $OUT/prof_${TAG}_kt.json 2> $OUT/prof_${TAG}_kt.err || exit 1
