@@ -59,6 +59,31 @@ def test_export_table_equals_the_two_headers(built):
     assert built.lib().g2048_device_count() >= 0
 
 
+def _template_args(text, kernel):
+    """Argument tuples of every `kernel<...>` host handle in `nm -C` output (the device stubs are named __device_stub__...)."""
+    found = set()
+    for args in re.findall(r"::%s<([^<>]*)>" % kernel, text):
+        found.add(tuple(int(a) if a.strip().isdigit() else {"true": True, "false": False}[a.strip()] for a in args.split(",")))
+    return found
+
+
+def test_step_kernel_instantiations_are_the_ones_the_gpu_matrix_covers(built):
+    """Every step_kernel / step_many_kernel instantiation the library holds is declared, with how a call reaches it, in
+    tests/test_gpu_step_matrix.py, which compares each with the oracle; adding or removing a variant without covering it fails
+    here, with no GPU needed."""
+    import subprocess
+    from test_gpu_step_matrix import STEP_KERNELS, STEP_MANY_KERNELS
+    text = subprocess.check_output(["nm", "-C", built.library_path()], text=True)
+    step = _template_args(text, "step_kernel")
+    many = _template_args(text, "step_many_kernel")
+    assert {a[3] for a in step} == {256} and {a[2] for a in many} == {256}            # BLOCK
+    declared_step = [v for v, _, _ in STEP_KERNELS]
+    declared_many = [v for v, _ in STEP_MANY_KERNELS]
+    assert len(set(declared_step)) == len(declared_step) and len(set(declared_many)) == len(declared_many)
+    for built_, declared in (({a[:3] + a[4:] for a in step}, set(declared_step)), ({a[:2] + a[3:] for a in many}, set(declared_many))):
+        assert built_ == declared, "built, not declared: %s; declared, not built: %s" % (sorted(built_ - declared), sorted(declared - built_))
+
+
 def test_launch_plan_arithmetic(built):
     """The chip-size arithmetic (helper-wavefront cap, SIMD row length of the balanced beam order, smallest balanced batch)
     as the library derives it from a compute-unit count: MI355X (256 CUs), a quarter partition (64), one XCD (32)."""
