@@ -29,6 +29,7 @@ ROLLOUT_OBS_SHIFT, OBS_F32, OBS_F16, OBS_BF16 = 4, 0, 1, 2
 SEEN_SLOT_BYTES = 32
 ENV_RECORD_BYTES, ENV_OP_STEP, ENV_OP_RESET, ENV_OP_PEEK, ENV_OP_MOVE, ENV_OP_SPAWN, ENV_OP_MOVE_AGENT = 80, 0, 1, 2, 3, 4, 5
 ENV_TOKEN_SHIFT = 8
+POLICY_F32, POLICY_BF16 = 0, 1
 
 _vp, _u64, _sz, _u32, _int = C.c_void_p, C.c_uint64, C.c_size_t, C.c_uint32, C.c_int
 SIGNATURES = {
@@ -82,6 +83,9 @@ SIGNATURES = {
     "g2048_seen_insert": (_int, [_vp, _u64, _vp, _u32, _vp, _vp, _vp, _sz, _vp]),
     "g2048_seen_rehash": (_int, [_vp, _u32, _vp, _u32, _vp, _vp]),
     "g2048_shaping_apply": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _sz, _vp]),
+    "g2048_policy_packed_bytes": (_sz, [_int, _int]),
+    "g2048_policy_pack": (_int, [_vp, _int, _int, _vp, _vp]),
+    "g2048_policy_forward": (_int, [_vp, _vp, _vp, _vp, _vp, _sz, _u32, _vp]),
 }
 
 

@@ -410,6 +410,57 @@ def rollout_step(boards, probs, scores, seed, step_index, id_base=0, *, mask=Non
     return out, actions, prob, reward, flags
 
 
+POLICY_PRECISIONS = {"f32": L.POLICY_F32, "bf16": L.POLICY_BF16}
+
+
+def policy_packed_bytes(precision="f32", n_out=4):
+    """Bytes of one packed network (g2048_policy_packed_bytes)."""
+    nb = L.lib().g2048_policy_packed_bytes(POLICY_PRECISIONS[precision], int(n_out))
+    if nb == 0:
+        raise ValueError("g2048: n_out must be 4 (actor) or 1 (critic)")
+    return nb
+
+
+def policy_pack(plain, n_out, precision="f32", out=None):
+    """Pack one network's plain float32 parameters (W1 b1 W2 b2 W3 b3 W4 b4 back to back, weights [out][in], BatchNorm folded
+    in: include/g2048.h) into the blob g2048_policy_forward streams. Writes `out` (uint8, policy_packed_bytes) in place when
+    given, on the current stream, without synchronising."""
+    L.require_device_tensor(plain, torch.float32, None, "plain")
+    if plain.dim() != 1 or plain.numel() != 45504 + 65 * int(n_out):
+        raise ValueError("g2048: plain must be a flat float32 tensor of 45,504 + 65 * n_out parameters")
+    nb = policy_packed_bytes(precision, n_out)
+    if out is None:
+        out = torch.empty(nb, dtype=torch.uint8, device=plain.device)
+    L.require_device_tensor(out, torch.uint8, None, "out")
+    if out.numel() != nb:
+        raise ValueError("g2048: out must hold %d bytes" % nb)
+    L.call(plain.device, L.lib().g2048_policy_pack, plain.data_ptr(), int(n_out), POLICY_PRECISIONS[precision], out.data_ptr(),
+           L.stream_ptr(plain.device))
+    return out
+
+
+def policy_forward(boards, actor_packed, critic_packed=None, precision="f32", probs=None, value=None):
+    """PPO actor (and critic) forward pass on the packed boards in ONE launch (g2048_policy_forward). Returns probs float32
+    (n,4), or (probs, value float32 (n,1)) when critic_packed is given."""
+    L.require_device_tensor(boards, torch.uint8, (16,), "boards")
+    n, dev = boards.shape[0], boards.device
+    if probs is None:
+        probs = torch.empty((n, 4), dtype=torch.float32, device=dev)
+    L.require_device_tensor(probs, torch.float32, (4,), "probs")
+    if probs.shape[0] != n:
+        raise ValueError("g2048: probs must have n rows")
+    if critic_packed is not None and value is None:
+        value = torch.empty((n, 1), dtype=torch.float32, device=dev)
+    if value is not None:
+        L.require_device_tensor(value, torch.float32, (1,), "value")
+        if value.shape[0] != n:
+            raise ValueError("g2048: value must have n rows")
+    L.call(dev, L.lib().g2048_policy_forward, boards.data_ptr(), actor_packed.data_ptr(),
+           critic_packed.data_ptr() if critic_packed is not None else None, probs.data_ptr(),
+           value.data_ptr() if value is not None else None, n, POLICY_PRECISIONS[precision], L.stream_ptr(dev))
+    return probs if critic_packed is None else (probs, value)
+
+
 class SeenStates:
     """The `seen_states` set and `highest_tile_seen` of PPOAgent (agents/ppo_agent.py:171-176) for ordered batches of
     transitions, resident on the GPU: an open-addressing hash set keyed by the 16-byte board (include/g2048.h,

@@ -1,14 +1,16 @@
 #!/usr/bin/env python3
 """Collect a PPO rollout (BASELINE config 4: 65,536 envs x 128 steps) entirely on the GPU.
 
-    python examples/ppo_rollout.py [--envs 65536] [--steps 128]
+    python examples/ppo_rollout.py [--envs 65536] [--steps 128] [--policy torch|device-f32|device-bf16]
 
 The policy is any torch module mapping float32 (N,16) observations to action probabilities (N,4) -- or
 (probs, value); here a small MLP. Everything between the policy's outputs and its next inputs (masked sampling,
 env step with auto-reset, reward, observation encoding) runs in HIP kernels; nothing crosses PCIe.
 Then one reference-style update: `RolloutCollector.sample(batch)` is PPOMemory.sample + the tensor preparation of
 PPOAgent.update (agents/ppo_agent.py:21-50, :342-354) as ONE gather launch on the device, and the loss below is the
-reference's (:356-400) on stock torch modules -- the learner stays the unchanged consumer."""
+reference's (:356-400) on stock torch modules -- the learner stays the unchanged consumer.
+--policy device-f32 / device-bf16 runs the same modules' forward pass as one HIP launch on the boards (g2048.DevicePolicy)
+during collection; after the update, refresh() re-packs the weights in place and the captured rollout replays with them."""
 import argparse
 import os
 import sys
@@ -25,6 +27,7 @@ ap.add_argument("--envs", type=int, default=65536)
 ap.add_argument("--steps", type=int, default=128)
 ap.add_argument("--batch", type=int, default=4096)
 ap.add_argument("--epochs", type=int, default=4)
+ap.add_argument("--policy", choices=("torch", "device-f32", "device-bf16"), default="torch")
 a = ap.parse_args()
 
 
@@ -40,7 +43,11 @@ class ActorCritic(nn.Module):
 
 
 net = ActorCritic().cuda().eval()
-rc = g2048.RolloutCollector(a.envs, a.steps, net, seed=1, shaping=True)
+policy = net
+if a.policy != "torch":     # the same modules, 16-256-128-64-{4|1}: actor = body + pi, critic = body + v
+    policy = g2048.DevicePolicy(nn.Sequential(net.body, net.pi).eval(), nn.Sequential(net.body, net.v).eval(),
+                                precision=a.policy[len("device-"):])
+rc = g2048.RolloutCollector(a.envs, a.steps, policy, seed=1, shaping=True)
 rc.collect()
 torch.cuda.synchronize(); t0 = time.perf_counter()
 traj = rc.collect()
@@ -68,5 +75,8 @@ for epoch in range(a.epochs):
     loss = actor_loss + value_coef * value_loss - entropy_coef * dist.entropy().mean()
     opt.zero_grad(); loss.backward(); opt.step()
 net.eval()
+if policy is not net:
+    policy.refresh()        # in place, no synchronisation: the next collect() replays its graph with the updated weights
+    rc.collect()
 rc.check()
 print("update on %d sampled transitions (of %d): loss %.4f after %d epochs" % (mb["actions"].shape[0], a.envs * a.steps, loss.item(), a.epochs))

@@ -46,7 +46,8 @@ extern "C" {
 #endif
 
 #define G2048_ABI_VERSION 5        /* 5: round 5, second half (ops MOVE / SPAWN / MOVE_AGENT of g2048_env_step; g2048_eval kinds CORNER_BONUS and
-                                      MERGE_POTENTIAL; no entry point added or removed)
+                                      MERGE_POTENTIAL; no entry point added or removed;
+                                      later, additive: g2048_policy_packed_bytes / _pack / _forward)
                                       4: round 5 (export table = this header + g2048_testing.h exactly: test / measurement hooks moved there,
                                       internal symbols hidden; g2048_replay_games also clamps a game's length to actions_stride)
                                       3: round 4 (actions_out of the g2048_play_games family, g2048_replay_games, g2048_env_step,
@@ -410,6 +411,38 @@ G2048_API int g2048_shaping_apply(const void *next_boards, const uint8_t *state_
                         const uint8_t *prev_highest, const void *table, const uint32_t *slots, uint64_t index_base,
                         double *shaped_out, uint8_t *novel_out_or_null, size_t n, void *stream);
 
+
+/* PPO actor / critic forward pass of the reference (agents/ppo_agent.py:61-136, ActorNetwork / CriticNetwork in eval mode) on
+ * the matrix cores: 16 -> 256 -> 128 -> 64 -> 4 (softmax) for the actor, -> 1 for the critic, with input
+ * x = float32(code) / float32(15) read from the packed boards (PPOAgent.normalize_state, as g2048_obs_f32).
+ *
+ *   g2048_policy_packed_bytes  bytes of one packed network (0 for a bad precision or n_out); a multiple of 16.
+ *   g2048_policy_pack          rearranges one network's plain f32 parameters into that blob, on `stream` (no synchronisation;
+ *                              packing into the same buffer again updates a forward pass captured in a graph). plain_f32 is
+ *                              W1 [256][16], b1 [256], W2 [128][256], b2 [128], W3 [64][128], b3 [64], W4 [n_out][64], b4 [n_out]
+ *                              back to back (45,504 + 65 n_out floats, device memory), each weight row-major [out][in] as torch
+ *                              stores it. n_out: 4 (actor) or 1 (critic). There is no BatchNorm in the kernel: the caller folds
+ *                              every eval-mode BatchNorm1d into a Linear first, with s = gamma / sqrt(running_var + eps) and
+ *                              t = beta - running_mean * s:
+ *                                BN after a Linear (Linear -> BN -> ReLU):  W' = diag(s) W,  b' = s * b + t;
+ *                                BN after a ReLU, i.e. before the next Linear (the reference's relu -> bn -> dropout -> fc):
+ *                                                                           W' = W diag(s),  b' = b + W t.
+ *                              The reference skips both BatchNorms for a batch of one row (ppo_agent.py:83, :89): such a
+ *                              batch takes the parameters without the fold.
+ *   g2048_policy_forward       probs_out[i] = softmax(actor(board i)) (float32 n x 4, the input g2048_rollout_step and
+ *                              g2048_sample_actions take) and, if critic_packed_or_null is given, value_out_or_null[i] =
+ *                              critic(board i), in ONE launch. opts = the precision both blobs were packed with:
+ *                                G2048_POLICY_F32   f32 MFMA, exact f32 products and sums (the parity path);
+ *                                G2048_POLICY_BF16  weights and the input / hidden activations rounded to bf16 (nearest even),
+ *                                                   f32 accumulation, bias and softmax.
+ *                              Boards, blobs and probs_out 16-byte aligned, value_out 4-byte aligned. Deterministic: every
+ *                              output is one fixed-order accumulation (no split-K, no atomics). Nothing past row n is written. */
+#define G2048_POLICY_F32   0
+#define G2048_POLICY_BF16  1
+G2048_API size_t g2048_policy_packed_bytes(int precision, int n_out);
+G2048_API int g2048_policy_pack(const float *plain_f32, int n_out, int precision, void *packed_out, void *stream);
+G2048_API int g2048_policy_forward(const void *boards, const void *actor_packed, const void *critic_packed_or_null, float *probs_out,
+                         float *value_out_or_null, size_t n, uint32_t opts, void *stream);
 #ifdef __cplusplus
 }
 #endif
