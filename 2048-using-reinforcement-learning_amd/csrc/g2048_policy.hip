@@ -8,6 +8,8 @@
 //                          directly (x = code / 15, PPOAgent.normalize_state). Bias initialises the accumulator, ReLU is
 //                          applied on the way out of it, the 4-way softmax runs in f32 in registers. blockIdx.y picks the
 //                          network (0 actor, 1 critic), so one launch serves both.
+//   policy_play_kernel     complete games of the actor (play.py / train.py): the same forward, then sampling, the env step and
+//                          the bookkeeping per game slot, slots refilled from a ticket counter (g2048_play_policy_games).
 //
 // Layout of the computation. Every layer is computed transposed, Y^T = W . X^T: the MFMA's A operand is a 16-row tile of
 // weights, its B operand 16 boards' activations, and the result tile holds output features in its rows (register r of lane l:
@@ -23,11 +25,17 @@
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 
+#include <algorithm>
+
 #include "../../include/g2048.h"
+#include "g2048_board.h"
+#include "g2048_rng.h"
 
 extern "C" void g2048_set_last_error_(const char *msg);
 
 namespace {
+
+using namespace g2048;
 
 typedef float f4 __attribute__((ext_vector_type(4)));
 typedef unsigned u4 __attribute__((ext_vector_type(4)));
@@ -194,6 +202,88 @@ __device__ inline void dense(const unsigned char *sec, const float *bias, int la
     }
 }
 
+// The pieces of the forward pass that the forward kernel and the game-playing kernel (policy_play_kernel, below) share. Both
+// compute a board's outputs with exactly these instructions, and a board's outputs do not depend on the tile column or the
+// tile e it sits in, so the two kernels give bit-identical probabilities for the same board and blob.
+
+// layer-1 B operand of one tile: features 4h .. 4h+3 of the board whose row h is `cells` (PPOAgent.normalize_state)
+__device__ __forceinline__ void board_operand(uint32_t cells, f4 (&x)[2])
+{
+#pragma unroll
+    for (int r = 0; r < 4; ++r) x[0][r] = (float)((cells >> (8 * r)) & 0xffu) / 15.0f;
+    x[1] = f4{0.0f, 0.0f, 0.0f, 0.0f};           // bf16: features 16..31 of the only chunk do not exist
+}
+
+// nn.Softmax(dim=-1) of one board's four logits: exp(z - max) / sum, in f32
+__device__ __forceinline__ float4 softmax4(f4 z)
+{
+    const float m = fmaxf(fmaxf(z[0], z[1]), fmaxf(z[2], z[3]));
+    const float e0 = expf(z[0] - m), e1 = expf(z[1] - m), e2 = expf(z[2] - m), e3 = expf(z[3] - m);
+    const float sum = ((e0 + e1) + e2) + e3;
+    return make_float4(e0 / sum, e1 / sum, e2 / sum, e3 / sum);
+}
+
+// Layers 1..4 of the network at W (bias = W + kBias, P = Packed<BF16>) for the E tiles of B operands x of a wavefront; declares
+// out[E][1]: register r of out[e][0] on lane l (l < 16) = output r of board 16 e + l (rows 4.. of the padded layer-4 tile are
+// zero weights). A macro, not a function: as an inlined function the same code compiles the forward kernel to another
+// schedule that runs 4-6 % slower (measured against the parent build); expanded in place it is instruction for instruction
+// the kernel it was. Layers 1 + 2 are fused over 32-feature slices of h1 (f32: two 16-feature chunks; bf16: one 32-feature
+// chunk).
+#define POLICY_LAYERS_(BF16, E, W, bias, lane, h, x, out) \
+    f4 acc2[E][kH2 / 16]; \
+_Pragma("unroll") \
+    for (int o = 0; o < kH2 / 16; ++o) { \
+        const f4 b = *reinterpret_cast<const f4 *>(bias + (P::kB2 - P::kBias) / 4 + 16 * o + 4 * h); \
+_Pragma("unroll") \
+        for (int e = 0; e < E; ++e) acc2[e][o] = b; \
+    } \
+_Pragma("unroll 1") \
+    for (int s = 0; s < kH1 / 32; ++s) { \
+        f4 h1[E][2]; \
+_Pragma("unroll") \
+        for (int q = 0; q < 2; ++q) { \
+            const int o1 = 2 * s + q; \
+            const f4 b = *reinterpret_cast<const f4 *>(bias + 16 * o1 + 4 * h); \
+            f4 acc[E]; \
+_Pragma("unroll") \
+            for (int e = 0; e < E; ++e) acc[e] = b; \
+            chunk_mma<BF16, E>(W + P::kL1 + ((size_t)o1 * 64 + lane) * 16, x, acc); \
+_Pragma("unroll") \
+            for (int e = 0; e < E; ++e) h1[e][q] = relu(acc[e]); \
+        } \
+_Pragma("unroll") \
+        for (int q = 0; q < 32 / P::kChunk; ++q) { \
+            const int c = s * (32 / P::kChunk) + q; \
+_Pragma("unroll") \
+            for (int o = 0; o < kH2 / 16; ++o) { \
+                f4 in[E][2]; \
+                f4 acc[E]; \
+_Pragma("unroll") \
+                for (int e = 0; e < E; ++e) { \
+                    in[e][0] = h1[e][q]; \
+                    in[e][1] = h1[e][1]; \
+                    acc[e] = acc2[e][o]; \
+                } \
+                chunk_mma<BF16, E>(W + P::kL2 + ((size_t)(c * (kH2 / 16) + o) * 64 + lane) * 16, in, acc); \
+_Pragma("unroll") \
+                for (int e = 0; e < E; ++e) acc2[e][o] = acc[e]; \
+            } \
+        } \
+    } \
+    f4 h2[E][kH2 / 16]; \
+_Pragma("unroll") \
+    for (int e = 0; e < E; ++e) \
+_Pragma("unroll") \
+        for (int o = 0; o < kH2 / 16; ++o) h2[e][o] = relu(acc2[e][o]); \
+    f4 acc3[E][kH3 / 16]; \
+    dense<BF16, E, kH2, kH3>(W + P::kL3, bias + (P::kB3 - P::kBias) / 4, lane, h2, acc3); \
+_Pragma("unroll") \
+    for (int e = 0; e < E; ++e) \
+_Pragma("unroll") \
+        for (int o = 0; o < kH3 / 16; ++o) acc3[e][o] = relu(acc3[e][o]); \
+    f4 out[E][1]; \
+    dense<BF16, E, kH3, kOutPad>(W + P::kL4, bias + (P::kB4 - P::kBias) / 4, lane, acc3, out);
+
 template <bool BF16, int E>
 __global__ __launch_bounds__(64 * kWaves) void policy_forward_kernel(
     const uint32_t *__restrict__ boards, const unsigned char *__restrict__ actor, const unsigned char *__restrict__ critic,
@@ -212,67 +302,10 @@ __global__ __launch_bounds__(64 * kWaves) void policy_forward_kernel(
 #pragma unroll
     for (int e = 0; e < E; ++e) {
         const size_t env = env0 + 16 * e + col;
-        const uint32_t cells = env < n ? boards[env * 4 + h] : 0u;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) x[e][0][r] = (float)((cells >> (8 * r)) & 0xffu) / 15.0f;
-        x[e][1] = f4{0.0f, 0.0f, 0.0f, 0.0f};    // bf16: features 16..31 of the only chunk do not exist
+        board_operand(env < n ? boards[env * 4 + h] : 0u, x[e]);
     }
 
-    // layers 1 + 2, fused over 32-feature slices of h1
-    f4 acc2[E][kH2 / 16];
-#pragma unroll
-    for (int o = 0; o < kH2 / 16; ++o) {
-        const f4 b = *reinterpret_cast<const f4 *>(bias + (P::kB2 - P::kBias) / 4 + 16 * o + 4 * h);
-#pragma unroll
-        for (int e = 0; e < E; ++e) acc2[e][o] = b;
-    }
-#pragma unroll 1
-    for (int s = 0; s < kH1 / 32; ++s) {
-        f4 h1[E][2];
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            const int o1 = 2 * s + q;
-            const f4 b = *reinterpret_cast<const f4 *>(bias + 16 * o1 + 4 * h);
-            f4 acc[E];
-#pragma unroll
-            for (int e = 0; e < E; ++e) acc[e] = b;
-            chunk_mma<BF16, E>(W + P::kL1 + ((size_t)o1 * 64 + lane) * 16, x, acc);
-#pragma unroll
-            for (int e = 0; e < E; ++e) h1[e][q] = relu(acc[e]);
-        }
-#pragma unroll
-        for (int q = 0; q < 32 / P::kChunk; ++q) {               // f32: two 16-feature chunks; bf16: one 32-feature chunk
-            const int c = s * (32 / P::kChunk) + q;
-#pragma unroll
-            for (int o = 0; o < kH2 / 16; ++o) {
-                f4 in[E][2];
-                f4 acc[E];
-#pragma unroll
-                for (int e = 0; e < E; ++e) {
-                    in[e][0] = h1[e][q];
-                    in[e][1] = h1[e][1];
-                    acc[e] = acc2[e][o];
-                }
-                chunk_mma<BF16, E>(W + P::kL2 + ((size_t)(c * (kH2 / 16) + o) * 64 + lane) * 16, in, acc);
-#pragma unroll
-                for (int e = 0; e < E; ++e) acc2[e][o] = acc[e];
-            }
-        }
-    }
-    f4 h2[E][kH2 / 16];
-#pragma unroll
-    for (int e = 0; e < E; ++e)
-#pragma unroll
-        for (int o = 0; o < kH2 / 16; ++o) h2[e][o] = relu(acc2[e][o]);
-
-    f4 acc3[E][kH3 / 16];
-    dense<BF16, E, kH2, kH3>(W + P::kL3, bias + (P::kB3 - P::kBias) / 4, lane, h2, acc3);
-#pragma unroll
-    for (int e = 0; e < E; ++e)
-#pragma unroll
-        for (int o = 0; o < kH3 / 16; ++o) acc3[e][o] = relu(acc3[e][o]);
-    f4 out[E][1];
-    dense<BF16, E, kH3, kOutPad>(W + P::kL4, bias + (P::kB4 - P::kBias) / 4, lane, acc3, out);
+    POLICY_LAYERS_(BF16, E, W, bias, lane, h, x, out);
 
     // rows 0..3 of the output tile sit in lanes 0..15 (h == 0), one board per lane
     if (h != 0) return;
@@ -281,20 +314,159 @@ __global__ __launch_bounds__(64 * kWaves) void policy_forward_kernel(
         const size_t env = env0 + 16 * e + col;
         if (env >= n) continue;
         const f4 z = out[e][0];
-        if (is_critic) {
-            value[env] = z[0];
-        } else {                                  // nn.Softmax(dim=-1): exp(z - max) / sum, in f32
-            const float m = fmaxf(fmaxf(z[0], z[1]), fmaxf(z[2], z[3]));
-            const float e0 = expf(z[0] - m), e1 = expf(z[1] - m), e2 = expf(z[2] - m), e3 = expf(z[3] - m);
-            const float sum = ((e0 + e1) + e2) + e3;
-            probs[env] = make_float4(e0 / sum, e1 / sum, e2 / sum, e3 / sum);
-        }
+        if (is_critic) value[env] = z[0];
+        else probs[env] = softmax4(z);
     }
 }
 
 // boards per wavefront: f32 is MFMA-issue bound, two 16-board tiles hide the 40-cycle dependent latency and halve the weight
 // stream; bf16 MFMAs are 16x cheaper, so it takes four tiles per fragment load (DESIGN.md "Policy forward")
 constexpr int kTilesF32 = 2, kTilesBF16 = 4;
+
+// --------------------------------------------------------------------------------------------------- complete games --
+// The reference's policy games (play.py:44-68, train.py:54-90) played to the end on the device, as g2048_play_games plays
+// the beam agent's. One wavefront is one block and owns S = 16 E game slots, slot s on lane s. Per move, for all of its
+// live slots at once: the slot lanes write their boards to LDS, every lane reads the dword its layer-1 B operand needs,
+// the wavefront runs the shared forward, lanes 0..15 write the probabilities to LDS, and each slot lane reads its own row,
+// picks its action, steps its board and does the bookkeeping in registers. Slots sit at different move indices, so the
+// RNG keys are derived per lane (rng_keys: the seed half is loop-invariant and hoisted). A finished game writes its
+// results and its slot takes the next game index from a ticket counter in the workspace: one atomicAdd per wavefront for
+// all its idle slots, the indices spread by an mbcnt prefix. A wavefront leaves when its slots are idle and the queue is
+// empty. Nothing waits on another wavefront: no spin, no grid barrier, and the games do not depend on which wavefront or
+// slot plays them.
+__device__ const uint32_t kPlayDirTable[G2048_DIR_TABLE_WORDS] = G2048_DIR_TABLE_INIT;
+
+template <bool BF16, int E>
+__global__ __launch_bounds__(64) void policy_play_kernel(
+    unsigned long long *__restrict__ ticket, const unsigned char *__restrict__ W, uint4 *__restrict__ boards,
+    uint32_t *__restrict__ score, size_t n, uint64_t seed, uint64_t id_base, int max_moves, uint32_t mode,
+    int32_t *__restrict__ moves_out, int32_t *__restrict__ valid_out, int32_t *__restrict__ invalid_out,
+    int4 *__restrict__ milestone_out, double *__restrict__ reward_out, uint8_t *__restrict__ alive_out,
+    uint8_t *__restrict__ actions_out)
+{
+    constexpr int S = 16 * E;
+    __shared__ uint4 s_board[S];
+    __shared__ float4 s_prob[S];
+    __shared__ uint4 s_dir[G2048_DIR_TABLE_WORDS / 4];
+    const int lane = threadIdx.x, h = lane >> 4, col = lane & 15;
+    const bool slot_lane = lane < S;
+    using P = Packed<BF16>;
+    const float *bias = reinterpret_cast<const float *>(W + P::kBias);
+    if (lane < G2048_DIR_TABLE_WORDS) reinterpret_cast<uint32_t *>(s_dir)[lane] = kPlayDirTable[lane];
+
+    Board cur{{0u, 0u, 0u, 0u}};
+    uint32_t sc = 0u;
+    size_t g = 0;
+    bool active = false, drained = false;        // drained: wave-uniform, the queue has no game left
+    int32_t t = 0, nvalid = 0;
+    int32_t ms[8];
+    double rsum = 0.0;
+    for (;;) {
+        if (!drained) {
+            const uint64_t idle = __ballot(slot_lane && !active);
+            if (idle != 0ull) {
+                const uint32_t cnt = (uint32_t)__popcll(idle);
+                unsigned long long got = 0ull;
+                if (lane == 0) got = atomicAdd(ticket, (unsigned long long)cnt);
+                const uint64_t base = ((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(got >> 32)) << 32) |
+                                      __builtin_amdgcn_readfirstlane((uint32_t)got);
+                const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
+                if (slot_lane && !active && base + rank < n) {
+                    g = (size_t)(base + rank);
+                    const uint4 v = boards[g];
+                    cur = Board{{v.x, v.y, v.z, v.w}};
+                    sc = score[g];
+                    t = 0; nvalid = 0; rsum = 0.0;
+#pragma unroll
+                    for (int k = 0; k < 8; ++k) ms[k] = -1;
+                    active = true;
+                }
+                drained = base + cnt >= n;
+            }
+        }
+        if (__ballot(active) == 0ull) break;
+
+        // slot lanes -> LDS (idle slots: the empty board) -> each lane's B-operand dword of every tile
+        if (slot_lane) s_board[lane] = active ? make_uint4(cur.w[0], cur.w[1], cur.w[2], cur.w[3]) : make_uint4(0u, 0u, 0u, 0u);
+        __syncthreads();
+        f4 x[E][2];
+#pragma unroll
+        for (int e = 0; e < E; ++e) board_operand(reinterpret_cast<const uint32_t *>(s_board)[(16 * e + col) * 4 + h], x[e]);
+        POLICY_LAYERS_(BF16, E, W, bias, lane, h, x, out);
+        if (h == 0) {
+#pragma unroll
+            for (int e = 0; e < E; ++e) s_prob[16 * e + col] = softmax4(out[e][0]);
+        }
+        __syncthreads();
+
+        if (slot_lane && active) {
+            const float4 p = s_prob[lane];
+            const uint64_t id = id_base + g;
+            const uint32_t mask = valid_mask_env(cur);
+            uint32_t a;
+            if (mode == G2048_PLAY_POLICY_GREEDY) {              // argmax over the valid moves, ties to the lowest index
+                const uint32_t m = mask ? mask : 15u;            // (no valid move: all four, as sample_action does)
+                float best = 0.0f;
+                a = 4u;
+#pragma unroll
+                for (int k = 3; k >= 0; --k) {
+                    const float v = k == 0 ? p.x : k == 1 ? p.y : k == 2 ? p.z : p.w;
+                    if (((m >> k) & 1u) && (a == 4u || v >= best)) { a = (uint32_t)k; best = v; }
+                }
+            } else {
+                const Keys kp = rng_keys(seed, DOM_POLICY, (uint64_t)t);
+                float pa;
+                a = sample_action(p.x, p.y, p.z, p.w, mode == G2048_PLAY_POLICY_MASKED ? mask : 15u, rng_draw(kp.k0, kp.k1, id, 0u), pa);
+            }
+            const Keys ks = rng_keys(seed, DOM_STEP, (uint64_t)t);
+            const uint4 s0 = s_dir[2u * a], s1 = s_dir[2u * a + 1u];
+            const StepOut o = step_board_sel(cur, DirSel{s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w}, rng_draw(ks.k0, ks.k1, id, 0u));
+            if (actions_out) actions_out[g * (size_t)max_moves + (size_t)t] = (uint8_t)a;
+            cur = o.board;
+            sc += o.gain;
+            rsum += o.reward;
+            const int32_t maxcode = (int32_t)(o.flags >> G2048_FLAG_MAXCODE_SHIFT);
+#pragma unroll
+            for (int k = 0; k < 8; ++k)
+                if (ms[k] < 0 && maxcode >= 6 + k) ms[k] = t;       // tiles 64 .. 8192, as g2048_track_episodes records them
+            nvalid += (o.flags & G2048_FLAG_VALID) ? 1 : 0;
+            ++t;
+            const bool done = (o.flags & G2048_FLAG_DONE) != 0u;
+            if (done || t == max_moves) {
+                boards[g] = make_uint4(cur.w[0], cur.w[1], cur.w[2], cur.w[3]);
+                score[g] = sc;
+                moves_out[g] = t;
+                valid_out[g] = nvalid;
+                invalid_out[g] = t - nvalid;
+                milestone_out[2 * g] = make_int4(ms[0], ms[1], ms[2], ms[3]);
+                milestone_out[2 * g + 1] = make_int4(ms[4], ms[5], ms[6], ms[7]);
+                if (reward_out) reward_out[g] = rsum;
+                alive_out[g] = done ? 0 : 1;
+                active = false;
+            }
+        }
+    }
+}
+
+template <bool BF16, int E>
+int launch_play(const dim3 &waves, hipStream_t s, unsigned long long *ticket, const unsigned char *W, uint4 *boards, uint32_t *score,
+                size_t n, uint64_t seed, uint64_t id_base, int max_moves, uint32_t mode, int32_t *moves, int32_t *valid, int32_t *invalid,
+                int4 *ms, double *reward, uint8_t *alive, uint8_t *actions)
+{
+    hipLaunchKernelGGL((policy_play_kernel<BF16, E>), waves, dim3(64), 0, s, ticket, W, boards, score, n, seed, id_base, max_moves, mode,
+                       moves, valid, invalid, ms, reward, alive, actions);
+    return check_launch("g2048_play_policy_games");
+}
+
+template <bool BF16, int E>
+size_t resident_waves()
+{
+    int dev = 0, cus = 0, per_cu = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, policy_play_kernel<BF16, E>, 64, 0) != hipSuccess)
+        return 0;
+    return (size_t)cus * (size_t)per_cu;
+}
 
 }  // namespace
 
@@ -351,6 +523,60 @@ int g2048_policy_forward(const void *boards, const void *actor_packed, const voi
         hipLaunchKernelGGL((policy_forward_kernel<false, kTilesF32>), grid, dim3(64 * kWaves), 0, s, b, a, c,
                            reinterpret_cast<float4 *>(probs_out), value_out_or_null, n);
     return check_launch("g2048_policy_forward");
+}
+
+size_t g2048_play_policy_workspace(size_t n_games)
+{
+    (void)n_games;
+    return 64;                                   // the ticket counter (uint64), padded
+}
+
+int g2048_play_policy_games(void *boards_inout, uint32_t *score_inout, const void *actor_packed, int32_t *moves_out,
+                            int32_t *valid_out, int32_t *invalid_out, int32_t *milestone_move_out, double *reward_sum_out_or_null,
+                            uint8_t *alive_out, uint8_t *actions_out_or_null, int max_moves, uint64_t seed, uint64_t game_id_base,
+                            size_t n_games, uint32_t opts, uint32_t max_waves, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (n_games == 0) return G2048_OK;
+    if (!boards_inout || !score_inout || !actor_packed || !moves_out || !valid_out || !invalid_out || !milestone_move_out ||
+        !alive_out || !workspace)
+        return fail(G2048_ERR_ARG, "g2048_play_policy_games: null pointer");
+    if (!aligned(boards_inout, 16) || !aligned(actor_packed, 16) || !aligned(milestone_move_out, 16) || !aligned(score_inout, 4) ||
+        !aligned(moves_out, 4) || !aligned(valid_out, 4) || !aligned(invalid_out, 4) || !aligned(reward_sum_out_or_null, 8) ||
+        !aligned(workspace, 8))
+        return fail(G2048_ERR_ARG, "g2048_play_policy_games: misaligned pointer (boards, weights, milestones: 16 bytes; rewards, "
+                                   "workspace: 8; counters and scores: 4)");
+    const uint32_t precision = opts & 0xfu, mode = (opts >> G2048_PLAY_POLICY_MODE_SHIFT) & 0xfu;
+    if ((opts >> (G2048_PLAY_POLICY_MODE_SHIFT + 4)) != 0u || (precision != G2048_POLICY_F32 && precision != G2048_POLICY_BF16))
+        return fail(G2048_ERR_ARG, "g2048_play_policy_games: unknown opts (precision | mode << 4)");
+    if (mode != G2048_PLAY_POLICY_MASKED && mode != G2048_PLAY_POLICY_UNMASKED && mode != G2048_PLAY_POLICY_GREEDY)
+        return fail(G2048_ERR_ARG, "g2048_play_policy_games: unknown mode");
+    if (max_moves < 1) return fail(G2048_ERR_ARG, "g2048_play_policy_games: max_moves must be at least 1");
+    if (workspace_bytes < g2048_play_policy_workspace(n_games))
+        return fail(G2048_ERR_ARG, "g2048_play_policy_games: workspace smaller than g2048_play_policy_workspace(n_games)");
+    const bool bf16 = precision == G2048_POLICY_BF16;
+    const size_t slots = 16 * (size_t)(bf16 ? kTilesBF16 : kTilesF32);
+    // auto: as many wavefronts as the chip holds at once (every later one would only find the queue empty)
+    const size_t cap = max_waves ? (size_t)max_waves : bf16 ? resident_waves<true, kTilesBF16>() : resident_waves<false, kTilesF32>();
+    if (cap == 0) return fail(G2048_ERR_HIP, "g2048_play_policy_games: no HIP device (occupancy query failed)");
+    const size_t waves = std::min(std::min((n_games + slots - 1) / slots, cap), (size_t)0x7fffffffu);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    auto *ticket = static_cast<unsigned long long *>(workspace);
+    hipError_t e = hipMemsetAsync(ticket, 0, sizeof *ticket, s);
+    if (e == hipSuccess && actions_out_or_null) e = hipMemsetAsync(actions_out_or_null, 0xff, n_games * (size_t)max_moves, s);
+    if (e != hipSuccess) {
+        char buf[200];
+        snprintf(buf, sizeof buf, "g2048_play_policy_games: hipMemsetAsync: %s", hipGetErrorString(e));
+        return fail(G2048_ERR_HIP, buf);
+    }
+    const dim3 grid((unsigned)waves);
+    auto *b = static_cast<uint4 *>(boards_inout);
+    const auto *w = static_cast<const unsigned char *>(actor_packed);
+    auto *ms = reinterpret_cast<int4 *>(milestone_move_out);
+    if (bf16)
+        return launch_play<true, kTilesBF16>(grid, s, ticket, w, b, score_inout, n_games, seed, game_id_base, max_moves, mode, moves_out,
+                                             valid_out, invalid_out, ms, reward_sum_out_or_null, alive_out, actions_out_or_null);
+    return launch_play<false, kTilesF32>(grid, s, ticket, w, b, score_inout, n_games, seed, game_id_base, max_moves, mode, moves_out,
+                                         valid_out, invalid_out, ms, reward_sum_out_or_null, alive_out, actions_out_or_null);
 }
 
 }  // extern "C"

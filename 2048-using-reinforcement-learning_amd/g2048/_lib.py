@@ -30,6 +30,7 @@ SEEN_SLOT_BYTES = 32
 ENV_RECORD_BYTES, ENV_OP_STEP, ENV_OP_RESET, ENV_OP_PEEK, ENV_OP_MOVE, ENV_OP_SPAWN, ENV_OP_MOVE_AGENT = 80, 0, 1, 2, 3, 4, 5
 ENV_TOKEN_SHIFT = 8
 POLICY_F32, POLICY_BF16 = 0, 1
+PLAY_POLICY_MASKED, PLAY_POLICY_UNMASKED, PLAY_POLICY_GREEDY, PLAY_POLICY_MODE_SHIFT = 0, 1, 2, 4
 
 _vp, _u64, _sz, _u32, _int = C.c_void_p, C.c_uint64, C.c_size_t, C.c_uint32, C.c_int
 SIGNATURES = {
@@ -86,6 +87,8 @@ SIGNATURES = {
     "g2048_policy_packed_bytes": (_sz, [_int, _int]),
     "g2048_policy_pack": (_int, [_vp, _int, _int, _vp, _vp]),
     "g2048_policy_forward": (_int, [_vp, _vp, _vp, _vp, _vp, _sz, _u32, _vp]),
+    "g2048_play_policy_workspace": (_sz, [_sz]),
+    "g2048_play_policy_games": (_int, [_vp] * 10 + [_int, _u64, _u64, _sz, _u32, _u32, _vp, _sz, _vp]),
 }
 
 

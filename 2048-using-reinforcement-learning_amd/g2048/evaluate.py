@@ -21,6 +21,9 @@ reached 2048 (:185-196), and `train.py` keeps every episode's move-set (`moveset
 counter-based draw keyed by (seed, move, game id), replaying those bytes on the device (`g2048_replay_games`) rebuilds every
 intermediate board, score and max tile of the games asked for -- `results["games"][i]` has the reference's `run_game` keys,
 `save_game_data` / `save_moveset` write the reference's two file formats.
+
+`evaluate_policy` is the same for a PPO actor (a DevicePolicy): the games of train.py / play.py, every game to its end in one
+`g2048_play_policy_games` launch, with the same result dict plus each game's summed env reward.
 """
 import json
 import time
@@ -138,6 +141,101 @@ def evaluate_beam_search(num_games=4096, beam_width=20, search_depth=30, seed=0x
     return results
 
 
+POLICY_MODES = ("masked", "unmasked", "greedy")
+
+
+def evaluate_policy(policy, num_games=4096, max_moves=2000, mode="masked", seed=0x2048, game_id_base=0, device=None,
+                    fused=True, histories=None, max_waves=0):
+    """Complete games of a PPO actor (a g2048.DevicePolicy; its critic, if any, is not used): the games of train.py:54-90
+    (mode="masked": agent.get_action(state, env.get_valid_moves()), max_steps = 2000) or play.py:44-68 ("unmasked":
+    agent.get_action(state)), or the argmax over the valid moves ("greedy"). The network sees one board at a time, as in the
+    reference, so it plays with the weights DevicePolicy uses for a batch of one row (actor.blob(1): no BatchNorm for the
+    reference's fc/bn layout). Game g starts from VecGame2048's reset of global id game_id_base + g.
+
+    fused=True: every game is played to the end in ONE launch (g2048_play_policy_games; max_waves = its wavefront count, 0 =
+    as many as the chip holds). fused=False: the step-by-step loop of existing launches -- policy_forward, sample_actions
+    (greedy: torch's argmax), step, track_episodes -- over the whole batch until every game has ended: the yardstick; the games
+    are identical. Returns evaluate_beam_search's result dict (scores, highest_tiles, moves, valid / invalid moves, milestones,
+    best_games, final_boards, best_*, unfinished, total_moves, elapsed_s, summary) plus "episode_rewards" (the f64 env rewards
+    of each game summed in move order: train.py's episode_reward, play.py's total_reward); "parameters" holds mode,
+    precision, max_moves, num_games and seed. histories: as in evaluate_beam_search (fused driver only)."""
+    if not hasattr(policy, "actor") or not hasattr(policy.actor, "blob"):
+        raise TypeError("g2048.evaluate_policy: policy must be a g2048.DevicePolicy")
+    if mode not in POLICY_MODES:
+        raise ValueError("g2048.evaluate_policy: mode must be one of %s" % (POLICY_MODES,))
+    if int(max_moves) < 1:
+        raise ValueError("g2048.evaluate_policy: max_moves must be at least 1")
+    if histories is not None and not fused:
+        raise ValueError("g2048.evaluate_policy: histories need the fused driver (fused=True)")
+    dev = policy.device
+    if device is not None and ops._dev_index(torch.device(device)) != ops._dev_index(dev):
+        raise ValueError("g2048.evaluate_policy: the policy lives on %s, not %s" % (dev, device))
+    n, max_moves = int(num_games), int(max_moves)
+    blob, precision = policy.actor.blob(1), policy.precision
+    t_start = time.perf_counter()
+    env = VecGame2048(n, device=dev, seed=seed, id_base=game_id_base)
+    boards0 = env.boards.clone() if histories is not None else None
+    if fused:
+        res = ops.play_policy_games(env.boards, env.scores, blob, precision, max_moves, mode, seed, game_id_base,
+                                    want_rewards=True, want_actions=histories is not None, max_waves=max_waves)
+    else:
+        res = _play_policy_stepwise(env, blob, precision, max_moves, mode, seed, game_id_base)
+    torch.cuda.synchronize(dev)
+    elapsed = time.perf_counter() - t_start
+    table = torch.cat([env.scores.to(torch.int64)[:, None], res["moves"].to(torch.int64)[:, None],
+                       res["valid_moves"].to(torch.int64)[:, None], res["invalid_moves"].to(torch.int64)[:, None],
+                       res["alive"].to(torch.int64)[:, None], torch.zeros(n, 1, dtype=torch.int64, device=dev),
+                       res["milestone_move"].to(torch.int64), ops.unpack(env.boards).to(torch.int64).reshape(n, 16)], dim=1)
+    params = {"mode": mode, "precision": precision, "max_moves": max_moves, "num_games": n, "seed": seed}
+    results = policy_results_from_table(table.cpu().numpy(), res["reward_sum"].cpu().numpy(), elapsed, params)
+    if histories is not None:
+        results["games"] = game_histories(results, histories, boards0, res["actions"], res["moves"], seed, game_id_base)
+    return results
+
+
+def policy_results_from_table(table, episode_rewards, elapsed, parameters):
+    """evaluate_policy's result dict from the per-game table (evaluate_beam_search's columns, no expansions) and the f64
+    reward sums."""
+    results = results_from_table(table, elapsed, None, None, parameters["seed"], parameters["max_moves"], parameters=parameters)
+    results["episode_rewards"] = [float(r) for r in episode_rewards]
+    results["summary"] = summarize(results)
+    return results
+
+
+def _play_policy_stepwise(env, blob, precision, max_moves, mode, seed, game_id_base, check_every=16):
+    """The unfused yardstick of g2048_play_policy_games: one policy_forward, one action launch (sample_actions with step_index
+    = t, or torch's argmax), one step and one track_episodes per move for the whole batch. A finished game is over (no move
+    changes its board), so stepping it again changes nothing; its counters and reward sum are frozen by `alive`."""
+    n, dev = env.n, env.device
+    alive = torch.ones(n, dtype=torch.uint8, device=dev)
+    moves = torch.zeros(n, dtype=torch.int32, device=dev)
+    valid_cnt = torch.zeros(n, dtype=torch.int32, device=dev)
+    invalid_cnt = torch.zeros(n, dtype=torch.int32, device=dev)
+    ms_move = torch.full((n, len(MILESTONES)), -1, dtype=torch.int32, device=dev)
+    reward_sum = torch.zeros(n, dtype=torch.float64, device=dev)
+    actions_rec = torch.full((n, max_moves), 0xFF, dtype=torch.uint8, device=dev)
+    probs = torch.empty((n, 4), dtype=torch.float32, device=dev)
+    bits = torch.tensor([1, 2, 4, 8], dtype=torch.uint8, device=dev)
+    for t in range(max_moves):
+        if t % check_every == 0 and not bool(alive.any()):
+            break
+        ops.policy_forward(env.boards, blob, None, precision, probs=probs)
+        if mode == "greedy":
+            valid = (ops.valid_moves(env.boards)[:, None] & bits) != 0
+            valid |= ~valid.any(dim=1, keepdim=True)               # no valid move: all four, as the sampler does
+            actions = probs.masked_fill(~valid, float("-inf")).argmax(dim=1).to(torch.uint8)
+        else:
+            mask = ops.valid_moves(env.boards) if mode == "masked" else None
+            actions, _ = ops.sample_actions(probs, mask, seed, t, game_id_base)
+        live = alive.bool()
+        actions_rec[:, t] = torch.where(live, actions, torch.full_like(actions, 0xFF))
+        _, reward, flags = ops.step(env.boards, actions, env.scores, seed, t, game_id_base, out=env.boards, reward_f64=True)
+        reward_sum = torch.where(live, reward_sum + reward, reward_sum)
+        ops.track_episodes(flags, alive, moves, valid_cnt, invalid_cnt, ms_move, t)
+    return {"moves": moves, "valid_moves": valid_cnt, "invalid_moves": invalid_cnt, "milestone_move": ms_move, "alive": alive,
+            "reward_sum": reward_sum, "actions": actions_rec}
+
+
 def _select_games(results, which):
     n = len(results["scores"])
     if isinstance(which, str):
@@ -217,8 +315,9 @@ def save_game_data(game, path):
 TABLE_COLUMNS = 6 + len(MILESTONES) + 16
 
 
-def results_from_table(table, elapsed, beam_width, search_depth, seed, max_moves):
-    """The result dict from the per-game table (rows in global game order; columns as built in evaluate_beam_search)."""
+def results_from_table(table, elapsed, beam_width, search_depth, seed, max_moves, parameters=None):
+    """The result dict from the per-game table (rows in global game order; columns as built in evaluate_beam_search).
+    parameters: the "parameters" entry to use instead of the beam search's (evaluate_policy)."""
     n = table.shape[0]
     scores = table[:, 0]
     final_boards = table[:, 14:30].reshape(n, 4, 4).astype("int32")
@@ -243,8 +342,8 @@ def results_from_table(table, elapsed, beam_width, search_depth, seed, max_moves
         "total_moves": int(table[:, 1].sum()),
         "total_expansions": int(table[:, 5].sum()),
         "elapsed_s": elapsed,
-        "parameters": {"beam_width": beam_width, "search_depth": search_depth, "num_games": n, "seed": seed,
-                       "max_moves": max_moves},
+        "parameters": parameters if parameters is not None else
+                      {"beam_width": beam_width, "search_depth": search_depth, "num_games": n, "seed": seed, "max_moves": max_moves},
     }
     results["summary"] = summarize(results)
     return results
@@ -279,7 +378,7 @@ def summarize(results):
     dist = {}
     for tile in tiles:
         dist[tile] = dist.get(tile, 0) + 1
-    return {
+    out = {
         "games": len(results["scores"]),
         "highest_tile": max(tiles) if tiles else 0,
         "best_score": max(results["scores"]) if tiles else 0,
@@ -291,6 +390,10 @@ def summarize(results):
         "moves_per_s": results["total_moves"] / results["elapsed_s"] if results.get("elapsed_s") else None,
         "expansions_per_s": results["total_expansions"] / results["elapsed_s"] if results.get("elapsed_s") else None,
     }
+    if "episode_rewards" in results:          # evaluate_policy: train.py's episode_reward
+        out["average_episode_reward"] = sum(results["episode_rewards"]) / n
+        out["games_per_s"] = len(results["scores"]) / results["elapsed_s"] if results.get("elapsed_s") else None
+    return out
 
 
 def save_overall_results(results, path):
@@ -301,8 +404,11 @@ def save_overall_results(results, path):
         "valid_moves": results["valid_moves"], "invalid_moves": results["invalid_moves"],
         "milestones": {str(k): v for k, v in results["milestones"].items()},
         "best_games": results["best_games"],
-        "parameters": {"beam_width": p["beam_width"], "search_depth": p["search_depth"], "num_games": p["num_games"]},
+        "parameters": ({"beam_width": p["beam_width"], "search_depth": p["search_depth"], "num_games": p["num_games"]}
+                       if "beam_width" in p else dict(p)),
     }
+    if "episode_rewards" in results:          # evaluate_policy
+        out["episode_rewards"] = results["episode_rewards"]
     with open(path, "w") as f:
         json.dump(out, f, indent=4)
     return path

@@ -834,6 +834,60 @@ def play_games(boards, scores, width, depth, max_moves=5000, early_threshold=512
     return out
 
 
+PLAY_POLICY_MODES = {"masked": L.PLAY_POLICY_MASKED, "unmasked": L.PLAY_POLICY_UNMASKED, "greedy": L.PLAY_POLICY_GREEDY}
+_PLAY_POLICY_WS = _PerStream()
+
+
+def play_policy_games(boards, scores, actor_packed, precision="f32", max_moves=2000, mode="masked", seed=0x2048, game_id_base=0,
+                      want_rewards=True, want_actions=False, max_waves=0):
+    """Every game played to the end by the PPO actor in ONE launch (g2048_play_policy_games; train.py:54-90 for mode="masked",
+    play.py:44-68 for "unmasked", the argmax over the valid moves for "greedy"). actor_packed: the blob of the weights to play
+    with (DevicePolicy.actor.blob(1) for the reference's batch-of-one rule), packed with `precision`. boards / scores are
+    updated in place. Returns a dict of per-game tensors: moves, valid_moves, invalid_moves (int32), milestone_move (int32
+    (n,8), -1 = never), alive (uint8), with want_rewards "reward_sum" (float64: the env rewards summed in move order) and with
+    want_actions "actions" (uint8 (n, max_moves), 0xFF from a game's end on: the input of `replay_games`). max_waves: the
+    number of wavefronts, 0 = as many as the chip holds (the games are the same for every value)."""
+    L.require_device_tensor(boards, torch.uint8, (16,), "boards")
+    _require_scores(scores)
+    L.require_device_tensor(actor_packed, torch.uint8, None, "actor_packed")
+    if precision not in POLICY_PRECISIONS:
+        raise ValueError("g2048: precision must be 'f32' or 'bf16'")
+    if mode not in PLAY_POLICY_MODES:
+        raise ValueError("g2048: mode must be one of %s" % (tuple(PLAY_POLICY_MODES),))
+    if actor_packed.numel() != policy_packed_bytes(precision, 4):
+        raise ValueError("g2048: actor_packed must be a %s actor blob of %d bytes" % (precision, policy_packed_bytes(precision, 4)))
+    n, dev = boards.shape[0], boards.device
+    if scores.shape[0] != n:
+        raise ValueError("g2048: scores length must equal the number of boards")
+    if int(max_moves) < 1:
+        raise ValueError("g2048: max_moves must be at least 1")
+    if not 0 <= int(max_waves) <= 0xFFFFFFFF:
+        raise ValueError("g2048: max_waves must be 0 (auto) or a positive 32-bit count")
+    out = {
+        "moves": torch.zeros(n, dtype=torch.int32, device=dev), "valid_moves": torch.zeros(n, dtype=torch.int32, device=dev),
+        "invalid_moves": torch.zeros(n, dtype=torch.int32, device=dev),
+        "milestone_move": torch.full((n, 8), -1, dtype=torch.int32, device=dev),
+        "alive": torch.zeros(n, dtype=torch.uint8, device=dev),
+    }
+    if want_rewards:
+        out["reward_sum"] = torch.zeros(n, dtype=torch.float64, device=dev)
+    if want_actions:
+        out["actions"] = torch.empty((n, int(max_moves)), dtype=torch.uint8, device=dev)     # (the library fills it with 0xFF)
+    need = int(L.lib().g2048_play_policy_workspace(n))
+    opts = POLICY_PRECISIONS[precision] | (PLAY_POLICY_MODES[mode] << L.PLAY_POLICY_MODE_SHIFT)
+    ptr = lambda k: out[k].data_ptr() if k in out else None      # noqa: E731
+    box = _PLAY_POLICY_WS.get((_dev_index(dev), L.stream_ptr(dev)), _ScratchBox)
+    with box.lock:          # grow-if-needed and enqueue as one step (see beam_get_action)
+        if box.buf is None or box.buf.numel() < need:
+            box.buf = torch.empty(need, dtype=torch.uint8, device=dev)
+        L.call(dev, L.lib().g2048_play_policy_games, boards.data_ptr(), scores.data_ptr(), actor_packed.data_ptr(),
+               out["moves"].data_ptr(), out["valid_moves"].data_ptr(), out["invalid_moves"].data_ptr(),
+               out["milestone_move"].data_ptr(), ptr("reward_sum"), out["alive"].data_ptr(), ptr("actions"), int(max_moves),
+               L.u64(seed), L.u64(game_id_base), n, opts, int(max_waves), box.buf.data_ptr(), need,
+               L.stream_ptr(dev))
+    return out
+
+
 def replay_games(boards0, actions, n_moves, seed, game_ids=None, game_id_base=0, scores0=None, longest=None):
     """Recorded games replayed into their per-move histories (g2048_replay_games; reference evaluate_beam_search.py:44-50,
     :72-75: board_history / scores_history / max_tiles_history of run_game). boards0 uint8 (k,16): where each game started;

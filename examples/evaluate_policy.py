@@ -1,0 +1,69 @@
+#!/usr/bin/env python3
+"""Evaluate a PPO actor over many complete games on the GPU (the games of train.py / play.py).
+
+    python examples/evaluate_policy.py --games 65536 [--weights reference|random] [--mode masked|unmasked|greedy]
+                                       [--precision f32|bf16] [--max-moves 2000] [--out overall_results.json]
+
+--weights reference (default) loads the reference's trained checkpoint from tests/golden/policy.npz into the reference's
+ActorNetwork layout; random uses a freshly initialised network of that layout. Every game is played to the end in one
+launch (g2048.evaluate_policy); prints the summary table and optionally writes overall_results.json with the per-game
+episode rewards."""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+import torch.nn as nn
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "2048-using-reinforcement-learning_amd"))
+import g2048  # noqa: E402
+from g2048.evaluate import save_overall_results  # noqa: E402
+
+
+class ActorNetwork(nn.Module):
+    """The reference's actor layout (agents/ppo_agent.py:61-98): fc1..fc4, BatchNorm after the first two ReLUs (skipped for a
+    batch of one board, as the reference's forward does), softmax."""
+
+    def __init__(self):
+        super().__init__()
+        self.fc1, self.bn1 = nn.Linear(16, 256), nn.BatchNorm1d(256)
+        self.fc2, self.bn2 = nn.Linear(256, 128), nn.BatchNorm1d(128)
+        self.fc3, self.fc4 = nn.Linear(128, 64), nn.Linear(64, 4)
+        self.relu, self.dropout, self.softmax = nn.ReLU(), nn.Dropout(0.2), nn.Softmax(dim=-1)
+
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--games", type=int, default=4096)
+ap.add_argument("--weights", choices=("reference", "random"), default="reference")
+ap.add_argument("--mode", choices=("masked", "unmasked", "greedy"), default="masked")
+ap.add_argument("--precision", choices=("f32", "bf16"), default="f32")
+ap.add_argument("--max-moves", type=int, default=2000)
+ap.add_argument("--seed", type=int, default=2025)
+ap.add_argument("--out", default=None)
+a = ap.parse_args()
+
+actor = ActorNetwork()
+if a.weights == "reference":
+    g = np.load(os.path.join(ROOT, "tests", "golden", "policy.npz"))
+    sd = {k[len("actor."):]: torch.from_numpy(g[k]) for k in g.files if k.startswith("actor.")}
+    actor.load_state_dict(sd, strict=False)         # (num_batches_tracked is not stored)
+else:
+    torch.manual_seed(a.seed)
+policy = g2048.DevicePolicy(actor.eval().to("cuda"), precision=a.precision)
+res = g2048.evaluate_policy(policy, num_games=a.games, max_moves=a.max_moves, mode=a.mode, seed=a.seed)
+s = res["summary"]
+print("==== POLICY EVALUATION SUMMARY (%s weights, %s, %s) ====" % (a.weights, a.mode, a.precision))
+print("Highest tile reached: %d" % s["highest_tile"])
+print("Best score: %d" % s["best_score"])
+print("Average score: %.1f" % s["average_score"])
+print("Average highest tile: %.1f" % s["average_highest_tile"])
+print("Average episode reward: %.2f" % s["average_episode_reward"])
+print("Games reaching >= 2048: %.1f%%   hit the %d-move cap: %d" % (100 * s["rate_2048_or_more"], a.max_moves, s["hit_move_cap"]))
+print("Highest tile distribution:", json.dumps(s["tile_distribution_pct"]))
+print("%d games, %d moves, %.3f s  (%.3g games/s, %.3g moves/s)" % (a.games, res["total_moves"], res["elapsed_s"], s["games_per_s"],
+                                                                     s["moves_per_s"]))
+if a.out:
+    print("wrote", save_overall_results(res, a.out))

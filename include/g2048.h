@@ -47,7 +47,8 @@ extern "C" {
 
 #define G2048_ABI_VERSION 5        /* 5: round 5, second half (ops MOVE / SPAWN / MOVE_AGENT of g2048_env_step; g2048_eval kinds CORNER_BONUS and
                                       MERGE_POTENTIAL; no entry point added or removed;
-                                      later, additive: g2048_policy_packed_bytes / _pack / _forward)
+                                      later, additive: g2048_policy_packed_bytes / _pack / _forward,
+                                      g2048_play_policy_games / _workspace)
                                       4: round 5 (export table = this header + g2048_testing.h exactly: test / measurement hooks moved there,
                                       internal symbols hidden; g2048_replay_games also clamps a game's length to actions_stride)
                                       3: round 4 (actions_out of the g2048_play_games family, g2048_replay_games, g2048_env_step,
@@ -443,6 +444,37 @@ G2048_API size_t g2048_policy_packed_bytes(int precision, int n_out);
 G2048_API int g2048_policy_pack(const float *plain_f32, int n_out, int precision, void *packed_out, void *stream);
 G2048_API int g2048_policy_forward(const void *boards, const void *actor_packed, const void *critic_packed_or_null, float *probs_out,
                          float *value_out_or_null, size_t n, uint32_t opts, void *stream);
+
+/* Complete games of the PPO actor (play.py:44-68, train.py:54-90), every game played to the end on the device in ONE launch,
+ * as g2048_play_games does for the beam agent. Game g (global id game_id_base + g) starts from boards_inout[g] /
+ * score_inout[g]; at move t = 0, 1, ... it takes p = softmax(actor(board)) -- bit for bit what g2048_policy_forward gives for
+ * the same board and blob (actor_packed, packed with the precision in opts) -- then the action by mode:
+ *   MASKED    train.py:56-61, agent.get_action(state, env.get_valid_moves()): exactly g2048_sample_actions(step_index = t,
+ *             env id = game id) with the env's valid-move mask (draw (seed, POLICY, t, game id));
+ *   UNMASKED  play.py:46, agent.get_action(state): the same with all four actions allowed. Like g2048_sample_actions with no
+ *             mask it samples from p_a + 1e-10, which differs from Categorical(probs) by at most 4e-10 in probability;
+ *   GREEDY    not in the reference: the argmax of p over the valid moves, ties to the lowest index (torch.argmax); no draw;
+ * and steps the board exactly as g2048_step(step_index = t, board id = game id) does, without auto-reset. The game ends when
+ * it is over (DONE) or after max_moves moves. Outputs per game: final board and score (in place), moves, valid / invalid
+ * move counts, milestone_move_out[g][0..8) = the move at which tiles 64..8192 first appeared (-1 = never; as
+ * g2048_track_episodes records them), alive_out[g] = 1 if the game hit max_moves without finishing, reward_sum_out_or_null[g]
+ * = the f64 env rewards (game_2048.py:212-277) summed in move order from 0.0 (train.py's episode_reward, play.py's
+ * total_reward), and actions_out_or_null = the move-set, max_moves bytes per game, 0xFF from the game's end on (the layout of
+ * g2048_play_games: g2048_replay_games rebuilds every intermediate board; the library fills it with 0xFF first).
+ * opts = precision (G2048_POLICY_*) | mode << G2048_PLAY_POLICY_MODE_SHIFT. max_waves = the number of wavefronts (32 games in
+ * flight per wavefront in f32, 64 in bf16; a finished game's slot takes the next game), 0 = as many as the chip holds at once;
+ * the games do not depend on it. workspace: g2048_play_policy_workspace(n_games) bytes of device memory, 8-byte aligned (a
+ * ticket counter the call clears on `stream`). Boards, weights and milestone_move_out 16-byte aligned, rewards 8, the rest 4.
+ * Nothing past game n_games is written. */
+#define G2048_PLAY_POLICY_MASKED   0u   /* train.py:56-61 */
+#define G2048_PLAY_POLICY_UNMASKED 1u   /* play.py:46 */
+#define G2048_PLAY_POLICY_GREEDY   2u   /* argmax over the valid moves (not in the reference) */
+#define G2048_PLAY_POLICY_MODE_SHIFT 4
+G2048_API size_t g2048_play_policy_workspace(size_t n_games);
+G2048_API int g2048_play_policy_games(void *boards_inout, uint32_t *score_inout, const void *actor_packed, int32_t *moves_out,
+                            int32_t *valid_out, int32_t *invalid_out, int32_t *milestone_move_out, double *reward_sum_out_or_null,
+                            uint8_t *alive_out, uint8_t *actions_out_or_null, int max_moves, uint64_t seed, uint64_t game_id_base,
+                            size_t n_games, uint32_t opts, uint32_t max_waves, void *workspace, size_t workspace_bytes, void *stream);
 #ifdef __cplusplus
 }
 #endif
