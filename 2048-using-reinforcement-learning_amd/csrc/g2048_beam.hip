@@ -17,6 +17,7 @@
 #include "../../include/g2048.h"
 #include "../../include/g2048_testing.h"
 #include "g2048_board.h"
+#include "g2048_host.h"
 #include "g2048_instrument.h"
 #include "g2048_rng.h"
 
@@ -26,7 +27,7 @@ namespace {
 
 constexpr int kMaxWidth = G2048_BEAM_MAX_WIDTH;
 constexpr size_t kOrderMaxGames = 1u << 20;
-constexpr int kSimdsPerCu = 4, kFallbackCus = 256;     // CDNA: four SIMDs per compute unit; MI355X's CU count if the device cannot be asked
+constexpr int kSimdsPerCu = 4;      // CDNA: four SIMDs per compute unit
 
 // Launch arithmetic that depends on the chip's size, all of it from the compute-unit count of the device the call runs on
 // (hipDeviceGetAttribute, asked per call: a partitioned or CU-masked device simply reports fewer):
@@ -57,16 +58,6 @@ constexpr uint32_t default_helpers(uint32_t n_games, uint32_t helper_cap)
     const uint32_t want = n_games / 2u > 1024u ? n_games / 2u : 1024u;      // round 3: half the games (a quarter before)
     const uint32_t most = kSpecSlotsPerGame * n_games < want ? kSpecSlotsPerGame * n_games : want;
     return most < helper_cap ? most : helper_cap;
-}
-
-int device_cus()
-{
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) {
-        (void)hipGetLastError();
-        return kFallbackCus;
-    }
-    return cus;
 }
 
 __device__ __forceinline__ uint32_t prefix_count(unsigned long long ballot)
@@ -1182,28 +1173,21 @@ __global__ __launch_bounds__(64) void play_spec_kernel(uint4 *__restrict__ board
 
 extern "C" {
 
-// defined in g2048_kernels.hip; the beam entry point reports through the same thread-local string
-const char *g2048_last_error(void);
-void g2048_set_last_error_(const char *msg);
-
-// Blocks of beam_kernel<passes> the current device holds at once (occupancy x CUs), asked once per device and kernel.
-static size_t beam_resident_blocks(int passes)
+// Blocks of the beam_kernel that serves `width` the current device holds at once (occupancy x CUs), asked once per device and kernel.
+static size_t beam_resident_blocks(int width)
 {
     constexpr int kDevs = 64;
     static std::atomic<uint32_t> cache[kDevs][4];                    // 0 = not asked yet
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kDevs) { (void)hipGetLastError(); return 0; }
-    const int pi = passes == 1 ? 0 : passes == 2 ? 1 : passes == 4 ? 2 : 3;
-    uint32_t v = cache[dev][pi].load(std::memory_order_relaxed);
+    const int passes = passes_for_width(width);
+    std::atomic<uint32_t> &slot = cache[dev][passes == 1 ? 0 : passes == 2 ? 1 : passes == 4 ? 2 : 3];
+    uint32_t v = slot.load(std::memory_order_relaxed);
     if (v == 0u) {
-        int per_cu = 0;
-        const hipError_t e = pi == 0 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, beam_kernel<1>, 64, 0)
-                           : pi == 1 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, beam_kernel<2>, 64, 0)
-                           : pi == 2 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, beam_kernel<4>, 64, 0)
-                                     : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, beam_kernel<8>, 64, 0);
-        if (e != hipSuccess || per_cu <= 0) { (void)hipGetLastError(); return 0; }
+        const int per_cu = with_passes(width, [](auto P) { return resident_per_cu(beam_kernel<decltype(P)::value>, 64); });
+        if (per_cu == 0) return 0;
         v = (uint32_t)per_cu * (uint32_t)device_cus();
-        cache[dev][pi].store(v, std::memory_order_relaxed);
+        slot.store(v, std::memory_order_relaxed);
     }
     return v;
 }
@@ -1215,19 +1199,19 @@ static int beam_impl(const void *root_boards, const uint8_t *valid_mask_or_null,
                      uint32_t *order_ws = nullptr, uint32_t *hist = nullptr, uint32_t call_index = 0)
 {
     if (n_games == 0) return G2048_OK;
-    if (!root_boards || !action_out || !prob_out) { g2048_set_last_error_("g2048_beam_get_action: null pointer"); return G2048_ERR_ARG; }
-    if (reinterpret_cast<uintptr_t>(root_boards) & 15u) { g2048_set_last_error_("g2048_beam_get_action: root array must be 16-byte aligned"); return G2048_ERR_ARG; }
-    if (width < 1 || width > kMaxWidth) { g2048_set_last_error_("g2048_beam_get_action: width must be in 1..128"); return G2048_ERR_ARG; }
-    if (opts & ~(G2048_BEAM_FIXED_DOWN | G2048_BEAM_RANK_BY_COUNTING)) { g2048_set_last_error_("g2048_beam_get_action: unknown opts"); return G2048_ERR_ARG; }
-    if (n_games > 0x7fffffffu) { g2048_set_last_error_("g2048_beam_get_action: too many games for one launch"); return G2048_ERR_ARG; }
-    if (early_threshold < 0 || mid_threshold < 0) { g2048_set_last_error_("g2048_beam_get_action: negative threshold"); return G2048_ERR_ARG; }
+    if (!root_boards || !action_out || !prob_out) return fail(G2048_ERR_ARG, "g2048_beam_get_action: null pointer");
+    if (!aligned(root_boards, 16)) return fail(G2048_ERR_ARG, "g2048_beam_get_action: root array must be 16-byte aligned");
+    if (width < 1 || width > kMaxWidth) return fail(G2048_ERR_ARG, "g2048_beam_get_action: width must be in 1..128");
+    if (opts & ~(G2048_BEAM_FIXED_DOWN | G2048_BEAM_RANK_BY_COUNTING)) return fail(G2048_ERR_ARG, "g2048_beam_get_action: unknown opts");
+    if (n_games > 0x7fffffffu) return fail(G2048_ERR_ARG, "g2048_beam_get_action: too many games for one launch");
+    if (early_threshold < 0 || mid_threshold < 0) return fail(G2048_ERR_ARG, "g2048_beam_get_action: negative threshold");
     const Keys k = rng_keys(seed, DOM_BEAM, step_index);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const dim3 grid((unsigned)n_games);
     const uint4 *roots = static_cast<const uint4 *>(root_boards);
     uint32_t fd = ((opts & G2048_BEAM_FIXED_DOWN) ? 1u : 0u) | ((opts & G2048_BEAM_RANK_BY_COUNTING) ? 2u : 0u);
     // every block resident at once (4096 games on MI355X: four of the six a SIMD holds): issue priority by remaining levels
-    if (n_games <= beam_resident_blocks(width <= 16 ? 1 : width <= 32 ? 2 : width <= 64 ? 4 : 8)) fd |= kFlagPrioByRemaining;
+    if (n_games <= beam_resident_blocks(width)) fd |= kFlagPrioByRemaining;
     // with scratch for it, and a batch of at least four searches per SIMD, the blocks take the games in a depth-balanced order
     uint32_t *order = nullptr;
     const LaunchPlan plan = launch_plan((order_ws || hist) ? device_cus() : 0, 0);
@@ -1236,30 +1220,17 @@ static int beam_impl(const void *root_boards, const uint8_t *valid_mask_or_null,
         order = order_ws;
         hipLaunchKernelGGL(beam_order_kernel, dim3(1), dim3(1024), 0, s, roots, order, (uint32_t)n_games, depth, plan.order_row);
     }
-    {
-#define G2048_LAUNCH_BEAM(P) hipLaunchKernelGGL(beam_kernel<P>, grid, dim3(64), 0, s, roots, valid_mask_or_null, action_out, prob_out, \
-                           expanded_out_or_null, width, depth, (uint32_t)early_threshold, (uint32_t)mid_threshold, \
-                           k.k0, k.k1, game_id_base, fd, keyblock, order, hist, call_index, plan.order_row)
-        if (width <= 16) G2048_LAUNCH_BEAM(1);
-        else if (width <= 32) G2048_LAUNCH_BEAM(2);
-        else if (width <= 64) G2048_LAUNCH_BEAM(4);
-        else G2048_LAUNCH_BEAM(8);
-#undef G2048_LAUNCH_BEAM
-    }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { g2048_set_last_error_(hipGetErrorString(e)); return G2048_ERR_HIP; }
-    return G2048_OK;
+    with_passes(width, [&](auto P) {
+        hipLaunchKernelGGL(beam_kernel<decltype(P)::value>, grid, dim3(64), 0, s, roots, valid_mask_or_null, action_out, prob_out,
+                           expanded_out_or_null, width, depth, (uint32_t)early_threshold, (uint32_t)mid_threshold,
+                           k.k0, k.k1, game_id_base, fd, keyblock, order, hist, call_index, plan.order_row);
+    });
+    return check_launch("g2048_beam_get_action");
 }
 
-static int play_resident_per_cu(int passes)          // blocks of play_spec_kernel<passes> a compute unit holds (0: could not ask)
+static int play_resident_per_cu(int width)           // blocks of the play_spec_kernel that serves `width` a compute unit holds (0: could not ask)
 {
-    int resident = 0;
-    const hipError_t oe = passes == 1 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&resident, play_spec_kernel<1>, 64, 0)
-                        : passes == 2 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&resident, play_spec_kernel<2>, 64, 0)
-                        : passes == 4 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&resident, play_spec_kernel<4>, 64, 0)
-                                      : hipOccupancyMaxActiveBlocksPerMultiprocessor(&resident, play_spec_kernel<8>, 64, 0);
-    if (oe != hipSuccess) { (void)hipGetLastError(); return 0; }
-    return resident;
+    return with_passes(width, [](auto P) { return resident_per_cu(play_spec_kernel<decltype(P)::value>, 64); });
 }
 
 static size_t play_workspace_bytes(size_t n_games)
@@ -1276,34 +1247,27 @@ static int play_impl(void *boards_inout, uint32_t *score_inout, int32_t *moves_o
                      const uint32_t *tuning = nullptr)
 {
     if (n_games == 0) return G2048_OK;
-    if (!boards_inout || !score_inout || !moves_out || !valid_out || !invalid_out || !milestone_move_out || !alive_out) {
-        g2048_set_last_error_("g2048_play_games: null pointer"); return G2048_ERR_ARG;
-    }
-    if ((reinterpret_cast<uintptr_t>(boards_inout) & 15u) || (reinterpret_cast<uintptr_t>(milestone_move_out) & 15u)) {
-        g2048_set_last_error_("g2048_play_games: board / milestone arrays must be 16-byte aligned"); return G2048_ERR_ARG;
-    }
+    if (!boards_inout || !score_inout || !moves_out || !valid_out || !invalid_out || !milestone_move_out || !alive_out)
+        return fail(G2048_ERR_ARG, "g2048_play_games: null pointer");
+    if (!aligned(boards_inout, 16) || !aligned(milestone_move_out, 16))
+        return fail(G2048_ERR_ARG, "g2048_play_games: board / milestone arrays must be 16-byte aligned");
     if (width < 1 || width > kMaxWidth || max_moves < 0 || early_threshold < 0 || mid_threshold < 0 || n_games > 0x7fffffffu ||
-        (opts & ~(G2048_BEAM_FIXED_DOWN | G2048_PLAY_ONE_PHASE | G2048_BEAM_RANK_BY_COUNTING))) {
-        g2048_set_last_error_("g2048_play_games: bad width / max_moves / thresholds / opts / n_games"); return G2048_ERR_ARG;
-    }
+        (opts & ~(G2048_BEAM_FIXED_DOWN | G2048_PLAY_ONE_PHASE | G2048_BEAM_RANK_BY_COUNTING)))
+        return fail(G2048_ERR_ARG, "g2048_play_games: bad width / max_moves / thresholds / opts / n_games");
     hipStream_t s = static_cast<hipStream_t>(stream);
     const uint32_t fd = ((opts & G2048_BEAM_FIXED_DOWN) ? 1u : 0u) | ((opts & G2048_BEAM_RANK_BY_COUNTING) ? 2u : 0u);
-    const int passes = width <= 16 ? 1 : width <= 32 ? 2 : width <= 64 ? 4 : 8;
     if (actions_out_or_null && max_moves > 0) {         // 0xFF = "no move": the owners overwrite one byte per move they apply
-        const hipError_t me = hipMemsetAsync(actions_out_or_null, 0xff, n_games * (size_t)max_moves, s);
-        if (me != hipSuccess) { g2048_set_last_error_(hipGetErrorString(me)); return G2048_ERR_HIP; }
+        if (const int rc = check_hip(hipMemsetAsync(actions_out_or_null, 0xff, n_games * (size_t)max_moves, s), "g2048_play_games")) return rc;
     }
-#define G2048_PLAY_ARGS static_cast<uint4 *>(boards_inout), score_inout, moves_out, valid_out, invalid_out, \
-                        reinterpret_cast<int4 *>(milestone_move_out), expanded_sum_out_or_null, alive_out, width, depth, \
-                        (uint32_t)early_threshold, (uint32_t)mid_threshold, max_moves, seed, game_id_base, fd, actions_out_or_null
+    // both kernels start with the same arguments; play_spec_kernel takes the helpers' after them
+    const auto launch = [&](auto kernel, unsigned blocks, auto... helper_args) {
+        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(64), 0, s, static_cast<uint4 *>(boards_inout), score_inout, moves_out, valid_out, invalid_out,
+                           reinterpret_cast<int4 *>(milestone_move_out), expanded_sum_out_or_null, alive_out, width, depth,
+                           (uint32_t)early_threshold, (uint32_t)mid_threshold, max_moves, seed, game_id_base, fd, actions_out_or_null,
+                           helper_args...);
+    };
     if ((opts & G2048_PLAY_ONE_PHASE) || n_games > kSpecMaxGames) {
-        const dim3 grid((unsigned)n_games);
-#define G2048_LAUNCH_PLAY(P) hipLaunchKernelGGL(play_kernel<P>, grid, dim3(64), 0, s, G2048_PLAY_ARGS)
-        if (passes == 1) G2048_LAUNCH_PLAY(1);
-        else if (passes == 2) G2048_LAUNCH_PLAY(2);
-        else if (passes == 4) G2048_LAUNCH_PLAY(4);
-        else G2048_LAUNCH_PLAY(8);
-#undef G2048_LAUNCH_PLAY
+        with_passes(width, [&](auto P) { launch(play_kernel<decltype(P)::value>, (unsigned)n_games); });
     } else {
         // Helpers: eight per game for a small batch, half the games for a large one, never more than a quarter of the
         // wavefronts the device holds of this kernel at once (launch_plan: CUs x resident blocks per CU / 4 -- 768 on a whole
@@ -1313,7 +1277,7 @@ static int play_impl(void *boards_inout, uint32_t *score_inout, int32_t *moves_o
         // posted result. Measured flat around these values (profiles/r02_eval_helpers.txt); g2048_play_games_tuned overrides
         // them for measurements and tests (every field clamped).
         const uint32_t n = (uint32_t)n_games;
-        const LaunchPlan plan = launch_plan(device_cus(), play_resident_per_cu(passes));
+        const LaunchPlan plan = launch_plan(device_cus(), play_resident_per_cu(width));
         uint32_t helpers = default_helpers(n, plan.helper_cap);
         uint32_t games_left = std::max<uint32_t>(n / 8u, 256u);
         int stuck_thr = 16;
@@ -1329,8 +1293,7 @@ static int play_impl(void *boards_inout, uint32_t *score_inout, int32_t *moves_o
         const size_t bytes = play_workspace_bytes(n_games);
         char *ws = static_cast<char *>(caller_ws);
         if (!ws) {
-            hipError_t e = hipMallocAsync(reinterpret_cast<void **>(&ws), bytes, s);
-            if (e != hipSuccess) { g2048_set_last_error_(hipGetErrorString(e)); return G2048_ERR_HIP; }
+            if (const int rc = check_hip(hipMallocAsync(reinterpret_cast<void **>(&ws), bytes, s), "g2048_play_games")) return rc;
         }
         SpecCtl *ctl = reinterpret_cast<SpecCtl *>(ws);
         uint32_t *reg_list = reinterpret_cast<uint32_t *>(ws + 64);
@@ -1339,22 +1302,14 @@ static int play_impl(void *boards_inout, uint32_t *score_inout, int32_t *moves_o
         if (me == hipSuccess) me = hipMemsetAsync(reg_list, 0xff, list_bytes, s);
         if (me != hipSuccess) {
             if (!caller_ws) (void)hipFreeAsync(ws, s);
-            g2048_set_last_error_(hipGetErrorString(me)); return G2048_ERR_HIP;
+            return check_hip(me, "g2048_play_games");
         }
-        const dim3 grid((unsigned)(n + helpers));
-#define G2048_LAUNCH_PLAY(P) hipLaunchKernelGGL(play_spec_kernel<P>, grid, dim3(64), 0, s, G2048_PLAY_ARGS, ctl, reg_list, slots, n, \
-                                                stuck_thr, reg_resolved, wait_us * 100u)
-        if (passes == 1) G2048_LAUNCH_PLAY(1);
-        else if (passes == 2) G2048_LAUNCH_PLAY(2);
-        else if (passes == 4) G2048_LAUNCH_PLAY(4);
-        else G2048_LAUNCH_PLAY(8);
-#undef G2048_LAUNCH_PLAY
+        with_passes(width, [&](auto P) {
+            launch(play_spec_kernel<decltype(P)::value>, n + helpers, ctl, reg_list, slots, n, stuck_thr, reg_resolved, wait_us * 100u);
+        });
         if (!caller_ws) (void)hipFreeAsync(ws, s);
     }
-#undef G2048_PLAY_ARGS
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { g2048_set_last_error_(hipGetErrorString(e)); return G2048_ERR_HIP; }
-    return G2048_OK;
+    return check_launch("g2048_play_games");
 }
 
 int g2048_play_games(void *boards_inout, uint32_t *score_inout, int32_t *moves_out, int32_t *valid_out, int32_t *invalid_out,
@@ -1372,21 +1327,29 @@ size_t g2048_play_games_workspace(size_t n_games)
     return (n_games == 0 || n_games > kSpecMaxGames) ? 0 : play_workspace_bytes(n_games);
 }
 
+// The caller's workspace as play_impl's caller_ws (*ws_out). Without one, or for a batch that has no helpers, every game plays
+// on its one wavefront (ONE_PHASE, no scratch); one that is given and needed must be large enough and 64-byte aligned.
+static int play_caller_workspace(const char *what, size_t n_games, void *workspace, size_t workspace_bytes, uint32_t *opts, void **ws_out)
+{
+    const size_t need = g2048_play_games_workspace(n_games);
+    if (!workspace || need == 0) *opts |= G2048_PLAY_ONE_PHASE;
+    else if (workspace_bytes < need || !aligned(workspace, 64))
+        return fail(G2048_ERR_ARG, "%s: workspace smaller than g2048_play_games_workspace(n_games) or not 64-byte aligned", what);
+    *ws_out = (*opts & G2048_PLAY_ONE_PHASE) ? nullptr : workspace;
+    return G2048_OK;
+}
+
 int g2048_play_games_ws(void *boards_inout, uint32_t *score_inout, int32_t *moves_out, int32_t *valid_out, int32_t *invalid_out,
                         int32_t *milestone_move_out, unsigned long long *expanded_sum_out_or_null, uint8_t *alive_out, uint8_t *actions_out_or_null,
                         int width, int depth, int early_threshold, int mid_threshold, int max_moves, uint64_t seed,
                         uint64_t game_id_base, size_t n_games, uint32_t opts, void *workspace, size_t workspace_bytes,
                         void *stream)
 {
-    const size_t need = g2048_play_games_workspace(n_games);
-    if (!workspace || need == 0) opts |= G2048_PLAY_ONE_PHASE;                  // no scratch: every game on its one wavefront
-    else if (workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 63u)) {
-        g2048_set_last_error_("g2048_play_games_ws: workspace smaller than g2048_play_games_workspace(n_games) or not 64-byte aligned");
-        return G2048_ERR_ARG;
-    }
+    void *ws = nullptr;
+    if (const int rc = play_caller_workspace("g2048_play_games_ws", n_games, workspace, workspace_bytes, &opts, &ws)) return rc;
     return play_impl(boards_inout, score_inout, moves_out, valid_out, invalid_out, milestone_move_out, expanded_sum_out_or_null,
                      alive_out, actions_out_or_null, width, depth, early_threshold, mid_threshold, max_moves, seed, game_id_base, n_games, opts, stream,
-                     (opts & G2048_PLAY_ONE_PHASE) ? nullptr : workspace);
+                     ws);
 }
 
 int g2048_play_games_tuned(void *boards_inout, uint32_t *score_inout, int32_t *moves_out, int32_t *valid_out, int32_t *invalid_out,
@@ -1395,23 +1358,18 @@ int g2048_play_games_tuned(void *boards_inout, uint32_t *score_inout, int32_t *m
                            uint64_t game_id_base, size_t n_games, uint32_t opts, void *workspace, size_t workspace_bytes,
                            const uint32_t *tuning4, void *stream)
 {
-    if (!tuning4) { g2048_set_last_error_("g2048_play_games_tuned: null tuning"); return G2048_ERR_ARG; }
-    const size_t need = g2048_play_games_workspace(n_games);
-    if (!workspace || need == 0) opts |= G2048_PLAY_ONE_PHASE;
-    else if (workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 63u)) {
-        g2048_set_last_error_("g2048_play_games_tuned: workspace smaller than g2048_play_games_workspace(n_games) or not 64-byte aligned");
-        return G2048_ERR_ARG;
-    }
+    if (!tuning4) return fail(G2048_ERR_ARG, "g2048_play_games_tuned: null tuning");
+    void *ws = nullptr;
+    if (const int rc = play_caller_workspace("g2048_play_games_tuned", n_games, workspace, workspace_bytes, &opts, &ws)) return rc;
     return play_impl(boards_inout, score_inout, moves_out, valid_out, invalid_out, milestone_move_out, expanded_sum_out_or_null,
                      alive_out, actions_out_or_null, width, depth, early_threshold, mid_threshold, max_moves, seed, game_id_base, n_games, opts, stream,
-                     (opts & G2048_PLAY_ONE_PHASE) ? nullptr : workspace, tuning4);
+                     ws, tuning4);
 }
 
 int g2048_launch_plan(int compute_units, int resident_blocks_per_cu, size_t n_games, uint32_t *out4)
 {
-    if (!out4 || compute_units < 0 || resident_blocks_per_cu < 0 || n_games > 0xffffffffu) {
-        g2048_set_last_error_("g2048_launch_plan: bad arguments"); return G2048_ERR_ARG;
-    }
+    if (!out4 || compute_units < 0 || resident_blocks_per_cu < 0 || n_games > 0xffffffffu)
+        return fail(G2048_ERR_ARG, "g2048_launch_plan: bad arguments");
     const LaunchPlan p = launch_plan(compute_units ? compute_units : device_cus(), resident_blocks_per_cu);
     out4[0] = p.order_row; out4[1] = p.order_min; out4[2] = p.helper_cap; out4[3] = default_helpers((uint32_t)n_games, p.helper_cap);
     return G2048_OK;
@@ -1419,13 +1377,10 @@ int g2048_launch_plan(int compute_units, int resident_blocks_per_cu, size_t n_ga
 
 int g2048_device_plan(int width, size_t n_games, uint32_t *out6)
 {
-    if (!out6 || width < 1 || width > kMaxWidth || n_games > 0xffffffffu) {
-        g2048_set_last_error_("g2048_device_plan: bad arguments"); return G2048_ERR_ARG;
-    }
-    const int passes = width <= 16 ? 1 : width <= 32 ? 2 : width <= 64 ? 4 : 8;
-    const int cus = device_cus(), resident = play_resident_per_cu(passes);
+    if (!out6 || width < 1 || width > kMaxWidth || n_games > 0xffffffffu) return fail(G2048_ERR_ARG, "g2048_device_plan: bad arguments");
+    const int cus = device_cus(), resident = play_resident_per_cu(width);
     const LaunchPlan p = launch_plan(cus, resident);
-    const size_t beam_blocks = beam_resident_blocks(passes);
+    const size_t beam_blocks = beam_resident_blocks(width);
     out6[0] = (uint32_t)cus; out6[1] = (uint32_t)resident; out6[2] = p.helper_cap;
     out6[3] = default_helpers((uint32_t)n_games, p.helper_cap); out6[4] = (uint32_t)beam_blocks;
     out6[5] = n_games <= beam_blocks ? 1u : 0u;
@@ -1435,14 +1390,10 @@ int g2048_device_plan(int width, size_t n_games, uint32_t *out6)
 int g2048_sort_selftest(uint32_t *keys_inout, const uint32_t *extra_or_null, size_t n_waves, int key_bits, void *stream)
 {
     if (n_waves == 0) return G2048_OK;
-    if (!keys_inout || n_waves > 0x7fffffffu || (key_bits != 32 && key_bits != 64)) {
-        g2048_set_last_error_("g2048_sort_selftest: bad arguments"); return G2048_ERR_ARG;
-    }
+    if (!keys_inout || n_waves > 0x7fffffffu || (key_bits != 32 && key_bits != 64)) return fail(G2048_ERR_ARG, "g2048_sort_selftest: bad arguments");
     hipLaunchKernelGGL(sort_selftest_kernel, dim3((unsigned)n_waves), dim3(64), 0, static_cast<hipStream_t>(stream), keys_inout,
                        extra_or_null, extra_or_null ? 1 : 0, key_bits == 64 ? 1 : 0);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { g2048_set_last_error_(hipGetErrorString(e)); return G2048_ERR_HIP; }
-    return G2048_OK;
+    return check_launch("g2048_sort_selftest");
 }
 
 int g2048_beam_get_action(const void *root_boards, const uint8_t *valid_mask_or_null, uint8_t *action_out,
@@ -1459,6 +1410,10 @@ size_t g2048_beam_workspace_bytes(size_t n_games)
     return (n_games >= launch_plan(device_cus(), 0).order_min && n_games <= kOrderMaxGames) ? n_games * sizeof(uint32_t) : 0;
 }
 
+// scratch of the _ws / _hist forms is optional (none given, or a batch too small to need any: the plain call); one that is used
+// must be large enough and 4-byte aligned
+static bool beam_scratch_ok(const void *scratch, size_t bytes, size_t need) { return !scratch || !need || (bytes >= need && aligned(scratch, 4)); }
+
 int g2048_beam_get_action_ws(const void *root_boards, const uint8_t *valid_mask_or_null, uint8_t *action_out,
                              float *prob_out, uint32_t *expanded_out_or_null, int width, int depth,
                              int early_threshold, int mid_threshold, uint64_t seed, uint64_t step_index,
@@ -1466,10 +1421,8 @@ int g2048_beam_get_action_ws(const void *root_boards, const uint8_t *valid_mask_
                              void *stream)
 {
     const size_t need = g2048_beam_workspace_bytes(n_games);
-    if (workspace && need && (workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 3u))) {
-        g2048_set_last_error_("g2048_beam_get_action_ws: workspace smaller than g2048_beam_workspace_bytes(n_games) or misaligned");
-        return G2048_ERR_ARG;
-    }
+    if (!beam_scratch_ok(workspace, workspace_bytes, need))
+        return fail(G2048_ERR_ARG, "g2048_beam_get_action_ws: workspace smaller than g2048_beam_workspace_bytes(n_games) or misaligned");
     return beam_impl(root_boards, valid_mask_or_null, action_out, prob_out, expanded_out_or_null, width, depth, early_threshold,
                      mid_threshold, seed, step_index, game_id_base, n_games, opts, stream, nullptr,
                      need ? static_cast<uint32_t *>(workspace) : nullptr);
@@ -1487,10 +1440,8 @@ int g2048_beam_get_action_hist(const void *root_boards, const uint8_t *valid_mas
                                uint32_t call_index, void *stream)
 {
     const size_t need = g2048_beam_history_bytes(n_games);
-    if (history && need && (history_bytes < need || (reinterpret_cast<uintptr_t>(history) & 3u) || call_index == 0u)) {
-        g2048_set_last_error_("g2048_beam_get_action_hist: history smaller than g2048_beam_history_bytes(n_games), misaligned, or call_index 0");
-        return G2048_ERR_ARG;
-    }
+    if (!beam_scratch_ok(history, history_bytes, need) || (history && need && call_index == 0u))
+        return fail(G2048_ERR_ARG, "g2048_beam_get_action_hist: history smaller than g2048_beam_history_bytes(n_games), misaligned, or call_index 0");
     return beam_impl(root_boards, valid_mask_or_null, action_out, prob_out, expanded_out_or_null, width, depth, early_threshold,
                      mid_threshold, seed, step_index, game_id_base, n_games, opts, stream, nullptr, nullptr,
                      (history && need) ? static_cast<uint32_t *>(history) : nullptr, call_index);
@@ -1501,7 +1452,7 @@ int g2048_beam_get_action_dyn(const void *root_boards, const uint8_t *valid_mask
                               int early_threshold, int mid_threshold, const uint32_t *keyblock,
                               uint64_t game_id_base, size_t n_games, uint32_t opts, void *stream)
 {
-    if (!keyblock) { g2048_set_last_error_("g2048_beam_get_action_dyn: null key block"); return G2048_ERR_ARG; }
+    if (!keyblock) return fail(G2048_ERR_ARG, "g2048_beam_get_action_dyn: null key block");
     return beam_impl(root_boards, valid_mask_or_null, action_out, prob_out, expanded_out_or_null, width, depth, early_threshold,
                      mid_threshold, 0, 0, game_id_base, n_games, opts, stream, keyblock);
 }

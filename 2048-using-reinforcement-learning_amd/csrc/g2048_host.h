@@ -1,0 +1,102 @@
+// g2048_host.h -- the host side every entry point of the C-ABI shares: one error string, one way to check arguments and HIP
+// calls, one way to pick a kernel instantiation from run-time values. Host code only, included by the library's four .hip
+// files and nothing else. An entry point reads: checks (fail / aligned), launch (with_* where the kernel is a template),
+// return check_launch("<its name>").
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdarg.h>
+#include <stddef.h>
+#include <stdint.h>
+#include <stdio.h>
+
+#include <type_traits>
+
+#include "../../include/g2048.h"
+
+namespace g2048 {
+
+// ------------------------------------------------------------------------------------------------------------ errors --
+inline thread_local char g_err[256] = "";           // what g2048_last_error() returns
+
+__attribute__((format(printf, 2, 3))) inline int fail(int code, const char *fmt, ...)
+{
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_err, sizeof g_err, fmt, ap);
+    va_end(ap);
+    return code;
+}
+
+// a HIP call's status as the entry point's: "<entry point>: <hip error string>"
+inline int check_hip(hipError_t e, const char *what)
+{
+    return e == hipSuccess ? G2048_OK : fail(G2048_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
+}
+
+inline int check_launch(const char *what) { return check_hip(hipGetLastError(), what); }
+
+// ---------------------------------------------------------------------------------------------------------- arguments --
+// bytes: a power of two. A null pointer is aligned, so an optional array needs no guard of its own.
+inline bool aligned(const void *p, size_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1u)) == 0; }
+
+inline unsigned blocks_for(size_t n, size_t per_block) { return (unsigned)((n + per_block - 1) / per_block); }
+
+// ------------------------------------------------------------------------------------------------------------ device --
+constexpr int kFallbackCus = 256;                    // MI355X's compute-unit count, if the device cannot be asked
+
+// asked per call: a partitioned or CU-masked device simply reports fewer
+inline int device_cus()
+{
+    int dev = 0, cus = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) {
+        (void)hipGetLastError();
+        return kFallbackCus;
+    }
+    return cus;
+}
+
+// blocks of `kernel` a compute unit holds at once (0: could not ask); x device_cus() = what the device holds
+template <class Kernel>
+int resident_per_cu(Kernel kernel, int block_threads)
+{
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, block_threads, 0) != hipSuccess || per_cu < 0) {
+        (void)hipGetLastError();
+        return 0;
+    }
+    return per_cu;
+}
+
+// ---------------------------------------------------------------------------------------------------------- dispatch --
+// From run-time values to template arguments: with_*(value..., f) calls the generic lambda f with the value as a constant
+// (decltype(X)::value inside f), once per value the kernels are compiled for. The order of the cases is the order in
+// which the kernels are instantiated, which is their order in the code object.
+template <int V> using int_c = std::integral_constant<int, V>;
+
+template <class F>
+auto with_bool(bool a, F &&f)
+{
+    return a ? f(std::true_type{}) : f(std::false_type{});
+}
+
+template <class F>
+auto with_bools(bool a, bool b, F &&f)
+{
+    return with_bool(a, [&](auto A) { return with_bool(b, [&](auto B) { return f(A, B); }); });
+}
+
+// the beam kernels take a level's 4 x width children 64 per pass and are compiled for 1, 2, 4 and 8 passes
+inline int passes_for_width(int width) { return width <= 16 ? 1 : width <= 32 ? 2 : width <= 64 ? 4 : 8; }
+
+template <class F>
+auto with_passes(int width, F &&f)
+{
+    switch (passes_for_width(width)) {
+        case 1: return f(int_c<1>{});
+        case 2: return f(int_c<2>{});
+        case 4: return f(int_c<4>{});
+        default: return f(int_c<8>{});
+    }
+}
+
+}  // namespace g2048

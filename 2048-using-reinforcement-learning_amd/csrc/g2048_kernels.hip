@@ -7,13 +7,12 @@
 // operations for the shaped reward. Compile with -ffp-contract=off (reward / eval operation order).
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
-#include <stdarg.h>
 #include <stddef.h>
-#include <stdio.h>
 
 #include "../../include/g2048.h"
 #include "../../include/g2048_testing.h"
 #include "g2048_board.h"
+#include "g2048_host.h"
 #include "g2048_instrument.h"
 #include "g2048_rng.h"
 
@@ -21,33 +20,11 @@ using namespace g2048;
 
 namespace {
 
-thread_local char g_err[256] = "";
-
-int fail(int code, const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof g_err, fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-int check_launch(const char *what)
-{
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(G2048_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
-    return G2048_OK;
-}
-
-inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-inline bool aligned4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
-
 // device key block (uint32[G2048_KEYBLOCK_WORDS]) read by the *_dyn entry points
 enum { KB_STEP = 0, KB_EPISODE = 2, KB_BEAM = 4, KB_POLICY = 6, KB_INDEX = 8 };
 
 constexpr int kBlock = 256;
 constexpr int kStepBoardsPerLane = 1;     // default of g2048_step: measured fastest (profiles/r01_step_tune.txt)
-inline unsigned blocks_for(size_t n, int per_block = kBlock) { return (unsigned)((n + per_block - 1) / per_block); }
 
 // selector words of the direction network (g2048_board.h, "direction by table"); every wave copies them into the
 // block's LDS table itself -- all waves write the same 32 words, and a wave's own write precedes its reads in its
@@ -649,8 +626,6 @@ __global__ void selftest_kernel(uint32_t *result, uint32_t a, uint32_t b, double
 extern "C" {
 
 const char *g2048_last_error(void) { return g_err; }
-// internal: lets the other translation units of this library report through the same string
-void g2048_set_last_error_(const char *msg) { snprintf(g_err, sizeof g_err, "%s", msg); }
 int g2048_abi_version(void) { return G2048_ABI_VERSION; }
 unsigned g2048_build_flags(void) { return kInstrument; }
 
@@ -683,8 +658,8 @@ static int step_impl(const void *boards_in, const uint8_t *actions, void *boards
         }
     }
     if (random_actions && keyblock) return fail(G2048_ERR_ARG, "g2048_step_dyn: RANDOM_ACTIONS needs the scalar form");
-    if (!aligned16(boards_in) || !aligned16(boards_out)) return fail(G2048_ERR_ARG, "g2048_step: board arrays must be 16-byte aligned");
-    if (!aligned4(score_inout) || !aligned4(reward_out) || ((opts & G2048_STEP_REWARD_F64) && (reinterpret_cast<uintptr_t>(reward_out) & 7u)))
+    if (!aligned(boards_in, 16) || !aligned(boards_out, 16)) return fail(G2048_ERR_ARG, "g2048_step: board arrays must be 16-byte aligned");
+    if (!aligned(score_inout, 4) || !aligned(reward_out, (opts & G2048_STEP_REWARD_F64) ? 8 : 4))
         return fail(G2048_ERR_ARG, "g2048_step: score/reward arrays misaligned");
     if (opts & ~(G2048_STEP_REWARD_F64 | G2048_STEP_AUTO_RESET | G2048_STEP_RANDOM_ACTIONS | G2048_STEP_NOOP_ACTIONS | (3u << G2048_STEP_TUNE_SHIFT))) return fail(G2048_ERR_ARG, "g2048_step: unknown opts 0x%x", opts);
     const Keys k = rng_keys(seed, DOM_STEP, step_index), e = rng_keys(seed, DOM_EPISODE, step_index);
@@ -698,38 +673,23 @@ static int step_impl(const void *boards_in, const uint8_t *actions, void *boards
     // wave-level parallelism hides the load latency; from 4 Mi boards on (beyond the Infinity Cache) two boards per lane,
     // both loads in flight before the first is computed, stream 4-5 % faster (profiles/r02_step_tune.txt)
     const int per_lane = tune == 1 ? 1 : tune == 2 ? 2 : (n >= ((size_t)1 << 22) ? 2 : kStepBoardsPerLane);
-#define G2048_LAUNCH_STEP(F, A, BB) \
-    hipLaunchKernelGGL((step_kernel<F, A, BB, kBlock>), dim3(blocks_for(n, kBlock * BB)), dim3(kBlock), 0, s, n, keyblock, in, actions, \
-                       score_inout, (uint32_t)board_id_base, rng_hi_term(board_id_base), k.k0, k.k1, out, reward_out, flags_out, e.k0, e.k1)
-#define G2048_LAUNCH_STEP_B(F, A) \
-    do { if (per_lane == 1) G2048_LAUNCH_STEP(F, A, 1); else G2048_LAUNCH_STEP(F, A, 2); } while (0)
+    // every variant takes the same arguments (a0, a1: the keys of the in-kernel policy); B boards per lane need 1 / B of the blocks
+    const auto launch = [&](auto kernel, int boards_per_lane, uint32_t a0 = 0, uint32_t a1 = 0) {
+        hipLaunchKernelGGL(kernel, dim3(blocks_for(n, kBlock * boards_per_lane)), dim3(kBlock), 0, s, n, keyblock, in, actions, score_inout,
+                           (uint32_t)board_id_base, rng_hi_term(board_id_base), k.k0, k.k1, out, reward_out, flags_out, e.k0, e.k1, a0, a1);
+    };
     if (opts & G2048_STEP_NOOP_ACTIONS) {            // reference semantics for action values outside 0..3 (drop-in class)
         if (random_actions) return fail(G2048_ERR_ARG, "g2048_step: NOOP_ACTIONS needs explicit actions");
-#define G2048_LAUNCH_NOOP(F, A) hipLaunchKernelGGL((step_kernel<F, A, 1, kBlock, false, true>), dim3(blocks_for(n, kBlock)), dim3(kBlock), 0, s, \
-                           n, keyblock, in, actions, score_inout, (uint32_t)board_id_base, rng_hi_term(board_id_base), k.k0, k.k1, out, reward_out, flags_out, e.k0, e.k1)
-        if (f64 && ar) G2048_LAUNCH_NOOP(true, true); else if (f64) G2048_LAUNCH_NOOP(true, false);
-        else if (ar) G2048_LAUNCH_NOOP(false, true); else G2048_LAUNCH_NOOP(false, false);
-#undef G2048_LAUNCH_NOOP
-        return check_launch("g2048_step");
-    }
-    if (random_actions) {           // uniform actions drawn in the kernel: (seed, SYNTH_ACTION, step_index, board id) >> 30
+        with_bools(f64, ar, [&](auto F, auto A) { launch(step_kernel<decltype(F)::value, decltype(A)::value, 1, kBlock, false, true>, 1); });
+    } else if (random_actions) {    // uniform actions drawn in the kernel: (seed, SYNTH_ACTION, step_index, board id) >> 30
         const Keys ak = rng_keys(seed, DOM_SYNTH_ACTION, step_index);
-#define G2048_LAUNCH_RANDOM(F, A) \
-        hipLaunchKernelGGL((step_kernel<F, A, 1, kBlock, true>), dim3(blocks_for(n, kBlock)), dim3(kBlock), 0, s, n, keyblock, in, actions, \
-                           score_inout, (uint32_t)board_id_base, rng_hi_term(board_id_base), k.k0, k.k1, out, reward_out, flags_out, e.k0, e.k1, ak.k0, ak.k1)
-        if (f64 && ar) G2048_LAUNCH_RANDOM(true, true);
-        else if (f64) G2048_LAUNCH_RANDOM(true, false);
-        else if (ar) G2048_LAUNCH_RANDOM(false, true);
-        else G2048_LAUNCH_RANDOM(false, false);
-#undef G2048_LAUNCH_RANDOM
-        return check_launch("g2048_step");
+        with_bools(f64, ar, [&](auto F, auto A) { launch(step_kernel<decltype(F)::value, decltype(A)::value, 1, kBlock, true>, 1, ak.k0, ak.k1); });
+    } else {
+        with_bools(f64, ar, [&](auto F, auto A) {
+            if (per_lane == 1) launch(step_kernel<decltype(F)::value, decltype(A)::value, 1, kBlock>, 1);
+            else launch(step_kernel<decltype(F)::value, decltype(A)::value, 2, kBlock>, 2);
+        });
     }
-    if (f64 && ar) G2048_LAUNCH_STEP_B(true, true);
-    else if (f64) G2048_LAUNCH_STEP_B(true, false);
-    else if (ar) G2048_LAUNCH_STEP_B(false, true);
-    else G2048_LAUNCH_STEP_B(false, false);
-#undef G2048_LAUNCH_STEP_B
-#undef G2048_LAUNCH_STEP
     return check_launch("g2048_step");
 }
 
@@ -757,28 +717,25 @@ int g2048_step_many(const void *boards_in, const uint8_t *actions_stream_or_null
 {
     if (n == 0) return G2048_OK;
     if (!boards_in || !boards_out || !score_inout || !flags_last_out) return fail(G2048_ERR_ARG, "g2048_step_many: null pointer");
-    if (!aligned16(boards_in) || !aligned16(boards_out)) return fail(G2048_ERR_ARG, "g2048_step_many: board arrays must be 16-byte aligned");
+    if (!aligned(boards_in, 16) || !aligned(boards_out, 16)) return fail(G2048_ERR_ARG, "g2048_step_many: board arrays must be 16-byte aligned");
     const bool f64 = (opts & G2048_STEP_REWARD_F64) != 0u, ar = (opts & G2048_STEP_AUTO_RESET) != 0u;
     const bool random_actions = (opts & G2048_STEP_RANDOM_ACTIONS) != 0u;
-    if (!aligned4(score_inout) || (episodes_out_or_null && !aligned4(episodes_out_or_null)) ||
-        (reward_stream_out_or_null && (reinterpret_cast<uintptr_t>(reward_stream_out_or_null) & (f64 ? 7u : 3u))))
+    if (!aligned(score_inout, 4) || !aligned(episodes_out_or_null, 4) || !aligned(reward_stream_out_or_null, f64 ? 8 : 4))
         return fail(G2048_ERR_ARG, "g2048_step_many: score / reward / episode arrays misaligned");
     if (!random_actions && !actions_stream_or_null)
         return fail(G2048_ERR_ARG, "g2048_step_many: no policy: pass an actions stream or set G2048_STEP_RANDOM_ACTIONS");
     if (opts & ~(G2048_STEP_REWARD_F64 | G2048_STEP_AUTO_RESET | G2048_STEP_RANDOM_ACTIONS)) return fail(G2048_ERR_ARG, "g2048_step_many: unknown opts 0x%x", opts);
     if (steps == 0) return fail(G2048_ERR_ARG, "g2048_step_many: steps must be at least 1");
     hipStream_t s = static_cast<hipStream_t>(stream);
-#define G2048_LAUNCH_MANY(F, A, R) hipLaunchKernelGGL((step_many_kernel<F, A, kBlock, R>), dim3(blocks_for(n)), dim3(kBlock), 0, s, \
-                           static_cast<const uint4 *>(boards_in), actions_stream_or_null, static_cast<uint4 *>(boards_out), score_inout, \
-                           reward_stream_out_or_null, flags_stream_out_or_null, flags_last_out, episodes_out_or_null, seed, step_index0, \
-                           steps, board_id_base, n)
-#define G2048_LAUNCH_MANY_R(F, A) do { if (random_actions) G2048_LAUNCH_MANY(F, A, true); else G2048_LAUNCH_MANY(F, A, false); } while (0)
-    if (f64 && ar) G2048_LAUNCH_MANY_R(true, true);
-    else if (f64) G2048_LAUNCH_MANY_R(true, false);
-    else if (ar) G2048_LAUNCH_MANY_R(false, true);
-    else G2048_LAUNCH_MANY_R(false, false);
-#undef G2048_LAUNCH_MANY_R
-#undef G2048_LAUNCH_MANY
+    const auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(blocks_for(n, kBlock)), dim3(kBlock), 0, s, static_cast<const uint4 *>(boards_in), actions_stream_or_null,
+                           static_cast<uint4 *>(boards_out), score_inout, reward_stream_out_or_null, flags_stream_out_or_null, flags_last_out,
+                           episodes_out_or_null, seed, step_index0, steps, board_id_base, n);
+    };
+    with_bools(f64, ar, [&](auto F, auto A) {
+        if (random_actions) launch(step_many_kernel<decltype(F)::value, decltype(A)::value, kBlock, true>);
+        else launch(step_many_kernel<decltype(F)::value, decltype(A)::value, kBlock, false>);
+    });
     return check_launch("g2048_step_many");
 }
 
@@ -786,7 +743,7 @@ int g2048_env_step(void *board_inout, uint32_t *score_inout, uint32_t action, ui
                    uint64_t index, uint64_t board_id, void *stream)
 {
     if (!board_inout || !score_inout || !record_out) return fail(G2048_ERR_ARG, "g2048_env_step: null pointer");
-    if (!aligned16(board_inout) || !aligned4(score_inout) || !aligned16(record_out)) return fail(G2048_ERR_ARG, "g2048_env_step: misaligned pointer");
+    if (!aligned(board_inout, 16) || !aligned(score_inout, 4) || !aligned(record_out, 16)) return fail(G2048_ERR_ARG, "g2048_env_step: misaligned pointer");
     const uint32_t token = (op >> G2048_ENV_TOKEN_SHIFT) & 0xffffu;
     if (op >> (G2048_ENV_TOKEN_SHIFT + 16)) return fail(G2048_ERR_ARG, "g2048_env_step: unknown op bits 0x%x", op);
     op &= (1u << G2048_ENV_TOKEN_SHIFT) - 1u;
@@ -804,12 +761,12 @@ int g2048_replay_games(const void *boards0, const uint32_t *score0_or_null, cons
 {
     if (n == 0) return G2048_OK;
     if (!boards0 || !actions || !n_moves || !boards_hist_out) return fail(G2048_ERR_ARG, "g2048_replay_games: null pointer");
-    if (!aligned16(boards0) || !aligned16(boards_hist_out) || !aligned4(n_moves) || (score0_or_null && !aligned4(score0_or_null)) ||
-        (score_hist_out_or_null && !aligned4(score_hist_out_or_null)) || (game_ids_or_null && (reinterpret_cast<uintptr_t>(game_ids_or_null) & 7u)))
+    if (!aligned(boards0, 16) || !aligned(boards_hist_out, 16) || !aligned(n_moves, 4) || !aligned(score0_or_null, 4) ||
+        !aligned(score_hist_out_or_null, 4) || !aligned(game_ids_or_null, 8))
         return fail(G2048_ERR_ARG, "g2048_replay_games: misaligned array");
     if (hist_stride == 0) return fail(G2048_ERR_ARG, "g2048_replay_games: hist_stride must be at least 1 (max moves + 1)");
     if (actions_stride == 0) return fail(G2048_ERR_ARG, "g2048_replay_games: actions_stride must be at least 1 (bytes per game row)");
-    hipLaunchKernelGGL(replay_kernel, dim3(blocks_for(n)), dim3(kBlock), 0, static_cast<hipStream_t>(stream),
+    hipLaunchKernelGGL(replay_kernel, dim3(blocks_for(n, kBlock)), dim3(kBlock), 0, static_cast<hipStream_t>(stream),
                        static_cast<const uint4 *>(boards0), score0_or_null, reinterpret_cast<const unsigned long long *>(game_ids_or_null),
                        game_id_base, actions, actions_stride, n_moves, static_cast<uint4 *>(boards_hist_out), score_hist_out_or_null,
                        flags_hist_out_or_null, hist_stride, seed, n);
@@ -821,9 +778,9 @@ int g2048_reset(void *boards_out, uint32_t *score_out, uint64_t seed, uint64_t e
 {
     if (n == 0) return G2048_OK;
     if (!boards_out) return fail(G2048_ERR_ARG, "g2048_reset: null pointer");
-    if (!aligned16(boards_out)) return fail(G2048_ERR_ARG, "g2048_reset: board array must be 16-byte aligned");
+    if (!aligned(boards_out, 16)) return fail(G2048_ERR_ARG, "g2048_reset: board array must be 16-byte aligned");
     const Keys k = rng_keys(seed, DOM_RESET, epoch);
-    hipLaunchKernelGGL(reset_kernel, dim3(blocks_for(n)), dim3(kBlock), 0, static_cast<hipStream_t>(stream),
+    hipLaunchKernelGGL(reset_kernel, dim3(blocks_for(n, kBlock)), dim3(kBlock), 0, static_cast<hipStream_t>(stream),
                        static_cast<uint4 *>(boards_out), score_out, k.k0, k.k1, board_id_base, n);
     return check_launch("g2048_reset");
 }
@@ -832,12 +789,12 @@ int g2048_valid_moves(const void *boards, uint8_t *mask4_out, size_t n, uint32_t
 {
     if (n == 0) return G2048_OK;
     if (!boards || !mask4_out) return fail(G2048_ERR_ARG, "g2048_valid_moves: null pointer");
-    if (!aligned16(boards)) return fail(G2048_ERR_ARG, "g2048_valid_moves: board array must be 16-byte aligned");
+    if (!aligned(boards, 16)) return fail(G2048_ERR_ARG, "g2048_valid_moves: board array must be 16-byte aligned");
     if (opts > G2048_VALID_AGENT) return fail(G2048_ERR_ARG, "g2048_valid_moves: unknown opts 0x%x", opts);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const uint4 *b = static_cast<const uint4 *>(boards);
-    if (opts == G2048_VALID_AGENT) hipLaunchKernelGGL(valid_kernel<true>, dim3(blocks_for(n)), dim3(kBlock), 0, s, b, mask4_out, n);
-    else hipLaunchKernelGGL(valid_kernel<false>, dim3(blocks_for(n)), dim3(kBlock), 0, s, b, mask4_out, n);
+    if (opts == G2048_VALID_AGENT) hipLaunchKernelGGL(valid_kernel<true>, dim3(blocks_for(n, kBlock)), dim3(kBlock), 0, s, b, mask4_out, n);
+    else hipLaunchKernelGGL(valid_kernel<false>, dim3(blocks_for(n, kBlock)), dim3(kBlock), 0, s, b, mask4_out, n);
     return check_launch("g2048_valid_moves");
 }
 
@@ -849,8 +806,8 @@ static int track_impl(const uint8_t *flags, const uint32_t *expanded_or_null, ui
     if (n == 0) return G2048_OK;
     if (!flags || !alive_inout || !moves_inout || !valid_inout || !invalid_inout || !milestone_move_inout)
         return fail(G2048_ERR_ARG, "g2048_track_episodes: null pointer");
-    if (!aligned16(milestone_move_inout)) return fail(G2048_ERR_ARG, "g2048_track_episodes: milestone array must be 16-byte aligned");
-    hipLaunchKernelGGL(track_kernel, dim3(blocks_for(n)), dim3(kBlock), 0, static_cast<hipStream_t>(stream), flags,
+    if (!aligned(milestone_move_inout, 16)) return fail(G2048_ERR_ARG, "g2048_track_episodes: milestone array must be 16-byte aligned");
+    hipLaunchKernelGGL(track_kernel, dim3(blocks_for(n, kBlock)), dim3(kBlock), 0, static_cast<hipStream_t>(stream), flags,
                        expanded_or_null, alive_inout, moves_inout, valid_inout, invalid_inout,
                        reinterpret_cast<int4 *>(milestone_move_inout), expanded_sum_inout_or_null, move_index, n, keyblock);
     return check_launch("g2048_track_episodes");
@@ -878,9 +835,9 @@ static int sample_impl(const float *probs, const uint8_t *mask4_or_null, uint8_t
 {
     if (n == 0) return G2048_OK;
     if (!probs || !actions_out || !prob_out) return fail(G2048_ERR_ARG, "g2048_sample_actions: null pointer");
-    if (!aligned16(probs) || !aligned4(prob_out)) return fail(G2048_ERR_ARG, "g2048_sample_actions: misaligned array");
+    if (!aligned(probs, 16) || !aligned(prob_out, 4)) return fail(G2048_ERR_ARG, "g2048_sample_actions: misaligned array");
     const Keys k = rng_keys(seed, DOM_POLICY, step_index);
-    hipLaunchKernelGGL(sample_kernel, dim3(blocks_for(n)), dim3(kBlock), 0, static_cast<hipStream_t>(stream),
+    hipLaunchKernelGGL(sample_kernel, dim3(blocks_for(n, kBlock)), dim3(kBlock), 0, static_cast<hipStream_t>(stream),
                        reinterpret_cast<const float4 *>(probs), mask4_or_null, actions_out, prob_out, k.k0, k.k1, env_id_base, n,
                        keyblock);
     return check_launch("g2048_sample_actions");
@@ -905,9 +862,9 @@ int g2048_simulate_move(const void *boards, const uint8_t *actions, const uint8_
     if (n == 0) return G2048_OK;
     if (!boards || !actions || !succ_boards_out || !reward_out || !done_out || !count_out)
         return fail(G2048_ERR_ARG, "g2048_simulate_move: null pointer");
-    if (!aligned16(boards) || !aligned16(succ_boards_out) || (reinterpret_cast<uintptr_t>(reward_out) & 7u))
+    if (!aligned(boards, 16) || !aligned(succ_boards_out, 16) || !aligned(reward_out, 8))
         return fail(G2048_ERR_ARG, "g2048_simulate_move: misaligned array");
-    hipLaunchKernelGGL(simulate_kernel, dim3(blocks_for(n * 32)), dim3(kBlock), 0, static_cast<hipStream_t>(stream),
+    hipLaunchKernelGGL(simulate_kernel, dim3(blocks_for(n * 32, kBlock)), dim3(kBlock), 0, static_cast<hipStream_t>(stream),
                        static_cast<const uint4 *>(boards), actions, highest_code_or_null, static_cast<uint4 *>(succ_boards_out),
                        reward_out, done_out, count_out, n);
     return check_launch("g2048_simulate_move");
@@ -920,10 +877,10 @@ int g2048_simulate_move_sampled(const void *boards, const uint8_t *actions, void
     if (n == 0) return G2048_OK;
     if (!boards || !actions || !succ_boards_out || !reward_out || !done_out || !count_out)
         return fail(G2048_ERR_ARG, "g2048_simulate_move_sampled: null pointer");
-    if (!aligned16(boards) || !aligned16(succ_boards_out) || (reinterpret_cast<uintptr_t>(reward_out) & 7u))
+    if (!aligned(boards, 16) || !aligned(succ_boards_out, 16) || !aligned(reward_out, 8))
         return fail(G2048_ERR_ARG, "g2048_simulate_move_sampled: misaligned array");
     const Keys k = rng_keys(seed, DOM_SIMULATE, step_index);
-    hipLaunchKernelGGL(simulate_sampled_kernel, dim3(blocks_for(n * 8)), dim3(kBlock), 0, static_cast<hipStream_t>(stream),
+    hipLaunchKernelGGL(simulate_sampled_kernel, dim3(blocks_for(n * 8, kBlock)), dim3(kBlock), 0, static_cast<hipStream_t>(stream),
                        static_cast<const uint4 *>(boards), actions, static_cast<uint4 *>(succ_boards_out), reward_out, done_out,
                        count_out, k.k0, k.k1, state_id_base, n);
     return check_launch("g2048_simulate_move_sampled");
@@ -933,10 +890,10 @@ int g2048_eval(const void *boards, int kind, const uint8_t *phase_or_null, doubl
 {
     if (n == 0) return G2048_OK;
     if (!boards || !out) return fail(G2048_ERR_ARG, "g2048_eval: null pointer");
-    if (!aligned16(boards) || (reinterpret_cast<uintptr_t>(out) & 7u)) return fail(G2048_ERR_ARG, "g2048_eval: misaligned array");
+    if (!aligned(boards, 16) || !aligned(out, 8)) return fail(G2048_ERR_ARG, "g2048_eval: misaligned array");
     hipStream_t s = static_cast<hipStream_t>(stream);
     const uint4 *b = static_cast<const uint4 *>(boards);
-    const dim3 grid(blocks_for(n)), block(kBlock);
+    const dim3 grid(blocks_for(n, kBlock)), block(kBlock);
     switch (kind) {
 #define G2048_EVAL_CASE(K) case K: hipLaunchKernelGGL(eval_kernel<K>, grid, block, 0, s, b, phase_or_null, out, n); break;
         G2048_EVAL_CASE(G2048_EVAL_FAST)
@@ -960,8 +917,8 @@ int g2048_obs_f32(const void *boards, float *obs_out, size_t n, void *stream)
 {
     if (n == 0) return G2048_OK;
     if (!boards || !obs_out) return fail(G2048_ERR_ARG, "g2048_obs_f32: null pointer");
-    if (!aligned16(boards) || !aligned16(obs_out)) return fail(G2048_ERR_ARG, "g2048_obs_f32: arrays must be 16-byte aligned");
-    hipLaunchKernelGGL(obs_kernel, dim3(blocks_for(n * 4)), dim3(kBlock), 0, static_cast<hipStream_t>(stream),
+    if (!aligned(boards, 16) || !aligned(obs_out, 16)) return fail(G2048_ERR_ARG, "g2048_obs_f32: arrays must be 16-byte aligned");
+    hipLaunchKernelGGL(obs_kernel, dim3(blocks_for(n * 4, kBlock)), dim3(kBlock), 0, static_cast<hipStream_t>(stream),
                        static_cast<const uint32_t *>(boards), reinterpret_cast<float4 *>(obs_out), n * 4);
     return check_launch("g2048_obs_f32");
 }
@@ -970,11 +927,11 @@ int g2048_obs_16(const void *boards, void *obs_out, int bf16, size_t n, void *st
 {
     if (n == 0) return G2048_OK;
     if (!boards || !obs_out) return fail(G2048_ERR_ARG, "g2048_obs_16: null pointer");
-    if (!aligned16(boards) || (reinterpret_cast<uintptr_t>(obs_out) & 7u)) return fail(G2048_ERR_ARG, "g2048_obs_16: misaligned array");
+    if (!aligned(boards, 16) || !aligned(obs_out, 8)) return fail(G2048_ERR_ARG, "g2048_obs_16: misaligned array");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (bf16) hipLaunchKernelGGL(obs16_kernel<true>, dim3(blocks_for(n * 4)), dim3(kBlock), 0, s, static_cast<const uint32_t *>(boards),
+    if (bf16) hipLaunchKernelGGL(obs16_kernel<true>, dim3(blocks_for(n * 4, kBlock)), dim3(kBlock), 0, s, static_cast<const uint32_t *>(boards),
                                  static_cast<uint2 *>(obs_out), n * 4);
-    else hipLaunchKernelGGL(obs16_kernel<false>, dim3(blocks_for(n * 4)), dim3(kBlock), 0, s, static_cast<const uint32_t *>(boards),
+    else hipLaunchKernelGGL(obs16_kernel<false>, dim3(blocks_for(n * 4, kBlock)), dim3(kBlock), 0, s, static_cast<const uint32_t *>(boards),
                             static_cast<uint2 *>(obs_out), n * 4);
     return check_launch("g2048_obs_16");
 }
@@ -983,8 +940,8 @@ int g2048_pack_i32(const int32_t *tiles, void *boards_out, size_t n, void *strea
 {
     if (n == 0) return G2048_OK;
     if (!tiles || !boards_out) return fail(G2048_ERR_ARG, "g2048_pack_i32: null pointer");
-    if (!aligned16(tiles) || !aligned16(boards_out)) return fail(G2048_ERR_ARG, "g2048_pack_i32: arrays must be 16-byte aligned");
-    hipLaunchKernelGGL(pack_kernel, dim3(blocks_for(n * 4)), dim3(kBlock), 0, static_cast<hipStream_t>(stream),
+    if (!aligned(tiles, 16) || !aligned(boards_out, 16)) return fail(G2048_ERR_ARG, "g2048_pack_i32: arrays must be 16-byte aligned");
+    hipLaunchKernelGGL(pack_kernel, dim3(blocks_for(n * 4, kBlock)), dim3(kBlock), 0, static_cast<hipStream_t>(stream),
                        reinterpret_cast<const int4 *>(tiles), static_cast<uint32_t *>(boards_out), n * 4);
     return check_launch("g2048_pack_i32");
 }
@@ -993,8 +950,8 @@ int g2048_unpack_i32(const void *boards, int32_t *tiles_out, size_t n, void *str
 {
     if (n == 0) return G2048_OK;
     if (!boards || !tiles_out) return fail(G2048_ERR_ARG, "g2048_unpack_i32: null pointer");
-    if (!aligned16(boards) || !aligned16(tiles_out)) return fail(G2048_ERR_ARG, "g2048_unpack_i32: arrays must be 16-byte aligned");
-    hipLaunchKernelGGL(unpack_kernel, dim3(blocks_for(n * 4)), dim3(kBlock), 0, static_cast<hipStream_t>(stream),
+    if (!aligned(boards, 16) || !aligned(tiles_out, 16)) return fail(G2048_ERR_ARG, "g2048_unpack_i32: arrays must be 16-byte aligned");
+    hipLaunchKernelGGL(unpack_kernel, dim3(blocks_for(n * 4, kBlock)), dim3(kBlock), 0, static_cast<hipStream_t>(stream),
                        static_cast<const uint32_t *>(boards), reinterpret_cast<int4 *>(tiles_out), n * 4);
     return check_launch("g2048_unpack_i32");
 }
@@ -1004,10 +961,10 @@ int g2048_synth_boards(void *boards_out, uint64_t seed, uint64_t board_id_base, 
 {
     if (n == 0) return G2048_OK;
     if (!boards_out) return fail(G2048_ERR_ARG, "g2048_synth_boards: null pointer");
-    if (!aligned16(boards_out)) return fail(G2048_ERR_ARG, "g2048_synth_boards: board array must be 16-byte aligned");
+    if (!aligned(boards_out, 16)) return fail(G2048_ERR_ARG, "g2048_synth_boards: board array must be 16-byte aligned");
     if (max_code_ < 1 || max_code_ > 17 || p_empty_u16 > 65536) return fail(G2048_ERR_ARG, "g2048_synth_boards: bad distribution");
     const Keys k = rng_keys(seed, DOM_SYNTH_BOARD, 0);
-    hipLaunchKernelGGL(synth_boards_kernel, dim3(blocks_for(n)), dim3(kBlock), 0, static_cast<hipStream_t>(stream),
+    hipLaunchKernelGGL(synth_boards_kernel, dim3(blocks_for(n, kBlock)), dim3(kBlock), 0, static_cast<hipStream_t>(stream),
                        static_cast<uint4 *>(boards_out), k.k0, k.k1, board_id_base, n, p_empty_u16, max_code_);
     return check_launch("g2048_synth_boards");
 }
@@ -1017,7 +974,7 @@ int g2048_synth_actions(uint8_t *actions_out, uint64_t seed, uint64_t step_index
     if (n == 0) return G2048_OK;
     if (!actions_out) return fail(G2048_ERR_ARG, "g2048_synth_actions: null pointer");
     const Keys k = rng_keys(seed, DOM_SYNTH_ACTION, step_index);
-    hipLaunchKernelGGL(synth_actions_kernel, dim3(blocks_for(n)), dim3(kBlock), 0, static_cast<hipStream_t>(stream),
+    hipLaunchKernelGGL(synth_actions_kernel, dim3(blocks_for(n, kBlock)), dim3(kBlock), 0, static_cast<hipStream_t>(stream),
                        actions_out, k.k0, k.k1, board_id_base, n);
     return check_launch("g2048_synth_actions");
 }
@@ -1027,8 +984,8 @@ int g2048_metrics(const void *boards, const uint32_t *score, const uint8_t *flag
 {
     if (n == 0) return G2048_OK;
     if (!boards || !out24) return fail(G2048_ERR_ARG, "g2048_metrics: null pointer");
-    if (!aligned16(boards)) return fail(G2048_ERR_ARG, "g2048_metrics: board array must be 16-byte aligned");
-    unsigned grid = blocks_for(n);
+    if (!aligned(boards, 16)) return fail(G2048_ERR_ARG, "g2048_metrics: board array must be 16-byte aligned");
+    unsigned grid = blocks_for(n, kBlock);
     if (grid > 2048u) grid = 2048u;
     hipLaunchKernelGGL(metrics_kernel, dim3(grid), dim3(kBlock), 0, static_cast<hipStream_t>(stream),
                        static_cast<const uint4 *>(boards), score, flags_or_null, expanded_or_null, out24, n);
@@ -1038,7 +995,7 @@ int g2048_metrics(const void *boards, const uint32_t *score, const uint8_t *flag
 int g2048_keys_advance(uint32_t *keyblock_out, unsigned long long *counter_inout, uint64_t seed, void *stream)
 {
     if (!keyblock_out || !counter_inout) return fail(G2048_ERR_ARG, "g2048_keys_advance: null pointer");
-    if ((reinterpret_cast<uintptr_t>(counter_inout) & 7u) || !aligned4(keyblock_out))
+    if (!aligned(counter_inout, 8) || !aligned(keyblock_out, 4))
         return fail(G2048_ERR_ARG, "g2048_keys_advance: misaligned pointer");
     hipLaunchKernelGGL(keys_advance_kernel, dim3(1), dim3(1), 0, static_cast<hipStream_t>(stream), keyblock_out, counter_inout, seed);
     return check_launch("g2048_keys_advance");

@@ -29,9 +29,8 @@
 
 #include "../../include/g2048.h"
 #include "g2048_board.h"
+#include "g2048_host.h"
 #include "g2048_rng.h"
-
-extern "C" void g2048_set_last_error_(const char *msg);
 
 namespace {
 
@@ -40,26 +39,6 @@ using namespace g2048;
 typedef float f4 __attribute__((ext_vector_type(4)));
 typedef unsigned u4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-int fail(int code, const char *msg)
-{
-    g2048_set_last_error_(msg);
-    return code;
-}
-
-int check_launch(const char *what)
-{
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        char buf[200];
-        snprintf(buf, sizeof buf, "%s: %s", what, hipGetErrorString(e));
-        g2048_set_last_error_(buf);
-        return G2048_ERR_HIP;
-    }
-    return G2048_OK;
-}
-
-inline bool aligned(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1u)) == 0; }
 
 // ------------------------------------------------------------------------------------------------ shapes and layouts --
 constexpr int kIn = 16, kH1 = 256, kH2 = 128, kH3 = 64, kOutPad = 16;
@@ -448,24 +427,11 @@ __global__ __launch_bounds__(64) void policy_play_kernel(
     }
 }
 
-template <bool BF16, int E>
-int launch_play(const dim3 &waves, hipStream_t s, unsigned long long *ticket, const unsigned char *W, uint4 *boards, uint32_t *score,
-                size_t n, uint64_t seed, uint64_t id_base, int max_moves, uint32_t mode, int32_t *moves, int32_t *valid, int32_t *invalid,
-                int4 *ms, double *reward, uint8_t *alive, uint8_t *actions)
+// the kernels' two instantiations: f(BF16, boards-of-16 per wavefront) with the constants of the precision asked for
+template <class F>
+auto with_precision(bool bf16, F &&f)
 {
-    hipLaunchKernelGGL((policy_play_kernel<BF16, E>), waves, dim3(64), 0, s, ticket, W, boards, score, n, seed, id_base, max_moves, mode,
-                       moves, valid, invalid, ms, reward, alive, actions);
-    return check_launch("g2048_play_policy_games");
-}
-
-template <bool BF16, int E>
-size_t resident_waves()
-{
-    int dev = 0, cus = 0, per_cu = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, policy_play_kernel<BF16, E>, 64, 0) != hipSuccess)
-        return 0;
-    return (size_t)cus * (size_t)per_cu;
+    return bf16 ? f(std::true_type{}, int_c<kTilesBF16>{}) : f(std::false_type{}, int_c<kTilesF32>{});
 }
 
 }  // namespace
@@ -489,10 +455,9 @@ int g2048_policy_pack(const float *plain_f32, int n_out, int precision, void *pa
     const size_t bytes = g2048_policy_packed_bytes(precision, n_out);
     const dim3 grid((unsigned)((bytes / 4 + 255) / 256));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (precision == G2048_POLICY_BF16)
-        hipLaunchKernelGGL(policy_pack_kernel<true>, grid, dim3(256), 0, s, plain_f32, n_out, static_cast<uint32_t *>(packed_out));
-    else
-        hipLaunchKernelGGL(policy_pack_kernel<false>, grid, dim3(256), 0, s, plain_f32, n_out, static_cast<uint32_t *>(packed_out));
+    with_bool(precision == G2048_POLICY_BF16, [&](auto BF16) {
+        hipLaunchKernelGGL(policy_pack_kernel<decltype(BF16)::value>, grid, dim3(256), 0, s, plain_f32, n_out, static_cast<uint32_t *>(packed_out));
+    });
     return check_launch("g2048_policy_pack");
 }
 
@@ -516,12 +481,10 @@ int g2048_policy_forward(const void *boards, const void *actor_packed, const voi
     const auto *b = static_cast<const uint32_t *>(boards);
     const auto *a = static_cast<const unsigned char *>(actor_packed);
     const auto *c = static_cast<const unsigned char *>(critic_packed_or_null);
-    if (bf16)
-        hipLaunchKernelGGL((policy_forward_kernel<true, kTilesBF16>), grid, dim3(64 * kWaves), 0, s, b, a, c,
+    with_precision(bf16, [&](auto BF16, auto E) {
+        hipLaunchKernelGGL((policy_forward_kernel<decltype(BF16)::value, decltype(E)::value>), grid, dim3(64 * kWaves), 0, s, b, a, c,
                            reinterpret_cast<float4 *>(probs_out), value_out_or_null, n);
-    else
-        hipLaunchKernelGGL((policy_forward_kernel<false, kTilesF32>), grid, dim3(64 * kWaves), 0, s, b, a, c,
-                           reinterpret_cast<float4 *>(probs_out), value_out_or_null, n);
+    });
     return check_launch("g2048_policy_forward");
 }
 
@@ -556,27 +519,26 @@ int g2048_play_policy_games(void *boards_inout, uint32_t *score_inout, const voi
     const bool bf16 = precision == G2048_POLICY_BF16;
     const size_t slots = 16 * (size_t)(bf16 ? kTilesBF16 : kTilesF32);
     // auto: as many wavefronts as the chip holds at once (every later one would only find the queue empty)
-    const size_t cap = max_waves ? (size_t)max_waves : bf16 ? resident_waves<true, kTilesBF16>() : resident_waves<false, kTilesF32>();
+    const size_t cap = max_waves ? (size_t)max_waves : (size_t)device_cus() * with_precision(bf16, [](auto BF16, auto E) {
+        return resident_per_cu(policy_play_kernel<decltype(BF16)::value, decltype(E)::value>, 64);
+    });
     if (cap == 0) return fail(G2048_ERR_HIP, "g2048_play_policy_games: no HIP device (occupancy query failed)");
     const size_t waves = std::min(std::min((n_games + slots - 1) / slots, cap), (size_t)0x7fffffffu);
     hipStream_t s = static_cast<hipStream_t>(stream);
     auto *ticket = static_cast<unsigned long long *>(workspace);
     hipError_t e = hipMemsetAsync(ticket, 0, sizeof *ticket, s);
     if (e == hipSuccess && actions_out_or_null) e = hipMemsetAsync(actions_out_or_null, 0xff, n_games * (size_t)max_moves, s);
-    if (e != hipSuccess) {
-        char buf[200];
-        snprintf(buf, sizeof buf, "g2048_play_policy_games: hipMemsetAsync: %s", hipGetErrorString(e));
-        return fail(G2048_ERR_HIP, buf);
-    }
+    if (const int rc = check_hip(e, "g2048_play_policy_games: hipMemsetAsync")) return rc;
     const dim3 grid((unsigned)waves);
     auto *b = static_cast<uint4 *>(boards_inout);
     const auto *w = static_cast<const unsigned char *>(actor_packed);
     auto *ms = reinterpret_cast<int4 *>(milestone_move_out);
-    if (bf16)
-        return launch_play<true, kTilesBF16>(grid, s, ticket, w, b, score_inout, n_games, seed, game_id_base, max_moves, mode, moves_out,
-                                             valid_out, invalid_out, ms, reward_sum_out_or_null, alive_out, actions_out_or_null);
-    return launch_play<false, kTilesF32>(grid, s, ticket, w, b, score_inout, n_games, seed, game_id_base, max_moves, mode, moves_out,
-                                         valid_out, invalid_out, ms, reward_sum_out_or_null, alive_out, actions_out_or_null);
+    with_precision(bf16, [&](auto BF16, auto E) {
+        hipLaunchKernelGGL((policy_play_kernel<decltype(BF16)::value, decltype(E)::value>), grid, dim3(64), 0, s, ticket, w, b, score_inout, n_games,
+                           seed, game_id_base, max_moves, mode, moves_out, valid_out, invalid_out, ms, reward_sum_out_or_null, alive_out,
+                           actions_out_or_null);
+    });
+    return check_launch("g2048_play_policy_games");
 }
 
 }  // extern "C"

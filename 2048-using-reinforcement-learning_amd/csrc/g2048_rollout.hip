@@ -20,33 +20,12 @@
 #include "../../include/g2048.h"
 #include "../../include/g2048_testing.h"
 #include "g2048_board.h"
+#include "g2048_host.h"
 #include "g2048_rng.h"
 
 using namespace g2048;
 
-extern "C" void g2048_set_last_error_(const char *msg);
-
 namespace {
-
-int fail(int code, const char *msg)
-{
-    g2048_set_last_error_(msg);
-    return code;
-}
-
-int check_launch(const char *what)
-{
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        char buf[200];
-        snprintf(buf, sizeof buf, "%s: %s", what, hipGetErrorString(e));
-        g2048_set_last_error_(buf);
-        return G2048_ERR_HIP;
-    }
-    return G2048_OK;
-}
-
-inline bool aligned(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1u)) == 0; }
 
 #include "g2048_step_table.h"
 
@@ -436,15 +415,15 @@ int g2048_rollout_step(const void *boards_in, const float *probs, const uint8_t 
     if (n == 0) return G2048_OK;
     if (!boards_in || !probs || !boards_out || !score_inout || !actions_out || !prob_out || !reward_out || !flags_out)
         return fail(G2048_ERR_ARG, "g2048_rollout_step: null pointer");
-    if (!aligned(boards_in, 16) || !aligned(boards_out, 16) || !aligned(probs, 16) || (next_boards_out_or_null && !aligned(next_boards_out_or_null, 16)))
+    if (!aligned(boards_in, 16) || !aligned(boards_out, 16) || !aligned(probs, 16) || !aligned(next_boards_out_or_null, 16))
         return fail(G2048_ERR_ARG, "g2048_rollout_step: board / probability arrays must be 16-byte aligned");
     const uint32_t kind = (opts >> G2048_ROLLOUT_OBS_SHIFT) & 3u;
     if ((opts & ~(G2048_STEP_REWARD_F64 | G2048_STEP_AUTO_RESET | (3u << G2048_ROLLOUT_OBS_SHIFT))) || kind > G2048_OBS_BF16)
         return fail(G2048_ERR_ARG, "g2048_rollout_step: unknown opts");
     if (!aligned(score_inout, 4) || !aligned(prob_out, 4) || !aligned(reward_out, (opts & G2048_STEP_REWARD_F64) ? 8 : 4) ||
-        (obs_next_out_or_null && !aligned(obs_next_out_or_null, 16)) || (step_counter_or_null && !aligned(step_counter_or_null, 8)))
+        !aligned(obs_next_out_or_null, 16) || !aligned(step_counter_or_null, 8))
         return fail(G2048_ERR_ARG, "g2048_rollout_step: misaligned array");
-    hipLaunchKernelGGL(rollout_step_kernel, dim3((unsigned)((n + kRolloutBlock - 1) / kRolloutBlock)), dim3(kRolloutBlock), 0,
+    hipLaunchKernelGGL(rollout_step_kernel, dim3(blocks_for(n, kRolloutBlock)), dim3(kRolloutBlock), 0,
                        static_cast<hipStream_t>(stream), n, static_cast<const uint4 *>(boards_in), reinterpret_cast<const float4 *>(probs),
                        score_inout, mask4_in_or_null, step_counter_or_null, seed, step_index, env_id_base,
                        static_cast<uint4 *>(boards_out), actions_out, prob_out, reward_out, flags_out,
@@ -466,21 +445,24 @@ int g2048_minibatch_gather(const void *obs, uint32_t obs_kind, const uint8_t *ac
     if (obs_kind > G2048_OBS_BF16) return fail(G2048_ERR_ARG, "g2048_minibatch_gather: unknown observation dtype");
     if (!aligned(obs, 16) || !aligned(next_boards, 16) || !aligned(states_out, 16) || !aligned(next_states_out, 16) ||
         !aligned(log_probs, 4) || !aligned(rewards, rewards_f64 ? 8 : 4) || !aligned(actions_out, 8) || !aligned(old_log_probs_out, 4) ||
-        !aligned(rewards_out, 4) || !aligned(dones_out, 4) || (indices_out_or_null && !aligned(indices_out_or_null, 8)))
+        !aligned(rewards_out, 4) || !aligned(dones_out, 4) || !aligned(indices_out_or_null, 8))
         return fail(G2048_ERR_ARG, "g2048_minibatch_gather: misaligned array");
     const uint32_t half_bits = minibatch_half_bits((uint64_t)n_transitions);
     const Keys k = rng_keys(seed, DOM_MINIBATCH, sample_index);
     if (batch > ((size_t)1 << 36)) return fail(G2048_ERR_ARG, "g2048_minibatch_gather: batch too large for one launch");
-    const dim3 grid((unsigned)((batch * 4u + 255u) / 256u));
-#define G2048_LAUNCH_MB(K, F) hipLaunchKernelGGL((minibatch_kernel<K, F>), grid, dim3(256), 0, static_cast<hipStream_t>(stream), obs, actions, \
-                              log_probs, rewards, static_cast<const uint32_t *>(next_boards), flags, (uint64_t)n_transitions, (uint64_t)batch, \
-                              half_bits, k.k0, k.k1, reinterpret_cast<float4 *>(states_out), reinterpret_cast<long long *>(actions_out), \
-                              old_log_probs_out, rewards_out, reinterpret_cast<float4 *>(next_states_out), dones_out, \
-                              reinterpret_cast<long long *>(indices_out_or_null))
-    if (obs_kind == G2048_OBS_F32) { if (rewards_f64) G2048_LAUNCH_MB(0, true); else G2048_LAUNCH_MB(0, false); }
-    else if (obs_kind == G2048_OBS_F16) { if (rewards_f64) G2048_LAUNCH_MB(1, true); else G2048_LAUNCH_MB(1, false); }
-    else { if (rewards_f64) G2048_LAUNCH_MB(2, true); else G2048_LAUNCH_MB(2, false); }
-#undef G2048_LAUNCH_MB
+    const dim3 grid(blocks_for(batch * 4u, 256));
+    const auto launch = [&](auto K) {
+        with_bool(rewards_f64 != 0u, [&](auto F) {
+            hipLaunchKernelGGL((minibatch_kernel<decltype(K)::value, decltype(F)::value>), grid, dim3(256), 0, static_cast<hipStream_t>(stream), obs,
+                               actions, log_probs, rewards, static_cast<const uint32_t *>(next_boards), flags, (uint64_t)n_transitions,
+                               (uint64_t)batch, half_bits, k.k0, k.k1, reinterpret_cast<float4 *>(states_out),
+                               reinterpret_cast<long long *>(actions_out), old_log_probs_out, rewards_out,
+                               reinterpret_cast<float4 *>(next_states_out), dones_out, reinterpret_cast<long long *>(indices_out_or_null));
+        });
+    };
+    if (obs_kind == G2048_OBS_F32) launch(int_c<0>{});
+    else if (obs_kind == G2048_OBS_F16) launch(int_c<1>{});
+    else launch(int_c<2>{});
     return check_launch("g2048_minibatch_gather");
 }
 
@@ -511,7 +493,7 @@ int g2048_seen_insert(const void *next_boards, uint64_t index_base, void *table,
     if (!aligned(next_boards, 16) || !aligned(table, 16) || !aligned(count_inout, 8) || !aligned(slot_out, 4) || !aligned(overflow_flag, 4))
         return fail(G2048_ERR_ARG, "g2048_seen_insert: misaligned array");
     if (capacity_log2 < 4 || capacity_log2 > 31) return fail(G2048_ERR_ARG, "g2048_seen_insert: capacity_log2 must be in 4..31");
-    hipLaunchKernelGGL(seen_insert_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
+    hipLaunchKernelGGL(seen_insert_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
                        static_cast<const uint4 *>(next_boards), (unsigned long long)index_base, static_cast<SeenSlot *>(table),
                        (uint32_t)((1ull << capacity_log2) - 1ull), count_inout, overflow_flag, slot_out, n);
     return check_launch("g2048_seen_insert");
@@ -525,7 +507,7 @@ int g2048_seen_rehash(const void *old_table, uint32_t old_capacity_log2, void *n
         return fail(G2048_ERR_ARG, "g2048_seen_rehash: bad capacities");
     if (!aligned(old_table, 16) || !aligned(new_table, 16)) return fail(G2048_ERR_ARG, "g2048_seen_rehash: misaligned table");
     const size_t slots = (size_t)1 << old_capacity_log2;
-    hipLaunchKernelGGL(seen_rehash_kernel, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
+    hipLaunchKernelGGL(seen_rehash_kernel, dim3(blocks_for(slots, 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
                        static_cast<const SeenSlot *>(old_table), slots, static_cast<SeenSlot *>(new_table),
                        (uint32_t)((1ull << new_capacity_log2) - 1ull), overflow_flag);
     return check_launch("g2048_seen_rehash");
@@ -540,7 +522,7 @@ int g2048_shaping_apply(const void *next_boards, const uint8_t *state_maxcode, c
         return fail(G2048_ERR_ARG, "g2048_shaping_apply: null pointer");
     if (!aligned(next_boards, 16) || !aligned(table, 16) || !aligned(env_reward, 8) || !aligned(shaped_out, 8) || !aligned(slots, 4))
         return fail(G2048_ERR_ARG, "g2048_shaping_apply: misaligned array");
-    hipLaunchKernelGGL(shaping_apply_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
+    hipLaunchKernelGGL(shaping_apply_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
                        static_cast<const uint4 *>(next_boards), state_maxcode, flags, env_reward, prev_highest,
                        static_cast<const SeenSlot *>(table), slots, (unsigned long long)index_base, shaped_out, novel_out_or_null, n);
     return check_launch("g2048_shaping_apply");

@@ -1,6 +1,6 @@
 """Builds csrc/libg2048_hip.so for gfx950 with hipcc (cross-compiles without a GPU).
 
-    python -m g2048._build            (from the package directory)
+    python -m g2048._build [-o LIBRARY] [extra compiler flags ...]           (from the package directory)
 
 The library is built in-tree so that it travels with the source snapshot; it is
 git-ignored. -ffp-contract=off is REQUIRED: the reward / heuristic kernels follow
@@ -33,17 +33,22 @@ def needs_build():
     return any(os.path.exists(d) and os.path.getmtime(d) > t for d in deps)
 
 
-def build(force=False, verbose=False):
-    if not force and not needs_build():
+def build(force=False, verbose=False, lib=None, extra_flags=()):
+    """lib / extra_flags: A/B and measurement builds next to the product's (tools/build_ab.sh); such a build is always made."""
+    if lib is None and not force and not needs_build():
         return LIB
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     srcs = [os.path.join(CSRC, f) for f in SOURCES if os.path.exists(os.path.join(CSRC, f))]
-    cmd = [hipcc] + FLAGS + ["-o", LIB] + srcs
+    cmd = [hipcc] + FLAGS + list(extra_flags) + ["-o", lib or LIB] + srcs
     if verbose:
         print(" ".join(cmd))
     subprocess.check_call(cmd)
-    return LIB
+    return lib or LIB
 
 
-if __name__ == "__main__":
-    print(build(force=True, verbose=True))
+if __name__ == "__main__":          # [-o LIBRARY] [extra compiler flags ...]
+    import sys
+    out, args = None, sys.argv[1:]
+    if args[:1] == ["-o"]:
+        out, args = args[1], args[2:]
+    print(build(force=True, verbose=True, lib=out, extra_flags=args))

@@ -1,0 +1,80 @@
+#!/usr/bin/env python3
+"""(host) Is the device code of two builds of the library the same?   python tools/device_code_diff.py A.so B.so
+
+Unbundles both with `llvm-objdump --offloading` and compares, per gfx950 code object (one per .hip file, in link order), the set
+of kernels and the bytes of .text and .rodata (the kernel descriptors live there). Where a whole section differs -- e.g. the
+same kernels emitted in another order -- every kernel is compared on its own: the function's bytes and its 64-byte descriptor
+`<kernel>.kd`; the ones that differ are printed. Exit status 0 only if everything matches. What a host-side refactor has to show."""
+import glob
+import os
+import shutil
+import struct
+import subprocess
+import sys
+import tempfile
+
+
+def code_objects(lib, tmp):
+    """The gfx950 code objects of `lib` as bytes, in bundle order (llvm-objdump writes them next to the file it reads)."""
+    objdump = shutil.which("llvm-objdump") or os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "lib", "llvm", "bin", "llvm-objdump")
+    os.makedirs(tmp)
+    copy = shutil.copy(lib, tmp)
+    subprocess.check_call([objdump, "--offloading", os.path.basename(copy)], cwd=tmp, stdout=subprocess.DEVNULL)
+    found = glob.glob(copy + ".*gfx950*")
+    return [open(f, "rb").read() for f in sorted(found, key=lambda f: int(f[len(copy) + 1:].split(".")[0]))]
+
+
+def parse(elf):
+    """(sections {name: (addr, bytes)}, symbols {name: (section name, value, size)}) of a little-endian ELF64 image."""
+    shoff, = struct.unpack_from("<Q", elf, 0x28)
+    shentsize, shnum, shstrndx = struct.unpack_from("<HHH", elf, 0x3A)
+    heads = [struct.unpack_from("<IIQQQQIIQQ", elf, shoff + i * shentsize) for i in range(shnum)]
+    cstr = lambda table, at: table[at:table.index(b"\0", at)].decode()
+    body = lambda h: b"" if h[1] == 8 else elf[h[4]:h[4] + h[5]]            # SHT_NOBITS holds no bytes
+    names = [cstr(body(heads[shstrndx]), h[0]) for h in heads]
+    sections = {n: (h[3], body(h)) for n, h in zip(names, heads)}
+    symbols = {}
+    symtab = next(h for h in heads if h[1] == 2)                               # SHT_SYMTAB; its sh_link is the string table
+    strtab = body(heads[symtab[6]])
+    for at in range(0, symtab[5], 24):
+        name, _, _, shndx, value, size = struct.unpack_from("<IBBHQQ", body(symtab), at)
+        if 0 < shndx < shnum:
+            symbols[cstr(strtab, name)] = (names[shndx], value, size)
+    return sections, symbols
+
+
+def symbol_bytes(sections, symbols, name):
+    sec, value, size = symbols[name]
+    addr, data = sections[sec]
+    return data[value - addr:value - addr + size]
+
+
+def main(a, b):
+    with tempfile.TemporaryDirectory() as tmp:
+        objs_a, objs_b = code_objects(a, os.path.join(tmp, "a")), code_objects(b, os.path.join(tmp, "b"))
+    same = len(objs_a) == len(objs_b) and len(objs_a) > 0
+    print("%s: %d gfx950 code objects; %s: %d" % (a, len(objs_a), b, len(objs_b)))
+    for i, (ea, eb) in enumerate(zip(objs_a, objs_b)):
+        (sec_a, sym_a), (sec_b, sym_b) = parse(ea), parse(eb)
+        kern_a, kern_b = ({s[:-3] for s in sym if s.endswith(".kd")} for sym in (sym_a, sym_b))
+        whole = {s: sec_a.get(s, (0, b""))[1] == sec_b.get(s, (0, b""))[1] for s in (".text", ".rodata")}
+        print("code object %d: %d kernels; " % (i, len(kern_a)) + "; ".join(
+            "%s %d bytes %s" % (s, len(sec_a.get(s, (0, b""))[1]), "identical" if ok else "DIFFERS") for s, ok in whole.items()))
+        if kern_a != kern_b:
+            same = False
+            print("  kernels only in %s: %s\n  kernels only in %s: %s" % (a, sorted(kern_a - kern_b), b, sorted(kern_b - kern_a)))
+        if not all(whole.values()):
+            differ = [k for k in sorted(kern_a & kern_b)
+                      if any(symbol_bytes(sec_a, sym_a, s) != symbol_bytes(sec_b, sym_b, s) for s in (k, k + ".kd"))]
+            print("  per kernel (function bytes + descriptor): %d of %d differ" % (len(differ), len(kern_a & kern_b)))
+            for k in differ:
+                same = False
+                print("    " + k)
+    print("device code: " + ("IDENTICAL" if same else "DIFFERENT"))
+    return 0 if same else 1
+
+
+if __name__ == "__main__":
+    if len(sys.argv) != 3:
+        sys.exit(__doc__)
+    sys.exit(main(sys.argv[1], sys.argv[2]))
