@@ -1,5 +1,5 @@
 // g2048_host.h -- the host side every entry point of the C-ABI shares: one error string, one way to check arguments and HIP
-// calls, one way to pick a kernel instantiation from run-time values. Host code only, included by the library's four .hip
+// calls, one way to pick a kernel instantiation from run-time values. Host code only, included by the library's .hip
 // files and nothing else. An entry point reads: checks (fail / aligned), launch (with_* where the kernel is a template),
 // return check_launch("<its name>").
 #pragma once

@@ -461,6 +461,63 @@ def policy_forward(boards, actor_packed, critic_packed=None, precision="f32", pr
     return probs if critic_packed is None else (probs, value)
 
 
+def tpolicy_plain_floats(dim_ff, n_layers):
+    """Floats of the plain parameter buffer g2048_tpolicy_pack reads (include/g2048.h)."""
+    return 128 + int(n_layers) * (16962 + 129 * int(dim_ff)) + 139781
+
+
+def tpolicy_packed_bytes(precision="f32", dim_ff=2048, n_layers=2):
+    """Bytes of the packed transformer policy (g2048_tpolicy_packed_bytes)."""
+    if precision not in POLICY_PRECISIONS:
+        raise ValueError("g2048: precision must be 'f32' or 'bf16'")
+    nb = L.lib().g2048_tpolicy_packed_bytes(POLICY_PRECISIONS[precision], int(dim_ff), int(n_layers))
+    if nb == 0:
+        raise ValueError("g2048: dim_ff must be a multiple of 32 and n_layers at least 1")
+    return nb
+
+
+def tpolicy_pack(plain, dim_ff, n_layers, precision="f32", out=None):
+    """Pack the transformer policy's plain float32 parameters (state-dict order plus the two LayerNorm eps per layer:
+    include/g2048.h) into the blob g2048_tpolicy_forward streams. Writes `out` (uint8, tpolicy_packed_bytes) in place when
+    given, on the current stream, without synchronising."""
+    L.require_device_tensor(plain, torch.float32, None, "plain")
+    nb = tpolicy_packed_bytes(precision, dim_ff, n_layers)
+    if plain.dim() != 1 or plain.numel() != tpolicy_plain_floats(dim_ff, n_layers):
+        raise ValueError("g2048: plain must be a flat float32 tensor of %d parameters" % tpolicy_plain_floats(dim_ff, n_layers))
+    if out is None:
+        out = torch.empty(nb, dtype=torch.uint8, device=plain.device)
+    L.require_device_tensor(out, torch.uint8, None, "out")
+    if out.numel() != nb:
+        raise ValueError("g2048: out must hold %d bytes" % nb)
+    L.call(plain.device, L.lib().g2048_tpolicy_pack, plain.data_ptr(), int(dim_ff), int(n_layers), POLICY_PRECISIONS[precision],
+           out.data_ptr(), L.stream_ptr(plain.device))
+    return out
+
+
+def tpolicy_forward(boards, packed, dim_ff, n_layers, precision="f32", probs=None, value=None, want_value=True):
+    """The transformer policy's forward pass on the packed boards in ONE launch (g2048_tpolicy_forward). Returns (probs
+    float32 (n,4), value float32 (n,1)), or probs alone with want_value=False."""
+    L.require_device_tensor(boards, torch.uint8, (16,), "boards")
+    L.require_device_tensor(packed, torch.uint8, None, "packed")
+    if packed.numel() != tpolicy_packed_bytes(precision, dim_ff, n_layers):
+        raise ValueError("g2048: packed must be a %s blob of %d bytes" % (precision, tpolicy_packed_bytes(precision, dim_ff, n_layers)))
+    n, dev = boards.shape[0], boards.device
+    if probs is None:
+        probs = torch.empty((n, 4), dtype=torch.float32, device=dev)
+    L.require_device_tensor(probs, torch.float32, (4,), "probs")
+    if probs.shape[0] != n:
+        raise ValueError("g2048: probs must have n rows")
+    if want_value and value is None:
+        value = torch.empty((n, 1), dtype=torch.float32, device=dev)
+    if value is not None:
+        L.require_device_tensor(value, torch.float32, (1,), "value")
+        if value.shape[0] != n:
+            raise ValueError("g2048: value must have n rows")
+    L.call(dev, L.lib().g2048_tpolicy_forward, boards.data_ptr(), packed.data_ptr(), probs.data_ptr(),
+           value.data_ptr() if value is not None else None, n, int(dim_ff), int(n_layers), POLICY_PRECISIONS[precision], L.stream_ptr(dev))
+    return probs if value is None else (probs, value)
+
+
 class SeenStates:
     """The `seen_states` set and `highest_tile_seen` of PPOAgent (agents/ppo_agent.py:171-176) for ordered batches of
     transitions, resident on the GPU: an open-addressing hash set keyed by the 16-byte board (include/g2048.h,

@@ -6,7 +6,8 @@ the `PPOMemory` deque and its per-sample Python loops (agents/ppo_agent.py:14-59
 in HBM as (T, N, ...) tensors; nothing crosses PCIe during collection. The policy is any torch module
 mapping float32 (N, 16) observations to action probabilities (N, 4) -- or (probs, value) like the
 reference's `TransformerModel` (models/transformer.py) -- and stays stock PyTorch-ROCm: it is the consumer; or a
-`g2048.DevicePolicy` (takes_boards = True), the reference's MLP actor / critic as one HIP launch on the boards.
+`g2048.DevicePolicy` (takes_boards = True), the reference's MLP actor / critic as one HIP launch on the boards; or a
+`g2048.DeviceTransformerPolicy` (takes_boards = True), that `TransformerModel` as one HIP launch on the boards.
 """
 import warnings
 
@@ -95,7 +96,7 @@ class RolloutCollector:
 
     # -- one env step, fused (1 g2048 launch) or reference-style (obs / mask / sample / step launches) --------------------
     def _policy(self, t):
-        # a policy that declares takes_boards (g2048.DevicePolicy) reads the packed boards obs[t] was encoded from
+        # a policy that declares takes_boards (g2048.DevicePolicy, g2048.DeviceTransformerPolicy) reads the packed boards obs[t] was encoded from
         out = self.policy(self.env.boards if getattr(self.policy, "takes_boards", False) else self._obs[t])
         probs, value = out if isinstance(out, (tuple, list)) else (out, None)
         if value is not None:

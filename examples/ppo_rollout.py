@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Collect a PPO rollout (BASELINE config 4: 65,536 envs x 128 steps) entirely on the GPU.
 
-    python examples/ppo_rollout.py [--envs 65536] [--steps 128] [--policy torch|device-f32|device-bf16]
+    python examples/ppo_rollout.py [--envs 65536] [--steps 128] [--policy torch|device-f32|device-bf16|transformer|transformer-bf16]
 
 The policy is any torch module mapping float32 (N,16) observations to action probabilities (N,4) -- or
 (probs, value); here a small MLP. Everything between the policy's outputs and its next inputs (masked sampling,
@@ -10,7 +10,9 @@ Then one reference-style update: `RolloutCollector.sample(batch)` is PPOMemory.s
 PPOAgent.update (agents/ppo_agent.py:21-50, :342-354) as ONE gather launch on the device, and the loss below is the
 reference's (:356-400) on stock torch modules -- the learner stays the unchanged consumer.
 --policy device-f32 / device-bf16 runs the same modules' forward pass as one HIP launch on the boards (g2048.DevicePolicy)
-during collection; after the update, refresh() re-packs the weights in place and the captured rollout replays with them."""
+during collection; after the update, refresh() re-packs the weights in place and the captured rollout replays with them.
+--policy transformer / transformer-bf16 swaps the MLP for the reference's transformer (models/transformer.py's structure: 16
+tokens, d_model 64, 4 heads, 2 layers) and runs its forward pass as one HIP launch (g2048.DeviceTransformerPolicy, f32 / bf16)."""
 import argparse
 import os
 import sys
@@ -27,7 +29,8 @@ ap.add_argument("--envs", type=int, default=65536)
 ap.add_argument("--steps", type=int, default=128)
 ap.add_argument("--batch", type=int, default=4096)
 ap.add_argument("--epochs", type=int, default=4)
-ap.add_argument("--policy", choices=("torch", "device-f32", "device-bf16"), default="torch")
+ap.add_argument("--policy", choices=("torch", "device-f32", "device-bf16", "transformer", "transformer-bf16"), default="torch")
+ap.add_argument("--dim-ff", type=int, default=128, help="feed-forward width of the transformer (the reference's default is 2048)")
 a = ap.parse_args()
 
 
@@ -42,9 +45,25 @@ class ActorCritic(nn.Module):
         return torch.softmax(self.pi(h), -1), self.v(h)
 
 
-net = ActorCritic().cuda().eval()
+class TransformerActorCritic(nn.Module):
+    def __init__(self, dim_ff):
+        super().__init__()
+        self.embedding = nn.Linear(1, 64)
+        self.encoder = nn.TransformerEncoder(nn.TransformerEncoderLayer(64, 4, dim_ff, batch_first=True), 2)
+        self.fc1, self.fc2 = nn.Linear(1024, 128), nn.Linear(128, 64)
+        self.pi, self.v = nn.Linear(64, 4), nn.Linear(64, 1)
+
+    def forward(self, x):
+        h = self.encoder(self.embedding(x.view(x.shape[0], 16, 1))).reshape(x.shape[0], -1)
+        h = torch.relu(self.fc2(torch.relu(self.fc1(h))))
+        return torch.softmax(self.pi(h), -1), self.v(h)
+
+
+net = (TransformerActorCritic(a.dim_ff) if a.policy.startswith("transformer") else ActorCritic()).cuda().eval()
 policy = net
-if a.policy != "torch":     # the same modules, 16-256-128-64-{4|1}: actor = body + pi, critic = body + v
+if a.policy.startswith("transformer"):      # recognised by structure: one TransformerEncoder and five Linears told apart by shape
+    policy = g2048.DeviceTransformerPolicy(net, precision="bf16" if a.policy.endswith("bf16") else "f32")
+elif a.policy != "torch":     # the same modules, 16-256-128-64-{4|1}: actor = body + pi, critic = body + v
     policy = g2048.DevicePolicy(nn.Sequential(net.body, net.pi).eval(), nn.Sequential(net.body, net.v).eval(),
                                 precision=a.policy[len("device-"):])
 rc = g2048.RolloutCollector(a.envs, a.steps, policy, seed=1, shaping=True)

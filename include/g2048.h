@@ -48,7 +48,7 @@ extern "C" {
 #define G2048_ABI_VERSION 5        /* 5: round 5, second half (ops MOVE / SPAWN / MOVE_AGENT of g2048_env_step; g2048_eval kinds CORNER_BONUS and
                                       MERGE_POTENTIAL; no entry point added or removed;
                                       later, additive: g2048_policy_packed_bytes / _pack / _forward,
-                                      g2048_play_policy_games / _workspace)
+                                      g2048_play_policy_games / _workspace, g2048_tpolicy_packed_bytes / _pack / _forward)
                                       4: round 5 (export table = this header + g2048_testing.h exactly: test / measurement hooks moved there,
                                       internal symbols hidden; g2048_replay_games also clamps a game's length to actions_stride)
                                       3: round 4 (actions_out of the g2048_play_games family, g2048_replay_games, g2048_env_step,
@@ -444,6 +444,40 @@ G2048_API size_t g2048_policy_packed_bytes(int precision, int n_out);
 G2048_API int g2048_policy_pack(const float *plain_f32, int n_out, int precision, void *packed_out, void *stream);
 G2048_API int g2048_policy_forward(const void *boards, const void *actor_packed, const void *critic_packed_or_null, float *probs_out,
                          float *value_out_or_null, size_t n, uint32_t opts, void *stream);
+
+/* Forward pass of the reference's transformer policy (models/transformer.py:4-40, TransformerModel in eval mode) on the matrix
+ * cores, in ONE launch, read from the packed boards (token t of a board = float32(code of cell t) / float32(15)):
+ * Linear(1,64) -> n_layers x nn.TransformerEncoderLayer(d_model 64, 4 heads, dim_ff, ReLU, post-norm, batch_first: x =
+ * norm1(x + out_proj(attention(x))), x = norm2(x + linear2(relu(linear1(x)))), scores scaled by 1/4, no mask) -> flatten
+ * (token-major, 1024) -> Linear(1024,128) + ReLU -> Linear(128,64) + ReLU -> Linear(64,4) + softmax (probs) and Linear(64,1)
+ * (value). d_model, the head count and the 16 tokens are fixed; dim_ff (a multiple of 32) and n_layers (>= 1) are arguments.
+ *
+ *   g2048_tpolicy_packed_bytes  bytes of the packed blob (0 for a bad argument); a multiple of 16.
+ *   g2048_tpolicy_pack          rearranges the plain f32 parameters into that blob, on `stream` (no synchronisation; packing
+ *                               into the same buffer again updates a forward pass captured in a graph). plain_f32 holds, back
+ *                               to back in the module's state-dict order, every weight row-major [out][in] as torch stores it:
+ *                                 embedding.weight [64][1], embedding.bias [64];
+ *                                 per layer: in_proj_weight [192][64] (q, k, v rows), in_proj_bias [192], out_proj.weight
+ *                                   [64][64], out_proj.bias [64], linear1.weight [dim_ff][64], linear1.bias [dim_ff],
+ *                                   linear2.weight [64][dim_ff], linear2.bias [64], norm1.weight [64], norm1.bias [64],
+ *                                   norm2.weight [64], norm2.bias [64], then norm1.eps, norm2.eps (two floats, not in the
+ *                                   state dict): 16,962 + 129 dim_ff floats;
+ *                                 fc1.weight [128][1024], fc1.bias [128], fc2.weight [64][128], fc2.bias [64], actor.weight
+ *                                   [4][64], actor.bias [4], critic.weight [1][64], critic.bias [1]: 139,781 floats.
+ *   g2048_tpolicy_forward       probs_out[i] (float32 n x 4) and, if value_out_or_null is given, value_out_or_null[i] of
+ *                               board i. opts = the precision the blob was packed with:
+ *                                 G2048_POLICY_F32   f32 MFMA, exact f32 products and sums (the parity path);
+ *                                 G2048_POLICY_BF16  the weights and the matmul inputs of the projections, the feed-forward
+ *                                                    and the head layers rounded to bf16 (nearest even), f32 accumulation; the
+ *                                                    attention products (Q K^T, P V) stay on the f32 MFMA.
+ *                               LayerNorm statistics (biased variance), both softmaxes, the biases and the residual adds are
+ *                               f32 in both. Boards, blob and probs_out 16-byte aligned, value_out 4-byte aligned. Every output
+ *                               is one fixed-order accumulation (no split-K, no atomics) that does not depend on n or on the
+ *                               board's place in the batch. Nothing past row n is written. */
+G2048_API size_t g2048_tpolicy_packed_bytes(int precision, int dim_ff, int n_layers);
+G2048_API int g2048_tpolicy_pack(const float *plain_f32, int dim_ff, int n_layers, int precision, void *packed_out, void *stream);
+G2048_API int g2048_tpolicy_forward(const void *boards, const void *packed, float *probs_out, float *value_out_or_null, size_t n,
+                          int dim_ff, int n_layers, uint32_t opts, void *stream);
 
 /* Complete games of the PPO actor (play.py:44-68, train.py:54-90), every game played to the end on the device in ONE launch,
  * as g2048_play_games does for the beam agent. Game g (global id game_id_base + g) starts from boards_inout[g] /
