@@ -6,6 +6,9 @@
 //   tpolicy_pack_params_kernel  the embedding, every bias, the LayerNorm weights and their eps into the blob's f32 section.
 //   tpolicy_forward_kernel      Linear(1,64) -> L x TransformerEncoderLayer(64, 4 heads, dim_ff, relu, post-norm) -> flatten ->
 //                               Linear(1024,128)+ReLU -> Linear(128,64)+ReLU -> {Linear(64,4)+softmax | Linear(64,1)}.
+//   tpolicy_play_kernel         complete games of that policy: the same forward for a block's 16 game slots, then sampling, the
+//                               env step and the bookkeeping per slot, slots refilled from a ticket counter
+//                               (g2048_play_tpolicy_games).
 //
 // Layout of the computation. A block of four wavefronts owns 16 boards, a wavefront four of them. In the encoder a board is one
 // MFMA column tile: tokens are the N dimension, and the activation x is held transposed as 16-feature row tiles, register r of
@@ -30,8 +33,12 @@
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 
+#include <algorithm>
+
 #include "../../include/g2048.h"
+#include "g2048_board.h"
 #include "g2048_host.h"
+#include "g2048_rng.h"
 
 namespace {
 
@@ -273,6 +280,168 @@ __device__ inline void dense_lds(const unsigned char *mat, int o, int lane, cons
     out = acc[0];
 }
 
+// The forward pass in three pieces that tpolicy_forward_kernel and the game-playing kernel (tpolicy_play_kernel, below) share.
+// Both expand exactly this text, and a board's outputs do not depend on the column, the tile or the block it sits in, so the
+// two kernels give bit-identical probabilities for the same board and blob. Macros, not functions, for the reason
+// POLICY_LAYERS_ of g2048_policy.hip is one: expanded in place, the forward kernel's code object is byte for byte what it was
+// before the pieces were named (profiles/r09_tpolicy_device_code_diff.txt). They use the kernel's names: W, P, lay, ff, layers,
+// lds, lane, wave, g, col.
+//   TPOLICY_ENCODER_  embedding and the encoder layers in registers, then the wavefront's four boards to lds[board][token][feature];
+//   TPOLICY_DENSE_    barrier, fc1, fc2 through LDS, barrier (every wavefront must reach it);
+//   TPOLICY_HEADS_    the head tile z (wavefront 0 only): lanes 0..15 hold the logits of board `col`, lanes 16..31 the value.
+#define TPOLICY_ENCODER_(BF16, CODE) \
+    /* embedding: x[f][token] = w[f] * (code / 15) + b[f]; CODE = the code of cell `col` of the wavefront's board e */ \
+    f4 x[kE][4]; \
+    { \
+        f4 ew[4], eb[4]; \
+_Pragma("unroll") \
+        for (int t = 0; t < 4; ++t) { \
+            ew[t] = load_f4(P + 16 * t + 4 * g); \
+            eb[t] = load_f4(P + kD + 16 * t + 4 * g); \
+        } \
+_Pragma("unroll") \
+        for (int e = 0; e < kE; ++e) { \
+            const float v = (float)(CODE) / 15.0f; \
+_Pragma("unroll") \
+            for (int t = 0; t < 4; ++t) x[e][t] = ew[t] * splat(v) + eb[t]; \
+        } \
+    } \
+ \
+_Pragma("unroll 1") \
+    for (int l = 0; l < layers; ++l) { \
+        const unsigned char *Wl = W + (size_t)l * lay.layer_frags() * kFrag; \
+        const float *Pl = P + 2 * kD + l * lay.layer_params(); \
+        const float *in_b = Pl, *out_b = Pl + 3 * kD, *b1 = Pl + 4 * kD, *b2 = b1 + ff, *norms = b2 + kD; \
+ \
+        /* self-attention, head by head; attn[e][h] = row tile h of the concatenated heads */ \
+        f4 attn[kE][4]; \
+_Pragma("unroll") \
+        for (int h = 0; h < kHeads; ++h) { \
+            f4 q[kE], k[kE], vt[kE]; \
+            const f4 qb = load_f4(in_b + 16 * h + 4 * g), kb = load_f4(in_b + kD + 16 * h + 4 * g); \
+            const f4 vb = splat(in_b[2 * kD + 16 * h + col]); \
+_Pragma("unroll") \
+            for (int e = 0; e < kE; ++e) { q[e] = qb; k[e] = kb; vt[e] = vb; } \
+            project64<BF16>(Wl, h, lane, x, q); \
+            project64<BF16>(Wl, 4 + h, lane, x, k); \
+            project64<BF16, true>(Wl, 8 + h, lane, x, vt); \
+_Pragma("unroll") \
+            for (int e = 0; e < kE; ++e) { \
+                f4 s = splat(0.0f); \
+_Pragma("unroll") \
+                for (int r = 0; r < 4; ++r) s = __builtin_amdgcn_mfma_f32_16x16x4f32(k[e][r], q[e][r], s, 0, 0, 0); \
+                s = s * splat(0.25f);  /* 1 / sqrt(head_dim) */ \
+                const float m = lanes_max(fmaxf(fmaxf(s[0], s[1]), fmaxf(s[2], s[3]))); \
+                f4 p{expf(s[0] - m), expf(s[1] - m), expf(s[2] - m), expf(s[3] - m)}; \
+                const float sum = lanes_sum((p[0] + p[1]) + (p[2] + p[3])); \
+                p = p / splat(sum); \
+                f4 o = splat(0.0f); \
+_Pragma("unroll") \
+                for (int r = 0; r < 4; ++r) o = __builtin_amdgcn_mfma_f32_16x16x4f32(vt[e][r], p[r], o, 0, 0, 0); \
+                attn[e][h] = o; \
+            } \
+        } \
+ \
+        /* x = norm1(x + out_proj(attn)) */ \
+        { \
+            f4 y[kE][4]; \
+_Pragma("unroll") \
+            for (int o = 0; o < 4; ++o) { \
+                f4 acc[kE]; \
+                const f4 b = load_f4(out_b + 16 * o + 4 * g); \
+_Pragma("unroll") \
+                for (int e = 0; e < kE; ++e) acc[e] = b; \
+                project64<BF16>(Wl + lay.out_proj() * kFrag, o, lane, attn, acc); \
+_Pragma("unroll") \
+                for (int e = 0; e < kE; ++e) y[e][o] = acc[e]; \
+            } \
+            add_norm(x, y, norms, norms[4 * kD], g); \
+        } \
+ \
+        /* x = norm2(x + W2 relu(W1 x + b1) + b2), 32 features of the hidden layer at a time */ \
+        { \
+            const unsigned char *W1 = Wl + lay.w1() * kFrag, *W2 = Wl + lay.w2() * kFrag; \
+            constexpr int CPS = BF16 ? 1 : 2;  /* W2 chunks per 32-feature slice */ \
+            const int c2 = ff / (32 / CPS);  /* W2 chunks per row tile */ \
+            f4 y[kE][4]; \
+_Pragma("unroll") \
+            for (int o = 0; o < 4; ++o) { \
+                const f4 b = load_f4(b2 + 16 * o + 4 * g); \
+_Pragma("unroll") \
+                for (int e = 0; e < kE; ++e) y[e][o] = b; \
+            } \
+_Pragma("unroll 1") \
+            for (int s = 0; s < ff / 32; ++s) { \
+                f4 h1[kE][2]; \
+_Pragma("unroll") \
+                for (int t = 0; t < 2; ++t) { \
+                    f4 acc[kE]; \
+                    const f4 b = load_f4(b1 + 32 * s + 16 * t + 4 * g); \
+_Pragma("unroll") \
+                    for (int e = 0; e < kE; ++e) acc[e] = b; \
+                    project64<BF16>(W1, 2 * s + t, lane, x, acc); \
+_Pragma("unroll") \
+                    for (int e = 0; e < kE; ++e) h1[e][t] = relu(acc[e]); \
+                } \
+_Pragma("unroll") \
+                for (int t = 0; t < CPS; ++t) { \
+                    const int c = CPS * s + t; \
+_Pragma("unroll") \
+                    for (int o = 0; o < 4; ++o) { \
+                        f4 in[kE][2], acc[kE]; \
+_Pragma("unroll") \
+                        for (int e = 0; e < kE; ++e) { \
+                            in[e][0] = h1[e][t]; \
+                            in[e][1] = h1[e][1]; \
+                            acc[e] = y[e][o]; \
+                        } \
+                        chunk_mma<BF16, kE>(W2 + ((size_t)(o * c2 + c) * 64 + lane) * 16, in, acc); \
+_Pragma("unroll") \
+                        for (int e = 0; e < kE; ++e) y[e][o] = acc[e]; \
+                    } \
+                } \
+            } \
+            add_norm(x, y, norms + 2 * kD, norms[4 * kD + 1], g); \
+        } \
+    } \
+ \
+    /* flatten: lds[board][token][feature] (the block's 16 boards) */ \
+_Pragma("unroll") \
+    for (int e = 0; e < kE; ++e) \
+_Pragma("unroll") \
+        for (int t = 0; t < 4; ++t) \
+            *reinterpret_cast<f4 *>(lds + (kE * wave + e) * kBoardStride + col * kTokStride + 16 * t + 4 * g) = x[e][t];
+
+#define TPOLICY_DENSE_(BF16) \
+    __syncthreads(); \
+ \
+    /* fc1: row tiles 2 wave, 2 wave + 1 for the 16 boards; flat k = 64 token + feature, tile t of 16 = token t / 4 */ \
+    const float *Pt = P + 2 * kD + layers * lay.layer_params(); \
+    f4 h1[2]; \
+_Pragma("unroll") \
+    for (int q = 0; q < 2; ++q) { \
+        const int o = 2 * wave + q; \
+        h1[q] = load_f4(Pt + 16 * o + 4 * g); \
+        dense_lds<BF16, kFlat / 16>(W + lay.fc1() * kFrag, o, lane, lds, kBoardStride, \
+                                    [](int t) { return (t >> 2) * kTokStride + 16 * (t & 3); }, h1[q]); \
+    } \
+    __syncthreads();  /* every wavefront is done with the encoder outputs */ \
+    float *a1 = lds, *a2 = lds + 16 * kH1Stride; \
+_Pragma("unroll") \
+    for (int q = 0; q < 2; ++q) *reinterpret_cast<f4 *>(a1 + col * kH1Stride + 16 * (2 * wave + q) + 4 * g) = relu(h1[q]); \
+    __syncthreads(); \
+ \
+    /* fc2: row tile `wave` */ \
+    f4 h2 = load_f4(Pt + kFc1 + 16 * wave + 4 * g); \
+    dense_lds<BF16, kFc1 / 16>(W + lay.fc2() * kFrag, wave, lane, a1, kH1Stride, [](int t) { return 16 * t; }, h2); \
+    *reinterpret_cast<f4 *>(a2 + col * kH2Stride + 16 * wave + 4 * g) = relu(h2); \
+    __syncthreads();
+
+#define TPOLICY_HEADS_(BF16) \
+    /* heads: rows 0..3 the actor's logits (lanes 0..15), row 4 the critic's value (register 0 of lanes 16..31) */ \
+    f4 z = load_f4(Pt + kFc1 + kFc2 + 4 * g); \
+    dense_lds<BF16, kFc2 / 16>(W + lay.heads() * kFrag, 0, lane, a2, kH2Stride, [](int t) { return 16 * t; }, z);
+
 // Two blocks per compute unit (2 x 68.25 KiB of LDS, two wavefronts per SIMD): asking for that keeps the kernel under 256
 // registers without scratch (f32 226, bf16 245 VGPRs) and is 8 % (f32) to 25 % (bf16) faster than one wavefront per SIMD with
 // 298 (profiles/r08_tpolicy_rate.txt).
@@ -287,160 +456,202 @@ __global__ __launch_bounds__(64 * kWaves, 2) void tpolicy_forward_kernel(const u
     const float *P = reinterpret_cast<const float *>(W + lay.params());
     const size_t env0 = (size_t)blockIdx.x * 16;
 
-    // embedding: x[f][token] = w[f] * (code / 15) + b[f]; boards past n read as empty
-    f4 x[kE][4];
-    {
-        f4 ew[4], eb[4];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            ew[t] = load_f4(P + 16 * t + 4 * g);
-            eb[t] = load_f4(P + kD + 16 * t + 4 * g);
-        }
-#pragma unroll
-        for (int e = 0; e < kE; ++e) {
-            const size_t env = env0 + (size_t)(kE * wave + e);
-            const float v = (float)(env < n ? boards[env * 16 + col] : (uint8_t)0) / 15.0f;
-#pragma unroll
-            for (int t = 0; t < 4; ++t) x[e][t] = ew[t] * splat(v) + eb[t];
-        }
-    }
-
-#pragma unroll 1
-    for (int l = 0; l < layers; ++l) {
-        const unsigned char *Wl = W + (size_t)l * lay.layer_frags() * kFrag;
-        const float *Pl = P + 2 * kD + l * lay.layer_params();
-        const float *in_b = Pl, *out_b = Pl + 3 * kD, *b1 = Pl + 4 * kD, *b2 = b1 + ff, *norms = b2 + kD;
-
-        // self-attention, head by head; attn[e][h] = row tile h of the concatenated heads
-        f4 attn[kE][4];
-#pragma unroll
-        for (int h = 0; h < kHeads; ++h) {
-            f4 q[kE], k[kE], vt[kE];
-            const f4 qb = load_f4(in_b + 16 * h + 4 * g), kb = load_f4(in_b + kD + 16 * h + 4 * g);
-            const f4 vb = splat(in_b[2 * kD + 16 * h + col]);
-#pragma unroll
-            for (int e = 0; e < kE; ++e) { q[e] = qb; k[e] = kb; vt[e] = vb; }
-            project64<BF16>(Wl, h, lane, x, q);
-            project64<BF16>(Wl, 4 + h, lane, x, k);
-            project64<BF16, true>(Wl, 8 + h, lane, x, vt);
-#pragma unroll
-            for (int e = 0; e < kE; ++e) {
-                f4 s = splat(0.0f);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) s = __builtin_amdgcn_mfma_f32_16x16x4f32(k[e][r], q[e][r], s, 0, 0, 0);
-                s = s * splat(0.25f);                                           // 1 / sqrt(head_dim)
-                const float m = lanes_max(fmaxf(fmaxf(s[0], s[1]), fmaxf(s[2], s[3])));
-                f4 p{expf(s[0] - m), expf(s[1] - m), expf(s[2] - m), expf(s[3] - m)};
-                const float sum = lanes_sum((p[0] + p[1]) + (p[2] + p[3]));
-                p = p / splat(sum);
-                f4 o = splat(0.0f);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) o = __builtin_amdgcn_mfma_f32_16x16x4f32(vt[e][r], p[r], o, 0, 0, 0);
-                attn[e][h] = o;
-            }
-        }
-
-        // x = norm1(x + out_proj(attn))
-        {
-            f4 y[kE][4];
-#pragma unroll
-            for (int o = 0; o < 4; ++o) {
-                f4 acc[kE];
-                const f4 b = load_f4(out_b + 16 * o + 4 * g);
-#pragma unroll
-                for (int e = 0; e < kE; ++e) acc[e] = b;
-                project64<BF16>(Wl + lay.out_proj() * kFrag, o, lane, attn, acc);
-#pragma unroll
-                for (int e = 0; e < kE; ++e) y[e][o] = acc[e];
-            }
-            add_norm(x, y, norms, norms[4 * kD], g);
-        }
-
-        // x = norm2(x + W2 relu(W1 x + b1) + b2), 32 features of the hidden layer at a time
-        {
-            const unsigned char *W1 = Wl + lay.w1() * kFrag, *W2 = Wl + lay.w2() * kFrag;
-            constexpr int CPS = BF16 ? 1 : 2;                                   // W2 chunks per 32-feature slice
-            const int c2 = ff / (32 / CPS);                                     // W2 chunks per row tile
-            f4 y[kE][4];
-#pragma unroll
-            for (int o = 0; o < 4; ++o) {
-                const f4 b = load_f4(b2 + 16 * o + 4 * g);
-#pragma unroll
-                for (int e = 0; e < kE; ++e) y[e][o] = b;
-            }
-#pragma unroll 1
-            for (int s = 0; s < ff / 32; ++s) {
-                f4 h1[kE][2];
-#pragma unroll
-                for (int t = 0; t < 2; ++t) {
-                    f4 acc[kE];
-                    const f4 b = load_f4(b1 + 32 * s + 16 * t + 4 * g);
-#pragma unroll
-                    for (int e = 0; e < kE; ++e) acc[e] = b;
-                    project64<BF16>(W1, 2 * s + t, lane, x, acc);
-#pragma unroll
-                    for (int e = 0; e < kE; ++e) h1[e][t] = relu(acc[e]);
-                }
-#pragma unroll
-                for (int t = 0; t < CPS; ++t) {
-                    const int c = CPS * s + t;
-#pragma unroll
-                    for (int o = 0; o < 4; ++o) {
-                        f4 in[kE][2], acc[kE];
-#pragma unroll
-                        for (int e = 0; e < kE; ++e) {
-                            in[e][0] = h1[e][t];
-                            in[e][1] = h1[e][1];
-                            acc[e] = y[e][o];
-                        }
-                        chunk_mma<BF16, kE>(W2 + ((size_t)(o * c2 + c) * 64 + lane) * 16, in, acc);
-#pragma unroll
-                        for (int e = 0; e < kE; ++e) y[e][o] = acc[e];
-                    }
-                }
-            }
-            add_norm(x, y, norms + 2 * kD, norms[4 * kD + 1], g);
-        }
-    }
-
-    // flatten: lds[board][token][feature] (the block's 16 boards)
-#pragma unroll
-    for (int e = 0; e < kE; ++e)
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-            *reinterpret_cast<f4 *>(lds + (kE * wave + e) * kBoardStride + col * kTokStride + 16 * t + 4 * g) = x[e][t];
-    __syncthreads();
-
-    // fc1: row tiles 2 wave, 2 wave + 1 for the 16 boards; flat k = 64 token + feature, tile t of 16 = token t / 4
-    const float *Pt = P + 2 * kD + layers * lay.layer_params();
-    f4 h1[2];
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-        const int o = 2 * wave + q;
-        h1[q] = load_f4(Pt + 16 * o + 4 * g);
-        dense_lds<BF16, kFlat / 16>(W + lay.fc1() * kFrag, o, lane, lds, kBoardStride,
-                                    [](int t) { return (t >> 2) * kTokStride + 16 * (t & 3); }, h1[q]);
-    }
-    __syncthreads();                                                            // every wavefront is done with the encoder outputs
-    float *a1 = lds, *a2 = lds + 16 * kH1Stride;
-#pragma unroll
-    for (int q = 0; q < 2; ++q) *reinterpret_cast<f4 *>(a1 + col * kH1Stride + 16 * (2 * wave + q) + 4 * g) = relu(h1[q]);
-    __syncthreads();
-
-    // fc2: row tile `wave`
-    f4 h2 = load_f4(Pt + kFc1 + 16 * wave + 4 * g);
-    dense_lds<BF16, kFc1 / 16>(W + lay.fc2() * kFrag, wave, lane, a1, kH1Stride, [](int t) { return 16 * t; }, h2);
-    *reinterpret_cast<f4 *>(a2 + col * kH2Stride + 16 * wave + 4 * g) = relu(h2);
-    __syncthreads();
+    // boards past n read as empty
+#define TPOLICY_GLOBAL_CELL_ (env0 + (size_t)(kE * wave + e) < n ? boards[(env0 + (size_t)(kE * wave + e)) * 16 + col] : (uint8_t)0)
+    TPOLICY_ENCODER_(BF16, TPOLICY_GLOBAL_CELL_);
+    TPOLICY_DENSE_(BF16);
     if (wave != 0) return;
-
-    // heads: rows 0..3 the actor's logits (lanes 0..15), row 4 the critic's value (register 0 of lanes 16..31)
-    f4 z = load_f4(Pt + kFc1 + kFc2 + 4 * g);
-    dense_lds<BF16, kFc2 / 16>(W + lay.heads() * kFrag, 0, lane, a2, kH2Stride, [](int t) { return 16 * t; }, z);
+    TPOLICY_HEADS_(BF16);
     const size_t env = env0 + col;
     if (env >= n) return;
     if (g == 0) probs[env] = softmax4(z);
     else if (g == 1 && value) value[env] = z[0];
+}
+
+// --------------------------------------------------------------------------------------------------- complete games --
+// Complete games of the transformer policy, as policy_play_kernel (g2048_policy.hip) plays the PPO actor's. A block keeps the
+// forward kernel's geometry: four wavefronts, 16 boards -- here 16 game slots, slot s on lane s of wavefront 0, its board one of
+// the four of wavefront s / 4. Per move: every wavefront reads the cell bytes of its four slots' boards from LDS (an idle slot
+// holds the empty board) and the block runs the shared forward; the head tile lands on lanes 0..15 of wavefront 0 with column =
+// slot, so each slot lane has its own logits in registers, takes the softmax, picks its action, steps its board and does the
+// bookkeeping with the code and the draws of policy_play_kernel. The forward leaves no registers over (226 / 245 VGPRs), so a
+// slot's state (board, score, move index, counters, milestones, f64 reward sum, game index: PlaySlots, 80 bytes a slot) is
+// parked in LDS between moves and loaded after the forward. A finished game writes its results and its slot takes the next
+// game index from the ticket counter in the workspace: one atomicAdd per block for all its idle slots, the indices spread by
+// an mbcnt prefix. Wavefront 0 publishes the mask of live slots through LDS under the move's first barrier: the block leaves
+// when no slot is live, which after a refill attempt means the queue is empty. With kSkipIdleWave a wavefront whose four slots
+// are all idle skips its encoder (wave-uniformly; it still reaches every barrier); that is switched off, not having been measured.
+// Nothing waits on another block: no spin, no grid barrier, and the games do not depend on which block or slot plays them.
+__device__ const uint32_t kTPlayDirTable[G2048_DIR_TABLE_WORDS] = G2048_DIR_TABLE_INIT;
+
+constexpr int kSlots = kWaves * kE;
+constexpr bool kSkipIdleWave = false;                // built, and the games tested with it on; off until an A/B at the tail shows it faster
+
+struct PlaySlots {                                   // one column per slot; slot lanes read and write only their own
+    uint4 board[kSlots];                             // the empty board while the slot is idle
+    int4 milestone[2][kSlots];
+    double reward[kSlots];
+    unsigned long long game[kSlots];
+    uint32_t score[kSlots];
+    int32_t moves[kSlots], valid[kSlots];
+    uint32_t active[kSlots];
+};
+
+// Everything of a launch that only the refill and the slots' steps need. The forward alone takes 72 / 82 of the 106 scalar
+// registers, and these would be two dozen more held across it. So the block copies them to LDS once and the slot lanes read
+// them from there, after the forward, when registers are free. (Not enough on its own to stay out of scratch: see the opaque
+// blob address in the kernel.)
+struct PlayArgs {
+    unsigned long long *ticket;
+    uint4 *boards;
+    uint32_t *score;
+    size_t n;
+    uint64_t seed, id_base;
+    int32_t *moves_out, *valid_out, *invalid_out;
+    int4 *milestone_out;
+    double *reward_out;
+    uint8_t *alive_out, *actions_out;
+    int max_moves;
+    uint32_t mode;
+};
+
+template <bool BF16>
+__global__ __launch_bounds__(64 * kWaves, 2) void tpolicy_play_kernel(const unsigned char *__restrict__ weights, int ff, int layers, const PlayArgs args)
+{
+    __shared__ PlayArgs par;
+    __shared__ __attribute__((aligned(16))) float lds[kLdsFloats];
+    __shared__ PlaySlots slots;
+    __shared__ uint4 s_dir[G2048_DIR_TABLE_WORDS / 4];
+    __shared__ uint32_t s_live;                      // bit s: slot s plays this move (written by wavefront 0 before the barrier)
+    const Layout lay(BF16, ff, layers);
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), g = lane >> 4, col = lane & 15;
+    const bool slot_lane = wave == 0 && lane < kSlots;
+    if (threadIdx.x < G2048_DIR_TABLE_WORDS) reinterpret_cast<uint32_t *>(s_dir)[threadIdx.x] = kTPlayDirTable[threadIdx.x];
+    if (slot_lane) {
+        slots.active[lane] = 0u;
+        slots.board[lane] = make_uint4(0u, 0u, 0u, 0u);
+    }
+    if (threadIdx.x == 0) par = args;
+    __syncthreads();                                 // par and s_dir are there
+    bool drained = false;                            // (wavefront 0) block-uniform: the queue has no game left
+
+    for (;;) {
+        if (wave == 0) {
+            bool active = slot_lane && slots.active[lane] != 0u;
+            if (!drained) {
+                const uint64_t idle = __ballot(slot_lane && !active);
+                if (idle != 0ull) {
+                    const uint32_t cnt = (uint32_t)__popcll(idle);
+                    unsigned long long got = 0ull;
+                    if (lane == 0) got = atomicAdd(par.ticket, (unsigned long long)cnt);
+                    const uint64_t base = ((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(got >> 32)) << 32) |
+                                          __builtin_amdgcn_readfirstlane((uint32_t)got);
+                    const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
+                    if (slot_lane && !active && base + rank < par.n) {
+                        const size_t game = (size_t)(base + rank);
+                        slots.board[lane] = par.boards[game];
+                        slots.score[lane] = par.score[game];
+                        slots.game[lane] = game;
+                        slots.moves[lane] = 0;
+                        slots.valid[lane] = 0;
+                        slots.reward[lane] = 0.0;
+                        slots.milestone[0][lane] = make_int4(-1, -1, -1, -1);
+                        slots.milestone[1][lane] = make_int4(-1, -1, -1, -1);
+                        slots.active[lane] = 1u;
+                        active = true;
+                    }
+                    drained = base + cnt >= par.n;
+                }
+            }
+            const uint64_t live = __ballot(active);
+            if (lane == 0) s_live = (uint32_t)live;
+        }
+        __syncthreads();                             // the slots' boards and s_live are there
+        const uint32_t live = s_live;
+        if (live == 0u) break;                       // block-uniform: every slot idle after a refill attempt = the queue is empty
+
+        // The blob's address is made opaque once per move. Otherwise every load of the forward that does not depend on the
+        // board (the embedding, the head biases) is hoisted out of the move loop and held in registers across it, which the
+        // forward has none to spare for: without this line the kernel compiles to 48 (f32) / 64 (bf16) bytes of scratch per lane,
+        // with it to none (profiles/r09_tpolicy_play_resource_usage.txt).
+        const unsigned char *W = weights;
+        asm volatile("" : "+s"(W));
+        const float *P = reinterpret_cast<const float *>(W + lay.params());
+
+        if (!kSkipIdleWave || ((live >> (kE * wave)) & ((1u << kE) - 1u)) != 0u) {
+#define TPOLICY_SLOT_CELL_ reinterpret_cast<const uint8_t *>(slots.board)[(kE * wave + e) * 16 + col]
+            TPOLICY_ENCODER_(BF16, TPOLICY_SLOT_CELL_);
+        }
+        // fc1 reads all 16 board columns of lds. A wavefront that skipped its encoder left its four columns as they were (on the
+        // first move: never written, possibly NaN). That is sound only because an MFMA column depends on nothing but its own
+        // column of B, through fc1, fc2 and the heads alike, and an idle slot's column is never read by a slot lane: anything
+        // that mixes columns here (a reduction over boards, say) would have to write the idle columns first.
+        TPOLICY_DENSE_(BF16);
+        if (wave != 0) continue;                     // to the next move's barrier, where wavefront 0 joins after its slots' steps
+        TPOLICY_HEADS_(BF16);
+
+        if (slot_lane && slots.active[lane] != 0u) {
+            const float4 p = softmax4(z);
+            const uint4 bw = slots.board[lane];
+            const Board cur{{bw.x, bw.y, bw.z, bw.w}};
+            const size_t game = (size_t)slots.game[lane];
+            const int32_t t = slots.moves[lane];
+            const uint64_t id = par.id_base + game;
+            const uint32_t mask = valid_mask_env(cur);
+            uint32_t a;
+            if (par.mode == G2048_PLAY_POLICY_GREEDY) {              // argmax over the valid moves, ties to the lowest index
+                const uint32_t m = mask ? mask : 15u;            // (no valid move: all four, as sample_action does)
+                float best = 0.0f;
+                a = 4u;
+#pragma unroll
+                for (int k = 3; k >= 0; --k) {
+                    const float v = k == 0 ? p.x : k == 1 ? p.y : k == 2 ? p.z : p.w;
+                    if (((m >> k) & 1u) && (a == 4u || v >= best)) { a = (uint32_t)k; best = v; }
+                }
+            } else {
+                const Keys kp = rng_keys(par.seed, DOM_POLICY, (uint64_t)t);
+                float pa;
+                a = sample_action(p.x, p.y, p.z, p.w, par.mode == G2048_PLAY_POLICY_MASKED ? mask : 15u, rng_draw(kp.k0, kp.k1, id, 0u), pa);
+            }
+            const Keys ks = rng_keys(par.seed, DOM_STEP, (uint64_t)t);
+            const uint4 s0 = s_dir[2u * a], s1 = s_dir[2u * a + 1u];
+            const StepOut o = step_board_sel(cur, DirSel{s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w}, rng_draw(ks.k0, ks.k1, id, 0u));
+            if (par.actions_out) par.actions_out[game * (size_t)par.max_moves + (size_t)t] = (uint8_t)a;
+            const uint32_t sc = slots.score[lane] + o.gain;
+            const double rsum = slots.reward[lane] + o.reward;
+            const int32_t maxcode = (int32_t)(o.flags >> G2048_FLAG_MAXCODE_SHIFT);
+            const int4 m0 = slots.milestone[0][lane], m1 = slots.milestone[1][lane];
+            int32_t ms[8] = {m0.x, m0.y, m0.z, m0.w, m1.x, m1.y, m1.z, m1.w};
+#pragma unroll
+            for (int k = 0; k < 8; ++k)
+                if (ms[k] < 0 && maxcode >= 6 + k) ms[k] = t;       // tiles 64 .. 8192, as g2048_track_episodes records them
+            const int32_t nvalid = slots.valid[lane] + ((o.flags & G2048_FLAG_VALID) ? 1 : 0);
+            const int32_t moved = t + 1;
+            const bool done = (o.flags & G2048_FLAG_DONE) != 0u;
+            const uint4 nb = make_uint4(o.board.w[0], o.board.w[1], o.board.w[2], o.board.w[3]);
+            if (done || moved == par.max_moves) {
+                par.boards[game] = nb;
+                par.score[game] = sc;
+                par.moves_out[game] = moved;
+                par.valid_out[game] = nvalid;
+                par.invalid_out[game] = moved - nvalid;
+                par.milestone_out[2 * game] = make_int4(ms[0], ms[1], ms[2], ms[3]);
+                par.milestone_out[2 * game + 1] = make_int4(ms[4], ms[5], ms[6], ms[7]);
+                if (par.reward_out) par.reward_out[game] = rsum;
+                par.alive_out[game] = done ? 0 : 1;
+                slots.board[lane] = make_uint4(0u, 0u, 0u, 0u);
+                slots.active[lane] = 0u;
+            } else {
+                slots.board[lane] = nb;
+                slots.score[lane] = sc;
+                slots.moves[lane] = moved;
+                slots.valid[lane] = nvalid;
+                slots.reward[lane] = rsum;
+                slots.milestone[0][lane] = make_int4(ms[0], ms[1], ms[2], ms[3]);
+                slots.milestone[1][lane] = make_int4(ms[4], ms[5], ms[6], ms[7]);
+            }
+        }
+    }
 }
 
 bool good_shape(int dim_ff, int n_layers) { return dim_ff >= 32 && dim_ff % 32 == 0 && dim_ff <= 65536 && n_layers >= 1 && n_layers <= 64; }
@@ -512,6 +723,58 @@ int g2048_tpolicy_forward(const void *boards, const void *packed, float *probs_o
                            reinterpret_cast<float4 *>(probs_out), value_out_or_null, n, dim_ff, n_layers);
     });
     return check_launch("g2048_tpolicy_forward");
+}
+
+size_t g2048_play_tpolicy_workspace(size_t n_games)
+{
+    (void)n_games;
+    return 64;                                       // the ticket counter (uint64), padded
+}
+
+int g2048_play_tpolicy_games(void *boards_inout, uint32_t *score_inout, const void *packed, int dim_ff, int n_layers, int32_t *moves_out,
+                             int32_t *valid_out, int32_t *invalid_out, int32_t *milestone_move_out, double *reward_sum_out_or_null,
+                             uint8_t *alive_out, uint8_t *actions_out_or_null, int max_moves, uint64_t seed, uint64_t game_id_base,
+                             size_t n_games, uint32_t opts, uint32_t max_blocks, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (n_games == 0) return G2048_OK;
+    if (!boards_inout || !score_inout || !packed || !moves_out || !valid_out || !invalid_out || !milestone_move_out || !alive_out ||
+        !workspace)
+        return fail(G2048_ERR_ARG, "g2048_play_tpolicy_games: null pointer");
+    if (!aligned(boards_inout, 16) || !aligned(packed, 16) || !aligned(milestone_move_out, 16) || !aligned(score_inout, 4) ||
+        !aligned(moves_out, 4) || !aligned(valid_out, 4) || !aligned(invalid_out, 4) || !aligned(reward_sum_out_or_null, 8) ||
+        !aligned(workspace, 8))
+        return fail(G2048_ERR_ARG, "g2048_play_tpolicy_games: misaligned pointer (boards, weights, milestones: 16 bytes; rewards, "
+                                   "workspace: 8; counters and scores: 4)");
+    const uint32_t precision = opts & 0xfu, mode = (opts >> G2048_PLAY_POLICY_MODE_SHIFT) & 0xfu;
+    if ((opts >> (G2048_PLAY_POLICY_MODE_SHIFT + 4)) != 0u || !good_precision((int)precision))
+        return fail(G2048_ERR_ARG, "g2048_play_tpolicy_games: unknown opts (precision | mode << 4)");
+    if (mode != G2048_PLAY_POLICY_MASKED && mode != G2048_PLAY_POLICY_UNMASKED && mode != G2048_PLAY_POLICY_GREEDY)
+        return fail(G2048_ERR_ARG, "g2048_play_tpolicy_games: unknown mode");
+    if (max_moves < 1) return fail(G2048_ERR_ARG, "g2048_play_tpolicy_games: max_moves must be at least 1");
+    if (!good_shape(dim_ff, n_layers))
+        return fail(G2048_ERR_ARG, "g2048_play_tpolicy_games: dim_ff must be a multiple of 32 (32 .. 65536) and n_layers 1 .. 64");
+    if (workspace_bytes < g2048_play_tpolicy_workspace(n_games))
+        return fail(G2048_ERR_ARG, "g2048_play_tpolicy_games: workspace smaller than g2048_play_tpolicy_workspace(n_games)");
+    const bool bf16 = precision == G2048_POLICY_BF16;
+    // auto: as many blocks as the chip holds at once (every later one would only find the queue empty)
+    const size_t cap = max_blocks ? (size_t)max_blocks : (size_t)device_cus() * with_bool(bf16, [](auto BF16) {
+        return resident_per_cu(tpolicy_play_kernel<decltype(BF16)::value>, 64 * kWaves);
+    });
+    if (cap == 0) return fail(G2048_ERR_HIP, "g2048_play_tpolicy_games: no HIP device (occupancy query failed)");
+    const size_t blocks = std::min(std::min((n_games + kSlots - 1) / kSlots, cap), (size_t)0x7fffffffu);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    auto *ticket = static_cast<unsigned long long *>(workspace);
+    hipError_t e = hipMemsetAsync(ticket, 0, sizeof *ticket, s);
+    if (e == hipSuccess && actions_out_or_null) e = hipMemsetAsync(actions_out_or_null, 0xff, n_games * (size_t)max_moves, s);
+    if (const int rc = check_hip(e, "g2048_play_tpolicy_games: hipMemsetAsync")) return rc;
+    const PlayArgs args{ticket, static_cast<uint4 *>(boards_inout), score_inout, n_games, seed, game_id_base, moves_out, valid_out,
+                        invalid_out, reinterpret_cast<int4 *>(milestone_move_out), reward_sum_out_or_null, alive_out, actions_out_or_null,
+                        max_moves, mode};
+    with_bool(bf16, [&](auto BF16) {
+        hipLaunchKernelGGL(tpolicy_play_kernel<decltype(BF16)::value>, dim3((unsigned)blocks), dim3(64 * kWaves), 0, s,
+                           static_cast<const unsigned char *>(packed), dim_ff, n_layers, args);
+    });
+    return check_launch("g2048_play_tpolicy_games");
 }
 
 }  // extern "C"

@@ -92,6 +92,8 @@ SIGNATURES = {
     "g2048_tpolicy_forward": (_int, [_vp, _vp, _vp, _vp, _sz, _int, _int, _u32, _vp]),
     "g2048_play_policy_workspace": (_sz, [_sz]),
     "g2048_play_policy_games": (_int, [_vp] * 10 + [_int, _u64, _u64, _sz, _u32, _u32, _vp, _sz, _vp]),
+    "g2048_play_tpolicy_workspace": (_sz, [_sz]),
+    "g2048_play_tpolicy_games": (_int, [_vp] * 3 + [_int, _int] + [_vp] * 7 + [_int, _u64, _u64, _sz, _u32, _u32, _vp, _sz, _vp]),
 }
 
 

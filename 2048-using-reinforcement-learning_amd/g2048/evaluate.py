@@ -23,7 +23,8 @@ intermediate board, score and max tile of the games asked for -- `results["games
 `save_game_data` / `save_moveset` write the reference's two file formats.
 
 `evaluate_policy` is the same for a PPO actor (a DevicePolicy): the games of train.py / play.py, every game to its end in one
-`g2048_play_policy_games` launch, with the same result dict plus each game's summed env reward.
+`g2048_play_policy_games` launch, with the same result dict plus each game's summed env reward. A DeviceTransformerPolicy plays
+the same games with the transformer's probabilities (`g2048_play_tpolicy_games`).
 """
 import json
 import time
@@ -144,6 +145,11 @@ def evaluate_beam_search(num_games=4096, beam_width=20, search_depth=30, seed=0x
 POLICY_MODES = ("masked", "unmasked", "greedy")
 
 
+def _is_transformer(policy):
+    from .tpolicy import DeviceTransformerPolicy
+    return isinstance(policy, DeviceTransformerPolicy)
+
+
 def evaluate_policy(policy, num_games=4096, max_moves=2000, mode="masked", seed=0x2048, game_id_base=0, device=None,
                     fused=True, histories=None, max_waves=0):
     """Complete games of a PPO actor (a g2048.DevicePolicy; its critic, if any, is not used): the games of train.py:54-90
@@ -158,9 +164,15 @@ def evaluate_policy(policy, num_games=4096, max_moves=2000, mode="masked", seed=
     are identical. Returns evaluate_beam_search's result dict (scores, highest_tiles, moves, valid / invalid moves, milestones,
     best_games, final_boards, best_*, unfinished, total_moves, elapsed_s, summary) plus "episode_rewards" (the f64 env rewards
     of each game summed in move order: train.py's episode_reward, play.py's total_reward); "parameters" holds mode,
-    precision, max_moves, num_games and seed. histories: as in evaluate_beam_search (fused driver only)."""
-    if not hasattr(policy, "actor") or not hasattr(policy.actor, "blob"):
-        raise TypeError("g2048.evaluate_policy: policy must be a g2048.DevicePolicy")
+    precision, max_moves, num_games and seed. histories: as in evaluate_beam_search (fused driver only).
+
+    policy may also be a g2048.DeviceTransformerPolicy: the same games, modes and result dict with the transformer's
+    probabilities (its value head is not used). fused=True is ONE g2048_play_tpolicy_games launch (max_waves = its BLOCK
+    count, 16 games in flight each; 0 = as many as the chip holds); fused=False the loop of tpolicy_forward(want_value=False),
+    valid_moves, sample_actions / argmax, step and track_episodes."""
+    transformer = _is_transformer(policy)
+    if not transformer and (not hasattr(policy, "actor") or not hasattr(policy.actor, "blob")):
+        raise TypeError("g2048.evaluate_policy: policy must be a g2048.DevicePolicy or a g2048.DeviceTransformerPolicy")
     if mode not in POLICY_MODES:
         raise ValueError("g2048.evaluate_policy: mode must be one of %s" % (POLICY_MODES,))
     if int(max_moves) < 1:
@@ -171,13 +183,21 @@ def evaluate_policy(policy, num_games=4096, max_moves=2000, mode="masked", seed=
     if device is not None and ops._dev_index(torch.device(device)) != ops._dev_index(dev):
         raise ValueError("g2048.evaluate_policy: the policy lives on %s, not %s" % (dev, device))
     n, max_moves = int(num_games), int(max_moves)
-    blob, precision = policy.actor.blob(1), policy.precision
+    precision = policy.precision
+    blob = policy.packed if transformer else policy.actor.blob(1)
     t_start = time.perf_counter()
     env = VecGame2048(n, device=dev, seed=seed, id_base=game_id_base)
     boards0 = env.boards.clone() if histories is not None else None
-    if fused:
+    if fused and transformer:
+        res = ops.play_tpolicy_games(env.boards, env.scores, blob, policy.dim_ff, policy.n_layers, precision, max_moves, mode, seed,
+                                     game_id_base, want_rewards=True, want_actions=histories is not None, max_blocks=max_waves)
+    elif fused:
         res = ops.play_policy_games(env.boards, env.scores, blob, precision, max_moves, mode, seed, game_id_base,
                                     want_rewards=True, want_actions=histories is not None, max_waves=max_waves)
+    elif transformer:
+        dim_ff, n_layers = policy.dim_ff, policy.n_layers
+        res = _play_policy_stepwise(env, blob, precision, max_moves, mode, seed, game_id_base, forward=lambda boards, probs:
+                                    ops.tpolicy_forward(boards, blob, dim_ff, n_layers, precision, probs=probs, want_value=False))
     else:
         res = _play_policy_stepwise(env, blob, precision, max_moves, mode, seed, game_id_base)
     torch.cuda.synchronize(dev)
@@ -202,10 +222,15 @@ def policy_results_from_table(table, episode_rewards, elapsed, parameters):
     return results
 
 
-def _play_policy_stepwise(env, blob, precision, max_moves, mode, seed, game_id_base, check_every=16):
+def _play_policy_stepwise(env, blob, precision, max_moves, mode, seed, game_id_base, check_every=16, forward=None):
     """The unfused yardstick of g2048_play_policy_games: one policy_forward, one action launch (sample_actions with step_index
     = t, or torch's argmax), one step and one track_episodes per move for the whole batch. A finished game is over (no move
-    changes its board), so stepping it again changes nothing; its counters and reward sum are frozen by `alive`."""
+    changes its board), so stepping it again changes nothing; its counters and reward sum are frozen by `alive`.
+    forward: forward(boards, probs) fills probs (float32 (n,4)) for the boards with one launch; None = the PPO actor's
+    policy_forward on `blob`. With the transformer's forward this is the yardstick of g2048_play_tpolicy_games."""
+    if forward is None:
+        def forward(boards, probs):
+            ops.policy_forward(boards, blob, None, precision, probs=probs)
     n, dev = env.n, env.device
     alive = torch.ones(n, dtype=torch.uint8, device=dev)
     moves = torch.zeros(n, dtype=torch.int32, device=dev)
@@ -219,7 +244,7 @@ def _play_policy_stepwise(env, blob, precision, max_moves, mode, seed, game_id_b
     for t in range(max_moves):
         if t % check_every == 0 and not bool(alive.any()):
             break
-        ops.policy_forward(env.boards, blob, None, precision, probs=probs)
+        forward(env.boards, probs)
         if mode == "greedy":
             valid = (ops.valid_moves(env.boards)[:, None] & bits) != 0
             valid |= ~valid.any(dim=1, keepdim=True)               # no valid move: all four, as the sampler does

@@ -945,6 +945,58 @@ def play_policy_games(boards, scores, actor_packed, precision="f32", max_moves=2
     return out
 
 
+_PLAY_TPOLICY_WS = _PerStream()
+
+
+def play_tpolicy_games(boards, scores, packed, dim_ff, n_layers, precision="f32", max_moves=2000, mode="masked", seed=0x2048,
+                       game_id_base=0, want_rewards=True, want_actions=False, max_blocks=0):
+    """Every game played to the end by the transformer policy in ONE launch (g2048_play_tpolicy_games): play_policy_games with
+    the network of tpolicy_forward. packed: the blob of tpolicy_pack for (precision, dim_ff, n_layers). boards / scores are
+    updated in place. Returns play_policy_games' dict of per-game tensors: moves, valid_moves, invalid_moves (int32),
+    milestone_move (int32 (n,8), -1 = never), alive (uint8), with want_rewards "reward_sum" (float64) and with want_actions
+    "actions" (uint8 (n, max_moves), 0xFF from a game's end on: the input of `replay_games`). max_blocks: the number of
+    blocks (16 games in flight each), 0 = as many as the chip holds (the games are the same for every value)."""
+    if precision not in POLICY_PRECISIONS:
+        raise ValueError("g2048: precision must be 'f32' or 'bf16'")
+    if mode not in PLAY_POLICY_MODES:
+        raise ValueError("g2048: mode must be one of %s" % (tuple(PLAY_POLICY_MODES),))
+    nb = tpolicy_packed_bytes(precision, dim_ff, n_layers)          # (the size needs no device: a wrong blob is refused anywhere)
+    if isinstance(packed, torch.Tensor) and packed.numel() != nb:
+        raise ValueError("g2048: packed must be a %s blob of %d bytes (dim_ff %d, %d layers)" % (precision, nb, dim_ff, n_layers))
+    L.require_device_tensor(boards, torch.uint8, (16,), "boards")
+    _require_scores(scores)
+    L.require_device_tensor(packed, torch.uint8, None, "packed")
+    n, dev = boards.shape[0], boards.device
+    if scores.shape[0] != n:
+        raise ValueError("g2048: scores length must equal the number of boards")
+    if int(max_moves) < 1:
+        raise ValueError("g2048: max_moves must be at least 1")
+    if not 0 <= int(max_blocks) <= 0xFFFFFFFF:
+        raise ValueError("g2048: max_blocks must be 0 (auto) or a positive 32-bit count")
+    out = {
+        "moves": torch.zeros(n, dtype=torch.int32, device=dev), "valid_moves": torch.zeros(n, dtype=torch.int32, device=dev),
+        "invalid_moves": torch.zeros(n, dtype=torch.int32, device=dev),
+        "milestone_move": torch.full((n, 8), -1, dtype=torch.int32, device=dev),
+        "alive": torch.zeros(n, dtype=torch.uint8, device=dev),
+    }
+    if want_rewards:
+        out["reward_sum"] = torch.zeros(n, dtype=torch.float64, device=dev)
+    if want_actions:
+        out["actions"] = torch.empty((n, int(max_moves)), dtype=torch.uint8, device=dev)     # (the library fills it with 0xFF)
+    need = int(L.lib().g2048_play_tpolicy_workspace(n))
+    opts = POLICY_PRECISIONS[precision] | (PLAY_POLICY_MODES[mode] << L.PLAY_POLICY_MODE_SHIFT)
+    ptr = lambda k: out[k].data_ptr() if k in out else None      # noqa: E731
+    box = _PLAY_TPOLICY_WS.get((_dev_index(dev), L.stream_ptr(dev)), _ScratchBox)
+    with box.lock:          # grow-if-needed and enqueue as one step (see beam_get_action)
+        if box.buf is None or box.buf.numel() < need:
+            box.buf = torch.empty(need, dtype=torch.uint8, device=dev)
+        L.call(dev, L.lib().g2048_play_tpolicy_games, boards.data_ptr(), scores.data_ptr(), packed.data_ptr(), int(dim_ff),
+               int(n_layers), out["moves"].data_ptr(), out["valid_moves"].data_ptr(), out["invalid_moves"].data_ptr(),
+               out["milestone_move"].data_ptr(), ptr("reward_sum"), out["alive"].data_ptr(), ptr("actions"), int(max_moves),
+               L.u64(seed), L.u64(game_id_base), n, opts, int(max_blocks), box.buf.data_ptr(), need, L.stream_ptr(dev))
+    return out
+
+
 def replay_games(boards0, actions, n_moves, seed, game_ids=None, game_id_base=0, scores0=None, longest=None):
     """Recorded games replayed into their per-move histories (g2048_replay_games; reference evaluate_beam_search.py:44-50,
     :72-75: board_history / scores_history / max_tiles_history of run_game). boards0 uint8 (k,16): where each game started;

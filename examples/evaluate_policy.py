@@ -1,13 +1,18 @@
 #!/usr/bin/env python3
-"""Evaluate a PPO actor over many complete games on the GPU (the games of train.py / play.py).
+"""Evaluate a PPO actor or the transformer policy over many complete games on the GPU (the games of train.py / play.py).
 
-    python examples/evaluate_policy.py --games 65536 [--weights reference|random] [--mode masked|unmasked|greedy]
+    python examples/evaluate_policy.py --games 65536 [--policy mlp|transformer] [--weights reference|random]
+                                       [--dim-ff 2048] [--layers 2] [--mode masked|unmasked|greedy]
                                        [--precision f32|bf16] [--max-moves 2000] [--out overall_results.json]
 
 --weights reference (default) loads the reference's trained checkpoint from tests/golden/policy.npz into the reference's
 ActorNetwork layout; random uses a freshly initialised network of that layout. Every game is played to the end in one
 launch (g2048.evaluate_policy); prints the summary table and optionally writes overall_results.json with the per-game
-episode rewards."""
+episode rewards.
+
+--policy transformer plays the reference's TransformerModel layout (models/transformer.py: --dim-ff, --layers) as a
+g2048.DeviceTransformerPolicy. There is no trained transformer checkpoint: it carries the hash-derived weights of
+tests/tpolicy_weights.py (--weights is ignored), so the games show the machinery, not a strong player."""
 import argparse
 import json
 import os
@@ -35,8 +40,32 @@ class ActorNetwork(nn.Module):
         self.relu, self.dropout, self.softmax = nn.ReLU(), nn.Dropout(0.2), nn.Softmax(dim=-1)
 
 
+class TransformerModel(nn.Module):
+    """The reference's transformer policy layout (models/transformer.py:4-40) from stock torch modules."""
+
+    def __init__(self, dim_ff, layers):
+        super().__init__()
+        self.embedding = nn.Linear(1, 64)
+        layer = nn.TransformerEncoderLayer(d_model=64, nhead=4, dim_feedforward=dim_ff, batch_first=True)
+        self.transformer_encoder = nn.TransformerEncoder(layer, num_layers=layers, enable_nested_tensor=False)
+        self.fc1, self.fc2 = nn.Linear(1024, 128), nn.Linear(128, 64)
+        self.actor, self.critic = nn.Linear(64, 4), nn.Linear(64, 1)
+
+
+def transformer_policy(dim_ff, layers, precision):
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import tpolicy_weights as tw
+    model = TransformerModel(dim_ff, layers).double()
+    shapes = [(k, tuple(v.shape)) for k, v in model.state_dict().items()]
+    model.load_state_dict({k: torch.from_numpy(v) for k, v in tw.state_dict(shapes).items()})
+    return g2048.DeviceTransformerPolicy(model.float().eval().to("cuda"), precision=precision)
+
+
 ap = argparse.ArgumentParser()
 ap.add_argument("--games", type=int, default=4096)
+ap.add_argument("--policy", choices=("mlp", "transformer"), default="mlp")
+ap.add_argument("--dim-ff", type=int, default=2048)
+ap.add_argument("--layers", type=int, default=2)
 ap.add_argument("--weights", choices=("reference", "random"), default="reference")
 ap.add_argument("--mode", choices=("masked", "unmasked", "greedy"), default="masked")
 ap.add_argument("--precision", choices=("f32", "bf16"), default="f32")
@@ -45,17 +74,22 @@ ap.add_argument("--seed", type=int, default=2025)
 ap.add_argument("--out", default=None)
 a = ap.parse_args()
 
-actor = ActorNetwork()
-if a.weights == "reference":
-    g = np.load(os.path.join(ROOT, "tests", "golden", "policy.npz"))
-    sd = {k[len("actor."):]: torch.from_numpy(g[k]) for k in g.files if k.startswith("actor.")}
-    actor.load_state_dict(sd, strict=False)         # (num_batches_tracked is not stored)
+if a.policy == "transformer":
+    policy = transformer_policy(a.dim_ff, a.layers, a.precision)
+    what = "transformer dim_ff %d x %d layers, hash" % (a.dim_ff, a.layers)
 else:
-    torch.manual_seed(a.seed)
-policy = g2048.DevicePolicy(actor.eval().to("cuda"), precision=a.precision)
+    actor = ActorNetwork()
+    if a.weights == "reference":
+        g = np.load(os.path.join(ROOT, "tests", "golden", "policy.npz"))
+        sd = {k[len("actor."):]: torch.from_numpy(g[k]) for k in g.files if k.startswith("actor.")}
+        actor.load_state_dict(sd, strict=False)         # (num_batches_tracked is not stored)
+    else:
+        torch.manual_seed(a.seed)
+    policy = g2048.DevicePolicy(actor.eval().to("cuda"), precision=a.precision)
+    what = a.weights
 res = g2048.evaluate_policy(policy, num_games=a.games, max_moves=a.max_moves, mode=a.mode, seed=a.seed)
 s = res["summary"]
-print("==== POLICY EVALUATION SUMMARY (%s weights, %s, %s) ====" % (a.weights, a.mode, a.precision))
+print("==== POLICY EVALUATION SUMMARY (%s weights, %s, %s) ====" % (what, a.mode, a.precision))
 print("Highest tile reached: %d" % s["highest_tile"])
 print("Best score: %d" % s["best_score"])
 print("Average score: %.1f" % s["average_score"])

@@ -48,7 +48,8 @@ extern "C" {
 #define G2048_ABI_VERSION 5        /* 5: round 5, second half (ops MOVE / SPAWN / MOVE_AGENT of g2048_env_step; g2048_eval kinds CORNER_BONUS and
                                       MERGE_POTENTIAL; no entry point added or removed;
                                       later, additive: g2048_policy_packed_bytes / _pack / _forward,
-                                      g2048_play_policy_games / _workspace, g2048_tpolicy_packed_bytes / _pack / _forward)
+                                      g2048_play_policy_games / _workspace, g2048_tpolicy_packed_bytes / _pack / _forward,
+                                      g2048_play_tpolicy_games / _workspace)
                                       4: round 5 (export table = this header + g2048_testing.h exactly: test / measurement hooks moved there,
                                       internal symbols hidden; g2048_replay_games also clamps a game's length to actions_stride)
                                       3: round 4 (actions_out of the g2048_play_games family, g2048_replay_games, g2048_env_step,
@@ -509,6 +510,33 @@ G2048_API int g2048_play_policy_games(void *boards_inout, uint32_t *score_inout,
                             int32_t *valid_out, int32_t *invalid_out, int32_t *milestone_move_out, double *reward_sum_out_or_null,
                             uint8_t *alive_out, uint8_t *actions_out_or_null, int max_moves, uint64_t seed, uint64_t game_id_base,
                             size_t n_games, uint32_t opts, uint32_t max_waves, void *workspace, size_t workspace_bytes, void *stream);
+
+/* Complete games of the transformer policy (the network of g2048_tpolicy_forward), every game played to the end on the device
+ * in ONE launch, as g2048_play_policy_games does for the PPO actor: the same games, modes, draws and outputs, with the
+ * transformer's probabilities. Game g (global id game_id_base + g) starts from boards_inout[g] / score_inout[g]; at move t = 0,
+ * 1, ... it takes p = the probs g2048_tpolicy_forward gives for the same board and blob (packed with the precision in opts;
+ * dim_ff, n_layers as packed), bit for bit, then the action by mode:
+ *   MASKED    exactly g2048_sample_actions(step_index = t, env id = game id) with the env's valid-move mask (draw (seed, POLICY,
+ *             t, game id));
+ *   UNMASKED  the same with all four actions allowed (it samples from p_a + 1e-10, as g2048_sample_actions with no mask);
+ *   GREEDY    the argmax of p over the valid moves, ties to the lowest index (torch.argmax); no draw;
+ * and steps the board exactly as g2048_step(step_index = t, board id = game id) does, without auto-reset. The game ends when it
+ * is over (DONE) or after max_moves moves. Outputs per game: final board and score (in place), moves, valid / invalid move
+ * counts, milestone_move_out[g][0..8) = the move at which tiles 64..8192 first appeared (-1 = never; as g2048_track_episodes
+ * records them), alive_out[g] = 1 if the game hit max_moves without finishing, reward_sum_out_or_null[g] = the f64 env rewards
+ * summed in move order from 0.0, and actions_out_or_null = the move-set, max_moves bytes per game, 0xFF from the game's end on
+ * (the input of g2048_replay_games; the library fills it with 0xFF first).
+ * opts = precision (G2048_POLICY_*) | mode (G2048_PLAY_POLICY_*) << G2048_PLAY_POLICY_MODE_SHIFT. max_blocks = the number of
+ * blocks (16 games in flight per block of four wavefronts; a finished game's slot takes the next game), 0 = as many as the chip
+ * holds at once; the games do not depend on it. workspace: g2048_play_tpolicy_workspace(n_games) bytes of device memory, 8-byte
+ * aligned (a ticket counter the call clears on `stream`). Boards, blob and milestone_move_out 16-byte aligned, rewards 8, the
+ * rest 4. Arguments are checked before any device call; n_games == 0 returns G2048_OK. Nothing past game n_games is written. */
+G2048_API size_t g2048_play_tpolicy_workspace(size_t n_games);
+G2048_API int g2048_play_tpolicy_games(void *boards_inout, uint32_t *score_inout, const void *packed, int dim_ff, int n_layers,
+                             int32_t *moves_out, int32_t *valid_out, int32_t *invalid_out, int32_t *milestone_move_out,
+                             double *reward_sum_out_or_null, uint8_t *alive_out, uint8_t *actions_out_or_null, int max_moves,
+                             uint64_t seed, uint64_t game_id_base, size_t n_games, uint32_t opts, uint32_t max_blocks, void *workspace,
+                             size_t workspace_bytes, void *stream);
 #ifdef __cplusplus
 }
 #endif

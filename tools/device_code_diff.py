@@ -4,7 +4,7 @@
 Unbundles both with `llvm-objdump --offloading` and compares, per gfx950 code object (one per .hip file, in link order), the set
 of kernels and the bytes of .text and .rodata (the kernel descriptors live there). Where a whole section differs -- e.g. the
 same kernels emitted in another order -- every kernel is compared on its own: the function's bytes and its 64-byte descriptor
-`<kernel>.kd`; the ones that differ are printed. Exit status 0 only if everything matches. What a host-side refactor has to show."""
+`<kernel>.kd` (without its entry offset, which moves when a kernel is added); the ones that differ are printed. Exit status 0 only if everything matches. What a host-side refactor has to show."""
 import glob
 import os
 import shutil
@@ -49,6 +49,15 @@ def symbol_bytes(sections, symbols, name):
     return data[value - addr:value - addr + size]
 
 
+# kernel_descriptor_t (llvm AMDGPUUsage, "Kernel Descriptor"): bytes 16..24 are KERNEL_CODE_ENTRY_BYTE_OFFSET, the distance from the
+# descriptor to the kernel's first instruction
+KD_ENTRY_OFFSET = slice(16, 24)
+
+
+def without_entry_offset(kd):
+    return kd[:KD_ENTRY_OFFSET.start] + kd[KD_ENTRY_OFFSET.stop:]
+
+
 def main(a, b):
     with tempfile.TemporaryDirectory() as tmp:
         objs_a, objs_b = code_objects(a, os.path.join(tmp, "a")), code_objects(b, os.path.join(tmp, "b"))
@@ -64,12 +73,25 @@ def main(a, b):
             same = False
             print("  kernels only in %s: %s\n  kernels only in %s: %s" % (a, sorted(kern_a - kern_b), b, sorted(kern_b - kern_a)))
         if not all(whole.values()):
-            differ = [k for k in sorted(kern_a & kern_b)
-                      if any(symbol_bytes(sec_a, sym_a, s) != symbol_bytes(sec_b, sym_b, s) for s in (k, k + ".kd"))]
-            print("  per kernel (function bytes + descriptor): %d of %d differ" % (len(differ), len(kern_a & kern_b)))
+            # a descriptor holds the offset from itself to the kernel's entry (KD_ENTRY_OFFSET), which moves with every kernel added
+            # to or taken from the code object: compared with that field left out, and reported apart from the function's bytes
+            def parts(k):
+                kd_a, kd_b = symbol_bytes(sec_a, sym_a, k + ".kd"), symbol_bytes(sec_b, sym_b, k + ".kd")
+                out = [] if symbol_bytes(sec_a, sym_a, k) == symbol_bytes(sec_b, sym_b, k) else ["function bytes"]
+                if without_entry_offset(kd_a) != without_entry_offset(kd_b):
+                    out.append("descriptor")
+                return out, kd_a != kd_b
+            report = {k: parts(k) for k in sorted(kern_a & kern_b)}
+            differ = [k for k, (what, _) in report.items() if what]
+            moved = [k for k, (what, kd) in report.items() if kd and not what]
+            print("  per kernel (function bytes + descriptor): %d of %d differ" % (len(differ), len(report)))
             for k in differ:
                 same = False
-                print("    " + k)
+                print("    %s: %s" % (k, ", ".join(report[k][0])))
+            if moved:
+                print("  identical but for the descriptor's entry offset (the kernel sits elsewhere in .text): %d" % len(moved))
+                for k in moved:
+                    print("    " + k)
     print("device code: " + ("IDENTICAL" if same else "DIFFERENT"))
     return 0 if same else 1
 
