@@ -1,0 +1,513 @@
+// g2048_qnet.hip -- the hybrid agent's CNN-transformer Q-network (agents/hybrid.py:700-727, HybridDQN, in eval mode, one board
+// per call) on the matrix cores of gfx950, one launch per forward pass (C-ABI: include/g2048.h, g2048_qnet_*).
+//
+//   qnet_pack_matrix_kernel  one weight matrix [rows][K] into 1 KiB MFMA fragments (a lane's A operand is one 16-byte load), its
+//                            columns permuted so that conv2's and the embedding's K run in the order the forward produces them.
+//   qnet_pack_params_kernel  conv1 (tap-major), every bias, the LayerNorm weights and their eps into the blob's f32 section.
+//   qnet_forward_kernel      Conv2d(1,32,k2,p1)+ReLU -> Conv2d(32,64,k2)+ReLU -> flatten -> Linear(1024,128) -> L x
+//                            TransformerEncoderLayer(128, dim_ff, relu, post-norm) at sequence length 1 -> Linear(128,4), and the
+//                            exploit action of DQNAgent.select_action (hybrid.py:943-953).
+//
+// What is computed. The reference feeds the encoder x.unsqueeze(1) with batch_first=False, and only ever calls the network with
+// one board, so every board is a sequence of ONE token: the softmax over one key is exactly 1.0 and the attention block is
+// out_proj(W_v x + b_v); Q, K and the head count cannot influence the result and are skipped. A layer is
+// x = norm1(x + out_proj(v(x))), x = norm2(x + linear2(relu(linear1(x)))). Board i's row is model(x[i:i+1]) in eval mode (the
+// reference never calls .eval(), so its dropout is live; like the other two policies this is the eval-mode function).
+//
+// Layout of the computation. Boards are the MFMA N dimension. A wavefront owns kE = 2 column tiles = 32 boards and runs the whole
+// network on them by itself, the activation held transposed in registers as 16-feature row tiles: register r of lane l (g = l >> 4,
+// c = l & 15) of tile t = x[feature 16 t + 4 g + r][board c]. That register is at once the MFMA's result layout and, as it stands,
+// the B operand of the next product (the packed weights carry the k order), so between conv1 and the Q-values nothing is
+// exchanged between lanes except LayerNorm's two cross-lane sums. A block is four such wavefronts (128 boards) that share nothing
+// but LDS space: no barrier after the boards are loaded.
+//   conv1   stays on the VALU in f32 (K = 4, inputs powers of two): the wavefront's boards lie in LDS as zero-padded 6 x 6 grids of
+//           tile values; per conv2 position a lane reads the 3 x 3 window that position's four taps see and computes the 32 conv1
+//           outputs it owns (its 8 channels x 4 taps) from it.
+//   conv2 + Linear(1024,128)  one position (y, x) at a time: conv2 is a 64 x 128 product per position (k = tap * 32 + channel), its
+//           64 outputs after ReLU are the K slice (k = channel, feature channel * 16 + position) of the 1024 -> 128 product and are
+//           consumed at once. The 1,024 features of a board never exist together.
+//   pair()  y = b2 + W2 . act(W1 x + b1), 32 hidden features at a time, a slice made and consumed at once: the feed-forward pair
+//           (act = ReLU, hidden = dim_ff) and the attention block (act = identity, W1 = the V rows of in_proj, W2 = out_proj,
+//           hidden = 128) are the same code. dim_ff costs no registers beyond one slice.
+// Precision. F32: f32 MFMA, exact f32 products and sums. BF16: the weights of conv2 and of every Linear and their inputs rounded
+// to bf16 (nearest even), f32 accumulation; conv1, the biases, LayerNorm (biased variance) and the residual adds are f32 in both.
+// Every output is one lane's fixed-order accumulation: no split-K, no atomics; a board's result does not depend on n, on its
+// place in the batch or on the launch geometry. Weight traffic: every wavefront streams the blob once per 32 boards (5.05 MB f32 /
+// 2.54 MB bf16 at dim_ff 2048, from L1 / L2). Measured (DESIGN.md has the arithmetic): f32 runs at 76 % of the MFMA peak and the
+// traffic does not bind; bf16 is bound by it (23 % of its peak), and a launch of any size takes at least one wavefront's serial
+// pass (0.89 ms f32, 0.35 ms bf16), so small batches are latency-bound. Compile with -ffp-contract=off.
+#include <hip/hip_runtime.h>
+#include <stdio.h>
+
+#include "../../include/g2048.h"
+#include "g2048_board.h"
+#include "g2048_host.h"
+
+namespace {
+
+using namespace g2048;
+
+typedef float f4 __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+
+// ------------------------------------------------------------------------------------------------ shapes and layouts --
+constexpr int kD = 128, kC1 = 32, kC2 = 64, kFlat = 1024, kK2 = 4 * kC1;      // widths; kK2: conv2's K per position
+constexpr int kFrag = 64 * 16;                       // bytes of one fragment
+
+// plain f32 layout (g2048_qnet_pack's input; include/g2048.h): the module's state-dict order
+constexpr int kPlC1W = 0, kPlC1B = kPlC1W + kC1 * 4, kPlC2W = kPlC1B + kC1, kPlC2B = kPlC2W + kC2 * kK2, kPlEmbW = kPlC2B + kC2,
+              kPlEmbB = kPlEmbW + kD * kFlat, kPlainLayer0 = kPlEmbB + kD;
+constexpr int kPlInW = 0, kPlInB = kPlInW + 3 * kD * kD, kPlOutW = kPlInB + 3 * kD, kPlOutB = kPlOutW + kD * kD, kPlW1 = kPlOutB + kD;
+__host__ __device__ constexpr int pl_b1(int ff) { return kPlW1 + ff * kD; }
+__host__ __device__ constexpr int pl_w2(int ff) { return pl_b1(ff) + ff; }
+__host__ __device__ constexpr int pl_b2(int ff) { return pl_w2(ff) + kD * ff; }
+__host__ __device__ constexpr int pl_norm(int ff) { return pl_b2(ff) + kD; }             // norm1.w norm1.b norm2.w norm2.b eps1 eps2
+__host__ __device__ constexpr int pl_layer(int ff) { return pl_norm(ff) + 4 * kD + 2; }
+constexpr int kPlFcW = 0, kPlFcB = kPlFcW + 4 * kD, kPlTail = kPlFcB + 4;
+
+// packed layout: the fragments of conv2 (4 row tiles, K 128), the embedding (8, K 1024); per layer of the V rows of in_proj (8),
+// out_proj (8), linear1 (dim_ff / 16), linear2 (8, K dim_ff); fc (1); then the f32 section. A matrix's fragments are ordered
+// [row tile o][chunk c]; a chunk is 16 input features (f32) or 32 (bf16). f32 section: conv1 weights [tap][channel] 128, conv1
+// bias 32, conv2 bias 64, embedding bias 128 | per layer: V bias 128, out_proj.bias 128, b1 dim_ff, b2 128, norm1.w norm1.b
+// norm2.w norm2.b 512, eps1 eps2 0 0 | fc bias 16 (4, then zeros).
+constexpr int kPHead = 4 * kC1 + kC1 + kC2 + kD;
+struct Layout {
+    int ff, layers, chunk;
+    __host__ __device__ Layout(bool bf16, int dim_ff, int n_layers) : ff(dim_ff), layers(n_layers), chunk(bf16 ? 32 : 16) {}
+    __host__ __device__ int chunks(int k) const { return k / chunk; }
+    __host__ __device__ size_t emb() const { return (size_t)(kC2 / 16) * chunks(kK2); }
+    __host__ __device__ size_t layer0() const { return emb() + (size_t)(kD / 16) * chunks(kFlat); }
+    __host__ __device__ size_t out_proj() const { return (size_t)(kD / 16) * chunks(kD); }   // fragment indices within a layer
+    __host__ __device__ size_t w1() const { return 2 * out_proj(); }
+    __host__ __device__ size_t w2() const { return w1() + (size_t)(ff / 16) * chunks(kD); }
+    __host__ __device__ size_t layer_frags() const { return w2() + (size_t)(kD / 16) * chunks(ff); }
+    __host__ __device__ size_t fc() const { return layer0() + (size_t)layers * layer_frags(); }
+    __host__ __device__ size_t params() const { return (fc() + chunks(kD)) * kFrag; }     // byte offset of the f32 section
+    __host__ __device__ int layer_params() const { return 3 * kD + ff + 4 * kD + 4; }
+    __host__ __device__ int n_params() const { return kPHead + layers * layer_params() + 16; }
+    __host__ __device__ size_t bytes() const { return params() + (size_t)n_params() * 4; }
+    __host__ __device__ size_t plain_floats() const { return (size_t)kPlainLayer0 + (size_t)layers * pl_layer(ff) + kPlTail; }
+};
+
+__device__ __host__ inline uint32_t bf16_rne(float v)
+{
+    const uint32_t u = __float_as_uint(v);
+    return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;        // finite inputs: round to nearest even by integer add
+}
+
+// ------------------------------------------------------------------------------------------------------------- pack --
+// One thread per packed 32-bit word (f32: one weight; bf16: two) of a matrix of `rows` rows (rows past them zero) and K columns:
+// word w of lane l of fragment (o, c) = W[16 o + (l & 15)][col(k)], k as the header says; packed column k is the plain column
+// (k % inner) * stride + k / inner (the identity for inner = K; conv2: inner 32, stride 4; the embedding: inner 64, stride 16).
+template <bool BF16>
+__global__ __launch_bounds__(256) void qnet_pack_matrix_kernel(const float *__restrict__ a, int rows, int K, int inner, int stride,
+                                                                unsigned words, uint32_t *__restrict__ packed)
+{
+    const unsigned w = blockIdx.x * 256u + threadIdx.x;
+    if (w >= words) return;
+    constexpr int kChunk = BF16 ? 32 : 16;
+    const int chunks = K / kChunk;
+    const int frag = (int)(w / 256u), lane = (int)(w % 256u) / 4, word = (int)(w % 4u);
+    const int o = frag / chunks, c = frag % chunks;
+    const int row = 16 * o + (lane & 15), g = lane >> 4;
+    auto weight = [&](int k) { return row < rows ? a[(size_t)row * K + (size_t)(k % inner) * stride + k / inner] : 0.0f; };
+    if (BF16) {
+        uint32_t pair[2];
+        for (int q = 0; q < 2; ++q) {
+            const int j = 2 * word + q;
+            pair[q] = bf16_rne(weight(32 * c + 16 * (j >> 2) + 4 * g + (j & 3)));
+        }
+        packed[w] = pair[0] | (pair[1] << 16);
+    } else {
+        packed[w] = __float_as_uint(weight(16 * c + 4 * g + word));
+    }
+}
+
+__global__ __launch_bounds__(256) void qnet_pack_params_kernel(const float *__restrict__ plain, int ff, int layers, int count,
+                                                                float *__restrict__ out)
+{
+    const int i = (int)(blockIdx.x * 256u + threadIdx.x);
+    if (i >= count) return;
+    const Layout lay(false, ff, layers);
+    int src = -1;
+    if (i < 4 * kC1) src = kPlC1W + (i % kC1) * 4 + i / kC1;            // [tap][channel] from [channel][1][2][2]
+    else if (i < 5 * kC1) src = kPlC1B + (i - 4 * kC1);
+    else if (i < 5 * kC1 + kC2) src = kPlC2B + (i - 5 * kC1);
+    else if (i < kPHead) src = kPlEmbB + (i - 5 * kC1 - kC2);
+    else if (i < kPHead + layers * lay.layer_params()) {
+        const int l = (i - kPHead) / lay.layer_params(), j = (i - kPHead) % lay.layer_params();
+        const int base = kPlainLayer0 + l * pl_layer(ff);
+        if (j < kD) src = base + kPlInB + 2 * kD + j;                    // the V third of in_proj_bias
+        else if (j < 2 * kD) src = base + kPlOutB + (j - kD);
+        else if (j < 2 * kD + ff) src = base + pl_b1(ff) + (j - 2 * kD);
+        else if (j < 3 * kD + ff) src = base + pl_b2(ff) + (j - 2 * kD - ff);
+        else if (j < 7 * kD + ff + 2) src = base + pl_norm(ff) + (j - 3 * kD - ff);
+    } else {
+        const int j = i - kPHead - layers * lay.layer_params(), base = kPlainLayer0 + layers * pl_layer(ff);
+        if (j < 4) src = base + kPlFcB + j;
+    }
+    out[i] = src >= 0 ? plain[src] : 0.0f;
+}
+
+// ---------------------------------------------------------------------------------------------------------- forward --
+constexpr int kWaves = 4, kE = 2;                    // wavefronts per block, column tiles per wavefront: 32 boards a wavefront
+constexpr int kWaveBoards = 16 * kE, kBlockBoards = kWaves * kWaveBoards;
+constexpr int kGrid = 36;                            // a board's zero-padded 6 x 6 grid; LDS holds [wave][grid cell][board]
+
+__device__ inline f4 relu(f4 v)
+{
+    return f4{fmaxf(v[0], 0.0f), fmaxf(v[1], 0.0f), fmaxf(v[2], 0.0f), fmaxf(v[3], 0.0f)};
+}
+
+__device__ inline bf16x8 to_bf16x8(f4 lo, f4 hi)
+{
+    // the float -> __bf16 cast is gfx950's v_cvt_pk_bf16_f32 (round to nearest even, two values per instruction)
+    return bf16x8{(__bf16)lo[0], (__bf16)lo[1], (__bf16)lo[2], (__bf16)lo[3], (__bf16)hi[0], (__bf16)hi[1], (__bf16)hi[2], (__bf16)hi[3]};
+}
+
+__device__ inline f4 load_f4(const void *p) { return *reinterpret_cast<const f4 *>(p); }
+__device__ inline f4 splat(float v) { return f4{v, v, v, v}; }
+
+// acc[e] += W(fragment) . act[e] over one chunk (f32: act[e][0] is the chunk's tile, 4 MFMAs; bf16: act[e][0..1], one MFMA)
+template <bool BF16>
+__device__ inline void chunk_mma(const unsigned char *frag, const f4 (&act)[kE][2], f4 (&acc)[kE])
+{
+    const f4 a = load_f4(frag);
+    if constexpr (BF16) {
+        const bf16x8 w = __builtin_bit_cast(bf16x8, a);
+#pragma unroll
+        for (int e = 0; e < kE; ++e) acc[e] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w, to_bf16x8(act[e][0], act[e][1]), acc[e], 0, 0, 0);
+    } else {
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+#pragma unroll
+            for (int e = 0; e < kE; ++e) acc[e] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[r], act[e][0][r], acc[e], 0, 0, 0);
+    }
+}
+
+// acc[e] += (row tile o of the matrix at `mat`, K = 16 T) . x[e]  (x: the T feature tiles of each column tile)
+template <bool BF16, int T>
+__device__ inline void project(const unsigned char *mat, int o, int lane, const f4 (&x)[kE][T], f4 (&acc)[kE])
+{
+    constexpr int TPC = BF16 ? 2 : 1, C = T / TPC;
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+        f4 in[kE][2];
+#pragma unroll
+        for (int e = 0; e < kE; ++e) {
+            in[e][0] = x[e][TPC * c];
+            in[e][1] = x[e][TPC * c + TPC - 1];
+        }
+        chunk_mma<BF16>(mat + ((size_t)(o * C + c) * 64 + lane) * 16, in, acc);
+    }
+}
+
+// y[e][m] += (row tile m of the matrix at `mat`, c2 chunks a row tile) . (the 32-feature slice s of its K, tiles h[e][0..1])
+template <bool BF16>
+__device__ inline void consume32(const unsigned char *mat, int c2, int s, int lane, const f4 (&h)[kE][2], f4 (&y)[kE][8])
+{
+    constexpr int CPS = BF16 ? 1 : 2;                // chunks per 32-feature slice
+#pragma unroll
+    for (int t = 0; t < CPS; ++t) {
+        const int c = CPS * s + t;
+#pragma unroll
+        for (int m = 0; m < 8; ++m) {
+            f4 in[kE][2], acc[kE];
+#pragma unroll
+            for (int e = 0; e < kE; ++e) {
+                in[e][0] = h[e][t];
+                in[e][1] = h[e][1];
+                acc[e] = y[e][m];
+            }
+            chunk_mma<BF16>(mat + ((size_t)(m * c2 + c) * 64 + lane) * 16, in, acc);
+#pragma unroll
+            for (int e = 0; e < kE; ++e) y[e][m] = acc[e];
+        }
+    }
+}
+
+// y = b2 + W2 . act(W1 x + b1), the hidden layer 32 features at a time (act: ReLU or the identity)
+template <bool BF16, bool RELU>
+__device__ inline void pair(const unsigned char *W1, const float *b1, const unsigned char *W2, const float *b2, int hidden, int lane,
+                            int g, const f4 (&x)[kE][8], f4 (&y)[kE][8])
+{
+    const int c2 = hidden / (BF16 ? 32 : 16);
+#pragma unroll
+    for (int m = 0; m < 8; ++m) {
+        const f4 b = load_f4(b2 + 16 * m + 4 * g);
+#pragma unroll
+        for (int e = 0; e < kE; ++e) y[e][m] = b;
+    }
+#pragma unroll 1
+    for (int s = 0; s < hidden / 32; ++s) {
+        f4 h[kE][2];
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            f4 acc[kE];
+            const f4 b = load_f4(b1 + 32 * s + 16 * t + 4 * g);
+#pragma unroll
+            for (int e = 0; e < kE; ++e) acc[e] = b;
+            project<BF16, 8>(W1, 2 * s + t, lane, x, acc);
+#pragma unroll
+            for (int e = 0; e < kE; ++e) h[e][t] = RELU ? relu(acc[e]) : acc[e];
+        }
+        consume32<BF16>(W2, c2, s, lane, h, y);
+    }
+}
+
+__device__ inline float lanes_sum(float v)           // over the four lanes c, c + 16, c + 32, c + 48, the same on all four
+{
+    v += __shfl_xor(v, 16);
+    return v + __shfl_xor(v, 32);
+}
+
+// x = LayerNorm(x + y) over the 128 features of every board column; np = weight[128] bias[128], biased variance
+__device__ inline void add_norm(f4 (&x)[kE][8], const f4 (&y)[kE][8], const float *np, float eps, int g)
+{
+#pragma unroll
+    for (int e = 0; e < kE; ++e) {
+        float s = 0.0f;
+#pragma unroll
+        for (int t = 0; t < 8; ++t) {
+            x[e][t] = x[e][t] + y[e][t];
+            s += (x[e][t][0] + x[e][t][1]) + (x[e][t][2] + x[e][t][3]);
+        }
+        const float mean = lanes_sum(s) / (float)kD;
+        float q = 0.0f;
+#pragma unroll
+        for (int t = 0; t < 8; ++t) {
+            x[e][t] = x[e][t] - splat(mean);
+            const f4 d2 = x[e][t] * x[e][t];
+            q += (d2[0] + d2[1]) + (d2[2] + d2[3]);
+        }
+        const float rstd = 1.0f / sqrtf(lanes_sum(q) / (float)kD + eps);
+#pragma unroll
+        for (int t = 0; t < 8; ++t) x[e][t] = x[e][t] * splat(rstd) * load_f4(np + 16 * t + 4 * g) + load_f4(np + kD + 16 * t + 4 * g);
+    }
+}
+
+// Two blocks per compute unit (two wavefronts per SIMD, each covering the other's fragment loads): 236 (f32) / 230 (bf16) VGPRs,
+// no scratch.
+template <bool BF16>
+__global__ __launch_bounds__(64 * kWaves, 2) void qnet_forward_kernel(const uint32_t *__restrict__ boards, const unsigned char *__restrict__ W,
+                                                                    float4 *__restrict__ q_out, uint8_t *__restrict__ actions, size_t n,
+                                                                    int ff, int layers)
+{
+    __shared__ float lds[kWaves][kGrid][kWaveBoards];
+    const Layout lay(BF16, ff, layers);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4, col = lane & 15;
+    const float *P = reinterpret_cast<const float *>(W + lay.params());
+    const size_t env0 = (size_t)blockIdx.x * kBlockBoards + (size_t)wave * kWaveBoards;
+
+    // the wavefront's boards as zero-padded grids of tile values (2 ** code, 0 for empty); boards past n read as empty
+    float (*grid)[kWaveBoards] = lds[wave];
+    for (int i = lane; i < kGrid * kWaveBoards; i += 64) (&grid[0][0])[i] = 0.0f;
+    __syncthreads();
+#pragma unroll
+    for (int e = 0; e < kE; ++e) {
+        const size_t env = env0 + 16 * e + col;
+        const uint32_t row = env < n ? boards[env * 4 + g] : 0u;       // lane (g, c): row g of board c
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const uint32_t code = (row >> (8 * k)) & 0xffu;
+            grid[6 * (g + 1) + k + 1][16 * e + col] = code ? __uint_as_float((127u + code) << 23) : 0.0f;
+        }
+    }
+    __syncthreads();
+
+    // conv1 -> conv2 -> Linear(1024,128), one conv2 position at a time
+    f4 x[kE][8];
+#pragma unroll
+    for (int m = 0; m < 8; ++m) {
+        const f4 b = load_f4(P + 5 * kC1 + kC2 + 16 * m + 4 * g);
+#pragma unroll
+        for (int e = 0; e < kE; ++e) x[e][m] = b;
+    }
+    {
+        const int cemb = kFlat / (BF16 ? 32 : 16);
+#pragma unroll 1
+        for (int p = 0; p < 16; ++p) {
+            // The blob's address is made opaque once per position: conv1's weights and conv2's fragments do not depend on the
+            // position, and hoisted out of this loop they would be held in registers the loop has none to spare for.
+            const unsigned char *Wc2 = W;
+            asm volatile("" : "+s"(Wc2));
+            const unsigned char *Wemb = Wc2 + lay.emb() * kFrag;
+            const float *c1w = reinterpret_cast<const float *>(Wc2 + lay.params()), *c1b = c1w + 4 * kC1, *c2b = c1w + 5 * kC1;
+            const int py = p >> 2, px = p & 3;
+            float win[kE][3][3];                     // the padded grid's cells (py .. py + 2, px .. px + 2)
+#pragma unroll
+            for (int e = 0; e < kE; ++e)
+#pragma unroll
+                for (int i = 0; i < 3; ++i)
+#pragma unroll
+                    for (int j = 0; j < 3; ++j) win[e][i][j] = grid[6 * (py + i) + px + j][16 * e + col];
+            f4 c2[kE][4];
+#pragma unroll
+            for (int o = 0; o < 4; ++o) {
+                const f4 b = load_f4(c2b + 16 * o + 4 * g);
+#pragma unroll
+                for (int e = 0; e < kE; ++e) c2[e][o] = b;
+            }
+#pragma unroll
+            for (int tap = 0; tap < 4; ++tap) {      // conv2's tap (dy, dx): conv1's output at (py + dy, px + dx), 32 channels
+                const int dy = tap >> 1, dx = tap & 1;
+                f4 c1[kE][2];
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {        // channels 16 h + 4 g + r
+                    const int ch = 16 * h + 4 * g;
+                    const f4 w0 = load_f4(c1w + ch), w1 = load_f4(c1w + kC1 + ch), w2 = load_f4(c1w + 2 * kC1 + ch),
+                             w3 = load_f4(c1w + 3 * kC1 + ch), b = load_f4(c1b + ch);
+#pragma unroll
+                    for (int e = 0; e < kE; ++e)
+                        c1[e][h] = relu((((b + w0 * splat(win[e][dy][dx])) + w1 * splat(win[e][dy][dx + 1])) +
+                                         w2 * splat(win[e][dy + 1][dx])) + w3 * splat(win[e][dy + 1][dx + 1]));
+                }
+                // k = tap * 32 + channel: the 32-feature slice `tap` of conv2's K
+#pragma unroll
+                for (int t = 0; t < (BF16 ? 1 : 2); ++t) {
+                    const int c = (BF16 ? 1 : 2) * tap + t;
+#pragma unroll
+                    for (int o = 0; o < 4; ++o) {
+                        f4 in[kE][2], acc[kE];
+#pragma unroll
+                        for (int e = 0; e < kE; ++e) {
+                            in[e][0] = c1[e][t];
+                            in[e][1] = c1[e][1];
+                            acc[e] = c2[e][o];
+                        }
+                        chunk_mma<BF16>(Wc2 + ((size_t)(o * (kK2 / (BF16 ? 32 : 16)) + c) * 64 + lane) * 16, in, acc);
+#pragma unroll
+                        for (int e = 0; e < kE; ++e) c2[e][o] = acc[e];
+                    }
+                }
+            }
+            // the embedding's K slice k = p * 64 + channel (plain feature channel * 16 + p), two 32-feature slices
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                f4 h[kE][2];
+#pragma unroll
+                for (int e = 0; e < kE; ++e) {
+                    h[e][0] = relu(c2[e][2 * s]);
+                    h[e][1] = relu(c2[e][2 * s + 1]);
+                }
+                consume32<BF16>(Wemb, cemb, 2 * p + s, lane, h, x);
+            }
+        }
+    }
+
+    // the encoder layers at sequence length 1
+#pragma unroll 1
+    for (int l = 0; l < layers; ++l) {
+        const unsigned char *Wl = W + (lay.layer0() + (size_t)l * lay.layer_frags()) * kFrag;
+        const float *Pl = P + kPHead + l * lay.layer_params();
+        const float *bv = Pl, *bo = Pl + kD, *b1 = Pl + 2 * kD, *b2 = b1 + ff, *norms = b2 + kD;
+        f4 y[kE][8];
+        pair<BF16, false>(Wl, bv, Wl + lay.out_proj() * kFrag, bo, kD, lane, g, x, y);
+        add_norm(x, y, norms, norms[4 * kD], g);
+        pair<BF16, true>(Wl + lay.w1() * kFrag, b1, Wl + lay.w2() * kFrag, b2, ff, lane, g, x, y);
+        add_norm(x, y, norms + 2 * kD, norms[4 * kD + 1], g);
+    }
+
+    // Linear(128,4): rows 0..3 of one row tile, on lanes 0..15 (g = 0); the exploit action from the board's own valid moves
+    const float *Pt = P + kPHead + layers * lay.layer_params();
+    f4 q[kE];
+    {
+        const f4 b = load_f4(Pt + 4 * g);
+#pragma unroll
+        for (int e = 0; e < kE; ++e) q[e] = b;
+    }
+    project<BF16, 8>(W + lay.fc() * kFrag, 0, lane, x, q);
+    if (g != 0) return;
+#pragma unroll
+    for (int e = 0; e < kE; ++e) {
+        const size_t env = env0 + 16 * e + col;
+        if (env >= n) continue;
+        q_out[env] = make_float4(q[e][0], q[e][1], q[e][2], q[e][3]);
+        if (actions) {
+            const uint4 bw = reinterpret_cast<const uint4 *>(boards)[env];
+            const uint32_t mask = valid_mask_env(Board{{bw.x, bw.y, bw.z, bw.w}});
+            // hybrid.py:949-953: q[i] = -1e9 where invalid, then np.argmax (ties to the lowest index; no valid move: action 0)
+            float best = (mask & 1u) ? q[e][0] : -1e9f;
+            uint32_t a = 0u;
+#pragma unroll
+            for (int k = 1; k < 4; ++k) {
+                const float v = ((mask >> k) & 1u) ? q[e][k] : -1e9f;
+                if (v > best) { best = v; a = (uint32_t)k; }
+            }
+            actions[env] = (uint8_t)a;
+        }
+    }
+}
+
+bool good_shape(int dim_ff, int n_layers) { return dim_ff >= 32 && dim_ff % 32 == 0 && dim_ff <= 65536 && n_layers >= 1 && n_layers <= 64; }
+bool good_precision(int p) { return p == G2048_POLICY_F32 || p == G2048_POLICY_BF16; }
+
+}  // namespace
+
+extern "C" {
+
+size_t g2048_qnet_packed_bytes(int precision, int dim_ff, int n_layers)
+{
+    if (!good_precision(precision) || !good_shape(dim_ff, n_layers)) return 0;
+    return Layout(precision == G2048_POLICY_BF16, dim_ff, n_layers).bytes();
+}
+
+int g2048_qnet_pack(const float *plain_f32, int dim_ff, int n_layers, int precision, void *packed_out, void *stream)
+{
+    if (!plain_f32 || !packed_out) return fail(G2048_ERR_ARG, "g2048_qnet_pack: null pointer");
+    if (!aligned(plain_f32, 4) || !aligned(packed_out, 16)) return fail(G2048_ERR_ARG, "g2048_qnet_pack: misaligned pointer");
+    if (!good_precision(precision)) return fail(G2048_ERR_ARG, "g2048_qnet_pack: unknown precision");
+    if (!good_shape(dim_ff, n_layers))
+        return fail(G2048_ERR_ARG, "g2048_qnet_pack: dim_ff must be a multiple of 32 (32 .. 65536) and n_layers 1 .. 64");
+    const bool bf16 = precision == G2048_POLICY_BF16;
+    const Layout lay(bf16, dim_ff, n_layers);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    auto *out = static_cast<unsigned char *>(packed_out);
+    // one launch per matrix: rows x K into the fragments from index `frag`, packed column k = plain (k % inner) * stride + k / inner
+    auto matrix = [&](const float *a, int rows, int K, int inner, int stride, size_t frag) {
+        const unsigned words = (unsigned)(((rows + 15) / 16) * lay.chunks(K)) * 256u;
+        with_bool(bf16, [&](auto BF16) {
+            hipLaunchKernelGGL(qnet_pack_matrix_kernel<decltype(BF16)::value>, dim3(words / 256u), dim3(256), 0, s, a, rows, K, inner, stride,
+                               words, reinterpret_cast<uint32_t *>(out + frag * kFrag));
+        });
+    };
+    matrix(plain_f32 + kPlC2W, kC2, kK2, kC1, 4, 0);
+    matrix(plain_f32 + kPlEmbW, kD, kFlat, kC2, 16, lay.emb());
+    for (int l = 0; l < n_layers; ++l) {
+        const float *p = plain_f32 + kPlainLayer0 + (size_t)l * pl_layer(dim_ff);
+        const size_t f = lay.layer0() + (size_t)l * lay.layer_frags();
+        matrix(p + kPlInW + 2 * kD * kD, kD, kD, kD, 1, f);              // the V rows 256 .. 383 of in_proj_weight
+        matrix(p + kPlOutW, kD, kD, kD, 1, f + lay.out_proj());
+        matrix(p + kPlW1, dim_ff, kD, kD, 1, f + lay.w1());
+        matrix(p + pl_w2(dim_ff), kD, dim_ff, dim_ff, 1, f + lay.w2());
+    }
+    const float *t = plain_f32 + kPlainLayer0 + (size_t)n_layers * pl_layer(dim_ff);
+    matrix(t + kPlFcW, 4, kD, kD, 1, lay.fc());
+    const int count = lay.n_params();
+    hipLaunchKernelGGL(qnet_pack_params_kernel, dim3(blocks_for((size_t)count, 256)), dim3(256), 0, s, plain_f32, dim_ff, n_layers, count,
+                       reinterpret_cast<float *>(out + lay.params()));
+    return check_launch("g2048_qnet_pack");
+}
+
+int g2048_qnet_forward(const void *boards, const void *packed, float *q_out, uint8_t *actions_out_or_null, size_t n, int dim_ff,
+                       int n_layers, uint32_t opts, void *stream)
+{
+    if (n == 0) return G2048_OK;
+    if (!boards || !packed || !q_out) return fail(G2048_ERR_ARG, "g2048_qnet_forward: null pointer");
+    if (!aligned(boards, 16) || !aligned(packed, 16) || !aligned(q_out, 16))
+        return fail(G2048_ERR_ARG, "g2048_qnet_forward: misaligned pointer (boards, packed weights, q: 16 bytes)");
+    if (opts != G2048_POLICY_F32 && opts != G2048_POLICY_BF16) return fail(G2048_ERR_ARG, "g2048_qnet_forward: unknown opts (precision)");
+    if (!good_shape(dim_ff, n_layers))
+        return fail(G2048_ERR_ARG, "g2048_qnet_forward: dim_ff must be a multiple of 32 (32 .. 65536) and n_layers 1 .. 64");
+    const size_t blocks = (n + kBlockBoards - 1) / kBlockBoards;
+    if (blocks > 0x7fffffffu) return fail(G2048_ERR_ARG, "g2048_qnet_forward: n too large for one launch");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    with_bool(opts == G2048_POLICY_BF16, [&](auto BF16) {
+        hipLaunchKernelGGL(qnet_forward_kernel<decltype(BF16)::value>, dim3((unsigned)blocks), dim3(64 * kWaves), 0, s,
+                           static_cast<const uint32_t *>(boards), static_cast<const unsigned char *>(packed),
+                           reinterpret_cast<float4 *>(q_out), actions_out_or_null, n, dim_ff, n_layers);
+    });
+    return check_launch("g2048_qnet_forward");
+}
+
+}  // extern "C"

@@ -94,6 +94,9 @@ SIGNATURES = {
     "g2048_play_policy_games": (_int, [_vp] * 10 + [_int, _u64, _u64, _sz, _u32, _u32, _vp, _sz, _vp]),
     "g2048_play_tpolicy_workspace": (_sz, [_sz]),
     "g2048_play_tpolicy_games": (_int, [_vp] * 3 + [_int, _int] + [_vp] * 7 + [_int, _u64, _u64, _sz, _u32, _u32, _vp, _sz, _vp]),
+    "g2048_qnet_packed_bytes": (_sz, [_int, _int, _int]),
+    "g2048_qnet_pack": (_int, [_vp, _int, _int, _int, _vp, _vp]),
+    "g2048_qnet_forward": (_int, [_vp, _vp, _vp, _vp, _sz, _int, _int, _u32, _vp]),
 }
 
 

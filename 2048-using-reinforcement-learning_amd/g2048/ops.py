@@ -518,6 +518,65 @@ def tpolicy_forward(boards, packed, dim_ff, n_layers, precision="f32", probs=Non
     return probs if value is None else (probs, value)
 
 
+def qnet_plain_floats(dim_ff, n_layers):
+    """Floats of the plain parameter buffer g2048_qnet_pack reads (include/g2048.h)."""
+    return 140132 + int(n_layers) * (66690 + 257 * int(dim_ff))
+
+
+def qnet_packed_bytes(precision="f32", dim_ff=2048, n_layers=2):
+    """Bytes of the packed hybrid Q-network (g2048_qnet_packed_bytes)."""
+    if precision not in POLICY_PRECISIONS:
+        raise ValueError("g2048: precision must be 'f32' or 'bf16'")
+    nb = L.lib().g2048_qnet_packed_bytes(POLICY_PRECISIONS[precision], int(dim_ff), int(n_layers))
+    if nb == 0:
+        raise ValueError("g2048: dim_ff must be a multiple of 32 and n_layers at least 1")
+    return nb
+
+
+def qnet_pack(plain, dim_ff, n_layers, precision="f32", out=None):
+    """Pack the hybrid Q-network's plain float32 parameters (state-dict order plus the two LayerNorm eps per layer:
+    include/g2048.h) into the blob g2048_qnet_forward streams. Writes `out` (uint8, qnet_packed_bytes) in place when given, on
+    the current stream, without synchronising."""
+    L.require_device_tensor(plain, torch.float32, None, "plain")
+    nb = qnet_packed_bytes(precision, dim_ff, n_layers)
+    if plain.dim() != 1 or plain.numel() != qnet_plain_floats(dim_ff, n_layers):
+        raise ValueError("g2048: plain must be a flat float32 tensor of %d parameters" % qnet_plain_floats(dim_ff, n_layers))
+    if out is None:
+        out = torch.empty(nb, dtype=torch.uint8, device=plain.device)
+    L.require_device_tensor(out, torch.uint8, None, "out")
+    if out.numel() != nb:
+        raise ValueError("g2048: out must hold %d bytes" % nb)
+    L.call(plain.device, L.lib().g2048_qnet_pack, plain.data_ptr(), int(dim_ff), int(n_layers), POLICY_PRECISIONS[precision],
+           out.data_ptr(), L.stream_ptr(plain.device))
+    return out
+
+
+def qnet_forward(boards, packed, dim_ff, n_layers, precision="f32", q=None, actions=None, want_actions=False):
+    """The hybrid agent's Q-network on the packed boards in ONE launch (g2048_qnet_forward). Returns q float32 (n,4), or (actions
+    uint8 (n,), q) when `actions` is given or want_actions is set: the exploit action of DQNAgent.select_action (the argmax of q
+    over the env's valid moves, ties to the lowest index, 0 for a board with no valid move)."""
+    L.require_device_tensor(boards, torch.uint8, (16,), "boards")
+    L.require_device_tensor(packed, torch.uint8, None, "packed")
+    if packed.numel() != qnet_packed_bytes(precision, dim_ff, n_layers):
+        raise ValueError("g2048: packed must be a %s blob of %d bytes" % (precision, qnet_packed_bytes(precision, dim_ff, n_layers)))
+    n, dev = boards.shape[0], boards.device
+    if q is None:
+        q = torch.empty((n, 4), dtype=torch.float32, device=dev)
+    L.require_device_tensor(q, torch.float32, (4,), "q")
+    if q.shape[0] != n:
+        raise ValueError("g2048: q must have n rows")
+    if want_actions and actions is None:
+        actions = torch.empty(n, dtype=torch.uint8, device=dev)
+    if actions is not None:
+        L.require_device_tensor(actions, torch.uint8, (), "actions")
+        if actions.shape[0] != n:
+            raise ValueError("g2048: actions must have n entries")
+    L.call(dev, L.lib().g2048_qnet_forward, boards.data_ptr(), packed.data_ptr(), q.data_ptr(),
+           actions.data_ptr() if actions is not None else None, n, int(dim_ff), int(n_layers), POLICY_PRECISIONS[precision],
+           L.stream_ptr(dev))
+    return q if actions is None else (actions, q)
+
+
 class SeenStates:
     """The `seen_states` set and `highest_tile_seen` of PPOAgent (agents/ppo_agent.py:171-176) for ordered batches of
     transitions, resident on the GPU: an open-addressing hash set keyed by the 16-byte board (include/g2048.h,

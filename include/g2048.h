@@ -49,7 +49,7 @@ extern "C" {
                                       MERGE_POTENTIAL; no entry point added or removed;
                                       later, additive: g2048_policy_packed_bytes / _pack / _forward,
                                       g2048_play_policy_games / _workspace, g2048_tpolicy_packed_bytes / _pack / _forward,
-                                      g2048_play_tpolicy_games / _workspace)
+                                      g2048_play_tpolicy_games / _workspace, g2048_qnet_packed_bytes / _pack / _forward)
                                       4: round 5 (export table = this header + g2048_testing.h exactly: test / measurement hooks moved there,
                                       internal symbols hidden; g2048_replay_games also clamps a game's length to actions_stride)
                                       3: round 4 (actions_out of the g2048_play_games family, g2048_replay_games, g2048_env_step,
@@ -537,6 +537,54 @@ G2048_API int g2048_play_tpolicy_games(void *boards_inout, uint32_t *score_inout
                              double *reward_sum_out_or_null, uint8_t *alive_out, uint8_t *actions_out_or_null, int max_moves,
                              uint64_t seed, uint64_t game_id_base, size_t n_games, uint32_t opts, uint32_t max_blocks, void *workspace,
                              size_t workspace_bytes, void *stream);
+
+/* Forward pass of the hybrid agent's CNN-transformer Q-network (agents/hybrid.py:700-727, HybridDQN) on the matrix cores, in ONE
+ * launch, read from the packed boards. Per board, with x = the 16 raw tile values as float32 (2 ** code, 0 for empty: the env's
+ * get_state(), not the / 15 of the policies): Conv2d(1,32,k=2,s=1,p=1) + ReLU (32 x 5 x 5) -> Conv2d(32,64,k=2,s=1,p=0) + ReLU
+ * (64 x 4 x 4) -> flatten channel-major (feature c * 16 + y * 4 + x) -> Linear(1024,128) -> n_layers x
+ * nn.TransformerEncoderLayer(d_model 128, dim_ff, ReLU, post-norm) -> Linear(128,4) = Q[4].
+ *   Sequence length 1. The reference builds the layer without batch_first and feeds it x.unsqueeze(1), so a batch of B boards is ONE
+ *     sequence of B tokens that attend to each other; it only ever calls the network with one board. Every board here is its own
+ *     sequence of one token: row i is model(x[i:i+1]), equally the module with the encoder input reshaped to (1, B, 128). The
+ *     softmax over one key is exactly 1.0, so the attention block is out_proj(W_v x + b_v): a layer is x = norm1(x +
+ *     out_proj(v(x))), x = norm2(x + linear2(relu(linear1(x)))). Q, K and the head count cannot influence the result and are
+ *     not read.
+ *   Eval mode. The reference never calls .eval(), so its dropout is live even in select_action; this is the eval-mode function,
+ *     as the two policies are.
+ * The widths 32, 64, 1024 and 128 are fixed; dim_ff (a multiple of 32) and n_layers (>= 1) are arguments.
+ *
+ *   g2048_qnet_packed_bytes  bytes of the packed blob (0 for a bad argument); a multiple of 16.
+ *   g2048_qnet_pack          rearranges the plain f32 parameters into that blob, on `stream` (no synchronisation; packing into
+ *                            the same buffer again updates later forward passes). plain_f32 holds, back to back in the module's
+ *                            state-dict order, every weight row-major [out][in] as torch stores it:
+ *                              cnn.0.weight [32][1][2][2], cnn.0.bias [32], cnn.2.weight [64][32][2][2], cnn.2.bias [64],
+ *                                embedding.weight [128][1024], embedding.bias [128]: 139,616 floats;
+ *                              per layer: in_proj_weight [384][128] and in_proj_bias [384] whole (only the V rows 256..383 are
+ *                                used), out_proj.weight [128][128], out_proj.bias [128], linear1.weight [dim_ff][128],
+ *                                linear1.bias [dim_ff], linear2.weight [128][dim_ff], linear2.bias [128], norm1.weight [128],
+ *                                norm1.bias [128], norm2.weight [128], norm2.bias [128], then norm1.eps, norm2.eps (two floats,
+ *                                not in the state dict): 66,690 + 257 dim_ff floats;
+ *                              fc.weight [4][128], fc.bias [4]: 516 floats.
+ *                            In all 140,132 + n_layers (66,690 + 257 dim_ff) floats (the reference's dim_ff 2048, 2 layers:
+ *                            1,326,180 parameters + 4 eps).
+ *   g2048_qnet_forward       q_out[i] (float32 n x 4) = Q of board i and, if actions_out_or_null is given, actions_out_or_null[i]
+ *                            = the exploit action of DQNAgent.select_action (hybrid.py:943-953): Q of every move that is invalid
+ *                            under the env's valid-move mask of that board (G2048_VALID_ENV semantics) replaced by -1e9, then the
+ *                            argmax with ties to the lowest index (np.argmax); a board with no valid move gets action 0. q_out
+ *                            holds the Q-values as computed, without that replacement. opts = the precision the blob was packed
+ *                            with:
+ *                              G2048_POLICY_F32   f32 MFMA, exact f32 products and sums (the parity path);
+ *                              G2048_POLICY_BF16  the weights and the matmul inputs of conv2 and of every Linear rounded to bf16
+ *                                                 (nearest even), f32 accumulation; conv1 stays in f32.
+ *                            LayerNorm statistics (biased variance), the biases and the residual adds are f32 in both. Boards,
+ *                            blob and q_out 16-byte aligned. Every output is one fixed-order accumulation (no split-K, no
+ *                            atomics) that does not depend on n, on the board's place in the batch or on the launch geometry.
+ *                            Arguments are checked before any device call; n == 0 returns G2048_OK. Nothing past row n is
+ *                            written. */
+G2048_API size_t g2048_qnet_packed_bytes(int precision, int dim_ff, int n_layers);
+G2048_API int g2048_qnet_pack(const float *plain_f32, int dim_ff, int n_layers, int precision, void *packed_out, void *stream);
+G2048_API int g2048_qnet_forward(const void *boards, const void *packed, float *q_out, uint8_t *actions_out_or_null, size_t n, int dim_ff,
+                       int n_layers, uint32_t opts, void *stream);
 #ifdef __cplusplus
 }
 #endif
