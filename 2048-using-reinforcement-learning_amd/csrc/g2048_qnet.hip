@@ -1,5 +1,5 @@
 // g2048_qnet.hip -- the hybrid agent's CNN-transformer Q-network (agents/hybrid.py:700-727, HybridDQN, in eval mode, one board
-// per call) on the matrix cores of gfx950, one launch per forward pass (C-ABI: include/g2048.h, g2048_qnet_*).
+// per call) on the matrix cores of gfx950, one launch per forward pass (C-ABI: include/g2048.h, g2048_qnet_*, g2048_play_qnet_*).
 //
 //   qnet_pack_matrix_kernel  one weight matrix [rows][K] into 1 KiB MFMA fragments (a lane's A operand is one 16-byte load), its
 //                            columns permuted so that conv2's and the embedding's K run in the order the forward produces them.
@@ -7,6 +7,10 @@
 //   qnet_forward_kernel      Conv2d(1,32,k2,p1)+ReLU -> Conv2d(32,64,k2)+ReLU -> flatten -> Linear(1024,128) -> L x
 //                            TransformerEncoderLayer(128, dim_ff, relu, post-norm) at sequence length 1 -> Linear(128,4), and the
 //                            exploit action of DQNAgent.select_action (hybrid.py:943-953).
+//   qnet_select_kernel       the whole of select_action (:909-953, use_beam_search = False) on given Q-values: epsilon coin,
+//                            exploit argmax, exploration biased to RIGHT / DOWN (g2048_qnet_select_actions).
+//   qnet_play_kernel         complete games (evaluate_agent, :1176-1210) in one launch, 32 game slots a wavefront
+//                            (g2048_play_qnet_games).
 //
 // What is computed. The reference feeds the encoder x.unsqueeze(1) with batch_first=False, and only ever calls the network with
 // one board, so every board is a sequence of ONE token: the softmax over one key is exactly 1.0 and the attention block is
@@ -39,9 +43,12 @@
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 
+#include <algorithm>
+
 #include "../../include/g2048.h"
 #include "g2048_board.h"
 #include "g2048_host.h"
+#include "g2048_rng.h"
 
 namespace {
 
@@ -149,7 +156,7 @@ __global__ __launch_bounds__(256) void qnet_pack_params_kernel(const float *__re
     out[i] = src >= 0 ? plain[src] : 0.0f;
 }
 
-// ---------------------------------------------------------------------------------------------------------- forward --
+// ------------------------------------------------------------------------------------------------- forward's parts --
 constexpr int kWaves = 4, kE = 2;                    // wavefronts per block, column tiles per wavefront: 32 boards a wavefront
 constexpr int kWaveBoards = 16 * kE, kBlockBoards = kWaves * kWaveBoards;
 constexpr int kGrid = 36;                            // a board's zero-padded 6 x 6 grid; LDS holds [wave][grid cell][board]
@@ -286,6 +293,184 @@ __device__ inline void add_norm(f4 (&x)[kE][8], const f4 (&y)[kE][8], const floa
     }
 }
 
+// ---------------------------------------------------------------------------------------------------- select_action --
+// The exploit half of DQNAgent.select_action (hybrid.py:943-953): q[i] = -1e9 where invalid, then np.argmax (ties to the lowest
+// index; no valid move: action 0). The forward kernel, the select kernel and the game kernel all decide with this function.
+__device__ inline uint32_t exploit_action(float q0, float q1, float q2, float q3, uint32_t mask)
+{
+    const float q[4] = {q0, q1, q2, q3};
+    float best = (mask & 1u) ? q[0] : -1e9f;
+    uint32_t a = 0u;
+#pragma unroll
+    for (int k = 1; k < 4; ++k) {
+        const float v = ((mask >> k) & 1u) ? q[k] : -1e9f;
+        if (v > best) { best = v; a = (uint32_t)k; }
+    }
+    return a;
+}
+
+// The whole of select_action at use_beam_search = False for one board: the coin u = (draw 1 >> 8) * 2^-24 < epsilon decides for
+// exploration (hybrid.py:912), which samples among the valid moves with the preferences (1, 1, 3, 3) when the max tile is >= 64
+// and np.argmax(board) is cell (3,3) -- cell 15's code is >= 6 and strictly above every other cell's -- and (1, 1, 1, 1)
+// otherwise (:914-936, random.choices(valid_actions, weights)): sample_action with draw 0. The normalised preferences are exact
+// in f32 and sample_action's + 1e-10f does not change them. A dead board samples among all four (:918-919).
+__device__ inline uint32_t select_action(uint32_t exploit, const Board &b, uint32_t mask, float epsilon, Keys k, uint64_t id, bool &explored)
+{
+    const float u = (float)(rng_draw(k.k0, k.k1, id, 1u) >> 8) * 5.9604644775390625e-08f;
+    explored = u < epsilon;
+    if (!explored) return exploit;
+    const uint32_t corner = b.w[3] >> 24;
+    uint32_t rest = 0u;
+#pragma unroll
+    for (int c = 0; c < 15; ++c) {
+        const uint32_t v = (b.w[c >> 2] >> (8 * (c & 3))) & 0xffu;
+        rest = v > rest ? v : rest;
+    }
+    const bool biased = corner >= 6u && corner > rest;
+    const float lo = biased ? 0.125f : 0.25f, hi = biased ? 0.375f : 0.25f;
+    float pa;
+    return sample_action(lo, lo, hi, hi, mask, rng_draw(k.k0, k.k1, id, 0u), pa);
+}
+
+__global__ __launch_bounds__(256) void qnet_select_kernel(const float4 *__restrict__ q, const uint4 *__restrict__ boards,
+                                                           uint8_t *__restrict__ actions, uint8_t *__restrict__ explored_out, float epsilon,
+                                                           uint32_t k0, uint32_t k1, uint64_t id_base, size_t n)
+{
+    const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const float4 qi = q[i];
+    const uint4 bw = boards[i];
+    const Board b{{bw.x, bw.y, bw.z, bw.w}};
+    const uint32_t mask = valid_mask_env(b);
+    bool explored;
+    actions[i] = (uint8_t)select_action(exploit_action(qi.x, qi.y, qi.z, qi.w, mask), b, mask, epsilon, Keys{k0, k1}, id_base + i, explored);
+    if (explored_out) explored_out[i] = explored ? 1 : 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------- forward --
+// The forward pass in two pieces that qnet_forward_kernel and the game-playing kernel (qnet_play_kernel, below) share. Both
+// expand exactly this text, and a wavefront's pass depends on nothing but its own 32 boards and the blob, so the two kernels give
+// bit-identical Q-values for the same board. Macros, not functions, for the reason TPOLICY_ENCODER_ of g2048_tpolicy.hip is one:
+// expanded in place, the forward kernel's code stays what it was before the pieces were named. They use the kernel's names: W, P,
+// lay, ff, layers, grid, lane, g, col.
+//   QNET_GRID_     the wavefront's boards into its zero-padded grids of tile values (2 ** code, 0 for empty); ROW = row g of the
+//                  board in column 16 e + col (the border cells are zeroed once and never written again);
+//   QNET_FORWARD_  conv1 .. Linear(128,4): q[e] on lanes 0..15 (g = 0) = Q of the board in column 16 e + col.
+#define QNET_GRID_(ROW) \
+_Pragma("unroll") \
+    for (int e = 0; e < kE; ++e) { \
+        const uint32_t row = (ROW); \
+_Pragma("unroll") \
+        for (int k = 0; k < 4; ++k) { \
+            const uint32_t code = (row >> (8 * k)) & 0xffu; \
+            grid[6 * (g + 1) + k + 1][16 * e + col] = code ? __uint_as_float((127u + code) << 23) : 0.0f; \
+        } \
+    }
+
+#define QNET_FORWARD_(BF16) \
+/* conv1 -> conv2 -> Linear(1024,128), one conv2 position at a time */ \
+    f4 x[kE][8]; \
+_Pragma("unroll") \
+    for (int m = 0; m < 8; ++m) { \
+        const f4 b = load_f4(P + 5 * kC1 + kC2 + 16 * m + 4 * g); \
+_Pragma("unroll") \
+        for (int e = 0; e < kE; ++e) x[e][m] = b; \
+    } \
+    { \
+        const int cemb = kFlat / (BF16 ? 32 : 16); \
+_Pragma("unroll 1") \
+        for (int p = 0; p < 16; ++p) { \
+/* The blob's address is made opaque once per position: conv1's weights and conv2's fragments do not depend on the */ \
+/* position, and hoisted out of this loop they would be held in registers the loop has none to spare for. */ \
+            const unsigned char *Wc2 = W; \
+            asm volatile("" : "+s"(Wc2)); \
+            const unsigned char *Wemb = Wc2 + lay.emb() * kFrag; \
+            const float *c1w = reinterpret_cast<const float *>(Wc2 + lay.params()), *c1b = c1w + 4 * kC1, *c2b = c1w + 5 * kC1; \
+            const int py = p >> 2, px = p & 3; \
+            float win[kE][3][3];  /* the padded grid's cells (py .. py + 2, px .. px + 2) */ \
+_Pragma("unroll") \
+            for (int e = 0; e < kE; ++e) \
+_Pragma("unroll") \
+                for (int i = 0; i < 3; ++i) \
+_Pragma("unroll") \
+                    for (int j = 0; j < 3; ++j) win[e][i][j] = grid[6 * (py + i) + px + j][16 * e + col]; \
+            f4 c2[kE][4]; \
+_Pragma("unroll") \
+            for (int o = 0; o < 4; ++o) { \
+                const f4 b = load_f4(c2b + 16 * o + 4 * g); \
+_Pragma("unroll") \
+                for (int e = 0; e < kE; ++e) c2[e][o] = b; \
+            } \
+_Pragma("unroll") \
+            for (int tap = 0; tap < 4; ++tap) {  /* conv2's tap (dy, dx): conv1's output at (py + dy, px + dx), 32 channels */ \
+                const int dy = tap >> 1, dx = tap & 1; \
+                f4 c1[kE][2]; \
+_Pragma("unroll") \
+                for (int h = 0; h < 2; ++h) {  /* channels 16 h + 4 g + r */ \
+                    const int ch = 16 * h + 4 * g; \
+                    const f4 w0 = load_f4(c1w + ch), w1 = load_f4(c1w + kC1 + ch), w2 = load_f4(c1w + 2 * kC1 + ch), \
+                             w3 = load_f4(c1w + 3 * kC1 + ch), b = load_f4(c1b + ch); \
+_Pragma("unroll") \
+                    for (int e = 0; e < kE; ++e) \
+                        c1[e][h] = relu((((b + w0 * splat(win[e][dy][dx])) + w1 * splat(win[e][dy][dx + 1])) + \
+                                         w2 * splat(win[e][dy + 1][dx])) + w3 * splat(win[e][dy + 1][dx + 1])); \
+                } \
+/* k = tap * 32 + channel: the 32-feature slice `tap` of conv2's K */ \
+_Pragma("unroll") \
+                for (int t = 0; t < (BF16 ? 1 : 2); ++t) { \
+                    const int c = (BF16 ? 1 : 2) * tap + t; \
+_Pragma("unroll") \
+                    for (int o = 0; o < 4; ++o) { \
+                        f4 in[kE][2], acc[kE]; \
+_Pragma("unroll") \
+                        for (int e = 0; e < kE; ++e) { \
+                            in[e][0] = c1[e][t]; \
+                            in[e][1] = c1[e][1]; \
+                            acc[e] = c2[e][o]; \
+                        } \
+                        chunk_mma<BF16>(Wc2 + ((size_t)(o * (kK2 / (BF16 ? 32 : 16)) + c) * 64 + lane) * 16, in, acc); \
+_Pragma("unroll") \
+                        for (int e = 0; e < kE; ++e) c2[e][o] = acc[e]; \
+                    } \
+                } \
+            } \
+/* the embedding's K slice k = p * 64 + channel (plain feature channel * 16 + p), two 32-feature slices */ \
+_Pragma("unroll") \
+            for (int s = 0; s < 2; ++s) { \
+                f4 h[kE][2]; \
+_Pragma("unroll") \
+                for (int e = 0; e < kE; ++e) { \
+                    h[e][0] = relu(c2[e][2 * s]); \
+                    h[e][1] = relu(c2[e][2 * s + 1]); \
+                } \
+                consume32<BF16>(Wemb, cemb, 2 * p + s, lane, h, x); \
+            } \
+        } \
+    } \
+ \
+/* the encoder layers at sequence length 1 */ \
+_Pragma("unroll 1") \
+    for (int l = 0; l < layers; ++l) { \
+        const unsigned char *Wl = W + (lay.layer0() + (size_t)l * lay.layer_frags()) * kFrag; \
+        const float *Pl = P + kPHead + l * lay.layer_params(); \
+        const float *bv = Pl, *bo = Pl + kD, *b1 = Pl + 2 * kD, *b2 = b1 + ff, *norms = b2 + kD; \
+        f4 y[kE][8]; \
+        pair<BF16, false>(Wl, bv, Wl + lay.out_proj() * kFrag, bo, kD, lane, g, x, y); \
+        add_norm(x, y, norms, norms[4 * kD], g); \
+        pair<BF16, true>(Wl + lay.w1() * kFrag, b1, Wl + lay.w2() * kFrag, b2, ff, lane, g, x, y); \
+        add_norm(x, y, norms + 2 * kD, norms[4 * kD + 1], g); \
+    } \
+ \
+/* Linear(128,4): rows 0..3 of one row tile, on lanes 0..15 (g = 0); the exploit action from the board's own valid moves */ \
+    const float *Pt = P + kPHead + layers * lay.layer_params(); \
+    f4 q[kE]; \
+    { \
+        const f4 b = load_f4(Pt + 4 * g); \
+_Pragma("unroll") \
+        for (int e = 0; e < kE; ++e) q[e] = b; \
+    } \
+    project<BF16, 8>(W + lay.fc() * kFrag, 0, lane, x, q);
+
 // Two blocks per compute unit (two wavefronts per SIMD, each covering the other's fragment loads): 236 (f32) / 230 (bf16) VGPRs,
 // no scratch.
 template <bool BF16>
@@ -299,124 +484,14 @@ __global__ __launch_bounds__(64 * kWaves, 2) void qnet_forward_kernel(const uint
     const float *P = reinterpret_cast<const float *>(W + lay.params());
     const size_t env0 = (size_t)blockIdx.x * kBlockBoards + (size_t)wave * kWaveBoards;
 
-    // the wavefront's boards as zero-padded grids of tile values (2 ** code, 0 for empty); boards past n read as empty
+    // the wavefront's boards as zero-padded grids of tile values; boards past n read as empty
     float (*grid)[kWaveBoards] = lds[wave];
     for (int i = lane; i < kGrid * kWaveBoards; i += 64) (&grid[0][0])[i] = 0.0f;
     __syncthreads();
-#pragma unroll
-    for (int e = 0; e < kE; ++e) {
-        const size_t env = env0 + 16 * e + col;
-        const uint32_t row = env < n ? boards[env * 4 + g] : 0u;       // lane (g, c): row g of board c
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const uint32_t code = (row >> (8 * k)) & 0xffu;
-            grid[6 * (g + 1) + k + 1][16 * e + col] = code ? __uint_as_float((127u + code) << 23) : 0.0f;
-        }
-    }
+    QNET_GRID_(env0 + 16 * e + col < n ? boards[(env0 + 16 * e + col) * 4 + g] : 0u)       // lane (g, c): row g of board c
     __syncthreads();
 
-    // conv1 -> conv2 -> Linear(1024,128), one conv2 position at a time
-    f4 x[kE][8];
-#pragma unroll
-    for (int m = 0; m < 8; ++m) {
-        const f4 b = load_f4(P + 5 * kC1 + kC2 + 16 * m + 4 * g);
-#pragma unroll
-        for (int e = 0; e < kE; ++e) x[e][m] = b;
-    }
-    {
-        const int cemb = kFlat / (BF16 ? 32 : 16);
-#pragma unroll 1
-        for (int p = 0; p < 16; ++p) {
-            // The blob's address is made opaque once per position: conv1's weights and conv2's fragments do not depend on the
-            // position, and hoisted out of this loop they would be held in registers the loop has none to spare for.
-            const unsigned char *Wc2 = W;
-            asm volatile("" : "+s"(Wc2));
-            const unsigned char *Wemb = Wc2 + lay.emb() * kFrag;
-            const float *c1w = reinterpret_cast<const float *>(Wc2 + lay.params()), *c1b = c1w + 4 * kC1, *c2b = c1w + 5 * kC1;
-            const int py = p >> 2, px = p & 3;
-            float win[kE][3][3];                     // the padded grid's cells (py .. py + 2, px .. px + 2)
-#pragma unroll
-            for (int e = 0; e < kE; ++e)
-#pragma unroll
-                for (int i = 0; i < 3; ++i)
-#pragma unroll
-                    for (int j = 0; j < 3; ++j) win[e][i][j] = grid[6 * (py + i) + px + j][16 * e + col];
-            f4 c2[kE][4];
-#pragma unroll
-            for (int o = 0; o < 4; ++o) {
-                const f4 b = load_f4(c2b + 16 * o + 4 * g);
-#pragma unroll
-                for (int e = 0; e < kE; ++e) c2[e][o] = b;
-            }
-#pragma unroll
-            for (int tap = 0; tap < 4; ++tap) {      // conv2's tap (dy, dx): conv1's output at (py + dy, px + dx), 32 channels
-                const int dy = tap >> 1, dx = tap & 1;
-                f4 c1[kE][2];
-#pragma unroll
-                for (int h = 0; h < 2; ++h) {        // channels 16 h + 4 g + r
-                    const int ch = 16 * h + 4 * g;
-                    const f4 w0 = load_f4(c1w + ch), w1 = load_f4(c1w + kC1 + ch), w2 = load_f4(c1w + 2 * kC1 + ch),
-                             w3 = load_f4(c1w + 3 * kC1 + ch), b = load_f4(c1b + ch);
-#pragma unroll
-                    for (int e = 0; e < kE; ++e)
-                        c1[e][h] = relu((((b + w0 * splat(win[e][dy][dx])) + w1 * splat(win[e][dy][dx + 1])) +
-                                         w2 * splat(win[e][dy + 1][dx])) + w3 * splat(win[e][dy + 1][dx + 1]));
-                }
-                // k = tap * 32 + channel: the 32-feature slice `tap` of conv2's K
-#pragma unroll
-                for (int t = 0; t < (BF16 ? 1 : 2); ++t) {
-                    const int c = (BF16 ? 1 : 2) * tap + t;
-#pragma unroll
-                    for (int o = 0; o < 4; ++o) {
-                        f4 in[kE][2], acc[kE];
-#pragma unroll
-                        for (int e = 0; e < kE; ++e) {
-                            in[e][0] = c1[e][t];
-                            in[e][1] = c1[e][1];
-                            acc[e] = c2[e][o];
-                        }
-                        chunk_mma<BF16>(Wc2 + ((size_t)(o * (kK2 / (BF16 ? 32 : 16)) + c) * 64 + lane) * 16, in, acc);
-#pragma unroll
-                        for (int e = 0; e < kE; ++e) c2[e][o] = acc[e];
-                    }
-                }
-            }
-            // the embedding's K slice k = p * 64 + channel (plain feature channel * 16 + p), two 32-feature slices
-#pragma unroll
-            for (int s = 0; s < 2; ++s) {
-                f4 h[kE][2];
-#pragma unroll
-                for (int e = 0; e < kE; ++e) {
-                    h[e][0] = relu(c2[e][2 * s]);
-                    h[e][1] = relu(c2[e][2 * s + 1]);
-                }
-                consume32<BF16>(Wemb, cemb, 2 * p + s, lane, h, x);
-            }
-        }
-    }
-
-    // the encoder layers at sequence length 1
-#pragma unroll 1
-    for (int l = 0; l < layers; ++l) {
-        const unsigned char *Wl = W + (lay.layer0() + (size_t)l * lay.layer_frags()) * kFrag;
-        const float *Pl = P + kPHead + l * lay.layer_params();
-        const float *bv = Pl, *bo = Pl + kD, *b1 = Pl + 2 * kD, *b2 = b1 + ff, *norms = b2 + kD;
-        f4 y[kE][8];
-        pair<BF16, false>(Wl, bv, Wl + lay.out_proj() * kFrag, bo, kD, lane, g, x, y);
-        add_norm(x, y, norms, norms[4 * kD], g);
-        pair<BF16, true>(Wl + lay.w1() * kFrag, b1, Wl + lay.w2() * kFrag, b2, ff, lane, g, x, y);
-        add_norm(x, y, norms + 2 * kD, norms[4 * kD + 1], g);
-    }
-
-    // Linear(128,4): rows 0..3 of one row tile, on lanes 0..15 (g = 0); the exploit action from the board's own valid moves
-    const float *Pt = P + kPHead + layers * lay.layer_params();
-    f4 q[kE];
-    {
-        const f4 b = load_f4(Pt + 4 * g);
-#pragma unroll
-        for (int e = 0; e < kE; ++e) q[e] = b;
-    }
-    project<BF16, 8>(W + lay.fc() * kFrag, 0, lane, x, q);
+    QNET_FORWARD_(BF16)
     if (g != 0) return;
 #pragma unroll
     for (int e = 0; e < kE; ++e) {
@@ -425,22 +500,191 @@ __global__ __launch_bounds__(64 * kWaves, 2) void qnet_forward_kernel(const uint
         q_out[env] = make_float4(q[e][0], q[e][1], q[e][2], q[e][3]);
         if (actions) {
             const uint4 bw = reinterpret_cast<const uint4 *>(boards)[env];
-            const uint32_t mask = valid_mask_env(Board{{bw.x, bw.y, bw.z, bw.w}});
-            // hybrid.py:949-953: q[i] = -1e9 where invalid, then np.argmax (ties to the lowest index; no valid move: action 0)
-            float best = (mask & 1u) ? q[e][0] : -1e9f;
-            uint32_t a = 0u;
-#pragma unroll
-            for (int k = 1; k < 4; ++k) {
-                const float v = ((mask >> k) & 1u) ? q[e][k] : -1e9f;
-                if (v > best) { best = v; a = (uint32_t)k; }
-            }
-            actions[env] = (uint8_t)a;
+            actions[env] = (uint8_t)exploit_action(q[e][0], q[e][1], q[e][2], q[e][3], valid_mask_env(Board{{bw.x, bw.y, bw.z, bw.w}}));
         }
+    }
+}
+
+// --------------------------------------------------------------------------------------------------- complete games --
+// Complete games of the Q-network (the reference's evaluate_agent, hybrid.py:1176-1210: select_action -> env.step until done),
+// as tpolicy_play_kernel (g2048_tpolicy.hip) plays the transformer policy's. The forward's unit is the wavefront: it runs the
+// whole network alone on its 32 boards. So a wavefront owns 32 game slots, slot s = column s of its grids = lane s, and shares
+// nothing with the other three of its block but the launch arguments and the direction table in LDS: after the prologue there
+// is no block barrier, no wavefront waits on another, nothing spins. Per move the wavefront rebuilds its 6 x 6 grids from the
+// slots' boards in LDS (an idle slot holds the empty board), runs the shared forward, moves Q of the boards 16..31 from lanes
+// 0..15 to lanes 16..31, and each slot lane picks its action (exploit_action / select_action with step index = the slot's own
+// move t, id = the game's id), steps its board and does the bookkeeping with the code and the draws of tpolicy_play_kernel. The
+// forward leaves no registers over, so a slot's state (QPlaySlots, 80 bytes a slot) is parked in LDS between moves and loaded
+// after the forward, and the launch arguments (QPlayArgs) are read from LDS too. A finished game writes its results and its slot
+// takes the next game index from the ticket counter in the workspace: one atomicAdd per wavefront for all its idle slots, the
+// indices spread by an mbcnt prefix. The wavefront leaves when all its slots are idle after a refill attempt, which means the
+// queue is empty. The games do not depend on which wavefront or slot plays them.
+__device__ const uint32_t kQPlayDirTable[G2048_DIR_TABLE_WORDS] = G2048_DIR_TABLE_INIT;
+
+struct QPlaySlots {                                  // one wavefront's slots, one column per slot; a slot lane touches only its own
+    uint4 board[kWaveBoards];                        // the empty board while the slot is idle
+    int4 milestone[2][kWaveBoards];
+    double reward[kWaveBoards];
+    unsigned long long game[kWaveBoards];
+    uint32_t score[kWaveBoards];
+    int32_t moves[kWaveBoards], valid[kWaveBoards];
+    uint32_t active[kWaveBoards];
+};
+
+struct QPlayArgs {
+    unsigned long long *ticket;
+    uint4 *boards;
+    uint32_t *score;
+    size_t n;
+    uint64_t seed, id_base;
+    int32_t *moves_out, *valid_out, *invalid_out;
+    int4 *milestone_out;
+    double *reward_out;
+    uint8_t *alive_out, *actions_out;
+    int max_moves;
+    float epsilon;
+    uint32_t n_waves;                                // wavefronts that play; the last block's surplus ones leave at once
+};
+
+// LDS accesses of one wavefront complete in program order; this only keeps the compiler from moving them across the point
+// where lanes read what other lanes of the wavefront wrote.
+__device__ inline void wave_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+template <bool BF16>
+__global__ __launch_bounds__(64 * kWaves, 2) void qnet_play_kernel(const unsigned char *__restrict__ weights, int ff, int layers, const QPlayArgs args)
+{
+    __shared__ QPlayArgs par;
+    __shared__ float lds[kWaves][kGrid][kWaveBoards];
+    __shared__ QPlaySlots wave_slots[kWaves];
+    __shared__ uint4 s_dir[G2048_DIR_TABLE_WORDS / 4];
+    const Layout lay(BF16, ff, layers);
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), g = lane >> 4, col = lane & 15;
+    const bool slot_lane = lane < kWaveBoards;
+    QPlaySlots &slots = wave_slots[wave];
+    float (*grid)[kWaveBoards] = lds[wave];
+    if (threadIdx.x < G2048_DIR_TABLE_WORDS) reinterpret_cast<uint32_t *>(s_dir)[threadIdx.x] = kQPlayDirTable[threadIdx.x];
+    for (int i = lane; i < kGrid * kWaveBoards; i += 64) (&grid[0][0])[i] = 0.0f;
+    if (slot_lane) {
+        slots.active[lane] = 0u;
+        slots.board[lane] = make_uint4(0u, 0u, 0u, 0u);
+    }
+    if (threadIdx.x == 0) par = args;
+    __syncthreads();                                 // par and s_dir are there; the only block barrier
+    if (blockIdx.x * (unsigned)kWaves + (unsigned)wave >= par.n_waves) return;
+    bool drained = false;                            // wavefront-uniform: the queue has no game left
+
+    for (;;) {
+        bool active = slot_lane && slots.active[lane] != 0u;
+        if (!drained) {
+            const uint64_t idle = __ballot(slot_lane && !active);
+            if (idle != 0ull) {
+                const uint32_t cnt = (uint32_t)__popcll(idle);
+                unsigned long long got = 0ull;
+                if (lane == 0) got = atomicAdd(par.ticket, (unsigned long long)cnt);
+                const uint64_t base = ((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(got >> 32)) << 32) |
+                                      __builtin_amdgcn_readfirstlane((uint32_t)got);
+                const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
+                if (slot_lane && !active && base + rank < par.n) {
+                    const size_t game = (size_t)(base + rank);
+                    slots.board[lane] = par.boards[game];
+                    slots.score[lane] = par.score[game];
+                    slots.game[lane] = game;
+                    slots.moves[lane] = 0;
+                    slots.valid[lane] = 0;
+                    slots.reward[lane] = 0.0;
+                    slots.milestone[0][lane] = make_int4(-1, -1, -1, -1);
+                    slots.milestone[1][lane] = make_int4(-1, -1, -1, -1);
+                    slots.active[lane] = 1u;
+                    active = true;
+                }
+                drained = base + cnt >= par.n;
+            }
+        }
+        if (__ballot(active) == 0ull) break;         // every slot idle after a refill attempt = the queue is empty
+        wave_sync();                                 // the slots' boards are there
+
+        // The blob's address is made opaque once per move as well as once per conv position (QNET_FORWARD_), for the reason
+        // tpolicy_play_kernel gives: otherwise every load of the forward that does not depend on the board is hoisted out of the
+        // move loop and held in registers across it, which the forward has none to spare for.
+        const unsigned char *W = weights;
+        asm volatile("" : "+s"(W));
+        const float *P = reinterpret_cast<const float *>(W + lay.params());
+
+        QNET_GRID_(reinterpret_cast<const uint32_t *>(slots.board)[(16 * e + col) * 4 + g])
+        wave_sync();                                 // the grids are there
+        QNET_FORWARD_(BF16)
+
+        // Q of slot s to lane s: q[0] of lanes 0..15 stays, q[1] of lane c goes to lane 16 + c
+        float qs[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float up = __shfl(q[1][k], col);
+            qs[k] = lane < 16 ? q[0][k] : up;
+        }
+
+        if (slot_lane && slots.active[lane] != 0u) {
+            const uint4 bw = slots.board[lane];
+            const Board cur{{bw.x, bw.y, bw.z, bw.w}};
+            const size_t game = (size_t)slots.game[lane];
+            const int32_t t = slots.moves[lane];
+            const uint64_t id = par.id_base + game;
+            const uint32_t mask = valid_mask_env(cur);
+            uint32_t a = exploit_action(qs[0], qs[1], qs[2], qs[3], mask);
+            const float epsilon = par.epsilon;
+            if (epsilon > 0.0f) {                    // (epsilon 0 never explores: no draw)
+                bool explored;
+                a = select_action(a, cur, mask, epsilon, rng_keys(par.seed, DOM_POLICY, (uint64_t)t), id, explored);
+            }
+            const Keys ks = rng_keys(par.seed, DOM_STEP, (uint64_t)t);
+            const uint4 s0 = s_dir[2u * a], s1 = s_dir[2u * a + 1u];
+            const StepOut o = step_board_sel(cur, DirSel{s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w}, rng_draw(ks.k0, ks.k1, id, 0u));
+            if (par.actions_out) par.actions_out[game * (size_t)par.max_moves + (size_t)t] = (uint8_t)a;
+            const uint32_t sc = slots.score[lane] + o.gain;
+            const double rsum = slots.reward[lane] + o.reward;
+            const int32_t maxcode = (int32_t)(o.flags >> G2048_FLAG_MAXCODE_SHIFT);
+            const int4 m0 = slots.milestone[0][lane], m1 = slots.milestone[1][lane];
+            int32_t ms[8] = {m0.x, m0.y, m0.z, m0.w, m1.x, m1.y, m1.z, m1.w};
+#pragma unroll
+            for (int k = 0; k < 8; ++k)
+                if (ms[k] < 0 && maxcode >= 6 + k) ms[k] = t;       // tiles 64 .. 8192, as g2048_track_episodes records them
+            const int32_t nvalid = slots.valid[lane] + ((o.flags & G2048_FLAG_VALID) ? 1 : 0);
+            const int32_t moved = t + 1;
+            const bool done = (o.flags & G2048_FLAG_DONE) != 0u;
+            const uint4 nb = make_uint4(o.board.w[0], o.board.w[1], o.board.w[2], o.board.w[3]);
+            if (done || moved == par.max_moves) {
+                par.boards[game] = nb;
+                par.score[game] = sc;
+                par.moves_out[game] = moved;
+                par.valid_out[game] = nvalid;
+                par.invalid_out[game] = moved - nvalid;
+                par.milestone_out[2 * game] = make_int4(ms[0], ms[1], ms[2], ms[3]);
+                par.milestone_out[2 * game + 1] = make_int4(ms[4], ms[5], ms[6], ms[7]);
+                if (par.reward_out) par.reward_out[game] = rsum;
+                par.alive_out[game] = done ? 0 : 1;
+                slots.board[lane] = make_uint4(0u, 0u, 0u, 0u);
+                slots.active[lane] = 0u;
+            } else {
+                slots.board[lane] = nb;
+                slots.score[lane] = sc;
+                slots.moves[lane] = moved;
+                slots.valid[lane] = nvalid;
+                slots.reward[lane] = rsum;
+                slots.milestone[0][lane] = make_int4(ms[0], ms[1], ms[2], ms[3]);
+                slots.milestone[1][lane] = make_int4(ms[4], ms[5], ms[6], ms[7]);
+            }
+        }
+        wave_sync();                                 // the next move's refill and grids see this move's slots
     }
 }
 
 bool good_shape(int dim_ff, int n_layers) { return dim_ff >= 32 && dim_ff % 32 == 0 && dim_ff <= 65536 && n_layers >= 1 && n_layers <= 64; }
 bool good_precision(int p) { return p == G2048_POLICY_F32 || p == G2048_POLICY_BF16; }
+bool good_epsilon(float e) { return e >= 0.0f && e <= 1.0f; }      // false for NaN
 
 }  // namespace
 
@@ -508,6 +752,72 @@ int g2048_qnet_forward(const void *boards, const void *packed, float *q_out, uin
                            reinterpret_cast<float4 *>(q_out), actions_out_or_null, n, dim_ff, n_layers);
     });
     return check_launch("g2048_qnet_forward");
+}
+
+int g2048_qnet_select_actions(const float *q, const void *boards, uint8_t *actions_out, uint8_t *explored_out_or_null, float epsilon,
+                              uint64_t seed, uint64_t step_index, uint64_t env_id_base, size_t n, void *stream)
+{
+    if (n == 0) return G2048_OK;
+    if (!q || !boards || !actions_out) return fail(G2048_ERR_ARG, "g2048_qnet_select_actions: null pointer");
+    if (!aligned(q, 16) || !aligned(boards, 16)) return fail(G2048_ERR_ARG, "g2048_qnet_select_actions: misaligned pointer (q, boards: 16 bytes)");
+    if (!good_epsilon(epsilon)) return fail(G2048_ERR_ARG, "g2048_qnet_select_actions: epsilon must lie in [0, 1]");
+    const size_t blocks = (n + 255) / 256;
+    if (blocks > 0x7fffffffu) return fail(G2048_ERR_ARG, "g2048_qnet_select_actions: n too large for one launch");
+    const Keys k = rng_keys(seed, DOM_POLICY, step_index);
+    hipLaunchKernelGGL(qnet_select_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       reinterpret_cast<const float4 *>(q), static_cast<const uint4 *>(boards), actions_out, explored_out_or_null, epsilon,
+                       k.k0, k.k1, env_id_base, n);
+    return check_launch("g2048_qnet_select_actions");
+}
+
+size_t g2048_play_qnet_workspace(size_t n_games)
+{
+    (void)n_games;
+    return 64;                                       // the ticket counter (uint64), padded
+}
+
+int g2048_play_qnet_games(void *boards_inout, uint32_t *score_inout, const void *packed, int dim_ff, int n_layers, int32_t *moves_out,
+                          int32_t *valid_out, int32_t *invalid_out, int32_t *milestone_move_out, double *reward_sum_out_or_null,
+                          uint8_t *alive_out, uint8_t *actions_out_or_null, int max_moves, float epsilon, uint64_t seed,
+                          uint64_t game_id_base, size_t n_games, uint32_t opts, uint32_t max_waves, void *workspace, size_t workspace_bytes,
+                          void *stream)
+{
+    if (n_games == 0) return G2048_OK;
+    if (!boards_inout || !score_inout || !packed || !moves_out || !valid_out || !invalid_out || !milestone_move_out || !alive_out ||
+        !workspace)
+        return fail(G2048_ERR_ARG, "g2048_play_qnet_games: null pointer");
+    if (!aligned(boards_inout, 16) || !aligned(packed, 16) || !aligned(milestone_move_out, 16) || !aligned(score_inout, 4) ||
+        !aligned(moves_out, 4) || !aligned(valid_out, 4) || !aligned(invalid_out, 4) || !aligned(reward_sum_out_or_null, 8) ||
+        !aligned(workspace, 8))
+        return fail(G2048_ERR_ARG, "g2048_play_qnet_games: misaligned pointer (boards, weights, milestones: 16 bytes; rewards, "
+                                   "workspace: 8; counters and scores: 4)");
+    if (opts != G2048_POLICY_F32 && opts != G2048_POLICY_BF16) return fail(G2048_ERR_ARG, "g2048_play_qnet_games: unknown opts (precision)");
+    if (max_moves < 1) return fail(G2048_ERR_ARG, "g2048_play_qnet_games: max_moves must be at least 1");
+    if (!good_epsilon(epsilon)) return fail(G2048_ERR_ARG, "g2048_play_qnet_games: epsilon must lie in [0, 1]");
+    if (!good_shape(dim_ff, n_layers))
+        return fail(G2048_ERR_ARG, "g2048_play_qnet_games: dim_ff must be a multiple of 32 (32 .. 65536) and n_layers 1 .. 64");
+    if (workspace_bytes < g2048_play_qnet_workspace(n_games))
+        return fail(G2048_ERR_ARG, "g2048_play_qnet_games: workspace smaller than g2048_play_qnet_workspace(n_games)");
+    const bool bf16 = opts == G2048_POLICY_BF16;
+    // auto: as many wavefronts as the chip holds at once (every later one would only find the queue empty)
+    const size_t cap = max_waves ? (size_t)max_waves : (size_t)device_cus() * kWaves * with_bool(bf16, [](auto BF16) {
+        return resident_per_cu(qnet_play_kernel<decltype(BF16)::value>, 64 * kWaves);
+    });
+    if (cap == 0) return fail(G2048_ERR_HIP, "g2048_play_qnet_games: no HIP device (occupancy query failed)");
+    const size_t waves = std::min(std::min((n_games + kWaveBoards - 1) / kWaveBoards, cap), (size_t)0x7fffffffu);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    auto *ticket = static_cast<unsigned long long *>(workspace);
+    hipError_t e = hipMemsetAsync(ticket, 0, sizeof *ticket, s);
+    if (e == hipSuccess && actions_out_or_null) e = hipMemsetAsync(actions_out_or_null, 0xff, n_games * (size_t)max_moves, s);
+    if (const int rc = check_hip(e, "g2048_play_qnet_games: hipMemsetAsync")) return rc;
+    const QPlayArgs args{ticket, static_cast<uint4 *>(boards_inout), score_inout, n_games, seed, game_id_base, moves_out, valid_out,
+                         invalid_out, reinterpret_cast<int4 *>(milestone_move_out), reward_sum_out_or_null, alive_out, actions_out_or_null,
+                         max_moves, epsilon, (uint32_t)waves};
+    with_bool(bf16, [&](auto BF16) {
+        hipLaunchKernelGGL(qnet_play_kernel<decltype(BF16)::value>, dim3(blocks_for(waves, kWaves)), dim3(64 * kWaves), 0, s,
+                           static_cast<const unsigned char *>(packed), dim_ff, n_layers, args);
+    });
+    return check_launch("g2048_play_qnet_games");
 }
 
 }  // extern "C"

@@ -97,6 +97,9 @@ SIGNATURES = {
     "g2048_qnet_packed_bytes": (_sz, [_int, _int, _int]),
     "g2048_qnet_pack": (_int, [_vp, _int, _int, _int, _vp, _vp]),
     "g2048_qnet_forward": (_int, [_vp, _vp, _vp, _vp, _sz, _int, _int, _u32, _vp]),
+    "g2048_qnet_select_actions": (_int, [_vp, _vp, _vp, _vp, C.c_float, _u64, _u64, _u64, _sz, _vp]),
+    "g2048_play_qnet_workspace": (_sz, [_sz]),
+    "g2048_play_qnet_games": (_int, [_vp] * 3 + [_int, _int] + [_vp] * 7 + [_int, C.c_float, _u64, _u64, _sz, _u32, _u32, _vp, _sz, _vp]),
 }
 
 

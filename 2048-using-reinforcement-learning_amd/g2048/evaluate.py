@@ -24,7 +24,8 @@ intermediate board, score and max tile of the games asked for -- `results["games
 
 `evaluate_policy` is the same for a PPO actor (a DevicePolicy): the games of train.py / play.py, every game to its end in one
 `g2048_play_policy_games` launch, with the same result dict plus each game's summed env reward. A DeviceTransformerPolicy plays
-the same games with the transformer's probabilities (`g2048_play_tpolicy_games`).
+the same games with the transformer's probabilities (`g2048_play_tpolicy_games`). `evaluate_qnet` plays the hybrid agent's
+Q-network (a DeviceQNetwork) with select_action's epsilon-greedy rule (`g2048_play_qnet_games`).
 """
 import json
 import time
@@ -213,6 +214,72 @@ def evaluate_policy(policy, num_games=4096, max_moves=2000, mode="masked", seed=
     return results
 
 
+def evaluate_qnet(qnet, num_games=4096, max_moves=2000, epsilon=0.0, seed=0x2048, game_id_base=0, device=None, fused=True,
+                  histories=None, max_waves=0):
+    """Complete games of the hybrid agent's Q-network (a g2048.DeviceQNetwork): the reference's evaluate_agent
+    (hybrid.py:1176-1210), select_action -> env.step until the game is over or max_moves moves were made (2000: train_agent's
+    max_steps). epsilon is select_action's (evaluate_agent runs at 0.01; 0 = the exploit action alone), with use_beam_search =
+    False: the model-valued beam search of the reference has no device counterpart. Game g starts from VecGame2048's reset of
+    global id game_id_base + g.
+
+    fused=True: every game is played to the end in ONE launch (g2048_play_qnet_games; max_waves = its wavefront count, 32
+    games in flight each, 0 = as many as the chip holds). fused=False: the step-by-step loop of the launches that exist apart
+    from it -- qnet_forward with actions, qnet_select_actions when epsilon > 0, step, track_episodes -- over the whole batch
+    until every game has ended: the yardstick; the games are identical. Returns evaluate_policy's result dict, episode_rewards
+    included; "parameters" holds epsilon, precision, max_moves, num_games and seed. histories: as in evaluate_beam_search
+    (fused driver only)."""
+    from .qnet import DeviceQNetwork
+    if not isinstance(qnet, DeviceQNetwork):
+        raise TypeError("g2048.evaluate_qnet: qnet must be a g2048.DeviceQNetwork")
+    epsilon = float(epsilon)
+    if not 0.0 <= epsilon <= 1.0:
+        raise ValueError("g2048.evaluate_qnet: epsilon must lie in [0, 1]")
+    if int(max_moves) < 1:
+        raise ValueError("g2048.evaluate_qnet: max_moves must be at least 1")
+    if histories is not None and not fused:
+        raise ValueError("g2048.evaluate_qnet: histories need the fused driver (fused=True)")
+    dev = qnet.device
+    if device is not None and ops._dev_index(torch.device(device)) != ops._dev_index(dev):
+        raise ValueError("g2048.evaluate_qnet: the network lives on %s, not %s" % (dev, device))
+    n, max_moves = int(num_games), int(max_moves)
+    precision, blob, dim_ff, n_layers = qnet.precision, qnet.packed, qnet.dim_ff, qnet.n_layers
+    t_start = time.perf_counter()
+    env = VecGame2048(n, device=dev, seed=seed, id_base=game_id_base)
+    boards0 = env.boards.clone() if histories is not None else None
+    if fused:
+        res = ops.play_qnet_games(env.boards, env.scores, blob, dim_ff, n_layers, precision, max_moves, epsilon, seed, game_id_base,
+                                  want_rewards=True, want_actions=histories is not None, max_waves=max_waves)
+    else:
+        res = _play_policy_stepwise(env, blob, precision, max_moves, None, seed, game_id_base,
+                                    act=qnet_stepwise_act(blob, dim_ff, n_layers, precision, n, dev, epsilon, seed, game_id_base))
+    torch.cuda.synchronize(dev)
+    elapsed = time.perf_counter() - t_start
+    table = torch.cat([env.scores.to(torch.int64)[:, None], res["moves"].to(torch.int64)[:, None],
+                       res["valid_moves"].to(torch.int64)[:, None], res["invalid_moves"].to(torch.int64)[:, None],
+                       res["alive"].to(torch.int64)[:, None], torch.zeros(n, 1, dtype=torch.int64, device=dev),
+                       res["milestone_move"].to(torch.int64), ops.unpack(env.boards).to(torch.int64).reshape(n, 16)], dim=1)
+    params = {"epsilon": epsilon, "precision": precision, "max_moves": max_moves, "num_games": n, "seed": seed}
+    results = policy_results_from_table(table.cpu().numpy(), res["reward_sum"].cpu().numpy(), elapsed, params)
+    if histories is not None:
+        results["games"] = game_histories(results, histories, boards0, res["actions"], res["moves"], seed, game_id_base)
+    return results
+
+
+def qnet_stepwise_act(blob, dim_ff, n_layers, precision, n, device, epsilon, seed, game_id_base):
+    """The `act` of _play_policy_stepwise for the Q-network, built only from launches that exist apart from the game kernel:
+    qnet_forward with its exploit actions and, when epsilon > 0, qnet_select_actions with step_index = the move."""
+    q = torch.empty((n, 4), dtype=torch.float32, device=device)
+    actions = torch.empty(n, dtype=torch.uint8, device=device)
+    explored = torch.empty(n, dtype=torch.uint8, device=device)
+
+    def act(boards, t):
+        ops.qnet_forward(boards, blob, dim_ff, n_layers, precision, q=q, actions=actions)
+        if epsilon > 0:
+            ops.qnet_select_actions(q, boards, epsilon, seed, t, game_id_base, actions=actions, explored=explored)
+        return actions
+    return act
+
+
 def policy_results_from_table(table, episode_rewards, elapsed, parameters):
     """evaluate_policy's result dict from the per-game table (evaluate_beam_search's columns, no expansions) and the f64
     reward sums."""
@@ -222,13 +289,16 @@ def policy_results_from_table(table, episode_rewards, elapsed, parameters):
     return results
 
 
-def _play_policy_stepwise(env, blob, precision, max_moves, mode, seed, game_id_base, check_every=16, forward=None):
+def _play_policy_stepwise(env, blob, precision, max_moves, mode, seed, game_id_base, check_every=16, forward=None, act=None):
     """The unfused yardstick of g2048_play_policy_games: one policy_forward, one action launch (sample_actions with step_index
     = t, or torch's argmax), one step and one track_episodes per move for the whole batch. A finished game is over (no move
     changes its board), so stepping it again changes nothing; its counters and reward sum are frozen by `alive`.
     forward: forward(boards, probs) fills probs (float32 (n,4)) for the boards with one launch; None = the PPO actor's
-    policy_forward on `blob`. With the transformer's forward this is the yardstick of g2048_play_tpolicy_games."""
-    if forward is None:
+    policy_forward on `blob`. With the transformer's forward this is the yardstick of g2048_play_tpolicy_games.
+    act: act(boards, t) returns the uint8 (n,) actions of move t itself, in place of forward, mode and the action launch (blob,
+    precision and mode are then unused): with the Q-network's forward and select launches this is the yardstick of
+    g2048_play_qnet_games."""
+    if forward is None and act is None:
         def forward(boards, probs):
             ops.policy_forward(boards, blob, None, precision, probs=probs)
     n, dev = env.n, env.device
@@ -244,12 +314,15 @@ def _play_policy_stepwise(env, blob, precision, max_moves, mode, seed, game_id_b
     for t in range(max_moves):
         if t % check_every == 0 and not bool(alive.any()):
             break
-        forward(env.boards, probs)
-        if mode == "greedy":
+        if act is not None:
+            actions = act(env.boards, t)
+        elif mode == "greedy":
+            forward(env.boards, probs)
             valid = (ops.valid_moves(env.boards)[:, None] & bits) != 0
             valid |= ~valid.any(dim=1, keepdim=True)               # no valid move: all four, as the sampler does
             actions = probs.masked_fill(~valid, float("-inf")).argmax(dim=1).to(torch.uint8)
         else:
+            forward(env.boards, probs)
             mask = ops.valid_moves(env.boards) if mode == "masked" else None
             actions, _ = ops.sample_actions(probs, mask, seed, t, game_id_base)
         live = alive.bool()

@@ -577,6 +577,32 @@ def qnet_forward(boards, packed, dim_ff, n_layers, precision="f32", q=None, acti
     return q if actions is None else (actions, q)
 
 
+def qnet_select_actions(q, boards, epsilon, seed=0x2048, step_index=0, id_base=0, actions=None, explored=None):
+    """DQNAgent.select_action (hybrid.py:909-953, use_beam_search = False) for every board in ONE launch
+    (g2048_qnet_select_actions), given q float32 (n,4) of qnet_forward: with probability epsilon (the coin is draw 1 of (seed,
+    POLICY, step_index, id_base + i)) the reference's biased exploration among the valid moves (draw 0), otherwise the exploit
+    action of qnet_forward. Returns (actions uint8 (n,), explored uint8 (n,): 1 where the board explored)."""
+    epsilon = float(epsilon)
+    if not 0.0 <= epsilon <= 1.0:
+        raise ValueError("g2048: epsilon must lie in [0, 1]")
+    L.require_device_tensor(q, torch.float32, (4,), "q")
+    L.require_device_tensor(boards, torch.uint8, (16,), "boards")
+    n, dev = boards.shape[0], boards.device
+    if q.shape[0] != n:
+        raise ValueError("g2048: q must have n rows")
+    if actions is None:
+        actions = torch.empty(n, dtype=torch.uint8, device=dev)
+    if explored is None:
+        explored = torch.empty(n, dtype=torch.uint8, device=dev)
+    for name, t in (("actions", actions), ("explored", explored)):
+        L.require_device_tensor(t, torch.uint8, (), name)
+        if t.shape[0] != n:
+            raise ValueError("g2048: %s must have n entries" % name)
+    L.call(dev, L.lib().g2048_qnet_select_actions, q.data_ptr(), boards.data_ptr(), actions.data_ptr(), explored.data_ptr(), epsilon,
+           L.u64(seed), L.u64(step_index), L.u64(id_base), n, L.stream_ptr(dev))
+    return actions, explored
+
+
 class SeenStates:
     """The `seen_states` set and `highest_tile_seen` of PPOAgent (agents/ppo_agent.py:171-176) for ordered batches of
     transitions, resident on the GPU: an open-addressing hash set keyed by the 16-byte board (include/g2048.h,
@@ -1053,6 +1079,61 @@ def play_tpolicy_games(boards, scores, packed, dim_ff, n_layers, precision="f32"
                int(n_layers), out["moves"].data_ptr(), out["valid_moves"].data_ptr(), out["invalid_moves"].data_ptr(),
                out["milestone_move"].data_ptr(), ptr("reward_sum"), out["alive"].data_ptr(), ptr("actions"), int(max_moves),
                L.u64(seed), L.u64(game_id_base), n, opts, int(max_blocks), box.buf.data_ptr(), need, L.stream_ptr(dev))
+    return out
+
+
+_PLAY_QNET_WS = _PerStream()
+
+
+def play_qnet_games(boards, scores, packed, dim_ff, n_layers, precision="f32", max_moves=2000, epsilon=0.0, seed=0x2048,
+                    game_id_base=0, want_rewards=True, want_actions=False, max_waves=0):
+    """Every game played to the end by the hybrid agent's Q-network in ONE launch (g2048_play_qnet_games; the reference's
+    evaluate_agent, hybrid.py:1176-1210): per move qnet_forward, then select_action at `epsilon` as qnet_select_actions picks
+    it (epsilon 0: the exploit action), then the env step. packed: the blob of qnet_pack for (precision, dim_ff, n_layers).
+    boards / scores are updated in place. Returns play_policy_games' dict of per-game tensors: moves, valid_moves,
+    invalid_moves (int32), milestone_move (int32 (n,8), -1 = never), alive (uint8), with want_rewards "reward_sum" (float64)
+    and with want_actions "actions" (uint8 (n, max_moves), 0xFF from a game's end on: the input of `replay_games`).
+    max_waves: the number of wavefronts (32 games in flight each), 0 = as many as the chip holds (the games are the same for
+    every value)."""
+    if precision not in POLICY_PRECISIONS:
+        raise ValueError("g2048: precision must be 'f32' or 'bf16'")
+    nb = qnet_packed_bytes(precision, dim_ff, n_layers)             # (the size needs no device: a wrong blob is refused anywhere)
+    if isinstance(packed, torch.Tensor) and packed.numel() != nb:
+        raise ValueError("g2048: packed must be a %s blob of %d bytes (dim_ff %d, %d layers)" % (precision, nb, dim_ff, n_layers))
+    epsilon = float(epsilon)
+    if not 0.0 <= epsilon <= 1.0:
+        raise ValueError("g2048: epsilon must lie in [0, 1]")
+    L.require_device_tensor(boards, torch.uint8, (16,), "boards")
+    _require_scores(scores)
+    L.require_device_tensor(packed, torch.uint8, None, "packed")
+    n, dev = boards.shape[0], boards.device
+    if scores.shape[0] != n:
+        raise ValueError("g2048: scores length must equal the number of boards")
+    if int(max_moves) < 1:
+        raise ValueError("g2048: max_moves must be at least 1")
+    if not 0 <= int(max_waves) <= 0xFFFFFFFF:
+        raise ValueError("g2048: max_waves must be 0 (auto) or a positive 32-bit count")
+    out = {
+        "moves": torch.zeros(n, dtype=torch.int32, device=dev), "valid_moves": torch.zeros(n, dtype=torch.int32, device=dev),
+        "invalid_moves": torch.zeros(n, dtype=torch.int32, device=dev),
+        "milestone_move": torch.full((n, 8), -1, dtype=torch.int32, device=dev),
+        "alive": torch.zeros(n, dtype=torch.uint8, device=dev),
+    }
+    if want_rewards:
+        out["reward_sum"] = torch.zeros(n, dtype=torch.float64, device=dev)
+    if want_actions:
+        out["actions"] = torch.empty((n, int(max_moves)), dtype=torch.uint8, device=dev)     # (the library fills it with 0xFF)
+    need = int(L.lib().g2048_play_qnet_workspace(n))
+    ptr = lambda k: out[k].data_ptr() if k in out else None      # noqa: E731
+    box = _PLAY_QNET_WS.get((_dev_index(dev), L.stream_ptr(dev)), _ScratchBox)
+    with box.lock:          # grow-if-needed and enqueue as one step (see beam_get_action)
+        if box.buf is None or box.buf.numel() < need:
+            box.buf = torch.empty(need, dtype=torch.uint8, device=dev)
+        L.call(dev, L.lib().g2048_play_qnet_games, boards.data_ptr(), scores.data_ptr(), packed.data_ptr(), int(dim_ff),
+               int(n_layers), out["moves"].data_ptr(), out["valid_moves"].data_ptr(), out["invalid_moves"].data_ptr(),
+               out["milestone_move"].data_ptr(), ptr("reward_sum"), out["alive"].data_ptr(), ptr("actions"), int(max_moves), epsilon,
+               L.u64(seed), L.u64(game_id_base), n, POLICY_PRECISIONS[precision], int(max_waves), box.buf.data_ptr(), need,
+               L.stream_ptr(dev))
     return out
 
 

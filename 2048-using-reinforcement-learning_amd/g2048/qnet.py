@@ -194,7 +194,8 @@ def forward_reference(p, boards, dtype=torch.float64, round_weights=None):
 class DeviceQNetwork:
     """Hybrid Q-network on the device: __call__(boards uint8 (N,16)) -> q float32 (N,4); act(boards) -> (actions uint8 (N,), q),
     the exploit action of DQNAgent.select_action (argmax of q over the env's valid moves, ties to the lowest index, 0 for a board
-    with no valid move). One g2048_qnet_forward launch per call; the outputs are buffers owned by the network (one set per
+    with no valid move); act(boards, epsilon, seed, step_index, id_base) with epsilon > 0 is the whole epsilon-greedy
+    select_action (one more launch). One g2048_qnet_forward launch per call; the outputs are buffers owned by the network (one set per
     (N, stream), overwritten by the next call with the same N on the same stream), so after the first call per (N, stream) a
     call neither allocates nor synchronises.
 
@@ -214,7 +215,7 @@ class DeviceQNetwork:
             raise RuntimeError("g2048: DeviceQNetwork needs the module on a ROCm device (got %s); there is no CPU path" % self.device)
         self.plain = torch.empty(ops.qnet_plain_floats(self.dim_ff, self.n_layers), dtype=torch.float32, device=self.device)
         self.packed = torch.empty(ops.qnet_packed_bytes(precision, self.dim_ff, self.n_layers), dtype=torch.uint8, device=self.device)
-        self._out = {}
+        self._out, self._explored = {}, {}
         self.refresh()
 
     def refresh(self):
@@ -239,6 +240,15 @@ class DeviceQNetwork:
         q, _ = self._buffers(boards)
         return ops.qnet_forward(boards, self.packed, self.dim_ff, self.n_layers, self.precision, q=q)
 
-    def act(self, boards):
+    def act(self, boards, epsilon=0.0, seed=0x2048, step_index=0, id_base=0):
+        """(actions, q). epsilon > 0 adds one g2048_qnet_select_actions launch: DQNAgent.select_action's epsilon-greedy with the
+        reference's biased exploration (use_beam_search = False), the draws keyed by (seed, step_index, id_base + row)."""
         q, actions = self._buffers(boards)
-        return ops.qnet_forward(boards, self.packed, self.dim_ff, self.n_layers, self.precision, q=q, actions=actions)
+        ops.qnet_forward(boards, self.packed, self.dim_ff, self.n_layers, self.precision, q=q, actions=actions)
+        if epsilon > 0:
+            key = (boards.shape[0], torch.cuda.current_stream(self.device).cuda_stream)
+            explored = self._explored.get(key)
+            if explored is None:
+                explored = self._explored[key] = torch.empty(boards.shape[0], dtype=torch.uint8, device=self.device)
+            ops.qnet_select_actions(q, boards, epsilon, seed, step_index, id_base, actions=actions, explored=explored)
+        return actions, q

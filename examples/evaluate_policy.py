@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
-"""Evaluate a PPO actor or the transformer policy over many complete games on the GPU (the games of train.py / play.py).
+"""Evaluate a PPO actor, the transformer policy or the hybrid agent's Q-network over many complete games on the GPU (the games
+of train.py / play.py, and of hybrid.py's evaluate_agent).
 
-    python examples/evaluate_policy.py --games 65536 [--policy mlp|transformer] [--weights reference|random]
-                                       [--dim-ff 2048] [--layers 2] [--mode masked|unmasked|greedy]
+    python examples/evaluate_policy.py --games 65536 [--policy mlp|transformer|hybrid] [--weights reference|random]
+                                       [--dim-ff 2048] [--layers 2] [--mode masked|unmasked|greedy] [--epsilon 0.01]
                                        [--precision f32|bf16] [--max-moves 2000] [--out overall_results.json]
 
 --weights reference (default) loads the reference's trained checkpoint from tests/golden/policy.npz into the reference's
@@ -12,7 +13,11 @@ episode rewards.
 
 --policy transformer plays the reference's TransformerModel layout (models/transformer.py: --dim-ff, --layers) as a
 g2048.DeviceTransformerPolicy. There is no trained transformer checkpoint: it carries the hash-derived weights of
-tests/tpolicy_weights.py (--weights is ignored), so the games show the machinery, not a strong player."""
+tests/tpolicy_weights.py (--weights is ignored), so the games show the machinery, not a strong player.
+
+--policy hybrid plays the reference's HybridDQN layout (agents/hybrid.py:700-727: --dim-ff, --layers) as a g2048.DeviceQNetwork
+through g2048.evaluate_qnet: select_action's epsilon-greedy rule at --epsilon (evaluate_agent's 0.01 by default; --mode is
+ignored), without the reference's beam search. It carries the hash-derived weights of tests/qnet_weights.py."""
 import argparse
 import json
 import os
@@ -52,6 +57,28 @@ class TransformerModel(nn.Module):
         self.actor, self.critic = nn.Linear(64, 4), nn.Linear(64, 1)
 
 
+class HybridDQN(nn.Module):
+    """The reference's Q-network layout (agents/hybrid.py:700-727) from stock torch modules."""
+
+    def __init__(self, dim_ff, layers):
+        super().__init__()
+        self.cnn = nn.Sequential(nn.Conv2d(1, 32, kernel_size=2, stride=1, padding=1), nn.ReLU(),
+                                 nn.Conv2d(32, 64, kernel_size=2, stride=1, padding=0), nn.ReLU())
+        self.embedding = nn.Linear(64 * 4 * 4, 128)
+        layer = nn.TransformerEncoderLayer(d_model=128, nhead=8, dim_feedforward=dim_ff)
+        self.transformer = nn.TransformerEncoder(layer, num_layers=layers, enable_nested_tensor=False)
+        self.fc = nn.Linear(128, 4)
+
+
+def hybrid_qnet(dim_ff, layers, precision):
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import qnet_weights as qw
+    model = HybridDQN(dim_ff, layers).double()
+    shapes = [(k, tuple(v.shape)) for k, v in model.state_dict().items()]
+    model.load_state_dict({k: torch.from_numpy(v) for k, v in qw.state_dict(shapes).items()})
+    return g2048.DeviceQNetwork(model.float().eval().to("cuda"), precision=precision)
+
+
 def transformer_policy(dim_ff, layers, precision):
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import tpolicy_weights as tw
@@ -63,18 +90,22 @@ def transformer_policy(dim_ff, layers, precision):
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--games", type=int, default=4096)
-ap.add_argument("--policy", choices=("mlp", "transformer"), default="mlp")
+ap.add_argument("--policy", choices=("mlp", "transformer", "hybrid"), default="mlp")
 ap.add_argument("--dim-ff", type=int, default=2048)
 ap.add_argument("--layers", type=int, default=2)
 ap.add_argument("--weights", choices=("reference", "random"), default="reference")
 ap.add_argument("--mode", choices=("masked", "unmasked", "greedy"), default="masked")
+ap.add_argument("--epsilon", type=float, default=0.01)
 ap.add_argument("--precision", choices=("f32", "bf16"), default="f32")
 ap.add_argument("--max-moves", type=int, default=2000)
 ap.add_argument("--seed", type=int, default=2025)
 ap.add_argument("--out", default=None)
 a = ap.parse_args()
 
-if a.policy == "transformer":
+if a.policy == "hybrid":
+    policy = hybrid_qnet(a.dim_ff, a.layers, a.precision)
+    what, a.mode = "hybrid Q-network dim_ff %d x %d layers, hash" % (a.dim_ff, a.layers), "epsilon %g" % a.epsilon
+elif a.policy == "transformer":
     policy = transformer_policy(a.dim_ff, a.layers, a.precision)
     what = "transformer dim_ff %d x %d layers, hash" % (a.dim_ff, a.layers)
 else:
@@ -87,7 +118,10 @@ else:
         torch.manual_seed(a.seed)
     policy = g2048.DevicePolicy(actor.eval().to("cuda"), precision=a.precision)
     what = a.weights
-res = g2048.evaluate_policy(policy, num_games=a.games, max_moves=a.max_moves, mode=a.mode, seed=a.seed)
+if a.policy == "hybrid":
+    res = g2048.evaluate_qnet(policy, num_games=a.games, max_moves=a.max_moves, epsilon=a.epsilon, seed=a.seed)
+else:
+    res = g2048.evaluate_policy(policy, num_games=a.games, max_moves=a.max_moves, mode=a.mode, seed=a.seed)
 s = res["summary"]
 print("==== POLICY EVALUATION SUMMARY (%s weights, %s, %s) ====" % (what, a.mode, a.precision))
 print("Highest tile reached: %d" % s["highest_tile"])

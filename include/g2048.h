@@ -585,6 +585,51 @@ G2048_API size_t g2048_qnet_packed_bytes(int precision, int dim_ff, int n_layers
 G2048_API int g2048_qnet_pack(const float *plain_f32, int dim_ff, int n_layers, int precision, void *packed_out, void *stream);
 G2048_API int g2048_qnet_forward(const void *boards, const void *packed, float *q_out, uint8_t *actions_out_or_null, size_t n, int dim_ff,
                        int n_layers, uint32_t opts, void *stream);
+
+/* DQNAgent.select_action (agents/hybrid.py:909-953) for n boards in ONE launch, given their Q-values: the epsilon-greedy choice
+ * between the exploit action of g2048_qnet_forward and the reference's biased exploration. Board i has id env_id_base + i; with
+ * (k0, k1) = the keys of (seed, POLICY domain, step_index):
+ *   coin     u = (float)(draw(k0, k1, id, 1) >> 8) * 2^-24; the board explores iff u < epsilon, compared in f32 (hybrid.py:912).
+ *            epsilon 0 never explores, epsilon 1 always does.
+ *   exploit  (:943-953) exactly the rule of g2048_qnet_forward's actions: Q of every move that is invalid under the env's mask
+ *            replaced by -1e9, the argmax with ties to the lowest index, action 0 for a board with no valid move.
+ *   explore  (:914-936) random.choices(valid_actions, weights): the preferences over the actions 0..3 are (1, 1, 3, 3) (RIGHT and DOWN
+ *            three times as likely) when the board's max tile is >= 64 and np.argmax(board) is cell (3,3), i.e. cell 15's code is >= 6 and
+ *            strictly greater than every other cell's, and (1, 1, 1, 1) otherwise; the action is what g2048_sample_actions draws
+ *            from p = (0.125, 0.125, 0.375, 0.375) or (0.25, 0.25, 0.25, 0.25) under the env's valid-move mask with draw(k0, k1,
+ *            id, 0). Those p are exact in f32 and the sampler's + 1e-10 does not change them. A board with no valid move samples
+ *            among all four (the reference's random.randint(0, 3), :918-919).
+ *   The reference's beam_search branch of select_action (:814-907: model-valued leaves, random.sample) is not part of this: the
+ *   launch is select_action with use_beam_search = False.
+ * q: float32 (n,4), 16-byte aligned, as g2048_qnet_forward wrote it; boards 16-byte aligned; explored_out_or_null[i] = 1 where
+ * the board explored. epsilon outside [0, 1] or NaN is refused. Arguments are checked before any device call; n == 0 returns
+ * G2048_OK. Nothing past row n is written. */
+G2048_API int g2048_qnet_select_actions(const float *q, const void *boards, uint8_t *actions_out, uint8_t *explored_out_or_null,
+                              float epsilon, uint64_t seed, uint64_t step_index, uint64_t env_id_base, size_t n, void *stream);
+
+/* Complete games of the Q-network (the reference's evaluate_agent, hybrid.py:1176-1210: select_action -> env.step until done),
+ * every game played to the end on the device in ONE launch, as g2048_play_tpolicy_games does for the transformer policy: the same
+ * games, draws and outputs. Game g (global id game_id_base + g) starts from boards_inout[g] / score_inout[g]; at move t = 0, 1,
+ * ... it takes Q = what g2048_qnet_forward gives for the same board and blob (packed with the precision in opts; dim_ff, n_layers
+ * as packed), bit for bit, then the action exactly as g2048_qnet_select_actions(epsilon, step_index = t, id = game id) picks it
+ * (epsilon 0: the exploit action, no draw; use_beam_search = False, as there), and steps the board exactly as
+ * g2048_step(step_index = t, board id = game id) does, without auto-reset. The game ends when it is over (DONE) or after
+ * max_moves moves. Outputs per game: final board and score (in place), moves, valid / invalid move counts,
+ * milestone_move_out[g][0..8) = the move at which tiles 64..8192 first appeared (-1 = never), alive_out[g] = 1 if the game hit
+ * max_moves without finishing, reward_sum_out_or_null[g] = the f64 env rewards summed in move order from 0.0, and
+ * actions_out_or_null = the move-set, max_moves bytes per game, 0xFF from the game's end on (the input of g2048_replay_games; the
+ * library fills it with 0xFF first).
+ * opts = the precision alone (G2048_POLICY_*). max_waves = the number of wavefronts, each of which holds 32 game slots and runs
+ * the network on them by itself (a finished game's slot takes the next game), 0 = as many as the chip holds at once; the games do
+ * not depend on it. workspace: g2048_play_qnet_workspace(n_games) bytes of device memory, 8-byte aligned (a ticket counter the
+ * call clears on `stream`). Boards, blob and milestone_move_out 16-byte aligned, rewards 8, the rest 4. Arguments are checked
+ * before any device call; n_games == 0 returns G2048_OK. Nothing past game n_games is written. */
+G2048_API size_t g2048_play_qnet_workspace(size_t n_games);
+G2048_API int g2048_play_qnet_games(void *boards_inout, uint32_t *score_inout, const void *packed, int dim_ff, int n_layers,
+                          int32_t *moves_out, int32_t *valid_out, int32_t *invalid_out, int32_t *milestone_move_out,
+                          double *reward_sum_out_or_null, uint8_t *alive_out, uint8_t *actions_out_or_null, int max_moves,
+                          float epsilon, uint64_t seed, uint64_t game_id_base, size_t n_games, uint32_t opts, uint32_t max_waves,
+                          void *workspace, size_t workspace_bytes, void *stream);
 #ifdef __cplusplus
 }
 #endif
