@@ -41,6 +41,51 @@ inline bool aligned(const void *p, size_t bytes) { return (reinterpret_cast<uint
 
 inline unsigned blocks_for(size_t n, size_t per_block) { return (unsigned)((n + per_block - 1) / per_block); }
 
+inline bool good_precision(int p) { return p == G2048_POLICY_F32 || p == G2048_POLICY_BF16; }
+
+// the encoder shapes the transformer policy and the Q-network are compiled for
+inline bool good_encoder_shape(int dim_ff, int n_layers)
+{
+    return dim_ff >= 32 && dim_ff % 32 == 0 && dim_ff <= 65536 && n_layers >= 1 && n_layers <= 64;
+}
+
+// --------------------------------------------------------------------------------------- complete games of a network --
+// What g2048_play_policy_games, g2048_play_tpolicy_games and g2048_play_qnet_games share on the host (the device side is
+// g2048_play.h). `stem` is the entry point's name without "_games", e.g. "g2048_play_policy": the messages name
+// <stem>_games and <stem>_workspace.
+
+// the workspace is the ticket counter (uint64), padded
+inline size_t ticket_workspace_bytes(size_t n_games)
+{
+    (void)n_games;
+    return 64;
+}
+
+// the arguments the three entry points have in common: G2048_OK, or the error as the entry point's
+inline int check_play_args(const char *stem, const void *boards, const uint32_t *score, const void *packed, const int32_t *moves,
+                           const int32_t *valid, const int32_t *invalid, const int32_t *milestones, const double *reward_or_null,
+                           const uint8_t *alive, int max_moves, size_t n_games, const void *workspace, size_t workspace_bytes)
+{
+    if (!boards || !score || !packed || !moves || !valid || !invalid || !milestones || !alive || !workspace)
+        return fail(G2048_ERR_ARG, "%s_games: null pointer", stem);
+    if (!aligned(boards, 16) || !aligned(packed, 16) || !aligned(milestones, 16) || !aligned(score, 4) || !aligned(moves, 4) ||
+        !aligned(valid, 4) || !aligned(invalid, 4) || !aligned(reward_or_null, 8) || !aligned(workspace, 8))
+        return fail(G2048_ERR_ARG, "%s_games: misaligned pointer (boards, weights, milestones: 16 bytes; rewards, workspace: 8; counters "
+                                   "and scores: 4)", stem);
+    if (max_moves < 1) return fail(G2048_ERR_ARG, "%s_games: max_moves must be at least 1", stem);
+    if (workspace_bytes < ticket_workspace_bytes(n_games))
+        return fail(G2048_ERR_ARG, "%s_games: workspace smaller than %s_workspace(n_games)", stem, stem);
+    return G2048_OK;
+}
+
+// before the launch, on its stream: the ticket counter to zero, the action bytes (if asked for) to 0xFF
+inline int reset_play_buffers(const char *stem, void *workspace, uint8_t *actions_or_null, size_t n_games, int max_moves, hipStream_t s)
+{
+    hipError_t e = hipMemsetAsync(workspace, 0, sizeof(unsigned long long), s);
+    if (e == hipSuccess && actions_or_null) e = hipMemsetAsync(actions_or_null, 0xff, n_games * (size_t)max_moves, s);
+    return e == hipSuccess ? G2048_OK : fail(G2048_ERR_HIP, "%s_games: hipMemsetAsync: %s", stem, hipGetErrorString(e));
+}
+
 // ------------------------------------------------------------------------------------------------------------ device --
 constexpr int kFallbackCus = 256;                    // MI355X's compute-unit count, if the device cannot be asked
 

@@ -30,15 +30,13 @@
 #include "../../include/g2048.h"
 #include "g2048_board.h"
 #include "g2048_host.h"
+#include "g2048_mfma.h"
+#include "g2048_play.h"
 #include "g2048_rng.h"
 
 namespace {
 
 using namespace g2048;
-
-typedef float f4 __attribute__((ext_vector_type(4)));
-typedef unsigned u4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 // ------------------------------------------------------------------------------------------------ shapes and layouts --
 constexpr int kIn = 16, kH1 = 256, kH2 = 128, kH3 = 64, kOutPad = 16;
@@ -62,12 +60,6 @@ template <bool BF16> struct Packed {
     static constexpr size_t kBytes = kB4 + 4 * kOutPad;
 };
 static_assert(Packed<false>::kBytes % 16 == 0 && Packed<true>::kBytes % 16 == 0, "packed sections stay 16-byte aligned");
-
-__device__ __host__ inline uint32_t bf16_rne(float v)
-{
-    const uint32_t u = __float_as_uint(v);
-    return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;        // finite inputs: round to nearest even by integer add
-}
 
 // ------------------------------------------------------------------------------------------------------------- pack --
 // One thread per packed 32-bit word (f32: one weight; bf16: two). Padding (layer 1's missing features in bf16, layer 4's
@@ -103,52 +95,15 @@ __global__ __launch_bounds__(256) void policy_pack_kernel(const float *__restric
     const int c = frag / (N / 16), o = frag % (N / 16);
     const int row = 16 * o + (lane & 15), h = lane >> 4;
     auto weight = [&](int k) { return (row < rows && k < K) ? plain[wofs + row * K + k] : 0.0f; };
-    if (BF16) {
-        uint32_t pair[2];
-        for (int q = 0; q < 2; ++q) {
-            const int j = 2 * word + q;
-            pair[q] = bf16_rne(weight(32 * c + 16 * (j >> 2) + 4 * h + (j & 3)));
-        }
-        packed[w] = pair[0] | (pair[1] << 16);
-    } else {
-        packed[w] = __float_as_uint(weight(16 * c + 4 * h + word));
-    }
+    packed[w] = fragment_word<BF16>(c, h, word, weight);
 }
 
 // ---------------------------------------------------------------------------------------------------------- forward --
 constexpr int kWaves = 4;
 
-__device__ inline f4 relu(f4 v)
-{
-    return f4{fmaxf(v[0], 0.0f), fmaxf(v[1], 0.0f), fmaxf(v[2], 0.0f), fmaxf(v[3], 0.0f)};
-}
-
-__device__ inline bf16x8 to_bf16x8(f4 lo, f4 hi)
-{
-    const u4 u{bf16_rne(lo[0]) | (bf16_rne(lo[1]) << 16), bf16_rne(lo[2]) | (bf16_rne(lo[3]) << 16),
-               bf16_rne(hi[0]) | (bf16_rne(hi[1]) << 16), bf16_rne(hi[2]) | (bf16_rne(hi[3]) << 16)};
-    return __builtin_bit_cast(bf16x8, u);
-}
-
-__device__ inline f4 load_f4(const unsigned char *p) { return *reinterpret_cast<const f4 *>(p); }
-
-// acc[e] += W(fragment at `frag`) . act[e] over one chunk. f32: act holds one 16-feature tile per e (4 MFMAs);
-// bf16: act holds two tiles per e (one MFMA).
-template <bool BF16, int E>
-__device__ inline void chunk_mma(const unsigned char *frag, const f4 (&act)[E][2], f4 (&acc)[E])
-{
-    const f4 a = load_f4(frag);
-    if constexpr (BF16) {
-        const bf16x8 w = __builtin_bit_cast(bf16x8, a);
-#pragma unroll
-        for (int e = 0; e < E; ++e) acc[e] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w, to_bf16x8(act[e][0], act[e][1]), acc[e], 0, 0, 0);
-    } else {
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-#pragma unroll
-            for (int e = 0; e < E; ++e) acc[e] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[r], act[e][0][r], acc[e], 0, 0, 0);
-    }
-}
+// chunk_mma's bf16 operand is rounded by integer add here, not by the __bf16 cast: the forward kernel was written and measured
+// with that form, and keeps it
+constexpr bool kIntRne = true;
 
 // One layer over activations held as 16-feature tiles act[e][t] (already through ReLU): out[e][o] = bias + W . act.
 template <bool BF16, int E, int K, int N>
@@ -174,7 +129,7 @@ __device__ inline void dense(const unsigned char *sec, const float *bias, int la
                 in[e][1] = act[e][TPC * c + TPC - 1];
                 acc[e] = out[e][o];
             }
-            chunk_mma<BF16, E>(sec + ((size_t)(c * (N / 16) + o) * 64 + lane) * 16, in, acc);
+            chunk_mma<BF16, E, false, kIntRne>(sec + ((size_t)(c * (N / 16) + o) * 64 + lane) * 16, in, acc);
 #pragma unroll
             for (int e = 0; e < E; ++e) out[e][o] = acc[e];
         }
@@ -191,15 +146,6 @@ __device__ __forceinline__ void board_operand(uint32_t cells, f4 (&x)[2])
 #pragma unroll
     for (int r = 0; r < 4; ++r) x[0][r] = (float)((cells >> (8 * r)) & 0xffu) / 15.0f;
     x[1] = f4{0.0f, 0.0f, 0.0f, 0.0f};           // bf16: features 16..31 of the only chunk do not exist
-}
-
-// nn.Softmax(dim=-1) of one board's four logits: exp(z - max) / sum, in f32
-__device__ __forceinline__ float4 softmax4(f4 z)
-{
-    const float m = fmaxf(fmaxf(z[0], z[1]), fmaxf(z[2], z[3]));
-    const float e0 = expf(z[0] - m), e1 = expf(z[1] - m), e2 = expf(z[2] - m), e3 = expf(z[3] - m);
-    const float sum = ((e0 + e1) + e2) + e3;
-    return make_float4(e0 / sum, e1 / sum, e2 / sum, e3 / sum);
 }
 
 // Layers 1..4 of the network at W (bias = W + kBias, P = Packed<BF16>) for the E tiles of B operands x of a wavefront; declares
@@ -226,7 +172,7 @@ _Pragma("unroll") \
             f4 acc[E]; \
 _Pragma("unroll") \
             for (int e = 0; e < E; ++e) acc[e] = b; \
-            chunk_mma<BF16, E>(W + P::kL1 + ((size_t)o1 * 64 + lane) * 16, x, acc); \
+            chunk_mma<BF16, E, false, kIntRne>(W + P::kL1 + ((size_t)o1 * 64 + lane) * 16, x, acc); \
 _Pragma("unroll") \
             for (int e = 0; e < E; ++e) h1[e][q] = relu(acc[e]); \
         } \
@@ -243,7 +189,7 @@ _Pragma("unroll") \
                     in[e][1] = h1[e][1]; \
                     acc[e] = acc2[e][o]; \
                 } \
-                chunk_mma<BF16, E>(W + P::kL2 + ((size_t)(c * (kH2 / 16) + o) * 64 + lane) * 16, in, acc); \
+                chunk_mma<BF16, E, false, kIntRne>(W + P::kL2 + ((size_t)(c * (kH2 / 16) + o) * 64 + lane) * 16, in, acc); \
 _Pragma("unroll") \
                 for (int e = 0; e < E; ++e) acc2[e][o] = acc[e]; \
             } \
@@ -304,24 +250,15 @@ constexpr int kTilesF32 = 2, kTilesBF16 = 4;
 
 // --------------------------------------------------------------------------------------------------- complete games --
 // The reference's policy games (play.py:44-68, train.py:54-90) played to the end on the device, as g2048_play_games plays
-// the beam agent's. One wavefront is one block and owns S = 16 E game slots, slot s on lane s. Per move, for all of its
-// live slots at once: the slot lanes write their boards to LDS, every lane reads the dword its layer-1 B operand needs,
-// the wavefront runs the shared forward, lanes 0..15 write the probabilities to LDS, and each slot lane reads its own row,
-// picks its action, steps its board and does the bookkeeping in registers. Slots sit at different move indices, so the
-// RNG keys are derived per lane (rng_keys: the seed half is loop-invariant and hoisted). A finished game writes its
-// results and its slot takes the next game index from a ticket counter in the workspace: one atomicAdd per wavefront for
-// all its idle slots, the indices spread by an mbcnt prefix. A wavefront leaves when its slots are idle and the queue is
-// empty. Nothing waits on another wavefront: no spin, no grid barrier, and the games do not depend on which wavefront or
-// slot plays them.
-__device__ const uint32_t kPlayDirTable[G2048_DIR_TABLE_WORDS] = G2048_DIR_TABLE_INIT;
-
+// the beam agent's, with the game-slot core of g2048_play.h. One wavefront is one block and owns S = 16 E game slots, slot s
+// on lane s. Per move, for all of its live slots at once: the slot lanes write their boards to LDS, every lane reads the
+// dword its layer-1 B operand needs, the wavefront runs the shared forward, lanes 0..15 write the probabilities to LDS, and
+// each slot lane reads its own row, picks its action (policy_action) and makes the move (play_move). The slot's Game stays
+// in registers: this kernel has them to spare. Slots sit at different move indices, so the RNG keys are derived per lane
+// (rng_keys: the seed half is loop-invariant and hoisted). A finished game's slot takes the next game index from the ticket
+// counter (claim_games). A wavefront leaves when its slots are idle and the queue is empty.
 template <bool BF16, int E>
-__global__ __launch_bounds__(64) void policy_play_kernel(
-    unsigned long long *__restrict__ ticket, const unsigned char *__restrict__ W, uint4 *__restrict__ boards,
-    uint32_t *__restrict__ score, size_t n, uint64_t seed, uint64_t id_base, int max_moves, uint32_t mode,
-    int32_t *__restrict__ moves_out, int32_t *__restrict__ valid_out, int32_t *__restrict__ invalid_out,
-    int4 *__restrict__ milestone_out, double *__restrict__ reward_out, uint8_t *__restrict__ alive_out,
-    uint8_t *__restrict__ actions_out)
+__global__ __launch_bounds__(64) void policy_play_kernel(const unsigned char *__restrict__ W, uint32_t mode, const PlayArgs par)
 {
     constexpr int S = 16 * E;
     __shared__ uint4 s_board[S];
@@ -331,41 +268,19 @@ __global__ __launch_bounds__(64) void policy_play_kernel(
     const bool slot_lane = lane < S;
     using P = Packed<BF16>;
     const float *bias = reinterpret_cast<const float *>(W + P::kBias);
-    if (lane < G2048_DIR_TABLE_WORDS) reinterpret_cast<uint32_t *>(s_dir)[lane] = kPlayDirTable[lane];
+    load_dir_table(s_dir, threadIdx.x);
 
-    Board cur{{0u, 0u, 0u, 0u}};
-    uint32_t sc = 0u;
-    size_t g = 0;
+    Game game{};
     bool active = false, drained = false;        // drained: wave-uniform, the queue has no game left
-    int32_t t = 0, nvalid = 0;
-    int32_t ms[8];
-    double rsum = 0.0;
     for (;;) {
-        if (!drained) {
-            const uint64_t idle = __ballot(slot_lane && !active);
-            if (idle != 0ull) {
-                const uint32_t cnt = (uint32_t)__popcll(idle);
-                unsigned long long got = 0ull;
-                if (lane == 0) got = atomicAdd(ticket, (unsigned long long)cnt);
-                const uint64_t base = ((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(got >> 32)) << 32) |
-                                      __builtin_amdgcn_readfirstlane((uint32_t)got);
-                const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
-                if (slot_lane && !active && base + rank < n) {
-                    g = (size_t)(base + rank);
-                    const uint4 v = boards[g];
-                    cur = Board{{v.x, v.y, v.z, v.w}};
-                    sc = score[g];
-                    t = 0; nvalid = 0; rsum = 0.0;
-#pragma unroll
-                    for (int k = 0; k < 8; ++k) ms[k] = -1;
-                    active = true;
-                }
-                drained = base + cnt >= n;
-            }
+        if (!drained && claim_games(par, lane, slot_lane && !active, game.index, drained)) {
+            game = start_game(par, game.index);
+            active = true;
         }
         if (__ballot(active) == 0ull) break;
 
         // slot lanes -> LDS (idle slots: the empty board) -> each lane's B-operand dword of every tile
+        const Board &cur = game.board;
         if (slot_lane) s_board[lane] = active ? make_uint4(cur.w[0], cur.w[1], cur.w[2], cur.w[3]) : make_uint4(0u, 0u, 0u, 0u);
         __syncthreads();
         f4 x[E][2];
@@ -379,50 +294,8 @@ __global__ __launch_bounds__(64) void policy_play_kernel(
         __syncthreads();
 
         if (slot_lane && active) {
-            const float4 p = s_prob[lane];
-            const uint64_t id = id_base + g;
-            const uint32_t mask = valid_mask_env(cur);
-            uint32_t a;
-            if (mode == G2048_PLAY_POLICY_GREEDY) {              // argmax over the valid moves, ties to the lowest index
-                const uint32_t m = mask ? mask : 15u;            // (no valid move: all four, as sample_action does)
-                float best = 0.0f;
-                a = 4u;
-#pragma unroll
-                for (int k = 3; k >= 0; --k) {
-                    const float v = k == 0 ? p.x : k == 1 ? p.y : k == 2 ? p.z : p.w;
-                    if (((m >> k) & 1u) && (a == 4u || v >= best)) { a = (uint32_t)k; best = v; }
-                }
-            } else {
-                const Keys kp = rng_keys(seed, DOM_POLICY, (uint64_t)t);
-                float pa;
-                a = sample_action(p.x, p.y, p.z, p.w, mode == G2048_PLAY_POLICY_MASKED ? mask : 15u, rng_draw(kp.k0, kp.k1, id, 0u), pa);
-            }
-            const Keys ks = rng_keys(seed, DOM_STEP, (uint64_t)t);
-            const uint4 s0 = s_dir[2u * a], s1 = s_dir[2u * a + 1u];
-            const StepOut o = step_board_sel(cur, DirSel{s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w}, rng_draw(ks.k0, ks.k1, id, 0u));
-            if (actions_out) actions_out[g * (size_t)max_moves + (size_t)t] = (uint8_t)a;
-            cur = o.board;
-            sc += o.gain;
-            rsum += o.reward;
-            const int32_t maxcode = (int32_t)(o.flags >> G2048_FLAG_MAXCODE_SHIFT);
-#pragma unroll
-            for (int k = 0; k < 8; ++k)
-                if (ms[k] < 0 && maxcode >= 6 + k) ms[k] = t;       // tiles 64 .. 8192, as g2048_track_episodes records them
-            nvalid += (o.flags & G2048_FLAG_VALID) ? 1 : 0;
-            ++t;
-            const bool done = (o.flags & G2048_FLAG_DONE) != 0u;
-            if (done || t == max_moves) {
-                boards[g] = make_uint4(cur.w[0], cur.w[1], cur.w[2], cur.w[3]);
-                score[g] = sc;
-                moves_out[g] = t;
-                valid_out[g] = nvalid;
-                invalid_out[g] = t - nvalid;
-                milestone_out[2 * g] = make_int4(ms[0], ms[1], ms[2], ms[3]);
-                milestone_out[2 * g + 1] = make_int4(ms[4], ms[5], ms[6], ms[7]);
-                if (reward_out) reward_out[g] = rsum;
-                alive_out[g] = done ? 0 : 1;
-                active = false;
-            }
+            const uint32_t a = policy_action(s_prob[lane], valid_mask_env(cur), mode, par.seed, game.moves, par.id_base + game.index);
+            active = !play_move(game, a, par, s_dir);
         }
     }
 }
@@ -451,7 +324,7 @@ int g2048_policy_pack(const float *plain_f32, int n_out, int precision, void *pa
     if (!plain_f32 || !packed_out) return fail(G2048_ERR_ARG, "g2048_policy_pack: null pointer");
     if (!aligned(plain_f32, 4) || !aligned(packed_out, 16)) return fail(G2048_ERR_ARG, "g2048_policy_pack: misaligned pointer");
     if (n_out != 1 && n_out != 4) return fail(G2048_ERR_ARG, "g2048_policy_pack: n_out must be 4 (actor) or 1 (critic)");
-    if (precision != G2048_POLICY_F32 && precision != G2048_POLICY_BF16) return fail(G2048_ERR_ARG, "g2048_policy_pack: unknown precision");
+    if (!good_precision(precision)) return fail(G2048_ERR_ARG, "g2048_policy_pack: unknown precision");
     const size_t bytes = g2048_policy_packed_bytes(precision, n_out);
     const dim3 grid((unsigned)((bytes / 4 + 255) / 256));
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -471,7 +344,7 @@ int g2048_policy_forward(const void *boards, const void *actor_packed, const voi
     if (!aligned(boards, 16) || !aligned(actor_packed, 16) || !aligned(critic_packed_or_null, 16) || !aligned(probs_out, 16) ||
         !aligned(value_out_or_null, 4))
         return fail(G2048_ERR_ARG, "g2048_policy_forward: misaligned pointer (boards, packed weights, probs: 16 bytes; value: 4)");
-    if (opts != G2048_POLICY_F32 && opts != G2048_POLICY_BF16) return fail(G2048_ERR_ARG, "g2048_policy_forward: unknown opts (precision)");
+    if (!good_precision((int)opts)) return fail(G2048_ERR_ARG, "g2048_policy_forward: unknown opts (precision)");
     const bool bf16 = opts == G2048_POLICY_BF16;
     const size_t per_block = (size_t)kWaves * 16 * (bf16 ? kTilesBF16 : kTilesF32);
     const size_t blocks = (n + per_block - 1) / per_block;
@@ -488,11 +361,7 @@ int g2048_policy_forward(const void *boards, const void *actor_packed, const voi
     return check_launch("g2048_policy_forward");
 }
 
-size_t g2048_play_policy_workspace(size_t n_games)
-{
-    (void)n_games;
-    return 64;                                   // the ticket counter (uint64), padded
-}
+size_t g2048_play_policy_workspace(size_t n_games) { return ticket_workspace_bytes(n_games); }
 
 int g2048_play_policy_games(void *boards_inout, uint32_t *score_inout, const void *actor_packed, int32_t *moves_out,
                             int32_t *valid_out, int32_t *invalid_out, int32_t *milestone_move_out, double *reward_sum_out_or_null,
@@ -500,22 +369,14 @@ int g2048_play_policy_games(void *boards_inout, uint32_t *score_inout, const voi
                             size_t n_games, uint32_t opts, uint32_t max_waves, void *workspace, size_t workspace_bytes, void *stream)
 {
     if (n_games == 0) return G2048_OK;
-    if (!boards_inout || !score_inout || !actor_packed || !moves_out || !valid_out || !invalid_out || !milestone_move_out ||
-        !alive_out || !workspace)
-        return fail(G2048_ERR_ARG, "g2048_play_policy_games: null pointer");
-    if (!aligned(boards_inout, 16) || !aligned(actor_packed, 16) || !aligned(milestone_move_out, 16) || !aligned(score_inout, 4) ||
-        !aligned(moves_out, 4) || !aligned(valid_out, 4) || !aligned(invalid_out, 4) || !aligned(reward_sum_out_or_null, 8) ||
-        !aligned(workspace, 8))
-        return fail(G2048_ERR_ARG, "g2048_play_policy_games: misaligned pointer (boards, weights, milestones: 16 bytes; rewards, "
-                                   "workspace: 8; counters and scores: 4)");
+    if (const int rc = check_play_args("g2048_play_policy", boards_inout, score_inout, actor_packed, moves_out, valid_out, invalid_out,
+                                       milestone_move_out, reward_sum_out_or_null, alive_out, max_moves, n_games, workspace, workspace_bytes))
+        return rc;
     const uint32_t precision = opts & 0xfu, mode = (opts >> G2048_PLAY_POLICY_MODE_SHIFT) & 0xfu;
-    if ((opts >> (G2048_PLAY_POLICY_MODE_SHIFT + 4)) != 0u || (precision != G2048_POLICY_F32 && precision != G2048_POLICY_BF16))
+    if ((opts >> (G2048_PLAY_POLICY_MODE_SHIFT + 4)) != 0u || !good_precision((int)precision))
         return fail(G2048_ERR_ARG, "g2048_play_policy_games: unknown opts (precision | mode << 4)");
     if (mode != G2048_PLAY_POLICY_MASKED && mode != G2048_PLAY_POLICY_UNMASKED && mode != G2048_PLAY_POLICY_GREEDY)
         return fail(G2048_ERR_ARG, "g2048_play_policy_games: unknown mode");
-    if (max_moves < 1) return fail(G2048_ERR_ARG, "g2048_play_policy_games: max_moves must be at least 1");
-    if (workspace_bytes < g2048_play_policy_workspace(n_games))
-        return fail(G2048_ERR_ARG, "g2048_play_policy_games: workspace smaller than g2048_play_policy_workspace(n_games)");
     const bool bf16 = precision == G2048_POLICY_BF16;
     const size_t slots = 16 * (size_t)(bf16 ? kTilesBF16 : kTilesF32);
     // auto: as many wavefronts as the chip holds at once (every later one would only find the queue empty)
@@ -525,18 +386,13 @@ int g2048_play_policy_games(void *boards_inout, uint32_t *score_inout, const voi
     if (cap == 0) return fail(G2048_ERR_HIP, "g2048_play_policy_games: no HIP device (occupancy query failed)");
     const size_t waves = std::min(std::min((n_games + slots - 1) / slots, cap), (size_t)0x7fffffffu);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    auto *ticket = static_cast<unsigned long long *>(workspace);
-    hipError_t e = hipMemsetAsync(ticket, 0, sizeof *ticket, s);
-    if (e == hipSuccess && actions_out_or_null) e = hipMemsetAsync(actions_out_or_null, 0xff, n_games * (size_t)max_moves, s);
-    if (const int rc = check_hip(e, "g2048_play_policy_games: hipMemsetAsync")) return rc;
-    const dim3 grid((unsigned)waves);
-    auto *b = static_cast<uint4 *>(boards_inout);
-    const auto *w = static_cast<const unsigned char *>(actor_packed);
-    auto *ms = reinterpret_cast<int4 *>(milestone_move_out);
+    const PlayArgs args{static_cast<unsigned long long *>(workspace), static_cast<uint4 *>(boards_inout), score_inout, n_games, seed,
+                        game_id_base, moves_out, valid_out, invalid_out, reinterpret_cast<int4 *>(milestone_move_out), reward_sum_out_or_null,
+                        alive_out, actions_out_or_null, max_moves};
+    if (const int rc = reset_play_buffers("g2048_play_policy", workspace, actions_out_or_null, n_games, max_moves, s)) return rc;
     with_precision(bf16, [&](auto BF16, auto E) {
-        hipLaunchKernelGGL((policy_play_kernel<decltype(BF16)::value, decltype(E)::value>), grid, dim3(64), 0, s, ticket, w, b, score_inout, n_games,
-                           seed, game_id_base, max_moves, mode, moves_out, valid_out, invalid_out, ms, reward_sum_out_or_null, alive_out,
-                           actions_out_or_null);
+        hipLaunchKernelGGL((policy_play_kernel<decltype(BF16)::value, decltype(E)::value>), dim3((unsigned)waves), dim3(64), 0, s,
+                           static_cast<const unsigned char *>(actor_packed), mode, args);
     });
     return check_launch("g2048_play_policy_games");
 }

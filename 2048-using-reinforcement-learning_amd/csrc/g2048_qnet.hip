@@ -1,16 +1,17 @@
 // g2048_qnet.hip -- the hybrid agent's CNN-transformer Q-network (agents/hybrid.py:700-727, HybridDQN, in eval mode, one board
 // per call) on the matrix cores of gfx950, one launch per forward pass (C-ABI: include/g2048.h, g2048_qnet_*, g2048_play_qnet_*).
 //
-//   qnet_pack_matrix_kernel  one weight matrix [rows][K] into 1 KiB MFMA fragments (a lane's A operand is one 16-byte load), its
-//                            columns permuted so that conv2's and the embedding's K run in the order the forward produces them.
+//   pack_matrix_kernel       (g2048_mfma.h) one weight matrix [rows][K] into 1 KiB MFMA fragments (a lane's A operand is one
+//                            16-byte load), its columns permuted so that conv2's and the embedding's K run in the order the
+//                            forward produces them (conv2: inner 32, stride 4; the embedding: inner 64, stride 16).
 //   qnet_pack_params_kernel  conv1 (tap-major), every bias, the LayerNorm weights and their eps into the blob's f32 section.
 //   qnet_forward_kernel      Conv2d(1,32,k2,p1)+ReLU -> Conv2d(32,64,k2)+ReLU -> flatten -> Linear(1024,128) -> L x
 //                            TransformerEncoderLayer(128, dim_ff, relu, post-norm) at sequence length 1 -> Linear(128,4), and the
 //                            exploit action of DQNAgent.select_action (hybrid.py:943-953).
 //   qnet_select_kernel       the whole of select_action (:909-953, use_beam_search = False) on given Q-values: epsilon coin,
 //                            exploit argmax, exploration biased to RIGHT / DOWN (g2048_qnet_select_actions).
-//   qnet_play_kernel         complete games (evaluate_agent, :1176-1210) in one launch, 32 game slots a wavefront
-//                            (g2048_play_qnet_games).
+//   qnet_play_kernel         complete games (evaluate_agent, :1176-1210) in one launch, 32 game slots a wavefront, with the
+//                            game-slot core of g2048_play.h (g2048_play_qnet_games).
 //
 // What is computed. The reference feeds the encoder x.unsqueeze(1) with batch_first=False, and only ever calls the network with
 // one board, so every board is a sequence of ONE token: the softmax over one key is exactly 1.0 and the attention block is
@@ -48,18 +49,16 @@
 #include "../../include/g2048.h"
 #include "g2048_board.h"
 #include "g2048_host.h"
+#include "g2048_mfma.h"
+#include "g2048_play.h"
 #include "g2048_rng.h"
 
 namespace {
 
 using namespace g2048;
 
-typedef float f4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 // ------------------------------------------------------------------------------------------------ shapes and layouts --
 constexpr int kD = 128, kC1 = 32, kC2 = 64, kFlat = 1024, kK2 = 4 * kC1;      // widths; kK2: conv2's K per position
-constexpr int kFrag = 64 * 16;                       // bytes of one fragment
 
 // plain f32 layout (g2048_qnet_pack's input; include/g2048.h): the module's state-dict order
 constexpr int kPlC1W = 0, kPlC1B = kPlC1W + kC1 * 4, kPlC2W = kPlC1B + kC1, kPlC2B = kPlC2W + kC2 * kK2, kPlEmbW = kPlC2B + kC2,
@@ -96,40 +95,8 @@ struct Layout {
     __host__ __device__ size_t plain_floats() const { return (size_t)kPlainLayer0 + (size_t)layers * pl_layer(ff) + kPlTail; }
 };
 
-__device__ __host__ inline uint32_t bf16_rne(float v)
-{
-    const uint32_t u = __float_as_uint(v);
-    return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;        // finite inputs: round to nearest even by integer add
-}
-
 // ------------------------------------------------------------------------------------------------------------- pack --
-// One thread per packed 32-bit word (f32: one weight; bf16: two) of a matrix of `rows` rows (rows past them zero) and K columns:
-// word w of lane l of fragment (o, c) = W[16 o + (l & 15)][col(k)], k as the header says; packed column k is the plain column
-// (k % inner) * stride + k / inner (the identity for inner = K; conv2: inner 32, stride 4; the embedding: inner 64, stride 16).
-template <bool BF16>
-__global__ __launch_bounds__(256) void qnet_pack_matrix_kernel(const float *__restrict__ a, int rows, int K, int inner, int stride,
-                                                                unsigned words, uint32_t *__restrict__ packed)
-{
-    const unsigned w = blockIdx.x * 256u + threadIdx.x;
-    if (w >= words) return;
-    constexpr int kChunk = BF16 ? 32 : 16;
-    const int chunks = K / kChunk;
-    const int frag = (int)(w / 256u), lane = (int)(w % 256u) / 4, word = (int)(w % 4u);
-    const int o = frag / chunks, c = frag % chunks;
-    const int row = 16 * o + (lane & 15), g = lane >> 4;
-    auto weight = [&](int k) { return row < rows ? a[(size_t)row * K + (size_t)(k % inner) * stride + k / inner] : 0.0f; };
-    if (BF16) {
-        uint32_t pair[2];
-        for (int q = 0; q < 2; ++q) {
-            const int j = 2 * word + q;
-            pair[q] = bf16_rne(weight(32 * c + 16 * (j >> 2) + 4 * g + (j & 3)));
-        }
-        packed[w] = pair[0] | (pair[1] << 16);
-    } else {
-        packed[w] = __float_as_uint(weight(16 * c + 4 * g + word));
-    }
-}
-
+// (the matrices: pack_matrix_kernel, g2048_mfma.h)
 __global__ __launch_bounds__(256) void qnet_pack_params_kernel(const float *__restrict__ plain, int ff, int layers, int count,
                                                                 float *__restrict__ out)
 {
@@ -161,37 +128,6 @@ constexpr int kWaves = 4, kE = 2;                    // wavefronts per block, co
 constexpr int kWaveBoards = 16 * kE, kBlockBoards = kWaves * kWaveBoards;
 constexpr int kGrid = 36;                            // a board's zero-padded 6 x 6 grid; LDS holds [wave][grid cell][board]
 
-__device__ inline f4 relu(f4 v)
-{
-    return f4{fmaxf(v[0], 0.0f), fmaxf(v[1], 0.0f), fmaxf(v[2], 0.0f), fmaxf(v[3], 0.0f)};
-}
-
-__device__ inline bf16x8 to_bf16x8(f4 lo, f4 hi)
-{
-    // the float -> __bf16 cast is gfx950's v_cvt_pk_bf16_f32 (round to nearest even, two values per instruction)
-    return bf16x8{(__bf16)lo[0], (__bf16)lo[1], (__bf16)lo[2], (__bf16)lo[3], (__bf16)hi[0], (__bf16)hi[1], (__bf16)hi[2], (__bf16)hi[3]};
-}
-
-__device__ inline f4 load_f4(const void *p) { return *reinterpret_cast<const f4 *>(p); }
-__device__ inline f4 splat(float v) { return f4{v, v, v, v}; }
-
-// acc[e] += W(fragment) . act[e] over one chunk (f32: act[e][0] is the chunk's tile, 4 MFMAs; bf16: act[e][0..1], one MFMA)
-template <bool BF16>
-__device__ inline void chunk_mma(const unsigned char *frag, const f4 (&act)[kE][2], f4 (&acc)[kE])
-{
-    const f4 a = load_f4(frag);
-    if constexpr (BF16) {
-        const bf16x8 w = __builtin_bit_cast(bf16x8, a);
-#pragma unroll
-        for (int e = 0; e < kE; ++e) acc[e] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w, to_bf16x8(act[e][0], act[e][1]), acc[e], 0, 0, 0);
-    } else {
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-#pragma unroll
-            for (int e = 0; e < kE; ++e) acc[e] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[r], act[e][0][r], acc[e], 0, 0, 0);
-    }
-}
-
 // acc[e] += (row tile o of the matrix at `mat`, K = 16 T) . x[e]  (x: the T feature tiles of each column tile)
 template <bool BF16, int T>
 __device__ inline void project(const unsigned char *mat, int o, int lane, const f4 (&x)[kE][T], f4 (&acc)[kE])
@@ -205,7 +141,7 @@ __device__ inline void project(const unsigned char *mat, int o, int lane, const 
             in[e][0] = x[e][TPC * c];
             in[e][1] = x[e][TPC * c + TPC - 1];
         }
-        chunk_mma<BF16>(mat + ((size_t)(o * C + c) * 64 + lane) * 16, in, acc);
+        chunk_mma<BF16, kE>(mat + ((size_t)(o * C + c) * 64 + lane) * 16, in, acc);
     }
 }
 
@@ -226,7 +162,7 @@ __device__ inline void consume32(const unsigned char *mat, int c2, int s, int la
                 in[e][1] = h[e][1];
                 acc[e] = y[e][m];
             }
-            chunk_mma<BF16>(mat + ((size_t)(m * c2 + c) * 64 + lane) * 16, in, acc);
+            chunk_mma<BF16, kE>(mat + ((size_t)(m * c2 + c) * 64 + lane) * 16, in, acc);
 #pragma unroll
             for (int e = 0; e < kE; ++e) y[e][m] = acc[e];
         }
@@ -260,12 +196,6 @@ __device__ inline void pair(const unsigned char *W1, const float *b1, const unsi
         }
         consume32<BF16>(W2, c2, s, lane, h, y);
     }
-}
-
-__device__ inline float lanes_sum(float v)           // over the four lanes c, c + 16, c + 32, c + 48, the same on all four
-{
-    v += __shfl_xor(v, 16);
-    return v + __shfl_xor(v, 32);
 }
 
 // x = LayerNorm(x + y) over the 128 features of every board column; np = weight[128] bias[128], biased variance
@@ -428,7 +358,7 @@ _Pragma("unroll") \
                             in[e][1] = c1[e][1]; \
                             acc[e] = c2[e][o]; \
                         } \
-                        chunk_mma<BF16>(Wc2 + ((size_t)(o * (kK2 / (BF16 ? 32 : 16)) + c) * 64 + lane) * 16, in, acc); \
+                        chunk_mma<BF16, kE>(Wc2 + ((size_t)(o * (kK2 / (BF16 ? 32 : 16)) + c) * 64 + lane) * 16, in, acc); \
 _Pragma("unroll") \
                         for (int e = 0; e < kE; ++e) c2[e][o] = acc[e]; \
                     } \
@@ -507,41 +437,18 @@ __global__ __launch_bounds__(64 * kWaves, 2) void qnet_forward_kernel(const uint
 
 // --------------------------------------------------------------------------------------------------- complete games --
 // Complete games of the Q-network (the reference's evaluate_agent, hybrid.py:1176-1210: select_action -> env.step until done),
-// as tpolicy_play_kernel (g2048_tpolicy.hip) plays the transformer policy's. The forward's unit is the wavefront: it runs the
-// whole network alone on its 32 boards. So a wavefront owns 32 game slots, slot s = column s of its grids = lane s, and shares
-// nothing with the other three of its block but the launch arguments and the direction table in LDS: after the prologue there
-// is no block barrier, no wavefront waits on another, nothing spins. Per move the wavefront rebuilds its 6 x 6 grids from the
-// slots' boards in LDS (an idle slot holds the empty board), runs the shared forward, moves Q of the boards 16..31 from lanes
-// 0..15 to lanes 16..31, and each slot lane picks its action (exploit_action / select_action with step index = the slot's own
-// move t, id = the game's id), steps its board and does the bookkeeping with the code and the draws of tpolicy_play_kernel. The
-// forward leaves no registers over, so a slot's state (QPlaySlots, 80 bytes a slot) is parked in LDS between moves and loaded
-// after the forward, and the launch arguments (QPlayArgs) are read from LDS too. A finished game writes its results and its slot
-// takes the next game index from the ticket counter in the workspace: one atomicAdd per wavefront for all its idle slots, the
-// indices spread by an mbcnt prefix. The wavefront leaves when all its slots are idle after a refill attempt, which means the
-// queue is empty. The games do not depend on which wavefront or slot plays them.
-__device__ const uint32_t kQPlayDirTable[G2048_DIR_TABLE_WORDS] = G2048_DIR_TABLE_INIT;
-
-struct QPlaySlots {                                  // one wavefront's slots, one column per slot; a slot lane touches only its own
-    uint4 board[kWaveBoards];                        // the empty board while the slot is idle
-    int4 milestone[2][kWaveBoards];
-    double reward[kWaveBoards];
-    unsigned long long game[kWaveBoards];
-    uint32_t score[kWaveBoards];
-    int32_t moves[kWaveBoards], valid[kWaveBoards];
-    uint32_t active[kWaveBoards];
-};
-
+// as tpolicy_play_kernel (g2048_tpolicy.hip) plays the transformer policy's, with the game-slot core of g2048_play.h. The
+// forward's unit is the wavefront: it runs the whole network alone on its 32 boards. So a wavefront owns 32 game slots, slot s =
+// column s of its grids = lane s, and shares nothing with the other three of its block but the launch arguments and the
+// direction table in LDS: after the prologue there is no block barrier, no wavefront waits on another, nothing spins. Per move
+// the wavefront refills its idle slots (refill_slots: one atomicAdd per wavefront), rebuilds its 6 x 6 grids from the slots'
+// boards in LDS (an idle slot holds the empty board), runs the shared forward, moves Q of the boards 16..31 from lanes 0..15 to
+// lanes 16..31, and each slot lane picks its action (exploit_action / select_action with step index = the slot's own move t, id =
+// the game's id) and makes the move (play_slot_move). The forward leaves no registers over, so a slot's state (PlaySlots, 80
+// bytes a slot) is parked in LDS between moves and loaded after the forward, and the launch arguments are read from LDS too
+// (PlayArgs). The wavefront leaves when all its slots are idle after a refill attempt, which means the queue is empty.
 struct QPlayArgs {
-    unsigned long long *ticket;
-    uint4 *boards;
-    uint32_t *score;
-    size_t n;
-    uint64_t seed, id_base;
-    int32_t *moves_out, *valid_out, *invalid_out;
-    int4 *milestone_out;
-    double *reward_out;
-    uint8_t *alive_out, *actions_out;
-    int max_moves;
+    PlayArgs play;
     float epsilon;
     uint32_t n_waves;                                // wavefronts that play; the last block's surplus ones leave at once
 };
@@ -560,51 +467,23 @@ __global__ __launch_bounds__(64 * kWaves, 2) void qnet_play_kernel(const unsigne
 {
     __shared__ QPlayArgs par;
     __shared__ float lds[kWaves][kGrid][kWaveBoards];
-    __shared__ QPlaySlots wave_slots[kWaves];
+    __shared__ PlaySlots<kWaveBoards> wave_slots[kWaves];
     __shared__ uint4 s_dir[G2048_DIR_TABLE_WORDS / 4];
     const Layout lay(BF16, ff, layers);
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), g = lane >> 4, col = lane & 15;
     const bool slot_lane = lane < kWaveBoards;
-    QPlaySlots &slots = wave_slots[wave];
+    PlaySlots<kWaveBoards> &slots = wave_slots[wave];
     float (*grid)[kWaveBoards] = lds[wave];
-    if (threadIdx.x < G2048_DIR_TABLE_WORDS) reinterpret_cast<uint32_t *>(s_dir)[threadIdx.x] = kQPlayDirTable[threadIdx.x];
+    load_dir_table(s_dir, threadIdx.x);
     for (int i = lane; i < kGrid * kWaveBoards; i += 64) (&grid[0][0])[i] = 0.0f;
-    if (slot_lane) {
-        slots.active[lane] = 0u;
-        slots.board[lane] = make_uint4(0u, 0u, 0u, 0u);
-    }
+    if (slot_lane) slots.clear(lane);
     if (threadIdx.x == 0) par = args;
     __syncthreads();                                 // par and s_dir are there; the only block barrier
     if (blockIdx.x * (unsigned)kWaves + (unsigned)wave >= par.n_waves) return;
     bool drained = false;                            // wavefront-uniform: the queue has no game left
 
     for (;;) {
-        bool active = slot_lane && slots.active[lane] != 0u;
-        if (!drained) {
-            const uint64_t idle = __ballot(slot_lane && !active);
-            if (idle != 0ull) {
-                const uint32_t cnt = (uint32_t)__popcll(idle);
-                unsigned long long got = 0ull;
-                if (lane == 0) got = atomicAdd(par.ticket, (unsigned long long)cnt);
-                const uint64_t base = ((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(got >> 32)) << 32) |
-                                      __builtin_amdgcn_readfirstlane((uint32_t)got);
-                const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
-                if (slot_lane && !active && base + rank < par.n) {
-                    const size_t game = (size_t)(base + rank);
-                    slots.board[lane] = par.boards[game];
-                    slots.score[lane] = par.score[game];
-                    slots.game[lane] = game;
-                    slots.moves[lane] = 0;
-                    slots.valid[lane] = 0;
-                    slots.reward[lane] = 0.0;
-                    slots.milestone[0][lane] = make_int4(-1, -1, -1, -1);
-                    slots.milestone[1][lane] = make_int4(-1, -1, -1, -1);
-                    slots.active[lane] = 1u;
-                    active = true;
-                }
-                drained = base + cnt >= par.n;
-            }
-        }
+        const bool active = refill_slots(slots, par.play, lane, slot_lane, slot_lane && slots.active[lane] != 0u, drained);
         if (__ballot(active) == 0ull) break;         // every slot idle after a refill attempt = the queue is empty
         wave_sync();                                 // the slots' boards are there
 
@@ -628,62 +507,21 @@ __global__ __launch_bounds__(64 * kWaves, 2) void qnet_play_kernel(const unsigne
         }
 
         if (slot_lane && slots.active[lane] != 0u) {
-            const uint4 bw = slots.board[lane];
-            const Board cur{{bw.x, bw.y, bw.z, bw.w}};
-            const size_t game = (size_t)slots.game[lane];
-            const int32_t t = slots.moves[lane];
-            const uint64_t id = par.id_base + game;
-            const uint32_t mask = valid_mask_env(cur);
+            Game game = slots.load(lane);
+            const uint32_t mask = valid_mask_env(game.board);
             uint32_t a = exploit_action(qs[0], qs[1], qs[2], qs[3], mask);
             const float epsilon = par.epsilon;
             if (epsilon > 0.0f) {                    // (epsilon 0 never explores: no draw)
                 bool explored;
-                a = select_action(a, cur, mask, epsilon, rng_keys(par.seed, DOM_POLICY, (uint64_t)t), id, explored);
+                a = select_action(a, game.board, mask, epsilon, rng_keys(par.play.seed, DOM_POLICY, (uint64_t)game.moves),
+                                  par.play.id_base + game.index, explored);
             }
-            const Keys ks = rng_keys(par.seed, DOM_STEP, (uint64_t)t);
-            const uint4 s0 = s_dir[2u * a], s1 = s_dir[2u * a + 1u];
-            const StepOut o = step_board_sel(cur, DirSel{s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w}, rng_draw(ks.k0, ks.k1, id, 0u));
-            if (par.actions_out) par.actions_out[game * (size_t)par.max_moves + (size_t)t] = (uint8_t)a;
-            const uint32_t sc = slots.score[lane] + o.gain;
-            const double rsum = slots.reward[lane] + o.reward;
-            const int32_t maxcode = (int32_t)(o.flags >> G2048_FLAG_MAXCODE_SHIFT);
-            const int4 m0 = slots.milestone[0][lane], m1 = slots.milestone[1][lane];
-            int32_t ms[8] = {m0.x, m0.y, m0.z, m0.w, m1.x, m1.y, m1.z, m1.w};
-#pragma unroll
-            for (int k = 0; k < 8; ++k)
-                if (ms[k] < 0 && maxcode >= 6 + k) ms[k] = t;       // tiles 64 .. 8192, as g2048_track_episodes records them
-            const int32_t nvalid = slots.valid[lane] + ((o.flags & G2048_FLAG_VALID) ? 1 : 0);
-            const int32_t moved = t + 1;
-            const bool done = (o.flags & G2048_FLAG_DONE) != 0u;
-            const uint4 nb = make_uint4(o.board.w[0], o.board.w[1], o.board.w[2], o.board.w[3]);
-            if (done || moved == par.max_moves) {
-                par.boards[game] = nb;
-                par.score[game] = sc;
-                par.moves_out[game] = moved;
-                par.valid_out[game] = nvalid;
-                par.invalid_out[game] = moved - nvalid;
-                par.milestone_out[2 * game] = make_int4(ms[0], ms[1], ms[2], ms[3]);
-                par.milestone_out[2 * game + 1] = make_int4(ms[4], ms[5], ms[6], ms[7]);
-                if (par.reward_out) par.reward_out[game] = rsum;
-                par.alive_out[game] = done ? 0 : 1;
-                slots.board[lane] = make_uint4(0u, 0u, 0u, 0u);
-                slots.active[lane] = 0u;
-            } else {
-                slots.board[lane] = nb;
-                slots.score[lane] = sc;
-                slots.moves[lane] = moved;
-                slots.valid[lane] = nvalid;
-                slots.reward[lane] = rsum;
-                slots.milestone[0][lane] = make_int4(ms[0], ms[1], ms[2], ms[3]);
-                slots.milestone[1][lane] = make_int4(ms[4], ms[5], ms[6], ms[7]);
-            }
+            play_slot_move(slots, lane, game, a, par.play, s_dir);
         }
         wave_sync();                                 // the next move's refill and grids see this move's slots
     }
 }
 
-bool good_shape(int dim_ff, int n_layers) { return dim_ff >= 32 && dim_ff % 32 == 0 && dim_ff <= 65536 && n_layers >= 1 && n_layers <= 64; }
-bool good_precision(int p) { return p == G2048_POLICY_F32 || p == G2048_POLICY_BF16; }
 bool good_epsilon(float e) { return e >= 0.0f && e <= 1.0f; }      // false for NaN
 
 }  // namespace
@@ -692,7 +530,7 @@ extern "C" {
 
 size_t g2048_qnet_packed_bytes(int precision, int dim_ff, int n_layers)
 {
-    if (!good_precision(precision) || !good_shape(dim_ff, n_layers)) return 0;
+    if (!good_precision(precision) || !good_encoder_shape(dim_ff, n_layers)) return 0;
     return Layout(precision == G2048_POLICY_BF16, dim_ff, n_layers).bytes();
 }
 
@@ -701,7 +539,7 @@ int g2048_qnet_pack(const float *plain_f32, int dim_ff, int n_layers, int precis
     if (!plain_f32 || !packed_out) return fail(G2048_ERR_ARG, "g2048_qnet_pack: null pointer");
     if (!aligned(plain_f32, 4) || !aligned(packed_out, 16)) return fail(G2048_ERR_ARG, "g2048_qnet_pack: misaligned pointer");
     if (!good_precision(precision)) return fail(G2048_ERR_ARG, "g2048_qnet_pack: unknown precision");
-    if (!good_shape(dim_ff, n_layers))
+    if (!good_encoder_shape(dim_ff, n_layers))
         return fail(G2048_ERR_ARG, "g2048_qnet_pack: dim_ff must be a multiple of 32 (32 .. 65536) and n_layers 1 .. 64");
     const bool bf16 = precision == G2048_POLICY_BF16;
     const Layout lay(bf16, dim_ff, n_layers);
@@ -711,8 +549,8 @@ int g2048_qnet_pack(const float *plain_f32, int dim_ff, int n_layers, int precis
     auto matrix = [&](const float *a, int rows, int K, int inner, int stride, size_t frag) {
         const unsigned words = (unsigned)(((rows + 15) / 16) * lay.chunks(K)) * 256u;
         with_bool(bf16, [&](auto BF16) {
-            hipLaunchKernelGGL(qnet_pack_matrix_kernel<decltype(BF16)::value>, dim3(words / 256u), dim3(256), 0, s, a, rows, K, inner, stride,
-                               words, reinterpret_cast<uint32_t *>(out + frag * kFrag));
+            hipLaunchKernelGGL(pack_matrix_kernel<decltype(BF16)::value>, dim3(words / 256u), dim3(256), 0, s, a, rows, (const float *)nullptr,
+                               0, K, inner, stride, words, reinterpret_cast<uint32_t *>(out + frag * kFrag));
         });
     };
     matrix(plain_f32 + kPlC2W, kC2, kK2, kC1, 4, 0);
@@ -740,8 +578,8 @@ int g2048_qnet_forward(const void *boards, const void *packed, float *q_out, uin
     if (!boards || !packed || !q_out) return fail(G2048_ERR_ARG, "g2048_qnet_forward: null pointer");
     if (!aligned(boards, 16) || !aligned(packed, 16) || !aligned(q_out, 16))
         return fail(G2048_ERR_ARG, "g2048_qnet_forward: misaligned pointer (boards, packed weights, q: 16 bytes)");
-    if (opts != G2048_POLICY_F32 && opts != G2048_POLICY_BF16) return fail(G2048_ERR_ARG, "g2048_qnet_forward: unknown opts (precision)");
-    if (!good_shape(dim_ff, n_layers))
+    if (!good_precision((int)opts)) return fail(G2048_ERR_ARG, "g2048_qnet_forward: unknown opts (precision)");
+    if (!good_encoder_shape(dim_ff, n_layers))
         return fail(G2048_ERR_ARG, "g2048_qnet_forward: dim_ff must be a multiple of 32 (32 .. 65536) and n_layers 1 .. 64");
     const size_t blocks = (n + kBlockBoards - 1) / kBlockBoards;
     if (blocks > 0x7fffffffu) return fail(G2048_ERR_ARG, "g2048_qnet_forward: n too large for one launch");
@@ -770,11 +608,7 @@ int g2048_qnet_select_actions(const float *q, const void *boards, uint8_t *actio
     return check_launch("g2048_qnet_select_actions");
 }
 
-size_t g2048_play_qnet_workspace(size_t n_games)
-{
-    (void)n_games;
-    return 64;                                       // the ticket counter (uint64), padded
-}
+size_t g2048_play_qnet_workspace(size_t n_games) { return ticket_workspace_bytes(n_games); }
 
 int g2048_play_qnet_games(void *boards_inout, uint32_t *score_inout, const void *packed, int dim_ff, int n_layers, int32_t *moves_out,
                           int32_t *valid_out, int32_t *invalid_out, int32_t *milestone_move_out, double *reward_sum_out_or_null,
@@ -783,21 +617,13 @@ int g2048_play_qnet_games(void *boards_inout, uint32_t *score_inout, const void 
                           void *stream)
 {
     if (n_games == 0) return G2048_OK;
-    if (!boards_inout || !score_inout || !packed || !moves_out || !valid_out || !invalid_out || !milestone_move_out || !alive_out ||
-        !workspace)
-        return fail(G2048_ERR_ARG, "g2048_play_qnet_games: null pointer");
-    if (!aligned(boards_inout, 16) || !aligned(packed, 16) || !aligned(milestone_move_out, 16) || !aligned(score_inout, 4) ||
-        !aligned(moves_out, 4) || !aligned(valid_out, 4) || !aligned(invalid_out, 4) || !aligned(reward_sum_out_or_null, 8) ||
-        !aligned(workspace, 8))
-        return fail(G2048_ERR_ARG, "g2048_play_qnet_games: misaligned pointer (boards, weights, milestones: 16 bytes; rewards, "
-                                   "workspace: 8; counters and scores: 4)");
-    if (opts != G2048_POLICY_F32 && opts != G2048_POLICY_BF16) return fail(G2048_ERR_ARG, "g2048_play_qnet_games: unknown opts (precision)");
-    if (max_moves < 1) return fail(G2048_ERR_ARG, "g2048_play_qnet_games: max_moves must be at least 1");
+    if (const int rc = check_play_args("g2048_play_qnet", boards_inout, score_inout, packed, moves_out, valid_out, invalid_out,
+                                       milestone_move_out, reward_sum_out_or_null, alive_out, max_moves, n_games, workspace, workspace_bytes))
+        return rc;
+    if (!good_precision((int)opts)) return fail(G2048_ERR_ARG, "g2048_play_qnet_games: unknown opts (precision)");
     if (!good_epsilon(epsilon)) return fail(G2048_ERR_ARG, "g2048_play_qnet_games: epsilon must lie in [0, 1]");
-    if (!good_shape(dim_ff, n_layers))
+    if (!good_encoder_shape(dim_ff, n_layers))
         return fail(G2048_ERR_ARG, "g2048_play_qnet_games: dim_ff must be a multiple of 32 (32 .. 65536) and n_layers 1 .. 64");
-    if (workspace_bytes < g2048_play_qnet_workspace(n_games))
-        return fail(G2048_ERR_ARG, "g2048_play_qnet_games: workspace smaller than g2048_play_qnet_workspace(n_games)");
     const bool bf16 = opts == G2048_POLICY_BF16;
     // auto: as many wavefronts as the chip holds at once (every later one would only find the queue empty)
     const size_t cap = max_waves ? (size_t)max_waves : (size_t)device_cus() * kWaves * with_bool(bf16, [](auto BF16) {
@@ -806,13 +632,10 @@ int g2048_play_qnet_games(void *boards_inout, uint32_t *score_inout, const void 
     if (cap == 0) return fail(G2048_ERR_HIP, "g2048_play_qnet_games: no HIP device (occupancy query failed)");
     const size_t waves = std::min(std::min((n_games + kWaveBoards - 1) / kWaveBoards, cap), (size_t)0x7fffffffu);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    auto *ticket = static_cast<unsigned long long *>(workspace);
-    hipError_t e = hipMemsetAsync(ticket, 0, sizeof *ticket, s);
-    if (e == hipSuccess && actions_out_or_null) e = hipMemsetAsync(actions_out_or_null, 0xff, n_games * (size_t)max_moves, s);
-    if (const int rc = check_hip(e, "g2048_play_qnet_games: hipMemsetAsync")) return rc;
-    const QPlayArgs args{ticket, static_cast<uint4 *>(boards_inout), score_inout, n_games, seed, game_id_base, moves_out, valid_out,
-                         invalid_out, reinterpret_cast<int4 *>(milestone_move_out), reward_sum_out_or_null, alive_out, actions_out_or_null,
-                         max_moves, epsilon, (uint32_t)waves};
+    if (const int rc = reset_play_buffers("g2048_play_qnet", workspace, actions_out_or_null, n_games, max_moves, s)) return rc;
+    const QPlayArgs args{{static_cast<unsigned long long *>(workspace), static_cast<uint4 *>(boards_inout), score_inout, n_games, seed,
+                          game_id_base, moves_out, valid_out, invalid_out, reinterpret_cast<int4 *>(milestone_move_out),
+                          reward_sum_out_or_null, alive_out, actions_out_or_null, max_moves}, epsilon, (uint32_t)waves};
     with_bool(bf16, [&](auto BF16) {
         hipLaunchKernelGGL(qnet_play_kernel<decltype(BF16)::value>, dim3(blocks_for(waves, kWaves)), dim3(64 * kWaves), 0, s,
                            static_cast<const unsigned char *>(packed), dim_ff, n_layers, args);

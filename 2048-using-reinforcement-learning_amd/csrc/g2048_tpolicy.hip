@@ -1,13 +1,13 @@
 // g2048_tpolicy.hip -- the reference's transformer policy (models/transformer.py:4-40, eval mode) on the matrix cores of
 // gfx950, one launch per forward pass (C-ABI: include/g2048.h, g2048_tpolicy_*).
 //
-//   tpolicy_pack_matrix_kernel  one weight matrix [rows][K] (plus, for the two heads, a second one stacked under it) into 1 KiB
-//                               MFMA fragments: a lane's A operand is one 16-byte load.
+//   pack_matrix_kernel          (g2048_mfma.h) one weight matrix [rows][K] (plus, for the two heads, a second one stacked under
+//                               it) into 1 KiB MFMA fragments: a lane's A operand is one 16-byte load.
 //   tpolicy_pack_params_kernel  the embedding, every bias, the LayerNorm weights and their eps into the blob's f32 section.
 //   tpolicy_forward_kernel      Linear(1,64) -> L x TransformerEncoderLayer(64, 4 heads, dim_ff, relu, post-norm) -> flatten ->
 //                               Linear(1024,128)+ReLU -> Linear(128,64)+ReLU -> {Linear(64,4)+softmax | Linear(64,1)}.
 //   tpolicy_play_kernel         complete games of that policy: the same forward for a block's 16 game slots, then sampling, the
-//                               env step and the bookkeeping per slot, slots refilled from a ticket counter
+//                               env step and the bookkeeping per slot with the game-slot core of g2048_play.h
 //                               (g2048_play_tpolicy_games).
 //
 // Layout of the computation. A block of four wavefronts owns 16 boards, a wavefront four of them. In the encoder a board is one
@@ -38,18 +38,16 @@
 #include "../../include/g2048.h"
 #include "g2048_board.h"
 #include "g2048_host.h"
+#include "g2048_mfma.h"
+#include "g2048_play.h"
 #include "g2048_rng.h"
 
 namespace {
 
 using namespace g2048;
 
-typedef float f4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 // ------------------------------------------------------------------------------------------------ shapes and layouts --
 constexpr int kD = 64, kHeads = 4, kTok = 16, kFc1 = 128, kFc2 = 64, kFlat = kTok * kD;
-constexpr int kFrag = 64 * 16;                       // bytes of one fragment
 
 // plain f32 layout (g2048_tpolicy_pack's input; include/g2048.h)
 constexpr int kPlainEmb = 0, kPlainLayer0 = 2 * kD;
@@ -84,43 +82,8 @@ struct Layout {
     __host__ __device__ size_t plain_floats() const { return (size_t)kPlainLayer0 + (size_t)layers * pl_layer(ff) + kPlTail; }
 };
 
-__device__ __host__ inline uint32_t bf16_rne(float v)
-{
-    const uint32_t u = __float_as_uint(v);
-    return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;        // finite inputs: round to nearest even by integer add
-}
-
 // ------------------------------------------------------------------------------------------------------------- pack --
-// One thread per packed 32-bit word (f32: one weight; bf16: two) of a matrix of rows_a + rows_b rows (a over b, rows past
-// them zero) and K columns: word w of lane l of fragment (o, c) = W[16 o + (l & 15)][k], k as the header says.
-template <bool BF16>
-__global__ __launch_bounds__(256) void tpolicy_pack_matrix_kernel(const float *__restrict__ a, int rows_a, const float *__restrict__ b,
-                                                                   int rows_b, int K, unsigned words, uint32_t *__restrict__ packed)
-{
-    const unsigned w = blockIdx.x * 256u + threadIdx.x;
-    if (w >= words) return;
-    constexpr int kChunk = BF16 ? 32 : 16;
-    const int chunks = K / kChunk;
-    const int frag = (int)(w / 256u), lane = (int)(w % 256u) / 4, word = (int)(w % 4u);
-    const int o = frag / chunks, c = frag % chunks;
-    const int row = 16 * o + (lane & 15), g = lane >> 4;
-    auto weight = [&](int k) {
-        if (row < rows_a) return a[(size_t)row * K + k];
-        if (row < rows_a + rows_b) return b[(size_t)(row - rows_a) * K + k];
-        return 0.0f;
-    };
-    if (BF16) {
-        uint32_t pair[2];
-        for (int q = 0; q < 2; ++q) {
-            const int j = 2 * word + q;
-            pair[q] = bf16_rne(weight(32 * c + 16 * (j >> 2) + 4 * g + (j & 3)));
-        }
-        packed[w] = pair[0] | (pair[1] << 16);
-    } else {
-        packed[w] = __float_as_uint(weight(16 * c + 4 * g + word));
-    }
-}
-
+// (the matrices: pack_matrix_kernel, g2048_mfma.h)
 __global__ __launch_bounds__(256) void tpolicy_pack_params_kernel(const float *__restrict__ plain, int ff, int layers, int count,
                                                                    float *__restrict__ out)
 {
@@ -155,44 +118,6 @@ constexpr int kH1Stride = kFc1 + 4, kH2Stride = kFc2 + 4;
 constexpr int kLdsFloats = 16 * kBoardStride;
 static_assert(16 * kH1Stride + 16 * kH2Stride <= kLdsFloats, "the fc1 / fc2 outputs reuse the encoder-output buffer");
 
-__device__ inline f4 relu(f4 v)
-{
-    return f4{fmaxf(v[0], 0.0f), fmaxf(v[1], 0.0f), fmaxf(v[2], 0.0f), fmaxf(v[3], 0.0f)};
-}
-
-__device__ inline bf16x8 to_bf16x8(f4 lo, f4 hi)
-{
-    // the float -> __bf16 cast is gfx950's v_cvt_pk_bf16_f32 (round to nearest even, two values per instruction)
-    return bf16x8{(__bf16)lo[0], (__bf16)lo[1], (__bf16)lo[2], (__bf16)lo[3], (__bf16)hi[0], (__bf16)hi[1], (__bf16)hi[2], (__bf16)hi[3]};
-}
-
-__device__ inline f4 load_f4(const void *p) { return *reinterpret_cast<const f4 *>(p); }
-__device__ inline f4 splat(float v) { return f4{v, v, v, v}; }
-
-// acc[e] += W(fragment) . act[e] over one chunk (f32: act[e][0] is the chunk's tile, 4 MFMAs; bf16: act[e][0..1], one MFMA).
-// TRANSPOSED: acc[e] += act[e]^T . W^T instead, the activation as the A operand and the same fragment as the B operand.
-template <bool BF16, int E, bool TRANSPOSED = false>
-__device__ inline void chunk_mma(const unsigned char *frag, const f4 (&act)[E][2], f4 (&acc)[E])
-{
-    const f4 a = load_f4(frag);
-    if constexpr (BF16) {
-        const bf16x8 w = __builtin_bit_cast(bf16x8, a);
-#pragma unroll
-        for (int e = 0; e < E; ++e) {
-            const bf16x8 x = to_bf16x8(act[e][0], act[e][1]);
-            acc[e] = TRANSPOSED ? __builtin_amdgcn_mfma_f32_16x16x32_bf16(x, w, acc[e], 0, 0, 0)
-                                : __builtin_amdgcn_mfma_f32_16x16x32_bf16(w, x, acc[e], 0, 0, 0);
-        }
-    } else {
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-#pragma unroll
-            for (int e = 0; e < E; ++e)
-                acc[e] = TRANSPOSED ? __builtin_amdgcn_mfma_f32_16x16x4f32(act[e][0][r], a[r], acc[e], 0, 0, 0)
-                                    : __builtin_amdgcn_mfma_f32_16x16x4f32(a[r], act[e][0][r], acc[e], 0, 0, 0);
-    }
-}
-
 // acc[e] += (row tile o of the matrix at `mat`, K = 64) . x[e]  (x: the four feature tiles of each board)
 template <bool BF16, bool TRANSPOSED = false>
 __device__ inline void project64(const unsigned char *mat, int o, int lane, const f4 (&x)[kE][4], f4 (&acc)[kE])
@@ -208,18 +133,6 @@ __device__ inline void project64(const unsigned char *mat, int o, int lane, cons
         }
         chunk_mma<BF16, kE, TRANSPOSED>(mat + ((size_t)(o * C + c) * 64 + lane) * 16, in, acc);
     }
-}
-
-__device__ inline float lanes_sum(float v)           // over the four lanes c, c + 16, c + 32, c + 48, the same on all four
-{
-    v += __shfl_xor(v, 16);
-    return v + __shfl_xor(v, 32);
-}
-
-__device__ inline float lanes_max(float v)
-{
-    v = fmaxf(v, __shfl_xor(v, 16));
-    return fmaxf(v, __shfl_xor(v, 32));
 }
 
 // x = LayerNorm(x + y) over the 64 features of every (board, token) column; np = weight[64] bias[64], biased variance
@@ -251,15 +164,6 @@ __device__ inline void add_norm(f4 (&x)[kE][4], const f4 (&y)[kE][4], const floa
 #pragma unroll
         for (int t = 0; t < 4; ++t) x[e][t] = x[e][t] * splat(rstd) * w[t] + b[t];
     }
-}
-
-// nn.Softmax(dim=-1) of one board's four logits: exp(z - max) / sum, in f32
-__device__ __forceinline__ float4 softmax4(f4 z)
-{
-    const float m = fmaxf(fmaxf(z[0], z[1]), fmaxf(z[2], z[3]));
-    const float e0 = expf(z[0] - m), e1 = expf(z[1] - m), e2 = expf(z[2] - m), e3 = expf(z[3] - m);
-    const float sum = ((e0 + e1) + e2) + e3;
-    return make_float4(e0 / sum, e1 / sum, e2 / sum, e3 / sum);
 }
 
 // out += (row tile o of the matrix at `mat`, K = 16 * KT) . act, the activation of the 16 boards read from LDS rows of
@@ -469,100 +373,41 @@ __global__ __launch_bounds__(64 * kWaves, 2) void tpolicy_forward_kernel(const u
 }
 
 // --------------------------------------------------------------------------------------------------- complete games --
-// Complete games of the transformer policy, as policy_play_kernel (g2048_policy.hip) plays the PPO actor's. A block keeps the
-// forward kernel's geometry: four wavefronts, 16 boards -- here 16 game slots, slot s on lane s of wavefront 0, its board one of
-// the four of wavefront s / 4. Per move: every wavefront reads the cell bytes of its four slots' boards from LDS (an idle slot
-// holds the empty board) and the block runs the shared forward; the head tile lands on lanes 0..15 of wavefront 0 with column =
-// slot, so each slot lane has its own logits in registers, takes the softmax, picks its action, steps its board and does the
-// bookkeeping with the code and the draws of policy_play_kernel. The forward leaves no registers over (226 / 245 VGPRs), so a
-// slot's state (board, score, move index, counters, milestones, f64 reward sum, game index: PlaySlots, 80 bytes a slot) is
-// parked in LDS between moves and loaded after the forward. A finished game writes its results and its slot takes the next
-// game index from the ticket counter in the workspace: one atomicAdd per block for all its idle slots, the indices spread by
-// an mbcnt prefix. Wavefront 0 publishes the mask of live slots through LDS under the move's first barrier: the block leaves
-// when no slot is live, which after a refill attempt means the queue is empty. With kSkipIdleWave a wavefront whose four slots
-// are all idle skips its encoder (wave-uniformly; it still reaches every barrier); that is switched off, not having been measured.
-// Nothing waits on another block: no spin, no grid barrier, and the games do not depend on which block or slot plays them.
-__device__ const uint32_t kTPlayDirTable[G2048_DIR_TABLE_WORDS] = G2048_DIR_TABLE_INIT;
-
+// Complete games of the transformer policy, as policy_play_kernel (g2048_policy.hip) plays the PPO actor's, with the game-slot
+// core of g2048_play.h. A block keeps the forward kernel's geometry: four wavefronts, 16 boards -- here 16 game slots, slot s on
+// lane s of wavefront 0, its board one of the four of wavefront s / 4. Per move: every wavefront reads the cell bytes of its four
+// slots' boards from LDS (an idle slot holds the empty board) and the block runs the shared forward; the head tile lands on lanes
+// 0..15 of wavefront 0 with column = slot, so each slot lane has its own logits in registers, takes the softmax, picks its action
+// (policy_action) and makes the move (play_slot_move). The forward leaves no registers over (226 / 245 VGPRs), so a slot's state
+// (PlaySlots, 80 bytes a slot) is parked in LDS between moves and loaded after the forward, and the launch arguments are read
+// from LDS too (PlayArgs). Idle slots are refilled once per move (refill_slots: one atomicAdd per block). Wavefront 0 publishes
+// the mask of live slots through LDS under the move's first barrier: the block leaves when no slot is live, which after a refill
+// attempt means the queue is empty. With kSkipIdleWave a wavefront whose four slots are all idle skips its encoder
+// (wave-uniformly; it still reaches every barrier); that is switched off, not having been measured.
 constexpr int kSlots = kWaves * kE;
 constexpr bool kSkipIdleWave = false;                // built, and the games tested with it on; off until an A/B at the tail shows it faster
 
-struct PlaySlots {                                   // one column per slot; slot lanes read and write only their own
-    uint4 board[kSlots];                             // the empty board while the slot is idle
-    int4 milestone[2][kSlots];
-    double reward[kSlots];
-    unsigned long long game[kSlots];
-    uint32_t score[kSlots];
-    int32_t moves[kSlots], valid[kSlots];
-    uint32_t active[kSlots];
-};
-
-// Everything of a launch that only the refill and the slots' steps need. The forward alone takes 72 / 82 of the 106 scalar
-// registers, and these would be two dozen more held across it. So the block copies them to LDS once and the slot lanes read
-// them from there, after the forward, when registers are free. (Not enough on its own to stay out of scratch: see the opaque
-// blob address in the kernel.)
-struct PlayArgs {
-    unsigned long long *ticket;
-    uint4 *boards;
-    uint32_t *score;
-    size_t n;
-    uint64_t seed, id_base;
-    int32_t *moves_out, *valid_out, *invalid_out;
-    int4 *milestone_out;
-    double *reward_out;
-    uint8_t *alive_out, *actions_out;
-    int max_moves;
-    uint32_t mode;
-};
-
 template <bool BF16>
-__global__ __launch_bounds__(64 * kWaves, 2) void tpolicy_play_kernel(const unsigned char *__restrict__ weights, int ff, int layers, const PlayArgs args)
+__global__ __launch_bounds__(64 * kWaves, 2) void tpolicy_play_kernel(const unsigned char *__restrict__ weights, int ff, int layers, uint32_t mode,
+                                                                    const PlayArgs args)
 {
-    __shared__ PlayArgs par;
+    __shared__ PlayArgs par;                         // (not enough on its own to stay out of scratch: see the opaque blob address)
     __shared__ __attribute__((aligned(16))) float lds[kLdsFloats];
-    __shared__ PlaySlots slots;
+    __shared__ PlaySlots<kSlots> slots;
     __shared__ uint4 s_dir[G2048_DIR_TABLE_WORDS / 4];
     __shared__ uint32_t s_live;                      // bit s: slot s plays this move (written by wavefront 0 before the barrier)
     const Layout lay(BF16, ff, layers);
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), g = lane >> 4, col = lane & 15;
     const bool slot_lane = wave == 0 && lane < kSlots;
-    if (threadIdx.x < G2048_DIR_TABLE_WORDS) reinterpret_cast<uint32_t *>(s_dir)[threadIdx.x] = kTPlayDirTable[threadIdx.x];
-    if (slot_lane) {
-        slots.active[lane] = 0u;
-        slots.board[lane] = make_uint4(0u, 0u, 0u, 0u);
-    }
+    load_dir_table(s_dir, threadIdx.x);
+    if (slot_lane) slots.clear(lane);
     if (threadIdx.x == 0) par = args;
     __syncthreads();                                 // par and s_dir are there
     bool drained = false;                            // (wavefront 0) block-uniform: the queue has no game left
 
     for (;;) {
         if (wave == 0) {
-            bool active = slot_lane && slots.active[lane] != 0u;
-            if (!drained) {
-                const uint64_t idle = __ballot(slot_lane && !active);
-                if (idle != 0ull) {
-                    const uint32_t cnt = (uint32_t)__popcll(idle);
-                    unsigned long long got = 0ull;
-                    if (lane == 0) got = atomicAdd(par.ticket, (unsigned long long)cnt);
-                    const uint64_t base = ((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(got >> 32)) << 32) |
-                                          __builtin_amdgcn_readfirstlane((uint32_t)got);
-                    const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
-                    if (slot_lane && !active && base + rank < par.n) {
-                        const size_t game = (size_t)(base + rank);
-                        slots.board[lane] = par.boards[game];
-                        slots.score[lane] = par.score[game];
-                        slots.game[lane] = game;
-                        slots.moves[lane] = 0;
-                        slots.valid[lane] = 0;
-                        slots.reward[lane] = 0.0;
-                        slots.milestone[0][lane] = make_int4(-1, -1, -1, -1);
-                        slots.milestone[1][lane] = make_int4(-1, -1, -1, -1);
-                        slots.active[lane] = 1u;
-                        active = true;
-                    }
-                    drained = base + cnt >= par.n;
-                }
-            }
+            const bool active = refill_slots(slots, par, lane, slot_lane, slot_lane && slots.active[lane] != 0u, drained);
             const uint64_t live = __ballot(active);
             if (lane == 0) s_live = (uint32_t)live;
         }
@@ -591,71 +436,13 @@ __global__ __launch_bounds__(64 * kWaves, 2) void tpolicy_play_kernel(const unsi
         TPOLICY_HEADS_(BF16);
 
         if (slot_lane && slots.active[lane] != 0u) {
-            const float4 p = softmax4(z);
-            const uint4 bw = slots.board[lane];
-            const Board cur{{bw.x, bw.y, bw.z, bw.w}};
-            const size_t game = (size_t)slots.game[lane];
-            const int32_t t = slots.moves[lane];
-            const uint64_t id = par.id_base + game;
-            const uint32_t mask = valid_mask_env(cur);
-            uint32_t a;
-            if (par.mode == G2048_PLAY_POLICY_GREEDY) {              // argmax over the valid moves, ties to the lowest index
-                const uint32_t m = mask ? mask : 15u;            // (no valid move: all four, as sample_action does)
-                float best = 0.0f;
-                a = 4u;
-#pragma unroll
-                for (int k = 3; k >= 0; --k) {
-                    const float v = k == 0 ? p.x : k == 1 ? p.y : k == 2 ? p.z : p.w;
-                    if (((m >> k) & 1u) && (a == 4u || v >= best)) { a = (uint32_t)k; best = v; }
-                }
-            } else {
-                const Keys kp = rng_keys(par.seed, DOM_POLICY, (uint64_t)t);
-                float pa;
-                a = sample_action(p.x, p.y, p.z, p.w, par.mode == G2048_PLAY_POLICY_MASKED ? mask : 15u, rng_draw(kp.k0, kp.k1, id, 0u), pa);
-            }
-            const Keys ks = rng_keys(par.seed, DOM_STEP, (uint64_t)t);
-            const uint4 s0 = s_dir[2u * a], s1 = s_dir[2u * a + 1u];
-            const StepOut o = step_board_sel(cur, DirSel{s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w}, rng_draw(ks.k0, ks.k1, id, 0u));
-            if (par.actions_out) par.actions_out[game * (size_t)par.max_moves + (size_t)t] = (uint8_t)a;
-            const uint32_t sc = slots.score[lane] + o.gain;
-            const double rsum = slots.reward[lane] + o.reward;
-            const int32_t maxcode = (int32_t)(o.flags >> G2048_FLAG_MAXCODE_SHIFT);
-            const int4 m0 = slots.milestone[0][lane], m1 = slots.milestone[1][lane];
-            int32_t ms[8] = {m0.x, m0.y, m0.z, m0.w, m1.x, m1.y, m1.z, m1.w};
-#pragma unroll
-            for (int k = 0; k < 8; ++k)
-                if (ms[k] < 0 && maxcode >= 6 + k) ms[k] = t;       // tiles 64 .. 8192, as g2048_track_episodes records them
-            const int32_t nvalid = slots.valid[lane] + ((o.flags & G2048_FLAG_VALID) ? 1 : 0);
-            const int32_t moved = t + 1;
-            const bool done = (o.flags & G2048_FLAG_DONE) != 0u;
-            const uint4 nb = make_uint4(o.board.w[0], o.board.w[1], o.board.w[2], o.board.w[3]);
-            if (done || moved == par.max_moves) {
-                par.boards[game] = nb;
-                par.score[game] = sc;
-                par.moves_out[game] = moved;
-                par.valid_out[game] = nvalid;
-                par.invalid_out[game] = moved - nvalid;
-                par.milestone_out[2 * game] = make_int4(ms[0], ms[1], ms[2], ms[3]);
-                par.milestone_out[2 * game + 1] = make_int4(ms[4], ms[5], ms[6], ms[7]);
-                if (par.reward_out) par.reward_out[game] = rsum;
-                par.alive_out[game] = done ? 0 : 1;
-                slots.board[lane] = make_uint4(0u, 0u, 0u, 0u);
-                slots.active[lane] = 0u;
-            } else {
-                slots.board[lane] = nb;
-                slots.score[lane] = sc;
-                slots.moves[lane] = moved;
-                slots.valid[lane] = nvalid;
-                slots.reward[lane] = rsum;
-                slots.milestone[0][lane] = make_int4(ms[0], ms[1], ms[2], ms[3]);
-                slots.milestone[1][lane] = make_int4(ms[4], ms[5], ms[6], ms[7]);
-            }
+            Game game = slots.load(lane);
+            const uint32_t a = policy_action(softmax4(z), valid_mask_env(game.board), mode, par.seed, game.moves,
+                                             par.id_base + game.index);
+            play_slot_move(slots, lane, game, a, par, s_dir);
         }
     }
 }
-
-bool good_shape(int dim_ff, int n_layers) { return dim_ff >= 32 && dim_ff % 32 == 0 && dim_ff <= 65536 && n_layers >= 1 && n_layers <= 64; }
-bool good_precision(int p) { return p == G2048_POLICY_F32 || p == G2048_POLICY_BF16; }
 
 }  // namespace
 
@@ -663,7 +450,7 @@ extern "C" {
 
 size_t g2048_tpolicy_packed_bytes(int precision, int dim_ff, int n_layers)
 {
-    if (!good_precision(precision) || !good_shape(dim_ff, n_layers)) return 0;
+    if (!good_precision(precision) || !good_encoder_shape(dim_ff, n_layers)) return 0;
     return Layout(precision == G2048_POLICY_BF16, dim_ff, n_layers).bytes();
 }
 
@@ -672,7 +459,7 @@ int g2048_tpolicy_pack(const float *plain_f32, int dim_ff, int n_layers, int pre
     if (!plain_f32 || !packed_out) return fail(G2048_ERR_ARG, "g2048_tpolicy_pack: null pointer");
     if (!aligned(plain_f32, 4) || !aligned(packed_out, 16)) return fail(G2048_ERR_ARG, "g2048_tpolicy_pack: misaligned pointer");
     if (!good_precision(precision)) return fail(G2048_ERR_ARG, "g2048_tpolicy_pack: unknown precision");
-    if (!good_shape(dim_ff, n_layers))
+    if (!good_encoder_shape(dim_ff, n_layers))
         return fail(G2048_ERR_ARG, "g2048_tpolicy_pack: dim_ff must be a multiple of 32 (32 .. 65536) and n_layers 1 .. 64");
     const bool bf16 = precision == G2048_POLICY_BF16;
     const Layout lay(bf16, dim_ff, n_layers);
@@ -682,7 +469,7 @@ int g2048_tpolicy_pack(const float *plain_f32, int dim_ff, int n_layers, int pre
     auto matrix = [&](const float *a, int rows_a, const float *b, int rows_b, int K, size_t frag) {
         const unsigned words = (unsigned)(((rows_a + rows_b + 15) / 16) * lay.chunks(K)) * 256u;
         with_bool(bf16, [&](auto BF16) {
-            hipLaunchKernelGGL(tpolicy_pack_matrix_kernel<decltype(BF16)::value>, dim3(words / 256u), dim3(256), 0, s, a, rows_a, b, rows_b, K,
+            hipLaunchKernelGGL(pack_matrix_kernel<decltype(BF16)::value>, dim3(words / 256u), dim3(256), 0, s, a, rows_a, b, rows_b, K, K, 1,
                                words, reinterpret_cast<uint32_t *>(out + frag * kFrag));
         });
     };
@@ -711,8 +498,8 @@ int g2048_tpolicy_forward(const void *boards, const void *packed, float *probs_o
     if (!boards || !packed || !probs_out) return fail(G2048_ERR_ARG, "g2048_tpolicy_forward: null pointer");
     if (!aligned(boards, 16) || !aligned(packed, 16) || !aligned(probs_out, 16) || !aligned(value_out_or_null, 4))
         return fail(G2048_ERR_ARG, "g2048_tpolicy_forward: misaligned pointer (boards, packed weights, probs: 16 bytes; value: 4)");
-    if (opts != G2048_POLICY_F32 && opts != G2048_POLICY_BF16) return fail(G2048_ERR_ARG, "g2048_tpolicy_forward: unknown opts (precision)");
-    if (!good_shape(dim_ff, n_layers))
+    if (!good_precision((int)opts)) return fail(G2048_ERR_ARG, "g2048_tpolicy_forward: unknown opts (precision)");
+    if (!good_encoder_shape(dim_ff, n_layers))
         return fail(G2048_ERR_ARG, "g2048_tpolicy_forward: dim_ff must be a multiple of 32 (32 .. 65536) and n_layers 1 .. 64");
     const size_t blocks = (n + 15) / 16;
     if (blocks > 0x7fffffffu) return fail(G2048_ERR_ARG, "g2048_tpolicy_forward: n too large for one launch");
@@ -725,11 +512,7 @@ int g2048_tpolicy_forward(const void *boards, const void *packed, float *probs_o
     return check_launch("g2048_tpolicy_forward");
 }
 
-size_t g2048_play_tpolicy_workspace(size_t n_games)
-{
-    (void)n_games;
-    return 64;                                       // the ticket counter (uint64), padded
-}
+size_t g2048_play_tpolicy_workspace(size_t n_games) { return ticket_workspace_bytes(n_games); }
 
 int g2048_play_tpolicy_games(void *boards_inout, uint32_t *score_inout, const void *packed, int dim_ff, int n_layers, int32_t *moves_out,
                              int32_t *valid_out, int32_t *invalid_out, int32_t *milestone_move_out, double *reward_sum_out_or_null,
@@ -737,24 +520,16 @@ int g2048_play_tpolicy_games(void *boards_inout, uint32_t *score_inout, const vo
                              size_t n_games, uint32_t opts, uint32_t max_blocks, void *workspace, size_t workspace_bytes, void *stream)
 {
     if (n_games == 0) return G2048_OK;
-    if (!boards_inout || !score_inout || !packed || !moves_out || !valid_out || !invalid_out || !milestone_move_out || !alive_out ||
-        !workspace)
-        return fail(G2048_ERR_ARG, "g2048_play_tpolicy_games: null pointer");
-    if (!aligned(boards_inout, 16) || !aligned(packed, 16) || !aligned(milestone_move_out, 16) || !aligned(score_inout, 4) ||
-        !aligned(moves_out, 4) || !aligned(valid_out, 4) || !aligned(invalid_out, 4) || !aligned(reward_sum_out_or_null, 8) ||
-        !aligned(workspace, 8))
-        return fail(G2048_ERR_ARG, "g2048_play_tpolicy_games: misaligned pointer (boards, weights, milestones: 16 bytes; rewards, "
-                                   "workspace: 8; counters and scores: 4)");
+    if (const int rc = check_play_args("g2048_play_tpolicy", boards_inout, score_inout, packed, moves_out, valid_out, invalid_out,
+                                       milestone_move_out, reward_sum_out_or_null, alive_out, max_moves, n_games, workspace, workspace_bytes))
+        return rc;
     const uint32_t precision = opts & 0xfu, mode = (opts >> G2048_PLAY_POLICY_MODE_SHIFT) & 0xfu;
     if ((opts >> (G2048_PLAY_POLICY_MODE_SHIFT + 4)) != 0u || !good_precision((int)precision))
         return fail(G2048_ERR_ARG, "g2048_play_tpolicy_games: unknown opts (precision | mode << 4)");
     if (mode != G2048_PLAY_POLICY_MASKED && mode != G2048_PLAY_POLICY_UNMASKED && mode != G2048_PLAY_POLICY_GREEDY)
         return fail(G2048_ERR_ARG, "g2048_play_tpolicy_games: unknown mode");
-    if (max_moves < 1) return fail(G2048_ERR_ARG, "g2048_play_tpolicy_games: max_moves must be at least 1");
-    if (!good_shape(dim_ff, n_layers))
+    if (!good_encoder_shape(dim_ff, n_layers))
         return fail(G2048_ERR_ARG, "g2048_play_tpolicy_games: dim_ff must be a multiple of 32 (32 .. 65536) and n_layers 1 .. 64");
-    if (workspace_bytes < g2048_play_tpolicy_workspace(n_games))
-        return fail(G2048_ERR_ARG, "g2048_play_tpolicy_games: workspace smaller than g2048_play_tpolicy_workspace(n_games)");
     const bool bf16 = precision == G2048_POLICY_BF16;
     // auto: as many blocks as the chip holds at once (every later one would only find the queue empty)
     const size_t cap = max_blocks ? (size_t)max_blocks : (size_t)device_cus() * with_bool(bf16, [](auto BF16) {
@@ -763,16 +538,13 @@ int g2048_play_tpolicy_games(void *boards_inout, uint32_t *score_inout, const vo
     if (cap == 0) return fail(G2048_ERR_HIP, "g2048_play_tpolicy_games: no HIP device (occupancy query failed)");
     const size_t blocks = std::min(std::min((n_games + kSlots - 1) / kSlots, cap), (size_t)0x7fffffffu);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    auto *ticket = static_cast<unsigned long long *>(workspace);
-    hipError_t e = hipMemsetAsync(ticket, 0, sizeof *ticket, s);
-    if (e == hipSuccess && actions_out_or_null) e = hipMemsetAsync(actions_out_or_null, 0xff, n_games * (size_t)max_moves, s);
-    if (const int rc = check_hip(e, "g2048_play_tpolicy_games: hipMemsetAsync")) return rc;
-    const PlayArgs args{ticket, static_cast<uint4 *>(boards_inout), score_inout, n_games, seed, game_id_base, moves_out, valid_out,
-                        invalid_out, reinterpret_cast<int4 *>(milestone_move_out), reward_sum_out_or_null, alive_out, actions_out_or_null,
-                        max_moves, mode};
+    if (const int rc = reset_play_buffers("g2048_play_tpolicy", workspace, actions_out_or_null, n_games, max_moves, s)) return rc;
+    const PlayArgs args{static_cast<unsigned long long *>(workspace), static_cast<uint4 *>(boards_inout), score_inout, n_games, seed,
+                        game_id_base, moves_out, valid_out, invalid_out, reinterpret_cast<int4 *>(milestone_move_out), reward_sum_out_or_null,
+                        alive_out, actions_out_or_null, max_moves};
     with_bool(bf16, [&](auto BF16) {
         hipLaunchKernelGGL(tpolicy_play_kernel<decltype(BF16)::value>, dim3((unsigned)blocks), dim3(64 * kWaves), 0, s,
-                           static_cast<const unsigned char *>(packed), dim_ff, n_layers, args);
+                           static_cast<const unsigned char *>(packed), dim_ff, n_layers, mode, args);
     });
     return check_launch("g2048_play_tpolicy_games");
 }

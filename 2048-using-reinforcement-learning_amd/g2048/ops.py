@@ -977,7 +977,46 @@ def play_games(boards, scores, width, depth, max_moves=5000, early_threshold=512
 
 
 PLAY_POLICY_MODES = {"masked": L.PLAY_POLICY_MASKED, "unmasked": L.PLAY_POLICY_UNMASKED, "greedy": L.PLAY_POLICY_GREEDY}
-_PLAY_POLICY_WS = _PerStream()
+_PLAY_NET_WS = _PerStream()
+
+
+def _net_game_results(boards, scores, max_moves, max_units, units_name, want_rewards, want_actions):
+    """The checks play_policy_games, play_tpolicy_games and play_qnet_games make on what they have in common, and their
+    dict of per-game result tensors."""
+    n, dev = boards.shape[0], boards.device
+    if scores.shape[0] != n:
+        raise ValueError("g2048: scores length must equal the number of boards")
+    if int(max_moves) < 1:
+        raise ValueError("g2048: max_moves must be at least 1")
+    if not 0 <= int(max_units) <= 0xFFFFFFFF:
+        raise ValueError("g2048: %s must be 0 (auto) or a positive 32-bit count" % units_name)
+    out = {
+        "moves": torch.zeros(n, dtype=torch.int32, device=dev), "valid_moves": torch.zeros(n, dtype=torch.int32, device=dev),
+        "invalid_moves": torch.zeros(n, dtype=torch.int32, device=dev),
+        "milestone_move": torch.full((n, 8), -1, dtype=torch.int32, device=dev),
+        "alive": torch.zeros(n, dtype=torch.uint8, device=dev),
+    }
+    if want_rewards:
+        out["reward_sum"] = torch.zeros(n, dtype=torch.float64, device=dev)
+    if want_actions:
+        out["actions"] = torch.empty((n, int(max_moves)), dtype=torch.uint8, device=dev)     # (the library fills it with 0xFF)
+    return out
+
+
+def _play_net_games(fn, workspace_fn, boards, scores, net_args, out, max_moves, tail_args):
+    """One g2048_play_*_games call: fn(boards, scores, *net_args, <the result arrays of `out`>, max_moves, *tail_args, workspace,
+    workspace bytes, stream), the workspace kept per (device, stream) and grown under its lock."""
+    n, dev = boards.shape[0], boards.device
+    need = int(workspace_fn(n))
+    ptr = lambda k: out[k].data_ptr() if k in out else None      # noqa: E731
+    box = _PLAY_NET_WS.get((_dev_index(dev), L.stream_ptr(dev)), _ScratchBox)
+    with box.lock:          # grow-if-needed and enqueue as one step (see beam_get_action)
+        if box.buf is None or box.buf.numel() < need:
+            box.buf = torch.empty(need, dtype=torch.uint8, device=dev)
+        L.call(dev, fn, boards.data_ptr(), scores.data_ptr(), *net_args, out["moves"].data_ptr(), out["valid_moves"].data_ptr(),
+               out["invalid_moves"].data_ptr(), out["milestone_move"].data_ptr(), ptr("reward_sum"), out["alive"].data_ptr(),
+               ptr("actions"), int(max_moves), *tail_args, box.buf.data_ptr(), need, L.stream_ptr(dev))
+    return out
 
 
 def play_policy_games(boards, scores, actor_packed, precision="f32", max_moves=2000, mode="masked", seed=0x2048, game_id_base=0,
@@ -998,39 +1037,11 @@ def play_policy_games(boards, scores, actor_packed, precision="f32", max_moves=2
         raise ValueError("g2048: mode must be one of %s" % (tuple(PLAY_POLICY_MODES),))
     if actor_packed.numel() != policy_packed_bytes(precision, 4):
         raise ValueError("g2048: actor_packed must be a %s actor blob of %d bytes" % (precision, policy_packed_bytes(precision, 4)))
-    n, dev = boards.shape[0], boards.device
-    if scores.shape[0] != n:
-        raise ValueError("g2048: scores length must equal the number of boards")
-    if int(max_moves) < 1:
-        raise ValueError("g2048: max_moves must be at least 1")
-    if not 0 <= int(max_waves) <= 0xFFFFFFFF:
-        raise ValueError("g2048: max_waves must be 0 (auto) or a positive 32-bit count")
-    out = {
-        "moves": torch.zeros(n, dtype=torch.int32, device=dev), "valid_moves": torch.zeros(n, dtype=torch.int32, device=dev),
-        "invalid_moves": torch.zeros(n, dtype=torch.int32, device=dev),
-        "milestone_move": torch.full((n, 8), -1, dtype=torch.int32, device=dev),
-        "alive": torch.zeros(n, dtype=torch.uint8, device=dev),
-    }
-    if want_rewards:
-        out["reward_sum"] = torch.zeros(n, dtype=torch.float64, device=dev)
-    if want_actions:
-        out["actions"] = torch.empty((n, int(max_moves)), dtype=torch.uint8, device=dev)     # (the library fills it with 0xFF)
-    need = int(L.lib().g2048_play_policy_workspace(n))
+    out = _net_game_results(boards, scores, max_moves, max_waves, "max_waves", want_rewards, want_actions)
     opts = POLICY_PRECISIONS[precision] | (PLAY_POLICY_MODES[mode] << L.PLAY_POLICY_MODE_SHIFT)
-    ptr = lambda k: out[k].data_ptr() if k in out else None      # noqa: E731
-    box = _PLAY_POLICY_WS.get((_dev_index(dev), L.stream_ptr(dev)), _ScratchBox)
-    with box.lock:          # grow-if-needed and enqueue as one step (see beam_get_action)
-        if box.buf is None or box.buf.numel() < need:
-            box.buf = torch.empty(need, dtype=torch.uint8, device=dev)
-        L.call(dev, L.lib().g2048_play_policy_games, boards.data_ptr(), scores.data_ptr(), actor_packed.data_ptr(),
-               out["moves"].data_ptr(), out["valid_moves"].data_ptr(), out["invalid_moves"].data_ptr(),
-               out["milestone_move"].data_ptr(), ptr("reward_sum"), out["alive"].data_ptr(), ptr("actions"), int(max_moves),
-               L.u64(seed), L.u64(game_id_base), n, opts, int(max_waves), box.buf.data_ptr(), need,
-               L.stream_ptr(dev))
-    return out
-
-
-_PLAY_TPOLICY_WS = _PerStream()
+    return _play_net_games(L.lib().g2048_play_policy_games, L.lib().g2048_play_policy_workspace, boards, scores,
+                           (actor_packed.data_ptr(),), out, max_moves,
+                           (L.u64(seed), L.u64(game_id_base), boards.shape[0], opts, int(max_waves)))
 
 
 def play_tpolicy_games(boards, scores, packed, dim_ff, n_layers, precision="f32", max_moves=2000, mode="masked", seed=0x2048,
@@ -1051,38 +1062,11 @@ def play_tpolicy_games(boards, scores, packed, dim_ff, n_layers, precision="f32"
     L.require_device_tensor(boards, torch.uint8, (16,), "boards")
     _require_scores(scores)
     L.require_device_tensor(packed, torch.uint8, None, "packed")
-    n, dev = boards.shape[0], boards.device
-    if scores.shape[0] != n:
-        raise ValueError("g2048: scores length must equal the number of boards")
-    if int(max_moves) < 1:
-        raise ValueError("g2048: max_moves must be at least 1")
-    if not 0 <= int(max_blocks) <= 0xFFFFFFFF:
-        raise ValueError("g2048: max_blocks must be 0 (auto) or a positive 32-bit count")
-    out = {
-        "moves": torch.zeros(n, dtype=torch.int32, device=dev), "valid_moves": torch.zeros(n, dtype=torch.int32, device=dev),
-        "invalid_moves": torch.zeros(n, dtype=torch.int32, device=dev),
-        "milestone_move": torch.full((n, 8), -1, dtype=torch.int32, device=dev),
-        "alive": torch.zeros(n, dtype=torch.uint8, device=dev),
-    }
-    if want_rewards:
-        out["reward_sum"] = torch.zeros(n, dtype=torch.float64, device=dev)
-    if want_actions:
-        out["actions"] = torch.empty((n, int(max_moves)), dtype=torch.uint8, device=dev)     # (the library fills it with 0xFF)
-    need = int(L.lib().g2048_play_tpolicy_workspace(n))
+    out = _net_game_results(boards, scores, max_moves, max_blocks, "max_blocks", want_rewards, want_actions)
     opts = POLICY_PRECISIONS[precision] | (PLAY_POLICY_MODES[mode] << L.PLAY_POLICY_MODE_SHIFT)
-    ptr = lambda k: out[k].data_ptr() if k in out else None      # noqa: E731
-    box = _PLAY_TPOLICY_WS.get((_dev_index(dev), L.stream_ptr(dev)), _ScratchBox)
-    with box.lock:          # grow-if-needed and enqueue as one step (see beam_get_action)
-        if box.buf is None or box.buf.numel() < need:
-            box.buf = torch.empty(need, dtype=torch.uint8, device=dev)
-        L.call(dev, L.lib().g2048_play_tpolicy_games, boards.data_ptr(), scores.data_ptr(), packed.data_ptr(), int(dim_ff),
-               int(n_layers), out["moves"].data_ptr(), out["valid_moves"].data_ptr(), out["invalid_moves"].data_ptr(),
-               out["milestone_move"].data_ptr(), ptr("reward_sum"), out["alive"].data_ptr(), ptr("actions"), int(max_moves),
-               L.u64(seed), L.u64(game_id_base), n, opts, int(max_blocks), box.buf.data_ptr(), need, L.stream_ptr(dev))
-    return out
-
-
-_PLAY_QNET_WS = _PerStream()
+    return _play_net_games(L.lib().g2048_play_tpolicy_games, L.lib().g2048_play_tpolicy_workspace, boards, scores,
+                           (packed.data_ptr(), int(dim_ff), int(n_layers)), out, max_moves,
+                           (L.u64(seed), L.u64(game_id_base), boards.shape[0], opts, int(max_blocks)))
 
 
 def play_qnet_games(boards, scores, packed, dim_ff, n_layers, precision="f32", max_moves=2000, epsilon=0.0, seed=0x2048,
@@ -1106,35 +1090,10 @@ def play_qnet_games(boards, scores, packed, dim_ff, n_layers, precision="f32", m
     L.require_device_tensor(boards, torch.uint8, (16,), "boards")
     _require_scores(scores)
     L.require_device_tensor(packed, torch.uint8, None, "packed")
-    n, dev = boards.shape[0], boards.device
-    if scores.shape[0] != n:
-        raise ValueError("g2048: scores length must equal the number of boards")
-    if int(max_moves) < 1:
-        raise ValueError("g2048: max_moves must be at least 1")
-    if not 0 <= int(max_waves) <= 0xFFFFFFFF:
-        raise ValueError("g2048: max_waves must be 0 (auto) or a positive 32-bit count")
-    out = {
-        "moves": torch.zeros(n, dtype=torch.int32, device=dev), "valid_moves": torch.zeros(n, dtype=torch.int32, device=dev),
-        "invalid_moves": torch.zeros(n, dtype=torch.int32, device=dev),
-        "milestone_move": torch.full((n, 8), -1, dtype=torch.int32, device=dev),
-        "alive": torch.zeros(n, dtype=torch.uint8, device=dev),
-    }
-    if want_rewards:
-        out["reward_sum"] = torch.zeros(n, dtype=torch.float64, device=dev)
-    if want_actions:
-        out["actions"] = torch.empty((n, int(max_moves)), dtype=torch.uint8, device=dev)     # (the library fills it with 0xFF)
-    need = int(L.lib().g2048_play_qnet_workspace(n))
-    ptr = lambda k: out[k].data_ptr() if k in out else None      # noqa: E731
-    box = _PLAY_QNET_WS.get((_dev_index(dev), L.stream_ptr(dev)), _ScratchBox)
-    with box.lock:          # grow-if-needed and enqueue as one step (see beam_get_action)
-        if box.buf is None or box.buf.numel() < need:
-            box.buf = torch.empty(need, dtype=torch.uint8, device=dev)
-        L.call(dev, L.lib().g2048_play_qnet_games, boards.data_ptr(), scores.data_ptr(), packed.data_ptr(), int(dim_ff),
-               int(n_layers), out["moves"].data_ptr(), out["valid_moves"].data_ptr(), out["invalid_moves"].data_ptr(),
-               out["milestone_move"].data_ptr(), ptr("reward_sum"), out["alive"].data_ptr(), ptr("actions"), int(max_moves), epsilon,
-               L.u64(seed), L.u64(game_id_base), n, POLICY_PRECISIONS[precision], int(max_waves), box.buf.data_ptr(), need,
-               L.stream_ptr(dev))
-    return out
+    out = _net_game_results(boards, scores, max_moves, max_waves, "max_waves", want_rewards, want_actions)
+    return _play_net_games(L.lib().g2048_play_qnet_games, L.lib().g2048_play_qnet_workspace, boards, scores,
+                           (packed.data_ptr(), int(dim_ff), int(n_layers)), out, max_moves,
+                           (epsilon, L.u64(seed), L.u64(game_id_base), boards.shape[0], POLICY_PRECISIONS[precision], int(max_waves)))
 
 
 def replay_games(boards0, actions, n_moves, seed, game_ids=None, game_id_base=0, scores0=None, longest=None):
