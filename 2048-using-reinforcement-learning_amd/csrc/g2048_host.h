@@ -49,6 +49,28 @@ inline bool good_encoder_shape(int dim_ff, int n_layers)
     return dim_ff >= 32 && dim_ff % 32 == 0 && dim_ff <= 65536 && n_layers >= 1 && n_layers <= 64;
 }
 
+// ------------------------------------------------------- the two encoder networks (g2048_tpolicy.hip, g2048_qnet.hip) --
+// precision and encoder shape: G2048_OK, or the error as `entry`'s. precision_arg: what that entry point calls the argument
+// the precision arrives in ("precision", "opts (precision)")
+inline int check_encoder_net(const char *entry, int precision, const char *precision_arg, int dim_ff, int n_layers)
+{
+    if (!good_precision(precision)) return fail(G2048_ERR_ARG, "%s: unknown %s", entry, precision_arg);
+    if (!good_encoder_shape(dim_ff, n_layers))
+        return fail(G2048_ERR_ARG, "%s: dim_ff must be a multiple of 32 (32 .. 65536) and n_layers 1 .. 64", entry);
+    return G2048_OK;
+}
+
+// One launch of pack_matrix_kernel (g2048_mfma.h; `kernel` is its instantiation for the precision, `chunk` that precision's input
+// features per fragment): the matrix of rows_a + rows_b rows (a over b) x K into the fragments from `dst` on, packed column
+// k = plain column (k % inner) * stride + k / inner (the identity for inner = K, stride = 1).
+template <class Kernel>
+void launch_pack_matrix(Kernel kernel, int chunk, hipStream_t s, void *dst, const float *a, int rows_a, int K, int inner, int stride,
+                        const float *b = nullptr, int rows_b = 0)
+{
+    const unsigned frags = (unsigned)(((rows_a + rows_b + 15) / 16) * (K / chunk));
+    hipLaunchKernelGGL(kernel, dim3(frags), dim3(256), 0, s, a, rows_a, b, rows_b, K, inner, stride, frags * 256u, static_cast<uint32_t *>(dst));
+}
+
 // --------------------------------------------------------------------------------------- complete games of a network --
 // What g2048_play_policy_games, g2048_play_tpolicy_games and g2048_play_qnet_games share on the host (the device side is
 // g2048_play.h). `stem` is the entry point's name without "_games", e.g. "g2048_play_policy": the messages name

@@ -538,33 +538,25 @@ int g2048_qnet_pack(const float *plain_f32, int dim_ff, int n_layers, int precis
 {
     if (!plain_f32 || !packed_out) return fail(G2048_ERR_ARG, "g2048_qnet_pack: null pointer");
     if (!aligned(plain_f32, 4) || !aligned(packed_out, 16)) return fail(G2048_ERR_ARG, "g2048_qnet_pack: misaligned pointer");
-    if (!good_precision(precision)) return fail(G2048_ERR_ARG, "g2048_qnet_pack: unknown precision");
-    if (!good_encoder_shape(dim_ff, n_layers))
-        return fail(G2048_ERR_ARG, "g2048_qnet_pack: dim_ff must be a multiple of 32 (32 .. 65536) and n_layers 1 .. 64");
+    if (const int rc = check_encoder_net("g2048_qnet_pack", precision, "precision", dim_ff, n_layers)) return rc;
     const bool bf16 = precision == G2048_POLICY_BF16;
     const Layout lay(bf16, dim_ff, n_layers);
     hipStream_t s = static_cast<hipStream_t>(stream);
     auto *out = static_cast<unsigned char *>(packed_out);
-    // one launch per matrix: rows x K into the fragments from index `frag`, packed column k = plain (k % inner) * stride + k / inner
-    auto matrix = [&](const float *a, int rows, int K, int inner, int stride, size_t frag) {
-        const unsigned words = (unsigned)(((rows + 15) / 16) * lay.chunks(K)) * 256u;
-        with_bool(bf16, [&](auto BF16) {
-            hipLaunchKernelGGL(pack_matrix_kernel<decltype(BF16)::value>, dim3(words / 256u), dim3(256), 0, s, a, rows, (const float *)nullptr,
-                               0, K, inner, stride, words, reinterpret_cast<uint32_t *>(out + frag * kFrag));
-        });
-    };
-    matrix(plain_f32 + kPlC2W, kC2, kK2, kC1, 4, 0);
-    matrix(plain_f32 + kPlEmbW, kD, kFlat, kC2, 16, lay.emb());
+    // one launch per matrix: rows x K into the fragments from the index that `out` is offset by, columns permuted by (inner, stride)
+    const auto pack = bf16 ? pack_matrix_kernel<true> : pack_matrix_kernel<false>;
+    launch_pack_matrix(pack, lay.chunk, s, out, plain_f32 + kPlC2W, kC2, kK2, kC1, 4);
+    launch_pack_matrix(pack, lay.chunk, s, out + lay.emb() * kFrag, plain_f32 + kPlEmbW, kD, kFlat, kC2, 16);
     for (int l = 0; l < n_layers; ++l) {
         const float *p = plain_f32 + kPlainLayer0 + (size_t)l * pl_layer(dim_ff);
-        const size_t f = lay.layer0() + (size_t)l * lay.layer_frags();
-        matrix(p + kPlInW + 2 * kD * kD, kD, kD, kD, 1, f);              // the V rows 256 .. 383 of in_proj_weight
-        matrix(p + kPlOutW, kD, kD, kD, 1, f + lay.out_proj());
-        matrix(p + kPlW1, dim_ff, kD, kD, 1, f + lay.w1());
-        matrix(p + pl_w2(dim_ff), kD, dim_ff, dim_ff, 1, f + lay.w2());
+        unsigned char *f = out + (lay.layer0() + (size_t)l * lay.layer_frags()) * kFrag;
+        launch_pack_matrix(pack, lay.chunk, s, f, p + kPlInW + 2 * kD * kD, kD, kD, kD, 1);     // the V rows 256 .. 383 of in_proj_weight
+        launch_pack_matrix(pack, lay.chunk, s, f + lay.out_proj() * kFrag, p + kPlOutW, kD, kD, kD, 1);
+        launch_pack_matrix(pack, lay.chunk, s, f + lay.w1() * kFrag, p + kPlW1, dim_ff, kD, kD, 1);
+        launch_pack_matrix(pack, lay.chunk, s, f + lay.w2() * kFrag, p + pl_w2(dim_ff), kD, dim_ff, dim_ff, 1);
     }
     const float *t = plain_f32 + kPlainLayer0 + (size_t)n_layers * pl_layer(dim_ff);
-    matrix(t + kPlFcW, 4, kD, kD, 1, lay.fc());
+    launch_pack_matrix(pack, lay.chunk, s, out + lay.fc() * kFrag, t + kPlFcW, 4, kD, kD, 1);
     const int count = lay.n_params();
     hipLaunchKernelGGL(qnet_pack_params_kernel, dim3(blocks_for((size_t)count, 256)), dim3(256), 0, s, plain_f32, dim_ff, n_layers, count,
                        reinterpret_cast<float *>(out + lay.params()));
@@ -578,9 +570,7 @@ int g2048_qnet_forward(const void *boards, const void *packed, float *q_out, uin
     if (!boards || !packed || !q_out) return fail(G2048_ERR_ARG, "g2048_qnet_forward: null pointer");
     if (!aligned(boards, 16) || !aligned(packed, 16) || !aligned(q_out, 16))
         return fail(G2048_ERR_ARG, "g2048_qnet_forward: misaligned pointer (boards, packed weights, q: 16 bytes)");
-    if (!good_precision((int)opts)) return fail(G2048_ERR_ARG, "g2048_qnet_forward: unknown opts (precision)");
-    if (!good_encoder_shape(dim_ff, n_layers))
-        return fail(G2048_ERR_ARG, "g2048_qnet_forward: dim_ff must be a multiple of 32 (32 .. 65536) and n_layers 1 .. 64");
+    if (const int rc = check_encoder_net("g2048_qnet_forward", (int)opts, "opts (precision)", dim_ff, n_layers)) return rc;
     const size_t blocks = (n + kBlockBoards - 1) / kBlockBoards;
     if (blocks > 0x7fffffffu) return fail(G2048_ERR_ARG, "g2048_qnet_forward: n too large for one launch");
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -620,10 +610,8 @@ int g2048_play_qnet_games(void *boards_inout, uint32_t *score_inout, const void 
     if (const int rc = check_play_args("g2048_play_qnet", boards_inout, score_inout, packed, moves_out, valid_out, invalid_out,
                                        milestone_move_out, reward_sum_out_or_null, alive_out, max_moves, n_games, workspace, workspace_bytes))
         return rc;
-    if (!good_precision((int)opts)) return fail(G2048_ERR_ARG, "g2048_play_qnet_games: unknown opts (precision)");
+    if (const int rc = check_encoder_net("g2048_play_qnet_games", (int)opts, "opts (precision)", dim_ff, n_layers)) return rc;
     if (!good_epsilon(epsilon)) return fail(G2048_ERR_ARG, "g2048_play_qnet_games: epsilon must lie in [0, 1]");
-    if (!good_encoder_shape(dim_ff, n_layers))
-        return fail(G2048_ERR_ARG, "g2048_play_qnet_games: dim_ff must be a multiple of 32 (32 .. 65536) and n_layers 1 .. 64");
     const bool bf16 = opts == G2048_POLICY_BF16;
     // auto: as many wavefronts as the chip holds at once (every later one would only find the queue empty)
     const size_t cap = max_waves ? (size_t)max_waves : (size_t)device_cus() * kWaves * with_bool(bf16, [](auto BF16) {

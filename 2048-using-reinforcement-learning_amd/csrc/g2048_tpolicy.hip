@@ -458,33 +458,25 @@ int g2048_tpolicy_pack(const float *plain_f32, int dim_ff, int n_layers, int pre
 {
     if (!plain_f32 || !packed_out) return fail(G2048_ERR_ARG, "g2048_tpolicy_pack: null pointer");
     if (!aligned(plain_f32, 4) || !aligned(packed_out, 16)) return fail(G2048_ERR_ARG, "g2048_tpolicy_pack: misaligned pointer");
-    if (!good_precision(precision)) return fail(G2048_ERR_ARG, "g2048_tpolicy_pack: unknown precision");
-    if (!good_encoder_shape(dim_ff, n_layers))
-        return fail(G2048_ERR_ARG, "g2048_tpolicy_pack: dim_ff must be a multiple of 32 (32 .. 65536) and n_layers 1 .. 64");
+    if (const int rc = check_encoder_net("g2048_tpolicy_pack", precision, "precision", dim_ff, n_layers)) return rc;
     const bool bf16 = precision == G2048_POLICY_BF16;
     const Layout lay(bf16, dim_ff, n_layers);
     hipStream_t s = static_cast<hipStream_t>(stream);
     auto *out = static_cast<unsigned char *>(packed_out);
-    // one launch per matrix: `rows` (a over b) x K into the fragments from index `frag`
-    auto matrix = [&](const float *a, int rows_a, const float *b, int rows_b, int K, size_t frag) {
-        const unsigned words = (unsigned)(((rows_a + rows_b + 15) / 16) * lay.chunks(K)) * 256u;
-        with_bool(bf16, [&](auto BF16) {
-            hipLaunchKernelGGL(pack_matrix_kernel<decltype(BF16)::value>, dim3(words / 256u), dim3(256), 0, s, a, rows_a, b, rows_b, K, K, 1,
-                               words, reinterpret_cast<uint32_t *>(out + frag * kFrag));
-        });
-    };
+    // one launch per matrix: rows x K into the fragments from the index that `out` is offset by
+    const auto pack = bf16 ? pack_matrix_kernel<true> : pack_matrix_kernel<false>;
     for (int l = 0; l < n_layers; ++l) {
         const float *p = plain_f32 + kPlainLayer0 + (size_t)l * pl_layer(dim_ff);
-        const size_t f = (size_t)l * lay.layer_frags();
-        matrix(p + kPlInW, 3 * kD, nullptr, 0, kD, f);
-        matrix(p + kPlOutW, kD, nullptr, 0, kD, f + lay.out_proj());
-        matrix(p + kPlW1, dim_ff, nullptr, 0, kD, f + lay.w1());
-        matrix(p + pl_w2(dim_ff), kD, nullptr, 0, dim_ff, f + lay.w2());
+        unsigned char *f = out + (size_t)l * lay.layer_frags() * kFrag;
+        launch_pack_matrix(pack, lay.chunk, s, f, p + kPlInW, 3 * kD, kD, kD, 1);
+        launch_pack_matrix(pack, lay.chunk, s, f + lay.out_proj() * kFrag, p + kPlOutW, kD, kD, kD, 1);
+        launch_pack_matrix(pack, lay.chunk, s, f + lay.w1() * kFrag, p + kPlW1, dim_ff, kD, kD, 1);
+        launch_pack_matrix(pack, lay.chunk, s, f + lay.w2() * kFrag, p + pl_w2(dim_ff), kD, dim_ff, dim_ff, 1);
     }
     const float *t = plain_f32 + kPlainLayer0 + (size_t)n_layers * pl_layer(dim_ff);
-    matrix(t + kPlFc1W, kFc1, nullptr, 0, kFlat, lay.fc1());
-    matrix(t + kPlFc2W, kFc2, nullptr, 0, kFc1, lay.fc2());
-    matrix(t + kPlActW, 4, t + kPlCriW, 1, kD, lay.heads());
+    launch_pack_matrix(pack, lay.chunk, s, out + lay.fc1() * kFrag, t + kPlFc1W, kFc1, kFlat, kFlat, 1);
+    launch_pack_matrix(pack, lay.chunk, s, out + lay.fc2() * kFrag, t + kPlFc2W, kFc2, kFc1, kFc1, 1);
+    launch_pack_matrix(pack, lay.chunk, s, out + lay.heads() * kFrag, t + kPlActW, 4, kD, kD, 1, t + kPlCriW, 1);      // actor over critic
     const int count = lay.n_params();
     hipLaunchKernelGGL(tpolicy_pack_params_kernel, dim3(blocks_for((size_t)count, 256)), dim3(256), 0, s, plain_f32, dim_ff, n_layers, count,
                        reinterpret_cast<float *>(out + lay.params()));
@@ -498,9 +490,7 @@ int g2048_tpolicy_forward(const void *boards, const void *packed, float *probs_o
     if (!boards || !packed || !probs_out) return fail(G2048_ERR_ARG, "g2048_tpolicy_forward: null pointer");
     if (!aligned(boards, 16) || !aligned(packed, 16) || !aligned(probs_out, 16) || !aligned(value_out_or_null, 4))
         return fail(G2048_ERR_ARG, "g2048_tpolicy_forward: misaligned pointer (boards, packed weights, probs: 16 bytes; value: 4)");
-    if (!good_precision((int)opts)) return fail(G2048_ERR_ARG, "g2048_tpolicy_forward: unknown opts (precision)");
-    if (!good_encoder_shape(dim_ff, n_layers))
-        return fail(G2048_ERR_ARG, "g2048_tpolicy_forward: dim_ff must be a multiple of 32 (32 .. 65536) and n_layers 1 .. 64");
+    if (const int rc = check_encoder_net("g2048_tpolicy_forward", (int)opts, "opts (precision)", dim_ff, n_layers)) return rc;
     const size_t blocks = (n + 15) / 16;
     if (blocks > 0x7fffffffu) return fail(G2048_ERR_ARG, "g2048_tpolicy_forward: n too large for one launch");
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -528,8 +518,7 @@ int g2048_play_tpolicy_games(void *boards_inout, uint32_t *score_inout, const vo
         return fail(G2048_ERR_ARG, "g2048_play_tpolicy_games: unknown opts (precision | mode << 4)");
     if (mode != G2048_PLAY_POLICY_MASKED && mode != G2048_PLAY_POLICY_UNMASKED && mode != G2048_PLAY_POLICY_GREEDY)
         return fail(G2048_ERR_ARG, "g2048_play_tpolicy_games: unknown mode");
-    if (!good_encoder_shape(dim_ff, n_layers))
-        return fail(G2048_ERR_ARG, "g2048_play_tpolicy_games: dim_ff must be a multiple of 32 (32 .. 65536) and n_layers 1 .. 64");
+    if (const int rc = check_encoder_net("g2048_play_tpolicy_games", (int)precision, "opts (precision | mode << 4)", dim_ff, n_layers)) return rc;
     const bool bf16 = precision == G2048_POLICY_BF16;
     // auto: as many blocks as the chip holds at once (every later one would only find the queue empty)
     const size_t cap = max_blocks ? (size_t)max_blocks : (size_t)device_cus() * with_bool(bf16, [](auto BF16) {

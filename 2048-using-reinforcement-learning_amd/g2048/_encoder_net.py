@@ -1,0 +1,223 @@
+"""What the networks built around an nn.TransformerEncoder (tpolicy.py, qnet.py) share on the host: recognising the module by
+structure, the plain parameter layout of an encoder layer, flatten / unflatten over a network's plain layout, the pieces of the
+float64 yardsticks, and the device-side wrapper (constructor, refresh(), boards check, output buffers). A refusal is a ValueError
+whose text starts with the network's display name.
+"""
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from . import _lib as L
+from . import ops
+
+
+def _refuse(name, msg):
+    raise ValueError(name + ": " + msg)
+
+
+def find_encoder(name, module):
+    """The one nn.TransformerEncoder of an eval-mode module (no final norm, at least one layer)."""
+    if not isinstance(module, nn.Module):
+        _refuse(name, "expected a torch.nn.Module, got %s" % type(module).__name__)
+    if any(m.training for m in module.modules()):
+        _refuse(name, "%s is in training mode; call .eval() first (inference only)" % type(module).__name__)
+    encoders = [m for m in module.modules() if isinstance(m, nn.TransformerEncoder)]
+    if len(encoders) != 1:
+        _refuse(name, "expected exactly one nn.TransformerEncoder, found %d" % len(encoders))
+    enc = encoders[0]
+    if enc.norm is not None:
+        _refuse(name, "the encoder has a final norm (encoder.norm), which the reference's model does not")
+    if len(enc.layers) < 1:
+        _refuse(name, "the encoder has no layers")
+    return enc
+
+
+def claim_by_shape(name, module, enc, out, linears, convs=None, check_conv=None):
+    """Sets out.<role> to the module's Linears outside the encoder, told apart by (in, out) features: linears = {shape: role}.
+    convs: the same for its Conv2ds by (in, out) channels, each passed to check_conv(m, role, what) when it is met."""
+    inside = set(id(m) for m in enc.modules())
+    found = {}
+    for m in module.modules():
+        if id(m) in inside:
+            continue
+        if convs is not None and isinstance(m, nn.Conv2d):
+            what = "Conv2d %d->%d" % (m.in_channels, m.out_channels)
+            role = convs.get((m.in_channels, m.out_channels))
+            if role is None:
+                _refuse(name, "unexpected %s" % what)
+            check_conv(m, role, what)
+            if role in found:
+                _refuse(name, "duplicate %s" % what)
+        elif isinstance(m, nn.Linear):
+            what = "Linear %d->%d" % (m.in_features, m.out_features)
+            role = linears.get((m.in_features, m.out_features))
+            if role is None:
+                _refuse(name, "unexpected %s outside the encoder" % what)
+            if role in found:
+                _refuse(name, "duplicate %s (%s)" % (what, role))
+            if m.bias is None:
+                _refuse(name, "the %s %s has a missing bias" % (role, what))
+        else:
+            continue
+        found[role] = m
+    for kind, roles in (("Conv2d", convs or {}), ("Linear", linears)):
+        for (i, o), role in roles.items():
+            if role not in found:
+                _refuse(name, "missing %s %d->%d (%s)" % (kind, i, o, role))
+    for role, m in found.items():
+        setattr(out, role, m)
+
+
+def _check_layer(name, i, lay, dim_ff, d_model, nhead, batch_first):
+    where = "encoder layer %d" % i
+    if not isinstance(lay, nn.TransformerEncoderLayer):
+        _refuse(name, "%s is a %s, not an nn.TransformerEncoderLayer" % (where, type(lay).__name__))
+    if lay.norm_first:
+        _refuse(name, "%s has norm_first=True (only post-norm layers are supported)" % where)
+    act = lay.activation
+    if not (act is F.relu or act is torch.relu or isinstance(act, nn.ReLU)):
+        _refuse(name, "%s has an activation other than ReLU" % where)
+    att = lay.self_attn
+    if batch_first and not att.batch_first:
+        _refuse(name, "%s has batch_first=False" % where)
+    if att.embed_dim != d_model:
+        _refuse(name, "%s has d_model %d, expected %d" % (where, att.embed_dim, d_model))
+    if nhead is not None and att.num_heads != nhead:
+        _refuse(name, "%s has nhead %d, expected %d" % (where, att.num_heads, nhead))
+    if att.in_proj_weight is None or att.bias_k is not None or att.add_zero_attn:
+        _refuse(name, "%s has an attention variant other than the plain packed q/k/v projection" % where)
+    if lay.linear1.out_features % 32 != 0:
+        _refuse(name, "%s has dim_ff %d, not a multiple of 32" % (where, lay.linear1.out_features))
+    if lay.linear1.out_features != dim_ff:
+        _refuse(name, "%s has dim_ff %d, layer 0 has %d" % (where, lay.linear1.out_features, dim_ff))
+    if att.in_proj_bias is None or att.out_proj.bias is None or lay.linear1.bias is None or lay.linear2.bias is None:
+        _refuse(name, "%s has a projection with a missing bias" % where)
+    for norm in (lay.norm1, lay.norm2):
+        if not isinstance(norm, nn.LayerNorm) or norm.weight is None or norm.bias is None:
+            _refuse(name, "%s needs LayerNorms with weight and bias" % where)
+
+
+def checked_layers(name, enc, d_model, nhead=None, batch_first=False):
+    """(layers, dim_ff) of the encoder: post-norm ReLU layers of d_model, all of layer 0's dim_feedforward (a multiple of 32).
+    nhead / batch_first: constraints only a network whose tokens attend to each other has."""
+    layers = list(enc.layers)
+    first = layers[0]
+    dim_ff = first.linear1.out_features if isinstance(first, nn.TransformerEncoderLayer) else 0
+    for i, lay in enumerate(layers):
+        _check_layer(name, i, lay, dim_ff, d_model, nhead, batch_first)
+    return layers, dim_ff
+
+
+def layer_tensors(layers):
+    """The encoder layers' parameters in the plain layout's order: state-dict order, then the two LayerNorm eps as Python floats."""
+    seq = []
+    for lay in layers:
+        a = lay.self_attn
+        seq += [a.in_proj_weight, a.in_proj_bias, a.out_proj.weight, a.out_proj.bias, lay.linear1.weight, lay.linear1.bias,
+                lay.linear2.weight, lay.linear2.bias, lay.norm1.weight, lay.norm1.bias, lay.norm2.weight, lay.norm2.bias,
+                float(lay.norm1.eps), float(lay.norm2.eps)]
+    return seq
+
+
+@torch.no_grad()
+def flatten(p, out=None):
+    """The plain float32 buffer of a Parsed module (on the module's device; written in place when `out` is given). A Parsed
+    record has its network's display name as `name` and its plain layout as plain_tensors()."""
+    seq = p.plain_tensors()
+    total = sum(t.numel() if isinstance(t, torch.Tensor) else 1 for t in seq)
+    if out is None:
+        out = torch.empty(total, dtype=torch.float32, device=p.embedding.weight.device)
+    if out.numel() != total:
+        raise ValueError("%s: the plain buffer holds %d floats, the module has %d" % (p.name, out.numel(), total))
+    o = 0
+    for t in seq:
+        if isinstance(t, torch.Tensor):
+            out[o:o + t.numel()].copy_(t.reshape(-1))
+            o += t.numel()
+        else:
+            out[o:o + 1].fill_(t)
+            o += 1
+    return out
+
+
+@torch.no_grad()
+def unflatten(p, plain):
+    """Loads a plain buffer back into the Parsed module's parameters (the inverse of flatten; eps entries are skipped)."""
+    o = 0
+    for t in p.plain_tensors():
+        if isinstance(t, torch.Tensor):
+            t.copy_(plain[o:o + t.numel()].reshape(t.shape))
+            o += t.numel()
+        else:
+            o += 1
+    return p
+
+
+def weight_caster(dtype, round_weights=None):
+    """w(parameter) of a forward_reference: detached, through round_weights if given (e.g. a bf16 round trip), then in dtype."""
+    def w(t):
+        t = t.detach()
+        if round_weights is not None:
+            t = round_weights(t)
+        return t.to(dtype)
+    return w
+
+
+def post_norm_tail(lay, x, attended, w):
+    """The rest of a post-norm encoder layer after the attention itself: norm1(x + out_proj(attended)), then the feed-forward
+    pair and norm2, with the weights through w."""
+    a, d = lay.self_attn, (x.shape[-1],)
+    x = F.layer_norm(x + attended @ w(a.out_proj.weight).T + w(a.out_proj.bias), d, w(lay.norm1.weight), w(lay.norm1.bias), lay.norm1.eps)
+    h = torch.relu(x @ w(lay.linear1.weight).T + w(lay.linear1.bias))
+    return F.layer_norm(x + h @ w(lay.linear2.weight).T + w(lay.linear2.bias), d, w(lay.norm2.weight), w(lay.norm2.bias), lay.norm2.eps)
+
+
+class OutputCache:
+    """The output buffers a device network owns: one set per (factory, N, stream), overwritten by the next call with the same N
+    on the same stream, so that after the first call per (N, stream) a call neither allocates nor synchronises."""
+
+    def __init__(self, name, device):
+        self.name, self.device, self._bufs = name, device, {}
+
+    def rows(self, boards):
+        """N of uint8 (N,16) boards on the network's device."""
+        L.require_device_tensor(boards, torch.uint8, (16,), "boards")
+        if boards.device != self.device:
+            raise ValueError("%s: boards on %s, weights on %s" % (self.name, boards.device, self.device))
+        return boards.shape[0]
+
+    def get(self, n, make):
+        """make(n, device)'s buffers for n rows on the current stream."""
+        key = (make, n, torch.cuda.current_stream(self.device).cuda_stream)
+        bufs = self._bufs.get(key)
+        if bufs is None:
+            bufs = self._bufs[key] = make(n, self.device)
+        return bufs
+
+
+class PackedNet:
+    """Base of DeviceTransformerPolicy and DeviceQNetwork: the module parsed, its parameters flattened into `plain` and packed
+    into `packed` on its device, refresh() to redo both IN PLACE on the current stream, and the output buffers. A subclass gives
+    name and, as staticmethods, parse and ops' plain_floats, packed_bytes and pack of its network."""
+
+    name = parse = plain_floats = packed_bytes = pack = None
+
+    def __init__(self, model, precision="f32"):
+        if precision not in ops.POLICY_PRECISIONS:
+            raise ValueError("%s: precision must be 'f32' or 'bf16'" % self.name)
+        self.model, self.precision = model, precision
+        self.parsed = self.parse(model)
+        self.dim_ff, self.n_layers = self.parsed.dim_ff, len(self.parsed.layers)
+        self.device = self.parsed.embedding.weight.device
+        if self.device.type != "cuda":
+            raise RuntimeError("g2048: %s needs the module on a ROCm device (got %s); there is no CPU path" % (self.name, self.device))
+        self.plain = torch.empty(self.plain_floats(self.dim_ff, self.n_layers), dtype=torch.float32, device=self.device)
+        self.packed = torch.empty(self.packed_bytes(precision, self.dim_ff, self.n_layers), dtype=torch.uint8, device=self.device)
+        self._out = OutputCache(self.name, self.device)
+        self.refresh()
+
+    def refresh(self):
+        if any(m.training for m in self.model.modules()):
+            raise ValueError("%s.refresh: %s is in training mode; call .eval() first" % (self.name, type(self.model).__name__))
+        flatten(self.parsed, self.plain)
+        self.pack(self.plain, self.dim_ff, self.n_layers, self.precision, out=self.packed)

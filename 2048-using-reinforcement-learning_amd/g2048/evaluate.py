@@ -131,10 +131,7 @@ def evaluate_beam_search(num_games=4096, beam_width=20, search_depth=30, seed=0x
     torch.cuda.synchronize(dev)
     elapsed = time.perf_counter() - t_start
 
-    # one int64 row per game: score, moves, valid, invalid, alive, expanded, 8 milestone moves, 16 tiles
-    table = torch.cat([env.scores.to(torch.int64)[:, None], moves.to(torch.int64)[:, None], valid_cnt.to(torch.int64)[:, None],
-                       invalid_cnt.to(torch.int64)[:, None], alive.to(torch.int64)[:, None], expanded_sum[:, None],
-                       ms_move.to(torch.int64), ops.unpack(env.boards).to(torch.int64).reshape(n, 16)], dim=1)
+    table = _game_table(env.scores, moves, valid_cnt, invalid_cnt, alive, expanded_sum, ms_move, env.boards)
     if _table_only:
         return table.cpu().numpy()
     results = results_from_table(table.cpu().numpy(), elapsed, beam_width, search_depth, seed, max_moves)
@@ -143,7 +140,35 @@ def evaluate_beam_search(num_games=4096, beam_width=20, search_depth=30, seed=0x
     return results
 
 
+def _game_table(scores, moves, valid, invalid, alive, expanded, milestone_move, boards):
+    """One int64 row per game: score, moves, valid, invalid, alive, expanded (None: 0), 8 milestone moves, 16 tiles."""
+    n = boards.shape[0]
+    if expanded is None:
+        expanded = torch.zeros(n, dtype=torch.int64, device=boards.device)
+    return torch.cat([scores.to(torch.int64)[:, None], moves.to(torch.int64)[:, None], valid.to(torch.int64)[:, None],
+                      invalid.to(torch.int64)[:, None], alive.to(torch.int64)[:, None], expanded[:, None],
+                      milestone_move.to(torch.int64), ops.unpack(boards).to(torch.int64).reshape(n, 16)], dim=1)
+
+
 POLICY_MODES = ("masked", "unmasked", "greedy")
+
+
+def _evaluate_net(dev, fused, play_fused, play_stepwise, params, game_id_base, histories):
+    """evaluate_policy and evaluate_qnet from their argument checks on: play_fused(env, want_actions) / play_stepwise(env) play
+    the games of `env` to their ends and return the per-game dict of ops.play_policy_games; params is the "parameters" entry."""
+    n, seed = params["num_games"], params["seed"]
+    t_start = time.perf_counter()
+    env = VecGame2048(n, device=dev, seed=seed, id_base=game_id_base)
+    boards0 = env.boards.clone() if histories is not None else None
+    res = play_fused(env, histories is not None) if fused else play_stepwise(env)
+    torch.cuda.synchronize(dev)
+    elapsed = time.perf_counter() - t_start
+    table = _game_table(env.scores, res["moves"], res["valid_moves"], res["invalid_moves"], res["alive"], None, res["milestone_move"],
+                        env.boards)
+    results = policy_results_from_table(table.cpu().numpy(), res["reward_sum"].cpu().numpy(), elapsed, params)
+    if histories is not None:
+        results["games"] = game_histories(results, histories, boards0, res["actions"], res["moves"], seed, game_id_base)
+    return results
 
 
 def _is_transformer(policy):
@@ -186,32 +211,19 @@ def evaluate_policy(policy, num_games=4096, max_moves=2000, mode="masked", seed=
     n, max_moves = int(num_games), int(max_moves)
     precision = policy.precision
     blob = policy.packed if transformer else policy.actor.blob(1)
-    t_start = time.perf_counter()
-    env = VecGame2048(n, device=dev, seed=seed, id_base=game_id_base)
-    boards0 = env.boards.clone() if histories is not None else None
-    if fused and transformer:
-        res = ops.play_tpolicy_games(env.boards, env.scores, blob, policy.dim_ff, policy.n_layers, precision, max_moves, mode, seed,
-                                     game_id_base, want_rewards=True, want_actions=histories is not None, max_blocks=max_waves)
-    elif fused:
-        res = ops.play_policy_games(env.boards, env.scores, blob, precision, max_moves, mode, seed, game_id_base,
-                                    want_rewards=True, want_actions=histories is not None, max_waves=max_waves)
-    elif transformer:
-        dim_ff, n_layers = policy.dim_ff, policy.n_layers
-        res = _play_policy_stepwise(env, blob, precision, max_moves, mode, seed, game_id_base, forward=lambda boards, probs:
-                                    ops.tpolicy_forward(boards, blob, dim_ff, n_layers, precision, probs=probs, want_value=False))
+    if transformer:
+        net, play, units = (policy.dim_ff, policy.n_layers), ops.play_tpolicy_games, "max_blocks"
+
+        def forward(boards, probs):
+            ops.tpolicy_forward(boards, blob, *net, precision, probs=probs, want_value=False)
     else:
-        res = _play_policy_stepwise(env, blob, precision, max_moves, mode, seed, game_id_base)
-    torch.cuda.synchronize(dev)
-    elapsed = time.perf_counter() - t_start
-    table = torch.cat([env.scores.to(torch.int64)[:, None], res["moves"].to(torch.int64)[:, None],
-                       res["valid_moves"].to(torch.int64)[:, None], res["invalid_moves"].to(torch.int64)[:, None],
-                       res["alive"].to(torch.int64)[:, None], torch.zeros(n, 1, dtype=torch.int64, device=dev),
-                       res["milestone_move"].to(torch.int64), ops.unpack(env.boards).to(torch.int64).reshape(n, 16)], dim=1)
-    params = {"mode": mode, "precision": precision, "max_moves": max_moves, "num_games": n, "seed": seed}
-    results = policy_results_from_table(table.cpu().numpy(), res["reward_sum"].cpu().numpy(), elapsed, params)
-    if histories is not None:
-        results["games"] = game_histories(results, histories, boards0, res["actions"], res["moves"], seed, game_id_base)
-    return results
+        net, play, units, forward = (), ops.play_policy_games, "max_waves", None
+    return _evaluate_net(
+        dev, fused,
+        lambda env, want_actions: play(env.boards, env.scores, blob, *net, precision, max_moves, mode, seed, game_id_base,
+                                       want_rewards=True, want_actions=want_actions, **{units: max_waves}),
+        lambda env: _play_policy_stepwise(env, blob, precision, max_moves, mode, seed, game_id_base, forward=forward),
+        {"mode": mode, "precision": precision, "max_moves": max_moves, "num_games": n, "seed": seed}, game_id_base, histories)
 
 
 def evaluate_qnet(qnet, num_games=4096, max_moves=2000, epsilon=0.0, seed=0x2048, game_id_base=0, device=None, fused=True,
@@ -243,26 +255,14 @@ def evaluate_qnet(qnet, num_games=4096, max_moves=2000, epsilon=0.0, seed=0x2048
         raise ValueError("g2048.evaluate_qnet: the network lives on %s, not %s" % (dev, device))
     n, max_moves = int(num_games), int(max_moves)
     precision, blob, dim_ff, n_layers = qnet.precision, qnet.packed, qnet.dim_ff, qnet.n_layers
-    t_start = time.perf_counter()
-    env = VecGame2048(n, device=dev, seed=seed, id_base=game_id_base)
-    boards0 = env.boards.clone() if histories is not None else None
-    if fused:
-        res = ops.play_qnet_games(env.boards, env.scores, blob, dim_ff, n_layers, precision, max_moves, epsilon, seed, game_id_base,
-                                  want_rewards=True, want_actions=histories is not None, max_waves=max_waves)
-    else:
-        res = _play_policy_stepwise(env, blob, precision, max_moves, None, seed, game_id_base,
-                                    act=qnet_stepwise_act(blob, dim_ff, n_layers, precision, n, dev, epsilon, seed, game_id_base))
-    torch.cuda.synchronize(dev)
-    elapsed = time.perf_counter() - t_start
-    table = torch.cat([env.scores.to(torch.int64)[:, None], res["moves"].to(torch.int64)[:, None],
-                       res["valid_moves"].to(torch.int64)[:, None], res["invalid_moves"].to(torch.int64)[:, None],
-                       res["alive"].to(torch.int64)[:, None], torch.zeros(n, 1, dtype=torch.int64, device=dev),
-                       res["milestone_move"].to(torch.int64), ops.unpack(env.boards).to(torch.int64).reshape(n, 16)], dim=1)
-    params = {"epsilon": epsilon, "precision": precision, "max_moves": max_moves, "num_games": n, "seed": seed}
-    results = policy_results_from_table(table.cpu().numpy(), res["reward_sum"].cpu().numpy(), elapsed, params)
-    if histories is not None:
-        results["games"] = game_histories(results, histories, boards0, res["actions"], res["moves"], seed, game_id_base)
-    return results
+    return _evaluate_net(
+        dev, fused,
+        lambda env, want_actions: ops.play_qnet_games(env.boards, env.scores, blob, dim_ff, n_layers, precision, max_moves, epsilon,
+                                                      seed, game_id_base, want_rewards=True, want_actions=want_actions,
+                                                      max_waves=max_waves),
+        lambda env: _play_policy_stepwise(env, blob, precision, max_moves, None, seed, game_id_base,
+                                          act=qnet_stepwise_act(blob, dim_ff, n_layers, precision, n, dev, epsilon, seed, game_id_base)),
+        {"epsilon": epsilon, "precision": precision, "max_moves": max_moves, "num_games": n, "seed": seed}, game_id_base, histories)
 
 
 def qnet_stepwise_act(blob, dim_ff, n_layers, precision, n, device, epsilon, seed, game_id_base):

@@ -34,6 +34,17 @@ def _require_scores(scores):
     L.require_device_tensor(scores, torch.uint32 if scores.dtype == torch.uint32 else torch.int32, None, "scores")
 
 
+def _output(t, n, dtype, tail, name, device):
+    """The output tensor `name` of n rows: allocated when t is None, else required to be a device tensor of `dtype` and, unless
+    `tail` is None, of shape (n, *tail)."""
+    if t is None:
+        return torch.empty((n,) + tuple(tail or ()), dtype=dtype, device=device)
+    L.require_device_tensor(t, dtype, tail, name)
+    if tail is not None and t.shape[0] != n:
+        raise ValueError("g2048: %s must have n %s" % (name, "rows" if tail else "entries"))
+    return t
+
+
 def step(boards, actions, scores, seed, step_index, id_base=0, out=None, reward=None, flags=None,
          reward_f64=False, auto_reset=False, tune=0, keyblock=None, noop_actions=False):
     """Game2048Env.step for every board (reference environment/game_2048.py:170-210).
@@ -266,9 +277,7 @@ def valid_moves(boards, agent_semantics=False, out=None):
     """4-bit masks (bit a = action a valid). Env semantics (game_2048.py:69-95) or the beam agent's own
     (_check_valid_moves, beam_search_agent.py:183-192 -- differs on DOWN)."""
     L.require_device_tensor(boards, torch.uint8, (16,), "boards")
-    if out is None:
-        out = torch.empty(boards.shape[0], dtype=torch.uint8, device=boards.device)
-    L.require_device_tensor(out, torch.uint8, None, "out")
+    out = _output(out, boards.shape[0], torch.uint8, None, "out", boards.device)
     L.call(boards.device, L.lib().g2048_valid_moves, boards.data_ptr(), out.data_ptr(), boards.shape[0],
                                       L.VALID_AGENT if agent_semantics else L.VALID_ENV, L.stream_ptr(boards.device))
     return out
@@ -340,12 +349,8 @@ def sample_actions(probs, mask4=None, seed=0x2048, step_index=0, id_base=0, acti
     if mask4 is not None:
         L.require_device_tensor(mask4, torch.uint8, None, "mask4")
     dev = probs.device
-    if actions is None:
-        actions = torch.empty(n, dtype=torch.uint8, device=dev)
-    if prob is None:
-        prob = torch.empty(n, dtype=torch.float32, device=dev)
-    L.require_device_tensor(actions, torch.uint8, None, "actions")
-    L.require_device_tensor(prob, torch.float32, None, "prob")
+    actions = _output(actions, n, torch.uint8, None, "actions", dev)
+    prob = _output(prob, n, torch.float32, None, "prob", dev)
     mp = mask4.data_ptr() if mask4 is not None else None
     if keyblock is not None:
         L.call(dev, L.lib().g2048_sample_actions_dyn, probs.data_ptr(), mp, actions.data_ptr(), prob.data_ptr(),
@@ -413,6 +418,17 @@ def rollout_step(boards, probs, scores, seed, step_index, id_base=0, *, mask=Non
 POLICY_PRECISIONS = {"f32": L.POLICY_F32, "bf16": L.POLICY_BF16}
 
 
+def _pack(fn, plain, args, nb, out):
+    """fn(plain, *args, out, stream) into `out`, a uint8 tensor of nb bytes (allocated when None)."""
+    if out is None:
+        out = torch.empty(nb, dtype=torch.uint8, device=plain.device)
+    L.require_device_tensor(out, torch.uint8, None, "out")
+    if out.numel() != nb:
+        raise ValueError("g2048: out must hold %d bytes" % nb)
+    L.call(plain.device, fn, plain.data_ptr(), *args, out.data_ptr(), L.stream_ptr(plain.device))
+    return out
+
+
 def policy_packed_bytes(precision="f32", n_out=4):
     """Bytes of one packed network (g2048_policy_packed_bytes)."""
     nb = L.lib().g2048_policy_packed_bytes(POLICY_PRECISIONS[precision], int(n_out))
@@ -428,15 +444,7 @@ def policy_pack(plain, n_out, precision="f32", out=None):
     L.require_device_tensor(plain, torch.float32, None, "plain")
     if plain.dim() != 1 or plain.numel() != 45504 + 65 * int(n_out):
         raise ValueError("g2048: plain must be a flat float32 tensor of 45,504 + 65 * n_out parameters")
-    nb = policy_packed_bytes(precision, n_out)
-    if out is None:
-        out = torch.empty(nb, dtype=torch.uint8, device=plain.device)
-    L.require_device_tensor(out, torch.uint8, None, "out")
-    if out.numel() != nb:
-        raise ValueError("g2048: out must hold %d bytes" % nb)
-    L.call(plain.device, L.lib().g2048_policy_pack, plain.data_ptr(), int(n_out), POLICY_PRECISIONS[precision], out.data_ptr(),
-           L.stream_ptr(plain.device))
-    return out
+    return _pack(L.lib().g2048_policy_pack, plain, (int(n_out), POLICY_PRECISIONS[precision]), policy_packed_bytes(precision, n_out), out)
 
 
 def policy_forward(boards, actor_packed, critic_packed=None, precision="f32", probs=None, value=None):
@@ -444,17 +452,9 @@ def policy_forward(boards, actor_packed, critic_packed=None, precision="f32", pr
     (n,4), or (probs, value float32 (n,1)) when critic_packed is given."""
     L.require_device_tensor(boards, torch.uint8, (16,), "boards")
     n, dev = boards.shape[0], boards.device
-    if probs is None:
-        probs = torch.empty((n, 4), dtype=torch.float32, device=dev)
-    L.require_device_tensor(probs, torch.float32, (4,), "probs")
-    if probs.shape[0] != n:
-        raise ValueError("g2048: probs must have n rows")
-    if critic_packed is not None and value is None:
-        value = torch.empty((n, 1), dtype=torch.float32, device=dev)
-    if value is not None:
-        L.require_device_tensor(value, torch.float32, (1,), "value")
-        if value.shape[0] != n:
-            raise ValueError("g2048: value must have n rows")
+    probs = _output(probs, n, torch.float32, (4,), "probs", dev)
+    if critic_packed is not None or value is not None:
+        value = _output(value, n, torch.float32, (1,), "value", dev)
     L.call(dev, L.lib().g2048_policy_forward, boards.data_ptr(), actor_packed.data_ptr(),
            critic_packed.data_ptr() if critic_packed is not None else None, probs.data_ptr(),
            value.data_ptr() if value is not None else None, n, POLICY_PRECISIONS[precision], L.stream_ptr(dev))
@@ -466,89 +466,78 @@ def tpolicy_plain_floats(dim_ff, n_layers):
     return 128 + int(n_layers) * (16962 + 129 * int(dim_ff)) + 139781
 
 
-def tpolicy_packed_bytes(precision="f32", dim_ff=2048, n_layers=2):
-    """Bytes of the packed transformer policy (g2048_tpolicy_packed_bytes)."""
+def qnet_plain_floats(dim_ff, n_layers):
+    """Floats of the plain parameter buffer g2048_qnet_pack reads (include/g2048.h)."""
+    return 140132 + int(n_layers) * (66690 + 257 * int(dim_ff))
+
+
+# what differs between the two encoder networks' blobs: the plain-float formula and the library's two symbols
+_NETS = {"tpolicy": (tpolicy_plain_floats, "g2048_tpolicy_packed_bytes", "g2048_tpolicy_pack"),
+         "qnet": (qnet_plain_floats, "g2048_qnet_packed_bytes", "g2048_qnet_pack")}
+
+
+def _net_packed_bytes(kind, precision, dim_ff, n_layers):
     if precision not in POLICY_PRECISIONS:
         raise ValueError("g2048: precision must be 'f32' or 'bf16'")
-    nb = L.lib().g2048_tpolicy_packed_bytes(POLICY_PRECISIONS[precision], int(dim_ff), int(n_layers))
+    nb = getattr(L.lib(), _NETS[kind][1])(POLICY_PRECISIONS[precision], int(dim_ff), int(n_layers))
     if nb == 0:
         raise ValueError("g2048: dim_ff must be a multiple of 32 and n_layers at least 1")
     return nb
+
+
+def _net_pack(kind, plain, dim_ff, n_layers, precision, out):
+    L.require_device_tensor(plain, torch.float32, None, "plain")
+    nb = _net_packed_bytes(kind, precision, dim_ff, n_layers)
+    floats = _NETS[kind][0](dim_ff, n_layers)
+    if plain.dim() != 1 or plain.numel() != floats:
+        raise ValueError("g2048: plain must be a flat float32 tensor of %d parameters" % floats)
+    return _pack(getattr(L.lib(), _NETS[kind][2]), plain, (int(dim_ff), int(n_layers), POLICY_PRECISIONS[precision]), nb, out)
+
+
+def _check_blob(kind, packed, precision, dim_ff, n_layers):
+    """A forward call's packed blob: a uint8 device tensor of the size of (precision, dim_ff, n_layers)."""
+    L.require_device_tensor(packed, torch.uint8, None, "packed")
+    nb = _net_packed_bytes(kind, precision, dim_ff, n_layers)
+    if packed.numel() != nb:
+        raise ValueError("g2048: packed must be a %s blob of %d bytes" % (precision, nb))
+
+
+def tpolicy_packed_bytes(precision="f32", dim_ff=2048, n_layers=2):
+    """Bytes of the packed transformer policy (g2048_tpolicy_packed_bytes)."""
+    return _net_packed_bytes("tpolicy", precision, dim_ff, n_layers)
 
 
 def tpolicy_pack(plain, dim_ff, n_layers, precision="f32", out=None):
     """Pack the transformer policy's plain float32 parameters (state-dict order plus the two LayerNorm eps per layer:
     include/g2048.h) into the blob g2048_tpolicy_forward streams. Writes `out` (uint8, tpolicy_packed_bytes) in place when
     given, on the current stream, without synchronising."""
-    L.require_device_tensor(plain, torch.float32, None, "plain")
-    nb = tpolicy_packed_bytes(precision, dim_ff, n_layers)
-    if plain.dim() != 1 or plain.numel() != tpolicy_plain_floats(dim_ff, n_layers):
-        raise ValueError("g2048: plain must be a flat float32 tensor of %d parameters" % tpolicy_plain_floats(dim_ff, n_layers))
-    if out is None:
-        out = torch.empty(nb, dtype=torch.uint8, device=plain.device)
-    L.require_device_tensor(out, torch.uint8, None, "out")
-    if out.numel() != nb:
-        raise ValueError("g2048: out must hold %d bytes" % nb)
-    L.call(plain.device, L.lib().g2048_tpolicy_pack, plain.data_ptr(), int(dim_ff), int(n_layers), POLICY_PRECISIONS[precision],
-           out.data_ptr(), L.stream_ptr(plain.device))
-    return out
+    return _net_pack("tpolicy", plain, dim_ff, n_layers, precision, out)
 
 
 def tpolicy_forward(boards, packed, dim_ff, n_layers, precision="f32", probs=None, value=None, want_value=True):
     """The transformer policy's forward pass on the packed boards in ONE launch (g2048_tpolicy_forward). Returns (probs
     float32 (n,4), value float32 (n,1)), or probs alone with want_value=False."""
     L.require_device_tensor(boards, torch.uint8, (16,), "boards")
-    L.require_device_tensor(packed, torch.uint8, None, "packed")
-    if packed.numel() != tpolicy_packed_bytes(precision, dim_ff, n_layers):
-        raise ValueError("g2048: packed must be a %s blob of %d bytes" % (precision, tpolicy_packed_bytes(precision, dim_ff, n_layers)))
+    _check_blob("tpolicy", packed, precision, dim_ff, n_layers)
     n, dev = boards.shape[0], boards.device
-    if probs is None:
-        probs = torch.empty((n, 4), dtype=torch.float32, device=dev)
-    L.require_device_tensor(probs, torch.float32, (4,), "probs")
-    if probs.shape[0] != n:
-        raise ValueError("g2048: probs must have n rows")
-    if want_value and value is None:
-        value = torch.empty((n, 1), dtype=torch.float32, device=dev)
-    if value is not None:
-        L.require_device_tensor(value, torch.float32, (1,), "value")
-        if value.shape[0] != n:
-            raise ValueError("g2048: value must have n rows")
+    probs = _output(probs, n, torch.float32, (4,), "probs", dev)
+    if want_value or value is not None:
+        value = _output(value, n, torch.float32, (1,), "value", dev)
     L.call(dev, L.lib().g2048_tpolicy_forward, boards.data_ptr(), packed.data_ptr(), probs.data_ptr(),
            value.data_ptr() if value is not None else None, n, int(dim_ff), int(n_layers), POLICY_PRECISIONS[precision], L.stream_ptr(dev))
     return probs if value is None else (probs, value)
 
 
-def qnet_plain_floats(dim_ff, n_layers):
-    """Floats of the plain parameter buffer g2048_qnet_pack reads (include/g2048.h)."""
-    return 140132 + int(n_layers) * (66690 + 257 * int(dim_ff))
-
-
 def qnet_packed_bytes(precision="f32", dim_ff=2048, n_layers=2):
     """Bytes of the packed hybrid Q-network (g2048_qnet_packed_bytes)."""
-    if precision not in POLICY_PRECISIONS:
-        raise ValueError("g2048: precision must be 'f32' or 'bf16'")
-    nb = L.lib().g2048_qnet_packed_bytes(POLICY_PRECISIONS[precision], int(dim_ff), int(n_layers))
-    if nb == 0:
-        raise ValueError("g2048: dim_ff must be a multiple of 32 and n_layers at least 1")
-    return nb
+    return _net_packed_bytes("qnet", precision, dim_ff, n_layers)
 
 
 def qnet_pack(plain, dim_ff, n_layers, precision="f32", out=None):
     """Pack the hybrid Q-network's plain float32 parameters (state-dict order plus the two LayerNorm eps per layer:
     include/g2048.h) into the blob g2048_qnet_forward streams. Writes `out` (uint8, qnet_packed_bytes) in place when given, on
     the current stream, without synchronising."""
-    L.require_device_tensor(plain, torch.float32, None, "plain")
-    nb = qnet_packed_bytes(precision, dim_ff, n_layers)
-    if plain.dim() != 1 or plain.numel() != qnet_plain_floats(dim_ff, n_layers):
-        raise ValueError("g2048: plain must be a flat float32 tensor of %d parameters" % qnet_plain_floats(dim_ff, n_layers))
-    if out is None:
-        out = torch.empty(nb, dtype=torch.uint8, device=plain.device)
-    L.require_device_tensor(out, torch.uint8, None, "out")
-    if out.numel() != nb:
-        raise ValueError("g2048: out must hold %d bytes" % nb)
-    L.call(plain.device, L.lib().g2048_qnet_pack, plain.data_ptr(), int(dim_ff), int(n_layers), POLICY_PRECISIONS[precision],
-           out.data_ptr(), L.stream_ptr(plain.device))
-    return out
+    return _net_pack("qnet", plain, dim_ff, n_layers, precision, out)
 
 
 def qnet_forward(boards, packed, dim_ff, n_layers, precision="f32", q=None, actions=None, want_actions=False):
@@ -556,21 +545,11 @@ def qnet_forward(boards, packed, dim_ff, n_layers, precision="f32", q=None, acti
     uint8 (n,), q) when `actions` is given or want_actions is set: the exploit action of DQNAgent.select_action (the argmax of q
     over the env's valid moves, ties to the lowest index, 0 for a board with no valid move)."""
     L.require_device_tensor(boards, torch.uint8, (16,), "boards")
-    L.require_device_tensor(packed, torch.uint8, None, "packed")
-    if packed.numel() != qnet_packed_bytes(precision, dim_ff, n_layers):
-        raise ValueError("g2048: packed must be a %s blob of %d bytes" % (precision, qnet_packed_bytes(precision, dim_ff, n_layers)))
+    _check_blob("qnet", packed, precision, dim_ff, n_layers)
     n, dev = boards.shape[0], boards.device
-    if q is None:
-        q = torch.empty((n, 4), dtype=torch.float32, device=dev)
-    L.require_device_tensor(q, torch.float32, (4,), "q")
-    if q.shape[0] != n:
-        raise ValueError("g2048: q must have n rows")
-    if want_actions and actions is None:
-        actions = torch.empty(n, dtype=torch.uint8, device=dev)
-    if actions is not None:
-        L.require_device_tensor(actions, torch.uint8, (), "actions")
-        if actions.shape[0] != n:
-            raise ValueError("g2048: actions must have n entries")
+    q = _output(q, n, torch.float32, (4,), "q", dev)
+    if want_actions or actions is not None:
+        actions = _output(actions, n, torch.uint8, (), "actions", dev)
     L.call(dev, L.lib().g2048_qnet_forward, boards.data_ptr(), packed.data_ptr(), q.data_ptr(),
            actions.data_ptr() if actions is not None else None, n, int(dim_ff), int(n_layers), POLICY_PRECISIONS[precision],
            L.stream_ptr(dev))
@@ -590,14 +569,8 @@ def qnet_select_actions(q, boards, epsilon, seed=0x2048, step_index=0, id_base=0
     n, dev = boards.shape[0], boards.device
     if q.shape[0] != n:
         raise ValueError("g2048: q must have n rows")
-    if actions is None:
-        actions = torch.empty(n, dtype=torch.uint8, device=dev)
-    if explored is None:
-        explored = torch.empty(n, dtype=torch.uint8, device=dev)
-    for name, t in (("actions", actions), ("explored", explored)):
-        L.require_device_tensor(t, torch.uint8, (), name)
-        if t.shape[0] != n:
-            raise ValueError("g2048: %s must have n entries" % name)
+    actions = _output(actions, n, torch.uint8, (), "actions", dev)
+    explored = _output(explored, n, torch.uint8, (), "explored", dev)
     L.call(dev, L.lib().g2048_qnet_select_actions, q.data_ptr(), boards.data_ptr(), actions.data_ptr(), explored.data_ptr(), epsilon,
            L.u64(seed), L.u64(step_index), L.u64(id_base), n, L.stream_ptr(dev))
     return actions, explored
@@ -1019,6 +992,25 @@ def _play_net_games(fn, workspace_fn, boards, scores, net_args, out, max_moves, 
     return out
 
 
+def _check_play_opts(precision, mode):
+    if precision not in POLICY_PRECISIONS:
+        raise ValueError("g2048: precision must be 'f32' or 'bf16'")
+    if mode not in PLAY_POLICY_MODES:
+        raise ValueError("g2048: mode must be one of %s" % (tuple(PLAY_POLICY_MODES),))
+
+
+def _check_play_blob(kind, packed, precision, dim_ff, n_layers):
+    nb = _net_packed_bytes(kind, precision, dim_ff, n_layers)        # (the size needs no device: a wrong blob is refused anywhere)
+    if isinstance(packed, torch.Tensor) and packed.numel() != nb:
+        raise ValueError("g2048: packed must be a %s blob of %d bytes (dim_ff %d, %d layers)" % (precision, nb, dim_ff, n_layers))
+
+
+def _require_games(boards, scores, packed, packed_name="packed"):
+    L.require_device_tensor(boards, torch.uint8, (16,), "boards")
+    _require_scores(scores)
+    L.require_device_tensor(packed, torch.uint8, None, packed_name)
+
+
 def play_policy_games(boards, scores, actor_packed, precision="f32", max_moves=2000, mode="masked", seed=0x2048, game_id_base=0,
                       want_rewards=True, want_actions=False, max_waves=0):
     """Every game played to the end by the PPO actor in ONE launch (g2048_play_policy_games; train.py:54-90 for mode="masked",
@@ -1028,13 +1020,8 @@ def play_policy_games(boards, scores, actor_packed, precision="f32", max_moves=2
     (n,8), -1 = never), alive (uint8), with want_rewards "reward_sum" (float64: the env rewards summed in move order) and with
     want_actions "actions" (uint8 (n, max_moves), 0xFF from a game's end on: the input of `replay_games`). max_waves: the
     number of wavefronts, 0 = as many as the chip holds (the games are the same for every value)."""
-    L.require_device_tensor(boards, torch.uint8, (16,), "boards")
-    _require_scores(scores)
-    L.require_device_tensor(actor_packed, torch.uint8, None, "actor_packed")
-    if precision not in POLICY_PRECISIONS:
-        raise ValueError("g2048: precision must be 'f32' or 'bf16'")
-    if mode not in PLAY_POLICY_MODES:
-        raise ValueError("g2048: mode must be one of %s" % (tuple(PLAY_POLICY_MODES),))
+    _require_games(boards, scores, actor_packed, "actor_packed")
+    _check_play_opts(precision, mode)
     if actor_packed.numel() != policy_packed_bytes(precision, 4):
         raise ValueError("g2048: actor_packed must be a %s actor blob of %d bytes" % (precision, policy_packed_bytes(precision, 4)))
     out = _net_game_results(boards, scores, max_moves, max_waves, "max_waves", want_rewards, want_actions)
@@ -1052,16 +1039,9 @@ def play_tpolicy_games(boards, scores, packed, dim_ff, n_layers, precision="f32"
     milestone_move (int32 (n,8), -1 = never), alive (uint8), with want_rewards "reward_sum" (float64) and with want_actions
     "actions" (uint8 (n, max_moves), 0xFF from a game's end on: the input of `replay_games`). max_blocks: the number of
     blocks (16 games in flight each), 0 = as many as the chip holds (the games are the same for every value)."""
-    if precision not in POLICY_PRECISIONS:
-        raise ValueError("g2048: precision must be 'f32' or 'bf16'")
-    if mode not in PLAY_POLICY_MODES:
-        raise ValueError("g2048: mode must be one of %s" % (tuple(PLAY_POLICY_MODES),))
-    nb = tpolicy_packed_bytes(precision, dim_ff, n_layers)          # (the size needs no device: a wrong blob is refused anywhere)
-    if isinstance(packed, torch.Tensor) and packed.numel() != nb:
-        raise ValueError("g2048: packed must be a %s blob of %d bytes (dim_ff %d, %d layers)" % (precision, nb, dim_ff, n_layers))
-    L.require_device_tensor(boards, torch.uint8, (16,), "boards")
-    _require_scores(scores)
-    L.require_device_tensor(packed, torch.uint8, None, "packed")
+    _check_play_opts(precision, mode)
+    _check_play_blob("tpolicy", packed, precision, dim_ff, n_layers)
+    _require_games(boards, scores, packed)
     out = _net_game_results(boards, scores, max_moves, max_blocks, "max_blocks", want_rewards, want_actions)
     opts = POLICY_PRECISIONS[precision] | (PLAY_POLICY_MODES[mode] << L.PLAY_POLICY_MODE_SHIFT)
     return _play_net_games(L.lib().g2048_play_tpolicy_games, L.lib().g2048_play_tpolicy_workspace, boards, scores,
@@ -1079,17 +1059,11 @@ def play_qnet_games(boards, scores, packed, dim_ff, n_layers, precision="f32", m
     and with want_actions "actions" (uint8 (n, max_moves), 0xFF from a game's end on: the input of `replay_games`).
     max_waves: the number of wavefronts (32 games in flight each), 0 = as many as the chip holds (the games are the same for
     every value)."""
-    if precision not in POLICY_PRECISIONS:
-        raise ValueError("g2048: precision must be 'f32' or 'bf16'")
-    nb = qnet_packed_bytes(precision, dim_ff, n_layers)             # (the size needs no device: a wrong blob is refused anywhere)
-    if isinstance(packed, torch.Tensor) and packed.numel() != nb:
-        raise ValueError("g2048: packed must be a %s blob of %d bytes (dim_ff %d, %d layers)" % (precision, nb, dim_ff, n_layers))
+    _check_play_blob("qnet", packed, precision, dim_ff, n_layers)
     epsilon = float(epsilon)
     if not 0.0 <= epsilon <= 1.0:
         raise ValueError("g2048: epsilon must lie in [0, 1]")
-    L.require_device_tensor(boards, torch.uint8, (16,), "boards")
-    _require_scores(scores)
-    L.require_device_tensor(packed, torch.uint8, None, "packed")
+    _require_games(boards, scores, packed)
     out = _net_game_results(boards, scores, max_moves, max_waves, "max_waves", want_rewards, want_actions)
     return _play_net_games(L.lib().g2048_play_qnet_games, L.lib().g2048_play_qnet_workspace, boards, scores,
                            (packed.data_ptr(), int(dim_ff), int(n_layers)), out, max_moves,

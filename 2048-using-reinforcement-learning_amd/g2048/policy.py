@@ -15,8 +15,8 @@ The actor's four outputs always go through the softmax. Anything else raises Val
 import torch
 import torch.nn as nn
 
-from . import _lib as L
 from . import ops
+from ._encoder_net import OutputCache
 
 WIDTHS = (16, 256, 128, 64)
 BATCHNORM_MODES = ("auto", "always", "never")
@@ -226,23 +226,19 @@ class DevicePolicy:
         if self.critic is not None and self.critic.device != self.actor.device:
             raise ValueError("DevicePolicy: actor and critic live on different devices")
         self.device = self.actor.device
-        self._out = {}
+        self._out = OutputCache("DevicePolicy", self.device)
 
     def refresh(self):
         self.actor.refresh()
         if self.critic is not None:
             self.critic.refresh()
 
+    def _outputs(self, n, device):
+        return (torch.empty((n, 4), dtype=torch.float32, device=device),
+                torch.empty((n, 1), dtype=torch.float32, device=device) if self.critic is not None else None)
+
     def __call__(self, boards):
-        L.require_device_tensor(boards, torch.uint8, (16,), "boards")
-        if boards.device != self.device:
-            raise ValueError("DevicePolicy: boards on %s, weights on %s" % (boards.device, self.device))
-        n = boards.shape[0]
-        key = (n, torch.cuda.current_stream(self.device).cuda_stream)
-        bufs = self._out.get(key)
-        if bufs is None:
-            bufs = (torch.empty((n, 4), dtype=torch.float32, device=self.device),
-                    torch.empty((n, 1), dtype=torch.float32, device=self.device) if self.critic is not None else None)
-            self._out[key] = bufs
+        n = self._out.rows(boards)
+        probs, value = self._out.get(n, self._outputs)
         return ops.policy_forward(boards, self.actor.blob(n), self.critic.blob(n) if self.critic is not None else None,
-                                  self.precision, probs=bufs[0], value=bufs[1])
+                                  self.precision, probs=probs, value=value)

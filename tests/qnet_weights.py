@@ -28,20 +28,9 @@ def exponent(name, shape):
     return e + RECIPE["fc_gain_exp"] if name == "fc.weight" else e
 
 
-def tensor(number, name, shape, seed=SEED):
-    """Tensor `number` (its position in the state dict) as a float64 array; every value is exact in float32."""
-    count = int(np.prod(shape))
-    key = np.uint64(((seed << 40) ^ (number << 32)) & tw.M64)
-    v = (tw.splitmix64(key ^ np.arange(count, dtype=np.uint64)) >> np.uint64(48)).astype(np.int64)
-    w = (2 * v - 65535).astype(np.float64) / 65536.0 * 2.0 ** exponent(name, shape)
-    if ".norm" in name and name.endswith("weight"):
-        w = w + 1.0
-    return w.reshape(shape)
-
-
 def state_dict(named_shapes, seed=SEED):
     """{name: float64 array} for [(name, shape)] in state-dict order."""
-    return {name: tensor(i, name, tuple(shape), seed) for i, (name, shape) in enumerate(named_shapes)}
+    return tw.state_dict(named_shapes, seed, exponent)
 
 
 def reference_shapes(dim_ff=2048, n_layers=2, prefix="transformer"):

@@ -43,8 +43,9 @@ def exponent(name, shape):
     return e + RECIPE["head_gain_exp"] if name in ("actor.weight", "critic.weight") else e
 
 
-def tensor(number, name, shape, seed=SEED):
-    """Tensor `number` (its position in the state dict) as a float64 array; every value is exact in float32."""
+def tensor(number, name, shape, seed=SEED, exponent=exponent):
+    """Tensor `number` (its position in the state dict) as a float64 array; every value is exact in float32. exponent(name,
+    shape): the per-tensor power of two (this module's, or another fixture's rule)."""
     count = int(np.prod(shape))
     key = np.uint64(((seed << 40) ^ (number << 32)) & M64)
     v = (splitmix64(key ^ np.arange(count, dtype=np.uint64)) >> np.uint64(48)).astype(np.int64)
@@ -54,9 +55,9 @@ def tensor(number, name, shape, seed=SEED):
     return w.reshape(shape)
 
 
-def state_dict(named_shapes, seed=SEED):
+def state_dict(named_shapes, seed=SEED, exponent=exponent):
     """{name: float64 array} for [(name, shape)] in state-dict order."""
-    return {name: tensor(i, name, tuple(shape), seed) for i, (name, shape) in enumerate(named_shapes)}
+    return {name: tensor(i, name, tuple(shape), seed, exponent) for i, (name, shape) in enumerate(named_shapes)}
 
 
 def checksum(arr):
