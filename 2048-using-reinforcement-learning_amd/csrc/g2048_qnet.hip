@@ -10,8 +10,15 @@
 //                            exploit action of DQNAgent.select_action (hybrid.py:943-953).
 //   qnet_select_kernel       the whole of select_action (:909-953, use_beam_search = False) on given Q-values: epsilon coin,
 //                            exploit argmax, exploration biased to RIGHT / DOWN (g2048_qnet_select_actions).
+//   qnet_beam_kernel         select_action at use_beam_search = True on given Q-values (g2048_qnet_beam_actions): where the
+//                            reference's beam_search plans (max tile >= threshold, at least 8 tiles) the exploit action is the
+//                            decision of g2048_lookahead.h -- one ranking of the root's at most 24 children, which is all the
+//                            reference's search does (its loop always leaves after the first level) -- and the argmax elsewhere.
+//                            search_depth >= 2 consults no network; search_depth 1 reads the candidates' Q-values.
+//   qnet_expand_kernel       the candidate boards of that ranking for search_depth 1, 32 slots a board (g2048_qnet_beam_expand).
 //   qnet_play_kernel         complete games (evaluate_agent, :1176-1210) in one launch, 32 game slots a wavefront, with the
-//                            game-slot core of g2048_play.h (g2048_play_qnet_games).
+//                            game-slot core of g2048_play.h (g2048_play_qnet_games; with the planned decision between the exploit
+//                            action and the epsilon coin, search_depth >= 2: g2048_play_qnet_beam_games).
 //
 // What is computed. The reference feeds the encoder x.unsqueeze(1) with batch_first=False, and only ever calls the network with
 // one board, so every board is a sequence of ONE token: the softmax over one key is exactly 1.0 and the attention block is
@@ -45,10 +52,12 @@
 #include <stdio.h>
 
 #include <algorithm>
+#include <cmath>
 
 #include "../../include/g2048.h"
 #include "g2048_board.h"
 #include "g2048_host.h"
+#include "g2048_lookahead.h"
 #include "g2048_mfma.h"
 #include "g2048_play.h"
 #include "g2048_rng.h"
@@ -277,6 +286,69 @@ __global__ __launch_bounds__(256) void qnet_select_kernel(const float4 *__restri
     if (explored_out) explored_out[i] = explored ? 1 : 0;
 }
 
+// ------------------------------------------------------------------------------------------------------ beam_search --
+// One decision's scratch (g2048_lookahead.h) as a column of LDS: lane s of S owns key[.][s] and rank[.][s], nobody else touches
+// them, and every index the decision uses is uniform over the lanes that run it, so the accesses are free of bank conflicts.
+template <int S>
+struct LookaheadLds {
+    double key[kLookaheadCandidates][S];
+    uint32_t rank[kLookaheadCandidates][S];
+};
+
+template <int S>
+struct LookaheadColumn {
+    LookaheadLds<S> &lds;
+    int s;
+    __device__ double &key(uint32_t i) { return lds.key[i][s]; }
+    __device__ uint32_t &rank(uint32_t i) { return lds.rank[i][s]; }
+};
+
+// The whole of select_action at use_beam_search = True (hybrid.py:909-953) on given Q-values, one lane a board: the exploit
+// action is beam_search's where it plans and the argmax elsewhere; the coin and the exploration are qnet_select_kernel's.
+constexpr int kBeamBlock = 64;
+__global__ __launch_bounds__(kBeamBlock) void qnet_beam_kernel(const float4 *__restrict__ q, const uint4 *__restrict__ boards,
+                                                              const float *__restrict__ succ_q, uint8_t *__restrict__ actions,
+                                                              uint8_t *__restrict__ planned_out, uint8_t *__restrict__ explored_out,
+                                                              uint32_t width, uint32_t threshold, double gamma, float epsilon,
+                                                              uint32_t k0, uint32_t k1, uint64_t id_base, size_t n)
+{
+    __shared__ LookaheadLds<kBeamBlock> lds;
+    const size_t i = (size_t)blockIdx.x * kBeamBlock + threadIdx.x;
+    if (i >= n) return;
+    const float4 qi = q[i];
+    const uint4 bw = boards[i];
+    const Board b{{bw.x, bw.y, bw.z, bw.w}};
+    const uint32_t mask = valid_mask_env(b);
+    uint32_t a = exploit_action(qi.x, qi.y, qi.z, qi.w, mask);
+    const bool planned = lookahead_planned(b, threshold);
+    if (planned) {
+        LookaheadColumn<kBeamBlock> column{lds, (int)threadIdx.x};
+        a = lookahead_action(b, width, gamma, succ_q ? succ_q + i * (kLookaheadSlots * 4u) : nullptr, column);
+    }
+    bool explored;
+    actions[i] = (uint8_t)select_action(a, b, mask, epsilon, Keys{k0, k1}, id_base + i, explored);
+    if (planned_out) planned_out[i] = planned ? 1 : 0;
+    if (explored_out) explored_out[i] = explored ? 1 : 0;
+}
+
+// The candidate boards of every board, one lane a slot (32 a board, slot 8 a + j): pick i of action a from draw 3 a + i of the
+// board's id, mapped as simulate_sampled_successor maps it (for a = 0 these are g2048_simulate_move_sampled's successors).
+__global__ __launch_bounds__(256) void qnet_expand_kernel(const uint4 *__restrict__ boards, uint4 *__restrict__ succ, uint8_t *__restrict__ count,
+                                                           uint32_t k0, uint32_t k1, uint64_t id_base, size_t n)
+{
+    const size_t gidx = (size_t)blockIdx.x * 256u + threadIdx.x;
+    const size_t i = gidx / kLookaheadSlots;
+    if (i >= n) return;
+    const uint32_t a = ((uint32_t)gidx >> 3) & 3u, j = (uint32_t)gidx & 7u;
+    const uint4 bw = boards[i];
+    const uint64_t id = id_base + i;
+    uint32_t c;
+    const Board o = lookahead_slot(Board{{bw.x, bw.y, bw.z, bw.w}}, a, j, rng_draw(k0, k1, id, 3u * a), rng_draw(k0, k1, id, 3u * a + 1u),
+                                   rng_draw(k0, k1, id, 3u * a + 2u), c);
+    succ[gidx] = make_uint4(o.w[0], o.w[1], o.w[2], o.w[3]);
+    if (j == 0u) count[i * 4u + a] = (uint8_t)c;
+}
+
 // ---------------------------------------------------------------------------------------------------------- forward --
 // The forward pass in two pieces that qnet_forward_kernel and the game-playing kernel (qnet_play_kernel, below) share. Both
 // expand exactly this text, and a wavefront's pass depends on nothing but its own 32 boards and the blob, so the two kernels give
@@ -453,6 +525,18 @@ struct QPlayArgs {
     uint32_t n_waves;                                // wavefronts that play; the last block's surplus ones leave at once
 };
 
+// With BEAM the exploit action of a board the reference's beam_search plans is that search's decision (g2048_lookahead.h,
+// search_depth >= 2: no network behind it) and the kernel takes two more arguments. They ride behind QPlayArgs in a struct of
+// their own, and the scratch of the decisions is LDS only this instantiation has, so that without BEAM the kernel is
+// instruction for instruction what it was before it had the parameter.
+struct QBeamPlayArgs {
+    QPlayArgs q;
+    uint32_t width, threshold;
+};
+template <bool BEAM> using QArgs = std::conditional_t<BEAM, QBeamPlayArgs, QPlayArgs>;
+__device__ inline const QPlayArgs &qplay(const QPlayArgs &a) { return a; }
+__device__ inline const QPlayArgs &qplay(const QBeamPlayArgs &a) { return a.q; }
+
 // LDS accesses of one wavefront complete in program order; this only keeps the compiler from moving them across the point
 // where lanes read what other lanes of the wavefront wrote.
 __device__ inline void wave_sync()
@@ -462,10 +546,12 @@ __device__ inline void wave_sync()
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-template <bool BF16>
-__global__ __launch_bounds__(64 * kWaves, 2) void qnet_play_kernel(const unsigned char *__restrict__ weights, int ff, int layers, const QPlayArgs args)
+template <bool BF16, bool BEAM>
+__global__ __launch_bounds__(64 * kWaves, 2) void qnet_play_kernel(const unsigned char *__restrict__ weights, int ff, int layers, const QArgs<BEAM> args)
 {
-    __shared__ QPlayArgs par;
+    __shared__ QArgs<BEAM> all_args;
+    __shared__ LookaheadLds<kWaveBoards> look[BEAM ? kWaves : 1];     // (not referenced without BEAM, and then not allocated)
+    const QPlayArgs &par = qplay(all_args);
     __shared__ float lds[kWaves][kGrid][kWaveBoards];
     __shared__ PlaySlots<kWaveBoards> wave_slots[kWaves];
     __shared__ uint4 s_dir[G2048_DIR_TABLE_WORDS / 4];
@@ -477,7 +563,7 @@ __global__ __launch_bounds__(64 * kWaves, 2) void qnet_play_kernel(const unsigne
     load_dir_table(s_dir, threadIdx.x);
     for (int i = lane; i < kGrid * kWaveBoards; i += 64) (&grid[0][0])[i] = 0.0f;
     if (slot_lane) slots.clear(lane);
-    if (threadIdx.x == 0) par = args;
+    if (threadIdx.x == 0) all_args = args;
     __syncthreads();                                 // par and s_dir are there; the only block barrier
     if (blockIdx.x * (unsigned)kWaves + (unsigned)wave >= par.n_waves) return;
     bool drained = false;                            // wavefront-uniform: the queue has no game left
@@ -510,6 +596,12 @@ __global__ __launch_bounds__(64 * kWaves, 2) void qnet_play_kernel(const unsigne
             Game game = slots.load(lane);
             const uint32_t mask = valid_mask_env(game.board);
             uint32_t a = exploit_action(qs[0], qs[1], qs[2], qs[3], mask);
+            if constexpr (BEAM) {
+                if (lookahead_planned(game.board, all_args.threshold)) {
+                    LookaheadColumn<kWaveBoards> column{look[wave], lane};
+                    a = lookahead_action(game.board, all_args.width, 0.0, nullptr, column);
+                }
+            }
             const float epsilon = par.epsilon;
             if (epsilon > 0.0f) {                    // (epsilon 0 never explores: no draw)
                 bool explored;
@@ -523,6 +615,58 @@ __global__ __launch_bounds__(64 * kWaves, 2) void qnet_play_kernel(const unsigne
 }
 
 bool good_epsilon(float e) { return e >= 0.0f && e <= 1.0f; }      // false for NaN
+
+// the settings of the reference's beam_search: G2048_OK, or the error as `entry`'s
+int check_beam_settings(const char *entry, int beam_width, int search_depth, int threshold)
+{
+    if (beam_width < 1 || beam_width > 64) return fail(G2048_ERR_ARG, "%s: beam_width must lie in 1 .. 64", entry);
+    if (search_depth < 1) return fail(G2048_ERR_ARG, "%s: search_depth must be at least 1", entry);
+    if (threshold < 1) return fail(G2048_ERR_ARG, "%s: threshold (a tile value) must be at least 1", entry);
+    return G2048_OK;
+}
+
+// g2048_play_qnet_games (BEAM false: the three settings are not read) and g2048_play_qnet_beam_games; `stem` as in g2048_host.h
+template <bool BEAM>
+int play_qnet(const char *stem, void *boards_inout, uint32_t *score_inout, const void *packed, int dim_ff, int n_layers, int32_t *moves_out,
+              int32_t *valid_out, int32_t *invalid_out, int32_t *milestone_move_out, double *reward_sum_out_or_null, uint8_t *alive_out,
+              uint8_t *actions_out_or_null, int max_moves, float epsilon, int beam_width, int search_depth, int threshold, uint64_t seed,
+              uint64_t game_id_base, size_t n_games, uint32_t opts, uint32_t max_waves, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (n_games == 0) return G2048_OK;
+    char entry[64];
+    snprintf(entry, sizeof entry, "%s_games", stem);
+    if (const int rc = check_play_args(stem, boards_inout, score_inout, packed, moves_out, valid_out, invalid_out, milestone_move_out,
+                                       reward_sum_out_or_null, alive_out, max_moves, n_games, workspace, workspace_bytes))
+        return rc;
+    if (const int rc = check_encoder_net(entry, (int)opts, "opts (precision)", dim_ff, n_layers)) return rc;
+    if (!good_epsilon(epsilon)) return fail(G2048_ERR_ARG, "%s: epsilon must lie in [0, 1]", entry);
+    if (BEAM) {
+        if (const int rc = check_beam_settings(entry, beam_width, search_depth, threshold)) return rc;
+        if (search_depth == 1)
+            return fail(G2048_ERR_ARG, "%s: search_depth 1 asks the network about every candidate and is not played in one launch; use "
+                                       "the stepwise form (g2048_qnet_beam_expand, g2048_qnet_forward, g2048_qnet_beam_actions)", entry);
+    }
+    const bool bf16 = opts == G2048_POLICY_BF16;
+    // auto: as many wavefronts as the chip holds at once (every later one would only find the queue empty)
+    const size_t cap = max_waves ? (size_t)max_waves : (size_t)device_cus() * kWaves * with_bool(bf16, [](auto BF16) {
+        return resident_per_cu(qnet_play_kernel<decltype(BF16)::value, BEAM>, 64 * kWaves);
+    });
+    if (cap == 0) return fail(G2048_ERR_HIP, "%s: no HIP device (occupancy query failed)", entry);
+    const size_t waves = std::min(std::min((n_games + kWaveBoards - 1) / kWaveBoards, cap), (size_t)0x7fffffffu);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (const int rc = reset_play_buffers(stem, workspace, actions_out_or_null, n_games, max_moves, s)) return rc;
+    const QPlayArgs base{{static_cast<unsigned long long *>(workspace), static_cast<uint4 *>(boards_inout), score_inout, n_games, seed,
+                          game_id_base, moves_out, valid_out, invalid_out, reinterpret_cast<int4 *>(milestone_move_out),
+                          reward_sum_out_or_null, alive_out, actions_out_or_null, max_moves}, epsilon, (uint32_t)waves};
+    QArgs<BEAM> args;
+    if constexpr (BEAM) args = QBeamPlayArgs{base, (uint32_t)beam_width, (uint32_t)threshold};
+    else args = base;
+    with_bool(bf16, [&](auto BF16) {
+        hipLaunchKernelGGL((qnet_play_kernel<decltype(BF16)::value, BEAM>), dim3(blocks_for(waves, kWaves)), dim3(64 * kWaves), 0, s,
+                           static_cast<const unsigned char *>(packed), dim_ff, n_layers, args);
+    });
+    return check_launch(entry);
+}
 
 }  // namespace
 
@@ -598,7 +742,46 @@ int g2048_qnet_select_actions(const float *q, const void *boards, uint8_t *actio
     return check_launch("g2048_qnet_select_actions");
 }
 
+int g2048_qnet_beam_actions(const float *q, const void *boards, const float *succ_q_or_null, uint8_t *actions_out,
+                            uint8_t *planned_out_or_null, uint8_t *explored_out_or_null, int beam_width, int search_depth, int threshold,
+                            double gamma, float epsilon, uint64_t seed, uint64_t step_index, uint64_t env_id_base, size_t n, void *stream)
+{
+    if (n == 0) return G2048_OK;
+    if (!q || !boards || !actions_out) return fail(G2048_ERR_ARG, "g2048_qnet_beam_actions: null pointer");
+    if (!aligned(q, 16) || !aligned(boards, 16) || !aligned(succ_q_or_null, 16))
+        return fail(G2048_ERR_ARG, "g2048_qnet_beam_actions: misaligned pointer (q, boards, succ_q: 16 bytes)");
+    if (const int rc = check_beam_settings("g2048_qnet_beam_actions", beam_width, search_depth, threshold)) return rc;
+    if (!std::isfinite(gamma)) return fail(G2048_ERR_ARG, "g2048_qnet_beam_actions: gamma must be finite");
+    if (search_depth == 1 && !succ_q_or_null)
+        return fail(G2048_ERR_ARG, "g2048_qnet_beam_actions: search_depth 1 needs succ_q (Q of the boards of g2048_qnet_beam_expand)");
+    if (!good_epsilon(epsilon)) return fail(G2048_ERR_ARG, "g2048_qnet_beam_actions: epsilon must lie in [0, 1]");
+    const size_t blocks = (n + kBeamBlock - 1) / kBeamBlock;
+    if (blocks > 0x7fffffffu) return fail(G2048_ERR_ARG, "g2048_qnet_beam_actions: n too large for one launch");
+    const Keys k = rng_keys(seed, DOM_POLICY, step_index);
+    hipLaunchKernelGGL(qnet_beam_kernel, dim3((unsigned)blocks), dim3(kBeamBlock), 0, static_cast<hipStream_t>(stream),
+                       reinterpret_cast<const float4 *>(q), static_cast<const uint4 *>(boards), search_depth == 1 ? succ_q_or_null : nullptr,
+                       actions_out, planned_out_or_null, explored_out_or_null, (uint32_t)beam_width, (uint32_t)threshold, gamma, epsilon,
+                       k.k0, k.k1, env_id_base, n);
+    return check_launch("g2048_qnet_beam_actions");
+}
+
+int g2048_qnet_beam_expand(const void *boards, void *succ_boards_out, uint8_t *count_out, uint64_t seed, uint64_t step_index,
+                           uint64_t state_id_base, size_t n, void *stream)
+{
+    if (n == 0) return G2048_OK;
+    if (!boards || !succ_boards_out || !count_out) return fail(G2048_ERR_ARG, "g2048_qnet_beam_expand: null pointer");
+    if (!aligned(boards, 16) || !aligned(succ_boards_out, 16) || !aligned(count_out, 4))
+        return fail(G2048_ERR_ARG, "g2048_qnet_beam_expand: misaligned pointer (boards, successors: 16 bytes; counts: 4)");
+    const size_t blocks = n / (256 / kLookaheadSlots) + 1;
+    if (blocks > 0x7fffffffu) return fail(G2048_ERR_ARG, "g2048_qnet_beam_expand: n too large for one launch");
+    const Keys k = rng_keys(seed, DOM_SIMULATE, step_index);
+    hipLaunchKernelGGL(qnet_expand_kernel, dim3(blocks_for(n * kLookaheadSlots, 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       static_cast<const uint4 *>(boards), static_cast<uint4 *>(succ_boards_out), count_out, k.k0, k.k1, state_id_base, n);
+    return check_launch("g2048_qnet_beam_expand");
+}
+
 size_t g2048_play_qnet_workspace(size_t n_games) { return ticket_workspace_bytes(n_games); }
+size_t g2048_play_qnet_beam_workspace(size_t n_games) { return ticket_workspace_bytes(n_games); }
 
 int g2048_play_qnet_games(void *boards_inout, uint32_t *score_inout, const void *packed, int dim_ff, int n_layers, int32_t *moves_out,
                           int32_t *valid_out, int32_t *invalid_out, int32_t *milestone_move_out, double *reward_sum_out_or_null,
@@ -606,29 +789,20 @@ int g2048_play_qnet_games(void *boards_inout, uint32_t *score_inout, const void 
                           uint64_t game_id_base, size_t n_games, uint32_t opts, uint32_t max_waves, void *workspace, size_t workspace_bytes,
                           void *stream)
 {
-    if (n_games == 0) return G2048_OK;
-    if (const int rc = check_play_args("g2048_play_qnet", boards_inout, score_inout, packed, moves_out, valid_out, invalid_out,
-                                       milestone_move_out, reward_sum_out_or_null, alive_out, max_moves, n_games, workspace, workspace_bytes))
-        return rc;
-    if (const int rc = check_encoder_net("g2048_play_qnet_games", (int)opts, "opts (precision)", dim_ff, n_layers)) return rc;
-    if (!good_epsilon(epsilon)) return fail(G2048_ERR_ARG, "g2048_play_qnet_games: epsilon must lie in [0, 1]");
-    const bool bf16 = opts == G2048_POLICY_BF16;
-    // auto: as many wavefronts as the chip holds at once (every later one would only find the queue empty)
-    const size_t cap = max_waves ? (size_t)max_waves : (size_t)device_cus() * kWaves * with_bool(bf16, [](auto BF16) {
-        return resident_per_cu(qnet_play_kernel<decltype(BF16)::value>, 64 * kWaves);
-    });
-    if (cap == 0) return fail(G2048_ERR_HIP, "g2048_play_qnet_games: no HIP device (occupancy query failed)");
-    const size_t waves = std::min(std::min((n_games + kWaveBoards - 1) / kWaveBoards, cap), (size_t)0x7fffffffu);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (const int rc = reset_play_buffers("g2048_play_qnet", workspace, actions_out_or_null, n_games, max_moves, s)) return rc;
-    const QPlayArgs args{{static_cast<unsigned long long *>(workspace), static_cast<uint4 *>(boards_inout), score_inout, n_games, seed,
-                          game_id_base, moves_out, valid_out, invalid_out, reinterpret_cast<int4 *>(milestone_move_out),
-                          reward_sum_out_or_null, alive_out, actions_out_or_null, max_moves}, epsilon, (uint32_t)waves};
-    with_bool(bf16, [&](auto BF16) {
-        hipLaunchKernelGGL(qnet_play_kernel<decltype(BF16)::value>, dim3(blocks_for(waves, kWaves)), dim3(64 * kWaves), 0, s,
-                           static_cast<const unsigned char *>(packed), dim_ff, n_layers, args);
-    });
-    return check_launch("g2048_play_qnet_games");
+    return play_qnet<false>("g2048_play_qnet", boards_inout, score_inout, packed, dim_ff, n_layers, moves_out, valid_out, invalid_out,
+                            milestone_move_out, reward_sum_out_or_null, alive_out, actions_out_or_null, max_moves, epsilon, 0, 0, 0, seed,
+                            game_id_base, n_games, opts, max_waves, workspace, workspace_bytes, stream);
+}
+
+int g2048_play_qnet_beam_games(void *boards_inout, uint32_t *score_inout, const void *packed, int dim_ff, int n_layers, int32_t *moves_out,
+                               int32_t *valid_out, int32_t *invalid_out, int32_t *milestone_move_out, double *reward_sum_out_or_null,
+                               uint8_t *alive_out, uint8_t *actions_out_or_null, int max_moves, float epsilon, int beam_width,
+                               int search_depth, int threshold, uint64_t seed, uint64_t game_id_base, size_t n_games, uint32_t opts,
+                               uint32_t max_waves, void *workspace, size_t workspace_bytes, void *stream)
+{
+    return play_qnet<true>("g2048_play_qnet_beam", boards_inout, score_inout, packed, dim_ff, n_layers, moves_out, valid_out, invalid_out,
+                           milestone_move_out, reward_sum_out_or_null, alive_out, actions_out_or_null, max_moves, epsilon, beam_width,
+                           search_depth, threshold, seed, game_id_base, n_games, opts, max_waves, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

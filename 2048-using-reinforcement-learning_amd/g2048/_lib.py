@@ -100,6 +100,11 @@ SIGNATURES = {
     "g2048_qnet_select_actions": (_int, [_vp, _vp, _vp, _vp, C.c_float, _u64, _u64, _u64, _sz, _vp]),
     "g2048_play_qnet_workspace": (_sz, [_sz]),
     "g2048_play_qnet_games": (_int, [_vp] * 3 + [_int, _int] + [_vp] * 7 + [_int, C.c_float, _u64, _u64, _sz, _u32, _u32, _vp, _sz, _vp]),
+    "g2048_qnet_beam_actions": (_int, [_vp] * 6 + [_int, _int, _int, C.c_double, C.c_float, _u64, _u64, _u64, _sz, _vp]),
+    "g2048_qnet_beam_expand": (_int, [_vp, _vp, _vp, _u64, _u64, _u64, _sz, _vp]),
+    "g2048_play_qnet_beam_workspace": (_sz, [_sz]),
+    "g2048_play_qnet_beam_games": (_int, [_vp] * 3 + [_int, _int] + [_vp] * 7 +
+                                   [_int, C.c_float, _int, _int, _int, _u64, _u64, _sz, _u32, _u32, _vp, _sz, _vp]),
 }
 
 

@@ -227,19 +227,27 @@ def evaluate_policy(policy, num_games=4096, max_moves=2000, mode="masked", seed=
 
 
 def evaluate_qnet(qnet, num_games=4096, max_moves=2000, epsilon=0.0, seed=0x2048, game_id_base=0, device=None, fused=True,
-                  histories=None, max_waves=0):
+                  histories=None, max_waves=0, use_beam_search=False, beam_width=15, search_depth=30, beam_search_threshold=64):
     """Complete games of the hybrid agent's Q-network (a g2048.DeviceQNetwork): the reference's evaluate_agent
     (hybrid.py:1176-1210), select_action -> env.step until the game is over or max_moves moves were made (2000: train_agent's
-    max_steps). epsilon is select_action's (evaluate_agent runs at 0.01; 0 = the exploit action alone), with use_beam_search =
-    False: the model-valued beam search of the reference has no device counterpart. Game g starts from VecGame2048's reset of
-    global id game_id_base + g.
+    max_steps). epsilon is select_action's (evaluate_agent runs at 0.01; 0 = the exploit action alone). Game g starts from
+    VecGame2048's reset of global id game_id_base + g.
+
+    use_beam_search=True is the reference's own configuration (DQNAgent sets it, with beam_width 15, search_depth 30,
+    beam_search_threshold 64, gamma 0.99): where its beam_search plans -- max tile >= the threshold and at least 8 tiles -- the
+    exploit action is that search's decision. The reference's search never goes past its first level (include/g2048.h), so at
+    search_depth >= 2 it is a closed form of the board that consults no network, and the network decides only boards below the
+    threshold or with fewer than 8 tiles. fused=True is then ONE g2048_play_qnet_beam_games launch, fused=False the loop with
+    qnet_beam_actions in place of qnet_select_actions. search_depth 1 values every candidate with the network (the draws of its
+    candidates keyed by (seed, SIMULATE, move, game id)) and runs only with fused=False. The default, False, is select_action
+    with use_beam_search = False.
 
     fused=True: every game is played to the end in ONE launch (g2048_play_qnet_games; max_waves = its wavefront count, 32
     games in flight each, 0 = as many as the chip holds). fused=False: the step-by-step loop of the launches that exist apart
     from it -- qnet_forward with actions, qnet_select_actions when epsilon > 0, step, track_episodes -- over the whole batch
     until every game has ended: the yardstick; the games are identical. Returns evaluate_policy's result dict, episode_rewards
-    included; "parameters" holds epsilon, precision, max_moves, num_games and seed. histories: as in evaluate_beam_search
-    (fused driver only)."""
+    included; "parameters" holds epsilon, precision, max_moves, num_games and seed, as before, and with the search also
+    use_beam_search, beam_width, search_depth, beam_search_threshold and gamma. histories: as in evaluate_beam_search (fused driver only)."""
     from .qnet import DeviceQNetwork
     if not isinstance(qnet, DeviceQNetwork):
         raise TypeError("g2048.evaluate_qnet: qnet must be a g2048.DeviceQNetwork")
@@ -250,34 +258,76 @@ def evaluate_qnet(qnet, num_games=4096, max_moves=2000, epsilon=0.0, seed=0x2048
         raise ValueError("g2048.evaluate_qnet: max_moves must be at least 1")
     if histories is not None and not fused:
         raise ValueError("g2048.evaluate_qnet: histories need the fused driver (fused=True)")
+    beam = None
+    if use_beam_search:
+        beam = (int(beam_width), int(search_depth), int(beam_search_threshold))
+        if not 1 <= beam[0] <= 64:
+            raise ValueError("g2048.evaluate_qnet: beam_width must lie in 1 .. 64")
+        if beam[1] < 1:
+            raise ValueError("g2048.evaluate_qnet: search_depth must be at least 1")
+        if beam[2] < 1:
+            raise ValueError("g2048.evaluate_qnet: beam_search_threshold (a tile value) must be at least 1")
+        if beam[1] == 1 and fused:
+            raise ValueError("g2048.evaluate_qnet: search_depth 1 asks the network about every candidate and is not played in one "
+                             "launch; it runs with fused=False")
     dev = qnet.device
     if device is not None and ops._dev_index(torch.device(device)) != ops._dev_index(dev):
         raise ValueError("g2048.evaluate_qnet: the network lives on %s, not %s" % (dev, device))
     n, max_moves = int(num_games), int(max_moves)
     precision, blob, dim_ff, n_layers = qnet.precision, qnet.packed, qnet.dim_ff, qnet.n_layers
+    params = {"epsilon": epsilon, "precision": precision, "max_moves": max_moves, "num_games": n, "seed": seed}
+    if beam is None:
+        def play(env, want_actions):
+            return ops.play_qnet_games(env.boards, env.scores, blob, dim_ff, n_layers, precision, max_moves, epsilon, seed, game_id_base,
+                                       want_rewards=True, want_actions=want_actions, max_waves=max_waves)
+    else:
+        params.update(use_beam_search=True, beam_width=beam[0], search_depth=beam[1], beam_search_threshold=beam[2], gamma=BEAM_GAMMA)
+
+        def play(env, want_actions):
+            return ops.play_qnet_beam_games(env.boards, env.scores, blob, dim_ff, n_layers, precision, max_moves, epsilon, *beam, seed,
+                                            game_id_base, want_rewards=True, want_actions=want_actions, max_waves=max_waves)
     return _evaluate_net(
-        dev, fused,
-        lambda env, want_actions: ops.play_qnet_games(env.boards, env.scores, blob, dim_ff, n_layers, precision, max_moves, epsilon,
-                                                      seed, game_id_base, want_rewards=True, want_actions=want_actions,
-                                                      max_waves=max_waves),
+        dev, fused, play,
         lambda env: _play_policy_stepwise(env, blob, precision, max_moves, None, seed, game_id_base,
-                                          act=qnet_stepwise_act(blob, dim_ff, n_layers, precision, n, dev, epsilon, seed, game_id_base)),
-        {"epsilon": epsilon, "precision": precision, "max_moves": max_moves, "num_games": n, "seed": seed}, game_id_base, histories)
+                                          act=qnet_stepwise_act(blob, dim_ff, n_layers, precision, n, dev, epsilon, seed, game_id_base,
+                                                                beam)),
+        params, game_id_base, histories)
 
 
-def qnet_stepwise_act(blob, dim_ff, n_layers, precision, n, device, epsilon, seed, game_id_base):
+BEAM_GAMMA = 0.99           # DQNAgent's gamma (hybrid.py:769); it enters the search only at search_depth 1
+
+
+def qnet_stepwise_act(blob, dim_ff, n_layers, precision, n, device, epsilon, seed, game_id_base, beam=None):
     """The `act` of _play_policy_stepwise for the Q-network, built only from launches that exist apart from the game kernel:
-    qnet_forward with its exploit actions and, when epsilon > 0, qnet_select_actions with step_index = the move."""
+    qnet_forward with its exploit actions and, when epsilon > 0, qnet_select_actions with step_index = the move.
+    beam = (beam_width, search_depth, threshold): use_beam_search = True -- qnet_forward, then qnet_beam_actions; at
+    search_depth 1 qnet_beam_expand and the forward on the n x 32 candidate boards come between them."""
     q = torch.empty((n, 4), dtype=torch.float32, device=device)
     actions = torch.empty(n, dtype=torch.uint8, device=device)
     explored = torch.empty(n, dtype=torch.uint8, device=device)
+    if beam is None:
+        def act(boards, t):
+            ops.qnet_forward(boards, blob, dim_ff, n_layers, precision, q=q, actions=actions)
+            if epsilon > 0:
+                ops.qnet_select_actions(q, boards, epsilon, seed, t, game_id_base, actions=actions, explored=explored)
+            return actions
+        return act
+    planned = torch.empty(n, dtype=torch.uint8, device=device)
+    depth_one = beam[1] == 1
+    if depth_one:
+        succ = torch.empty((n, 32, 16), dtype=torch.uint8, device=device)
+        count = torch.empty((n, 4), dtype=torch.uint8, device=device)
+        succ_q = torch.empty((n, 32, 4), dtype=torch.float32, device=device)
 
-    def act(boards, t):
-        ops.qnet_forward(boards, blob, dim_ff, n_layers, precision, q=q, actions=actions)
-        if epsilon > 0:
-            ops.qnet_select_actions(q, boards, epsilon, seed, t, game_id_base, actions=actions, explored=explored)
+    def act_beam(boards, t):
+        ops.qnet_forward(boards, blob, dim_ff, n_layers, precision, q=q)
+        if depth_one:
+            ops.qnet_beam_expand(boards, seed, t, game_id_base, succ=succ, count=count)
+            ops.qnet_forward(succ.view(n * 32, 16), blob, dim_ff, n_layers, precision, q=succ_q.view(n * 32, 4))
+        ops.qnet_beam_actions(q, boards, succ_q if depth_one else None, *beam, BEAM_GAMMA, epsilon, seed, t, game_id_base,
+                              actions=actions, planned=planned, explored=explored)
         return actions
-    return act
+    return act_beam
 
 
 def policy_results_from_table(table, episode_rewards, elapsed, parameters):

@@ -576,6 +576,64 @@ def qnet_select_actions(q, boards, epsilon, seed=0x2048, step_index=0, id_base=0
     return actions, explored
 
 
+def _check_beam_settings(beam_width, search_depth, threshold):
+    if not 1 <= int(beam_width) <= 64:
+        raise ValueError("g2048: beam_width must lie in 1 .. 64")
+    if int(search_depth) < 1:
+        raise ValueError("g2048: search_depth must be at least 1")
+    if int(threshold) < 1:
+        raise ValueError("g2048: threshold (beam_search_threshold, a tile value) must be at least 1")
+
+
+def qnet_beam_actions(q, boards, succ_q=None, beam_width=15, search_depth=30, threshold=64, gamma=0.99, epsilon=0.0, seed=0x2048,
+                      step_index=0, id_base=0, actions=None, planned=None, explored=None):
+    """DQNAgent.select_action with use_beam_search = True (hybrid.py:909-953) for every board in ONE launch
+    (g2048_qnet_beam_actions), given q float32 (n,4) of qnet_forward: qnet_select_actions (same coin, same exploration, same
+    draws) whose exploit action is the reference's beam_search where it plans -- max tile >= threshold and at least 8 tiles --
+    and the argmax of q elsewhere. The search is one ranking of the board's at most 24 children (include/g2048.h); at
+    search_depth >= 2 it consults no network, at search_depth 1 it reads succ_q float32 (n,32,4): qnet_forward of
+    qnet_beam_expand's boards. Returns (actions uint8 (n,), planned uint8 (n,): 1 where the board is planned, explored uint8
+    (n,))."""
+    epsilon, gamma = float(epsilon), float(gamma)
+    if not 0.0 <= epsilon <= 1.0:
+        raise ValueError("g2048: epsilon must lie in [0, 1]")
+    _check_beam_settings(beam_width, search_depth, threshold)
+    if gamma != gamma or gamma in (float("inf"), -float("inf")):
+        raise ValueError("g2048: gamma must be finite")
+    if int(search_depth) == 1 and succ_q is None:
+        raise ValueError("g2048: search_depth 1 needs succ_q, the Q-values of qnet_beam_expand's boards")
+    L.require_device_tensor(q, torch.float32, (4,), "q")
+    L.require_device_tensor(boards, torch.uint8, (16,), "boards")
+    n, dev = boards.shape[0], boards.device
+    if q.shape[0] != n:
+        raise ValueError("g2048: q must have n rows")
+    if succ_q is not None:
+        L.require_device_tensor(succ_q, torch.float32, (32, 4), "succ_q")
+        if succ_q.shape[0] != n:
+            raise ValueError("g2048: succ_q must have n rows")
+    actions = _output(actions, n, torch.uint8, (), "actions", dev)
+    planned = _output(planned, n, torch.uint8, (), "planned", dev)
+    explored = _output(explored, n, torch.uint8, (), "explored", dev)
+    L.call(dev, L.lib().g2048_qnet_beam_actions, q.data_ptr(), boards.data_ptr(), succ_q.data_ptr() if succ_q is not None else None,
+           actions.data_ptr(), planned.data_ptr(), explored.data_ptr(), int(beam_width), int(search_depth), int(threshold), gamma,
+           epsilon, L.u64(seed), L.u64(step_index), L.u64(id_base), n, L.stream_ptr(dev))
+    return actions, planned, explored
+
+
+def qnet_beam_expand(boards, seed=0x2048, step_index=0, id_base=0, succ=None, count=None):
+    """The candidate boards of the reference's beam_search for every board in ONE launch (g2048_qnet_beam_expand): succ uint8
+    (n,32,16), slot 8 a + j = candidate j of action a (the hybrid agent's simulate_move: up to three sampled empty cells x {2, 4};
+    pick i of action a from draw 3 a + i of (seed, SIMULATE, step_index, id_base + row)); count uint8 (n,4). An invalid move has
+    count 1 and the board itself in slot 8 a; unused slots are the empty board. Returns (succ, count)."""
+    L.require_device_tensor(boards, torch.uint8, (16,), "boards")
+    n, dev = boards.shape[0], boards.device
+    succ = _output(succ, n, torch.uint8, (32, 16), "succ", dev)
+    count = _output(count, n, torch.uint8, (4,), "count", dev)
+    L.call(dev, L.lib().g2048_qnet_beam_expand, boards.data_ptr(), succ.data_ptr(), count.data_ptr(), L.u64(seed), L.u64(step_index),
+           L.u64(id_base), n, L.stream_ptr(dev))
+    return succ, count
+
+
 class SeenStates:
     """The `seen_states` set and `highest_tile_seen` of PPOAgent (agents/ppo_agent.py:171-176) for ordered batches of
     transitions, resident on the GPU: an open-addressing hash set keyed by the 16-byte board (include/g2048.h,
@@ -1068,6 +1126,28 @@ def play_qnet_games(boards, scores, packed, dim_ff, n_layers, precision="f32", m
     return _play_net_games(L.lib().g2048_play_qnet_games, L.lib().g2048_play_qnet_workspace, boards, scores,
                            (packed.data_ptr(), int(dim_ff), int(n_layers)), out, max_moves,
                            (epsilon, L.u64(seed), L.u64(game_id_base), boards.shape[0], POLICY_PRECISIONS[precision], int(max_waves)))
+
+
+def play_qnet_beam_games(boards, scores, packed, dim_ff, n_layers, precision="f32", max_moves=2000, epsilon=0.0, beam_width=15,
+                         search_depth=30, threshold=64, seed=0x2048, game_id_base=0, want_rewards=True, want_actions=False, max_waves=0):
+    """play_qnet_games with the reference's use_beam_search = True in ONE launch (g2048_play_qnet_beam_games): per move
+    qnet_forward, then select_action as qnet_beam_actions picks it at (beam_width, search_depth, threshold), then the env step.
+    search_depth >= 2 only (the search then consults no network); search_depth 1 is played move by move
+    (evaluate_qnet(fused=False)). Arguments and the returned dict are play_qnet_games'."""
+    _check_play_blob("qnet", packed, precision, dim_ff, n_layers)
+    epsilon = float(epsilon)
+    if not 0.0 <= epsilon <= 1.0:
+        raise ValueError("g2048: epsilon must lie in [0, 1]")
+    _check_beam_settings(beam_width, search_depth, threshold)
+    if int(search_depth) == 1:
+        raise ValueError("g2048: search_depth 1 asks the network about every candidate and is not played in one launch "
+                         "(qnet_beam_expand, qnet_forward, qnet_beam_actions per move: evaluate_qnet(fused=False))")
+    _require_games(boards, scores, packed)
+    out = _net_game_results(boards, scores, max_moves, max_waves, "max_waves", want_rewards, want_actions)
+    return _play_net_games(L.lib().g2048_play_qnet_beam_games, L.lib().g2048_play_qnet_beam_workspace, boards, scores,
+                           (packed.data_ptr(), int(dim_ff), int(n_layers)), out, max_moves,
+                           (epsilon, int(beam_width), int(search_depth), int(threshold), L.u64(seed), L.u64(game_id_base),
+                            boards.shape[0], POLICY_PRECISIONS[precision], int(max_waves)))
 
 
 def replay_games(boards0, actions, n_moves, seed, game_ids=None, game_id_base=0, scores0=None, longest=None):

@@ -96,11 +96,21 @@ def _explored(n, device):
     return torch.empty(n, dtype=torch.uint8, device=device)
 
 
+def _planned(n, device):
+    return torch.empty(n, dtype=torch.uint8, device=device)
+
+
+def _candidates(n, device):         # the 32 candidate boards of every board, their count per action, their Q-values
+    return (torch.empty((n, 32, 16), dtype=torch.uint8, device=device), torch.empty((n, 4), dtype=torch.uint8, device=device),
+            torch.empty((n * 32, 4), dtype=torch.float32, device=device))
+
+
 class DeviceQNetwork(E.PackedNet):
     """Hybrid Q-network on the device: __call__(boards uint8 (N,16)) -> q float32 (N,4); act(boards) -> (actions uint8 (N,), q),
     the exploit action of DQNAgent.select_action (argmax of q over the env's valid moves, ties to the lowest index, 0 for a board
     with no valid move); act(boards, epsilon, seed, step_index, id_base) with epsilon > 0 is the whole epsilon-greedy
-    select_action (one more launch). One g2048_qnet_forward launch per call; the outputs are buffers owned by the network (one set per
+    select_action (one more launch); act_beam(...) is select_action with the reference's use_beam_search = True. One
+    g2048_qnet_forward launch per call; the outputs are buffers owned by the network (one set per
     (N, stream), overwritten by the next call with the same N on the same stream), so after the first call per (N, stream) a
     call neither allocates nor synchronises.
 
@@ -124,4 +134,25 @@ class DeviceQNetwork(E.PackedNet):
         ops.qnet_forward(boards, self.packed, self.dim_ff, self.n_layers, self.precision, q=q, actions=actions)
         if epsilon > 0:
             ops.qnet_select_actions(q, boards, epsilon, seed, step_index, id_base, actions=actions, explored=self._out.get(n, _explored))
+        return actions, q
+
+    def act_beam(self, boards, epsilon=0.0, seed=0x2048, step_index=0, id_base=0, beam_width=15, search_depth=30,
+                 beam_search_threshold=64, gamma=0.99):
+        """(actions, q): act with the reference's use_beam_search = True (DQNAgent.select_action, hybrid.py:909-953; the defaults
+        are DQNAgent's own settings). Where beam_search plans -- max tile >= beam_search_threshold and at least 8 tiles -- the
+        exploit action is its decision, elsewhere the argmax of q; at the reference's settings the network therefore decides only
+        boards below 64 or with fewer than 8 tiles. search_depth >= 2: the forward plus ONE g2048_qnet_beam_actions launch (the
+        search consults no network and no draw). search_depth 1: forward, g2048_qnet_beam_expand (draws keyed by (seed, SIMULATE,
+        step_index, id_base + row)), the forward on the n x 32 candidate boards, then the decision."""
+        n = self._out.rows(boards)
+        q, actions = self._out.get(n, _outputs)
+        ops.qnet_forward(boards, self.packed, self.dim_ff, self.n_layers, self.precision, q=q)
+        succ_q = None
+        if int(search_depth) == 1:
+            succ, count, succ_q = self._out.get(n, _candidates)
+            ops.qnet_beam_expand(boards, seed, step_index, id_base, succ=succ, count=count)
+            ops.qnet_forward(succ.view(n * 32, 16), self.packed, self.dim_ff, self.n_layers, self.precision, q=succ_q)
+            succ_q = succ_q.view(n, 32, 4)
+        ops.qnet_beam_actions(q, boards, succ_q, beam_width, search_depth, beam_search_threshold, gamma, epsilon, seed, step_index,
+                              id_base, actions=actions, planned=self._out.get(n, _planned), explored=self._out.get(n, _explored))
         return actions, q

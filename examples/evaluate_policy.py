@@ -4,7 +4,8 @@ of train.py / play.py, and of hybrid.py's evaluate_agent).
 
     python examples/evaluate_policy.py --games 65536 [--policy mlp|transformer|hybrid] [--weights reference|random]
                                        [--dim-ff 2048] [--layers 2] [--mode masked|unmasked|greedy] [--epsilon 0.01]
-                                       [--precision f32|bf16] [--max-moves 2000] [--out overall_results.json]
+                                       [--beam] [--beam-width 15] [--precision f32|bf16] [--max-moves 2000]
+                                       [--out overall_results.json]
 
 --weights reference (default) loads the reference's trained checkpoint from tests/golden/policy.npz into the reference's
 ActorNetwork layout; random uses a freshly initialised network of that layout. Every game is played to the end in one
@@ -17,7 +18,9 @@ tests/tpolicy_weights.py (--weights is ignored), so the games show the machinery
 
 --policy hybrid plays the reference's HybridDQN layout (agents/hybrid.py:700-727: --dim-ff, --layers) as a g2048.DeviceQNetwork
 through g2048.evaluate_qnet: select_action's epsilon-greedy rule at --epsilon (evaluate_agent's 0.01 by default; --mode is
-ignored), without the reference's beam search. It carries the hash-derived weights of tests/qnet_weights.py."""
+ignored). --beam is the reference's own setting, use_beam_search = True (search_depth 30, threshold 64, --beam-width 15): where
+the agent's beam_search plans -- max tile >= 64 and at least 8 tiles -- its decision replaces the network's, so the network
+decides only boards below 64 or with fewer than 8 tiles. It carries the hash-derived weights of tests/qnet_weights.py."""
 import argparse
 import json
 import os
@@ -96,6 +99,8 @@ ap.add_argument("--layers", type=int, default=2)
 ap.add_argument("--weights", choices=("reference", "random"), default="reference")
 ap.add_argument("--mode", choices=("masked", "unmasked", "greedy"), default="masked")
 ap.add_argument("--epsilon", type=float, default=0.01)
+ap.add_argument("--beam", action="store_true", help="hybrid: the reference's use_beam_search = True")
+ap.add_argument("--beam-width", type=int, default=15)
 ap.add_argument("--precision", choices=("f32", "bf16"), default="f32")
 ap.add_argument("--max-moves", type=int, default=2000)
 ap.add_argument("--seed", type=int, default=2025)
@@ -104,7 +109,7 @@ a = ap.parse_args()
 
 if a.policy == "hybrid":
     policy = hybrid_qnet(a.dim_ff, a.layers, a.precision)
-    what, a.mode = "hybrid Q-network dim_ff %d x %d layers, hash" % (a.dim_ff, a.layers), "epsilon %g" % a.epsilon
+    what, a.mode = "hybrid Q-network dim_ff %d x %d layers, hash" % (a.dim_ff, a.layers), "epsilon %g%s" % (a.epsilon, ", beam search width %d" % a.beam_width if a.beam else "")
 elif a.policy == "transformer":
     policy = transformer_policy(a.dim_ff, a.layers, a.precision)
     what = "transformer dim_ff %d x %d layers, hash" % (a.dim_ff, a.layers)
@@ -119,7 +124,8 @@ else:
     policy = g2048.DevicePolicy(actor.eval().to("cuda"), precision=a.precision)
     what = a.weights
 if a.policy == "hybrid":
-    res = g2048.evaluate_qnet(policy, num_games=a.games, max_moves=a.max_moves, epsilon=a.epsilon, seed=a.seed)
+    res = g2048.evaluate_qnet(policy, num_games=a.games, max_moves=a.max_moves, epsilon=a.epsilon, seed=a.seed, use_beam_search=a.beam,
+                              beam_width=a.beam_width)
 else:
     res = g2048.evaluate_policy(policy, num_games=a.games, max_moves=a.max_moves, mode=a.mode, seed=a.seed)
 s = res["summary"]

@@ -49,7 +49,9 @@ extern "C" {
                                       MERGE_POTENTIAL; no entry point added or removed;
                                       later, additive: g2048_policy_packed_bytes / _pack / _forward,
                                       g2048_play_policy_games / _workspace, g2048_tpolicy_packed_bytes / _pack / _forward,
-                                      g2048_play_tpolicy_games / _workspace, g2048_qnet_packed_bytes / _pack / _forward)
+                                      g2048_play_tpolicy_games / _workspace, g2048_qnet_packed_bytes / _pack / _forward,
+                                      g2048_qnet_select_actions, g2048_play_qnet_games / _workspace, g2048_qnet_beam_actions / _expand,
+                                      g2048_play_qnet_beam_games / _workspace)
                                       4: round 5 (export table = this header + g2048_testing.h exactly: test / measurement hooks moved there,
                                       internal symbols hidden; g2048_replay_games also clamps a game's length to actions_stride)
                                       3: round 4 (actions_out of the g2048_play_games family, g2048_replay_games, g2048_env_step,
@@ -599,8 +601,8 @@ G2048_API int g2048_qnet_forward(const void *boards, const void *packed, float *
  *            from p = (0.125, 0.125, 0.375, 0.375) or (0.25, 0.25, 0.25, 0.25) under the env's valid-move mask with draw(k0, k1,
  *            id, 0). Those p are exact in f32 and the sampler's + 1e-10 does not change them. A board with no valid move samples
  *            among all four (the reference's random.randint(0, 3), :918-919).
- *   The reference's beam_search branch of select_action (:814-907: model-valued leaves, random.sample) is not part of this: the
- *   launch is select_action with use_beam_search = False.
+ *   The reference's beam_search branch of select_action (:814-907) is not part of this launch, which is select_action with
+ *   use_beam_search = False; g2048_qnet_beam_actions is the one with it.
  * q: float32 (n,4), 16-byte aligned, as g2048_qnet_forward wrote it; boards 16-byte aligned; explored_out_or_null[i] = 1 where
  * the board explored. epsilon outside [0, 1] or NaN is refused. Arguments are checked before any device call; n == 0 returns
  * G2048_OK. Nothing past row n is written. */
@@ -630,6 +632,56 @@ G2048_API int g2048_play_qnet_games(void *boards_inout, uint32_t *score_inout, c
                           double *reward_sum_out_or_null, uint8_t *alive_out, uint8_t *actions_out_or_null, int max_moves,
                           float epsilon, uint64_t seed, uint64_t game_id_base, size_t n_games, uint32_t opts, uint32_t max_waves,
                           void *workspace, size_t workspace_bytes, void *stream);
+
+/* DQNAgent.select_action with use_beam_search = True (agents/hybrid.py:909-953, the reference's own setting: beam_width 15,
+ * search_depth 30, beam_search_threshold 64, gamma 0.99), and the games played that way.
+ *
+ * What the reference's beam_search (:814-907) computes. Its loop over the depth ends after the first level whatever search_depth
+ * is: the early-exit test (:871) reads the fourth field of a beam entry as `done`, and that field is the transition probability,
+ * which is never 0. So a decision is one ranking of the root's children, and at search_depth >= 2 -- the reference's 30 included --
+ * the network is never consulted on a planned board (leaf values are taken only at the last step) and the random draws cannot
+ * change the result (the reward of a candidate depends on the moved board and the spawned tile's value, not on its cell). With the
+ * reference's settings the network therefore decides only boards whose max tile is below 64 or that hold fewer than 8 tiles.
+ *   planned     the search decides board B when its max tile >= threshold and at least 8 cells are filled; otherwise the exploit
+ *               action of g2048_qnet_forward does, as in g2048_qnet_select_actions.
+ *   candidates  in the order a = 0, 1, 2, 3 (LEFT, UP, RIGHT, DOWN, all four directions true as in the env). M = move(B, a). M == B:
+ *               one candidate, reward -1.0, p = 1.0. Else, e = empty cells of M, k = min(3, e): 2k candidates -- pick 0 with a 2,
+ *               pick 0 with a 4, pick 1 with a 2, ... -- with the rewards of g2048_simulate_move_sampled (weighted 0.9 / 0.1) and
+ *               p = 1.0 / (2k). Slot 8 a + j is candidate j of action a.
+ *   totals      search_depth >= 2: 0.0 + reward. search_depth == 1: (0.0 + reward) + gamma * (double)v, v = the float32 maximum of
+ *               the four Q-values of the candidate's board (an invalid move's board is B itself). Finite values are assumed.
+ *   beam        key = total * p in f64; the first beam_width candidates in descending key order, equal keys in candidate order.
+ *   action      the beam is walked in order, every action sums the keys of its members in that order; the largest sum wins, equal
+ *               sums go to the action whose first member stands earliest in the beam.
+ * All of it is f64 in the reference's operation order and bit-exact (tests/golden/qnet_beam.npz).
+ *
+ *   g2048_qnet_beam_actions   g2048_qnet_select_actions with that exploit action, one launch: the same coin, the same
+ *                             exploration, the same draws. planned_out_or_null[i] = 1 where board i is planned (whether or not it
+ *                             then explored). succ_q_or_null: float32 (n, 32, 4), 16-byte aligned, Q of slot 8 a + j as
+ *                             g2048_qnet_forward wrote it for the boards of g2048_qnet_beam_expand; required at search_depth 1 and
+ *                             not read otherwise. beam_width 1 .. 64, search_depth >= 1, threshold (a tile value) >= 1, gamma finite.
+ *   g2048_qnet_beam_expand    the candidate boards for search_depth 1: succ_boards_out (n x 32 boards, 16-byte aligned), slot 8 a + j;
+ *                             count_out (uint8 n x 4, 4-byte aligned) = candidates per action. Pick i of action a of board
+ *                             state_id_base + b uses draw 3 a + i of (seed, SIMULATE domain, step_index, that id) with
+ *                             g2048_simulate_move_sampled's mapping (for a = 0 its very successors). An invalid move has count 1 and
+ *                             the board itself in slot 8 a; unused slots hold the empty board.
+ *   g2048_play_qnet_beam_games / _workspace   g2048_play_qnet_games with beam_width, search_depth and threshold after epsilon:
+ *                             the same launch, games, draws and outputs, the exploit action of a planned board being the search's.
+ *                             search_depth >= 2 only: search_depth 1 needs the network per candidate and is refused (play it
+ *                             move by move with the three launches above).
+ * Arguments are checked before any device call; n == 0 returns G2048_OK before any check. Nothing past row n is written. */
+G2048_API int g2048_qnet_beam_actions(const float *q, const void *boards, const float *succ_q_or_null, uint8_t *actions_out,
+                            uint8_t *planned_out_or_null, uint8_t *explored_out_or_null, int beam_width, int search_depth,
+                            int threshold, double gamma, float epsilon, uint64_t seed, uint64_t step_index, uint64_t env_id_base,
+                            size_t n, void *stream);
+G2048_API int g2048_qnet_beam_expand(const void *boards, void *succ_boards_out, uint8_t *count_out, uint64_t seed, uint64_t step_index,
+                           uint64_t state_id_base, size_t n, void *stream);
+G2048_API size_t g2048_play_qnet_beam_workspace(size_t n_games);
+G2048_API int g2048_play_qnet_beam_games(void *boards_inout, uint32_t *score_inout, const void *packed, int dim_ff, int n_layers,
+                               int32_t *moves_out, int32_t *valid_out, int32_t *invalid_out, int32_t *milestone_move_out,
+                               double *reward_sum_out_or_null, uint8_t *alive_out, uint8_t *actions_out_or_null, int max_moves,
+                               float epsilon, int beam_width, int search_depth, int threshold, uint64_t seed, uint64_t game_id_base,
+                               size_t n_games, uint32_t opts, uint32_t max_waves, void *workspace, size_t workspace_bytes, void *stream);
 #ifdef __cplusplus
 }
 #endif
