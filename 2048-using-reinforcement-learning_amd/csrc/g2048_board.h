@@ -43,7 +43,7 @@ constexpr uint32_t B7F = 0x7f7f7f7fu;
 
 // RNG domains (DESIGN.md "RNG")
 enum : uint32_t { DOM_STEP = 1, DOM_RESET = 2, DOM_BEAM = 3, DOM_SYNTH_BOARD = 4, DOM_SYNTH_ACTION = 5, DOM_EPISODE = 6, DOM_POLICY = 7,
-                  DOM_SIMULATE = 8, DOM_MINIBATCH = 9 };
+                  DOM_SIMULATE = 8, DOM_MINIBATCH = 9, DOM_REPLAY = 10 };
 
 // ---------------------------------------------------------------- intrinsics --
 // v_perm_b32: bytes of {s0:s1} (s1 = bytes 0..3, s0 = bytes 4..7) picked by the

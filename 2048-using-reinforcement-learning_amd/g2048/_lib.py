@@ -29,6 +29,7 @@ ROLLOUT_OBS_SHIFT, OBS_F32, OBS_F16, OBS_BF16 = 4, 0, 1, 2
 SEEN_SLOT_BYTES = 32
 ENV_RECORD_BYTES, ENV_OP_STEP, ENV_OP_RESET, ENV_OP_PEEK, ENV_OP_MOVE, ENV_OP_SPAWN, ENV_OP_MOVE_AGENT = 80, 0, 1, 2, 3, 4, 5
 ENV_TOKEN_SHIFT = 8
+PER_SCAN_TILE = 256
 POLICY_F32, POLICY_BF16 = 0, 1
 PLAY_POLICY_MASKED, PLAY_POLICY_UNMASKED, PLAY_POLICY_GREEDY, PLAY_POLICY_MODE_SHIFT = 0, 1, 2, 4
 
@@ -105,6 +106,12 @@ SIGNATURES = {
     "g2048_play_qnet_beam_workspace": (_sz, [_sz]),
     "g2048_play_qnet_beam_games": (_int, [_vp] * 3 + [_int, _int] + [_vp] * 7 +
                                    [_int, C.c_float, _int, _int, _int, _u64, _u64, _sz, _u32, _u32, _vp, _sz, _vp]),
+    "g2048_per_update_workspace": (_sz, [_sz]),
+    "g2048_per_push": (_int, [_vp] * 6 + [_sz, _sz, _sz] + [_vp] * 4 + [_u32, _vp, _sz, _vp, _vp]),
+    "g2048_per_sample_workspace": (_sz, [_sz, _sz]),
+    "g2048_per_sample": (_int, [_vp] * 6 + [_sz, _sz, _sz, C.c_float, C.c_float, _sz, _u64, _u64] + [_vp] * 12),
+    "g2048_dqn_shape_rewards": (_int, [_vp, _vp, _vp, _sz, _vp, _vp]),
+    "g2048_per_update_priorities": (_int, [_vp, _sz, _sz, _sz, _vp, _vp, _sz, _vp, _vp]),
 }
 
 

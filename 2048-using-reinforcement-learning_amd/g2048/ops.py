@@ -1241,6 +1241,122 @@ def minibatch_gather(obs, actions, log_probs, rewards, next_boards, flags, batch
     return out
 
 
+# ---- the hybrid agent's prioritized replay (include/g2048.h, "prioritized experience replay") ---------------------------------
+def per_update_workspace_bytes(capacity):
+    return int(L.lib().g2048_per_update_workspace(int(capacity)))
+
+
+def per_sample_workspace_bytes(size, batch=0):
+    return int(L.lib().g2048_per_sample_workspace(int(size), int(batch)))
+
+
+def _per_workspace(t, nbytes, device):
+    """A workspace of at least nbytes: allocated when t is None (float64, so that it is 16-byte aligned), else checked."""
+    if t is None:
+        return torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=device)
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.is_contiguous()) or t.numel() * t.element_size() < nbytes:
+        raise ValueError("g2048: workspace must be a contiguous device tensor of at least %d bytes" % nbytes)
+    return t
+
+
+def _require_per_buffer(states, next_states, actions, rewards, dones, priorities):
+    L.require_device_tensor(states, torch.uint8, (16,), "states")
+    L.require_device_tensor(next_states, torch.uint8, (16,), "next_states")
+    L.require_device_tensor(actions, torch.uint8, None, "actions")
+    L.require_device_tensor(rewards, torch.float32, None, "rewards")
+    L.require_device_tensor(dones, torch.uint8, None, "dones")
+    L.require_device_tensor(priorities, torch.float32, None, "priorities")
+    capacity = priorities.shape[0]
+    if not (states.shape[0] == next_states.shape[0] == actions.shape[0] == rewards.shape[0] == dones.shape[0] == capacity):
+        raise ValueError("g2048: all arrays of a replay buffer must have one entry per slot")
+    return capacity
+
+
+def per_push(states, next_states, actions, rewards, dones, priorities, size, head, boards, actions_in, rewards_in, next_boards, flags,
+             workspace=None):
+    """m calls of PrioritizedReplayBuffer.push (agents/hybrid.py:736-740) in order into the ring (g2048_per_push). The six ring
+    arrays have `capacity` slots; boards / next_boards uint8 (m,16), actions_in uint8, rewards_in float32 or float64, flags uint8
+    (bit 0 = done). Returns the (size, head) after the push."""
+    capacity = _require_per_buffer(states, next_states, actions, rewards, dones, priorities)
+    dev = priorities.device
+    L.require_device_tensor(boards, torch.uint8, (16,), "boards")
+    L.require_device_tensor(next_boards, torch.uint8, (16,), "next_boards")
+    L.require_device_tensor(actions_in, torch.uint8, None, "actions")
+    if rewards_in.dtype not in (torch.float32, torch.float64):
+        raise TypeError("g2048: rewards must be float32 or float64")
+    L.require_device_tensor(rewards_in, rewards_in.dtype, None, "rewards")
+    L.require_device_tensor(flags, torch.uint8, None, "flags")
+    m = boards.shape[0]
+    if not (next_boards.shape[0] == actions_in.shape[0] == rewards_in.shape[0] == flags.shape[0] == m):
+        raise ValueError("g2048: all arrays of a push must have one entry per transition")
+    workspace = _per_workspace(workspace, per_update_workspace_bytes(capacity), dev)
+    size, head = int(size), int(head)
+    L.call(dev, L.lib().g2048_per_push, states.data_ptr(), next_states.data_ptr(), actions.data_ptr(), rewards.data_ptr(), dones.data_ptr(),
+           priorities.data_ptr(), capacity, size, head, boards.data_ptr(), next_boards.data_ptr(), actions_in.data_ptr(),
+           rewards_in.data_ptr(), int(rewards_in.dtype == torch.float64), flags.data_ptr(), m, workspace.data_ptr(), L.stream_ptr(dev))
+    evicted = max(0, size + m - capacity)
+    return min(size + m, capacity), (head + evicted) % capacity
+
+
+def per_sample(states, next_states, actions, rewards, dones, priorities, size, head, alpha, beta, batch, seed=0x2048, sample_index=0,
+               u=None, workspace=None, out=None, want_probs=False):
+    """PrioritizedReplayBuffer.sample (agents/hybrid.py:742-757) and the head of DQNAgent.train_step (:961-969, :971-1034) on the
+    ring (g2048_per_sample), no host round trip. u: None (counter draws of (seed, REPLAY, sample_index)) or float64 (batch,) on
+    the device. Returns dict(indices, weights, states, actions, rewards, next_states, dones, shaped[, probs]); out: the dict a
+    previous call of the same batch size returned, to be overwritten."""
+    capacity = _require_per_buffer(states, next_states, actions, rewards, dones, priorities)
+    dev = priorities.device
+    size, head, batch = int(size), int(head), int(batch)
+    if u is not None:
+        L.require_device_tensor(u, torch.float64, None, "u")
+        if u.shape[0] != batch:
+            raise ValueError("g2048: u must have one draw per sample")
+    if out is None:
+        out = {}
+    shapes = (("indices", torch.int64, ()), ("weights", torch.float32, ()), ("states", torch.float32, (16,)), ("actions", torch.int64, ()),
+              ("rewards", torch.float32, ()), ("next_states", torch.float32, (16,)), ("dones", torch.float32, ()),
+              ("shaped", torch.float32, ()))
+    for name, dtype, tail in shapes:
+        out[name] = _output(out.get(name), batch, dtype, tail, name, dev)
+    if want_probs or "probs" in out:
+        out["probs"] = _output(out.get("probs"), size, torch.float32, (), "probs", dev)
+    workspace = _per_workspace(workspace, per_sample_workspace_bytes(size, batch), dev)
+    L.call(dev, L.lib().g2048_per_sample, states.data_ptr(), next_states.data_ptr(), actions.data_ptr(), rewards.data_ptr(), dones.data_ptr(),
+           priorities.data_ptr(), capacity, size, head, float(alpha), float(beta), batch, L.u64(seed), L.u64(sample_index),
+           u.data_ptr() if u is not None else None, workspace.data_ptr(), *[out[name].data_ptr() for name, _, _ in shapes],
+           out["probs"].data_ptr() if "probs" in out else None, L.stream_ptr(dev))
+    return out
+
+
+def dqn_shape_rewards(states, next_states, rewards, out=None):
+    """The reward shaping of DQNAgent.train_step (agents/hybrid.py:971-1034) for n (state, next state, reward) triples
+    (g2048_dqn_shape_rewards): boards uint8 (n,16), rewards float32; float32 out, bit for bit the reference's."""
+    L.require_device_tensor(states, torch.uint8, (16,), "states")
+    L.require_device_tensor(next_states, torch.uint8, (16,), "next_states")
+    L.require_device_tensor(rewards, torch.float32, None, "rewards")
+    n, dev = states.shape[0], states.device
+    if not (next_states.shape[0] == rewards.shape[0] == n):
+        raise ValueError("g2048: states, next_states and rewards must have one entry per transition")
+    out = _output(out, n, torch.float32, (), "out", dev)
+    L.call(dev, L.lib().g2048_dqn_shape_rewards, states.data_ptr(), next_states.data_ptr(), rewards.data_ptr(), n, out.data_ptr(),
+           L.stream_ptr(dev))
+    return out
+
+
+def per_update_priorities(priorities, size, head, indices, td_errors, workspace=None):
+    """update_priorities(indices, td_errors + 1e-5) (agents/hybrid.py:1063-1064, :759-762) on the ring's priorities
+    (g2048_per_update_priorities): logical int64 indices, float32 td errors; of duplicates the latest in the batch wins."""
+    L.require_device_tensor(priorities, torch.float32, None, "priorities")
+    L.require_device_tensor(indices, torch.int64, None, "indices")
+    L.require_device_tensor(td_errors, torch.float32, None, "td_errors")
+    if indices.shape[0] != td_errors.shape[0]:
+        raise ValueError("g2048: indices and td_errors must have one entry per sample")
+    capacity, dev = priorities.shape[0], priorities.device
+    workspace = _per_workspace(workspace, per_update_workspace_bytes(capacity), dev)
+    L.call(dev, L.lib().g2048_per_update_priorities, priorities.data_ptr(), capacity, int(size), int(head), indices.data_ptr(),
+           td_errors.data_ptr(), indices.shape[0], workspace.data_ptr(), L.stream_ptr(dev))
+
+
 def launch_plan(compute_units=0, resident_blocks_per_cu=0, n_games=0):
     """The chip-size arithmetic of the library (g2048_launch_plan; a host function, usable without a GPU when compute_units
     is given): dict(order_row, order_min_games, helper_cap, default_helpers)."""

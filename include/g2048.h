@@ -51,7 +51,8 @@ extern "C" {
                                       g2048_play_policy_games / _workspace, g2048_tpolicy_packed_bytes / _pack / _forward,
                                       g2048_play_tpolicy_games / _workspace, g2048_qnet_packed_bytes / _pack / _forward,
                                       g2048_qnet_select_actions, g2048_play_qnet_games / _workspace, g2048_qnet_beam_actions / _expand,
-                                      g2048_play_qnet_beam_games / _workspace)
+                                      g2048_play_qnet_beam_games / _workspace, g2048_per_push / _sample / _sample_workspace /
+                                      _update_priorities / _update_workspace, g2048_dqn_shape_rewards)
                                       4: round 5 (export table = this header + g2048_testing.h exactly: test / measurement hooks moved there,
                                       internal symbols hidden; g2048_replay_games also clamps a game's length to actions_stride)
                                       3: round 4 (actions_out of the g2048_play_games family, g2048_replay_games, g2048_env_step,
@@ -682,6 +683,59 @@ G2048_API int g2048_play_qnet_beam_games(void *boards_inout, uint32_t *score_ino
                                double *reward_sum_out_or_null, uint8_t *alive_out, uint8_t *actions_out_or_null, int max_moves,
                                float epsilon, int beam_width, int search_depth, int threshold, uint64_t seed, uint64_t game_id_base,
                                size_t n_games, uint32_t opts, uint32_t max_waves, void *workspace, size_t workspace_bytes, void *stream);
+/* ---- the hybrid agent's prioritized experience replay ("per") and train_step's reward shaping, on the device --------------
+ * PrioritizedReplayBuffer (agents/hybrid.py:730-765) and the part of DQNAgent.train_step around it that needs no gradient
+ * (:959-969 the batch as tensors, :971-1034 the shaping, :1063-1064 the new priorities). The gradient step stays the caller's.
+ *
+ * The buffer is a ring of `capacity` slots in caller-owned device arrays: states and next_states (packed boards, 16 bytes
+ * each, 16-byte aligned), actions (uint8), rewards (float32), dones (uint8), priorities (float32). The caller tracks `size`
+ * (live entries, <= capacity) and `head` (the physical slot of the oldest entry, < capacity) and passes both by value.
+ * Logical index i (0 = oldest: the reference's deque index) lives at slot (head + i) % capacity; every index that crosses this
+ * interface is logical. Nothing here synchronises; every call is a few launches on `stream`.
+ *
+ *   g2048_per_push   m calls of push (:736-740) in order: boards / next_boards (the next states BEFORE any auto-reset, as
+ *       g2048_step and g2048_rollout_step write them), actions_in, rewards_in (float32, or float64 when rewards_f64: rounded to
+ *       float32 as torch.tensor(rewards, dtype=float32) does, :966) and flags (bit 0 = done). Every new entry gets the priority
+ *       M = the maximum of the `size` live priorities before the call, 1.0 for an empty buffer. That is exact: the first push
+ *       appends M itself, so no eviction during the batch can lower the maximum. Entry k goes to slot (head + size + k) %
+ *       capacity; afterwards the caller's size is min(size + m, capacity) and its head has advanced by the entries evicted,
+ *       max(0, size + m - capacity). m > capacity is refused. workspace: g2048_per_update_workspace(capacity) bytes.
+ *   g2048_per_sample   sample (:742-757) and the head of train_step, `batch` draws with replacement:
+ *         w_i = priorities_i ^ alpha and probs_i = w_i / sum(w) in float32 (the sum is accumulated in float64 in a fixed order);
+ *         cdf = the running sum of (double)probs in logical order, divided by its last entry (np.random.choice);
+ *         indices_out[j] = the number of cdf entries <= u_j (searchsorted(side='right'); a draw >= 1 gives the last entry);
+ *         weights_out[j] = (size * probs[index_j]) ^ (-beta) in float32, divided by the batch's maximum (:754-755);
+ *         states_out / next_states_out float32 [batch][16] (the tile values 2^code, 0 = empty), actions_out int64, rewards_out,
+ *         dones_out float32 (:964-968); shaped_out = g2048_dqn_shape_rewards of the gathered transitions; probs_out_or_null
+ *         float32 [size].
+ *       u_j = u_or_null[j] (float64, device memory) when given, else h_j * 2^-32 with h_j draw 0 of (seed, REPLAY domain,
+ *       sample_index, id j). size < batch is refused: train_step returns before it samples then (:956-957). The scan is made
+ *       of stream-ordered launches over tiles of G2048_PER_SCAN_TILE entries (tile sums, one wave over the sums, the final
+ *       pass); no block waits for another and no floating-point sum goes through an atomic, so two calls give the same bits.
+ *       workspace: g2048_per_sample_workspace(size, batch) bytes, 16-byte aligned. The buffer is not modified.
+ *   g2048_dqn_shape_rewards   the shaping loop (:971-1034) for any n (state, next state, reward) triples, bit for bit: the
+ *       mixed float32 / float64 arithmetic of the reference's NumPy scalars is kept (csrc/g2048_per.h states each step).
+ *   g2048_per_update_priorities   update_priorities(indices, td_errors + 1e-5) (:1063-1064, :759-762): entry indices[j] gets
+ *       max(float32(td_errors[j] + 1e-5f), 1e-5f); indices outside 0 .. size-1 are ignored; of duplicate indices the occurrence
+ *       latest in the batch wins, as in the reference's loop (decided by an integer maximum of the batch position, not by write
+ *       order). workspace: g2048_per_update_workspace(capacity) bytes, contents irrelevant.
+ * Arguments are checked before any device call. */
+#define G2048_PER_SCAN_TILE 256
+G2048_API size_t g2048_per_update_workspace(size_t capacity);
+G2048_API int g2048_per_push(void *states, void *next_states, uint8_t *actions, float *rewards, uint8_t *dones, float *priorities,
+                   size_t capacity, size_t size, size_t head, const void *boards, const void *next_boards,
+                   const uint8_t *actions_in, const void *rewards_in, uint32_t rewards_f64, const uint8_t *flags, size_t m,
+                   void *workspace, void *stream);
+G2048_API size_t g2048_per_sample_workspace(size_t size, size_t batch);
+G2048_API int g2048_per_sample(const void *states, const void *next_states, const uint8_t *actions, const float *rewards,
+                     const uint8_t *dones, const float *priorities, size_t capacity, size_t size, size_t head, float alpha,
+                     float beta, size_t batch, uint64_t seed, uint64_t sample_index, const double *u_or_null, void *workspace,
+                     int64_t *indices_out, float *weights_out, float *states_out, int64_t *actions_out, float *rewards_out,
+                     float *next_states_out, float *dones_out, float *shaped_out, float *probs_out_or_null, void *stream);
+G2048_API int g2048_dqn_shape_rewards(const void *states, const void *next_states, const float *rewards, size_t n, float *shaped_out,
+                            void *stream);
+G2048_API int g2048_per_update_priorities(float *priorities, size_t capacity, size_t size, size_t head, const int64_t *indices,
+                                const float *td_errors, size_t batch, void *workspace, void *stream);
 #ifdef __cplusplus
 }
 #endif
