@@ -31,6 +31,7 @@ ENV_RECORD_BYTES, ENV_OP_STEP, ENV_OP_RESET, ENV_OP_PEEK, ENV_OP_MOVE, ENV_OP_SP
 ENV_TOKEN_SHIFT = 8
 PER_SCAN_TILE = 256
 POLICY_F32, POLICY_BF16 = 0, 1
+QNET_BATCH_MAX = 4096
 PLAY_POLICY_MASKED, PLAY_POLICY_UNMASKED, PLAY_POLICY_GREEDY, PLAY_POLICY_MODE_SHIFT = 0, 1, 2, 4
 
 _vp, _u64, _sz, _u32, _int = C.c_void_p, C.c_uint64, C.c_size_t, C.c_uint32, C.c_int
@@ -112,6 +113,9 @@ SIGNATURES = {
     "g2048_per_sample": (_int, [_vp] * 6 + [_sz, _sz, _sz, C.c_float, C.c_float, _sz, _u64, _u64] + [_vp] * 12),
     "g2048_dqn_shape_rewards": (_int, [_vp, _vp, _vp, _sz, _vp, _vp]),
     "g2048_per_update_priorities": (_int, [_vp, _sz, _sz, _sz, _vp, _vp, _sz, _vp, _vp]),
+    "g2048_qnet_batch_workspace": (_sz, [_sz, _int]),
+    "g2048_qnet_forward_batch": (_int, [_vp, _vp, _vp, _sz, _int, _int, _vp, _vp]),
+    "g2048_dqn_targets": (_int, [_vp, _vp, _vp, _vp, C.c_float, _vp, _vp, _sz, _vp]),
 }
 
 

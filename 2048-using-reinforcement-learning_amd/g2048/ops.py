@@ -556,6 +556,59 @@ def qnet_forward(boards, packed, dim_ff, n_layers, precision="f32", q=None, acti
     return q if actions is None else (actions, q)
 
 
+def qnet_batch_workspace_bytes(n, dim_ff):
+    """Bytes of the workspace qnet_forward_batch needs for n boards (g2048_qnet_batch_workspace)."""
+    nb = L.lib().g2048_qnet_batch_workspace(int(n), int(dim_ff))
+    if nb == 0:
+        raise ValueError("g2048: qnet_forward_batch takes 1 .. %d boards (they are one sequence; a larger batch is refused, not "
+                         "truncated) and a dim_ff that is a multiple of 32 (got n = %d, dim_ff = %d)" % (L.QNET_BATCH_MAX, int(n), int(dim_ff)))
+    return nb
+
+
+def qnet_forward_batch(boards, plain, dim_ff, n_layers, q=None, workspace=None):
+    """The hybrid agent's Q-network on n boards as ONE call of the reference's module (g2048_qnet_forward_batch): the boards are
+    one sequence of n tokens that attend to each other, as in DQNAgent.train_step. plain: the PLAIN float32 parameter buffer
+    (qnet_plain_floats; qnet.flatten), read directly; f32 only. 2 + 5 n_layers launches on the current stream, no
+    synchronisation. workspace: a uint8 device tensor of at least qnet_batch_workspace_bytes(n, dim_ff) (allocated when None).
+    Returns q float32 (n,4)."""
+    L.require_device_tensor(boards, torch.uint8, (16,), "boards")
+    L.require_device_tensor(plain, torch.float32, None, "plain")
+    n, dev = boards.shape[0], boards.device
+    if plain.dim() != 1 or plain.numel() != qnet_plain_floats(dim_ff, n_layers):
+        raise ValueError("g2048: plain must be a flat float32 tensor of %d parameters" % qnet_plain_floats(dim_ff, n_layers))
+    q = _output(q, n, torch.float32, (4,), "q", dev)
+    if n == 0:
+        return q
+    nb = qnet_batch_workspace_bytes(n, dim_ff)
+    if workspace is None:
+        workspace = torch.empty(nb, dtype=torch.uint8, device=dev)
+    L.require_device_tensor(workspace, torch.uint8, None, "workspace")
+    if workspace.numel() < nb:
+        raise ValueError("g2048: workspace must hold at least %d bytes" % nb)
+    L.call(dev, L.lib().g2048_qnet_forward_batch, boards.data_ptr(), plain.data_ptr(), q.data_ptr(), n, int(dim_ff), int(n_layers),
+           workspace.data_ptr(), L.stream_ptr(dev))
+    return q
+
+
+def dqn_targets(q_online_next, q_target_next, shaped, dones, gamma=0.99, targets=None, next_actions=None):
+    """The Double-DQN targets of DQNAgent.train_step (agents/hybrid.py:1042-1046) in ONE launch (g2048_dqn_targets), given the
+    online and the target network's Q float32 (n,4) on the next states, shaped and dones float32 (n,): next_actions int64 (n,) =
+    the unmasked argmax of q_online_next (first maximum), targets float32 (n,) = shaped + (1 - dones) * gamma * q_target_next at
+    that action, in torch's order of operations, bit for bit. Returns (targets, next_actions)."""
+    L.require_device_tensor(q_online_next, torch.float32, (4,), "q_online_next")
+    L.require_device_tensor(q_target_next, torch.float32, (4,), "q_target_next")
+    L.require_device_tensor(shaped, torch.float32, (), "shaped")
+    L.require_device_tensor(dones, torch.float32, (), "dones")
+    n, dev = q_online_next.shape[0], q_online_next.device
+    if not (q_target_next.shape[0] == shaped.shape[0] == dones.shape[0] == n):
+        raise ValueError("g2048: the two Q, shaped and dones must have one row per transition")
+    targets = _output(targets, n, torch.float32, (), "targets", dev)
+    next_actions = _output(next_actions, n, torch.int64, (), "next_actions", dev)
+    L.call(dev, L.lib().g2048_dqn_targets, q_online_next.data_ptr(), q_target_next.data_ptr(), shaped.data_ptr(), dones.data_ptr(),
+           float(gamma), next_actions.data_ptr(), targets.data_ptr(), n, L.stream_ptr(dev))
+    return targets, next_actions
+
+
 def qnet_select_actions(q, boards, epsilon, seed=0x2048, step_index=0, id_base=0, actions=None, explored=None):
     """DQNAgent.select_action (hybrid.py:909-953, use_beam_search = False) for every board in ONE launch
     (g2048_qnet_select_actions), given q float32 (n,4) of qnet_forward: with probability epsilon (the coin is draw 1 of (seed,

@@ -32,8 +32,9 @@ _PADDING = {"conv1": 1, "conv2": 0}
 
 
 class Parsed:
-    """The module's parts: conv1, conv2, embedding, layers (TransformerEncoderLayer list), fc, dim_ff."""
-    __slots__ = ("conv1", "conv2", "embedding", "layers", "fc", "dim_ff")
+    """The module's parts: conv1, conv2, embedding, layers (TransformerEncoderLayer list), fc, dim_ff; nhead and batch_first are
+    tuples with one entry per layer (they matter to forward_batch only)."""
+    __slots__ = ("conv1", "conv2", "embedding", "layers", "fc", "dim_ff", "nhead", "batch_first")
     name = NAME
 
     def plain_tensors(p):
@@ -63,6 +64,8 @@ def parse(module):
     out = Parsed()
     E.claim_by_shape(NAME, module, enc, out, _ROLES, _CONVS, _check_conv)
     out.layers, out.dim_ff = E.checked_layers(NAME, enc, D_MODEL)
+    out.nhead = tuple(int(lay.self_attn.num_heads) for lay in out.layers)
+    out.batch_first = tuple(bool(lay.self_attn.batch_first) for lay in out.layers)
     return out
 
 
@@ -86,6 +89,51 @@ def forward_reference(p, boards, dtype=torch.float64, round_weights=None):
         a = lay.self_attn
         x = E.post_norm_tail(lay, x, x @ w(a.in_proj_weight)[2 * D_MODEL:].T + w(a.in_proj_bias)[2 * D_MODEL:], w)
     return x @ w(p.fc.weight).T + w(p.fc.bias)
+
+
+NHEAD = 8
+
+
+def check_batch_layers(p):
+    """forward_batch's constraints on the parsed module's layers: one sequence of tokens that attend to each other, 8 heads."""
+    for i, (h, bf) in enumerate(zip(p.nhead, p.batch_first)):
+        if bf:
+            E._refuse(NAME, "forward_batch: encoder layer %d has batch_first=True: the module's own batch call is then the per-board "
+                            "function, which __call__ computes" % i)
+        if h != NHEAD:
+            E._refuse(NAME, "forward_batch: encoder layer %d has nhead %d, expected %d (the attention kernel is built for 8 heads of 16)"
+                      % (i, h, NHEAD))
+
+
+@torch.no_grad()
+def forward_batch_reference(p, boards, dtype=torch.float64):
+    """Q (N,4) of the parsed network on uint8 (N,16) boards as ONE call of the module in eval mode, with plain torch ops in `dtype`
+    (any device): the N boards are one sequence of N tokens that attend to each other (the encoder layer is not batch_first and
+    sees x.unsqueeze(1)). Per layer the whole in_proj, 8 heads of 16, softmax(q.k / 4) over all N keys, P.V, then the post-norm
+    tail. The yardstick of g2048_qnet_forward_batch; at N = 1 it is forward_reference."""
+    check_batch_layers(p)
+    w = E.weight_caster(dtype)
+    n = boards.shape[0]
+    x = tile_values(boards, dtype).reshape(-1, 1, 4, 4)
+    x = torch.relu(F.conv2d(x, w(p.conv1.weight), w(p.conv1.bias), padding=1))
+    x = torch.relu(F.conv2d(x, w(p.conv2.weight), w(p.conv2.bias)))
+    x = x.reshape(n, -1) @ w(p.embedding.weight).T + w(p.embedding.bias)
+    for lay in p.layers:
+        a = lay.self_attn
+        q, k, v = (x @ w(a.in_proj_weight).T + w(a.in_proj_bias)).split(D_MODEL, dim=1)
+        head = D_MODEL // NHEAD
+        q, k, v = (t.reshape(n, NHEAD, head).transpose(0, 1) for t in (q, k, v))            # (heads, N, 16)
+        prob = torch.softmax(q @ k.transpose(1, 2) / (head ** 0.5), dim=-1)
+        x = E.post_norm_tail(lay, x, (prob @ v).transpose(0, 1).reshape(n, D_MODEL), w)
+    return x @ w(p.fc.weight).T + w(p.fc.bias)
+
+
+def _q_only(n, device):
+    return torch.empty((n, 4), dtype=torch.float32, device=device)
+
+
+def _targets(n, device):
+    return torch.empty(n, dtype=torch.float32, device=device), torch.empty(n, dtype=torch.int64, device=device)
 
 
 def _outputs(n, device):
@@ -126,6 +174,24 @@ class DeviceQNetwork(E.PackedNet):
         q, _ = self._out.get(self._out.rows(boards), _outputs)
         return ops.qnet_forward(boards, self.packed, self.dim_ff, self.n_layers, self.precision, q=q)
 
+    def forward_batch(self, boards):
+        """q float32 (N,4) of the module's own eval-mode BATCH call on uint8 (N,16) boards, as DQNAgent.train_step makes it
+        (hybrid.py:1038-1044): the N boards are one sequence of N tokens that attend to each other, so a row depends on every
+        board of the call (g2048_qnet_forward_batch; 2 + 5 n_layers launches, no synchronisation). 1 <= N <= 4096. The weights
+        are this network's plain buffer, so refresh() refreshes this path too. f32 only: the first layer's attention logits
+        reach 1e9 and bf16 logits would pick keys at random. The output buffer and the workspace are the network's (one of each
+        per (N, stream))."""
+        if self.precision != "f32":
+            raise ValueError("%s.forward_batch: precision 'bf16' is refused: the attention logits reach 1e9 on raw tile values, and "
+                             "bf16 logits would pick keys at random; build the network with precision='f32'" % NAME)
+        check_batch_layers(self.parsed)
+        n = self._out.rows(boards)
+        return ops.qnet_forward_batch(boards, self.plain, self.dim_ff, self.n_layers, q=self._out.get(n, _q_only),
+                                      workspace=self._out.get(n, self._batch_workspace))
+
+    def _batch_workspace(self, n, device):          # refuses n = 0 and n above the maximum
+        return torch.empty(ops.qnet_batch_workspace_bytes(n, self.dim_ff), dtype=torch.uint8, device=device)
+
     def act(self, boards, epsilon=0.0, seed=0x2048, step_index=0, id_base=0):
         """(actions, q). epsilon > 0 adds one g2048_qnet_select_actions launch: DQNAgent.select_action's epsilon-greedy with the
         reference's biased exploration (use_beam_search = False), the draws keyed by (seed, step_index, id_base + row)."""
@@ -156,3 +222,16 @@ class DeviceQNetwork(E.PackedNet):
         ops.qnet_beam_actions(q, boards, succ_q, beam_width, search_depth, beam_search_threshold, gamma, epsilon, seed, step_index,
                               id_base, actions=actions, planned=self._out.get(n, _planned), explored=self._out.get(n, _explored))
         return actions, q
+
+
+def dqn_targets(online, target, next_boards, shaped_rewards, dones, gamma=0.99):
+    """The no-gradient block of DQNAgent.train_step (agents/hybrid.py:1041-1046) on the device: (targets float32 (N,),
+    next_actions int64 (N,)) with next_actions = online.forward_batch(next_boards).argmax(1) (unmasked, first maximum), next_q
+    = target.forward_batch(next_boards) at those actions and targets = shaped_rewards + (1 - dones) * gamma * next_q. online,
+    target: DeviceQNetwork; next_boards uint8 (N,16); shaped_rewards, dones float32 (N,) as DeviceReplayBuffer.sample returns
+    them. Three launch groups on the current stream, no host synchronisation; the outputs are buffers of `online` (one pair per
+    (N, stream))."""
+    q_online = online.forward_batch(next_boards)
+    q_target = target.forward_batch(next_boards)
+    targets, next_actions = online._out.get(next_boards.shape[0], _targets)
+    return ops.dqn_targets(q_online, q_target, shaped_rewards, dones, gamma, targets=targets, next_actions=next_actions)

@@ -5,9 +5,11 @@
 
 A VecGame2048 batch is played by DeviceQNetwork.act(epsilon=...) (DQNAgent.select_action); every step of every env is pushed
 into a g2048.DeviceReplayBuffer (PrioritizedReplayBuffer.push); every --every steps a batch is sampled -- sample(), the float32
-tensors train_step builds and its reward shaping, one call, no host round trip --, Double-DQN targets are formed from two
-DeviceQNetwork forwards in plain torch ops (:1038-1046, with the per-board forward DeviceQNetwork computes), and the Huber
-errors go back as the new priorities (:1050, :1063-1064).
+tensors train_step builds and its reward shaping, one call, no host round trip --, the Double-DQN targets come from
+g2048.dqn_targets (:1041-1046: the online and the target network's batch forward on the next states, as the reference makes
+it: one sequence of tokens that attend to each other, then argmax, gather and the target in one launch), the current Q from
+online.forward_batch (:1038), and the Huber errors go back as the new priorities (:1050, :1063-1064). The batch forward is f32
+only, so --precision bf16 applies to the acting network alone.
 There is no optimiser here and no claim about learning: the gradient step stays stock PyTorch on the caller's side (DESIGN.md
 section 11). The script shows that the pieces fit and prints the rates.
 """
@@ -49,8 +51,9 @@ class HybridDQN(nn.Module):             # the reference's layout (agents/hybrid.
 
 dev, seed, gamma = torch.device("cuda"), 1, 0.99
 torch.manual_seed(0)
-online = g2048.DeviceQNetwork(HybridDQN(a.dim_ff).to(dev).eval(), precision=a.precision)
-target = g2048.DeviceQNetwork(HybridDQN(a.dim_ff).to(dev).eval(), precision=a.precision)
+online = g2048.DeviceQNetwork(HybridDQN(a.dim_ff).to(dev).eval())
+target = g2048.DeviceQNetwork(HybridDQN(a.dim_ff).to(dev).eval())
+actor = online if a.precision == "f32" else g2048.DeviceQNetwork(online.model, precision=a.precision)     # the same module
 env = g2048.VecGame2048(a.envs, device=dev, seed=seed)
 buf = g2048.DeviceReplayBuffer(a.capacity, alpha=0.6, device=dev, seed=seed)
 huber = nn.SmoothL1Loss(reduction="none")
@@ -58,7 +61,7 @@ huber = nn.SmoothL1Loss(reduction="none")
 
 def play(t):
     state = env.boards.clone()
-    actions, _ = online.act(state, epsilon=a.epsilon, seed=seed, step_index=t)
+    actions, _ = actor.act(state, epsilon=a.epsilon, seed=seed, step_index=t)
     nxt, reward, done, _ = env.step(actions)
     buf.push(state, actions, reward, nxt, env.flags)
     # finished games start over (the next state pushed above is the finished board, as the reference's loop stores it)
@@ -70,10 +73,9 @@ def learn(round_index):
     beta = 0.4 + 0.6 * min(round_index / 1000.0, 1.0)
     (states, actions, rewards, next_states, dones), indices, weights, shaped = buf.sample(a.batch, beta=beta)
     boards, next_boards = buf.boards(indices)              # the same batch as uint8 codes, the form DeviceQNetwork reads
-    q = online(boards).gather(1, actions.unsqueeze(1)).squeeze(1)
-    next_actions = online(next_boards).argmax(1, keepdim=True)
-    next_q = target(next_boards).gather(1, next_actions).squeeze(1)
-    td = huber(q, shaped + (1 - dones) * gamma * next_q)
+    targets, _ = g2048.dqn_targets(online, target, next_boards, shaped, dones, gamma)
+    q = online.forward_batch(boards).gather(1, actions.unsqueeze(1)).squeeze(1)
+    td = huber(q, targets)
     buf.update_priorities(indices, td)
     return (weights * td).mean()
 

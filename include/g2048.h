@@ -52,7 +52,8 @@ extern "C" {
                                       g2048_play_tpolicy_games / _workspace, g2048_qnet_packed_bytes / _pack / _forward,
                                       g2048_qnet_select_actions, g2048_play_qnet_games / _workspace, g2048_qnet_beam_actions / _expand,
                                       g2048_play_qnet_beam_games / _workspace, g2048_per_push / _sample / _sample_workspace /
-                                      _update_priorities / _update_workspace, g2048_dqn_shape_rewards)
+                                      _update_priorities / _update_workspace, g2048_dqn_shape_rewards, g2048_qnet_forward_batch,
+                                      g2048_qnet_batch_workspace, g2048_dqn_targets)
                                       4: round 5 (export table = this header + g2048_testing.h exactly: test / measurement hooks moved there,
                                       internal symbols hidden; g2048_replay_games also clamps a game's length to actions_stride)
                                       3: round 4 (actions_out of the g2048_play_games family, g2048_replay_games, g2048_env_step,
@@ -736,6 +737,40 @@ G2048_API int g2048_dqn_shape_rewards(const void *states, const void *next_state
                             void *stream);
 G2048_API int g2048_per_update_priorities(float *priorities, size_t capacity, size_t size, size_t head, const int64_t *indices,
                                 const float *td_errors, size_t batch, void *workspace, void *stream);
+
+/* ---- the Q-network's BATCH forward and train_step's Double-DQN targets (agents/hybrid.py:1038-1046) ----------------------
+ * train_step calls the module of g2048_qnet_forward on a whole batch. Its encoder layer is not batch_first and is fed
+ * x.unsqueeze(1), so the n boards are ONE sequence of n tokens that attend to each other: per layer the whole in_proj (Q, K, V),
+ * 8 heads of dimension 16, scores q.k / 4 over all n keys, softmax (f32, the row maximum subtracted), P.V, out_proj, residual,
+ * norm1, the feed-forward pair, norm2; then fc. Row i of the result depends on every board of the call; n = 1 is
+ * g2048_qnet_forward's function. Eval mode (no dropout), 8 heads only.
+ *
+ *   g2048_qnet_forward_batch   q_out (float32 n x 4) = the module's eval-mode output on the n boards as one call. WEIGHTS: the
+ *       PLAIN f32 buffer that g2048_qnet_pack takes as its input (layout above, 16-byte aligned), read directly: there is no
+ *       second packed blob, and whoever keeps that buffer current keeps this entry point current. f32 only (f32 MFMA, f32
+ *       softmax): the embedding is unnormalised and the inputs are tile values up to 131,072, the first layer's logits reach
+ *       1e9 and its softmax is nearly one-hot; bf16 logits would pick keys at random. The call is 2 + 5 n_layers launches on
+ *       `stream` (conv; embedding; per layer in_proj, attention, out_proj + norm1, linear1, linear2 + norm2, the last with fc),
+ *       the activations between them in `workspace`: g2048_qnet_batch_workspace(n, dim_ff) bytes of device memory, 16-byte
+ *       aligned, contents irrelevant before and meaningless after. Every output element is one wavefront's fixed-order
+ *       accumulation (no split-K, no atomics): two calls give the same bits. The order of the boards matters to the last bits
+ *       (the keys are summed in call order). 1 <= n <= G2048_QNET_BATCH_MAX; a larger n is refused, not truncated; n == 0
+ *       returns G2048_OK and does nothing. Nothing past row n of q_out is written.
+ *   g2048_qnet_batch_workspace   that size; 0 for n == 0, n > G2048_QNET_BATCH_MAX or a bad dim_ff. Non-decreasing in n.
+ *   g2048_dqn_targets   hybrid.py:1042-1046 in one launch, given q_online_next and q_target_next (float32 n x 4, 16-byte aligned: two
+ *       g2048_qnet_forward_batch calls on the next states), shaped and dones (float32 [n], as g2048_per_sample writes them):
+ *         next_actions_out[i] (int64) = argmax of q_online_next[i], UNMASKED (the reference applies no valid-move mask here), the
+ *           first maximum on ties;
+ *         targets_out[i] (float32) = shaped[i] + ((1 - dones[i]) * gamma) * q_target_next[i][next_actions_out[i]], each of the
+ *           three operations rounded to float32, no fused multiply-add: torch's `shaped + (1 - dones) * gamma * next_q` on the
+ *           same Q, bit for bit.
+ * Arguments are checked before any device call (null, misaligned, dim_ff not a multiple of 32, n_layers < 1, n too large). */
+#define G2048_QNET_BATCH_MAX 4096
+G2048_API size_t g2048_qnet_batch_workspace(size_t n, int dim_ff);
+G2048_API int g2048_qnet_forward_batch(const void *boards, const float *plain_f32, float *q_out, size_t n, int dim_ff, int n_layers,
+                             void *workspace, void *stream);
+G2048_API int g2048_dqn_targets(const float *q_online_next, const float *q_target_next, const float *shaped, const float *dones,
+                      float gamma, int64_t *next_actions_out, float *targets_out, size_t n, void *stream);
 #ifdef __cplusplus
 }
 #endif
