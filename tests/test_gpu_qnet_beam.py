@@ -2,29 +2,27 @@
 own DQNAgent.beam_search recorded (tests/golden/qnet_beam.npz), DeviceQNetwork.act_beam at search_depth 1 against the plain
 restatement (tests/qnet_beam_ref.py) on the device's own Q-values, the epsilon coin against g2048_qnet_select_actions, and
 g2048_play_qnet_beam_games against the unfused loop (every output, bit for bit) and, move by move, against the restatement.
-Everything is exact: the decision is integer and f64 arithmetic in a fixed order, and the forward's accuracy is pinned elsewhere
-(tests/test_gpu_qnet.py)."""
+The game tests play and compare through tests/play_harness.py, as the other three game kernels' tests do; the Q-network
+builder is tests/test_gpu_qnet_play.py's. Everything is exact: the decision is integer and f64 arithmetic in a fixed order,
+and the forward's accuracy is pinned elsewhere (tests/test_gpu_qnet.py)."""
+from functools import partial
+
 import numpy as np
 import pytest
 import torch
 
+import play_harness as H
 import qnet_beam_ref as R
 import qnet_weights as qw
 from conftest import load_golden
-from test_gpu_qnet_play import DEV, assert_same, device_net, play, replay
+from play_harness import DEV, g2048  # noqa: F401
+from test_gpu_qnet_play import device_net
 from test_policy_host import random_boards
 
 pytestmark = pytest.mark.gpu
 
 REFERENCE = (15, 30, 64)            # DQNAgent's beam_width, search_depth, beam_search_threshold
 EARLY = (4, 2, 8)                   # a narrow beam that plans from the first 8 on: other arguments, many planned moves
-
-
-@pytest.fixture(scope="module")
-def g2048():
-    import __graft_entry__ as ge
-    ge.ensure_built()
-    return ge.import_package()
 
 
 @pytest.fixture(scope="module")
@@ -149,21 +147,7 @@ def test_epsilon_is_select_actions_own(g2048, golden):
     assert bool((exploit != ops.qnet_select_actions(q, b, 0.0, seed, t, base)[0]).any())
 
 
-def play_beam(net, n, max_moves, epsilon, seed, beam, base=0, fused=True):
-    from g2048 import ops
-    from g2048.evaluate import _play_policy_stepwise, qnet_stepwise_act
-    from g2048.vec import VecGame2048
-    env = VecGame2048(n, device=torch.device(DEV), seed=seed, id_base=base)
-    start = env.boards.clone()
-    if fused:
-        r = ops.play_qnet_beam_games(env.boards, env.scores, net.packed, net.dim_ff, net.n_layers, net.precision, max_moves, epsilon, *beam,
-                                     seed, base, want_rewards=True, want_actions=True)
-    else:
-        act = qnet_stepwise_act(net.packed, net.dim_ff, net.n_layers, net.precision, n, torch.device(DEV), epsilon, seed, base, beam)
-        r = _play_policy_stepwise(env, net.packed, net.precision, max_moves, None, seed, base, act=act)
-    torch.cuda.synchronize()
-    r.update(boards=env.boards, scores=env.scores, start=start)
-    return r
+play, play_beam = partial(H.play, H.QNET), partial(H.play, H.QNET_BEAM)
 
 
 @pytest.mark.parametrize("network", ["fixture", "small"])
@@ -173,11 +157,10 @@ def test_fused_beam_games_equal_the_unfused_loop(g2048, epsilon, precision, netw
     net = device_net(network, precision)
     for n, cap, beam in ((300, 160, REFERENCE), (33, 400, REFERENCE), (77, 60, EARLY)):
         seed = 2000 + n + cap
-        a = play_beam(net, n, cap, epsilon, seed, beam, fused=False)
-        b = play_beam(net, n, cap, epsilon, seed, beam, fused=True)
-        assert_same(a, b, "epsilon %g %s %s n=%d cap=%d beam %s" % (epsilon, precision, network, n, cap, beam))
-        assert int(b["moves"].min()) >= 1 and bool((b["valid_moves"] + b["invalid_moves"] == b["moves"]).all())
-        assert bool((b["moves"] <= cap).all()) and bool(((b["moves"] == cap) | (b["alive"] == 0)).all())
+        a = play_beam(net, n, cap, (epsilon,) + beam, seed, fused=False)
+        b = play_beam(net, n, cap, (epsilon,) + beam, seed, fused=True)
+        H.assert_same(a, b, "epsilon %g %s %s n=%d cap=%d beam %s" % (epsilon, precision, network, n, cap, beam))
+        H.check_game_invariants(b, cap)
         assert int((b["milestone_move"][:, 0] >= 0).sum()) > 0 or beam is EARLY, "no game reached 64: the search never planned"
 
 
@@ -187,8 +170,8 @@ def test_recorded_beam_games_carry_the_restatements_actions(g2048, oracle, preci
     exploit action of a fresh forward on it."""
     net = device_net("fixture", precision)
     n, seed, cap = 64, 777, 250
-    r = play_beam(net, n, cap, 0.0, seed, beam)
-    bh, _, q, longest = replay(net, r, seed, True)
+    r = play_beam(net, n, cap, (0.0,) + beam, seed)
+    bh, _, q, longest = H.replay(H.QNET_BEAM, net, r, seed, True)
     moves, acts = r["moves"].cpu().numpy(), r["actions"].cpu().numpy()
     live = np.arange(longest)[None, :] < moves[:, None]
     pos = bh[:, :longest][live]
@@ -213,8 +196,8 @@ def test_games_without_the_search_are_what_they_were(g2048):
         net = device_net("fixture", precision)
         a = play(net, 300, 160, 0.05, 4321, fused=False)
         b = play(net, 300, 160, 0.05, 4321, fused=True)
-        assert_same(a, b, "no search, %s" % precision)
-        c = play_beam(net, 300, 160, 0.05, 4321, REFERENCE)
+        H.assert_same(a, b, "no search, %s" % precision)
+        c = play_beam(net, 300, 160, (0.05,) + REFERENCE, 4321)
         assert not torch.equal(b["actions"], c["actions"])
 
 
