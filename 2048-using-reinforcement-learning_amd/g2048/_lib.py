@@ -116,6 +116,8 @@ SIGNATURES = {
     "g2048_qnet_batch_workspace": (_sz, [_sz, _int]),
     "g2048_qnet_forward_batch": (_int, [_vp, _vp, _vp, _sz, _int, _int, _vp, _vp]),
     "g2048_dqn_targets": (_int, [_vp, _vp, _vp, _vp, C.c_float, _vp, _vp, _sz, _vp]),
+    "g2048_qnet_grad_workspace": (_sz, [_sz, _int, _int]),
+    "g2048_qnet_loss_grad": (_int, [_vp] * 5 + [_sz, _int, _int] + [_vp] * 6),
 }
 
 

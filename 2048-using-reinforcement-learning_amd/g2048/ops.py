@@ -590,6 +590,60 @@ def qnet_forward_batch(boards, plain, dim_ff, n_layers, q=None, workspace=None):
     return q
 
 
+def qnet_grad_workspace_bytes(n, dim_ff, n_layers):
+    """Bytes of the workspace qnet_loss_grad needs for n boards (g2048_qnet_grad_workspace)."""
+    nb = L.lib().g2048_qnet_grad_workspace(int(n), int(dim_ff), int(n_layers))
+    if nb == 0:
+        raise ValueError("g2048: qnet_loss_grad takes 1 .. %d boards (they are one sequence; a larger batch is refused, not "
+                         "truncated), a dim_ff that is a multiple of 32 and 1 .. 64 layers (got n = %d, dim_ff = %d, n_layers = %d)"
+                         % (L.QNET_BATCH_MAX, int(n), int(dim_ff), int(n_layers)))
+    return nb
+
+
+def qnet_loss_grad(boards, plain, actions, targets, weights, dim_ff, n_layers, grad=None, td=None, loss=None, q=None, workspace=None):
+    """The gradient half of DQNAgent.train_step (agents/hybrid.py:1038, :1049-1055) on the device (g2048_qnet_loss_grad): q =
+    the batch forward of qnet_forward_batch (the same bits), td = the Huber error of q[i, actions[i]] against targets[i], loss =
+    mean(weights * td) and grad = d loss / d parameter in the layout of `plain` (the LayerNorm-eps slots 0), overwritten, never
+    accumulated into. boards uint8 (n,16), actions int64 (n,), targets and weights float32 (n,), plain the PLAIN float32
+    parameter buffer. Eval mode (no dropout), f32 only. An action outside 0..3 is the caller's error (the kernel reads
+    actions & 3). No synchronisation. Returns (loss float32 (), td float32 (n,), q float32 (n,4), grad float32 (plain.numel(),))."""
+    L.require_device_tensor(boards, torch.uint8, (16,), "boards")
+    L.require_device_tensor(plain, torch.float32, None, "plain")
+    L.require_device_tensor(actions, torch.int64, (), "actions")
+    L.require_device_tensor(targets, torch.float32, (), "targets")
+    L.require_device_tensor(weights, torch.float32, (), "weights")
+    n, dev = boards.shape[0], boards.device
+    floats = qnet_plain_floats(dim_ff, n_layers)
+    if plain.dim() != 1 or plain.numel() != floats:
+        raise ValueError("g2048: plain must be a flat float32 tensor of %d parameters" % floats)
+    if not (actions.shape[0] == targets.shape[0] == weights.shape[0] == n):
+        raise ValueError("g2048: actions, targets and weights must have one entry per board")
+    if grad is None:
+        grad = torch.empty(floats, dtype=torch.float32, device=dev)
+    L.require_device_tensor(grad, torch.float32, None, "grad")
+    if grad.dim() != 1 or grad.numel() != floats:
+        raise ValueError("g2048: grad must be a flat float32 tensor of %d floats" % floats)
+    td = _output(td, n, torch.float32, (), "td", dev)
+    q = _output(q, n, torch.float32, (4,), "q", dev)
+    if loss is None:
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+    L.require_device_tensor(loss, torch.float32, None, "loss")
+    if loss.numel() != 1:
+        raise ValueError("g2048: loss must hold one float32")
+    if n == 0:
+        return loss, td, q, grad
+    nb = qnet_grad_workspace_bytes(n, dim_ff, n_layers)
+    if workspace is None:
+        workspace = torch.empty(nb, dtype=torch.uint8, device=dev)
+    L.require_device_tensor(workspace, torch.uint8, None, "workspace")
+    if workspace.numel() < nb:
+        raise ValueError("g2048: workspace must hold at least %d bytes" % nb)
+    L.call(dev, L.lib().g2048_qnet_loss_grad, boards.data_ptr(), plain.data_ptr(), actions.data_ptr(), targets.data_ptr(),
+           weights.data_ptr(), n, int(dim_ff), int(n_layers), grad.data_ptr(), td.data_ptr(), loss.data_ptr(), q.data_ptr(),
+           workspace.data_ptr(), L.stream_ptr(dev))
+    return loss, td, q, grad
+
+
 def dqn_targets(q_online_next, q_target_next, shaped, dones, gamma=0.99, targets=None, next_actions=None):
     """The Double-DQN targets of DQNAgent.train_step (agents/hybrid.py:1042-1046) in ONE launch (g2048_dqn_targets), given the
     online and the target network's Q float32 (n,4) on the next states, shaped and dones float32 (n,): next_actions int64 (n,) =

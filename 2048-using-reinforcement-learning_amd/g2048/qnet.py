@@ -128,8 +128,54 @@ def forward_batch_reference(p, boards, dtype=torch.float64):
     return x @ w(p.fc.weight).T + w(p.fc.bias)
 
 
+def _check_loss_inputs(n, actions, targets, weights):
+    for name, t, dtype in (("actions", actions, torch.int64), ("targets", targets, torch.float32), ("weights", weights, torch.float32)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("%s: %s must be a torch.Tensor" % (NAME, name))
+        if t.dtype != dtype:
+            raise TypeError("%s: %s must be %s (got %s)" % (NAME, name, dtype, t.dtype))
+        if tuple(t.shape) != (n,):
+            raise ValueError("%s: %s must have shape (%d,), one entry per board (got %s)" % (NAME, name, n, tuple(t.shape)))
+
+
+def loss_grad_reference(p, boards, actions, targets, weights, dtype=torch.float64):
+    """The gradient half of DQNAgent.train_step (hybrid.py:1038, :1049-1055) in eval mode with plain torch ops in `dtype`:
+    autograd over the ops of forward_batch_reference, the Huber error of q[i, actions[i]] against targets[i]
+    (nn.SmoothL1Loss(reduction='none'), beta 1) and loss = mean(weights * td). Returns (loss, td, q, grads): grads maps every
+    parameter of the parsed module to its gradient, in the plain layout's order. The yardstick of g2048_qnet_loss_grad; the
+    module's own .grad fields are not touched."""
+    check_batch_layers(p)
+    n = boards.shape[0]
+    _check_loss_inputs(n, actions, targets, weights)
+    params = [t for t in p.plain_tensors() if isinstance(t, torch.Tensor)]
+    leaf = {id(t): t.detach().to(dtype).requires_grad_(True) for t in params}
+    w = lambda t: leaf[id(t)]
+    with torch.enable_grad():
+        x = tile_values(boards, dtype).reshape(-1, 1, 4, 4)
+        x = torch.relu(F.conv2d(x, w(p.conv1.weight), w(p.conv1.bias), padding=1))
+        x = torch.relu(F.conv2d(x, w(p.conv2.weight), w(p.conv2.bias)))
+        x = x.reshape(n, -1) @ w(p.embedding.weight).T + w(p.embedding.bias)
+        for lay in p.layers:
+            a = lay.self_attn
+            q, k, v = (x @ w(a.in_proj_weight).T + w(a.in_proj_bias)).split(D_MODEL, dim=1)
+            head = D_MODEL // NHEAD
+            q, k, v = (t.reshape(n, NHEAD, head).transpose(0, 1) for t in (q, k, v))
+            prob = torch.softmax(q @ k.transpose(1, 2) / (head ** 0.5), dim=-1)
+            x = E.post_norm_tail(lay, x, (prob @ v).transpose(0, 1).reshape(n, D_MODEL), w)
+        qv = x @ w(p.fc.weight).T + w(p.fc.bias)
+        td = F.smooth_l1_loss(qv.gather(1, actions.unsqueeze(1)).squeeze(1), targets.to(dtype), reduction="none")
+        loss = (weights.to(dtype) * td).mean()
+        grads = torch.autograd.grad(loss, [leaf[id(t)] for t in params])
+    return loss.detach(), td.detach(), qv.detach(), dict(zip(params, grads))
+
+
 def _q_only(n, device):
     return torch.empty((n, 4), dtype=torch.float32, device=device)
+
+
+def _loss_outputs(n, device):       # loss, td, q
+    return (torch.empty((), dtype=torch.float32, device=device), torch.empty(n, dtype=torch.float32, device=device),
+            torch.empty((n, 4), dtype=torch.float32, device=device))
 
 
 def _targets(n, device):
@@ -191,6 +237,51 @@ class DeviceQNetwork(E.PackedNet):
 
     def _batch_workspace(self, n, device):          # refuses n = 0 and n above the maximum
         return torch.empty(ops.qnet_batch_workspace_bytes(n, self.dim_ff), dtype=torch.uint8, device=device)
+
+    def _grad_workspace(self, n, device):           # refuses n = 0 and n above the maximum
+        return torch.empty(ops.qnet_grad_workspace_bytes(n, self.dim_ff, self.n_layers), dtype=torch.uint8, device=device)
+
+    @property
+    def grad(self):
+        """The gradient buffer loss_and_grad fills: float32 of plain.numel(), laid out like `plain` (allocated on first use)."""
+        g = self.__dict__.get("_grad")
+        if g is None:
+            g = self.__dict__["_grad"] = torch.zeros_like(self.plain)
+        return g
+
+    def loss_and_grad(self, boards, actions, targets, weights):
+        """(loss float32 (), td_errors float32 (N,), q float32 (N,4)) of DQNAgent.train_step's gradient half (hybrid.py:1038,
+        :1049-1055) on uint8 (N,16) boards, int64 (N,) actions, float32 (N,) targets and weights: q = forward_batch(boards) (the
+        same bits), td = the Huber error of q[i, actions[i]] against targets[i], loss = mean(weights * td); net.grad is
+        OVERWRITTEN with d loss / d parameter in the layout of net.plain (g2048_qnet_loss_grad: the forward with its activations
+        kept, then the backward, one phase per launch; no host synchronisation). Eval mode: the reference's live dropout is left
+        out. f32 only, for forward_batch's reason. An action outside 0..3 is the caller's error (the kernel reads actions & 3).
+        The outputs and the workspace are the network's (one set per (N, stream))."""
+        if self.precision != "f32":
+            raise ValueError("%s.loss_and_grad: precision 'bf16' is refused: the attention logits reach 1e9 on raw tile values, and "
+                             "bf16 logits would pick keys at random; build the network with precision='f32'" % NAME)
+        check_batch_layers(self.parsed)
+        if not isinstance(boards, torch.Tensor) or boards.dim() != 2:
+            raise TypeError("%s.loss_and_grad: boards must be a uint8 (N,16) tensor" % NAME)
+        _check_loss_inputs(boards.shape[0], actions, targets, weights)
+        n = self._out.rows(boards)
+        loss, td, q = self._out.get(n, _loss_outputs)
+        ops.qnet_loss_grad(boards, self.plain, actions, targets, weights, self.dim_ff, self.n_layers, grad=self.grad, td=td, loss=loss,
+                           q=q, workspace=self._out.get(n, self._grad_workspace))
+        return loss, td, q
+
+    def attach_grads(self):
+        """Sets every parameter's .grad of the module to a view into net.grad, at the offsets of flatten: from then on
+        loss_and_grad, clip_grad_norm_(model.parameters(), ..), optimizer.step() and net.refresh() form a whole update with no
+        gradient copy. Keep the optimizer's zero_grad(set_to_none=False), or call attach_grads() again after it."""
+        o = 0
+        for t in self.parsed.plain_tensors():
+            if isinstance(t, torch.Tensor):
+                t.grad = self.grad[o:o + t.numel()].view(t.shape)
+                o += t.numel()
+            else:
+                o += 1
+        return self.grad
 
     def act(self, boards, epsilon=0.0, seed=0x2048, step_index=0, id_base=0):
         """(actions, q). epsilon > 0 adds one g2048_qnet_select_actions launch: DQNAgent.select_action's epsilon-greedy with the

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """The data side of the hybrid agent's training loop (reference agents/hybrid.py:955-1074) entirely on the GPU.
 
-    python examples/dqn_replay.py [--envs 4096] [--steps 200] [--capacity 200000] [--batch 256] [--every 4] [--dim-ff 2048]
+    python examples/dqn_replay.py [--envs 4096] [--steps 200] [--capacity 200000] [--batch 256] [--every 4] [--dim-ff 2048] [--train]
 
 A VecGame2048 batch is played by DeviceQNetwork.act(epsilon=...) (DQNAgent.select_action); every step of every env is pushed
 into a g2048.DeviceReplayBuffer (PrioritizedReplayBuffer.push); every --every steps a batch is sampled -- sample(), the float32
@@ -10,8 +10,13 @@ g2048.dqn_targets (:1041-1046: the online and the target network's batch forward
 it: one sequence of tokens that attend to each other, then argmax, gather and the target in one launch), the current Q from
 online.forward_batch (:1038), and the Huber errors go back as the new priorities (:1050, :1063-1064). The batch forward is f32
 only, so --precision bf16 applies to the acting network alone.
-There is no optimiser here and no claim about learning: the gradient step stays stock PyTorch on the caller's side (DESIGN.md
-section 11). The script shows that the pieces fit and prints the rates.
+Without --train there is no optimiser here and no claim about learning; the script shows that the pieces fit and prints the rates.
+
+--train runs the whole train_step (:955-1074): sample, targets, online.loss_and_grad (the forward with its activations kept, the
+prioritised Huber loss and the backward pass on the device, the gradients landing in the views attach_grads() gave the module's
+parameters), then stock torch for the elementwise rest -- clip_grad_norm_ at 10, AdamW(lr 1e-3, weight_decay 1e-4),
+CosineAnnealingLR --, update_priorities(indices, td + 1e-5), online.refresh(), and the target network synchronised every 250
+training steps. Eval mode throughout: the reference's live dropout is left out. Still no claim about learning curves.
 """
 import argparse
 import os
@@ -33,6 +38,7 @@ ap.add_argument("--every", type=int, default=4, help="env steps between two samp
 ap.add_argument("--epsilon", type=float, default=0.2)
 ap.add_argument("--dim-ff", type=int, default=2048)
 ap.add_argument("--precision", choices=("f32", "bf16"), default="f32")
+ap.add_argument("--train", action="store_true", help="the full train_step: loss_and_grad, clip, AdamW, cosine schedule, target sync")
 a = ap.parse_args()
 if a.envs > a.capacity:
     sys.exit("--envs must not exceed --capacity: a push holds one transition per env")
@@ -57,6 +63,11 @@ actor = online if a.precision == "f32" else g2048.DeviceQNetwork(online.model, p
 env = g2048.VecGame2048(a.envs, device=dev, seed=seed)
 buf = g2048.DeviceReplayBuffer(a.capacity, alpha=0.6, device=dev, seed=seed)
 huber = nn.SmoothL1Loss(reduction="none")
+TARGET_SYNC = 250
+if a.train:
+    online.attach_grads()              # every parameter's .grad is a view into online.grad from here on
+    optimizer = torch.optim.AdamW(online.model.parameters(), lr=1e-3, weight_decay=1e-4)
+    scheduler = torch.optim.lr_scheduler.CosineAnnealingLR(optimizer, T_max=10000, eta_min=1e-5)
 
 
 def play(t):
@@ -74,10 +85,27 @@ def learn(round_index):
     (states, actions, rewards, next_states, dones), indices, weights, shaped = buf.sample(a.batch, beta=beta)
     boards, next_boards = buf.boards(indices)              # the same batch as uint8 codes, the form DeviceQNetwork reads
     targets, _ = g2048.dqn_targets(online, target, next_boards, shaped, dones, gamma)
+    if a.train:
+        return train(round_index, boards, actions, targets, weights, indices)
     q = online.forward_batch(boards).gather(1, actions.unsqueeze(1)).squeeze(1)
     td = huber(q, targets)
     buf.update_priorities(indices, td)
     return (weights * td).mean()
+
+
+def train(round_index, boards, actions, targets, weights, indices):
+    loss, td, _ = online.loss_and_grad(boards, actions, targets, weights)             # :1038, :1049-1055; fills online.grad
+    torch.nn.utils.clip_grad_norm_(online.model.parameters(), max_norm=10.0)
+    optimizer.step()                                                                  # no zero_grad: the next call overwrites
+    scheduler.step()
+    buf.update_priorities(indices, td)                                                # adds the reference's 1e-5 itself
+    online.refresh()
+    if actor is not online:
+        actor.refresh()
+    if (round_index + 1) % TARGET_SYNC == 0:
+        target.model.load_state_dict(online.model.state_dict())
+        target.refresh()
+    return loss
 
 
 def run(steps, t0):

@@ -771,6 +771,37 @@ G2048_API int g2048_qnet_forward_batch(const void *boards, const float *plain_f3
                              void *workspace, void *stream);
 G2048_API int g2048_dqn_targets(const float *q_online_next, const float *q_target_next, const float *shaped, const float *dones,
                       float gamma, int64_t *next_actions_out, float *targets_out, size_t n, void *stream);
+
+/* ---- the Q-network's loss and gradient pass (agents/hybrid.py:1038, :1049-1055) ------------------------------------------
+ * The lines of train_step that need gradients, for the module of g2048_qnet_forward_batch (eval mode, f32, 8 heads, the n boards
+ * ONE sequence). The reference runs them with its dropout live; that is left out, as everywhere in this library.
+ *
+ *   g2048_qnet_loss_grad   given boards (uint8 n x 16), actions (int64 [n]), targets and weights (float32 [n]):
+ *         q_out (float32 n x 4)  = the bits of g2048_qnet_forward_batch on the same boards and weights;
+ *         d = q_out[i][actions[i]] - targets[i];
+ *         td_out[i] = 0.5 d^2 if |d| < 1 else |d| - 0.5       (nn.SmoothL1Loss(reduction='none'), beta 1);
+ *         loss_out[0] = mean(weights[i] * td_out[i]);
+ *         grad_out = d loss / d parameter for every parameter, g2048_qnet_plain_floats(dim_ff, n_layers) floats laid out exactly
+ *           like the plain buffer (so that parameter t's gradient is the slice at t's offset); the two LayerNorm-eps slots of
+ *           every layer are written as 0. grad_out is OVERWRITTEN, never accumulated into.
+ *       An action outside 0 .. 3 is the caller's error: the kernel uses actions[i] & 3, so nothing is read out of bounds.
+ *       The forward keeps its activations in `workspace` (g2048_qnet_grad_workspace(n, dim_ff, n_layers) bytes of device memory,
+ *       16-byte aligned, contents irrelevant before and meaningless after); the backward is one phase per launch on `stream`:
+ *       the head, LayerNorm backward, data-gradient and weight-gradient products on the f32 matrix cores, the attention backward
+ *       in two kernels (the probabilities recomputed from qkv and the forward's row maximum and sum), the convolutions' on the
+ *       VALU. No atomics, no split-K across blocks: every gradient element is one fixed-order accumulation, sums over the boards
+ *       per tile of 16 and then over the tiles in order, so two calls give the same bits. Nothing past row n of q_out and
+ *       td_out or past the stated sizes is written. 1 <= n <= G2048_QNET_BATCH_MAX (a larger n is refused, not truncated); n == 0
+ *       returns G2048_OK and does nothing. f32 only, for the reason g2048_qnet_forward_batch gives.
+ *       The first layer's softmax is nearly one-hot on raw tile values (logits up to 1e9): at n >= 2 on boards with large tiles
+ *       the gradients that pass through it (the convolutions', the embedding's, layer 0's in_proj) are not a float32 quantity in
+ *       ANY float32 implementation, stock torch included; they are computed all the same.
+ *   g2048_qnet_grad_workspace   that size; 0 for n == 0, n > G2048_QNET_BATCH_MAX, a bad dim_ff or n_layers. Non-decreasing in n.
+ * Arguments are checked before any device call (null, misaligned, dim_ff not a multiple of 32, n_layers < 1, n too large). */
+G2048_API size_t g2048_qnet_grad_workspace(size_t n, int dim_ff, int n_layers);
+G2048_API int g2048_qnet_loss_grad(const void *boards, const float *plain_f32, const int64_t *actions, const float *targets,
+                         const float *weights, size_t n, int dim_ff, int n_layers, float *grad_out, float *td_out, float *loss_out,
+                         float *q_out, void *workspace, void *stream);
 #ifdef __cplusplus
 }
 #endif
