@@ -364,3 +364,18 @@ def test_example_runs(g2048):
                          capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
     assert "transitions/s" in out.stdout and "sample + update rounds" in out.stdout
+
+
+def test_example_trains(g2048):
+    """--train is the only place outside tests/test_gpu_qnet_train_round.py where the whole train_step runs in sequence; dim_ff 160
+    runs a main group and a tail step of the products' contraction."""
+    import re
+    out = subprocess.run([sys.executable, os.path.join(REPO, "examples", "dqn_replay.py"), "--envs", "256", "--steps", "40", "--train",
+                          "--dim-ff", "160"], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
+    rounds = re.search(r"with (\d+) sample \+ update rounds", out.stdout)
+    loss = re.search(r"last weighted Huber loss (\S+)", out.stdout)
+    assert rounds and int(rounds.group(1)) == 10 and loss, out.stdout[-2000:]
+    assert np.isfinite(float(loss.group(1))) and float(loss.group(1)) >= 0, out.stdout[-2000:]
+    prio = re.search(r"priorities (\S+) \.\. (\S+),", out.stdout)
+    assert prio and all(np.isfinite(float(x)) and float(x) > 0 for x in prio.groups()), out.stdout[-2000:]

@@ -2,10 +2,16 @@
 n tokens that attend to each other) on the fixture's weights (tests/golden/qnet_batch.npz), random-init modules against their own
 CPU f64 batch forward at every tile edge with canaries, n = 1 against the per-board kernel, determinism bit for bit and a poisoned
 workspace, the proof that the other boards of a call are attended to, permutation, the Double-DQN targets against torch on the
-launch's own Q bit for bit and against the reference's f64 actions and targets, and refresh().
+launch's own Q bit for bit and against the reference's f64 actions and targets, and refresh(); a shape matrix (MATRIX) that runs the
+products' main-plus-tail loop in every combination, a third layer and the sizes up to G2048_QNET_BATCH_MAX, with the targets at the
+limit.
 
 Tolerance, the f32 convention of test_gpu_qnet.py: |q - q_f64| <= 8 x max|q_f32 - q_f64| of the case, q_f32 the stock module's
-float32 CPU batch call on the same boards and weights; the measured multiple is printed."""
+float32 CPU batch call on the same boards and weights; the measured multiple is printed. On the shape matrix's early boards
+(codes 0..3) the yardstick itself must lie in (0, 1e-5], so that a blown yardstick cannot hide a failure.
+
+Measured on an MI355X over the shape matrix: early boards 0.47 - 2.49 x (yardstick 5.5e-8 .. 5.1e-7), full boards 0.39 - 1.08 x
+(yardstick 1.5e-7 .. 5.3e-4); per shape in docs/LOG.md R19.1."""
 import functools
 
 import numpy as np
@@ -22,6 +28,15 @@ DEV = "cuda:0"
 F32_FACTOR = 8.0
 LEFT_OUT_CAP = 0.01
 RAGGED = (1, 15, 16, 17, 31, 33, 255, 257, 1025)            # every tile edge, and one size beyond any single LDS key tile
+# The shape matrix: (dim_ff, layers, sizes). The products walk their contraction in groups of 128 (eight accumulators) and finish
+# in steps of 32 into the first two: 96 = three tail steps alone, 160 = one group and one step (and a third layer), 224 = one group
+# and three steps, 416 = three groups and one step with the last block of the dim_ff / 64 grid half empty; 32 carries the sizes
+# around and at G2048_QNET_BATCH_MAX.
+MATRIX = ((96, 1, (1, 17, 33, 257)), (160, 3, (1, 17, 33, 257)), (224, 2, (1, 17, 33, 257)), (416, 1, (17, 33)), (32, 1, (2049, 4095, 4096)))
+MATRIX_CASES = [(ff, layers, n) for ff, layers, sizes in MATRIX for n in sizes]
+MATRIX_IDS = ["ff%d-L%d-n%d" % c for c in MATRIX_CASES]
+MODEL_SEED, BOARD_SEED = 2, 11
+FAIR_F32 = 1e-5                                             # above this stock float32 is no yardstick (test_qnet_grad_host.py)
 
 
 def check(q, want, f32_cpu, what):
@@ -65,6 +80,46 @@ def device_net(model):
     return DeviceQNetwork(copy.deepcopy(model).float().to(DEV))
 
 
+def matrix_boards(n, kind):
+    """'early': random_boards % 4, codes 0..3 (tiles <= 8), on which every quantity is a fair float32 quantity; 'full':
+    case_boards. Below 16 boards the last n of 16 (the recipes need a few rows; one board is then a random one, not the empty one)."""
+    from test_policy_host import random_boards
+    m = max(n, 16)
+    return ((random_boards(m, BOARD_SEED) % 4).astype(np.uint8) if kind == "early" else case_boards(m, BOARD_SEED))[m - n:]
+
+
+@functools.lru_cache(maxsize=None)
+def matrix_net(dim_ff, layers):
+    """The shape's random-init module on the device: one network for all its sizes, so its buffers are reused across them."""
+    return device_net(random_model(MODEL_SEED, dim_ff, layers))
+
+
+@functools.lru_cache(maxsize=None)
+def matrix_forward(dim_ff, layers, n, kind):
+    """(boards, the CPU f64 batch forward, the stock module's CPU f32 batch call) of a matrix case (shared, never modified)."""
+    from g2048 import qnet
+    model = random_model(MODEL_SEED, dim_ff, layers)
+    boards = matrix_boards(n, kind)
+    with torch.no_grad():
+        f32 = model(tiles(boards, torch.float32)).numpy().astype(np.float64)
+    return boards, qnet.forward_batch_reference(qnet.parse(model.double()), torch.from_numpy(boards)).numpy(), f32
+
+
+def forward_with_canaries(net, boards):
+    """ops.qnet_forward_batch into a q with 67 rows and a workspace with 4,096 bytes to spare, neither of which may be touched."""
+    from g2048 import ops
+    n = len(boards)
+    b = torch.from_numpy(boards).to(DEV)
+    nb = ops.qnet_batch_workspace_bytes(n, net.dim_ff)
+    q = torch.full((n + 67, 4), 7.0, device=DEV)
+    ws = torch.full((nb + 4096,), 0xA5, dtype=torch.uint8, device=DEV)
+    ops.qnet_forward_batch(b, net.plain, net.dim_ff, net.n_layers, q=q[:n], workspace=ws[:nb])
+    torch.cuda.synchronize()
+    assert torch.all(q[n:] == 7.0), "rows past n were written (n = %d)" % n
+    assert torch.all(ws[nb:] == 0xA5), "bytes past the workspace were written (n = %d)" % n
+    return q[:n].cpu().numpy()
+
+
 @functools.lru_cache(maxsize=None)
 def fixture_nets():
     g = load_golden("qnet_batch.npz")
@@ -84,20 +139,25 @@ def test_reference_class_on_the_fixture_weights():
 
 @pytest.mark.parametrize("shape", [(2, 64, 2), (12, 32, 1)], ids=["ff64-L2", "ff32-L1"])
 def test_ragged_sizes_and_canaries(shape):
-    from g2048 import ops
     model, boards, truth, f32 = random_case(*shape)
     net = device_net(model)
     assert (net.dim_ff, net.n_layers) == shape[1:]
     for n in RAGGED:
-        b = torch.from_numpy(boards[:n]).to(DEV)
-        nb = ops.qnet_batch_workspace_bytes(n, net.dim_ff)
-        q = torch.full((n + 67, 4), 7.0, device=DEV)
-        ws = torch.full((nb + 4096,), 0xA5, dtype=torch.uint8, device=DEV)
-        ops.qnet_forward_batch(b, net.plain, net.dim_ff, net.n_layers, q=q[:n], workspace=ws[:nb])
-        torch.cuda.synchronize()
-        assert torch.all(q[n:] == 7.0), "rows past n were written (n = %d)" % n
-        assert torch.all(ws[nb:] == 0xA5), "bytes past the workspace were written (n = %d)" % n
-        check(q[:n].cpu().numpy(), truth[n], f32[n], "dim_ff %d L %d n=%d" % (net.dim_ff, net.n_layers, n))
+        check(forward_with_canaries(net, boards[:n]), truth[n], f32[n], "dim_ff %d L %d n=%d" % (net.dim_ff, net.n_layers, n))
+
+
+@pytest.mark.parametrize("case", MATRIX_CASES, ids=MATRIX_IDS)
+def test_shape_matrix_with_canaries(case):
+    """Every combination of the products' main groups and tail steps, a third layer, and the sizes up to the stated maximum, on
+    early boards (the tight check: stock float32 must itself be within 1e-5 there) and on full boards."""
+    dim_ff, layers, n = case
+    net = matrix_net(dim_ff, layers)
+    assert (net.dim_ff, net.n_layers) == (dim_ff, layers)
+    for kind in ("early", "full"):
+        boards, truth, f32 = matrix_forward(dim_ff, layers, n, kind)
+        yard = np.abs(f32 - truth).max() / np.abs(truth).max()
+        assert kind == "full" or 0 < yard <= FAIR_F32, "stock float32 is no fair yardstick on this case: %.3g" % yard
+        check(forward_with_canaries(net, boards), truth, f32, "%s boards, dim_ff %d L %d n=%d" % (kind, dim_ff, layers, n))
 
 
 def test_one_board_is_the_per_board_function():
@@ -170,6 +230,27 @@ def test_dqn_targets_on_the_launchs_own_q():
     tt, aa = torch.full((n + 9,), 7.0, device=DEV), torch.full((n + 9,), 9, dtype=torch.int64, device=DEV)
     ops.dqn_targets(q_online, q_target, shaped, dones, 0.99, targets=tt[:n], next_actions=aa[:n])
     assert torch.all(tt[n:] == 7.0) and torch.all(aa[n:] == 9) and torch.equal(tt[:n], targets)
+
+
+def test_dqn_targets_at_the_batch_limit():
+    import g2048
+    from g2048 import ops
+    n = 4096
+    online, target = matrix_net(32, 1), device_net(random_model(MODEL_SEED + 1, 32, 1))
+    rng = np.random.default_rng(5)
+    b = torch.from_numpy(matrix_boards(n, "early")).to(DEV)
+    shaped = torch.from_numpy(rng.normal(4.0, 3.0, n).astype(np.float32)).to(DEV)
+    dones = torch.from_numpy((rng.random(n) < 0.1).astype(np.float32)).to(DEV)
+    targets, actions = g2048.dqn_targets(online, target, b, shaped, dones, gamma=0.99)
+    assert targets.shape == (n,) and actions.shape == (n,)
+    q_online, q_target = online.forward_batch(b), target.forward_batch(b)       # bit-repeatable: the Q the launch read
+    want, want_actions = torch_targets(q_online, q_target, shaped, dones, 0.99)
+    assert torch.equal(actions, want_actions) and torch.equal(targets, want), "n = 4096: not the torch expression on the launch's own Q"
+    assert torch.equal(targets[dones == 1], shaped[dones == 1]) and 0 < int(dones.sum()) < n
+    assert len(torch.unique(actions)) > 1 and not torch.equal(q_online, q_target)
+    tt, aa = torch.full((n + 9,), 7.0, device=DEV), torch.full((n + 9,), 9, dtype=torch.int64, device=DEV)
+    ops.dqn_targets(q_online, q_target, shaped, dones, 0.99, targets=tt[:n], next_actions=aa[:n])
+    assert torch.all(tt[n:] == 7.0) and torch.all(aa[n:] == 9) and torch.equal(tt[:n], want) and torch.equal(aa[:n], want_actions)
 
 
 def test_dqn_targets_against_the_reference():

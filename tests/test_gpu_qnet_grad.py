@@ -1,11 +1,19 @@
 """g2048_qnet_loss_grad on the MI355X: the loss and the gradients of every parameter against the stock module's float64 autograd
 through the lines of train_step (random-init modules at every tile edge, with canaries) and against the reference class's
 recorded gradients (tests/golden/qnet_grad.npz), q bit for bit against forward_batch, repeatability and a poisoned workspace, zero
-weights, a permuted batch, and attach_grads() with a stock optimiser.
+weights, a permuted batch, attach_grads() with a stock optimiser, and the shape matrix of test_gpu_qnet_batch.py (a main group
+followed by tail steps in the forward's products and in dX, a third layer, the sizes up to G2048_QNET_BATCH_MAX).
 
 Tolerance, the f32 convention of test_gpu_qnet_batch.py applied per case: for every checked tensor max|g - g64| / max|g64| <= 8 x
 the worst such ratio of the stock module's float32 CPU autograd over the checked tensors of the same case; loss and td are held
-to the same bound relative to their own maxima. The measured multiples are printed.
+to the same bound relative to their own maxima. The measured multiples are printed, and below them every checked tensor's error
+as a multiple of that tensor's OWN float32 error (not asserted: it shows how much slack the shared yardstick leaves). On the shape
+matrix's early boards the yardstick itself must lie in (0, 1e-5].
+
+Measured on an MI355X over the shape matrix (early boards): 0.49 - 2.14 x the case's yardstick, at most 5.67 x a tensor's own float32
+error (out_proj.weight at n = 4,096); dim_ff 160 with 3 layers on full boards 0.78 x (n = 1) and 0.47 x (n = 17). The yardstick at
+the batch limit sits just under the fairness bound: 5.6e-6 (n = 2,049), 9.6e-6 (4,095), 6.6e-6 (4,096), and it depends on the CPU's
+thread count (docs/LOG.md R19.1).
 
 Two kinds of case. On EARLY boards (codes 0..3, tiles <= 8) every parameter is checked. On FULL boards (tiles up to 131,072)
 layer 0's attention logits reach 1e9 and its softmax is nearly one-hot: at n >= 2 the gradients that pass through it (cnn.*,
@@ -21,7 +29,7 @@ import torch
 
 import qnet_grad_ref as R
 from conftest import load_golden
-from test_gpu_qnet_batch import RAGGED, case_boards, device_net
+from test_gpu_qnet_batch import FAIR_F32, MATRIX_CASES, MATRIX_IDS, MODEL_SEED, RAGGED, case_boards, device_net, matrix_boards, matrix_net
 from test_policy_host import random_boards
 from test_qnet_host import golden_model, random_model
 
@@ -51,6 +59,17 @@ def random_case(seed, dim_ff, layers, kind):
     return m32, boards, cases
 
 
+@functools.lru_cache(maxsize=None)
+def matrix_case(dim_ff, layers, n, kind):
+    """(boards, actions, targets, weights, the stock module's CPU float64 and float32 loss and gradients) of a case of the shape
+    matrix of test_gpu_qnet_batch.py (shared, never modified)."""
+    model = random_model(MODEL_SEED, dim_ff, layers)
+    boards = matrix_boards(n, kind)
+    m64, m32 = copy.deepcopy(model).double(), copy.deepcopy(model).float()
+    a, t, w = R.case_inputs(m64, boards)
+    return boards, a, t, w, R.stock_loss_grad(m64, boards, a, t, w), R.stock_loss_grad(m32, boards, a, t, w)
+
+
 def split(net, grad):
     slices, eps, total = R.plain_slices(net.parsed)
     g = grad.cpu().numpy().astype(np.float64)
@@ -70,6 +89,11 @@ def check(got, want, f32, every, what):
     print("%s: gradients %.3g of max|g| (tensor %d) = %.2f x the CPU-f32 error %.3g (bound %.0f x); loss %.2f x, td %.2f x%s"
           % (what, r[worst], worst, r[worst] / yard, yard, R.F32_FACTOR, e_loss / yard, e_td / yard,
              "" if every else "; upstream of the layer-0 softmax, not checked: %.3g (CPU f32: %.3g)" % (r[:first].max(), y[:first].max())))
+    # not asserted: how much slack the shared yardstick leaves. 0/0 (both exact) counts as 0, x/0 as inf
+    with np.errstate(divide="ignore", invalid="ignore"):
+        own = np.where(r[first:] > 0, r[first:] / y[first:], 0.0)
+    print("    every checked tensor against its OWN CPU-f32 error: max %.2f x (tensor %d); %s"
+          % (own.max(), first + int(np.argmax(own)), " ".join("%.2f" % v for v in own)))
     assert all(np.all(np.isfinite(g)) for g in got[3]) and np.isfinite(got[0]) and np.all(np.isfinite(got[1])), what
     assert yard > 0 and r[first:].max() <= bound, what
     assert e_loss <= bound and e_td <= bound, what
@@ -84,30 +108,77 @@ def run(net, boards, a, t, w):
     return float(loss), td.cpu().numpy().astype(np.float64), q.cpu().numpy().astype(np.float64), grads
 
 
+def run_with_canaries(net, boards, a, t, w):
+    """ops.qnet_loss_grad into outputs and a workspace with room to spare, none of which may be touched; q against forward_batch
+    bit for bit and the LayerNorm-eps slots: (loss, td, None, per-tensor gradients) as float64 NumPy."""
+    from g2048 import ops
+    n, floats = len(boards), net.plain.numel()
+    b, da, dt, dw = to_dev(boards, a, t, w)
+    nb = ops.qnet_grad_workspace_bytes(n, net.dim_ff, net.n_layers)
+    grad = torch.full((floats + 64,), 7.0, device=DEV)
+    td, q = torch.full((n + 67,), 7.0, device=DEV), torch.full((n + 67, 4), 7.0, device=DEV)
+    loss = torch.full((3,), 7.0, device=DEV)
+    ws = torch.full((nb + 4096,), 0xA5, dtype=torch.uint8, device=DEV)
+    ops.qnet_loss_grad(b, net.plain, da, dt, dw, net.dim_ff, net.n_layers, grad=grad[:floats], td=td[:n], loss=loss[:1].view(()), q=q[:n],
+                       workspace=ws[:nb])
+    torch.cuda.synchronize()
+    assert torch.all(grad[floats:] == 7.0) and torch.all(td[n:] == 7.0) and torch.all(q[n:] == 7.0) and torch.all(loss[1:] == 7.0), n
+    assert torch.all(ws[nb:] == 0xA5), "bytes past the workspace were written (n = %d)" % n
+    assert torch.equal(q[:n], net.forward_batch(b)), "q is not forward_batch's, bit for bit (n = %d)" % n
+    grads, eps = split(net, grad[:floats])
+    assert np.all(eps == 0) and len(eps) == 2 * net.n_layers, "the LayerNorm-eps slots of grad must be 0"
+    return float(loss[0]), td[:n].cpu().numpy().astype(np.float64), None, grads
+
+
+def check_repeatable(net, codes, a, t, w):
+    """Two calls give the same bits, and so does a call whose workspace and grad held NaN before it, twice."""
+    from g2048 import ops
+    n = len(codes)
+    args = to_dev(codes, a, t, w)
+    first = [x.clone() for x in net.loss_and_grad(*args)] + [net.grad.clone()]
+    again = list(net.loss_and_grad(*args)) + [net.grad]
+    assert all(torch.equal(x, y) for x, y in zip(first, again)), "two calls differ (n = %d)" % n
+    nb = ops.qnet_grad_workspace_bytes(n, net.dim_ff, net.n_layers)
+    ws = torch.full((nb // 4,), float("nan"), device=DEV)
+    grad = torch.full_like(net.grad, float("nan"))
+    out = ops.qnet_loss_grad(*args[:1], net.plain, *args[1:], net.dim_ff, net.n_layers, grad=grad, workspace=ws.view(torch.uint8))
+    assert all(torch.equal(x, y) for x, y in zip(first, out)), "NaN in grad or in the workspace before the call changes the result (n = %d)" % n
+    ws.fill_(float("nan"))
+    grad.fill_(float("nan"))
+    out = ops.qnet_loss_grad(*args[:1], net.plain, *args[1:], net.dim_ff, net.n_layers, grad=grad, workspace=ws.view(torch.uint8))
+    assert all(torch.equal(x, y) for x, y in zip(first, out))
+
+
 @pytest.mark.parametrize("shape", SHAPES, ids=IDS)
 def test_tile_edges_with_canaries(shape):
-    from g2048 import ops
     model, boards, cases = random_case(*shape, "early")
     net = device_net(model)
-    floats = net.plain.numel()
     for n in RAGGED:
         a, t, w, want, f32 = cases[n]
-        b, da, dt, dw = to_dev(boards[:n], a, t, w)
-        nb = ops.qnet_grad_workspace_bytes(n, net.dim_ff, net.n_layers)
-        grad = torch.full((floats + 64,), 7.0, device=DEV)
-        td, q = torch.full((n + 67,), 7.0, device=DEV), torch.full((n + 67, 4), 7.0, device=DEV)
-        loss = torch.full((3,), 7.0, device=DEV)
-        ws = torch.full((nb + 4096,), 0xA5, dtype=torch.uint8, device=DEV)
-        ops.qnet_loss_grad(b, net.plain, da, dt, dw, net.dim_ff, net.n_layers, grad=grad[:floats], td=td[:n], loss=loss[:1].view(()), q=q[:n],
-                           workspace=ws[:nb])
-        torch.cuda.synchronize()
-        assert torch.all(grad[floats:] == 7.0) and torch.all(td[n:] == 7.0) and torch.all(q[n:] == 7.0) and torch.all(loss[1:] == 7.0), n
-        assert torch.all(ws[nb:] == 0xA5), "bytes past the workspace were written (n = %d)" % n
-        assert torch.equal(q[:n], net.forward_batch(b)), "q is not forward_batch's, bit for bit (n = %d)" % n
-        grads, eps = split(net, grad[:floats])
-        assert np.all(eps == 0) and len(eps) == 2 * net.n_layers, "the LayerNorm-eps slots of grad must be 0"
-        got = (float(loss[0]), td[:n].cpu().numpy().astype(np.float64), None, grads)
+        got = run_with_canaries(net, boards[:n], a, t, w)
         check(got, want, f32, True, "early boards, dim_ff %d L %d n=%d" % (net.dim_ff, net.n_layers, n))
+
+
+@pytest.mark.parametrize("case", MATRIX_CASES, ids=MATRIX_IDS)
+def test_shape_matrix_with_canaries(case):
+    """The shape matrix of test_gpu_qnet_batch.py on early boards, every tensor checked: a main group followed by tail steps in
+    the forward's products and in dX, GradWorkspace::x(l), layer(l) and the backward's loop at a third layer, and the sizes up to
+    G2048_QNET_BATCH_MAX, where the call must also be repeatable and independent of what grad and the workspace held."""
+    dim_ff, layers, n = case
+    net = matrix_net(dim_ff, layers)
+    boards, a, t, w, want, f32 = matrix_case(dim_ff, layers, n, "early")
+    bound = check(run_with_canaries(net, boards, a, t, w), want, f32, True, "early boards, dim_ff %d L %d n=%d" % (dim_ff, layers, n))
+    assert 0 < bound / R.F32_FACTOR <= FAIR_F32, "stock float32 autograd is no fair yardstick on this case: %.3g" % (bound / R.F32_FACTOR)
+    if n == 4096:
+        check_repeatable(net, boards, a, t, w)
+
+
+@pytest.mark.parametrize("n", (1, 17))
+def test_full_boards_at_a_third_layer(n):
+    """test_full_boards' convention at dim_ff 160 with 3 layers: every tensor at n = 1, those downstream of layer 0's softmax at 17."""
+    net = matrix_net(160, 3)
+    boards, a, t, w, want, f32 = matrix_case(160, 3, n, "full")
+    check(run(net, boards, a, t, w), want, f32, n == 1, "full boards, dim_ff 160 L 3 n=%d" % n)
 
 
 @pytest.mark.parametrize("shape", SHAPES, ids=IDS)
@@ -156,27 +227,13 @@ def test_reference_class_gradients_on_the_fixture_weights():
 
 
 def test_repeatable_and_nothing_accumulates():
-    from g2048 import ops
     g, policy_boards, fixture = fixture_net()
     model, boards, cases = random_case(2, 64, 2, "early")
     small = device_net(model)
     a256, _, w256 = R.recipe(256)
     for net, codes, (a, t, w) in ((small, boards[:17], cases[17][:3]), (small, boards[:257], cases[257][:3]),
                                   (fixture, policy_boards[:256], (a256, g["full_256_targets"], w256))):
-        n = len(codes)
-        args = to_dev(codes, a, t, w)
-        first = [x.clone() for x in net.loss_and_grad(*args)] + [net.grad.clone()]
-        again = list(net.loss_and_grad(*args)) + [net.grad]
-        assert all(torch.equal(x, y) for x, y in zip(first, again)), "two calls differ (n = %d)" % n
-        nb = ops.qnet_grad_workspace_bytes(n, net.dim_ff, net.n_layers)
-        ws = torch.full((nb // 4,), float("nan"), device=DEV)
-        grad = torch.full_like(net.grad, float("nan"))
-        out = ops.qnet_loss_grad(*args[:1], net.plain, *args[1:], net.dim_ff, net.n_layers, grad=grad, workspace=ws.view(torch.uint8))
-        assert all(torch.equal(x, y) for x, y in zip(first, out)), "NaN in grad or in the workspace before the call changes the result (n = %d)" % n
-        ws.fill_(float("nan"))
-        grad.fill_(float("nan"))
-        out = ops.qnet_loss_grad(*args[:1], net.plain, *args[1:], net.dim_ff, net.n_layers, grad=grad, workspace=ws.view(torch.uint8))
-        assert all(torch.equal(x, y) for x, y in zip(first, out))
+        check_repeatable(net, codes, a, t, w)
 
 
 def test_zero_weights_and_a_permuted_batch():

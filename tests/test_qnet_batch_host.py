@@ -140,7 +140,7 @@ def test_batch_entry_points_validate_without_device():
     assert "#define G2048_QNET_BATCH_MAX 4096" in hdr
     # the workspace: x, qkv, att (128 + 384 + 128 floats a board) and the wider of the flattened conv output and the hidden layer,
     # boards rounded up to a tile of 16
-    for ff in (32, 64, 2048, 4096):
+    for ff in (32, 64, 2048, 4096, 96, 160, 224, 416):
         last = 0
         for n in (1, 15, 16, 17, 255, 256, 257, 1025, 4096):
             nb = L.g2048_qnet_batch_workspace(n, ff)

@@ -49,6 +49,16 @@ def test_loss_grad_reference_is_the_stock_modules_own_autograd():
                 print("%s, %s boards, n=%d: upstream %.3g, other %.3g of max|g|" % (name, kind, n, r[:R.N_UPSTREAM].max(), r[R.N_UPSTREAM:].max()))
                 assert (r if every else r[R.N_UPSTREAM:]).max() <= 1e-9 and np.all(np.isfinite(np.concatenate(g2)))
                 assert abs(loss2 - loss) <= 1e-12 * abs(loss) and np.abs(td2 - td).max() <= 1e-12 * td.max() and np.abs(q2 - q).max() <= 1e-9 * np.abs(q).max()
+    # three layers and a dim_ff with a main group and a tail step: the yardstick of the GPU tests' shape matrix
+    m = random_model(2, 160, 3).double()
+    codes = (random_boards(33, 11) % 4).astype(np.uint8)
+    a, t, w = R.case_inputs(m, codes)
+    loss, td, q, g = R.stock_loss_grad(m, codes, a, t, w)
+    loss2, td2, q2, g2 = reference(qnet.parse(m), codes, a, t, w)
+    r = R.ratios(g2, g)
+    print("random init, dim_ff 160, 3 layers, early boards, n=33: %.3g of max|g| over %d tensors" % (r.max(), len(r)))
+    assert len(g) == 6 + 3 * 12 + 2 and r.max() <= 1e-9 and np.all(np.isfinite(np.concatenate(g2)))
+    assert abs(loss2 - loss) <= 1e-12 * abs(loss) and np.abs(td2 - td).max() <= 1e-12 * td.max() and np.abs(q2 - q).max() <= 1e-9 * np.abs(q).max()
     assert all(x.grad is None for x in fixture_model.parameters()), "the yardstick must not touch the module's .grad"
 
 
@@ -167,7 +177,7 @@ def test_grad_entry_points_validate_without_device():
     hdr = open(__import__("os").path.join(__import__("conftest").REPO, "include", "g2048.h")).read()
     assert "g2048_qnet_loss_grad" in hdr and "g2048_qnet_grad_workspace" in hdr
     W = L.g2048_qnet_grad_workspace
-    for ff, layers in ((32, 1), (64, 2), (2048, 2), (4096, 3)):
+    for ff, layers in ((32, 1), (64, 2), (2048, 2), (4096, 3), (96, 1), (160, 3), (224, 2), (416, 1)):
         last = 0
         for n in (1, 15, 16, 17, 255, 256, 257, 1025, 4096):
             nb = W(n, ff, layers)
