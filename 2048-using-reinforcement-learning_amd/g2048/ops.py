@@ -644,6 +644,52 @@ def qnet_loss_grad(boards, plain, actions, targets, weights, dim_ff, n_layers, g
     return loss, td, q, grad
 
 
+def qnet_step_workspace_bytes(dim_ff, n_layers):
+    """Bytes of the workspace qnet_adamw_step needs (g2048_qnet_step_workspace): one float64 per partial sum of the norm."""
+    nb = L.lib().g2048_qnet_step_workspace(int(dim_ff), int(n_layers))
+    if nb == 0:
+        raise ValueError("g2048: qnet_adamw_step takes a dim_ff that is a multiple of 32 and 1 .. 64 layers (got dim_ff = %d, "
+                         "n_layers = %d)" % (int(dim_ff), int(n_layers)))
+    return nb
+
+
+def qnet_adamw_step(plain, grad, exp_avg, exp_avg_sq, dim_ff, n_layers, lr, step, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-4,
+                    max_norm=10.0, norm=None, workspace=None):
+    """clip_grad_norm_(max_norm) and AdamW.step() of DQNAgent.train_step (agents/hybrid.py:1057-1058) over the whole Q-network in
+    two launches (g2048_qnet_adamw_step): plain, grad, exp_avg and exp_avg_sq are flat float32 device tensors of
+    qnet_plain_floats(dim_ff, n_layers) in the plain layout, all updated IN PLACE (grad is left clipped); step >= 1 is the number
+    of this update; max_norm None means no clipping. The LayerNorm-eps slots keep their bits in all four. A gradient norm that
+    is not finite leaves all four untouched. No synchronisation. Returns the gradient norm before clipping, float32 ()."""
+    floats = qnet_plain_floats(dim_ff, n_layers)
+    buffers = (("plain", plain), ("grad", grad), ("exp_avg", exp_avg), ("exp_avg_sq", exp_avg_sq))
+    for name, t in buffers:                 # dtype and length of all four before any device: such a mistake reads the same everywhere
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("g2048: %s must be a torch.Tensor" % name)
+        if t.dtype != torch.float32 or t.dim() != 1 or t.numel() != floats:
+            raise (TypeError if t.dtype != torch.float32 else ValueError)(
+                "g2048: %s must be a flat float32 tensor of %d floats (got %s %s)" % (name, floats, t.dtype, tuple(t.shape)))
+    for name, t in buffers:
+        L.require_device_tensor(t, torch.float32, None, name)
+        if t.device != plain.device:
+            raise ValueError("g2048: %s on %s, plain on %s" % (name, t.device, plain.device))
+    dev = plain.device
+    if norm is None:
+        norm = torch.empty((), dtype=torch.float32, device=dev)
+    L.require_device_tensor(norm, torch.float32, None, "norm")
+    if norm.numel() != 1:
+        raise ValueError("g2048: norm must hold one float32")
+    nb = qnet_step_workspace_bytes(dim_ff, n_layers)
+    if workspace is None:
+        workspace = torch.empty(nb, dtype=torch.uint8, device=dev)
+    L.require_device_tensor(workspace, torch.uint8, None, "workspace")
+    if workspace.numel() < nb:
+        raise ValueError("g2048: workspace must hold at least %d bytes" % nb)
+    L.call(dev, L.lib().g2048_qnet_adamw_step, plain.data_ptr(), grad.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(),
+           int(dim_ff), int(n_layers), float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay),
+           float("inf") if max_norm is None else float(max_norm), int(step), norm.data_ptr(), workspace.data_ptr(), L.stream_ptr(dev))
+    return norm
+
+
 def dqn_targets(q_online_next, q_target_next, shaped, dones, gamma=0.99, targets=None, next_actions=None):
     """The Double-DQN targets of DQNAgent.train_step (agents/hybrid.py:1042-1046) in ONE launch (g2048_dqn_targets), given the
     online and the target network's Q float32 (n,4) on the next states, shaped and dones float32 (n,): next_actions int64 (n,) =

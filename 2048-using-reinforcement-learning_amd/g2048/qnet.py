@@ -169,6 +169,34 @@ def loss_grad_reference(p, boards, actions, targets, weights, dtype=torch.float6
     return loss.detach(), td.detach(), qv.detach(), dict(zip(params, grads))
 
 
+@torch.no_grad()
+def adamw_step_reference(plain, grad, exp_avg, exp_avg_sq, eps_at, lr, step, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-4,
+                         max_norm=10.0, dtype=torch.float64):
+    """clip_grad_norm_(max_norm) followed by AdamW.step() number `step` (>= 1) on flat buffers in the plain layout, with plain
+    torch ops in `dtype` (any device): the yardstick of g2048_qnet_adamw_step. With norm = ||grad|| (summed in float64, then
+    rounded to `dtype`) and c = min(1, max_norm / (norm + 1e-6)) (max_norm None: no clipping),
+        g = grad c;  p = plain (1 - lr wd);  m = m + (g - m)(1 - beta1);  v = v beta2 + (g g)(1 - beta2);
+        p = p - (lr / bc1) (m / (sqrt(v) / sqrt(bc2) + eps)),  bc1 = 1 - beta1^step, bc2 = 1 - beta2^step,
+    the scalars formed in Python floats as torch's AdamW forms them. eps_at: the offsets of the LayerNorm-eps slots, which are
+    settings and keep their values in all four buffers. A norm that is not finite changes nothing. Returns new (plain, grad,
+    exp_avg, exp_avg_sq, norm) in `dtype`; the arguments are not modified."""
+    p0, g0, m0, v0 = (t.detach().to(dtype) for t in (plain, grad, exp_avg, exp_avg_sq))
+    norm = torch.linalg.vector_norm(g0, dtype=torch.float64).to(dtype)         # summed in float64 whatever the dtype, as the kernel sums it
+    if not bool(torch.isfinite(norm)):
+        return p0.clone(), g0.clone(), m0.clone(), v0.clone(), norm
+    beta1, beta2 = betas
+    c = torch.clamp((norm + 1e-6).reciprocal() * (float("inf") if max_norm is None else max_norm), max=1.0)      # torch's max_norm / tensor
+    g = g0 * c
+    p = p0 * (1 - lr * weight_decay)
+    m = m0 + (g - m0) * (1 - beta1)
+    v = v0 * beta2 + (g * g) * (1 - beta2)
+    p = p - (lr / (1 - beta1 ** step)) * (m / (v.sqrt() / (1 - beta2 ** step) ** 0.5 + eps))
+    at = torch.as_tensor(list(eps_at), dtype=torch.int64, device=p.device)
+    for new, old in ((p, p0), (g, g0), (m, m0), (v, v0)):
+        new[at] = old[at]
+    return p, g, m, v, norm
+
+
 def _q_only(n, device):
     return torch.empty((n, 4), dtype=torch.float32, device=device)
 
@@ -184,6 +212,10 @@ def _targets(n, device):
 
 def _outputs(n, device):
     return torch.empty((n, 4), dtype=torch.float32, device=device), torch.empty(n, dtype=torch.uint8, device=device)
+
+
+def _norm_out(n, device):         # the gradient norm of adamw_step
+    return torch.empty((), dtype=torch.float32, device=device)
 
 
 def _explored(n, device):
@@ -211,7 +243,9 @@ class DeviceQNetwork(E.PackedNet):
     precision: "f32" (exact f32 MFMA, the parity path) or "bf16" (bf16 weights and matmul inputs, f32 accumulation, biases,
     LayerNorm and residual adds).
     refresh() re-flattens and re-packs the weights IN PLACE on the current stream (call it after an optimizer step; the module
-    must be back in eval mode)."""
+    must be back in eval mode); after attach_params() the module IS the plain buffer and refresh() only packs.
+    The learner's tail on the device: adamw_step(lr) (gradient clipping and AdamW over net.plain from net.grad) and
+    sync_from(other) (the target-network update)."""
 
     name, parse = NAME, staticmethod(parse)
     plain_floats, packed_bytes, pack = map(staticmethod, (ops.qnet_plain_floats, ops.qnet_packed_bytes, ops.qnet_pack))
@@ -283,6 +317,110 @@ class DeviceQNetwork(E.PackedNet):
                 o += 1
         return self.grad
 
+    def _step_workspace(self, n, device):
+        return torch.empty(ops.qnet_step_workspace_bytes(self.dim_ff, self.n_layers), dtype=torch.uint8, device=device)
+
+    def _moment(self, key):
+        t = self.__dict__.get(key)
+        if t is None:
+            t = self.__dict__[key] = torch.zeros_like(self.plain)
+        return t
+
+    @property
+    def exp_avg(self):
+        """AdamW's first moment of adamw_step: float32 of plain.numel(), laid out like `plain` (zeros, allocated on first use)."""
+        return self._moment("_exp_avg")
+
+    @property
+    def exp_avg_sq(self):
+        """AdamW's second moment of adamw_step, like exp_avg."""
+        return self._moment("_exp_avg_sq")
+
+    opt_step = 0            # the number of adamw_step calls so far
+    _attached = None        # attach_params(): (parameter, offset in floats) of the first and the last parameter
+
+    @property
+    def params_attached(self):
+        """True while the module's parameters are the views attach_params() made (the first and the last are looked at)."""
+        if self._attached is None:
+            return False
+        base = self.plain.data_ptr()
+        return all(t.data_ptr() == base + 4 * o for t, o in self._attached)
+
+    @torch.no_grad()
+    def attach_params(self):
+        """Rebinds the storage of every parameter of net.model to a view into net.plain, at the offsets of flatten (the
+        counterpart of attach_grads): from then on the module IS the plain buffer. load_state_dict and an optimizer write
+        through, adamw_step and sync_from need no copy back into the module, and refresh() skips the re-flatten and only
+        packs. The parameters' current values are kept. model.to(...), .float() or anything else that gives the parameters
+        new storage undoes the attachment (refresh() then re-flattens again, as before); call attach_params() again after
+        it. Returns net.plain."""
+        flatten(self.parsed, self.plain)
+        pairs, o = [], 0
+        for t in self.parsed.plain_tensors():
+            if isinstance(t, torch.Tensor):
+                t.data = self.plain[o:o + t.numel()].view(t.shape)
+                pairs.append((t, o))
+                o += t.numel()
+            else:
+                o += 1
+        self._attached = (pairs[0], pairs[-1])
+        return self.plain
+
+    def refresh(self):
+        if not self.params_attached:
+            return super().refresh()
+        if any(m.training for m in self.model.modules()):
+            raise ValueError("%s.refresh: %s is in training mode; call .eval() first" % (self.name, type(self.model).__name__))
+        self.pack(self.plain, self.dim_ff, self.n_layers, self.precision, out=self.packed)
+
+    def _plain_changed(self):
+        """After net.plain was written on the device: the packed blob, and the module unless it is the plain buffer."""
+        self.pack(self.plain, self.dim_ff, self.n_layers, self.precision, out=self.packed)
+        if not self.params_attached:
+            unflatten(self.parsed, self.plain)
+
+    def adamw_step(self, lr, max_norm=10.0, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-4, step=None):
+        """clip_grad_norm_(max_norm) and AdamW.step() of DQNAgent.train_step (hybrid.py:1057-1058) on the device, after
+        loss_and_grad: net.plain is updated IN PLACE from net.grad (left clipped, as clip_grad_norm_ leaves it), the moments are
+        net.exp_avg and net.exp_avg_sq (g2048_qnet_adamw_step: two launches), then net.packed is packed again, and the module's
+        parameters are loaded from net.plain unless attach_params() made them views of it: afterwards the module equals
+        net.plain bit for bit either way. Returns the gradient norm before clipping as a float32 () tensor (the network's, one
+        per stream), without synchronising. max_norm None: no clipping. lr is this update's learning rate (g2048.cosine_lr).
+        step, the update's number in AdamW's bias correction, defaults to net.opt_step + 1; net.opt_step counts the CALLS: a
+        gradient with an inf or a NaN leaves weights, gradient and moments untouched (the returned norm is then not finite),
+        and that skipped call still counts, because the host never learns of it. f32 only. The LayerNorm-eps slots are
+        settings and are not updated."""
+        if self.precision != "f32":
+            raise ValueError("%s.adamw_step: precision 'bf16' is refused: loss_and_grad is f32 only; build the network with "
+                             "precision='f32'" % NAME)
+        step = self.opt_step + 1 if step is None else int(step)
+        norm = ops.qnet_adamw_step(self.plain, self.grad, self.exp_avg, self.exp_avg_sq, self.dim_ff, self.n_layers, lr, step, betas=betas,
+                                   eps=eps, weight_decay=weight_decay, max_norm=max_norm, norm=self._out.get(0, _norm_out),
+                                   workspace=self._out.get(0, self._step_workspace))
+        self.opt_step += 1
+        self._plain_changed()
+        return norm
+
+    def sync_from(self, other):
+        """The target-network update (DQNAgent.update_target_model, hybrid.py:811, :1073) without a state_dict round: ONE device
+        copy of other.plain into net.plain, net.packed packed again at this network's own precision, and the module's
+        parameters loaded from net.plain unless attach_params() made them views of it. Raises ValueError when dim_ff,
+        n_layers, the LayerNorm eps or the device differ."""
+        if not isinstance(other, DeviceQNetwork):
+            raise TypeError("%s.sync_from: expected a %s, got %s" % (NAME, NAME, type(other).__name__))
+        if (other.dim_ff, other.n_layers) != (self.dim_ff, self.n_layers):
+            raise ValueError("%s.sync_from: the other network has dim_ff %d and %d layers, this one dim_ff %d and %d layers"
+                             % (NAME, other.dim_ff, other.n_layers, self.dim_ff, self.n_layers))
+        if other.device != self.device:
+            raise ValueError("%s.sync_from: the other network is on %s, this one on %s" % (NAME, other.device, self.device))
+        mine, theirs = ([t for t in n.parsed.plain_tensors() if not isinstance(t, torch.Tensor)] for n in (self, other))
+        if mine != theirs:
+            raise ValueError("%s.sync_from: the two modules' LayerNorm eps differ (%s, %s): they are settings, not weights" % (NAME, theirs, mine))
+        self.plain.copy_(other.plain)
+        self._plain_changed()
+        return self
+
     def act(self, boards, epsilon=0.0, seed=0x2048, step_index=0, id_base=0):
         """(actions, q). epsilon > 0 adds one g2048_qnet_select_actions launch: DQNAgent.select_action's epsilon-greedy with the
         reference's biased exploration (use_beam_search = False), the draws keyed by (seed, step_index, id_base + row)."""
@@ -326,3 +464,19 @@ def dqn_targets(online, target, next_boards, shaped_rewards, dones, gamma=0.99):
     q_target = target.forward_batch(next_boards)
     targets, next_actions = online._out.get(next_boards.shape[0], _targets)
     return ops.dqn_targets(q_online, q_target, shaped_rewards, dones, gamma, targets=targets, next_actions=next_actions)
+
+
+def cosine_lr(t, base_lr=1e-3, t_max=150000, eta_min=1e-4):
+    """The learning rate of torch's CosineAnnealingLR(T_max=t_max, eta_min=eta_min) over an optimizer of lr base_lr after t
+    scheduler.step() calls, 0 <= t <= t_max, in closed form (the defaults are DQNAgent's: hybrid.py:782-783). Pure Python."""
+    import math
+    if not 0 <= t <= t_max:
+        raise ValueError("g2048: cosine_lr is defined for 0 <= t <= t_max (got t = %s, t_max = %s)" % (t, t_max))
+    return eta_min + (base_lr - eta_min) * (1.0 + math.cos(math.pi * t / t_max)) / 2.0
+
+
+def dqn_epsilon(step_counter, start=1.0, end=0.001, decay_steps=150000):
+    """DQNAgent's exploration rate after step_counter train_step calls (hybrid.py:1068-1070): progress = min(step_counter /
+    decay_steps, 1), epsilon = max(end, start - (start - end) * progress ** 0.6). Pure Python."""
+    progress = min(step_counter / decay_steps, 1.0)
+    return max(end, start - (start - end) * (progress ** 0.6))

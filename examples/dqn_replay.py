@@ -2,6 +2,7 @@
 """The data side of the hybrid agent's training loop (reference agents/hybrid.py:955-1074) entirely on the GPU.
 
     python examples/dqn_replay.py [--envs 4096] [--steps 200] [--capacity 200000] [--batch 256] [--every 4] [--dim-ff 2048] [--train]
+                                  [--device-step]
 
 A VecGame2048 batch is played by DeviceQNetwork.act(epsilon=...) (DQNAgent.select_action); every step of every env is pushed
 into a g2048.DeviceReplayBuffer (PrioritizedReplayBuffer.push); every --every steps a batch is sampled -- sample(), the float32
@@ -17,6 +18,10 @@ prioritised Huber loss and the backward pass on the device, the gradients landin
 parameters), then stock torch for the elementwise rest -- clip_grad_norm_ at 10, AdamW(lr 1e-3, weight_decay 1e-4),
 CosineAnnealingLR --, update_priorities(indices, td + 1e-5), online.refresh(), and the target network synchronised every 250
 training steps. Eval mode throughout: the reference's live dropout is left out. Still no claim about learning curves.
+
+--train --device-step keeps that tail on the device too: attach_params() makes both modules views of their plain buffers,
+online.adamw_step(g2048.cosine_lr(round)) is the clipping, the AdamW update and the re-pack in two launches plus the pack, and
+target.sync_from(online) is the target update in one copy; the last gradient norm is printed at the end.
 """
 import argparse
 import os
@@ -39,7 +44,10 @@ ap.add_argument("--epsilon", type=float, default=0.2)
 ap.add_argument("--dim-ff", type=int, default=2048)
 ap.add_argument("--precision", choices=("f32", "bf16"), default="f32")
 ap.add_argument("--train", action="store_true", help="the full train_step: loss_and_grad, clip, AdamW, cosine schedule, target sync")
+ap.add_argument("--device-step", action="store_true", help="with --train: clipping, AdamW and the target sync on the device (adamw_step, sync_from)")
 a = ap.parse_args()
+if a.device_step and not a.train:
+    sys.exit("--device-step needs --train")
 if a.envs > a.capacity:
     sys.exit("--envs must not exceed --capacity: a push holds one transition per env")
 
@@ -64,7 +72,11 @@ env = g2048.VecGame2048(a.envs, device=dev, seed=seed)
 buf = g2048.DeviceReplayBuffer(a.capacity, alpha=0.6, device=dev, seed=seed)
 huber = nn.SmoothL1Loss(reduction="none")
 TARGET_SYNC = 250
-if a.train:
+last_norm = None
+if a.device_step:
+    online.attach_params()             # both modules are their plain buffers from here on
+    target.attach_params()
+elif a.train:
     online.attach_grads()              # every parameter's .grad is a view into online.grad from here on
     optimizer = torch.optim.AdamW(online.model.parameters(), lr=1e-3, weight_decay=1e-4)
     scheduler = torch.optim.lr_scheduler.CosineAnnealingLR(optimizer, T_max=10000, eta_min=1e-5)
@@ -95,6 +107,8 @@ def learn(round_index):
 
 def train(round_index, boards, actions, targets, weights, indices):
     loss, td, _ = online.loss_and_grad(boards, actions, targets, weights)             # :1038, :1049-1055; fills online.grad
+    if a.device_step:
+        return device_step(round_index, loss, td, indices)
     torch.nn.utils.clip_grad_norm_(online.model.parameters(), max_norm=10.0)
     optimizer.step()                                                                  # no zero_grad: the next call overwrites
     scheduler.step()
@@ -105,6 +119,17 @@ def train(round_index, boards, actions, targets, weights, indices):
     if (round_index + 1) % TARGET_SYNC == 0:
         target.model.load_state_dict(online.model.state_dict())
         target.refresh()
+    return loss
+
+
+def device_step(round_index, loss, td, indices):
+    global last_norm
+    last_norm = online.adamw_step(g2048.cosine_lr(min(round_index, 10000), t_max=10000, eta_min=1e-5), max_norm=10.0)   # the schedule above
+    buf.update_priorities(indices, td)
+    if actor is not online:
+        actor.refresh()
+    if (round_index + 1) % TARGET_SYNC == 0:
+        target.sync_from(online)
     return loss
 
 
@@ -130,3 +155,5 @@ print("%d envs x %d steps: %d transitions pushed in %.3f s = %.3g transitions/s,
 prio = buf.logical_priorities()
 print("buffer: %d of %d entries, priorities %.3g .. %.3g, last weighted Huber loss %s"
       % (len(buf), a.capacity, float(prio.min()), float(prio.max()), "%.4g" % float(loss) if loss is not None else "none"))
+if last_norm is not None:
+    print("device step: %d updates, last gradient norm before clipping %.4g" % (online.opt_step, float(last_norm)))

@@ -53,7 +53,8 @@ extern "C" {
                                       g2048_qnet_select_actions, g2048_play_qnet_games / _workspace, g2048_qnet_beam_actions / _expand,
                                       g2048_play_qnet_beam_games / _workspace, g2048_per_push / _sample / _sample_workspace /
                                       _update_priorities / _update_workspace, g2048_dqn_shape_rewards, g2048_qnet_forward_batch,
-                                      g2048_qnet_batch_workspace, g2048_dqn_targets)
+                                      g2048_qnet_batch_workspace, g2048_dqn_targets, g2048_qnet_loss_grad / _grad_workspace,
+                                      g2048_qnet_adamw_step / _step_workspace)
                                       4: round 5 (export table = this header + g2048_testing.h exactly: test / measurement hooks moved there,
                                       internal symbols hidden; g2048_replay_games also clamps a game's length to actions_stride)
                                       3: round 4 (actions_out of the g2048_play_games family, g2048_replay_games, g2048_env_step,
@@ -802,6 +803,46 @@ G2048_API size_t g2048_qnet_grad_workspace(size_t n, int dim_ff, int n_layers);
 G2048_API int g2048_qnet_loss_grad(const void *boards, const float *plain_f32, const int64_t *actions, const float *targets,
                          const float *weights, size_t n, int dim_ff, int n_layers, float *grad_out, float *td_out, float *loss_out,
                          float *q_out, void *workspace, void *stream);
+/* ---- the Q-network's gradient clipping and AdamW update (agents/hybrid.py:1057-1058) ---------------------------------------
+ * clip_grad_norm_(parameters, max_norm) and AdamW.step() of train_step over the whole network at once: the parameters are the
+ * PLAIN f32 buffer (layout above), the gradients the buffer g2048_qnet_loss_grad fills, the two moment estimates two more
+ * buffers of the same layout that start as zeros. All four hold 140132 + n_layers * (66690 + 257 * dim_ff) floats and are
+ * 16-byte aligned.
+ *
+ *   g2048_qnet_adamw_step   update number `step` (>= 1), two launches on `stream`, no host synchronisation:
+ *       1. the gradient norm. Block b adds grad[i]^2 over chunk b of the buffer in a fixed order and writes one partial sum to
+ *          `workspace`. The chunks are equal, a multiple of 1,024 floats and a function of the float count ALONE (never of the
+ *          device's compute units); there are at most G2048_QNET_STEP_MAX_PARTIALS of them for every accepted dim_ff and
+ *          n_layers. Squares, partial sums and the total are f64, so the norm is the f64 norm to f32 rounding.
+ *       2. clip and update. Every block adds all partials up again in the same order, so all hold the same norm;
+ *          norm_out[0] = (float)sqrt(total). If that is not finite (an inf or a NaN in grad) the launch writes NOTHING else:
+ *          plain, grad, exp_avg and exp_avg_sq keep their bits (stock torch would write NaN into every weight). Otherwise, with
+ *          c = min(1, max_norm / (norm + 1e-6)) (clip_grad_norm_'s rule, evaluated as torch evaluates it in f32: the reciprocal of
+ *          norm + 1e-6, times max_norm; max_norm = +inf: no clipping), for every element:
+ *              g = grad[i] * c;  grad[i] = g                      (grad is left clipped, as clip_grad_norm_ leaves it)
+ *              p = plain[i] * (1 - lr * weight_decay)
+ *              m = m + (g - m) * (1 - beta1)
+ *              v = v * beta2 + (g * g) * (1 - beta2)
+ *              p = p - (lr / bc1) * (m / (sqrt(v) / sqrt(bc2) + eps))     bc1 = 1 - beta1^step, bc2 = 1 - beta2^step
+ *          every operation rounded to f32 on its own, in the order of torch's AdamW. 1 - lr * weight_decay, 1 - beta1, 1 - beta2,
+ *          lr / bc1 and sqrt(bc2) are formed on the host in f64 and passed to the kernel as floats, as torch forms them from its
+ *          Python scalars; for that beta1 and beta2 are read as the shortest decimal that rounds to the float given (0.999f
+ *          is 0.999: 1 - (double)0.999f would be 1.3e-5 off 0.001).
+ *          The two LayerNorm-eps slots of every layer (the last two floats of each layer's block) are settings, not parameters:
+ *          all four buffers keep their bits there (grad, exp_avg and exp_avg_sq are 0 there and stay 0; weight decay would
+ *          otherwise shrink the eps by lr * weight_decay a step). grad there is part of the norm like any other element.
+ *       No atomics, no block waits on another: two calls from the same state give the same bits. Nothing outside the four
+ *       buffers, norm_out[0] and the workspace is written.
+ *   g2048_qnet_step_workspace   bytes of `workspace` (device memory, 16-byte aligned, contents irrelevant before and meaningless
+ *       after): one f64 per partial sum, at most 8 * G2048_QNET_STEP_MAX_PARTIALS; 0 for a bad dim_ff or n_layers.
+ * Arguments are checked before any device call: a null or misaligned pointer, dim_ff not a multiple of 32, n_layers outside
+ * 1 .. 64, step 0, an lr, beta1, beta2, eps or weight_decay that is negative or not finite, beta1 or beta2 >= 1, max_norm NaN or
+ * <= 0 return G2048_ERR_ARG. */
+#define G2048_QNET_STEP_MAX_PARTIALS 1024
+G2048_API size_t g2048_qnet_step_workspace(int dim_ff, int n_layers);
+G2048_API int g2048_qnet_adamw_step(float *plain, float *grad, float *exp_avg, float *exp_avg_sq, int dim_ff, int n_layers, float lr,
+                          float beta1, float beta2, float eps, float weight_decay, float max_norm, uint64_t step, float *norm_out,
+                          void *workspace, void *stream);
 #ifdef __cplusplus
 }
 #endif
