@@ -57,6 +57,15 @@ __device__ __forceinline__ void store_board(uint4 *p, size_t i, const Board &b)
     p[i] = make_uint4(b.w[0], b.w[1], b.w[2], b.w[3]);
 }
 
+// base + a 32-bit BYTE offset: with a wave-uniform base the access takes the SGPR-base + 32-bit-VGPR-offset form, where an element
+// index (64-bit once scaled) costs a 64-bit add per lane and a VGPR pair per stream
+template <class T>
+__device__ __forceinline__ T *byte_at(T *base, uint32_t byte_offset)
+{
+    using Byte = std::conditional_t<std::is_const_v<T>, const char, char>;
+    return reinterpret_cast<T *>(reinterpret_cast<Byte *>(base) + byte_offset);
+}
+
 // ------------------------------------------------------------------ step ------
 // Game2048Env.step (environment/game_2048.py:170-210), one board per lane per pass, B passes per lane.
 // All B loads of a lane are issued before the first board is computed: with ~400 VALU instructions per
@@ -90,7 +99,7 @@ __global__ __launch_bounds__(BLOCK) void step_kernel(size_t n, const uint32_t *_
     __shared__ uint4 s_dir[kStepTableWords / 4];
     const uint2 dir_word = step_table_word();                     // (stored to LDS below, once the lane's own loads are on their way)
     const TenthFromLds tenth{reinterpret_cast<const StepTable *>(s_dir)};
-    // per-block scalar bases + a 32-bit lane offset: the 7 streams are addressed as SGPR base + VGPR offset
+    // per-block scalar bases + a 32-bit lane offset: the 7 streams are addressed as SGPR base + VGPR offset (B > 1: byte_at)
     const size_t block0 = (size_t)blockIdx.x * (BLOCK * B);
     const uint4 *bin = boards_in + block0;
     uint4 *bout = boards_out + block0;
@@ -114,9 +123,16 @@ __global__ __launch_bounds__(BLOCK) void step_kernel(size_t n, const uint32_t *_
 #pragma unroll
     for (int k = 0; k < B; ++k) {
         const uint32_t j = min(threadIdx.x + (uint32_t)k * BLOCK, lim - 1u);
-        prev[k] = load_board(bin, j);
-        if (!RANDOM_ACTIONS) action[k] = act[j];
-        sc[k] = scp[j];
+        if constexpr (B == 1) {
+            prev[k] = load_board(bin, j);
+            if (!RANDOM_ACTIONS) action[k] = act[j];
+            sc[k] = scp[j];
+        } else {
+            const uint4 v = *byte_at(bin, j * 16u);
+            prev[k] = Board{{v.x, v.y, v.z, v.w}};
+            if (!RANDOM_ACTIONS) action[k] = *byte_at(act, j);
+            sc[k] = *byte_at(scp, j * 4u);
+        }
     }
     step_table_store(s_dir, dir_word);
     if (B > 1) __builtin_amdgcn_s_setprio(0);
@@ -124,8 +140,10 @@ __global__ __launch_bounds__(BLOCK) void step_kernel(size_t n, const uint32_t *_
     for (int k = 0; k < B; ++k) {
         // (B == 1: the clamped index serves the stores too -- the same offsets as the loads' -- since the lanes it differs for leave
         // before them)
+        // (B > 1: no exec region around the body either, for the same reason as below -- with one, the action and score loads of
+        // both boards sink into it, behind the table's write, and the head of the wavefront makes two dependent memory trips; the
+        // lanes past the end compute on their clamped loads and are masked at the stores alone)
         const uint32_t j = B == 1 ? min(threadIdx.x, lim - 1u) : threadIdx.x + (uint32_t)k * BLOCK;
-        if (B > 1 && !(full || j < lim)) break;
         const uint32_t id = id_lo_base + (uint32_t)block0 + j;           // low word of the board id (the launch never wraps it)
         if (RANDOM_ACTIONS) action[k] = rng_draw_lo(a0, a1, id, 0u) >> 30;    // what g2048_synth_actions would write
         const StepOut o = NOOP_ACTIONS ? step_board_sel_noop(prev[k], dir_sel(s_dir, action[k] & 3u), action[k] > 3u, rng_draw_lo(k0, k1, id, 0u), tenth)
@@ -141,14 +159,22 @@ __global__ __launch_bounds__(BLOCK) void step_kernel(size_t n, const uint32_t *_
         // B == 1: the lanes past the end of a ragged last block ran the arithmetic on their clamped loads (no exec region around
         // the body: the compiler would sink the loads into it, behind the table's write); they store nothing
         if (B == 1 && !(full || threadIdx.x < lim)) return;
-        store_board(bout, j, cur);
-        scp[j] = s;
-        if (REWARD_F64) rw64[j] = o.reward;
-        else rw32[j] = (float)o.reward;
-        flp[j] = (uint8_t)o.flags;        // bit0 DONE, bit1 VALID, bits 3..7 max code (include/g2048.h)
+        if constexpr (B == 1) {
+            store_board(bout, j, cur);
+            scp[j] = s;
+            if (REWARD_F64) rw64[j] = o.reward;
+            else rw32[j] = (float)o.reward;
+            flp[j] = (uint8_t)o.flags;        // bit0 DONE, bit1 VALID, bits 3..7 max code (include/g2048.h)
+        } else if (full || j < lim) {
+            *byte_at(bout, j * 16u) = make_uint4(cur.w[0], cur.w[1], cur.w[2], cur.w[3]);
+            *byte_at(scp, j * 4u) = s;
+            if (REWARD_F64) *byte_at(rw64, j * 8u) = o.reward;
+            else *byte_at(rw32, j * 4u) = (float)o.reward;
+            *byte_at(flp, j) = (uint8_t)o.flags;
+        }
         if constexpr (kStepTiming && !REWARD_F64) {       // lanes 0..2 of every wavefront: start tick, end tick, SIMD over the reward
             const uint32_t l = threadIdx.x & 63u;
-            if (k == 0 && l < 3u) reinterpret_cast<uint32_t *>(rw32)[j] = l == 0u ? (uint32_t)tm0 : l == 1u ? (uint32_t)wall_clock64() : simd_id();
+            if (k == 0 && l < 3u && (full || j < lim)) reinterpret_cast<uint32_t *>(rw32)[j] = l == 0u ? (uint32_t)tm0 : l == 1u ? (uint32_t)wall_clock64() : simd_id();
         }
     }
 }
@@ -620,6 +646,61 @@ __global__ void selftest_kernel(uint32_t *result, uint32_t a, uint32_t b, double
     *result = bad;
 }
 
+// ------------------------------------------------------- step: host side -----
+// What one plain step launch is bound to: the arrays, the board count and the two id words the kernel takes. g2048_step fills one
+// per call, g2048_step_pack once for many calls (StepCall).
+struct StepBound {
+    const uint4 *in; const uint8_t *actions; uint4 *out; uint32_t *score; void *reward; uint8_t *flags;
+    size_t n; uint32_t id_lo, id_hi_term;
+};
+
+// the block g2048_step_pack fills and g2048_step_packed launches from
+struct StepCall { uint64_t magic; StepBound b; uint64_t seed; uint32_t opts, per_lane, grid, reserved; };
+static_assert(sizeof(StepCall) <= G2048_STEP_CALL_BYTES, "the caller's block holds a StepCall");
+constexpr uint64_t kStepCallMagic = 0x6b63617038343032ull;        // "2048pack"
+
+constexpr uint32_t kStepOpts = G2048_STEP_REWARD_F64 | G2048_STEP_AUTO_RESET | G2048_STEP_RANDOM_ACTIONS | G2048_STEP_NOOP_ACTIONS |
+                               (3u << G2048_STEP_TUNE_SHIFT);
+
+// the argument checks of a step, as `what`'s (no device call)
+int step_check(const char *what, const void *boards_in, const uint8_t *actions, const void *boards_out, const uint32_t *score_inout,
+               const void *reward_out, const uint8_t *flags_out, uint32_t opts)
+{
+    const bool random_actions = (opts & G2048_STEP_RANDOM_ACTIONS) != 0u;
+    if (!boards_in || (!actions && !random_actions) || !boards_out || !score_inout || !reward_out || !flags_out)
+        return fail(G2048_ERR_ARG, "%s: null pointer", what);
+    if (!aligned(boards_in, 16) || !aligned(boards_out, 16)) return fail(G2048_ERR_ARG, "%s: board arrays must be 16-byte aligned", what);
+    if (!aligned(score_inout, 4) || !aligned(reward_out, (opts & G2048_STEP_REWARD_F64) ? 8 : 4))
+        return fail(G2048_ERR_ARG, "%s: score/reward arrays misaligned", what);
+    if (opts & ~kStepOpts) return fail(G2048_ERR_ARG, "%s: unknown opts 0x%x", what, opts);
+    if (((opts >> G2048_STEP_TUNE_SHIFT) & 3u) == 3u)
+        return fail(G2048_ERR_ARG, "%s: tune 3 (four boards per lane) was removed: measured slower at every size", what);
+    return G2048_OK;
+}
+
+// default: one board per lane -- measured fastest up to a few Mi boards per launch, where the launch is short and
+// wave-level parallelism hides the load latency; from 4 Mi boards on (beyond the Infinity Cache) two boards per lane,
+// both loads in flight before the first is computed, stream 4-5 % faster (profiles/r02_step_tune.txt)
+int step_boards_per_lane(uint32_t opts, size_t n)
+{
+    const unsigned tune = (opts >> G2048_STEP_TUNE_SHIFT) & 3u;            // 0 = default
+    return tune == 1 ? 1 : tune == 2 ? 2 : (n >= ((size_t)1 << 22) ? 2 : kStepBoardsPerLane);
+}
+
+// every variant takes the same arguments (a0, a1: the keys of the in-kernel policy); B boards per lane need 1 / B of the blocks
+template <class Kernel>
+void launch_step(Kernel kernel, unsigned grid, hipStream_t s, const StepBound &b, const uint32_t *keyblock, const Keys &k, const Keys &e,
+                 uint32_t a0 = 0, uint32_t a1 = 0)
+{
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), 0, s, b.n, keyblock, b.in, b.actions, b.score, b.id_lo, b.id_hi_term, k.k0, k.k1, b.out,
+                       b.reward, b.flags, e.k0, e.k1, a0, a1);
+}
+
+// explicit actions, low two bits: the launch g2048_step and g2048_step_packed share (defined below step_impl: the kernels stay in
+// the order in which step_impl names them)
+void launch_plain_step(bool f64, bool ar, int per_lane, unsigned grid, hipStream_t s, const StepBound &b, const uint32_t *keyblock,
+                       const Keys &k, const Keys &e);
+
 }  // namespace
 
 // ==================================================================== C-ABI ====
@@ -642,8 +723,7 @@ static int step_impl(const void *boards_in, const uint8_t *actions, void *boards
 {
     if (n == 0) return G2048_OK;
     const bool random_actions = (opts & G2048_STEP_RANDOM_ACTIONS) != 0u;
-    if (!boards_in || (!actions && !random_actions) || !boards_out || !score_inout || !reward_out || !flags_out)
-        return fail(G2048_ERR_ARG, "g2048_step: null pointer");
+    if (const int rc = step_check("g2048_step", boards_in, actions, boards_out, score_inout, reward_out, flags_out, opts)) return rc;
     {   // The kernel hashes the low word of a board id and takes the high word's term as a launch constant: a range of ids that
         // crosses a multiple of 2^32 becomes two launches, cut there (every per-board array is offset by the same number of boards).
         const uint64_t to_wrap = 0x100000000ull - (board_id_base & 0xffffffffull);
@@ -658,40 +738,38 @@ static int step_impl(const void *boards_in, const uint8_t *actions, void *boards
         }
     }
     if (random_actions && keyblock) return fail(G2048_ERR_ARG, "g2048_step_dyn: RANDOM_ACTIONS needs the scalar form");
-    if (!aligned(boards_in, 16) || !aligned(boards_out, 16)) return fail(G2048_ERR_ARG, "g2048_step: board arrays must be 16-byte aligned");
-    if (!aligned(score_inout, 4) || !aligned(reward_out, (opts & G2048_STEP_REWARD_F64) ? 8 : 4))
-        return fail(G2048_ERR_ARG, "g2048_step: score/reward arrays misaligned");
-    if (opts & ~(G2048_STEP_REWARD_F64 | G2048_STEP_AUTO_RESET | G2048_STEP_RANDOM_ACTIONS | G2048_STEP_NOOP_ACTIONS | (3u << G2048_STEP_TUNE_SHIFT))) return fail(G2048_ERR_ARG, "g2048_step: unknown opts 0x%x", opts);
     const Keys k = rng_keys(seed, DOM_STEP, step_index), e = rng_keys(seed, DOM_EPISODE, step_index);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const uint4 *in = static_cast<const uint4 *>(boards_in);
-    uint4 *out = static_cast<uint4 *>(boards_out);
+    const StepBound b = {static_cast<const uint4 *>(boards_in), actions, static_cast<uint4 *>(boards_out), score_inout, reward_out, flags_out,
+                         n, (uint32_t)board_id_base, rng_hi_term(board_id_base)};
     const bool f64 = opts & G2048_STEP_REWARD_F64, ar = opts & G2048_STEP_AUTO_RESET;
-    const unsigned tune = (opts >> G2048_STEP_TUNE_SHIFT) & 3u;            // 0 = default
-    if (tune == 3u) return fail(G2048_ERR_ARG, "g2048_step: tune 3 (four boards per lane) was removed: measured slower at every size");
-    // default: one board per lane -- measured fastest up to a few Mi boards per launch, where the launch is short and
-    // wave-level parallelism hides the load latency; from 4 Mi boards on (beyond the Infinity Cache) two boards per lane,
-    // both loads in flight before the first is computed, stream 4-5 % faster (profiles/r02_step_tune.txt)
-    const int per_lane = tune == 1 ? 1 : tune == 2 ? 2 : (n >= ((size_t)1 << 22) ? 2 : kStepBoardsPerLane);
-    // every variant takes the same arguments (a0, a1: the keys of the in-kernel policy); B boards per lane need 1 / B of the blocks
-    const auto launch = [&](auto kernel, int boards_per_lane, uint32_t a0 = 0, uint32_t a1 = 0) {
-        hipLaunchKernelGGL(kernel, dim3(blocks_for(n, kBlock * boards_per_lane)), dim3(kBlock), 0, s, n, keyblock, in, actions, score_inout,
-                           (uint32_t)board_id_base, rng_hi_term(board_id_base), k.k0, k.k1, out, reward_out, flags_out, e.k0, e.k1, a0, a1);
-    };
+    const int per_lane = step_boards_per_lane(opts, n);
     if (opts & G2048_STEP_NOOP_ACTIONS) {            // reference semantics for action values outside 0..3 (drop-in class)
         if (random_actions) return fail(G2048_ERR_ARG, "g2048_step: NOOP_ACTIONS needs explicit actions");
-        with_bools(f64, ar, [&](auto F, auto A) { launch(step_kernel<decltype(F)::value, decltype(A)::value, 1, kBlock, false, true>, 1); });
+        with_bools(f64, ar, [&](auto F, auto A) {
+            launch_step(step_kernel<decltype(F)::value, decltype(A)::value, 1, kBlock, false, true>, blocks_for(n, kBlock), s, b, keyblock, k, e);
+        });
     } else if (random_actions) {    // uniform actions drawn in the kernel: (seed, SYNTH_ACTION, step_index, board id) >> 30
         const Keys ak = rng_keys(seed, DOM_SYNTH_ACTION, step_index);
-        with_bools(f64, ar, [&](auto F, auto A) { launch(step_kernel<decltype(F)::value, decltype(A)::value, 1, kBlock, true>, 1, ak.k0, ak.k1); });
-    } else {
         with_bools(f64, ar, [&](auto F, auto A) {
-            if (per_lane == 1) launch(step_kernel<decltype(F)::value, decltype(A)::value, 1, kBlock>, 1);
-            else launch(step_kernel<decltype(F)::value, decltype(A)::value, 2, kBlock>, 2);
+            launch_step(step_kernel<decltype(F)::value, decltype(A)::value, 1, kBlock, true>, blocks_for(n, kBlock), s, b, keyblock, k, e, ak.k0, ak.k1);
         });
+    } else {
+        launch_plain_step(f64, ar, per_lane, blocks_for(n, (size_t)kBlock * per_lane), s, b, keyblock, k, e);
     }
     return check_launch("g2048_step");
 }
+
+namespace {
+void launch_plain_step(bool f64, bool ar, int per_lane, unsigned grid, hipStream_t s, const StepBound &b, const uint32_t *keyblock,
+                       const Keys &k, const Keys &e)
+{
+    with_bools(f64, ar, [&](auto F, auto A) {
+        if (per_lane == 1) launch_step(step_kernel<decltype(F)::value, decltype(A)::value, 1, kBlock>, grid, s, b, keyblock, k, e);
+        else launch_step(step_kernel<decltype(F)::value, decltype(A)::value, 2, kBlock>, grid, s, b, keyblock, k, e);
+    });
+}
+}  // namespace
 
 int g2048_step(const void *boards_in, const uint8_t *actions, void *boards_out, uint32_t *score_inout,
                void *reward_out, uint8_t *flags_out, uint64_t seed, uint64_t step_index,
@@ -699,6 +777,36 @@ int g2048_step(const void *boards_in, const uint8_t *actions, void *boards_out, 
 {
     return step_impl(boards_in, actions, boards_out, score_inout, reward_out, flags_out, seed, step_index, board_id_base, n,
                      opts, stream, nullptr);
+}
+
+int g2048_step_pack(const void *boards_in, const uint8_t *actions, void *boards_out, uint32_t *score_inout, void *reward_out,
+                    uint8_t *flags_out, uint64_t seed, uint64_t board_id_base, size_t n, uint32_t opts, void *call_out)
+{
+    if (!call_out || !aligned(call_out, 8)) return fail(G2048_ERR_ARG, "g2048_step_pack: call_out must be an 8-byte aligned block of G2048_STEP_CALL_BYTES");
+    static_cast<StepCall *>(call_out)->magic = 0;           // a refused pack leaves no block g2048_step_packed would take
+    if (const int rc = step_check("g2048_step_pack", boards_in, actions, boards_out, score_inout, reward_out, flags_out, opts)) return rc;
+    if (opts & (G2048_STEP_RANDOM_ACTIONS | G2048_STEP_NOOP_ACTIONS))
+        return fail(G2048_ERR_ARG, "g2048_step_pack: RANDOM_ACTIONS and NOOP_ACTIONS go through g2048_step");
+    if ((uint64_t)n > 0x100000000ull - (board_id_base & 0xffffffffull))
+        return fail(G2048_ERR_ARG, "g2048_step_pack: the board ids cross a multiple of 2^32 (two launches): use g2048_step");
+    const int per_lane = step_boards_per_lane(opts, n);
+    StepCall c = {};
+    c.b = StepBound{static_cast<const uint4 *>(boards_in), actions, static_cast<uint4 *>(boards_out), score_inout, reward_out, flags_out,
+                    n, (uint32_t)board_id_base, rng_hi_term(board_id_base)};
+    c.seed = seed; c.opts = opts; c.per_lane = (uint32_t)per_lane; c.grid = blocks_for(n, (size_t)kBlock * per_lane);
+    c.magic = kStepCallMagic;
+    *static_cast<StepCall *>(call_out) = c;
+    return G2048_OK;
+}
+
+int g2048_step_packed(const void *call, uint64_t step_index, void *stream)
+{
+    const StepCall *c = static_cast<const StepCall *>(call);
+    if (!c || !aligned(c, 8) || c->magic != kStepCallMagic) return fail(G2048_ERR_ARG, "g2048_step_packed: not a block g2048_step_pack filled");
+    if (c->b.n == 0) return G2048_OK;
+    launch_plain_step(c->opts & G2048_STEP_REWARD_F64, c->opts & G2048_STEP_AUTO_RESET, (int)c->per_lane, c->grid, static_cast<hipStream_t>(stream),
+                      c->b, nullptr, rng_keys(c->seed, DOM_STEP, step_index), rng_keys(c->seed, DOM_EPISODE, step_index));
+    return check_launch("g2048_step_packed");
 }
 
 int g2048_step_dyn(const void *boards_in, const uint8_t *actions, void *boards_out, uint32_t *score_inout,

@@ -25,6 +25,7 @@ BEAM_RANK_BY_COUNTING = 0x04
 PLAY_ONE_PHASE = 0x02
 BEAM_MAX_WIDTH = 128
 KEYBLOCK_WORDS = 16
+STEP_CALL_BYTES = 128
 ROLLOUT_OBS_SHIFT, OBS_F32, OBS_F16, OBS_BF16 = 4, 0, 1, 2
 SEEN_SLOT_BYTES = 32
 ENV_RECORD_BYTES, ENV_OP_STEP, ENV_OP_RESET, ENV_OP_PEEK, ENV_OP_MOVE, ENV_OP_SPAWN, ENV_OP_MOVE_AGENT = 80, 0, 1, 2, 3, 4, 5
@@ -42,6 +43,8 @@ SIGNATURES = {
     "g2048_build_flags": (C.c_uint, []),
     "g2048_device_count": (_int, []),
     "g2048_step": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _u64, _u64, _u64, _sz, _u32, _vp]),
+    "g2048_step_pack": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _u64, _u64, _sz, _u32, _vp]),
+    "g2048_step_packed": (_int, [_vp, _u64, _vp]),
     "g2048_step_many": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _u64, _u32, _u64, _sz, _u32, _vp]),
     "g2048_reset": (_int, [_vp, _vp, _u64, _u64, _u64, _sz, _vp]),
     "g2048_valid_moves": (_int, [_vp, _vp, _sz, _u32, _vp]),

@@ -90,9 +90,11 @@ def step(boards, actions, scores, seed, step_index, id_base=0, out=None, reward=
 
 
 class PreparedStep:
-    """g2048_step with everything but the step index bound and checked ONCE: calling it costs one ctypes call (a few
-    microseconds) instead of the tensor checks of `step`, so a host loop of back-to-back steps stays ahead of the GPU even
-    at ~13 us per launch. Same semantics as `step(..., out=, reward=, flags=)` with explicit actions."""
+    """g2048_step with everything but the step index bound and checked ONCE: calling it costs one ctypes call of three
+    arguments (g2048_step_packed on the block g2048_step_pack filled) instead of the tensor checks of `step`, so a host loop
+    of back-to-back steps stays ahead of the GPU even at ~9 us per step. Same semantics as `step(..., out=, reward=, flags=)`
+    with explicit actions. What g2048_step_pack refuses as more than one plain launch (a board-id range that crosses a
+    multiple of 2^32) keeps going through g2048_step, twelve arguments a call."""
 
     def __init__(self, boards, actions, scores, seed, id_base=0, *, out, reward, flags, auto_reset=False, tune=0):
         step(boards, actions, scores, seed, 0, id_base, out=out, reward=reward, flags=flags,
@@ -101,14 +103,24 @@ class PreparedStep:
         self.device = boards.device
         opts = ((L.STEP_REWARD_F64 if reward.dtype == torch.float64 else 0) | (L.STEP_AUTO_RESET if auto_reset else 0) |
                 ((int(tune) & 3) << 8))
-        self._fn = L.lib().g2048_step
-        self._head = (boards.data_ptr(), actions.data_ptr(), out.data_ptr(), scores.data_ptr(), reward.data_ptr(), flags.data_ptr(),
-                      L.u64(seed))
-        self._tail = (L.u64(id_base), boards.shape[0], opts)
+        head = (boards.data_ptr(), actions.data_ptr(), out.data_ptr(), scores.data_ptr(), reward.data_ptr(), flags.data_ptr(),
+                L.u64(seed))
+        tail = (L.u64(id_base), boards.shape[0], opts)
+        self._block = (L.C.c_uint64 * (L.STEP_CALL_BYTES // 8))()
+        self._call = L.C.addressof(self._block)
+        self.packed = L.lib().g2048_step_pack(*head, *tail, self._call) == L.OK
+        if self.packed:
+            self._fn = L.lib().g2048_step_packed
+        else:
+            self._fn, self._head, self._tail = L.lib().g2048_step, head, tail
 
     def __call__(self, step_index, stream_ptr=None):
-        rc = self._fn(*self._head, int(step_index), *self._tail,
-                      stream_ptr if stream_ptr is not None else torch.cuda.current_stream(self.device).cuda_stream)
+        if stream_ptr is None:
+            stream_ptr = torch.cuda.current_stream(self.device).cuda_stream
+        if self.packed:
+            rc = self._fn(self._call, int(step_index), stream_ptr)
+        else:
+            rc = self._fn(*self._head, int(step_index), *self._tail, stream_ptr)
         if rc != L.OK:
             L.check(rc)
 

@@ -136,6 +136,24 @@ G2048_API int g2048_step(const void *boards_in, const uint8_t *actions, void *bo
                uint64_t seed, uint64_t step_index, uint64_t board_id_base, size_t n,
                uint32_t opts, void *stream);
 
+/* g2048_step for a caller that makes the same call step after step (a host-paced loop of launches): everything but the step
+ * index and the stream is checked and bound ONCE, into a caller-owned block, and each step is then a call of three arguments.
+ *   g2048_step_pack    performs every argument check of g2048_step (null pointers, alignment, unknown opts, tune 3) and fills
+ *                      call_out -- G2048_STEP_CALL_BYTES bytes, 8-byte aligned -- with the bound arguments, the kernel variant
+ *                      and grid g2048_step would choose, and a magic word. It makes no HIP call. It refuses, with
+ *                      G2048_ERR_ARG, what is not one plain launch: G2048_STEP_RANDOM_ACTIONS, G2048_STEP_NOOP_ACTIONS and a
+ *                      range of board ids that crosses a multiple of 2^32; such a caller keeps using g2048_step. A refused
+ *                      call leaves a block g2048_step_packed does not accept.
+ *   g2048_step_packed  derives the keys of step_index and makes exactly the launch g2048_step(..., step_index, ..., stream)
+ *                      would make with the bound arguments: the results are the same bit for bit. A block without the magic
+ *                      word is refused with G2048_ERR_ARG. The block may be copied and reused for any number of calls, on any
+ *                      stream; the arrays it names must be alive at every call. */
+#define G2048_STEP_CALL_BYTES 128
+G2048_API int g2048_step_pack(const void *boards_in, const uint8_t *actions, void *boards_out,
+               uint32_t *score_inout, void *reward_out, uint8_t *flags_out,
+               uint64_t seed, uint64_t board_id_base, size_t n, uint32_t opts, void *call_out);
+G2048_API int g2048_step_packed(const void *call, uint64_t step_index, void *stream);
+
 /* `steps` consecutive Game2048Env.step calls (environment/game_2048.py:170-210) of every board in ONE launch: the board and
  * its score stay in registers between the steps instead of making a 46-byte round trip through memory per step. Step t
  * (0 <= t < steps) is bit-for-bit g2048_step(step_index = step_index0 + t) with the same opts. The actions are either the
