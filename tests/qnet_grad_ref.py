@@ -1,6 +1,6 @@
 """What the CPU and the GPU tests of the Q-network's loss and gradient pass share: the inputs' recipe, the stock module's own
 autograd through the lines of train_step (the yardstick in float64, the tolerance's measure in float32), and the plain layout's
-offsets. Tensors are numbered in the plain layout's order, which is the module's parameter order."""
+offsets, and layer 0's attention probabilities from the float64 module. Tensors are numbered in the plain layout's order, which is the module's parameter order."""
 import numpy as np
 import torch
 import torch.nn as nn
@@ -40,6 +40,19 @@ def stock_loss_grad(model, codes, actions, targets, weights):
     grads = [p.grad.detach().numpy().astype(np.float64).reshape(-1) for p in model.parameters()]
     model.zero_grad()
     return float(loss.detach()), td.detach().numpy().astype(np.float64), q.detach().numpy().astype(np.float64), grads
+
+
+def layer0_attention(model64, codes):
+    """(logits, P) of layer 0's attention from the float64 module alone, both [head][query][key]: the boards of the call are one
+    sequence, P is the softmax over the keys of q . k / sqrt(16) per head, q and k from embedding(cnn(x)) through in_proj."""
+    n = len(codes)
+    attn = model64.transformer.layers[0].self_attn
+    with torch.no_grad():
+        h = model64.embedding(model64.cnn(tile_values(codes, torch.float64).view(-1, 1, 4, 4)).view(n, -1))
+        qk = h @ attn.in_proj_weight[:256].T + attn.in_proj_bias[:256]
+        q, k = qk[:, :128].view(n, 8, 16), qk[:, 128:].view(n, 8, 16)
+        logits = torch.einsum("ihd,jhd->hij", q, k) / 4.0
+        return logits.numpy(), torch.softmax(logits, -1).numpy()
 
 
 def plain_slices(parsed):

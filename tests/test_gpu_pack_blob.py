@@ -4,7 +4,9 @@ forward tests cannot see a padding word; this one sees every byte: the order of 
 rounding to nearest even, the zero rows past a matrix (the head tile's actor rows over its critic row; the Q-network's four fc
 rows), conv2's and the embedding's column permutations, the f32 section and its zero padding.
 
-Smallest legal shape (dim_ff 32, one layer) on the hash weights of tests/tpolicy_weights.py / tests/qnet_weights.py, whose values
+The smallest legal shape (dim_ff 32, one layer) and dim_ff 96 with three layers (an odd number of 32-feature slices, linear2 with
+three bf16 chunks, the second and third layers' offsets l * layer_frags() and l * layer_params()), assembled by one function of
+(dim_ff, layers) on the hash weights of tests/tpolicy_weights.py / tests/qnet_weights.py, whose values
 have 16 significant bits, so bf16 rounding is exercised, ties included. The bf16 reference rounds with torch's own float32 ->
 bfloat16 conversion, not with the kernel's integer formula."""
 import numpy as np
@@ -17,7 +19,10 @@ import tpolicy_weights as tw
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
-DIM_FF, LAYERS, EPS = 32, 1, 1e-5
+EPS = 1e-5
+# the smallest legal shape, and three 32-feature slices (an odd chunk count of linear2 in bf16, a fragment index o * c2 + c with c2
+# no power of two) with a third layer's offset in the fragments and in the f32 section
+SHAPES = [(32, 1), (96, 3)]
 
 
 def bf16_bits(x):
@@ -60,47 +65,54 @@ def plain_buffer(sd, shapes):
     return np.concatenate(out)
 
 
-def tpolicy_case(bf16):
-    shapes = tw.reference_shapes(DIM_FF, LAYERS)
+def tpolicy_case(bf16, dim_ff, layers):
+    shapes = tw.reference_shapes(dim_ff, layers)
     sd = {k: v.astype(np.float32) for k, v in tw.state_dict(shapes).items()}
-    p = "transformer_encoder.layers.0."
-    mats = [sd[p + "self_attn.in_proj_weight"], sd[p + "self_attn.out_proj.weight"], sd[p + "linear1.weight"], sd[p + "linear2.weight"],
-            sd["fc1.weight"], sd["fc2.weight"], np.concatenate([sd["actor.weight"], sd["critic.weight"]])]
+    mats, params = [], [sd["embedding.weight"], sd["embedding.bias"]]
+    for l in range(layers):
+        p = "transformer_encoder.layers.%d." % l
+        mats += [sd[p + "self_attn.in_proj_weight"], sd[p + "self_attn.out_proj.weight"], sd[p + "linear1.weight"], sd[p + "linear2.weight"]]
+        params += [sd[p + "self_attn.in_proj_bias"], sd[p + "self_attn.out_proj.bias"], sd[p + "linear1.bias"], sd[p + "linear2.bias"],
+                   sd[p + "norm1.weight"], sd[p + "norm1.bias"], sd[p + "norm2.weight"], sd[p + "norm2.bias"], [EPS, EPS, 0.0, 0.0]]
+    mats += [sd["fc1.weight"], sd["fc2.weight"], np.concatenate([sd["actor.weight"], sd["critic.weight"]])]
     head_bias = np.zeros(16, np.float32)
     head_bias[:4], head_bias[4] = sd["actor.bias"], sd["critic.bias"][0]
-    params = floats(sd["embedding.weight"], sd["embedding.bias"], sd[p + "self_attn.in_proj_bias"], sd[p + "self_attn.out_proj.bias"],
-                    sd[p + "linear1.bias"], sd[p + "linear2.bias"], sd[p + "norm1.weight"], sd[p + "norm1.bias"], sd[p + "norm2.weight"],
-                    sd[p + "norm2.bias"], [EPS, EPS, 0.0, 0.0], sd["fc1.bias"], sd["fc2.bias"], head_bias)
-    return plain_buffer(sd, shapes), np.concatenate([fragments(m, bf16) for m in mats] + [params])
+    params += [sd["fc1.bias"], sd["fc2.bias"], head_bias]
+    return plain_buffer(sd, shapes), np.concatenate([fragments(m, bf16) for m in mats] + [floats(*params)])
 
 
-def qnet_case(bf16):
-    shapes = qw.reference_shapes(DIM_FF, LAYERS)
+def qnet_case(bf16, dim_ff, layers):
+    shapes = qw.reference_shapes(dim_ff, layers)
     sd = {k: v.astype(np.float32) for k, v in qw.state_dict(shapes).items()}
-    p = "transformer.layers.0."
     conv2 = sd["cnn.2.weight"].reshape(64, 32, 4).transpose(0, 2, 1).reshape(64, 128)             # k = tap * 32 + channel
     emb = sd["embedding.weight"].reshape(128, 64, 16).transpose(0, 2, 1).reshape(128, 1024)      # k = position * 64 + channel
-    mats = [conv2, emb, sd[p + "self_attn.in_proj_weight"][256:], sd[p + "self_attn.out_proj.weight"], sd[p + "linear1.weight"],
-            sd[p + "linear2.weight"], sd["fc.weight"]]
+    mats = [conv2, emb]
+    params = [sd["cnn.0.weight"].reshape(32, 4).T, sd["cnn.0.bias"], sd["cnn.2.bias"], sd["embedding.bias"]]     # conv1 [tap][channel]
+    for l in range(layers):
+        p = "transformer.layers.%d." % l
+        mats += [sd[p + "self_attn.in_proj_weight"][256:], sd[p + "self_attn.out_proj.weight"], sd[p + "linear1.weight"], sd[p + "linear2.weight"]]
+        params += [sd[p + "self_attn.in_proj_bias"][256:], sd[p + "self_attn.out_proj.bias"], sd[p + "linear1.bias"], sd[p + "linear2.bias"],
+                   sd[p + "norm1.weight"], sd[p + "norm1.bias"], sd[p + "norm2.weight"], sd[p + "norm2.bias"], [EPS, EPS, 0.0, 0.0]]
+    mats.append(sd["fc.weight"])
     fc_bias = np.zeros(16, np.float32)
     fc_bias[:4] = sd["fc.bias"]
-    params = floats(sd["cnn.0.weight"].reshape(32, 4).T, sd["cnn.0.bias"], sd["cnn.2.bias"], sd["embedding.bias"],   # conv1 [tap][channel]
-                    sd[p + "self_attn.in_proj_bias"][256:], sd[p + "self_attn.out_proj.bias"], sd[p + "linear1.bias"],
-                    sd[p + "linear2.bias"], sd[p + "norm1.weight"], sd[p + "norm1.bias"], sd[p + "norm2.weight"], sd[p + "norm2.bias"],
-                    [EPS, EPS, 0.0, 0.0], fc_bias)
-    return plain_buffer(sd, shapes), np.concatenate([fragments(m, bf16) for m in mats] + [params])
+    params.append(fc_bias)
+    return plain_buffer(sd, shapes), np.concatenate([fragments(m, bf16) for m in mats] + [floats(*params)])
 
 
-@pytest.mark.parametrize("precision", ["f32", "bf16"])
-@pytest.mark.parametrize("net", ["tpolicy", "qnet"])
-def test_packed_blob_is_the_documented_layout_byte_for_byte(net, precision):
+CASES = [(net, precision, shape) for shape in SHAPES for precision in ("f32", "bf16") for net in ("tpolicy", "qnet")]
+
+
+@pytest.mark.parametrize("net,precision,shape", CASES, ids=["%s-%s" % c[:2] + ("" if c[2] == SHAPES[0] else "-ff%d-L%d" % c[2]) for c in CASES])
+def test_packed_blob_is_the_documented_layout_byte_for_byte(net, precision, shape):
     from g2048 import ops
-    plain, want = (tpolicy_case if net == "tpolicy" else qnet_case)(precision == "bf16")
+    dim_ff, layers = shape
+    plain, want = (tpolicy_case if net == "tpolicy" else qnet_case)(precision == "bf16", dim_ff, layers)
     pack, size = (ops.tpolicy_pack, ops.tpolicy_packed_bytes) if net == "tpolicy" else (ops.qnet_pack, ops.qnet_packed_bytes)
-    assert want.nbytes == size(precision, DIM_FF, LAYERS)
+    assert want.nbytes == size(precision, dim_ff, layers)
     out = torch.full((want.nbytes,), 0xA5, dtype=torch.uint8, device=DEV)           # every byte must be written
-    got = pack(torch.from_numpy(plain).to(DEV), DIM_FF, LAYERS, precision, out=out).cpu().numpy().view(np.uint32)
+    got = pack(torch.from_numpy(plain).to(DEV), dim_ff, layers, precision, out=out).cpu().numpy().view(np.uint32)
     wrong = np.flatnonzero(got != want)
-    print("%s %s: %d bytes, %d of %d words differ%s" % (net, precision, want.nbytes, len(wrong), len(want),
-                                                         "" if not len(wrong) else ", the first at word %d" % wrong[0]))
+    print("%s %s dim_ff %d L %d: %d bytes, %d of %d words differ%s" % (net, precision, dim_ff, layers, want.nbytes, len(wrong), len(want),
+                                                                       "" if not len(wrong) else ", the first at word %d" % wrong[0]))
     assert len(wrong) == 0

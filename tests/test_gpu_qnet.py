@@ -1,5 +1,6 @@
 """g2048_qnet_forward on the MI355X: the reference's HybridDQN on the fixture's weights (tests/golden/qnet.npz), a random-init
-module against its own CPU f64 per-board forward at ragged sizes with canaries, the smallest legal shape, position independence
+module against its own CPU f64 per-board forward at ragged sizes with canaries, the smallest legal shape, two shapes that are no
+power of two (dim_ff 96 with one layer, 160 with three: the packed blob's odd slice counts and third-layer offsets), position independence
 and determinism bit for bit, the exploit action against the launch's own Q-values and against the reference's f64 actions,
 in-place refresh and argument validation.
 
@@ -20,7 +21,7 @@ import torch
 
 import qnet_weights as qw
 from conftest import load_golden
-from test_policy_host import random_boards
+from test_policy_host import distinct_layers, random_boards
 from test_qnet_host import bf16_round, golden_model, random_model, tiles
 
 pytestmark = pytest.mark.gpu
@@ -129,6 +130,46 @@ def test_one_layer_dim_ff_32(precision):
     net = DeviceQNetwork(model.float().to(DEV), precision=precision)
     assert net.dim_ff == 32 and net.n_layers == 1
     check(precision, net(torch.from_numpy(boards).to(DEV)).cpu().numpy(), truth, f32_cpu, rounded, "L=1 dim_ff=32")
+
+
+# The packed path away from powers of two: 96 = three 32-feature slices of the feed-forward pair (an odd count; linear2 with three
+# bf16 chunks, fragment index o * c2 + c with c2 = 6 or 3), 160 = five slices with a second and a third layer's offsets into the
+# fragments and the f32 section.
+PACKED_SHAPES = [(96, 1), (160, 3)]
+
+
+@functools.lru_cache(maxsize=None)
+def packed_shape_case(dim_ff, layers):
+    """A random-init module of the shape with every layer's tensors its own (distinct_layers: a fresh module's layers are copies
+    of one), 257 boards and their CPU forwards (shared, never modified)."""
+    model = random_model(2, dim_ff, layers)
+    distinct_layers(model.transformer.layers, 5)
+    boards = case_boards(257, 11)
+    truth, f32_cpu, rounded = cpu_forwards(model, boards)
+    return model.float(), boards, truth, f32_cpu, rounded
+
+
+@pytest.mark.parametrize("precision", ["f32", "bf16"])
+@pytest.mark.parametrize("shape", PACKED_SHAPES, ids=["ff%d-L%d" % s for s in PACKED_SHAPES])
+def test_packed_shape_matrix_with_canaries(shape, precision):
+    from g2048 import DeviceQNetwork, ops
+    dim_ff, layers = shape
+    model, all_boards, truth, f32_cpu, rounded = packed_shape_case(dim_ff, layers)
+    net = DeviceQNetwork(device_copy(model), precision=precision)
+    assert (net.dim_ff, net.n_layers) == shape
+    for n in (17, 257):
+        b = torch.from_numpy(all_boards[:n]).to(DEV)
+        q = torch.full((n + 67, 4), 7.0, device=DEV)
+        actions = torch.full((n + 67,), 9, dtype=torch.uint8, device=DEV)
+        ops.qnet_forward(b, net.packed, dim_ff, layers, precision, q=q[:n], actions=actions[:n])
+        torch.cuda.synchronize()
+        assert torch.all(q[n:] == 7.0) and torch.all(actions[n:] == 9), "rows past n were written (n = %d)" % n
+        assert torch.all(actions[:n] < 4)
+        check(precision, q[:n].cpu().numpy(), truth[:n], f32_cpu[:n], rounded[:n], "dim_ff %d L %d n=%d" % (dim_ff, layers, n))
+    if layers == 3:
+        for i in (0, 130, 256):                              # alone: another wavefront, block and column than in the large call
+            a, q1 = net.act(b[i:i + 1].clone())
+            assert torch.equal(q1[0], q[i]) and a[0] == actions[i], "board %d alone differs from row %d of the large call" % (i, i)
 
 
 @pytest.mark.parametrize("precision", ["f32", "bf16"])

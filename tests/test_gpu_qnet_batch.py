@@ -4,14 +4,16 @@ CPU f64 batch forward at every tile edge with canaries, n = 1 against the per-bo
 workspace, the proof that the other boards of a call are attended to, permutation, the Double-DQN targets against torch on the
 launch's own Q bit for bit and against the reference's f64 actions and targets, and refresh(); a shape matrix (MATRIX) that runs the
 products' main-plus-tail loop in every combination, a third layer and the sizes up to G2048_QNET_BATCH_MAX, with the targets at the
-limit.
+limit; and the peaked-attention cases (REGIME_CASES, shared with test_gpu_qnet_grad.py): layer 0's softmax spread over a few keys,
+on mid boards, on full boards under the conditioned module, and at three layers whose tensors differ from layer to layer.
 
 Tolerance, the f32 convention of test_gpu_qnet.py: |q - q_f64| <= 8 x max|q_f32 - q_f64| of the case, q_f32 the stock module's
 float32 CPU batch call on the same boards and weights; the measured multiple is printed. On the shape matrix's early boards
 (codes 0..3) the yardstick itself must lie in (0, 1e-5], so that a blown yardstick cannot hide a failure.
 
 Measured on an MI355X over the shape matrix: early boards 0.47 - 2.49 x (yardstick 5.5e-8 .. 5.1e-7), full boards 0.39 - 1.08 x
-(yardstick 1.5e-7 .. 5.3e-4); per shape in docs/LOG.md R19.1."""
+(yardstick 1.5e-7 .. 5.3e-4); per shape in docs/LOG.md R19.1. Peaked-attention cases: 0.61 - 1.09 x (yardstick 1.9e-7 .. 5.6e-7;
+R22.1)."""
 import functools
 
 import numpy as np
@@ -37,6 +39,15 @@ MATRIX_CASES = [(ff, layers, n) for ff, layers, sizes in MATRIX for n in sizes]
 MATRIX_IDS = ["ff%d-L%d-n%d" % c for c in MATRIX_CASES]
 MODEL_SEED, BOARD_SEED = 2, 11
 FAIR_F32 = 1e-5                                             # above this stock float32 is no yardstick (test_qnet_grad_host.py)
+# The peaked-attention cases (regime, dim_ff, layers, n): layer 0's softmax neither uniform (early boards) nor one-hot (full boards).
+# 1,025 is one beyond a single LDS key tile and four boards per thread in the conv1 weight gradient's reduction.
+# 'distinct' is 'mid' at three layers with the second and third layers' tensors made their own: nn.TransformerEncoder deep-copies one
+# layer, so in every other random-init module here the layers carry the same weights and a wrong layer offset l * pl_layer(ff)
+# would read the right numbers.
+REGIMES = ("mid", "conditioned")
+REGIME_CASES = ([(r, ff, layers, n) for r in REGIMES for ff, layers, sizes in ((64, 2, (17, 257, 1025)), (160, 3, (17, 257))) for n in sizes]
+                + [("distinct", 160, 3, n) for n in (17, 257)])
+REGIME_IDS = ["%s-ff%d-L%d-n%d" % c for c in REGIME_CASES]
 
 
 def check(q, want, f32_cpu, what):
@@ -81,11 +92,16 @@ def device_net(model):
 
 
 def matrix_boards(n, kind):
-    """'early': random_boards % 4, codes 0..3 (tiles <= 8), on which every quantity is a fair float32 quantity; 'full':
-    case_boards. Below 16 boards the last n of 16 (the recipes need a few rows; one board is then a random one, not the empty one)."""
+    """'early': random_boards % 4, codes 0..3 (tiles <= 8), on which every quantity is a fair float32 quantity and layer 0's
+    attention is uniform; 'mid': random_boards % 8, codes 0..7 (tiles <= 128), on which layer 0's attention is peaked and float32
+    still fair; 'full': case_boards. Below 16 boards the last n of 16 (the recipes need a few rows; one board is then a random one,
+    not the empty one)."""
     from test_policy_host import random_boards
     m = max(n, 16)
-    return ((random_boards(m, BOARD_SEED) % 4).astype(np.uint8) if kind == "early" else case_boards(m, BOARD_SEED))[m - n:]
+    if kind in ("early", "mid"):
+        return (random_boards(m, BOARD_SEED) % (4 if kind == "early" else 8)).astype(np.uint8)[m - n:]
+    assert kind == "full", kind
+    return case_boards(m, BOARD_SEED)[m - n:]
 
 
 @functools.lru_cache(maxsize=None)
@@ -100,6 +116,44 @@ def matrix_forward(dim_ff, layers, n, kind):
     from g2048 import qnet
     model = random_model(MODEL_SEED, dim_ff, layers)
     boards = matrix_boards(n, kind)
+    with torch.no_grad():
+        f32 = model(tiles(boards, torch.float32)).numpy().astype(np.float64)
+    return boards, qnet.forward_batch_reference(qnet.parse(model.double()), torch.from_numpy(boards)).numpy(), f32
+
+
+def regime_model(regime, dim_ff, layers):
+    """The module of a peaked-attention case. 'mid': the matrix's random-init module. 'conditioned': the same with cnn[0].weight
+    times 2^-10 (exact in every format), taken before any float64 or float32 copy: full boards then leave layer 0's logits near
+    100 instead of 1e9, a softmax that is sharp but a float32 quantity. 'distinct': 'mid' with the layers after the first
+    perturbed each by its own draws (distinct_layers), layer 0 and with it the attention regime as in 'mid'."""
+    from test_policy_host import distinct_layers
+    model = random_model(MODEL_SEED, dim_ff, layers)
+    if regime == "conditioned":
+        with torch.no_grad():
+            model.cnn[0].weight.mul_(2.0 ** -10)
+    elif regime == "distinct":
+        distinct_layers(model.transformer.layers[1:], 5)
+    else:
+        assert regime == "mid", regime
+    return model
+
+
+def regime_boards(regime, n):
+    return matrix_boards(n, "full" if regime == "conditioned" else "mid")
+
+
+@functools.lru_cache(maxsize=None)
+def regime_net(regime, dim_ff, layers):
+    return device_net(regime_model(regime, dim_ff, layers))
+
+
+@functools.lru_cache(maxsize=None)
+def regime_forward(regime, dim_ff, layers, n):
+    """(boards, the CPU f64 batch forward, the stock module's CPU f32 batch call) of a peaked-attention case (shared, never
+    modified)."""
+    from g2048 import qnet
+    model = regime_model(regime, dim_ff, layers)
+    boards = regime_boards(regime, n)
     with torch.no_grad():
         f32 = model(tiles(boards, torch.float32)).numpy().astype(np.float64)
     return boards, qnet.forward_batch_reference(qnet.parse(model.double()), torch.from_numpy(boards)).numpy(), f32
@@ -158,6 +212,17 @@ def test_shape_matrix_with_canaries(case):
         yard = np.abs(f32 - truth).max() / np.abs(truth).max()
         assert kind == "full" or 0 < yard <= FAIR_F32, "stock float32 is no fair yardstick on this case: %.3g" % yard
         check(forward_with_canaries(net, boards), truth, f32, "%s boards, dim_ff %d L %d n=%d" % (kind, dim_ff, layers, n))
+
+
+@pytest.mark.parametrize("case", REGIME_CASES, ids=REGIME_IDS)
+def test_peaked_attention_with_canaries(case):
+    """Layer 0's softmax peaked on a few keys: mid boards, and full boards (codes up to 17, logits past float32 exp's overflow)
+    under the conditioned module."""
+    regime, dim_ff, layers, n = case
+    net = regime_net(regime, dim_ff, layers)
+    assert (net.dim_ff, net.n_layers) == (dim_ff, layers)
+    boards, truth, f32 = regime_forward(*case)
+    check(forward_with_canaries(net, boards), truth, f32, "%s, dim_ff %d L %d n=%d" % case)
 
 
 def test_one_board_is_the_per_board_function():

@@ -3,7 +3,7 @@ own DQNAgent.beam_search recorded (tests/golden/qnet_beam.npz), DeviceQNetwork.a
 restatement (tests/qnet_beam_ref.py) on the device's own Q-values, the epsilon coin against g2048_qnet_select_actions, and
 g2048_play_qnet_beam_games against the unfused loop (every output, bit for bit) and, move by move, against the restatement.
 The game tests play and compare through tests/play_harness.py, as the other three game kernels' tests do; the Q-network
-builder is tests/test_gpu_qnet_play.py's. Everything is exact: the decision is integer and f64 arithmetic in a fixed order,
+builder is tests/test_gpu_qnet_play.py's (the fixture's network, the small one, and dim_ff 96 with 3 layers). Everything is exact: the decision is integer and f64 arithmetic in a fixed order,
 and the forward's accuracy is pinned elsewhere (tests/test_gpu_qnet.py)."""
 from functools import partial
 
@@ -150,9 +150,11 @@ def test_epsilon_is_select_actions_own(g2048, golden):
 play, play_beam = partial(H.play, H.QNET), partial(H.play, H.QNET_BEAM)
 
 
-@pytest.mark.parametrize("network", ["fixture", "small"])
-@pytest.mark.parametrize("precision", ["f32", "bf16"])
-@pytest.mark.parametrize("epsilon", [0.0, 0.05])
+FUSED_CASES = ([(e, p, w) for w in ("fixture", "small") for p in ("f32", "bf16") for e in (0.0, 0.05)]
+               + [(0.05, p, "odd") for p in ("f32", "bf16")])
+
+
+@pytest.mark.parametrize("epsilon,precision,network", FUSED_CASES, ids=["%s-%s-%s" % c for c in FUSED_CASES])
 def test_fused_beam_games_equal_the_unfused_loop(g2048, epsilon, precision, network):
     net = device_net(network, precision)
     for n, cap, beam in ((300, 160, REFERENCE), (33, 400, REFERENCE), (77, 60, EARLY)):

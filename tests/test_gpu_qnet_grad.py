@@ -1,8 +1,9 @@
 """g2048_qnet_loss_grad on the MI355X: the loss and the gradients of every parameter against the stock module's float64 autograd
 through the lines of train_step (random-init modules at every tile edge, with canaries) and against the reference class's
 recorded gradients (tests/golden/qnet_grad.npz), q bit for bit against forward_batch, repeatability and a poisoned workspace, zero
-weights, a permuted batch, attach_grads() with a stock optimiser, and the shape matrix of test_gpu_qnet_batch.py (a main group
-followed by tail steps in the forward's products and in dX, a third layer, the sizes up to G2048_QNET_BATCH_MAX).
+weights, a permuted batch, attach_grads() with a stock optimiser, the shape matrix of test_gpu_qnet_batch.py (a main group
+followed by tail steps in the forward's products and in dX, a third layer, the sizes up to G2048_QNET_BATCH_MAX), and its
+peaked-attention cases (a layer-0 softmax that is neither uniform nor one-hot, with canaries and repeatability).
 
 Tolerance, the f32 convention of test_gpu_qnet_batch.py applied per case: for every checked tensor max|g - g64| / max|g64| <= 8 x
 the worst such ratio of the stock module's float32 CPU autograd over the checked tensors of the same case; loss and td are held
@@ -15,11 +16,19 @@ error (out_proj.weight at n = 4,096); dim_ff 160 with 3 layers on full boards 0.
 the batch limit sits just under the fairness bound: 5.6e-6 (n = 2,049), 9.6e-6 (4,095), 6.6e-6 (4,096), and it depends on the CPU's
 thread count (docs/LOG.md R19.1).
 
-Two kinds of case. On EARLY boards (codes 0..3, tiles <= 8) every parameter is checked. On FULL boards (tiles up to 131,072)
-layer 0's attention logits reach 1e9 and its softmax is nearly one-hot: at n >= 2 the gradients that pass through it (cnn.*,
-embedding.*, layer 0's in_proj_*) are no float32 quantity -- stock float32 autograd is off by up to eight times the gradient
-there -- so they are asserted finite and their error is printed, and the other parameters are checked. At n = 1 the softmax is
-exactly 1 and all of them are checked."""
+Three kinds of case. On EARLY boards (codes 0..3, tiles <= 8) every parameter is checked; layer 0's attention is uniform there
+(logits <= 0.3, max P = 1 / n), so its backward's dS is next to nothing. On FULL boards (tiles up to 131,072) layer 0's attention
+logits reach 1e9 and its softmax is nearly one-hot: at n >= 2 the gradients that pass through it (cnn.*, embedding.*, layer 0's
+in_proj_*) are no float32 quantity -- stock float32 autograd is off by up to eight times the gradient there -- so they are asserted
+finite and their error is printed, and the other parameters are checked. At n = 1 the softmax is exactly 1 and all of them are
+checked. The PEAKED-ATTENTION cases (REGIME_CASES of test_gpu_qnet_batch.py) lie in between, every parameter checked and the
+yardstick held to (0, 1e-5]: 'mid' boards (codes 0..7: mean max-P 0.19 - 0.31), full boards under the 'conditioned' module
+(cnn[0].weight x 2^-10: codes up to 17 in conv1's weight gradient, logits -111 .. 37, max-P about 2 / n) and 'distinct' (mid, three
+layers whose tensors differ from layer to layer, which a fresh nn.TransformerEncoder's do not), at n = 17, 257 and 1,025 (four
+boards per thread in conv1's weight gradient). tests/test_qnet_grad_host.py asserts on the CPU that the cases are in these regimes.
+
+Measured on an MI355X over the peaked-attention cases: 0.50 - 1.93 x the case's yardstick (8.1e-7 .. 4.2e-6), at most 3.86 x a
+tensor's own float32 error (layer 0's in_proj_weight, mid boards at n = 1,025); per case in docs/LOG.md R22.1."""
 import copy
 import functools
 
@@ -29,7 +38,8 @@ import torch
 
 import qnet_grad_ref as R
 from conftest import load_golden
-from test_gpu_qnet_batch import FAIR_F32, MATRIX_CASES, MATRIX_IDS, MODEL_SEED, RAGGED, case_boards, device_net, matrix_boards, matrix_net
+from test_gpu_qnet_batch import (FAIR_F32, MATRIX_CASES, MATRIX_IDS, MODEL_SEED, RAGGED, REGIME_CASES, REGIME_IDS, REGIMES, case_boards,
+                                 device_net, matrix_boards, matrix_net, regime_boards, regime_model, regime_net)
 from test_policy_host import random_boards
 from test_qnet_host import golden_model, random_model
 
@@ -68,6 +78,17 @@ def matrix_case(dim_ff, layers, n, kind):
     m64, m32 = copy.deepcopy(model).double(), copy.deepcopy(model).float()
     a, t, w = R.case_inputs(m64, boards)
     return boards, a, t, w, R.stock_loss_grad(m64, boards, a, t, w), R.stock_loss_grad(m32, boards, a, t, w)
+
+
+@functools.lru_cache(maxsize=None)
+def regime_case(regime, dim_ff, layers, n):
+    """matrix_case for a peaked-attention case of test_gpu_qnet_batch.py ('mid' boards, or full boards under the conditioned
+    module); the float64 module comes last for the regime test of test_qnet_grad_host.py (shared, never modified)."""
+    model = regime_model(regime, dim_ff, layers)
+    boards = regime_boards(regime, n)
+    m64, m32 = copy.deepcopy(model).double(), copy.deepcopy(model).float()
+    a, t, w = R.case_inputs(m64, boards)
+    return boards, a, t, w, R.stock_loss_grad(m64, boards, a, t, w), R.stock_loss_grad(m32, boards, a, t, w), m64
 
 
 def split(net, grad):
@@ -171,6 +192,26 @@ def test_shape_matrix_with_canaries(case):
     assert 0 < bound / R.F32_FACTOR <= FAIR_F32, "stock float32 autograd is no fair yardstick on this case: %.3g" % (bound / R.F32_FACTOR)
     if n == 4096:
         check_repeatable(net, boards, a, t, w)
+
+
+@pytest.mark.parametrize("case", REGIME_CASES, ids=REGIME_IDS)
+def test_peaked_attention_with_canaries(case):
+    """Every tensor under a layer-0 softmax that is neither uniform nor one-hot: the attention backward's dS, and through it the
+    embedding's and the three convolution backward kernels' results, on mid boards (codes 0..7) and, under the conditioned
+    module, on full boards (codes up to 17, logits past float32 exp's overflow, several boards per thread in conv1's weight
+    gradient at n = 1,025). The yardstick must be a fair one, as on the shape matrix."""
+    regime, dim_ff, layers, n = case
+    net = regime_net(regime, dim_ff, layers)
+    boards, a, t, w, want, f32, _ = regime_case(*case)
+    bound = check(run_with_canaries(net, boards, a, t, w), want, f32, True, "%s, dim_ff %d L %d n=%d" % case)
+    assert 0 < bound / R.F32_FACTOR <= FAIR_F32, "stock float32 autograd is no fair yardstick on this case: %.3g" % (bound / R.F32_FACTOR)
+
+
+@pytest.mark.parametrize("regime", REGIMES)
+def test_peaked_attention_is_repeatable(regime):
+    net = regime_net(regime, 64, 2)
+    boards, a, t, w = regime_case(regime, 64, 2, 257)[:4]
+    check_repeatable(net, boards, a, t, w)
 
 
 @pytest.mark.parametrize("n", (1, 17))

@@ -5,8 +5,9 @@ forward's own Q, the greedy decisions against qnet.forward_reference in float64,
 the id split, canaries past n, and evaluate_qnet. The checks the game kernels have in common are tests/play_harness.py's; this
 file holds the networks, the shapes, the seeds, the bounds, select_action in NumPy and the tests that have no sibling.
 
-The networks carry the hash-derived weights of tests/qnet_weights.py: the fixture's (dim_ff 2048, 2 layers) and a small one
-(dim_ff 32, 1 layer)."""
+The networks carry the hash-derived weights of tests/qnet_weights.py: the fixture's (dim_ff 2048, 2 layers), a small one
+(dim_ff 32, 1 layer) and one that is no power of two (dim_ff 96, 3 layers: an odd number of 32-feature slices and a third layer's
+offsets in the packed blob)."""
 from functools import partial
 
 import numpy as np
@@ -23,6 +24,9 @@ from test_qnet_host import RefSpelling, bf16_round, golden_model
 pytestmark = pytest.mark.gpu
 
 _MODELS, _NETS = {}, {}
+SHAPES = {"small": (32, 1), "odd": (96, 3)}
+FUSED_CASES = ([(e, p, w) for w in ("fixture", "small") for p in ("f32", "bf16") for e in (0.0, 0.25, 1.0)]
+               + [(0.25, p, "odd") for p in ("f32", "bf16")])
 
 DEAD = [1, 2, 1, 2, 2, 1, 2, 1, 1, 2, 1, 2, 2, 1, 2, 1]                 # full, no merge: no valid move
 ONLY_RIGHT = [1, 2, 1, 0, 2, 1, 2, 0, 1, 2, 1, 0, 2, 1, 2, 0]
@@ -32,14 +36,14 @@ BIASED_LEFT_RIGHT = [1, 1, 2, 3, 2, 3, 1, 2, 1, 2, 3, 1, 2, 1, 2, 8]    # 256 in
 
 
 def hash_model(network):
-    """RefSpelling in float64 eval mode, on the CPU, carrying the hash-derived weights: the fixture's network or the small one."""
+    """RefSpelling in float64 eval mode, on the CPU, carrying the hash-derived weights: the fixture's network or one of SHAPES."""
     if network not in _MODELS:
         if network == "fixture":
             model = golden_model()[2]
         else:
-            model = RefSpelling(32, 1).double()
+            model = RefSpelling(*SHAPES[network]).double()
             shapes = [(k, tuple(v.shape)) for k, v in model.state_dict().items()]
-            assert shapes == qw.reference_shapes(32, 1)
+            assert shapes == qw.reference_shapes(*SHAPES[network])
             model.load_state_dict({k: torch.from_numpy(v) for k, v in qw.state_dict(shapes).items()})
             model = model.eval()
         _MODELS[network] = model
@@ -118,9 +122,7 @@ def test_select_launch_against_numpy(g2048, oracle):
     assert torch.equal(net.act(b)[0], greedy)
 
 
-@pytest.mark.parametrize("network", ["fixture", "small"])
-@pytest.mark.parametrize("precision", ["f32", "bf16"])
-@pytest.mark.parametrize("epsilon", [0.0, 0.25, 1.0])
+@pytest.mark.parametrize("epsilon,precision,network", FUSED_CASES, ids=["%s-%s-%s" % c for c in FUSED_CASES])
 def test_fused_equals_unfused(g2048, epsilon, precision, network):
     net = device_net(network, precision)
     for n, cap in ((1, 2000), (31, 2000), (33, 2000), (129, 2000), (4097, 2000), (4097, 37)):

@@ -1,5 +1,6 @@
 """g2048_tpolicy_forward on the MI355X: the reference's transformer class on the fixture's weights (tests/golden/tpolicy.npz),
-the bench shape with random weights against the module's own CPU f64 forward at ragged sizes, position independence and
+the bench shape with random weights against the module's own CPU f64 forward at ragged sizes, two shapes that are no power of two
+(dim_ff 96 with one layer, 160 with three: the packed blob's odd slice counts and third-layer offsets), position independence and
 determinism bit for bit, the RolloutCollector boards hook, in-place refresh under a captured rollout graph, and argument
 validation.
 
@@ -15,7 +16,7 @@ import torch
 
 from test_gpu_policy import TOL, _collector_state, _start_from, _traj
 from test_gpu_rollout import TinyTransformerPolicy, replay_and_check
-from test_policy_host import random_boards
+from test_policy_host import distinct_layers, random_boards
 from test_tpolicy_host import bf16_round, golden_model, scale_heads
 
 pytestmark = pytest.mark.gpu
@@ -123,6 +124,47 @@ def test_one_layer_dim_ff_32(precision):
     assert pol.dim_ff == 32 and pol.n_layers == 1
     p, v = pol(torch.from_numpy(boards).to(DEV))
     check(precision, p.cpu().numpy(), v.cpu().numpy(), truth[0], truth[1], rounded, "L=1 dim_ff=32")
+
+
+# The packed path away from powers of two: 96 = three 32-feature slices of the feed-forward pair (an odd count; linear2 with three
+# bf16 chunks, fragment index o * c2 + c with c2 = 6 or 3), 160 = five slices with a second and a third layer's offsets into the
+# fragments and the f32 section.
+PACKED_SHAPES = [(96, 1), (160, 3)]
+
+
+@functools.lru_cache(maxsize=None)
+def packed_shape_case(dim_ff, layers):
+    """A random-init model of the shape with every layer's tensors its own (distinct_layers: a fresh module's layers are copies
+    of one), 257 boards and their CPU forwards (shared, never modified)."""
+    model = tiny_model(2, dim_ff=dim_ff, num_layers=layers)
+    distinct_layers(model.encoder.layers, 5)
+    boards = random_boards(257, 11)
+    truth, rounded = cpu_forwards(model, boards)
+    return model.float(), boards, truth, rounded
+
+
+@pytest.mark.parametrize("precision", ["f32", "bf16"])
+@pytest.mark.parametrize("shape", PACKED_SHAPES, ids=["ff%d-L%d" % s for s in PACKED_SHAPES])
+def test_packed_shape_matrix_with_canaries(shape, precision):
+    import copy
+    from g2048 import DeviceTransformerPolicy, ops
+    dim_ff, layers = shape
+    model, all_boards, truth, rounded = packed_shape_case(dim_ff, layers)
+    pol = DeviceTransformerPolicy(copy.deepcopy(model).to(DEV), precision=precision)
+    assert (pol.dim_ff, pol.n_layers) == shape
+    for n in (17, 257):
+        b = torch.from_numpy(all_boards[:n]).to(DEV)
+        probs = torch.full((n + 67, 4), 7.0, device=DEV)
+        value = torch.full((n + 67, 1), 7.0, device=DEV)
+        ops.tpolicy_forward(b, pol.packed, dim_ff, layers, precision, probs=probs[:n], value=value[:n])
+        torch.cuda.synchronize()
+        assert torch.all(probs[n:] == 7.0) and torch.all(value[n:] == 7.0), "rows past n were written (n = %d)" % n
+        check(precision, probs[:n].cpu().numpy(), value[:n].cpu().numpy(), truth[0][:n], truth[1][:n],
+              (rounded[0][:n], rounded[1][:n]), "dim_ff %d L %d n=%d" % (dim_ff, layers, n))
+    if layers == 3:
+        for i in (0, 130, 256):                              # alone: another wavefront and block than in the large call
+            p, v = pol(b[i:i + 1].clone())
+            assert torch.equal(p[0], probs[i]) and torch.equal(v[0], value[i]), "board %d alone differs from row %d of the large call" % (i, i)
 
 
 @pytest.mark.parametrize("precision", ["f32", "bf16"])

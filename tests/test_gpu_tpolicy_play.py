@@ -5,7 +5,8 @@ tests/play_harness.py's, shared with the other three game kernels; this file hol
 bounds.
 
 The networks carry the hash-derived weights of tests/tpolicy_weights.py: the fixture's (dim_ff 2048, 2 layers), a small one
-(dim_ff 32, 1 layer) and the bench shape (dim_ff 128, 2 layers)."""
+(dim_ff 32, 1 layer), the bench shape (dim_ff 128, 2 layers) and one that is no power of two (dim_ff 96, 3 layers: an odd number
+of 32-feature slices and a third layer's offsets in the packed blob)."""
 from functools import partial
 
 import pytest
@@ -18,7 +19,9 @@ from test_tpolicy_host import RefSpelling
 
 pytestmark = pytest.mark.gpu
 
-SHAPES = {"fixture": (2048, 2), "small": (32, 1), "bench": (128, 2)}
+SHAPES = {"fixture": (2048, 2), "small": (32, 1), "bench": (128, 2), "odd": (96, 3)}
+FUSED_CASES = ([(m, p, w) for w in ("fixture", "small") for p in ("f32", "bf16") for m in ("masked", "unmasked", "greedy")]
+               + [("masked", p, "odd") for p in ("f32", "bf16")])
 _MODELS, _POLICIES = {}, {}
 
 
@@ -46,9 +49,7 @@ def policy(network, precision):
 play = partial(H.play, H.TPOLICY)
 
 
-@pytest.mark.parametrize("network", ["fixture", "small"])
-@pytest.mark.parametrize("precision", ["f32", "bf16"])
-@pytest.mark.parametrize("mode", ["masked", "unmasked", "greedy"])
+@pytest.mark.parametrize("mode,precision,network", FUSED_CASES, ids=["%s-%s-%s" % c for c in FUSED_CASES])
 def test_fused_equals_unfused(g2048, mode, precision, network):
     pol = policy(network, precision)
     for n, cap in ((1, 2000), (15, 2000), (17, 2000), (4097, 2000), (4097, 37)):

@@ -70,6 +70,19 @@ def random_boards(n, seed=0):
     return b
 
 
+def distinct_layers(layers, seed):
+    """nn.TransformerEncoder deep-copies one layer, so the layers of a fresh module carry the SAME weights (and zero attention
+    biases): a kernel that read layer 1's weights for layer 2 would compute the same thing. Adds to every parameter of every given
+    layer its own uniform draws from (-0.05, 0.05), in place, so that each layer's tensors are its own and no bias is zero."""
+    import torch
+    g = torch.Generator().manual_seed(seed)
+    with torch.no_grad():
+        for layer in layers:
+            for p in layer.parameters():
+                p.add_(((torch.rand(p.shape, generator=g, dtype=torch.float64) - 0.5) * 0.1).to(p.dtype))
+    return layers
+
+
 def numpy_forward(sd, x, batchnorm, softmax):
     """f64 NumPy forward of the reference layout straight from a state dict (no folding): the independent yardstick."""
     g = {k: np.asarray(v, dtype=np.float64) for k, v in sd.items()}

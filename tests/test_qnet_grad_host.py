@@ -6,7 +6,9 @@ the C-ABI's argument validation and workspace arithmetic without a device. The k
 
 Full boards (tiles up to 131,072) at n >= 2: the parameters upstream of layer 0's nearly one-hot softmax have gradients that
 even float64 reproduces to 1e-8 only between two spellings of the same function, and float32 not at all; they are compared on
-the early boards (codes 0..3) and at n = 1, and the other parameters everywhere."""
+the early boards (codes 0..3) and at n = 1, and the other parameters everywhere. Early boards leave layer 0's attention uniform;
+the GPU tests' peaked-attention cases (mid boards, the conditioned module on full boards) are held here to the regime they claim:
+the spread of layer 0's softmax, its logits' range, the codes on the boards and a fair stock float32, from the float64 module alone."""
 import ctypes as C
 
 import numpy as np
@@ -15,6 +17,8 @@ import torch
 
 import qnet_grad_ref as R
 from conftest import load_golden
+from test_gpu_qnet_batch import FAIR_F32, REGIME_CASES, REGIME_IDS
+from test_gpu_qnet_grad import regime_case
 from test_policy_host import random_boards
 from test_qnet_host import RefSpelling, golden_model, random_model
 
@@ -114,6 +118,36 @@ def test_fixture_pins_both_huber_branches_every_action_and_a_fair_float32():
         else:
             assert err[~up].max() <= 1e-5
             print("%s: stock float32 autograd upstream of the layer-0 softmax is off by %.3g x max|g| (not a float32 quantity)" % (case, err[up].max()))
+
+
+@pytest.mark.parametrize("case", REGIME_CASES, ids=REGIME_IDS)
+def test_peaked_attention_cases_are_in_the_regime_they_claim(case):
+    """The conditions on the inputs of the GPU tests' peaked-attention cases, from the float64 module alone: layer 0's softmax
+    spread over a few keys, neither uniform (1 / n) nor one-hot, and stock float32 autograd a fair yardstick for every tensor."""
+    regime, dim_ff, layers, n = case
+    boards, _, _, _, g64, g32, m64 = regime_case(*case)
+    logits, P = R.layer0_attention(m64, boards)
+    assert P.shape == (8, n, n) and np.abs(P.sum(-1) - 1).max() <= 1e-12
+    top = P.max(-1)
+    mean_top, one_hot, yard = top.mean(), (top > 0.999).mean(), R.ratios(g32[3], g64[3]).max()
+    largest = np.abs(logits).max()
+    print("%s, dim_ff %d L %d n=%d: layer-0 logits %.3g .. %.3g, mean max-P %.3g (1/n = %.3g), one-hot rows %.3g, codes up to %d, "
+          "yardstick %.3g" % (case + (logits.min(), logits.max(), mean_top, 1 / n, one_hot, boards.max(), yard)))
+    assert 0 < yard <= FAIR_F32, "stock float32 autograd is no fair yardstick on this case: %.3g" % yard
+    if regime in ("mid", "distinct"):
+        layers1 = list(m64.transformer.layers[1:])
+        same = all(torch.equal(x, y) for a, b in zip(layers1, layers1[1:]) for x, y in zip(a.parameters(), b.parameters()))
+        assert same == (regime == "mid"), "a fresh module's layers are copies of one; the 'distinct' module's must not be"
+        assert boards.max() == 7
+        assert mean_top >= 0.15 and one_hot <= 0.01
+    else:
+        assert one_hot <= 0.05
+        # the largest logit in magnitude. It is negative (-111; the largest positive one is 37): a row spans more than float32 exp's
+        # range, so a shift by anything below the row's maximum overflows, but exp of the unshifted logits does not; a softmax
+        # without its max subtraction is caught by the full boards under the stock module (logits 1e9), not by these cases
+        assert largest > 88.8, "every layer-0 logit is within float32 exp's range: %.3g" % largest
+        assert boards.max() == 17 and (boards >= 12).sum() >= 16
+        assert all(np.abs(g).max() > 0 for g in g64[3][:R.N_UPSTREAM])
 
 
 class Stub:
