@@ -1,0 +1,544 @@
+// g2048_ppo_grad.hip -- the gradient half of PPOAgent.update (agents/ppo_agent.py:357-400) on the device: the TRAINING-mode
+// forward of the reference's actor and critic (16-256-128-64-{4|1}, BatchNorm1d on batch statistics after the first two ReLUs,
+// its running statistics moving by momentum 0.1), the returns / advantages block, the clipped-surrogate + value + entropy loss
+// and the backward pass through both networks, the gradients written in the networks' plain parameter layout (include/g2048.h),
+// where a stock torch optimiser reads them through views. C-ABI: g2048_ppo_train_workspace / g2048_ppo_forward_train /
+// g2048_ppo_advantages / g2048_ppo_loss_grad. The reference's live dropout is left out, as everywhere in this library. f32 only.
+//
+// One phase per launch, per network:
+//   fc1       relu(x W^T + b) for K = 16: one chunk of the f32 matrix cores' product, one wavefront a 16-row x 16-feature tile
+//   bn        batch statistics and the normalised rows on the VALU: a block 32 features, 32 row groups; a thread adds its rows in
+//             eight partial sums in a fixed order, the block combines the groups pairwise. Mean and rstd are kept for the backward.
+//   fc2, fc3  qb_linear_kernel (g2048_qnet_batch_fwd.h)
+//   head      a thread a row: fc4 (K = 64, 4 or 1 outputs) on the VALU, softmax; with the loss asked for, the row's loss terms,
+//             d loss / d logits and the gradient into relu(fc3)'s output with its mask (M = 4 or 1 is below qg_dx_kernel's tile)
+//   dw, dx    qg_dw_kernel / qg_dx_kernel (g2048_grad_products.h)
+//   bn_bwd    dgamma = sum dy xhat, dbeta = sum dy, dx = gamma rstd (dy - dbeta / n - xhat dgamma / n) x the ReLU mask below it,
+//             the sums as in bn
+//   loss      one block's fixed-order sums of the rows' terms
+// n == 1: the reference skips both BatchNorms; so does this (their gradients are written as 0, the running statistics stay).
+// No atomics, no split-K across blocks, no block waits on another; every output element is one fixed-order accumulation, so two
+// calls give the same bits; nothing past row n or past the stated sizes is read or written, and no row past n of the workspace
+// is relied on. The gradient buffers are overwritten, never accumulated into. Compile with -ffp-contract=off.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+
+#include "../../include/g2048.h"
+#include "g2048_grad_products.h"
+#include "g2048_host.h"
+#include "g2048_mfma.h"
+#include "g2048_qnet_batch_fwd.h"
+
+namespace {
+
+constexpr int kIn = 16, kH1 = 256, kH2 = 128, kH3 = 64;
+// plain layout of one network, in floats (include/g2048.h); fc4.bias follows fc4.weight's 64 n_out floats
+constexpr int kFc1W = 0, kFc1B = kFc1W + kH1 * kIn, kBn1W = kFc1B + kH1, kBn1B = kBn1W + kH1, kFc2W = kBn1B + kH1, kFc2B = kFc2W + kH2 * kH1,
+              kBn2W = kFc2B + kH2, kBn2B = kBn2W + kH2, kFc3W = kBn2B + kH2, kFc3B = kFc3W + kH3 * kH2, kFc4W = kFc3B + kH3;
+static_assert(kFc4W == 46272, "the plain layout of include/g2048.h");
+constexpr int kRun1 = 0, kRun2 = 2 * kH1, kRunFloats = 2 * kH1 + 2 * kH2;      // running: mean1 var1 mean2 var2
+constexpr float kBnEps = 1e-5f, kMomentum = 0.1f;
+
+// workspace of one network, in floats, every array [np] rows (np = n rounded up to a tile of 16; rows past n are never touched)
+struct NetWorkspace {
+    size_t np;
+    explicit NetWorkspace(size_t n) : np((n + 15) / 16 * 16) {}
+    size_t h1() const { return 0; }                                   // relu(fc1 x)
+    size_t b1() const { return h1() + np * kH1; }                     // BN1's output
+    size_t h2() const { return b1() + np * kH1; }
+    size_t b2() const { return h2() + np * kH2; }
+    size_t h3() const { return b2() + np * kH2; }
+    size_t out() const { return h3() + np * kH3; }                    // [np][4]: probabilities or values, when the caller keeps none
+    size_t dz() const { return out() + np * 4; }                      // [np][n_out]
+    size_t d3() const { return dz() + np * 4; }
+    size_t d2() const { return d3() + np * kH3; }
+    size_t d1() const { return d2() + np * kH2; }
+    size_t stat() const { return d1() + np * kH1; }                   // mean1 rstd1 mean2 rstd2
+    size_t floats() const { return stat() + kRunFloats; }
+};
+// the whole workspace: actor, critic, then the rows' three loss terms
+inline size_t workspace_floats(size_t n) { return 2 * NetWorkspace(n).floats() + 3 * NetWorkspace(n).np; }
+
+// -------------------------------------------------------------------------------------------------------------- fc1 --
+// Y [n][256] = relu(X [n][16] W^T + b): qb_linear_kernel's tile for one chunk of K. Lane (col, g): the A operand W[16 o + col][4 g ..],
+// the B operand X[row][4 g ..]; grid (4, row tiles), four wavefronts a block.
+__global__ __launch_bounds__(256) void pg_fc1_kernel(const float *__restrict__ X, const float *__restrict__ W, const float *__restrict__ bias,
+                                                      float *__restrict__ Y, int n)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4, col = lane & 15;
+    const int o = (int)blockIdx.x * 4 + wave;
+    const int row = (int)blockIdx.y * 16 + col;
+    const bool live = row < n;
+    f4 acc = load_w(bias + 16 * o + 4 * g);
+    const f4 w = load_w(W + (size_t)(16 * o + col) * kIn + 4 * g), x = live ? load_f4(X + (size_t)row * kIn + 4 * g) : splat(0.0f);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w[r], x[r], acc, 0, 0, 0);
+    if (live) *reinterpret_cast<f4 *>(Y + (size_t)row * kH1 + 16 * o + 4 * g) = relu(acc);
+}
+
+// -------------------------------------------------------------------------------------------------------- BatchNorm --
+// A block of 1,024 = 32 features x 32 row groups; thread (group, feature) owns the rows group, group + 32, ..: partial sum u of eight
+// takes every eighth of them (eight independent loads in flight), the eight are combined pairwise, then the 32 groups pairwise
+// through LDS. The same on every thread of a feature.
+constexpr int kBnGroups = 32, kBnParts = 8;
+
+// body(u, row) for every row of the thread, u = the partial sum the row belongs to
+template <class Body>
+__device__ inline void bn_rows(int grp, int n, Body body)
+{
+    int i = grp;
+    for (; i + (kBnParts - 1) * kBnGroups < n; i += kBnParts * kBnGroups)
+#pragma unroll
+        for (int u = 0; u < kBnParts; ++u) body(u, i + kBnGroups * u);
+#pragma unroll
+    for (int u = 0; u < kBnParts - 1; ++u)
+        if (i + kBnGroups * u < n) body(u, i + kBnGroups * u);
+}
+
+__device__ inline float bn_block_sum(const float (&a)[kBnParts], float (&red)[kBnGroups][32], int grp, int f)
+{
+    __syncthreads();                                 // the previous sum's readers are done with red
+    red[grp][f] = ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
+    __syncthreads();
+    float r[kBnGroups];
+#pragma unroll
+    for (int i = 0; i < kBnGroups; ++i) r[i] = red[i][f];
+#pragma unroll
+    for (int w = kBnGroups / 2; w > 0; w >>= 1)
+#pragma unroll
+        for (int i = 0; i < w; ++i) r[i] = r[2 * i] + r[2 * i + 1];
+    return r[0];
+}
+
+// Y = (X - mean) rstd gamma + beta over the n rows of X [n][F] (n >= 2), mean and the biased variance of the batch; stat: mean [F],
+// rstd [F] kept for the backward. running (optional): mean [F], var [F], moved by momentum 0.1 towards the batch mean and the
+// UNBIASED variance, as torch's training-mode BatchNorm1d moves them. grid F / 32.
+__global__ __launch_bounds__(1024) void pg_bn_kernel(const float *__restrict__ X, int F, const float *__restrict__ gamma, const float *__restrict__ beta,
+                                                      float *__restrict__ Y, float *__restrict__ stat, float *__restrict__ running, int n)
+{
+    __shared__ float red[kBnGroups][32];
+    const int f = threadIdx.x & 31, grp = threadIdx.x >> 5, feat = (int)blockIdx.x * 32 + f;
+    const float *x = X + feat;
+    float a[kBnParts];
+#pragma unroll
+    for (int u = 0; u < kBnParts; ++u) a[u] = 0.0f;
+    bn_rows(grp, n, [&](int u, int row) { a[u] += x[(size_t)row * F]; });
+    const float mean = bn_block_sum(a, red, grp, f) / (float)n;
+#pragma unroll
+    for (int u = 0; u < kBnParts; ++u) a[u] = 0.0f;
+    bn_rows(grp, n, [&](int u, int row) {
+        const float d = x[(size_t)row * F] - mean;
+        a[u] += d * d;
+    });
+    const float ss = bn_block_sum(a, red, grp, f);
+    const float rstd = 1.0f / sqrtf(ss / (float)n + kBnEps), ga = gamma[feat], be = beta[feat];
+    for (int i = grp; i < n; i += kBnGroups) Y[(size_t)i * F + feat] = (x[(size_t)i * F] - mean) * rstd * ga + be;
+    if (grp == 0) {
+        stat[feat] = mean;
+        stat[F + feat] = rstd;
+        if (running) {
+            running[feat] = (1.0f - kMomentum) * running[feat] + kMomentum * mean;
+            running[F + feat] = (1.0f - kMomentum) * running[F + feat] + kMomentum * (ss / (float)(n - 1));
+        }
+    }
+}
+
+// The backward of pg_bn_kernel, in place: D [n][F] holds d loss / d Y and leaves as d loss / d H, where X = relu(H) is the
+// BatchNorm's input (zero where X <= 0). dgamma [F] = sum dy xhat, dbeta [F] = sum dy with xhat = (X - mean) rstd from stat.
+__global__ __launch_bounds__(1024) void pg_bn_bwd_kernel(float *__restrict__ D, const float *__restrict__ X, int F, const float *__restrict__ gamma,
+                                                          const float *__restrict__ stat, float *__restrict__ dgamma, float *__restrict__ dbeta, int n)
+{
+    __shared__ float red[kBnGroups][32];
+    const int f = threadIdx.x & 31, grp = threadIdx.x >> 5, feat = (int)blockIdx.x * 32 + f;
+    const float *x = X + feat;
+    float *d = D + feat;
+    const float mean = stat[feat], rstd = stat[F + feat];
+    float a[kBnParts], b[kBnParts];
+#pragma unroll
+    for (int u = 0; u < kBnParts; ++u) a[u] = b[u] = 0.0f;
+    bn_rows(grp, n, [&](int u, int row) {
+        const float dy = d[(size_t)row * F];
+        a[u] += dy;
+        b[u] += dy * ((x[(size_t)row * F] - mean) * rstd);
+    });
+    const float db = bn_block_sum(a, red, grp, f), dg = bn_block_sum(b, red, grp, f);
+    const float scale = gamma[feat] * rstd, mb = db / (float)n, mg = dg / (float)n;
+    for (int i = grp; i < n; i += kBnGroups) {
+        const float xv = x[(size_t)i * F];
+        const float v = scale * (d[(size_t)i * F] - mb - (xv - mean) * rstd * mg);
+        d[(size_t)i * F] = xv > 0.0f ? v : 0.0f;
+    }
+    if (grp == 0) {
+        dgamma[feat] = dg;
+        dbeta[feat] = db;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------ heads --
+// z[j] = fc4.bias[j] + fc4.weight[j] . h over K = 64: four partial sums (k & 3) of fused multiply-adds, combined pairwise
+template <int O>
+__device__ inline void fc4_row(const float *__restrict__ h, const float *__restrict__ W, float (&hv)[kH3], float (&z)[O])
+{
+#pragma unroll
+    for (int k = 0; k < kH3; k += 4) {
+        const f4 v = load_f4(h + k);
+        hv[k] = v[0], hv[k + 1] = v[1], hv[k + 2] = v[2], hv[k + 3] = v[3];
+    }
+#pragma unroll
+    for (int j = 0; j < O; ++j) {
+        float a[4] = {W[O * kH3 + j], 0.0f, 0.0f, 0.0f};
+#pragma unroll
+        for (int k = 0; k < kH3; k += 4)
+#pragma unroll
+            for (int u = 0; u < 4; ++u) a[u] = fmaf(W[j * kH3 + k + u], hv[k + u], a[u]);
+        z[j] = (a[0] + a[1]) + (a[2] + a[3]);
+    }
+}
+
+// d3[k] = (sum_j dz[j] fc4.weight[j][k]) where h[k] > 0, else 0
+template <int O>
+__device__ inline void fc4_row_dx(const float (&dz)[O], const float *__restrict__ W, const float (&hv)[kH3], float *__restrict__ d3)
+{
+#pragma unroll
+    for (int k = 0; k < kH3; k += 4) {
+        f4 v;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            float s = dz[0] * W[k + u];
+#pragma unroll
+            for (int j = 1; j < O; ++j) s = fmaf(dz[j], W[j * kH3 + k + u], s);
+            v[u] = hv[k + u] > 0.0f ? s : 0.0f;
+        }
+        *reinterpret_cast<f4 *>(d3 + k) = v;
+    }
+}
+
+// The actor's head, a thread a row: p = softmax(fc4 h3) to probs. With `actions` (the loss asked for):
+//   q = p / sum(p); l = log(clamp(q, eps, 1 - eps)), eps = 2^-23 (Categorical(probs=p) in f32); ratio = exp(l[a] - old);
+//   term = min(ratio A, clamp(ratio, 1 - clip, 1 + clip) A); ent = -sum l q; loss share = -term / n - ent_coef ent / n
+// and its derivative: minimum splits a tie's gradient in halves, clamp passes it on [lo, hi] (edges included), a binding clamp of q
+// passes none; back through the renormalisation and the softmax to dz [row][4] and through fc4 to d3 [row][64].
+__global__ __launch_bounds__(64) void pg_actor_head_kernel(const float *__restrict__ h3, const float *__restrict__ W, float4 *__restrict__ probs,
+                                                            const long long *__restrict__ actions, const float *__restrict__ old_log_probs,
+                                                            const float *__restrict__ adv, float clip, float ent_coef, float *__restrict__ term,
+                                                            float *__restrict__ ent, float4 *__restrict__ dz_out, float *__restrict__ d3, int n)
+{
+    const int i = (int)blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    float hv[kH3], z[4];
+    fc4_row<4>(h3 + (size_t)i * kH3, W, hv, z);
+    const float4 p4 = softmax4(f4{z[0], z[1], z[2], z[3]});
+    probs[i] = p4;
+    if (!actions) return;
+    const float p[4] = {p4.x, p4.y, p4.z, p4.w};
+    const float eps = 1.1920928955078125e-07f, inv_n = 1.0f / (float)n;
+    const float s = ((p[0] + p[1]) + p[2]) + p[3];
+    const int a = (int)(actions[i] & 3);
+    float q[4], l[4], e = 0.0f;
+    bool open[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        q[j] = p[j] / s;
+        open[j] = q[j] >= eps && q[j] <= 1.0f - eps;
+        l[j] = logf(fminf(fmaxf(q[j], eps), 1.0f - eps));
+        e += l[j] * q[j];
+    }
+    const float A = adv[i], ratio = expf(l[a] - old_log_probs[i]), lo = 1.0f - clip, hi = 1.0f + clip;
+    const float s1 = ratio * A, s2 = fminf(fmaxf(ratio, lo), hi) * A;
+    term[i] = fminf(s1, s2);
+    ent[i] = -e;
+    const float g1 = s1 < s2 ? 1.0f : s1 == s2 ? 0.5f : 0.0f, g2 = s2 < s1 ? 1.0f : s1 == s2 ? 0.5f : 0.0f;
+    const float dratio = -inv_n * (g1 * A + (ratio >= lo && ratio <= hi ? g2 * A : 0.0f));
+    const float dla = dratio * ratio, ce = ent_coef * inv_n;
+    float gq[4], gp[4], dz[4], dot = 0.0f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const float dl = ce * q[j] + (j == a ? dla : 0.0f);                 // d loss / d l[j]: the entropy's l q, the taken action's ratio
+        gq[j] = ce * l[j] + (open[j] ? dl / q[j] : 0.0f);
+        dot += gq[j] * p[j];
+    }
+    float dot2 = 0.0f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        gp[j] = gq[j] / s - dot / (s * s);
+        dot2 += gp[j] * p[j];
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) dz[j] = p[j] * (gp[j] - dot2);
+    dz_out[i] = make_float4(dz[0], dz[1], dz[2], dz[3]);
+    fc4_row_dx<4>(dz, W, hv, d3 + (size_t)i * kH3);
+}
+
+// The critic's head: v = fc4 h3 to values. With `returns`: term = (v - returns)^2, dz = value_coef . 2 (v - returns) / n.
+__global__ __launch_bounds__(64) void pg_critic_head_kernel(const float *__restrict__ h3, const float *__restrict__ W, float *__restrict__ values,
+                                                             const float *__restrict__ returns, float value_coef, float *__restrict__ term,
+                                                             float *__restrict__ dz_out, float *__restrict__ d3, int n)
+{
+    const int i = (int)blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    float hv[kH3], z[1];
+    fc4_row<1>(h3 + (size_t)i * kH3, W, hv, z);
+    values[i] = z[0];
+    if (!returns) return;
+    const float d = z[0] - returns[i];
+    term[i] = d * d;
+    const float dz[1] = {value_coef * (2.0f * d) / (float)n};
+    dz_out[i] = dz[0];
+    fc4_row_dx<1>(dz, W, hv, d3 + (size_t)i * kH3);
+}
+
+// One block's fixed-order sums: thread t adds its rows t, t + 256, .. in order, then a fixed tree over the 256 threads, for each
+// of K arrays of n floats, `stride` apart; the sums are left in red[k][0].
+template <int K>
+__device__ inline void block_sums(const float *__restrict__ terms, size_t stride, int n, float (&red)[K][256])
+{
+    const int t = threadIdx.x;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        float v = 0.0f;
+        for (int i = t; i < n; i += 256) v += terms[k * stride + i];
+        red[k][t] = v;
+    }
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (t < s)
+#pragma unroll
+            for (int k = 0; k < K; ++k) red[k][t] += red[k][t + s];
+        __syncthreads();
+    }
+}
+
+// terms: the actor's min(..) [n], the critic's squared errors, the entropies. out = {loss, actor_loss, value_loss, entropy}
+__global__ __launch_bounds__(256) void pg_loss_kernel(const float *__restrict__ terms, size_t stride, float value_coef, float ent_coef,
+                                                       float *__restrict__ out, int n)
+{
+    __shared__ float red[3][256];
+    block_sums<3>(terms, stride, n, red);
+    if (threadIdx.x == 0) {
+        const float actor = -(red[0][0] / (float)n), value = red[1][0] / (float)n, entropy = red[2][0] / (float)n;
+        out[0] = actor + value_coef * value - ent_coef * entropy;
+        out[1] = actor;
+        out[2] = value;
+        out[3] = entropy;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------- advantages --
+// ppo_agent.py:368-373 in one block of 256: thread t keeps its rows t, t + 256, .. (at most 16) in registers. The mean and the
+// unbiased variance are the block's fixed-order sums (block_sums' order), the variance of the deviations from the mean.
+__global__ __launch_bounds__(256) void pg_advantages_kernel(const float *__restrict__ values, const float *__restrict__ next_values,
+                                                             const float *__restrict__ rewards, const float *__restrict__ dones, float gamma,
+                                                             float *__restrict__ returns_out, float *__restrict__ adv_out, int n)
+{
+    __shared__ float red[256];
+    constexpr int kRows = G2048_PPO_BATCH_MAX / 256;
+    const int t = threadIdx.x;
+    float adv[kRows], v = 0.0f;
+#pragma unroll
+    for (int u = 0; u < kRows; ++u) {
+        const int i = t + 256 * u;
+        adv[u] = 0.0f;
+        if (i < n) {
+            const float ret = rewards[i] + gamma * next_values[i] * (1.0f - dones[i]);
+            returns_out[i] = ret;
+            adv[u] = ret - values[i];
+            v += adv[u];
+        }
+    }
+    if (n > 1) {
+        red[t] = v;
+        __syncthreads();
+        for (int s = 128; s > 0; s >>= 1) {
+            if (t < s) red[t] += red[t + s];
+            __syncthreads();
+        }
+        const float mean = red[0] / (float)n;
+        __syncthreads();
+        v = 0.0f;
+#pragma unroll
+        for (int u = 0; u < kRows; ++u)
+            if (t + 256 * u < n) {
+                adv[u] -= mean;
+                v += adv[u] * adv[u];
+            }
+        red[t] = v;
+        __syncthreads();
+        for (int s = 128; s > 0; s >>= 1) {
+            if (t < s) red[t] += red[t + s];
+            __syncthreads();
+        }
+        const float denom = sqrtf(red[0] / (float)(n - 1)) + 1e-8f;
+#pragma unroll
+        for (int u = 0; u < kRows; ++u) adv[u] /= denom;
+    }
+#pragma unroll
+    for (int u = 0; u < kRows; ++u)
+        if (t + 256 * u < n) adv_out[t + 256 * u] = adv[u];
+}
+
+// ------------------------------------------------------------------------------------------------------------- host --
+struct Net {
+    const float *P;        // plain parameters
+    float *running;        // or null
+    float *G;              // gradient buffer, or null (forward only)
+    float *ws;             // this network's workspace
+    int n_out;
+};
+
+// the training-mode forward up to relu(fc3 ..), the activations kept in net.ws; returns where BN1's and BN2's outputs lie
+void launch_trunk(const Net &net, const float *states, int n, hipStream_t s)
+{
+    const NetWorkspace w((size_t)n);
+    const unsigned tiles = (unsigned)(w.np / 16);
+    const bool bn = n > 1;
+    float *h1 = net.ws + w.h1(), *b1 = bn ? net.ws + w.b1() : h1, *h2 = net.ws + w.h2(), *b2 = bn ? net.ws + w.b2() : h2, *h3 = net.ws + w.h3(),
+          *stat = net.ws + w.stat();
+    hipLaunchKernelGGL(pg_fc1_kernel, dim3(kH1 / 64, tiles), dim3(256), 0, s, states, net.P + kFc1W, net.P + kFc1B, h1, n);
+    if (bn)
+        hipLaunchKernelGGL(pg_bn_kernel, dim3(kH1 / 32), dim3(1024), 0, s, static_cast<const float *>(h1), kH1, net.P + kBn1W, net.P + kBn1B, b1, stat,
+                           net.running ? net.running + kRun1 : nullptr, n);
+    hipLaunchKernelGGL(qb_linear_kernel<true>, dim3(kH2 / 64, tiles), dim3(256), 0, s, static_cast<const float *>(b1), kH1, net.P + kFc2W,
+                       net.P + kFc2B, h2, kH2, n);
+    if (bn)
+        hipLaunchKernelGGL(pg_bn_kernel, dim3(kH2 / 32), dim3(1024), 0, s, static_cast<const float *>(h2), kH2, net.P + kBn2W, net.P + kBn2B, b2,
+                           stat + 2 * kH1, net.running ? net.running + kRun2 : nullptr, n);
+    hipLaunchKernelGGL(qb_linear_kernel<true>, dim3(kH3 / 64, tiles), dim3(256), 0, s, static_cast<const float *>(b2), kH2, net.P + kFc3W,
+                       net.P + kFc3B, h3, kH3, n);
+}
+
+// from dz [n][n_out] and d3 [n][64] (the head's) to every gradient of the network
+int launch_backward(const Net &net, const float *states, int n, hipStream_t s)
+{
+    const NetWorkspace w((size_t)n);
+    const unsigned tiles = (unsigned)(w.np / 16);
+    const bool bn = n > 1;
+    const float *P = net.P, *none = nullptr;
+    float *G = net.G;
+    const float *h1 = net.ws + w.h1(), *b1 = bn ? net.ws + w.b1() : h1, *h2 = net.ws + w.h2(), *b2 = bn ? net.ws + w.b2() : h2, *h3 = net.ws + w.h3(),
+                *stat = net.ws + w.stat(), *dz = net.ws + w.dz();
+    float *d3 = net.ws + w.d3(), *d2 = net.ws + w.d2(), *d1 = net.ws + w.d1();
+    const int O = net.n_out;
+    const auto dx = [&](const float *dY, int M, const float *W, int K, const float *mask, float *dX) {
+        hipLaunchKernelGGL(qg_dx_kernel, dim3((unsigned)(K + 63) / 64, tiles), dim3(256), 0, s, dY, M, W, K, none, mask, dX, n);
+    };
+    const auto dw = [&](const float *dY, int ldy, int M, const float *X, int K, float *dW, float *db) {
+        hipLaunchKernelGGL(qg_dw_kernel, dim3((unsigned)(K + 63) / 64, (unsigned)(M + 15) / 16), dim3(256), 0, s, dY, ldy, M, X, K, dW, db, n);
+    };
+    dw(dz, O, O, h3, kH3, G + kFc4W, G + kFc4W + O * kH3);
+    dw(d3, kH3, kH3, b2, kH2, G + kFc3W, G + kFc3B);
+    dx(d3, kH3, P + kFc3W, kH2, bn ? none : h2, d2);
+    if (bn)
+        hipLaunchKernelGGL(pg_bn_bwd_kernel, dim3(kH2 / 32), dim3(1024), 0, s, d2, h2, kH2, P + kBn2W, stat + 2 * kH1, G + kBn2W, G + kBn2B, n);
+    dw(d2, kH2, kH2, b1, kH1, G + kFc2W, G + kFc2B);
+    dx(d2, kH2, P + kFc2W, kH1, bn ? none : h1, d1);
+    if (bn)
+        hipLaunchKernelGGL(pg_bn_bwd_kernel, dim3(kH1 / 32), dim3(1024), 0, s, d1, h1, kH1, P + kBn1W, stat, G + kBn1W, G + kBn1B, n);
+    dw(d1, kH1, kH1, states, kIn, G + kFc1W, G + kFc1B);
+    if (!bn) {                                       // the reference's forward skips both BatchNorms for one row: no gradient
+        hipError_t e = hipMemsetAsync(G + kBn1W, 0, 2 * kH1 * sizeof(float), s);
+        if (e == hipSuccess) e = hipMemsetAsync(G + kBn2W, 0, 2 * kH2 * sizeof(float), s);
+        if (e != hipSuccess) return fail(G2048_ERR_HIP, "g2048_ppo_loss_grad: hipMemsetAsync: %s", hipGetErrorString(e));
+    }
+    return G2048_OK;
+}
+
+inline bool good_coef(float v) { return v >= 0.0f && std::isfinite(v); }
+
+}  // namespace
+
+extern "C" {
+
+size_t g2048_ppo_train_workspace(size_t n)
+{
+    if (n == 0 || n > G2048_PPO_BATCH_MAX) return 0;
+    return workspace_floats(n) * sizeof(float);
+}
+
+int g2048_ppo_forward_train(const float *states, const float *plain, float *running_or_null, int n_out, float *out, size_t n, void *workspace,
+                            void *stream)
+{
+    if (n == 0) return G2048_OK;
+    if (!states || !plain || !out || !workspace) return fail(G2048_ERR_ARG, "g2048_ppo_forward_train: null pointer");
+    if (!aligned(states, 16) || !aligned(plain, 16) || !aligned(workspace, 16) || !aligned(running_or_null, 4) ||
+        !aligned(out, n_out == 4 ? 16 : 4))
+        return fail(G2048_ERR_ARG, "g2048_ppo_forward_train: misaligned pointer (states, plain weights, workspace, probabilities: 16 bytes; "
+                                   "the rest: 4)");
+    if (n_out != 4 && n_out != 1) return fail(G2048_ERR_ARG, "g2048_ppo_forward_train: n_out must be 4 (actor) or 1 (critic)");
+    if (n > G2048_PPO_BATCH_MAX)
+        return fail(G2048_ERR_ARG, "g2048_ppo_forward_train: n must not exceed G2048_PPO_BATCH_MAX = %d (the batch statistics are the "
+                                   "whole batch's; a larger batch is not truncated)", G2048_PPO_BATCH_MAX);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int ni = (int)n;
+    const Net net{plain, running_or_null, nullptr, static_cast<float *>(workspace), n_out};
+    const float *h3 = net.ws + NetWorkspace(n).h3();
+    launch_trunk(net, states, ni, s);
+    if (n_out == 4)
+        hipLaunchKernelGGL(pg_actor_head_kernel, dim3(blocks_for(n, 64)), dim3(64), 0, s, h3, plain + kFc4W, reinterpret_cast<float4 *>(out),
+                           static_cast<const long long *>(nullptr), static_cast<const float *>(nullptr), static_cast<const float *>(nullptr), 0.0f,
+                           0.0f, static_cast<float *>(nullptr), static_cast<float *>(nullptr), static_cast<float4 *>(nullptr),
+                           static_cast<float *>(nullptr), ni);
+    else
+        hipLaunchKernelGGL(pg_critic_head_kernel, dim3(blocks_for(n, 64)), dim3(64), 0, s, h3, plain + kFc4W, out, static_cast<const float *>(nullptr),
+                           0.0f, static_cast<float *>(nullptr), static_cast<float *>(nullptr), static_cast<float *>(nullptr), ni);
+    return check_launch("g2048_ppo_forward_train");
+}
+
+int g2048_ppo_advantages(const float *values, const float *next_values, const float *rewards, const float *dones, float gamma,
+                         float *returns_out, float *adv_out, size_t n, void *stream)
+{
+    if (n == 0) return G2048_OK;
+    if (!values || !next_values || !rewards || !dones || !returns_out || !adv_out) return fail(G2048_ERR_ARG, "g2048_ppo_advantages: null pointer");
+    if (!aligned(values, 4) || !aligned(next_values, 4) || !aligned(rewards, 4) || !aligned(dones, 4) || !aligned(returns_out, 4) ||
+        !aligned(adv_out, 4))
+        return fail(G2048_ERR_ARG, "g2048_ppo_advantages: misaligned pointer (4 bytes)");
+    if (!std::isfinite(gamma)) return fail(G2048_ERR_ARG, "g2048_ppo_advantages: gamma must be finite");
+    if (n > G2048_PPO_BATCH_MAX)
+        return fail(G2048_ERR_ARG, "g2048_ppo_advantages: n must not exceed G2048_PPO_BATCH_MAX = %d (one block normalises the whole batch; "
+                                   "a larger batch is not truncated)", G2048_PPO_BATCH_MAX);
+    hipLaunchKernelGGL(pg_advantages_kernel, dim3(1), dim3(256), 0, static_cast<hipStream_t>(stream), values, next_values, rewards, dones, gamma,
+                       returns_out, adv_out, (int)n);
+    return check_launch("g2048_ppo_advantages");
+}
+
+int g2048_ppo_loss_grad(const float *states, const int64_t *actions, const float *old_log_probs, const float *advantages, const float *returns,
+                        const float *plain_actor, const float *plain_critic, float *running_actor_or_null, float *running_critic_or_null,
+                        float clip_epsilon, float value_coef, float entropy_coef, size_t n, float *grad_actor_out, float *grad_critic_out,
+                        float *loss_out, void *workspace, void *stream)
+{
+    if (n == 0) return G2048_OK;
+    if (!states || !actions || !old_log_probs || !advantages || !returns || !plain_actor || !plain_critic || !grad_actor_out ||
+        !grad_critic_out || !loss_out || !workspace)
+        return fail(G2048_ERR_ARG, "g2048_ppo_loss_grad: null pointer");
+    if (!aligned(states, 16) || !aligned(plain_actor, 16) || !aligned(plain_critic, 16) || !aligned(grad_actor_out, 16) ||
+        !aligned(grad_critic_out, 16) || !aligned(workspace, 16) || !aligned(actions, 8) || !aligned(old_log_probs, 4) ||
+        !aligned(advantages, 4) || !aligned(returns, 4) || !aligned(running_actor_or_null, 4) || !aligned(running_critic_or_null, 4) ||
+        !aligned(loss_out, 4))
+        return fail(G2048_ERR_ARG, "g2048_ppo_loss_grad: misaligned pointer (states, plain weights, gradients, workspace: 16 bytes; actions: 8; "
+                                   "the rest: 4)");
+    if (!good_coef(clip_epsilon) || !good_coef(value_coef) || !good_coef(entropy_coef))
+        return fail(G2048_ERR_ARG, "g2048_ppo_loss_grad: clip_epsilon, value_coef and entropy_coef must be finite and not negative");
+    if (n > G2048_PPO_BATCH_MAX)
+        return fail(G2048_ERR_ARG, "g2048_ppo_loss_grad: n must not exceed G2048_PPO_BATCH_MAX = %d (the batch statistics are the whole "
+                                   "batch's; a larger batch is not truncated)", G2048_PPO_BATCH_MAX);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int ni = (int)n;
+    const NetWorkspace w(n);
+    float *base = static_cast<float *>(workspace), *terms = base + 2 * w.floats();
+    const Net actor{plain_actor, running_actor_or_null, grad_actor_out, base, 4};
+    const Net critic{plain_critic, running_critic_or_null, grad_critic_out, base + w.floats(), 1};
+    launch_trunk(actor, states, ni, s);
+    launch_trunk(critic, states, ni, s);
+    hipLaunchKernelGGL(pg_actor_head_kernel, dim3(blocks_for(n, 64)), dim3(64), 0, s, static_cast<const float *>(actor.ws + w.h3()),
+                       plain_actor + kFc4W, reinterpret_cast<float4 *>(actor.ws + w.out()), reinterpret_cast<const long long *>(actions),
+                       old_log_probs, advantages, clip_epsilon, entropy_coef, terms, terms + 2 * w.np, reinterpret_cast<float4 *>(actor.ws + w.dz()),
+                       actor.ws + w.d3(), ni);
+    hipLaunchKernelGGL(pg_critic_head_kernel, dim3(blocks_for(n, 64)), dim3(64), 0, s, static_cast<const float *>(critic.ws + w.h3()),
+                       plain_critic + kFc4W, critic.ws + w.out(), returns, value_coef, terms + w.np, critic.ws + w.dz(), critic.ws + w.d3(), ni);
+    hipLaunchKernelGGL(pg_loss_kernel, dim3(1), dim3(256), 0, s, static_cast<const float *>(terms), w.np, value_coef, entropy_coef, loss_out, ni);
+    int rc = launch_backward(actor, states, ni, s);
+    if (rc == G2048_OK) rc = launch_backward(critic, states, ni, s);
+    return rc == G2048_OK ? check_launch("g2048_ppo_loss_grad") : rc;
+}
+
+}  // extern "C"

@@ -1,6 +1,7 @@
 // g2048_qnet_batch_fwd.h -- the forward kernels of the hybrid agent's Q-network on a BATCH of boards (one sequence of n tokens), shared
 // by g2048_qnet_batch.hip (the forward alone) and g2048_qnet_grad.hip (the forward that keeps its activations, then the gradient
-// pass). Device code, included by those two files and nothing else; every kernel is per translation unit. What the phases are and
+// pass); g2048_ppo_grad.hip takes qb_linear_kernel from here for the PPO networks' fc2 and fc3. Device code, included by those
+// three files and nothing else; every kernel is per translation unit. What the phases are and
 // why the weights are read from the plain buffer: the head of g2048_qnet_batch.hip. The outputs the gradient pass needs on top
 // (conv1's output, the attention rows' maximum and sum, the sums before the LayerNorms) are optional pointers that the forward
 // alone passes as null; they change no arithmetic.

@@ -15,9 +15,9 @@
 //   sum       the loss: one block's fixed-order sum of the n terms
 //   ln        LayerNorm backward for a tile of 16 boards (mean and rstd recomputed as the forward computes them), with the tile's
 //             share of dgamma = sum dy . xhat and dbeta = sum dy; `tiles` then adds the tiles' shares in order
-//   dx        dX = dY . W (+ the residual's other gradient path, or x the ReLU mask) on the f32 matrix cores, one wavefront a
+//   dx        (g2048_grad_products.h) dX = dY . W (+ the residual's other gradient path, or x the ReLU mask) on the f32 matrix cores, one wavefront a
 //             16-board x 16-feature tile, the A operand a column slice of the row-major W
-//   dw        dW[M][K] = sum_n dY[n][M] . X[n][K] and db = sum_n dY on the f32 matrix cores: the boards are the contraction, one
+//   dw        (g2048_grad_products.h) dW[M][K] = sum_n dY[n][M] . X[n][K] and db = sum_n dY on the f32 matrix cores: the boards are the contraction, one
 //             wavefront owns a 16 x 16 tile of dW over all n
 //   att_dq    one wavefront a (query tile, head): P recomputed from qkv with the forward's maximum and sum, D_i = sum dO_i . O_i,
 //             dS_ij = P_ij (dO_i . V_j - D_i), dQ_i = 1/4 sum_j dS_ij K_j
@@ -35,6 +35,7 @@
 
 #include "../../include/g2048.h"
 #include "g2048_host.h"
+#include "g2048_grad_products.h"
 #include "g2048_mfma.h"
 #include "g2048_qnet_batch_fwd.h"
 
@@ -74,9 +75,6 @@ struct GradWorkspace {
     size_t part() const { return term() + np; }                                        // [np / 16][256]
     size_t floats() const { return part() + np / 16 * 2 * kD; }
 };
-
-__device__ inline float sum4(f4 v) { return (v[0] + v[1]) + (v[2] + v[3]); }
-__device__ inline f4 sum8(const f4 (&a)[8]) { return ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7])); }
 
 // ------------------------------------------------------------------------------------------------------------- head --
 // One block a board, thread k feature k: d = q[a] - target, td, the derivative dq = w / n . clamp(d, -1, 1) at action a (a row of
@@ -164,106 +162,6 @@ __global__ __launch_bounds__(256) void qg_tiles_kernel(const float *__restrict__
         if (i + u < tiles) a[u] += part[(size_t)(i + u) * (2 * kD) + t];
     out[t] = (a[0] + a[1]) + (a[2] + a[3]);
     if (zero && t < 2) zero[t] = 0.0f;
-}
-
-// --------------------------------------------------------------------------------------------------------------- dx --
-// dX [n][K] = dY [n][M] . W [M][K] (+ RES, or where MASK <= 0 zero): the tile is D[feature 16 o + 4 g + r][board col]. Lane (col, g):
-// the A operand is the column slice W[16 c + 4 g + r][16 o + col] of chunk c (M in chunks of 16), the B operand dY[board][16 c +
-// 4 g ..], one 16-byte load. As in the forward's product, eight chunks at a time into eight accumulators, combined pairwise.
-template <int N>
-__device__ inline void dx_chunks(const float *__restrict__ wcol, size_t K, const float *__restrict__ yrow, bool live, f4 (&acc)[8])
-{
-    f4 w[N], y[N];
-#pragma unroll
-    for (int c = 0; c < N; ++c) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) w[c][r] = wcol[(size_t)(16 * c + r) * K];
-        y[c] = live ? load_f4(yrow + 16 * c) : splat(0.0f);
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-        for (int c = 0; c < N; ++c) acc[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[c][r], y[c][r], acc[c], 0, 0, 0);
-}
-
-// four wavefronts a block = four feature tiles of one board tile; grid (K / 64 up, board tiles). M is a multiple of 32.
-__global__ __launch_bounds__(256) void qg_dx_kernel(const float *__restrict__ dY, int M, const float *__restrict__ W, int K,
-                                                     const float *__restrict__ res, const float *__restrict__ mask, float *__restrict__ dX, int n)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4, col = lane & 15;
-    const int o = (int)blockIdx.x * 4 + wave;
-    if (16 * o >= K) return;
-    const int board = (int)blockIdx.y * 16 + col;
-    const bool live = board < n;
-    const float *wcol = W + (size_t)(4 * g) * K + 16 * o + col, *yrow = dY + (size_t)board * M + 4 * g;
-    f4 acc[8];
-#pragma unroll
-    for (int c = 0; c < 8; ++c) acc[c] = splat(0.0f);
-    int m = 0;
-    for (; m + 128 <= M; m += 128) dx_chunks<8>(wcol + (size_t)m * K, (size_t)K, yrow + m, live, acc);
-    for (; m < M; m += 32) dx_chunks<2>(wcol + (size_t)m * K, (size_t)K, yrow + m, live, acc);
-    if (!live) return;
-    f4 v = sum8(acc);
-    const size_t at = (size_t)board * K + 16 * o + 4 * g;
-    if (res) v = load_f4(res + at) + v;                                     // the residual's two paths, in this order
-    if (mask) {
-        const f4 a = load_f4(mask + at);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = a[r] > 0.0f ? v[r] : 0.0f;
-    }
-    *reinterpret_cast<f4 *>(dX + at) = v;
-}
-
-// --------------------------------------------------------------------------------------------------------------- dw --
-// dW [M][K] = sum over the boards of dY[board][M] . X[board][K]; db [M] = sum over the boards of dY. The tile is D[row 16 mo + 4 g + r]
-// [column 16 ko + col]; the contraction runs over the boards in tiles of 16 (board 16 t + 4 g + r on MFMA r of lane group g): the A
-// operand is dY[board][16 mo + col] (row stride ldy; rows past M and boards past n read as zero), the B operand X[board][16 ko + col].
-// Eight board tiles at a time into eight accumulators, combined pairwise. The wavefronts of column tile 0 also add their A operands
-// up into db. Four wavefronts a block = four column tiles; grid (K / 64 up, M / 16 up).
-__global__ __launch_bounds__(256) void qg_dw_kernel(const float *__restrict__ dY, int ldy, int M, const float *__restrict__ X, int K,
-                                                     float *__restrict__ dW, float *__restrict__ db, int n)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4, col = lane & 15;
-    const int ko = (int)blockIdx.x * 4 + wave, mo = blockIdx.y;
-    if (16 * ko >= K) return;
-    const int mrow = 16 * mo + col;
-    const bool mlive = mrow < M;
-    const float *ycol = dY + mrow, *xcol = X + 16 * ko + col;
-    const int tiles = (n + 15) / 16;
-    f4 acc[8];
-    float bs[8];
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-        acc[c] = splat(0.0f);
-        bs[c] = 0.0f;
-    }
-    for (int t0 = 0; t0 < tiles; t0 += 8) {
-        f4 a[8], b[8];
-#pragma unroll
-        for (int c = 0; c < 8; ++c)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int board = 16 * (t0 + c) + 4 * g + r;
-                a[c][r] = board < n && mlive ? ycol[(size_t)board * ldy] : 0.0f;
-                b[c][r] = board < n ? xcol[(size_t)board * K] : 0.0f;
-            }
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-#pragma unroll
-            for (int c = 0; c < 8; ++c) acc[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[c][r], b[c][r], acc[c], 0, 0, 0);
-#pragma unroll
-        for (int c = 0; c < 8; ++c) bs[c] += sum4(a[c]);
-    }
-    const f4 v = sum8(acc);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int row = 16 * mo + 4 * g + r;
-        if (row < M) dW[(size_t)row * K + 16 * ko + col] = v[r];
-    }
-    if (ko == 0) {
-        const float s = lanes_sum(((bs[0] + bs[1]) + (bs[2] + bs[3])) + ((bs[4] + bs[5]) + (bs[6] + bs[7])));
-        if (g == 0 && mlive) db[mrow] = s;
-    }
 }
 
 // ----------------------------------------------------------------------------------------------- attention backward --

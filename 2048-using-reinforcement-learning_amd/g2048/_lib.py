@@ -34,6 +34,7 @@ PER_SCAN_TILE = 256
 POLICY_F32, POLICY_BF16 = 0, 1
 QNET_BATCH_MAX = 4096
 QNET_STEP_MAX_PARTIALS = 1024
+PPO_BATCH_MAX = 4096
 PLAY_POLICY_MASKED, PLAY_POLICY_UNMASKED, PLAY_POLICY_GREEDY, PLAY_POLICY_MODE_SHIFT = 0, 1, 2, 4
 
 _vp, _u64, _sz, _u32, _int = C.c_void_p, C.c_uint64, C.c_size_t, C.c_uint32, C.c_int
@@ -124,6 +125,10 @@ SIGNATURES = {
     "g2048_qnet_loss_grad": (_int, [_vp] * 5 + [_sz, _int, _int] + [_vp] * 6),
     "g2048_qnet_step_workspace": (_sz, [_int, _int]),
     "g2048_qnet_adamw_step": (_int, [_vp] * 4 + [_int, _int] + [C.c_float] * 6 + [_u64, _vp, _vp, _vp]),
+    "g2048_ppo_train_workspace": (_sz, [_sz]),
+    "g2048_ppo_forward_train": (_int, [_vp, _vp, _vp, _int, _vp, _sz, _vp, _vp]),
+    "g2048_ppo_advantages": (_int, [_vp] * 4 + [C.c_float, _vp, _vp, _sz, _vp]),
+    "g2048_ppo_loss_grad": (_int, [_vp] * 9 + [C.c_float] * 3 + [_sz] + [_vp] * 5),
 }
 
 

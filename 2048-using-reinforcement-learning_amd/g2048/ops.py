@@ -1522,6 +1522,136 @@ def per_update_priorities(priorities, size, head, indices, td_errors, workspace=
            td_errors.data_ptr(), indices.shape[0], workspace.data_ptr(), L.stream_ptr(dev))
 
 
+PPO_TRUNK_FLOATS, PPO_RUNNING_FLOATS = 46272, 768
+
+
+def ppo_plain_floats(n_out):
+    """Floats of one PPO network's plain parameter (and gradient) buffer: 46272 + 65 n_out, n_out 4 (actor) or 1 (critic)."""
+    if n_out not in (4, 1):
+        raise ValueError("g2048: n_out must be 4 (actor) or 1 (critic)")
+    return PPO_TRUNK_FLOATS + 65 * n_out
+
+
+def ppo_plain_offsets(n_out):
+    """[(name, offset, shape)] of the plain layout (include/g2048.h), in the order of the reference module's named_parameters()."""
+    shapes = [("fc1.weight", (256, 16)), ("fc1.bias", (256,)), ("bn1.weight", (256,)), ("bn1.bias", (256,)), ("fc2.weight", (128, 256)),
+              ("fc2.bias", (128,)), ("bn2.weight", (128,)), ("bn2.bias", (128,)), ("fc3.weight", (64, 128)), ("fc3.bias", (64,)),
+              ("fc4.weight", (n_out, 64)), ("fc4.bias", (n_out,))]
+    out, o = [], 0
+    for name, shape in shapes:
+        out.append((name, o, shape))
+        o += shape[0] * (shape[1] if len(shape) == 2 else 1)
+    assert o == ppo_plain_floats(n_out)
+    return out
+
+
+PPO_RUNNING_OFFSETS = [("bn1.running_mean", 0, 256), ("bn1.running_var", 256, 256), ("bn2.running_mean", 512, 128),
+                       ("bn2.running_var", 640, 128)]
+
+
+def ppo_train_workspace_bytes(n):
+    """Bytes of the workspace the PPO training calls need for n rows (g2048_ppo_train_workspace)."""
+    nb = L.lib().g2048_ppo_train_workspace(int(n))
+    if nb == 0:
+        raise ValueError("g2048: the PPO training pass takes 1 .. %d rows (the batch statistics are the whole batch's; a larger batch "
+                         "is refused, not truncated); got n = %d" % (L.PPO_BATCH_MAX, int(n)))
+    return nb
+
+
+def _ppo_workspace(workspace, n, dev):
+    nb = ppo_train_workspace_bytes(n)
+    if workspace is None:
+        workspace = torch.empty(nb, dtype=torch.uint8, device=dev)
+    L.require_device_tensor(workspace, torch.uint8, None, "workspace")
+    if workspace.numel() < nb:
+        raise ValueError("g2048: workspace must hold at least %d bytes" % nb)
+    return workspace
+
+
+def _ppo_flat(t, floats, name):
+    L.require_device_tensor(t, torch.float32, None, name)
+    if t.dim() != 1 or t.numel() != floats:
+        raise ValueError("g2048: %s must be a flat float32 tensor of %d floats" % (name, floats))
+    return t
+
+
+def ppo_forward_train(states, plain, n_out, running=None, out=None, workspace=None):
+    """One PPO network's TRAINING-mode forward (g2048_ppo_forward_train): BatchNorm on batch statistics (skipped for one row, as
+    the reference's forward skips it), no dropout. states float32 (n,16); plain: the network's plain float32 parameter buffer
+    (ppo_plain_floats(n_out)); running: the 768-float running-statistics buffer, moved by momentum 0.1 when given, untouched
+    when None. Returns probabilities float32 (n,4) for n_out 4, values float32 (n,1) for n_out 1. No synchronisation."""
+    L.require_device_tensor(states, torch.float32, (16,), "states")
+    _ppo_flat(plain, ppo_plain_floats(n_out), "plain")
+    if running is not None:
+        _ppo_flat(running, PPO_RUNNING_FLOATS, "running")
+    n, dev = states.shape[0], states.device
+    out = _output(out, n, torch.float32, (n_out,), "out", dev)
+    if n == 0:
+        return out
+    workspace = _ppo_workspace(workspace, n, dev)
+    L.call(dev, L.lib().g2048_ppo_forward_train, states.data_ptr(), plain.data_ptr(), running.data_ptr() if running is not None else None,
+           int(n_out), out.data_ptr(), n, workspace.data_ptr(), L.stream_ptr(dev))
+    return out
+
+
+def ppo_advantages(values, next_values, rewards, dones, gamma=0.995, returns=None, advantages=None):
+    """agents/ppo_agent.py:368-373 in one launch (g2048_ppo_advantages): returns = rewards + gamma * next_values * (1 - dones),
+    advantages = returns - values, normalised by their mean and unbiased std (+ 1e-8) when there is more than one row. All float32
+    (n,) (values and next_values may be (n,1)). Returns (returns, advantages). No synchronisation."""
+    values, next_values = (t.reshape(-1) if isinstance(t, torch.Tensor) else t for t in (values, next_values))
+    for t, name in ((values, "values"), (next_values, "next_values"), (rewards, "rewards"), (dones, "dones")):
+        L.require_device_tensor(t, torch.float32, (), name)
+    n, dev = values.shape[0], values.device
+    if not (next_values.shape[0] == rewards.shape[0] == dones.shape[0] == n):
+        raise ValueError("g2048: values, next_values, rewards and dones must have one entry per row")
+    returns = _output(returns, n, torch.float32, (), "returns", dev)
+    advantages = _output(advantages, n, torch.float32, (), "advantages", dev)
+    if n > L.PPO_BATCH_MAX:
+        ppo_train_workspace_bytes(n)                 # raises
+    L.call(dev, L.lib().g2048_ppo_advantages, values.data_ptr(), next_values.data_ptr(), rewards.data_ptr(), dones.data_ptr(), float(gamma),
+           returns.data_ptr(), advantages.data_ptr(), n, L.stream_ptr(dev))
+    return returns, advantages
+
+
+def ppo_loss_grad(states, actions, old_log_probs, advantages, returns, plain_actor, plain_critic, running_actor=None, running_critic=None,
+                  clip_epsilon=0.3, value_coef=0.4, entropy_coef=0.05, grad_actor=None, grad_critic=None, losses=None, workspace=None):
+    """One epoch body of PPOAgent.update (agents/ppo_agent.py:378-400) up to backward() on the device (g2048_ppo_loss_grad): both
+    networks' training-mode forwards (running statistics moved where a buffer is given), the clipped-surrogate, value and entropy
+    loss and d loss / d parameter of both networks in their plain layouts, OVERWRITTEN, never accumulated into. states float32
+    (n,16), actions int64 (n,), old_log_probs, advantages, returns float32 (n,). No dropout, f32 only. An action outside 0..3 is
+    the caller's error (the kernel reads actions & 3). No synchronisation. Returns (losses float32 (4,) = loss, actor_loss,
+    value_loss, entropy; grad_actor; grad_critic)."""
+    L.require_device_tensor(states, torch.float32, (16,), "states")
+    L.require_device_tensor(actions, torch.int64, (), "actions")
+    for t, name in ((old_log_probs, "old_log_probs"), (advantages, "advantages"), (returns, "returns")):
+        L.require_device_tensor(t, torch.float32, (), name)
+    n, dev = states.shape[0], states.device
+    if not (actions.shape[0] == old_log_probs.shape[0] == advantages.shape[0] == returns.shape[0] == n):
+        raise ValueError("g2048: actions, old_log_probs, advantages and returns must have one entry per row")
+    _ppo_flat(plain_actor, ppo_plain_floats(4), "plain_actor")
+    _ppo_flat(plain_critic, ppo_plain_floats(1), "plain_critic")
+    for t, name in ((running_actor, "running_actor"), (running_critic, "running_critic")):
+        if t is not None:
+            _ppo_flat(t, PPO_RUNNING_FLOATS, name)
+    if grad_actor is None:
+        grad_actor = torch.empty(ppo_plain_floats(4), dtype=torch.float32, device=dev)
+    if grad_critic is None:
+        grad_critic = torch.empty(ppo_plain_floats(1), dtype=torch.float32, device=dev)
+    _ppo_flat(grad_actor, ppo_plain_floats(4), "grad_actor")
+    _ppo_flat(grad_critic, ppo_plain_floats(1), "grad_critic")
+    if losses is None:
+        losses = torch.empty(4, dtype=torch.float32, device=dev)
+    _ppo_flat(losses, 4, "losses")
+    if n == 0:
+        return losses, grad_actor, grad_critic
+    workspace = _ppo_workspace(workspace, n, dev)
+    L.call(dev, L.lib().g2048_ppo_loss_grad, states.data_ptr(), actions.data_ptr(), old_log_probs.data_ptr(), advantages.data_ptr(),
+           returns.data_ptr(), plain_actor.data_ptr(), plain_critic.data_ptr(), running_actor.data_ptr() if running_actor is not None else None,
+           running_critic.data_ptr() if running_critic is not None else None, float(clip_epsilon), float(value_coef), float(entropy_coef), n,
+           grad_actor.data_ptr(), grad_critic.data_ptr(), losses.data_ptr(), workspace.data_ptr(), L.stream_ptr(dev))
+    return losses, grad_actor, grad_critic
+
+
 def launch_plan(compute_units=0, resident_blocks_per_cu=0, n_games=0):
     """The chip-size arithmetic of the library (g2048_launch_plan; a host function, usable without a GPU when compute_units
     is given): dict(order_row, order_min_games, helper_cap, default_helpers)."""

@@ -2,6 +2,7 @@
 """Collect a PPO rollout (BASELINE config 4: 65,536 envs x 128 steps) entirely on the GPU.
 
     python examples/ppo_rollout.py [--envs 65536] [--steps 128] [--policy torch|device-f32|device-bf16|transformer|transformer-bf16]
+                                   [--learner torch|device]
 
 The policy is any torch module mapping float32 (N,16) observations to action probabilities (N,4) -- or
 (probs, value); here a small MLP. Everything between the policy's outputs and its next inputs (masked sampling,
@@ -12,7 +13,11 @@ reference's (:356-400) on stock torch modules -- the learner stays the unchanged
 --policy device-f32 / device-bf16 runs the same modules' forward pass as one HIP launch on the boards (g2048.DevicePolicy)
 during collection; after the update, refresh() re-packs the weights in place and the captured rollout replays with them.
 --policy transformer / transformer-bf16 swaps the MLP for the reference's transformer (models/transformer.py's structure: 16
-tokens, d_model 64, 4 heads, 2 layers) and runs its forward pass as one HIP launch (g2048.DeviceTransformerPolicy, f32 / bf16)."""
+tokens, d_model 64, 4 heads, 2 layers) and runs its forward pass as one HIP launch (g2048.DeviceTransformerPolicy, f32 / bf16).
+--learner device swaps the MLP for the reference's own actor and critic (fc1..fc4, bn1, bn2) and runs PPOAgent.update() with the
+reference's hyper-parameters (batch 256, 8 epochs, clip 0.3, Adam 8e-4 / 2e-3): the advantages block and every epoch's
+training-mode forwards, loss and gradients are g2048.DevicePPOLearner's HIP launches, clip_grad_norm_(0.5) and stock
+torch.optim.Adam run on views of its buffers. Dropout is left out, as everywhere in this library."""
 import argparse
 import os
 import sys
@@ -31,7 +36,10 @@ ap.add_argument("--batch", type=int, default=4096)
 ap.add_argument("--epochs", type=int, default=4)
 ap.add_argument("--policy", choices=("torch", "device-f32", "device-bf16", "transformer", "transformer-bf16"), default="torch")
 ap.add_argument("--dim-ff", type=int, default=128, help="feed-forward width of the transformer (the reference's default is 2048)")
+ap.add_argument("--learner", choices=("torch", "device"), default="torch")
 a = ap.parse_args()
+if a.learner == "device" and a.policy.startswith("transformer"):
+    ap.error("--learner device trains the reference's MLP actor and critic; use --policy torch, device-f32 or device-bf16")
 
 
 class ActorCritic(nn.Module):
@@ -59,10 +67,43 @@ class TransformerActorCritic(nn.Module):
         return torch.softmax(self.pi(h), -1), self.v(h)
 
 
-net = (TransformerActorCritic(a.dim_ff) if a.policy.startswith("transformer") else ActorCritic()).cuda().eval()
+class RefNet(nn.Module):
+    """The reference's ActorNetwork (n_out 4) / CriticNetwork (n_out 1) layout, agents/ppo_agent.py:61-136."""
+
+    def __init__(self, n_out):
+        super().__init__()
+        self.fc1, self.bn1 = nn.Linear(16, 256), nn.BatchNorm1d(256)
+        self.fc2, self.bn2 = nn.Linear(256, 128), nn.BatchNorm1d(128)
+        self.fc3, self.fc4 = nn.Linear(128, 64), nn.Linear(64, n_out)
+        self.dropout, self.softmax = nn.Dropout(0.2), n_out == 4
+
+    def forward(self, x):
+        x = torch.relu(self.fc1(x))
+        x = self.dropout(self.bn1(x) if x.shape[0] > 1 else x)
+        x = torch.relu(self.fc2(x))
+        x = self.dropout(self.bn2(x) if x.shape[0] > 1 else x)
+        x = self.fc4(torch.relu(self.fc3(x)))
+        return torch.softmax(x, -1) if self.softmax else x
+
+
+class Pair(nn.Module):
+    def __init__(self):
+        super().__init__()
+        self.actor, self.critic = RefNet(4), RefNet(1)
+
+    def forward(self, x):
+        return self.actor(x), self.critic(x)
+
+
+if a.learner == "device":
+    net = Pair().cuda().eval()
+else:
+    net = (TransformerActorCritic(a.dim_ff) if a.policy.startswith("transformer") else ActorCritic()).cuda().eval()
 policy = net
 if a.policy.startswith("transformer"):      # recognised by structure: one TransformerEncoder and five Linears told apart by shape
     policy = g2048.DeviceTransformerPolicy(net, precision="bf16" if a.policy.endswith("bf16") else "f32")
+elif a.policy != "torch" and a.learner == "device":
+    policy = g2048.DevicePolicy(net.actor, net.critic, precision=a.policy[len("device-"):])
 elif a.policy != "torch":     # the same modules, 16-256-128-64-{4|1}: actor = body + pi, critic = body + v
     policy = g2048.DevicePolicy(nn.Sequential(net.body, net.pi).eval(), nn.Sequential(net.body, net.v).eval(),
                                 precision=a.policy[len("device-"):])
@@ -74,6 +115,33 @@ torch.cuda.synchronize(); dt = time.perf_counter() - t0
 print("%d env-steps in %.3f s = %.3g env-steps/s" % (a.envs * a.steps, dt, a.envs * a.steps / dt))
 print("obs", tuple(traj["obs"].shape), "rewards mean %.3f" % float(traj["rewards"].mean()),
       "episodes finished", int(traj["dones"].sum()), "max tile seen", 1 << int(traj["max_code"].max()))
+
+
+def device_update():
+    """PPOAgent.update() (agents/ppo_agent.py:336-420) with its own settings; everything that needs the networks is a HIP launch."""
+    learner = g2048.DevicePPOLearner(net.actor, net.critic, clip_epsilon=0.3, value_coef=0.4, entropy_coef=0.05)
+    learner.attach_params()
+    learner.attach_grads()
+    opts = [torch.optim.Adam(net.actor.parameters(), lr=8e-4), torch.optim.Adam(net.critic.parameters(), lr=2e-3)]
+    mb = rc.sample(256)
+    returns, adv = learner.advantages(mb["states"], mb["next_states"], mb["rewards"], mb["dones"], gamma=0.995)
+    for epoch in range(8):
+        losses = learner.loss_and_grad(mb["states"], mb["actions"], mb["old_log_probs"], adv, returns)
+        for module, opt in zip((net.actor, net.critic), opts):        # the reference's NaN check would synchronise; left to the caller
+            torch.nn.utils.clip_grad_norm_(module.parameters(), 0.5)
+            opt.step()
+    if policy is not net:
+        policy.refresh()    # the modules are in eval mode and ARE the learner's buffers: re-fold, re-pack, replay
+        rc.collect()
+    rc.check()
+    loss, actor_loss, value_loss, entropy = losses.tolist()
+    print("device update on 256 sampled transitions (of %d): loss %.4f (actor %.4f, value %.4f, entropy %.4f) after 8 epochs"
+          % (a.envs * a.steps, loss, actor_loss, value_loss, entropy))
+
+
+if a.learner == "device":
+    device_update()
+    sys.exit(0)
 
 # ---- one PPO update in the reference's form (agents/ppo_agent.py:336-420), on a minibatch gathered on the device
 gamma, clip_epsilon, value_coef, entropy_coef = 0.99, 0.2, 0.5, 0.01

@@ -54,7 +54,8 @@ extern "C" {
                                       g2048_play_qnet_beam_games / _workspace, g2048_per_push / _sample / _sample_workspace /
                                       _update_priorities / _update_workspace, g2048_dqn_shape_rewards, g2048_qnet_forward_batch,
                                       g2048_qnet_batch_workspace, g2048_dqn_targets, g2048_qnet_loss_grad / _grad_workspace,
-                                      g2048_qnet_adamw_step / _step_workspace)
+                                      g2048_qnet_adamw_step / _step_workspace, g2048_ppo_train_workspace / _forward_train /
+                                      _advantages / _loss_grad)
                                       4: round 5 (export table = this header + g2048_testing.h exactly: test / measurement hooks moved there,
                                       internal symbols hidden; g2048_replay_games also clamps a game's length to actions_stride)
                                       3: round 4 (actions_out of the g2048_play_games family, g2048_replay_games, g2048_env_step,
@@ -861,6 +862,58 @@ G2048_API size_t g2048_qnet_step_workspace(int dim_ff, int n_layers);
 G2048_API int g2048_qnet_adamw_step(float *plain, float *grad, float *exp_avg, float *exp_avg_sq, int dim_ff, int n_layers, float lr,
                           float beta1, float beta2, float eps, float weight_decay, float max_norm, uint64_t step, float *norm_out,
                           void *workspace, void *stream);
+
+/* ---- the PPO update's loss and gradient pass (agents/ppo_agent.py:357-400) --------------------------------------------------
+ * The lines of PPOAgent.update() that need the networks in TRAINING mode, for the reference's ActorNetwork / CriticNetwork
+ * (16-256-128-64-{4|1}): h1 = relu(fc1 x), b1 = BN1(h1), h2 = relu(fc2 b1), b2 = BN2(h2), h3 = relu(fc3 b2), z = fc4 h3. The
+ * BatchNorms use the batch mean and the biased variance over the n rows (eps 1e-5); given a running-statistics buffer they move
+ * it by momentum 0.1 towards the batch mean and the UNBIASED variance, as torch does. For n == 1 the reference's forward skips
+ * both BatchNorms, and so does this: their gradients are written as 0 and the running statistics are untouched. The reference
+ * runs these lines with its dropout live; that is left out, as everywhere in this library. f32 only. The inputs are the float
+ * observations PPOAgent.update builds (states float32 [n][16], 16-byte aligned), not packed boards.
+ *
+ * One network's parameters are one PLAIN f32 buffer of 46272 + 65 * n_out floats (n_out 4: actor, 1: critic), torch's row-major
+ * [out][in], back to back:
+ *     fc1.weight [256][16]  fc1.bias [256]  bn1.weight [256]  bn1.bias [256]  fc2.weight [128][256]  fc2.bias [128]
+ *     bn2.weight [128]  bn2.bias [128]  fc3.weight [64][128]  fc3.bias [64]  fc4.weight [n_out][64]  fc4.bias [n_out]
+ * A gradient buffer has the same layout. A running-statistics buffer is 768 floats: bn1.running_mean [256], bn1.running_var
+ * [256], bn2.running_mean [128], bn2.running_var [128]. Plain and gradient buffers are 16-byte aligned.
+ *
+ *   g2048_ppo_train_workspace   bytes of `workspace` for n rows (device memory, 16-byte aligned, contents irrelevant before and
+ *       meaningless after); 0 for n == 0 or n > G2048_PPO_BATCH_MAX. Non-decreasing in n. One size serves the three calls below.
+ *   g2048_ppo_forward_train   one network's training-mode forward: out = softmax probabilities float32 [n][4] (16-byte aligned)
+ *       for n_out 4, values float32 [n][1] for n_out 1. The running statistics are updated iff running_or_null is given.
+ *   g2048_ppo_advantages   :368-373 in one launch: returns_out = rewards + gamma * next_values * (1 - dones), adv = returns_out -
+ *       values, and for n > 1 adv_out = (adv - mean) / (std + 1e-8) with torch's unbiased std; mean and variance are one block's
+ *       fixed-order sums. For n == 1 adv_out = adv.
+ *   g2048_ppo_loss_grad   one epoch body :378-400 up to backward(): both training-mode forwards (each network's running statistics
+ *       updated iff its pointer is given), then with p = softmax(z_actor) and Categorical(probs = p) evaluated as torch evaluates
+ *       it in f32 (q = p / sum p; log q taken of q clamped to [eps, 1 - eps], eps = 2^-23; no gradient through a binding clamp):
+ *         ratio = exp(log q[a] - old_log_probs), a = actions[i] & 3 (int64; nothing is read out of bounds);
+ *         actor_loss = -mean(min(ratio A, clamp(ratio, 1 - clip_epsilon, 1 + clip_epsilon) A)), A = advantages, with torch's
+ *           subgradients: a tie's gradient is split in halves, clamp passes it on the closed range;
+ *         value_loss = mean((v - returns)^2);  entropy = mean(-sum q log q);
+ *         loss = actor_loss + value_coef * value_loss - entropy_coef * entropy;
+ *         loss_out = {loss, actor_loss, value_loss, entropy}. A NaN loss is reported there; the reference's `continue` on it is
+ *           the caller's decision.
+ *       grad_actor_out and grad_critic_out = d loss / d parameter, in the plain layout, OVERWRITTEN, never accumulated into.
+ *       One phase per launch on `stream`: fc1 and the products fc2, fc3, dX and dW / db on the f32 matrix cores, BatchNorm forward
+ *       and backward and the heads (fc4, the loss, its derivative) on the VALU. No atomics, no split-K across blocks: every
+ *       output element is one fixed-order accumulation, so two calls give the same bits. Nothing past row n or past the stated
+ *       sizes is read or written.
+ * 1 <= n <= G2048_PPO_BATCH_MAX (the batch statistics are the whole batch's: a larger n is refused, not truncated); n == 0
+ * returns G2048_OK and does nothing. Arguments are checked before any device call: a null or misaligned pointer, n too large,
+ * n_out other than 4 or 1, a clip_epsilon, value_coef or entropy_coef that is negative or not finite return G2048_ERR_ARG. */
+#define G2048_PPO_BATCH_MAX 4096
+G2048_API size_t g2048_ppo_train_workspace(size_t n);
+G2048_API int g2048_ppo_forward_train(const float *states, const float *plain, float *running_or_null, int n_out, float *out, size_t n,
+                            void *workspace, void *stream);
+G2048_API int g2048_ppo_advantages(const float *values, const float *next_values, const float *rewards, const float *dones, float gamma,
+                         float *returns_out, float *adv_out, size_t n, void *stream);
+G2048_API int g2048_ppo_loss_grad(const float *states, const int64_t *actions, const float *old_log_probs, const float *advantages,
+                        const float *returns, const float *plain_actor, const float *plain_critic, float *running_actor_or_null,
+                        float *running_critic_or_null, float clip_epsilon, float value_coef, float entropy_coef, size_t n,
+                        float *grad_actor_out, float *grad_critic_out, float *loss_out, void *workspace, void *stream);
 #ifdef __cplusplus
 }
 #endif

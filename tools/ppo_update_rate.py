@@ -1,0 +1,185 @@
+"""DevicePPOLearner (the gradient half of PPOAgent.update, agents/ppo_agent.py:357-400) against stock torch on the same GPU.
+
+    python3 tools/ppo_update_rate.py                      the table
+    python3 tools/ppo_update_rate.py --trace N [CALLS]    only CALLS (50) loss_and_grad calls at n = N, for a kernel trace:
+        rocprofv3 --kernel-trace --stats --output-format csv -d OUT -- python3 tools/ppo_update_rate.py --trace 256
+
+The reference's actor and critic (16-256-128-64-{4|1}, BatchNorm1d after the first two ReLUs, torch's default init) in training
+mode with dropout p = 0 on BOTH sides, at n = 256 (the reference's batch) and 4,096 (the limit). Versions, alternating within
+every round:
+  torch fwd+loss+bwd    both stock modules' forwards, Categorical, the clipped-surrogate / value / entropy loss,
+                        zero_grad(set_to_none=False) and backward(): the yardstick;
+  device loss_and_grad  the same function, one g2048_ppo_loss_grad call;
+  torch update          the whole update(): the no-gradient block (two critic forwards, returns, normalised advantages), then 8
+                        epochs of the above with clip_grad_norm_(0.5) per network and two torch.optim.Adam steps;
+  device update         the same with learner.advantages and learner.loss_and_grad, the clipping and the SAME stock Adam running on
+                        the attached views.
+The reference's `if torch.isnan(loss): continue` is left out on both sides (it is a host synchronisation per epoch).
+A round times REPS back-to-back calls of a version between one event pair and divides; median of 7 rounds after 2 warm-up rounds,
+min - max in brackets. Before timing, the device gradients and stock torch's float32 ones are both compared with the modules'
+float64 autograd on the same GPU, per tensor as max|g - g64| / max|g64|.
+Output: one text table (profiles/r23_ppo_update_rate.txt keeps a run)."""
+import copy
+import os
+import statistics
+import sys
+
+import torch
+import torch.nn as nn
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import __graft_entry__ as ge  # noqa: E402
+
+ge.import_package()
+from g2048 import DevicePPOLearner, ops  # noqa: E402
+
+dev = torch.device("cuda")
+REPS, EPOCHS = 10, 8
+GAMMA, CLIP, VALUE_COEF, ENTROPY_COEF, LR, MAX_NORM = 0.995, 0.3, 0.4, 0.05, 5e-4, 0.5
+
+
+class Net(nn.Module):                   # the reference's structure and forward, stock torch, default init, dropout p = 0
+    def __init__(self, n_out):
+        super().__init__()
+        self.fc1, self.bn1 = nn.Linear(16, 256), nn.BatchNorm1d(256)
+        self.fc2, self.bn2 = nn.Linear(256, 128), nn.BatchNorm1d(128)
+        self.fc3, self.fc4 = nn.Linear(128, 64), nn.Linear(64, n_out)
+        self.dropout, self.softmax = nn.Dropout(0.0), n_out == 4
+
+    def forward(self, x):
+        x = torch.relu(self.fc1(x))
+        if x.shape[0] > 1:
+            x = self.bn1(x)
+        x = torch.relu(self.fc2(self.dropout(x)))
+        if x.shape[0] > 1:
+            x = self.bn2(x)
+        x = self.fc4(torch.relu(self.fc3(self.dropout(x))))
+        return torch.softmax(x, -1) if self.softmax else x
+
+
+def event_time(fn):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(REPS):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) * 1e-3 / REPS
+
+
+def alternate(versions, warmup, rounds):
+    """{name: [seconds per call and round]}: every round runs each version, in order."""
+    times = {name: [] for name, _ in versions}
+    for r in range(warmup + rounds):
+        for name, fn in versions:
+            dt = event_time(fn)
+            if r >= warmup:
+                times[name].append(dt)
+    return times
+
+
+def torch_loss(actor, critic, x, actions, old, adv, ret):
+    dist = torch.distributions.Categorical(probs=actor(x))
+    ratio = torch.exp(dist.log_prob(actions) - old)
+    actor_loss = -torch.min(ratio * adv, torch.clamp(ratio, 1 - CLIP, 1 + CLIP) * adv).mean()
+    value_loss = nn.functional.mse_loss(critic(x).squeeze(-1), ret)
+    return actor_loss + VALUE_COEF * value_loss - ENTROPY_COEF * dist.entropy().mean()
+
+
+def torch_step(actor, critic, *args):
+    loss = torch_loss(actor, critic, *args)
+    actor.zero_grad(set_to_none=False)
+    critic.zero_grad(set_to_none=False)
+    loss.backward()
+    return loss
+
+
+def torch_update(actor, critic, opts, x, nx, actions, old, rewards, dones):
+    with torch.no_grad():
+        values, next_values = critic(x).squeeze(-1), critic(nx).squeeze(-1)
+        ret = rewards + GAMMA * next_values * (1 - dones)
+        adv = ret - values
+        adv = (adv - adv.mean()) / (adv.std() + 1e-8)
+    for _ in range(EPOCHS):
+        torch_step(actor, critic, x, actions, old, adv, ret)
+        for net, opt in zip((actor, critic), opts):
+            nn.utils.clip_grad_norm_(net.parameters(), MAX_NORM)
+            opt.step()
+
+
+def device_update(learner, actor, critic, opts, x, nx, actions, old, rewards, dones):
+    ret, adv = learner.advantages(x, nx, rewards, dones, GAMMA)
+    for _ in range(EPOCHS):
+        learner.loss_and_grad(x, actions, old, adv, ret)
+        for net, opt in zip((actor, critic), opts):
+            nn.utils.clip_grad_norm_(net.parameters(), MAX_NORM)
+            opt.step()
+
+
+def inputs(actor64, critic64, n):
+    x = ops.synth_boards(n, seed=3, device=dev).float() / 15.0          # PPOAgent.normalize_state
+    nx = ops.synth_boards(n, seed=4, device=dev).float() / 15.0
+    i = torch.arange(n, device=dev)
+    actions = (5 * i + 1) % 4
+    with torch.no_grad():
+        a64, c64 = copy.deepcopy(actor64), copy.deepcopy(critic64)
+        lp = torch.log(a64(x.double()).gather(1, actions.unsqueeze(1)).squeeze(1))
+        v = c64(x.double()).squeeze(-1)
+    old = (lp + ((37 * i + 11) % 101 - 50) / 100.0).float()
+    adv = (((13 * i) % 17 - 8) / 4.0 + 2 * x[:, 0]).float()
+    ret = (v + 0.5 + x.sum(1) / 8.0 + ((7 * i) % 11 - 5) / 5.0).float()
+    rewards, dones = ((3 * i) % 7).float(), (i % 5 == 0).float()
+    return x, nx, actions, old, adv, ret, rewards, dones
+
+
+def fresh(seed=0):
+    torch.manual_seed(seed)
+    return Net(4).to(dev).train(), Net(1).to(dev).train()
+
+
+if sys.argv[1:2] == ["--trace"]:
+    n, calls = int(sys.argv[2]), int(sys.argv[3]) if len(sys.argv) > 3 else 50
+    actor, critic = fresh()
+    x, nx, actions, old, adv, ret, rewards, dones = inputs(copy.deepcopy(actor).double(), copy.deepcopy(critic).double(), n)
+    learner = DevicePPOLearner(actor, critic, CLIP, VALUE_COEF, ENTROPY_COEF)
+    for _ in range(calls):
+        learner.loss_and_grad(x, actions, old, adv, ret)
+    torch.cuda.synchronize()
+    print("%d loss_and_grad calls at n = %d" % (calls, n))
+    sys.exit(0)
+
+print("# %d calls per event pair; median of 7 rounds after 2 warm-up rounds, the versions alternating; an update is the advantages "
+      "block + %d epochs with clip_grad_norm_(%.1f) and stock torch.optim.Adam" % (REPS, EPOCHS, MAX_NORM))
+print("# workspace of the device pass: %s" % ", ".join("n = %d: %.1f MB" % (n, ops.ppo_train_workspace_bytes(n) / 1e6) for n in (256, 4096)))
+print("%-7s %-22s %10s %22s %12s %10s" % ("rows", "version", "us", "[min - max] us", "rows/s", "vs torch"))
+for n in (256, 4096):
+    actor, critic = fresh()                                             # stock torch's
+    d_actor, d_critic = copy.deepcopy(actor), copy.deepcopy(critic)     # the device learner's
+    actor64, critic64 = copy.deepcopy(actor).double(), copy.deepcopy(critic).double()
+    x, nx, actions, old, adv, ret, rewards, dones = inputs(actor64, critic64, n)
+    learner = DevicePPOLearner(d_actor, d_critic, CLIP, VALUE_COEF, ENTROPY_COEF)
+    learner.attach_params()
+    learner.attach_grads()
+    torch_step(actor64, critic64, x.double(), actions, old.double(), adv.double(), ret.double())
+    want = [p.grad.reshape(-1).clone() for net in (actor64, critic64) for p in net.parameters()]
+    torch_step(actor, critic, x, actions, old, adv, ret)
+    got32 = [p.grad.reshape(-1).double() for net in (actor, critic) for p in net.parameters()]
+    learner.loss_and_grad(x, actions, old, adv, ret)
+    got = [p.grad.reshape(-1).double() for net in (d_actor, d_critic) for p in net.parameters()]
+    ratio = lambda gs: max(((g - z).abs().max() / z.abs().max()).item() for g, z in zip(gs, want))      # noqa: E731
+    r_dev, r_torch = ratio(got), ratio(got32)
+    print("# n = %d: worst max|g - g64| / max|g64| over the 24 tensors: device %.3g, torch f32 %.3g" % (n, r_dev, r_torch))
+    assert r_dev <= 8 * r_torch, "loss_and_grad does not compute torch's gradients"
+    opts = [torch.optim.Adam(net.parameters(), lr=LR) for net in (actor, critic)]
+    d_opts = [torch.optim.Adam(net.parameters(), lr=LR) for net in (d_actor, d_critic)]
+    versions = [("torch fwd+loss+bwd", lambda: torch_step(actor, critic, x, actions, old, adv, ret)),
+                ("device loss_and_grad", lambda: learner.loss_and_grad(x, actions, old, adv, ret)),
+                ("torch update", lambda: torch_update(actor, critic, opts, x, nx, actions, old, rewards, dones)),
+                ("device update", lambda: device_update(learner, d_actor, d_critic, d_opts, x, nx, actions, old, rewards, dones))]
+    times = alternate(versions, 2, 7)
+    for name, _ in versions:
+        tt = times[name]
+        med = statistics.median(tt)
+        base = statistics.median(times["torch update" if name.endswith("update") else "torch fwd+loss+bwd"])
+        print("%-7d %-22s %10.1f %22s %12.4g %9.2fx" % (n, name, med * 1e6, "[%.1f - %.1f]" % (min(tt) * 1e6, max(tt) * 1e6), n / med, base / med))
