@@ -31,6 +31,15 @@ __device__ inline f4 relu(f4 v)
     return f4{fmaxf(v[0], 0.0f), fmaxf(v[1], 0.0f), fmaxf(v[2], 0.0f), fmaxf(v[3], 0.0f)};
 }
 
+// torch.relu: a NaN stays a NaN (fmaxf returns the operand that is none). Finite values as relu's.
+__device__ inline f4 relu_nan(f4 v)
+{
+    f4 r;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) r[i] = v[i] > 0.0f ? v[i] : v[i] != v[i] ? v[i] : 0.0f;
+    return r;
+}
+
 __device__ inline f4 load_f4(const void *p) { return *reinterpret_cast<const f4 *>(p); }
 __device__ inline f4 splat(float v) { return f4{v, v, v, v}; }
 

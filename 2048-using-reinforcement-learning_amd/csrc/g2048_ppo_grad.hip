@@ -20,6 +20,8 @@
 // No atomics, no split-K across blocks, no block waits on another; every output element is one fixed-order accumulation, so two
 // calls give the same bits; nothing past row n or past the stated sizes is read or written, and no row past n of the workspace
 // is relied on. The gradient buffers are overwritten, never accumulated into. Compile with -ffp-contract=off.
+// A NaN or an infinity in an input shows in the loss parts and the gradients as it does in stock torch: every ReLU, clamp and
+// minimum of this pass is a comparison that passes a NaN on (relu_nan, clamp_nan, min_nan), not fmaxf / fminf, which drop it.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -74,7 +76,7 @@ __global__ __launch_bounds__(256) void pg_fc1_kernel(const float *__restrict__ X
     const f4 w = load_w(W + (size_t)(16 * o + col) * kIn + 4 * g), x = live ? load_f4(X + (size_t)row * kIn + 4 * g) : splat(0.0f);
 #pragma unroll
     for (int r = 0; r < 4; ++r) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w[r], x[r], acc, 0, 0, 0);
-    if (live) *reinterpret_cast<f4 *>(Y + (size_t)row * kH1 + 16 * o + 4 * g) = relu(acc);
+    if (live) *reinterpret_cast<f4 *>(Y + (size_t)row * kH1 + 16 * o + 4 * g) = relu_nan(acc);
 }
 
 // -------------------------------------------------------------------------------------------------------- BatchNorm --
@@ -214,6 +216,11 @@ __device__ inline void fc4_row_dx(const float (&dz)[O], const float *__restrict_
     }
 }
 
+// torch.clamp and torch.min: a NaN operand gives NaN, where fminf / fmaxf return the operand that is none. Plain comparisons; for
+// finite operands (lo <= hi) the values are fminf(fmaxf(x, lo), hi) and fminf(a, b).
+__device__ inline float clamp_nan(float x, float lo, float hi) { return x < lo ? lo : x > hi ? hi : x; }
+__device__ inline float min_nan(float a, float b) { return (a < b || a != a) ? a : b; }
+
 // The actor's head, a thread a row: p = softmax(fc4 h3) to probs. With `actions` (the loss asked for):
 //   q = p / sum(p); l = log(clamp(q, eps, 1 - eps)), eps = 2^-23 (Categorical(probs=p) in f32); ratio = exp(l[a] - old);
 //   term = min(ratio A, clamp(ratio, 1 - clip, 1 + clip) A); ent = -sum l q; loss share = -term / n - ent_coef ent / n
@@ -241,12 +248,12 @@ __global__ __launch_bounds__(64) void pg_actor_head_kernel(const float *__restri
     for (int j = 0; j < 4; ++j) {
         q[j] = p[j] / s;
         open[j] = q[j] >= eps && q[j] <= 1.0f - eps;
-        l[j] = logf(fminf(fmaxf(q[j], eps), 1.0f - eps));
+        l[j] = logf(clamp_nan(q[j], eps, 1.0f - eps));
         e += l[j] * q[j];
     }
     const float A = adv[i], ratio = expf(l[a] - old_log_probs[i]), lo = 1.0f - clip, hi = 1.0f + clip;
-    const float s1 = ratio * A, s2 = fminf(fmaxf(ratio, lo), hi) * A;
-    term[i] = fminf(s1, s2);
+    const float s1 = ratio * A, s2 = clamp_nan(ratio, lo, hi) * A;
+    term[i] = min_nan(s1, s2);
     ent[i] = -e;
     const float g1 = s1 < s2 ? 1.0f : s1 == s2 ? 0.5f : 0.0f, g2 = s2 < s1 ? 1.0f : s1 == s2 ? 0.5f : 0.0f;
     const float dratio = -inv_n * (g1 * A + (ratio >= lo && ratio <= hi ? g2 * A : 0.0f));
@@ -398,12 +405,12 @@ void launch_trunk(const Net &net, const float *states, int n, hipStream_t s)
     if (bn)
         hipLaunchKernelGGL(pg_bn_kernel, dim3(kH1 / 32), dim3(1024), 0, s, static_cast<const float *>(h1), kH1, net.P + kBn1W, net.P + kBn1B, b1, stat,
                            net.running ? net.running + kRun1 : nullptr, n);
-    hipLaunchKernelGGL(qb_linear_kernel<true>, dim3(kH2 / 64, tiles), dim3(256), 0, s, static_cast<const float *>(b1), kH1, net.P + kFc2W,
+    hipLaunchKernelGGL((qb_linear_kernel<true, true>), dim3(kH2 / 64, tiles), dim3(256), 0, s, static_cast<const float *>(b1), kH1, net.P + kFc2W,
                        net.P + kFc2B, h2, kH2, n);
     if (bn)
         hipLaunchKernelGGL(pg_bn_kernel, dim3(kH2 / 32), dim3(1024), 0, s, static_cast<const float *>(h2), kH2, net.P + kBn2W, net.P + kBn2B, b2,
                            stat + 2 * kH1, net.running ? net.running + kRun2 : nullptr, n);
-    hipLaunchKernelGGL(qb_linear_kernel<true>, dim3(kH3 / 64, tiles), dim3(256), 0, s, static_cast<const float *>(b2), kH2, net.P + kFc3W,
+    hipLaunchKernelGGL((qb_linear_kernel<true, true>), dim3(kH3 / 64, tiles), dim3(256), 0, s, static_cast<const float *>(b2), kH2, net.P + kFc3W,
                        net.P + kFc3B, h3, kH3, n);
 }
 

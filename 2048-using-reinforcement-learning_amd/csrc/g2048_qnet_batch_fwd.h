@@ -127,8 +127,9 @@ __device__ inline f4 tile_product(const float *__restrict__ wrow, const float *_
     return ((acc[0] + acc[1]) + (acc[2] + acc[3])) + ((acc[4] + acc[5]) + (acc[6] + acc[7]));
 }
 
-// Y [n][M] = act(X [n][K] W^T + b): four wavefronts a block = four feature tiles of one board tile; grid (M / 64 up, board tiles)
-template <bool RELU>
+// Y [n][M] = act(X [n][K] W^T + b): four wavefronts a block = four feature tiles of one board tile; grid (M / 64 up, board tiles).
+// KEEP_NAN: the ReLU passes a NaN on, as torch.relu does (the PPO update, whose NaN loss is its caller's signal).
+template <bool RELU, bool KEEP_NAN = false>
 __global__ __launch_bounds__(256) void qb_linear_kernel(const float *__restrict__ X, int K, const float *__restrict__ W,
                                                          const float *__restrict__ bias, float *__restrict__ Y, int M, int n)
 {
@@ -139,7 +140,7 @@ __global__ __launch_bounds__(256) void qb_linear_kernel(const float *__restrict_
     const bool live = board < n;
     f4 acc = load_w(bias + 16 * o + 4 * g);
     acc = tile_product(W + (size_t)(16 * o + col) * K + 4 * g, X + (size_t)board * K + 4 * g, live, K, acc);
-    if (RELU) acc = relu(acc);
+    if (RELU) acc = KEEP_NAN ? relu_nan(acc) : relu(acc);
     if (live) *reinterpret_cast<f4 *>(Y + (size_t)board * M + 16 * o + 4 * g) = acc;
 }
 

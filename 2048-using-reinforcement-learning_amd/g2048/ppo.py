@@ -137,7 +137,11 @@ class DevicePPOLearner:
       two training-mode critic forwards (both move the running statistics, as the reference's do) and one launch.
     loss_and_grad(states, actions, old_log_probs, advantages, returns) -> float32 (4,) device tensor (loss, actor_loss, value_loss,
       entropy): one epoch body (:378-400) up to backward(); actor.grad / critic.grad are OVERWRITTEN. A NaN loss is reported, not
-      skipped: the reference's `continue` is the caller's decision.
+      skipped: the reference's `continue` is the caller's decision. Non-finite inputs show as they do in stock torch: the ReLUs,
+      the clamps and the minimum pass a NaN on (torch.relu / clamp / min, not fmaxf / fminf), so each loss part is finite, NaN,
+      +inf or -inf where stock float32's is (a NaN or -inf old log-prob with advantage 0, a NaN state: a NaN loss), and a
+      gradient tensor holds a non-finite value where stock's does. As in stock torch, old_log_probs = -inf under a positive
+      advantage gives a FINITE loss over NaN actor gradients (exp's backward, 0 x inf): check the gradients, not the loss alone.
     1 <= N <= 4096; states are float32 (N,16) as RolloutCollector.sample returns them, not packed boards."""
 
     def __init__(self, actor, critic, clip_epsilon=0.3, value_coef=0.4, entropy_coef=0.05):

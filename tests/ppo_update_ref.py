@@ -5,7 +5,10 @@ float32) and the conditions the inputs must meet for the comparison to mean some
 critic, each in named_parameters() order, which is the plain layout's order.
 
 The tolerance follows tests/qnet_grad_ref.py: per case and tensor max|got - f64| / max|f64| <= F32_FACTOR x the worst such ratio
-of stock CPU float32 autograd over the case's 24 gradient tensors."""
+of stock CPU float32 autograd over the case's 24 gradient tensors.
+
+Below the first regime's cases: the builders of tests/test_gpu_ppo_update_edges.py (poisoned inputs, the advantages block's lines, a
+saturated policy, other coefficients, dead features, a whole update of several epochs), each with the scan that chose its seed."""
 import copy
 import functools
 
@@ -20,9 +23,11 @@ CLIP, VALUE_COEF, ENTROPY_COEF = 0.3, 0.4, 0.05          # PPOAgent's own settin
 RELU_MARGIN = 1e-5
 DISTINCT_ABOVE, DISTINCT = 300, 64                       # n > 300: 64 distinct boards repeated
 F32_EPS = float(torch.finfo(torch.float32).eps)          # 2^-23: what Categorical clamps float32 probabilities to
-GPU_SIZES = (1, 2, 3, 15, 16, 17, 127, 128, 129, 256, 257, 1025, 4095, 4096)
+# 31, 33, 224, 225: the edges of BatchNorm's own row grouping (32 row groups, passes of 256 rows)
+GPU_SIZES = (1, 2, 3, 15, 16, 17, 31, 33, 127, 128, 129, 224, 225, 256, 257, 1025, 4095, 4096)
 # the board seed per n: the first for which every ReLU input keeps RELU_MARGIN (find_seed; tests/test_ppo_update_host.py checks them)
-SEEDS = {1: 0, 2: 0, 3: 0, 15: 1, 16: 0, 17: 0, 32: 0, 127: 6, 128: 135, 129: 16, 256: 3360, 257: 5031, 1025: 2, 4095: 28, 4096: 2}
+SEEDS = {1: 0, 2: 0, 3: 0, 15: 1, 16: 0, 17: 0, 31: 0, 32: 0, 33: 0, 127: 6, 128: 135, 129: 16, 224: 1705, 225: 950, 256: 3360, 257: 5031,
+         1025: 2, 4095: 28, 4096: 2}
 WEIGHT_SEED = 23
 
 
@@ -89,9 +94,11 @@ def categorical_parts(probs, actions, eps=None):
     return logits.gather(-1, actions.unsqueeze(-1)).squeeze(-1), -(logits * q).sum(-1)
 
 
-def stock_update(nets, x, actions, old_log_probs, advantages, returns, calls=1, eps=None):
+def stock_update(nets, x, actions, old_log_probs, advantages, returns, calls=1, eps=None, clip=CLIP, value_coef=VALUE_COEF,
+                 entropy_coef=ENTROPY_COEF):
     """ppo_agent.py:378-400 up to backward() on deep copies of the stock modules in their own dtype, the forwards made `calls`
-    times (the running statistics move each time; the gradients are the last call's). Everything as float64 NumPy: dict(losses
+    times (the running statistics move each time; the gradients are the last call's); the three coefficients default to the
+    reference agent's. Everything as float64 NumPy: dict(losses
     (loss, actor_loss, value_loss, entropy), probs, values, grads [24], running [8], log_probs)."""
     actor, critic = (copy.deepcopy(net) for net in nets)
     dtype = actor.fc1.weight.dtype
@@ -105,10 +112,10 @@ def stock_update(nets, x, actions, old_log_probs, advantages, returns, calls=1, 
         if value_pred.dim() == 0:
             value_pred = value_pred.unsqueeze(0)
         ratio = torch.exp(new_log_probs - old)
-        clipped_ratio = torch.clamp(ratio, 1 - CLIP, 1 + CLIP)
+        clipped_ratio = torch.clamp(ratio, 1 - clip, 1 + clip)
         actor_loss = -torch.min(ratio * adv, clipped_ratio * adv).mean()
         value_loss = F.mse_loss(value_pred, ret)
-        loss = actor_loss + VALUE_COEF * value_loss - ENTROPY_COEF * entropy
+        loss = actor_loss + value_coef * value_loss - entropy_coef * entropy
     loss.backward()
     f64 = lambda t: t.detach().numpy().astype(np.float64)       # noqa: E731
     # one row: the forward skips both BatchNorms, autograd leaves their .grad None; the device writes zeros
@@ -137,15 +144,16 @@ def recipe(nets64, x, actions=None, eps=None):
 class Case:
     """One n: the float32 and float64 modules, the inputs, the float64 yardstick, stock float32's own error and the bound."""
 
-    def __init__(self, n, seed, nets32=None, x=None, actions=None, eps=None):
-        self.n, self.seed = n, seed
+    def __init__(self, n, seed, nets32=None, x=None, actions=None, eps=None, coefs=(CLIP, VALUE_COEF, ENTROPY_COEF)):
+        self.n, self.seed, self.coefs = n, seed, coefs
+        kw = dict(zip(("clip", "value_coef", "entropy_coef"), coefs))
         self.nets32 = nets32 if nets32 is not None else make_modules()
         self.nets64 = tuple(copy.deepcopy(net).double() for net in self.nets32)
         self.x = states_of(n, seed) if x is None else x
         self.actions, self.old, self.adv, self.ret = recipe(self.nets64, self.x, actions, eps)
         self.args = (self.x, self.actions, self.old, self.adv, self.ret)
-        self.want = stock_update(self.nets64, *self.args, eps=eps)
-        self.f32 = stock_update(self.nets32, *self.args)
+        self.want = stock_update(self.nets64, *self.args, eps=eps, **kw)
+        self.f32 = stock_update(self.nets32, *self.args, **kw)
         self.yardstick = float(ratios(self.f32["grads"], self.want["grads"]).max())
         self.bound = F32_FACTOR * self.yardstick
 
@@ -178,3 +186,265 @@ def clamp_case():
 def rel(got, want):
     """max|got - want| / max|want| of one tensor."""
     return float(ratios([got], [np.asarray(want, np.float64)])[0])
+
+
+# ------------------------------------------------------------------------------------------------ non-finite inputs --
+NAN, INF = float("nan"), float("inf")
+# (name, the input array poisoned on the LAST row, the value, the sign the row's advantage is given (None: kept), the network the
+# poison does not reach)
+POISONS = (("old=nan", "old", NAN, None, "critic"), ("old=+inf", "old", INF, None, "critic"),
+           ("old=-inf,A>0", "old", -INF, 1.0, "critic"), ("old=-inf,A<0", "old", -INF, -1.0, "critic"),
+           ("old=-inf,A=0", "old", -INF, 0.0, "critic"), ("adv=nan", "adv", NAN, None, "critic"), ("adv=+inf", "adv", INF, None, "critic"),
+           ("ret=nan", "ret", NAN, None, "actor"), ("ret=+inf", "ret", INF, None, "actor"))
+POISON_SIZES = (17, 129)
+
+
+def poisoned_args(c, which, value, sign):
+    """c.args with the last row of one of old / adv / ret set to `value` (and, with `sign`, that row's advantage to sign |A|)."""
+    args = dict(x=c.x, actions=c.actions, old=c.old.copy(), adv=c.adv.copy(), ret=c.ret.copy())
+    if sign is not None:
+        args["adv"][-1] = np.float32(sign) * abs(args["adv"][-1])
+    args[which][-1] = value
+    return args["x"], args["actions"], args["old"], args["adv"], args["ret"]
+
+
+def classes(values):
+    """'finite', 'nan', '+inf' or '-inf' per value."""
+    return ["nan" if np.isnan(v) else "finite" if np.isfinite(v) else "+inf" if v > 0 else "-inf" for v in np.asarray(values, np.float64)]
+
+
+def nonfinite(tensors):
+    """Per tensor: does it contain a value that is not finite."""
+    return [not bool(np.isfinite(t).all()) for t in tensors]
+
+
+def advantage_lines(dtype, values, next_values, rewards, dones, gamma=0.995):
+    """ppo_agent.py:368-373 in stock torch of `dtype`: (returns, advantages) as float64 NumPy."""
+    v, nv, r, d = (torch.from_numpy(np.asarray(t)).to(dtype).reshape(-1) for t in (values, next_values, rewards, dones))
+    returns = r + gamma * nv * (1 - d)
+    adv = returns - v
+    if adv.shape[0] > 1:
+        adv = (adv - adv.mean()) / (adv.std() + 1e-8)
+    return returns.numpy().astype(np.float64), adv.numpy().astype(np.float64)
+
+
+ADV_FLOOR = 8 * 2.0 ** -24                              # the advantages block: at least 8 float32 roundings
+
+
+def advantage_bound(f32, want):
+    return F32_FACTOR * max(rel(f32[0], want[0]), rel(f32[1], want[1]), ADV_FLOOR)
+
+
+# --------------------------------------------------------------------------------------------------- saturated policy --
+SAT_N, SAT_SCALE, SAT_SEED = 32, 128.0, 24
+SAT_LOW, SAT_HIGH = F32_EPS / 8, 8 * F32_EPS            # 1 - max q below LOW: float32's q is exactly 1; above HIGH: it is not
+
+
+def saturated_modules():
+    nets = make_modules()
+    with torch.no_grad():
+        nets[0].fc4.weight.mul_(SAT_SCALE)
+    return nets
+
+
+def saturated_measures(nets64, x):
+    """Of the float64 actor on the rows x: dict(gap: the largest logit gap of a row, rest: 1 - max q per row, summed from the other
+    three, q, top: argmax, low: argmin)."""
+    actor = nets64[0]
+    x64 = torch.from_numpy(x).double()
+    with torch.no_grad():
+        h3 = torch.relu(relu_inputs(actor, x64)[2])
+        z = actor.fc4(h3)
+        q = torch.softmax(z, -1).numpy()
+    z = z.numpy()
+    rest = np.sort(q, axis=1)[:, :3].sum(1)
+    return dict(gap=float((z.max(1) - z.min(1)).max()), rest=rest, q=q, top=q.argmax(1), low=q.argmin(1))
+
+
+def saturated_actions(m):
+    """Even rows take the most probable action (the saturated one where the row is saturated), odd rows the least probable."""
+    i = np.arange(len(m["top"]))
+    return np.where(i % 2 == 0, m["top"], m["low"]).astype(np.int64)
+
+
+def saturated_ok(m):
+    """The conditions of the saturated case that are decided by the rows alone (tests/test_ppo_update_host.py states them)."""
+    sat = m["rest"] < SAT_LOW
+    a = saturated_actions(m)
+    rows = np.arange(len(a))
+    taken = m["q"][rows, a]
+    return bool(m["gap"] > 89 and 0.25 <= sat.mean() <= 0.75 and not ((m["rest"] >= SAT_LOW) & (m["rest"] <= SAT_HIGH)).any()
+                and (np.abs(m["q"] / F32_EPS - 1) >= 0.01).all() and (sat & (a == m["top"])).any() and (taken < F32_EPS).any())
+
+
+def find_saturated_seed(nets64, start=0, limit=20000):
+    for seed in range(start, start + limit):
+        x = states_of(SAT_N, seed)
+        if relu_margin(nets64, torch.from_numpy(x).double()) >= RELU_MARGIN and saturated_ok(saturated_measures(nets64, x)):
+            return seed
+    raise RuntimeError("no board seed in %d .. %d gives the saturated case" % (start, start + limit))
+
+
+@functools.lru_cache(maxsize=None)
+def saturated_case():
+    """A saturated policy: the actor's fc4.weight x 128, so that the logits span more than float32's exp and q rounds to exactly 1
+    on part of the rows. float64 clamps at 2^-52: the yardstick is float64 evaluated with float32's eps, as in clamp_case."""
+    nets = saturated_modules()
+    nets64 = tuple(copy.deepcopy(net).double() for net in nets)
+    x = states_of(SAT_N, SAT_SEED)
+    return Case(SAT_N, SAT_SEED, nets32=nets, x=x, actions=saturated_actions(saturated_measures(nets64, x)), eps=F32_EPS)
+
+
+# ------------------------------------------------------------------------------------------------------- coefficients --
+COEF_SETS = ((0.1, 1.0, 0.0), (0.2, 0.0, 0.01), (0.0, 0.5, 0.5))
+
+
+@functools.lru_cache(maxsize=None)
+def coef_case(k):
+    return Case(17, SEEDS[17], coefs=COEF_SETS[k])
+
+
+# ------------------------------------------------------------------------------------------------------ dead features --
+DEAD, DEAD_BIAS = tuple(range(8)), -10.0
+# at this seed's 17 rows these features of the fresh modules are 0 on every row as well (tests/test_ppo_update_host.py finds them
+# anew): they belong to the set the GPU test holds to exactly 0
+DEAD_ACTOR = DEAD + (19, 20, 25, 33, 35, 42, 45, 49, 62, 63, 66, 67, 69, 72, 74, 81, 84, 102, 108, 113, 120, 123, 129, 133, 136, 143, 154, 166,
+                     171, 181, 203, 205, 215, 218, 224, 238, 243, 248, 255)
+DEAD_CRITIC = DEAD + (8, 17, 33, 42, 43, 44, 46, 60, 77, 78, 79, 80, 83, 99, 110, 113, 117, 121, 124, 126, 136, 143, 155, 157, 163, 167, 171,
+                      177, 180, 185, 214, 216, 240, 243, 255)
+
+
+def dead_features(net64, x):
+    """The fc1 features that are 0 on every row of x after the ReLU."""
+    z1 = relu_inputs(net64, torch.from_numpy(x).double())[0]
+    return tuple(np.where((z1 <= 0).all(0).numpy())[0].tolist())
+
+
+@functools.lru_cache(maxsize=None)
+def dead_case():
+    """case(17) with fc1.bias of the features DEAD at -10 in both modules: they are 0 on every row after the ReLU, BatchNorm's
+    output there is its bias."""
+    nets = make_modules()
+    with torch.no_grad():
+        for net in nets:
+            net.fc1.bias[list(DEAD)] = DEAD_BIAS
+    return Case(17, SEEDS[17], nets32=nets)
+
+
+# -------------------------------------------------------------------------------------------------- a whole update --
+LOOP_N, LOOP_EPOCHS, LOOP_SEED = 48, 3, 60            # the first seed find_loop_seed accepts
+LR_ACTOR, LR_CRITIC, MAX_NORM = 8e-4, 2e-3, 0.5       # PPOAgent's own; Adam's eps is set to its lr (tests/test_gpu_ppo_update.py)
+
+
+def loop_inputs(seed):
+    """(states, next_states, rewards, dones) of the closed-loop case: next states from the next seed, rewards that correlate with
+    the input, every fifth row done."""
+    x, nx = states_of(LOOP_N, seed), states_of(LOOP_N, seed + 1)
+    i = np.arange(LOOP_N, dtype=np.int64)
+    rewards = ((11 * i) % 13 - 4) / 2.0 + 4.0 * x[:, 1].astype(np.float64)
+    dones = (i % 5 == 2)
+    return x, nx, rewards.astype(np.float32), dones.astype(np.float32)
+
+
+def stock_advantages(critic, x, nx, rewards, dones, gamma=0.995):
+    """ppo_agent.py:357-373 on the given critic (training mode, its running statistics move twice): dict(values, next_values,
+    returns, advantages) as torch tensors of the module's dtype."""
+    dtype = critic.fc1.weight.dtype
+    xs, nxs, r, d = (torch.from_numpy(np.asarray(t)).to(dtype) for t in (x, nx, rewards, dones))
+    with torch.no_grad():
+        values, next_values = critic(xs).squeeze(), critic(nxs).squeeze()
+        returns = r + gamma * next_values * (1 - d)
+        adv = returns - values
+        if adv.shape[0] > 1:
+            adv = (adv - adv.mean()) / (adv.std() + 1e-8)
+    return dict(values=values, next_values=next_values, returns=returns, advantages=adv)
+
+
+def running_of(nets):
+    return [t.detach().numpy().astype(np.float64).copy() for net in nets for t in (net.bn1.running_mean, net.bn1.running_var,
+                                                                                    net.bn2.running_mean, net.bn2.running_var)]
+
+
+def stock_loop(nets, inputs, actions, old, epochs=LOOP_EPOCHS, margins=False):
+    """PPOAgent.update()'s sequence on deep copies of the stock modules in their own dtype: the advantages block, then per epoch
+    the loss, backward(), clip_grad_norm_(0.5) per module and an Adam step per module (eps = lr). dict(adv: stock_advantages'
+    results as float64 NumPy, running_adv [8], per epoch: losses [4], grads [24] (before clipping), norms (actor, critic), delta
+    [24] (parameters minus their start), ratio, margin (of the weights the epoch's forward used; only with margins), running [8]
+    and tracked [4] after the last epoch, start [24])."""
+    actor, critic = (copy.deepcopy(net) for net in nets)
+    dtype = actor.fc1.weight.dtype
+    x, nx, rewards, dones = inputs
+    f64 = lambda t: t.detach().numpy().astype(np.float64).copy()       # noqa: E731
+    adv = stock_advantages(critic, x, nx, rewards, dones)
+    out = dict(adv={k: f64(v) for k, v in adv.items()}, running_adv=running_of((actor, critic)), epochs=[])
+    xs, a, old_t = torch.from_numpy(x).to(dtype), torch.from_numpy(actions), torch.from_numpy(np.asarray(old)).to(dtype)
+    params = [p for net in (actor, critic) for p in net.parameters()]
+    out["start"] = [f64(p).reshape(-1) for p in params]
+    opts = (torch.optim.Adam(actor.parameters(), lr=LR_ACTOR, eps=LR_ACTOR), torch.optim.Adam(critic.parameters(), lr=LR_CRITIC, eps=LR_CRITIC))
+    for _ in range(epochs):
+        ep = {}
+        if margins:
+            ep["margin"] = relu_margin((actor, critic), xs)
+        log_probs, entropies = categorical_parts(actor(xs), a)
+        entropy = entropies.mean()
+        ratio = torch.exp(log_probs - old_t)
+        actor_loss = -torch.min(ratio * adv["advantages"], torch.clamp(ratio, 1 - CLIP, 1 + CLIP) * adv["advantages"]).mean()
+        value_loss = F.mse_loss(critic(xs).squeeze(), adv["returns"])
+        loss = actor_loss + VALUE_COEF * value_loss - ENTROPY_COEF * entropy
+        for opt in opts:
+            opt.zero_grad()
+        loss.backward()
+        ep["losses"] = np.array([float(t.detach()) for t in (loss, actor_loss, value_loss, entropy)])
+        ep["grads"] = [f64(p.grad).reshape(-1) for p in params]
+        ep["norms"] = tuple(float(torch.nn.utils.clip_grad_norm_(net.parameters(), MAX_NORM)) for net in (actor, critic))
+        for opt in opts:
+            opt.step()
+        ep["delta"] = [f64(p).reshape(-1) - s for p, s in zip(params, out["start"])]
+        ep["ratio"] = f64(ratio)
+        out["epochs"].append(ep)
+    out["running"] = running_of((actor, critic))
+    out["tracked"] = [int(bn.num_batches_tracked) for net in (actor, critic) for bn in (net.bn1, net.bn2)]
+    return out
+
+
+def loop_margins_hold(nets64, seed):
+    """The seed's condition: the ReLU margin holds for the next states under the initial critic and for the states in every epoch
+    of the float64 run."""
+    inputs = loop_inputs(seed)
+    if relu_margin(nets64[1:], torch.from_numpy(inputs[1]).double()) < RELU_MARGIN:
+        return False
+    if relu_margin(nets64, torch.from_numpy(inputs[0]).double()) < RELU_MARGIN:
+        return False
+    actions, old, _, _ = recipe(nets64, inputs[0])
+    return all(ep["margin"] >= RELU_MARGIN for ep in stock_loop(nets64, inputs, actions, old, margins=True)["epochs"])
+
+
+def find_loop_seed(nets64, start=0, limit=20000):
+    for seed in range(start, start + limit):
+        if loop_margins_hold(nets64, seed):
+            return seed
+    raise RuntimeError("no board seed in %d .. %d keeps the ReLU margin through the epochs" % (start, start + limit))
+
+
+class LoopCase:
+    """The closed-loop case: the inputs, the float64 run (the reference), the float32 run (the measure) and the case's bound,
+    F32_FACTOR x the worst gradient tensor of the float32 run's first epoch against float64's, as in Case."""
+
+    def __init__(self, seed):
+        self.seed = seed
+        self.nets32 = make_modules()
+        self.nets64 = tuple(copy.deepcopy(net).double() for net in self.nets32)
+        self.inputs = loop_inputs(seed)
+        self.x = self.inputs[0]
+        self.actions, self.old, _, _ = recipe(self.nets64, self.x)
+        self.want = stock_loop(self.nets64, self.inputs, self.actions, self.old, margins=True)
+        self.f32 = stock_loop(self.nets32, self.inputs, self.actions, self.old)
+        self.yardstick = float(ratios(self.f32["epochs"][0]["grads"], self.want["epochs"][0]["grads"]).max())
+        self.bound = F32_FACTOR * self.yardstick
+        self.adv_bound = advantage_bound((self.f32["adv"]["returns"], self.f32["adv"]["advantages"]),
+                                         (self.want["adv"]["returns"], self.want["adv"]["advantages"]))
+
+
+@functools.lru_cache(maxsize=None)
+def loop_case():
+    return LoopCase(LOOP_SEED)

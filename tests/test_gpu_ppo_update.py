@@ -20,7 +20,9 @@ Measured on an MI355X (per case in docs/LOG.md R23.1): gradients 0.27 - 2.28 x t
 n = 17; loss parts <= 0.16 x; probabilities <= 0.26 x, values <= 0.43 x (1.54 x at n = 1, where the yardstick is 3.6e-7); running
 statistics <= 0.14 x after one call and <= 0.36 x after three; the clamp case 0.61 x (loss parts against stock float32 0.11 x); the
 reference classes' fixture 0.41 x of a yardstick of 1.6e-5; advantages <= 8.3e-8 of their maxima (bound 3.8e-6); the Adam step at most
-0.12 of its derived tolerance."""
+0.12 of its derived tolerance. Added with docs/LOG.md R24.1: n = 31, 33, 224, 225 (the edges of BatchNorm's 32 row groups and its
+passes of 256 rows; gradients 1.49, 2.35, 1.19, 1.88 x) and the advantages block at n = 255, 256, 257, 4,095 (<= 9.5e-8). The regimes
+away from this one are in tests/test_gpu_ppo_update_edges.py."""
 import copy
 
 import numpy as np
@@ -69,13 +71,14 @@ def split_running(running):
 class Call:
     """One g2048_ppo_loss_grad call through ops into padded outputs; everything the checks need, as float64 NumPy plus the bits."""
 
-    def __init__(self, learner, c, run_a, run_c, workspace, fill):
+    def __init__(self, learner, c, run_a, run_c, workspace, fill, args=None):
         from g2048 import ops
+        clip, value_coef, entropy_coef = c.coefs
         self.ga_all, ga = padded(ops.ppo_plain_floats(4), fill)
         self.gc_all, gc = padded(ops.ppo_plain_floats(1), fill)
         self.l_all, losses = padded(4, fill)
-        ops.ppo_loss_grad(*to_dev(*c.args), learner.actor.plain, learner.critic.plain, run_a, run_c, R.CLIP, R.VALUE_COEF, R.ENTROPY_COEF,
-                          grad_actor=ga, grad_critic=gc, losses=losses, workspace=workspace)
+        ops.ppo_loss_grad(*to_dev(*(c.args if args is None else args)), learner.actor.plain, learner.critic.plain, run_a, run_c, clip,
+                          value_coef, entropy_coef, grad_actor=ga, grad_critic=gc, losses=losses, workspace=workspace)
         torch.cuda.synchronize()
         self.bits = [t.clone() for t in (ga, gc, losses)]
         self.grads = split(learner.actor, ga) + split(learner.critic, gc)
@@ -176,7 +179,7 @@ def test_batch_above_the_limit_is_refused():
         learner.advantages(x, x, f, f)
 
 
-@pytest.mark.parametrize("n", [1, 2, 17, 4096])
+@pytest.mark.parametrize("n", [1, 2, 17, 255, 256, 257, 4095, 4096])      # 255 .. 257: the edges of the block's 256-thread tree
 def test_advantages_against_float64_torch(n):
     """ppo_agent.py:368-373 with dones of 0 and 1 against the same lines in float64 torch (no normalisation at n = 1). The bound:
     the inputs are float32 and the lines are a handful of float32 operations and two sums of n terms; stock float32 torch on the

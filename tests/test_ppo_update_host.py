@@ -1,5 +1,6 @@
 """CPU-side checks of the PPO update's loss and gradient pass (g2048.DevicePPOLearner, g2048_ppo_loss_grad): the conditions on the
-inputs of tests/test_gpu_ppo_update.py that keep it from being vacuous or flaky, the by-hand Categorical of the clamp case
+inputs of tests/test_gpu_ppo_update.py and tests/test_gpu_ppo_update_edges.py that keep them from being vacuous or flaky (each edge
+case is in the regime it claims: poisoned, saturated, other coefficients, dead features, a whole update), the by-hand Categorical of the clamp case
 against torch's own, the fixture of the reference's own classes, the plain layout's offsets, the converter's refusals and the
 C-ABI's argument validation. The kernels themselves are checked on the GPU."""
 import ctypes as C
@@ -228,3 +229,181 @@ def test_ppo_entry_points_validate_without_device():
                dict(vc=float("inf"))):
         assert lg(**kw) == -1 and b"finite and not negative" in L.g2048_last_error(), kw
     assert lg(n=4097) == -1 and b"G2048_PPO_BATCH_MAX" in L.g2048_last_error() and b"not truncated" in L.g2048_last_error()
+
+
+# ---------------------------------------------------------------------- the edge cases of tests/test_gpu_ppo_update_edges.py --
+def quiet_update(nets, args, **kw):
+    import warnings
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        return R.stock_update(nets, *args, **kw)
+
+
+@pytest.mark.parametrize("n", R.POISON_SIZES)
+def test_poisoned_inputs_are_what_they_claim_in_stock_torch(n):
+    """Per poison: exactly the last row of the named array differs from the case's (with a sign asked for, that row's advantage
+    too); stock float32 and float64 agree on the class of every loss part and on which gradient tensors hold a non-finite value
+    (the pattern the device is held to is no accident of one precision); the network the poison does not reach keeps the case's
+    gradients; old = +inf leaves everything finite, every other poison does not; and old = nan and old = -inf with A = 0, the
+    two whose loss a minimum that drops NaN would report as finite, have a NaN loss with every actor gradient non-finite."""
+    c = R.case(n)
+    assert (n - 1) % 64 == 0 or n == 17                  # 129: row 128 is the first row of the head's third block of 64
+    assert abs(c.adv[-1]) > 0.1
+    for name, which, value, sign, clean in R.POISONS:
+        args = R.poisoned_args(c, which, value, sign)
+        for got, was, key in zip(args[2:], c.args[2:], ("old", "adv", "ret")):
+            assert np.array_equal(got[:-1], was[:-1]), name
+            assert np.array_equal(got[-1:], was[-1:], equal_nan=True) == (key != which and not (key == "adv" and sign is not None
+                                                                                                   and got[-1] != was[-1])), name
+        if sign is not None:
+            assert np.sign(args[3][-1]) == sign
+        f32, f64 = quiet_update(c.nets32, args), quiet_update(c.nets64, args)
+        assert R.classes(f32["losses"]) == R.classes(f64["losses"]), name
+        assert R.nonfinite(f32["grads"]) == R.nonfinite(f64["grads"]), name
+        keep = slice(12, 24) if clean == "critic" else slice(0, 12)
+        assert all(np.array_equal(a, b) for a, b in zip(f64["grads"][keep], c.want["grads"][keep])), name
+        print("n = %d, %s: loss parts %s, non-finite gradient tensors %d" % (n, name, R.classes(f32["losses"]), sum(R.nonfinite(f32["grads"]))))
+        if name == "old=+inf":
+            assert R.classes(f32["losses"]) == ["finite"] * 4 and not any(R.nonfinite(f32["grads"]))
+            assert f64["ratio"][-1] == 0.0
+        else:
+            other = slice(0, 12) if clean == "critic" else slice(12, 24)
+            assert all(R.nonfinite(f32["grads"][other])) and not any(R.nonfinite(f32["grads"][keep])), name
+        if name in ("old=nan", "old=-inf,A=0"):
+            assert R.classes(f32["losses"])[:2] == ["nan", "nan"]
+        if name == "old=-inf,A>0":                      # a finite loss over NaN gradients: stock torch's own behaviour (0 x inf in exp's backward)
+            assert R.classes(f32["losses"]) == ["finite"] * 4
+
+
+def test_advantage_block_inputs():
+    """The advantages block's NaN case and zero-deviation case in stock torch: a NaN reward makes its own return and every advantage
+    NaN; with rewards 1, values 0.25 and next values 0 every float32 step of the block is exact, the deviation is exactly 0 and
+    the divisor is 1e-8 in float32 and float64 alike."""
+    n = 17
+    rewards = np.ones(n, np.float32)
+    rewards[5] = np.nan
+    ret, adv = R.advantage_lines(torch.float32, np.zeros(n, np.float32), np.ones(n, np.float32), rewards, np.zeros(n, np.float32))
+    assert np.isnan(ret).sum() == 1 and np.isnan(ret[5]) and np.isnan(adv).all()
+    flat = (np.full(n, 0.25, np.float32), np.zeros(n, np.float32), np.ones(n, np.float32), np.zeros(n, np.float32))
+    for dtype in (torch.float32, torch.float64):
+        ret, adv = R.advantage_lines(dtype, *flat)
+        assert np.array_equal(ret, np.ones(n)) and np.array_equal(adv, np.zeros(n))
+
+
+def test_saturated_case_is_saturated():
+    """The saturated case's conditions, from the float64 modules: the largest logit gap of a row exceeds 89 (an exp without the
+    maximum subtracted overflows float32); on a quarter to three quarters of the rows 1 - max q < 2^-23 / 8 (float32's q is
+    exactly 1 and the upper clamp binds) and on no row is it within a factor 8 of 2^-23, where float32 and float64 could decide
+    differently; no q within 1 % of 2^-23; saturated rows that take the saturated action, rows that take an action clamped from
+    below; ratios on both clip branches; the by-hand float32 evaluation is torch's bit for bit; SAT_SEED is the scan's answer.
+    The yardstick is held to 1e-4, the bound of the n = 2 and 3 cases: fc4's weights, and with them the trunk's gradients, are
+    128 times the fresh modules'."""
+    c = R.saturated_case()
+    assert R.find_saturated_seed(c.nets64) == R.SAT_SEED == c.seed
+    assert R.relu_margin(c.nets64, torch.from_numpy(c.x).double()) >= R.RELU_MARGIN
+    m = R.saturated_measures(c.nets64, c.x)
+    sat = m["rest"] < R.SAT_LOW
+    rows = np.arange(R.SAT_N)
+    taken = m["q"][rows, c.actions]
+    print("saturated case: seed %d, logit gap %.4g, %d of %d rows saturated, float32 yardstick %.3g, ratios %.3g .. %.3g, 1 - max q %.3g .. %.3g"
+          % (c.seed, m["gap"], sat.sum(), R.SAT_N, c.yardstick, c.want["ratio"].min(), c.want["ratio"].max(), m["rest"].min(), m["rest"].max()))
+    assert m["gap"] > 89
+    assert 0.25 <= sat.mean() <= 0.75
+    assert not ((m["rest"] >= R.SAT_LOW) & (m["rest"] <= R.SAT_HIGH)).any()
+    assert (np.abs(m["q"] / R.F32_EPS - 1) >= 0.01).all()
+    assert (sat & (c.actions == m["top"])).any() and (taken < R.F32_EPS).any() and R.saturated_ok(m)
+    assert (c.f32["probs"].max(1)[sat] == 1.0).all() and (c.f32["probs"].max(1)[~sat] < 1.0).all()
+    r = c.want["ratio"]
+    assert (r < 1 - R.CLIP).any() and (r > 1 + R.CLIP).any()
+    assert min(np.abs(r - (1 - R.CLIP)).min(), np.abs(r - (1 + R.CLIP)).min()) >= 1e-3
+    hand = R.stock_update(c.nets32, *c.args, eps=R.F32_EPS)
+    assert np.array_equal(hand["losses"], c.f32["losses"]) and all(np.array_equal(a, b) for a, b in zip(hand["grads"], c.f32["grads"]))
+    assert np.isfinite(c.want["losses"]).all() and all(np.isfinite(g).all() and g.any() for g in c.want["grads"])
+    assert 0 < c.yardstick <= 1e-4
+
+
+def test_coefficient_sets_cannot_be_ignored():
+    """The three coefficient sets at n = 17: a fair float32 yardstick, no ratio within 1e-3 of the set's own clip edges, and the
+    float64 gradients differ between every two sets (the default's included) and from what each single coefficient replaced by the
+    reference's would give, by at least 1e-2 of max|g| on some tensor: over a hundred times the bound, so that a constant in place
+    of an argument cannot pass. value_coef = 0 makes every critic gradient exactly 0 in float64."""
+    base = R.case(17)
+    sets = [base] + [R.coef_case(k) for k in range(3)]
+
+    def differ(a, b):
+        r = R.ratios(a, b)
+        return float(np.where(np.isfinite(r), r, 1.0).max())       # inf: a tensor that is exactly 0 on one side only
+    for i, a in enumerate(sets):
+        clip = a.coefs[0]
+        r = a.want["ratio"]
+        assert 0 < a.yardstick <= 1e-5
+        assert min(np.abs(r - (1 - clip)).min(), np.abs(r - (1 + clip)).min()) >= 1e-3
+        for b in sets[i + 1:]:
+            d = differ(a.want["grads"], b.want["grads"])
+            print("coefficients %s against %s: the gradients differ by %.3g of max|g|" % (a.coefs, b.coefs, d))
+            assert d >= 1e-2 >= 100 * max(a.bound, b.bound)
+    default = (R.CLIP, R.VALUE_COEF, R.ENTROPY_COEF)
+    for c in sets[1:]:
+        for pos, name in enumerate(("clip", "value_coef", "entropy_coef")):
+            alt = list(c.coefs)
+            alt[pos] = default[pos]
+            other = R.stock_update(c.nets64, *c.args, clip=alt[0], value_coef=alt[1], entropy_coef=alt[2])
+            d = differ(other["grads"], c.want["grads"])
+            print("coefficients %s with the reference's %s: the gradients differ by %.3g of max|g|" % (c.coefs, name, d))
+            assert d >= 1e-2
+    zero = R.coef_case(1)
+    assert zero.coefs[1] == 0.0 and all(not g.any() for g in zero.want["grads"][12:]) and all(g.any() for g in zero.want["grads"][:12])
+    assert R.coef_case(0).coefs[2] == 0.0 and R.coef_case(2).coefs[0] == 0.0
+
+
+def test_dead_feature_case():
+    """fc1.bias = -10 on features 0 - 7 of both modules at n = 17: these are 0 on every row after the ReLU, and so are, at this
+    seed, the features DEAD_ACTOR / DEAD_CRITIC name beyond them (found anew here); in float64 their fc1 and bn1.weight gradients
+    are exactly 0, bn1.bias's and fc2.weight's columns are not. The ReLU margin is taken without the eight forced features: they lie
+    at -10 +- 1, far from 0, and would otherwise only raise the layer's max|z| the margin is relative to."""
+    c = R.dead_case()
+    x64 = torch.from_numpy(c.x).double()
+    for net, dead, base in zip(c.nets64, (R.DEAD_ACTOR, R.DEAD_CRITIC), (0, 12)):
+        assert R.dead_features(net, c.x) == tuple(sorted(dead)) and dead[:8] == R.DEAD
+        z = R.relu_inputs(net, x64)
+        assert float(z[0][:, :8].max()) < -5.0
+        z[0] = z[0][:, 8:]
+        margin = min(float(t.abs().min() / t.abs().max()) for t in z)
+        print("dead-feature case: %d dead features, ReLU margin %.3g" % (len(dead), margin))
+        assert margin >= R.RELU_MARGIN
+        g = c.want["grads"]
+        idx = list(dead)
+        assert not g[base + 0].reshape(256, 16)[idx].any() and not g[base + 1][idx].any() and not g[base + 2][idx].any()
+        assert np.abs(g[base + 3][idx]).min() > 0 and np.abs(g[base + 4].reshape(128, 256)[:, idx]).max(0).min() > 0
+    assert 0 < c.yardstick <= 1e-5
+    p, r = c.want["probs"], c.want["ratio"]
+    assert p.min() >= 1e-3 and p.max() <= 1 - 1e-3
+    assert min(np.abs(r - (1 - R.CLIP)).min(), np.abs(r - (1 + R.CLIP)).min()) >= 1e-3
+
+
+def test_closed_loop_case():
+    """The whole-update case (n = 48, 3 epochs, the advantages block first): LOOP_SEED is the scan's answer; the ReLU margin holds
+    for the next states under the initial critic and for the states under the weights of every epoch of the float64 run; the clip
+    acts on both networks in every epoch; the ratios are on both clip branches in the last epoch; both done values occur; the
+    advantages depend on WHICH forward's values are subtracted; and with Adam's eps = lr the float32 run's parameters stay
+    within 1e-6 of max|p| of the float64 run's (at eps = 1e-8 a gradient within rounding of zero moves a weight by 2 lr)."""
+    c = R.loop_case()
+    assert R.find_loop_seed(c.nets64) == R.LOOP_SEED == c.seed
+    x, nx, rewards, dones = c.inputs
+    assert not np.array_equal(x, nx) and set(dones.tolist()) == {0.0, 1.0}
+    assert R.relu_margin(c.nets64[1:], torch.from_numpy(nx).double()) >= R.RELU_MARGIN
+    assert 0 < c.yardstick <= 1e-5
+    adv = c.want["adv"]
+    swapped = R.advantage_lines(torch.float64, adv["next_values"], adv["next_values"], rewards, dones)[1]
+    assert R.rel(swapped, adv["advantages"]) > 1e-2 > 1000 * c.adv_bound
+    for e, (w, f) in enumerate(zip(c.want["epochs"], c.f32["epochs"])):
+        dev = max(np.abs(a - b).max() / np.abs(s).max() for a, b, s in zip(f["delta"], w["delta"], c.want["start"]))
+        print("epoch %d: ReLU margin %.3g, gradient norms %.3g (actor) %.3g (critic), ratios %.3g .. %.3g, float32 run off by %.3g of max|p|"
+              % (e, w["margin"], w["norms"][0], w["norms"][1], w["ratio"].min(), w["ratio"].max(), dev))
+        assert w["margin"] >= R.RELU_MARGIN
+        assert min(w["norms"]) > R.MAX_NORM and min(f["norms"]) > R.MAX_NORM
+        assert dev <= 1e-6
+        assert all(np.abs(d).max() > 0 for d in w["delta"])
+    r = c.want["epochs"][-1]["ratio"]
+    assert (r < 1 - R.CLIP).any() and (r > 1 + R.CLIP).any()
+    assert c.want["tracked"] == [3, 3, 5, 5] and len(c.want["epochs"]) == R.LOOP_EPOCHS
