@@ -18,19 +18,14 @@
 // No atomics, no block waits on another, nothing depends on the compute-unit count: two calls give the same bits.
 #include <hip/hip_runtime.h>
 
-#include <cmath>
-#include <stdlib.h>
-
 #include "../../include/g2048.h"
 #include "g2048_host.h"
-#include "g2048_mfma.h"
+#include "g2048_step_common.h"      // wave_sum, block_sum, load_group, store_group, decimal_of, good_hyper
 
 namespace {
 
 using namespace g2048;
 
-constexpr int kStepThreads = 256;
-constexpr size_t kStepGroup = 4 * kStepThreads;      // floats a block takes in one pass: 16 bytes a lane
 constexpr size_t kEpsBase = 139616;                  // the first layer's block starts here (a multiple of 4)
 constexpr size_t kFcFloats = 4 * 128 + 4;
 static_assert(G2048_QNET_STEP_MAX_PARTIALS == 4 * kStepThreads, "the update kernel reads four partial sums a thread");
@@ -45,41 +40,6 @@ constexpr size_t step_chunk(size_t floats)
     return (per + kStepGroup - 1) / kStepGroup * kStepGroup;
 }
 constexpr size_t step_partials(size_t floats) { return (floats + step_chunk(floats) - 1) / step_chunk(floats); }
-
-// the same on every lane: the xor butterfly adds the same pairs everywhere, and a + b is b + a
-__device__ inline double wave_sum(double v)
-{
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s);
-    return v;
-}
-
-// the block's sum, the same on every thread: the four wavefronts' sums through LDS, added pairwise
-__device__ inline double block_sum(double v, double (&red)[kStepThreads / 64])
-{
-    v = wave_sum(v);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
-
-// the 1 .. 4 floats at `at` (a multiple of 4): a short group is the buffer's tail, the missing floats read as zero
-__device__ inline f4 load_group(const float *__restrict__ p, size_t at, size_t floats)
-{
-    if (at + 4 <= floats) return load_f4(p + at);
-    f4 v = splat(0.0f);
-    for (size_t j = 0; at + j < floats; ++j) v[j] = p[at + j];
-    return v;
-}
-
-__device__ inline void store_group(float *__restrict__ p, size_t at, size_t floats, f4 v)
-{
-    if (at + 4 <= floats) {
-        *reinterpret_cast<f4 *>(p + at) = v;
-        return;
-    }
-    for (size_t j = 0; at + j < floats; ++j) p[at + j] = v[j];
-}
 
 // ------------------------------------------------------------------------------------------------------------- norm --
 // partial[block] = the sum of grad[i]^2 over the block's chunk: thread t takes the groups t, t + 256, .. of the chunk in order, one
@@ -155,21 +115,6 @@ __global__ __launch_bounds__(kStepThreads) void qs_update_kernel(float *__restri
         store_group(exp_avg_sq, at, floats, v);
     }
 }
-
-// A float hyper-parameter as the decimal its caller wrote: the shortest decimal that rounds to it (0.999f -> 0.999), in f64. The
-// update needs 1 - beta, and 1 - (double)0.999f is 1.3e-5 off 0.001: the second moment would be scaled by that much against
-// torch's, whose AdamW forms 1 - beta2 from the Python scalar. A value that is no short decimal comes back within half an ulp.
-inline double decimal_of(float v)
-{
-    char s[32];
-    for (int digits = 1; digits <= 9; ++digits) {
-        snprintf(s, sizeof s, "%.*g", digits, (double)v);
-        if (strtof(s, nullptr) == v) break;
-    }
-    return strtod(s, nullptr);
-}
-
-inline bool good_hyper(float v) { return std::isfinite(v) && v >= 0.0f; }
 
 }  // namespace
 

@@ -13,7 +13,8 @@ import subprocess
 CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "csrc")
 LIB = os.environ.get("G2048_LIB") or os.path.join(CSRC, "libg2048_hip.so")     # G2048_LIB: A/B builds only (tools/)
 SOURCES = ["g2048_kernels.hip", "g2048_beam.hip", "g2048_rollout.hip", "g2048_policy.hip", "g2048_tpolicy.hip",
-           "g2048_qnet.hip", "g2048_qnet_batch.hip", "g2048_qnet_grad.hip", "g2048_qnet_step.hip", "g2048_per.hip", "g2048_ppo_grad.hip"]
+           "g2048_qnet.hip", "g2048_qnet_batch.hip", "g2048_qnet_grad.hip", "g2048_qnet_step.hip", "g2048_per.hip", "g2048_ppo_grad.hip",
+           "g2048_ppo_step.hip"]
 INCLUDE = os.path.join(CSRC, "..", "..", "include")
 PUBLIC_HEADERS = [os.path.join(INCLUDE, "g2048.h"), os.path.join(INCLUDE, "g2048_testing.h")]
 # -fvisibility=hidden: the export table is exactly what the two headers declare with G2048_API (tests/test_abi_and_host.py)

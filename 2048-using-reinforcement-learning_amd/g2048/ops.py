@@ -1652,6 +1652,74 @@ def ppo_loss_grad(states, actions, old_log_probs, advantages, returns, plain_act
     return losses, grad_actor, grad_critic
 
 
+def ppo_step_workspace_bytes():
+    """Bytes of the workspace ppo_adam_step needs (g2048_ppo_step_workspace): the scalars its first launch prepares."""
+    return L.lib().g2048_ppo_step_workspace()
+
+
+def ppo_pair(v, name):
+    """(actor's, critic's) of a hyper-parameter given as a scalar or a pair."""
+    if isinstance(v, (tuple, list)):
+        if len(v) != 2:
+            raise ValueError("g2048: %s must be a scalar or an (actor, critic) pair" % name)
+        return float(v[0]), float(v[1])
+    return float(v), float(v)
+
+
+def ppo_adam_step(plain_actor, grad_actor, exp_avg_actor, exp_avg_sq_actor, plain_critic, grad_critic, exp_avg_critic, exp_avg_sq_critic,
+                  counters, losses=None, lr=(8e-4, 2e-3), betas=(0.9, 0.999), eps=1e-8, max_norm=0.5, norms=None, workspace=None):
+    """What follows backward() in an epoch of PPOAgent.update (agents/ppo_agent.py:403-416) for both networks in two launches
+    (g2048_ppo_adam_step): the NaN check on losses[0], clip_grad_norm_(max_norm) per network and an Adam step per network. The
+    eight buffers are flat float32 device tensors of ppo_plain_floats(4) (actor) and ppo_plain_floats(1) (critic) in the plain
+    layout, all updated IN PLACE (the gradients are left clipped); counters is int64 (4,) on the device = {actor steps applied,
+    critic steps applied, calls skipped for a NaN loss, calls skipped for a gradient norm that is not finite}, and the bias
+    correction's step number is taken from it ON THE DEVICE. losses: ppo_loss_grad's float32 (4,) (or any float32 tensor whose
+    first element is the loss), None: no loss gate. lr and eps are a scalar or an (actor, critic) pair; max_norm None means no
+    clipping. A NaN loss or a norm of either network that is not finite leaves all eight buffers and both step counters untouched.
+    No synchronisation. Returns the two gradient norms before clipping, float32 (2,), written on every call."""
+    buffers = (("plain_actor", plain_actor, 4), ("grad_actor", grad_actor, 4), ("exp_avg_actor", exp_avg_actor, 4),
+               ("exp_avg_sq_actor", exp_avg_sq_actor, 4), ("plain_critic", plain_critic, 1), ("grad_critic", grad_critic, 1),
+               ("exp_avg_critic", exp_avg_critic, 1), ("exp_avg_sq_critic", exp_avg_sq_critic, 1))
+    for name, t, n_out in buffers:          # dtype and length of all eight before any device: such a mistake reads the same everywhere
+        floats = ppo_plain_floats(n_out)
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("g2048: %s must be a torch.Tensor" % name)
+        if t.dtype != torch.float32 or t.dim() != 1 or t.numel() != floats:
+            raise (TypeError if t.dtype != torch.float32 else ValueError)(
+                "g2048: %s must be a flat float32 tensor of %d floats (got %s %s)" % (name, floats, t.dtype, tuple(t.shape)))
+    for name, t, _ in buffers:
+        L.require_device_tensor(t, torch.float32, None, name)
+        if t.device != plain_actor.device:
+            raise ValueError("g2048: %s on %s, plain_actor on %s" % (name, t.device, plain_actor.device))
+    dev = plain_actor.device
+    L.require_device_tensor(counters, torch.int64, None, "counters")
+    if counters.dim() != 1 or counters.numel() != 4:
+        raise ValueError("g2048: counters must be an int64 tensor of 4")
+    if losses is not None:
+        L.require_device_tensor(losses, torch.float32, None, "losses")
+        if losses.numel() < 1:
+            raise ValueError("g2048: losses must hold at least one float32")
+    if norms is None:
+        norms = torch.empty(2, dtype=torch.float32, device=dev)
+    L.require_device_tensor(norms, torch.float32, None, "norms")
+    if norms.numel() != 2:
+        raise ValueError("g2048: norms must hold two float32")
+    nb = ppo_step_workspace_bytes()
+    if workspace is None:
+        workspace = torch.empty(nb, dtype=torch.uint8, device=dev)
+    L.require_device_tensor(workspace, torch.uint8, None, "workspace")
+    if workspace.numel() < nb:
+        raise ValueError("g2048: workspace must hold at least %d bytes" % nb)
+    for t, name in ((counters, "counters"), (losses, "losses"), (norms, "norms"), (workspace, "workspace")):
+        if t is not None and t.device != dev:
+            raise ValueError("g2048: %s on %s, plain_actor on %s" % (name, t.device, dev))
+    (lr_a, lr_c), (eps_a, eps_c) = ppo_pair(lr, "lr"), ppo_pair(eps, "eps")
+    L.call(dev, L.lib().g2048_ppo_adam_step, *[t.data_ptr() for _, t, _ in buffers], losses.data_ptr() if losses is not None else None,
+           counters.data_ptr(), lr_a, lr_c, float(betas[0]), float(betas[1]), eps_a, eps_c,
+           float("inf") if max_norm is None else float(max_norm), norms.data_ptr(), workspace.data_ptr(), L.stream_ptr(dev))
+    return norms
+
+
 def launch_plan(compute_units=0, resident_blocks_per_cu=0, n_games=0):
     """The chip-size arithmetic of the library (g2048_launch_plan; a host function, usable without a GPU when compute_units
     is given): dict(order_row, order_min_games, helper_cap, default_helpers)."""

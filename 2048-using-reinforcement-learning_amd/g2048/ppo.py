@@ -1,4 +1,4 @@
-"""The gradient half of the reference's PPOAgent.update() (agents/ppo_agent.py:357-400) on the device.
+"""The reference's PPOAgent.update() (agents/ppo_agent.py:357-416) on the device.
 
 `DevicePPOLearner(actor, critic, clip_epsilon=0.3, value_coef=0.4, entropy_coef=0.05)` takes the reference's ActorNetwork /
 CriticNetwork layout (attributes fc1..fc4 Linear 16-256-128-64-{4|1}, bn1, bn2 BatchNorm1d, in either mode; anything else raises
@@ -10,8 +10,24 @@ Each network lives in three flat float32 buffers on the modules' device: `plain`
 the module's named_parameters() order), `grad` (same layout, overwritten by loss_and_grad) and `running` (bn1.running_mean,
 bn1.running_var, bn2.running_mean, bn2.running_var). attach_params() makes the modules' parameters and running buffers views
 into them, attach_grads() the parameters' .grad: from then on loss_and_grad, clip_grad_norm_, a stock torch.optim.Adam step and
-DevicePolicy.refresh() (on the same modules, back in eval mode) form a whole update with no copy. There is no Adam kernel for
-these buffers. Nothing here synchronises with the host; the outputs are buffers owned by the learner, one set per (N, stream).
+DevicePolicy.refresh() (on the same modules, back in eval mode) form a whole update with no copy.
+
+The end of every epoch (:403-416: the NaN check on the loss, clip_grad_norm_(0.5) per network, an Adam step per network) is
+adam_step(): two launches over both networks (g2048_ppo_adam_step), the moments in two more buffers per network (`exp_avg`,
+`exp_avg_sq`, laid out like `plain`). update() is the whole sequence: advantages(), then per epoch loss_and_grad and adam_step.
+No host decision and no host read is in it, so the rules that the reference decides on the host are decided on the device:
+
+  the skip rules   a call of adam_step changes NOTHING in plain, grad, exp_avg and exp_avg_sq of EITHER network if (1) the loss it
+      is given is a NaN (the reference's `if torch.isnan(loss): continue`; isnan only, a +inf loss over finite gradients is
+      applied), or else (2) the gradient norm of either network is not finite (stock torch would write NaN into that network's
+      weights; an update that reaches one network and not the other is of no use to a caller).
+  the counters     `opt_counters`, int64 (4,) on the device: {actor steps applied, critic steps applied, calls skipped by (1),
+      calls skipped by (2)}. Adam's bias correction takes its step number from the first two ON THE DEVICE: a skipped call does
+      not advance it, as the reference's `continue` does not reach optimizer.step(). The host never learns of a skip unless it
+      reads the counters.
+
+Nothing here synchronises with the host (optimizer_state_dict / load_optimizer_state_dict excepted); the outputs are buffers owned
+by the learner, one set per (N, stream).
 """
 import torch
 import torch.nn as nn
@@ -50,7 +66,7 @@ def parse(module, n_out):
 
 
 class _TrainNet:
-    """One network's module and its three flat buffers."""
+    """One network's module and its flat buffers: plain, grad, running, and adam_step's exp_avg and exp_avg_sq."""
 
     def __init__(self, module, n_out):
         self.module, self.n_out = module, n_out
@@ -96,6 +112,28 @@ class _TrainNet:
         for p, (_, o, _) in zip(self.params, self.offsets):
             p.grad = self.grad[o:o + p.numel()].view(p.shape)
 
+    @property
+    def params_attached(self):
+        """True while the module's parameters are the views attach_params() made (the first and the last are looked at)."""
+        base = self.plain.data_ptr()
+        return all(self.params[i].data_ptr() == base + 4 * self.offsets[i][1] for i in (0, -1))
+
+    def _moment(self, key):
+        t = self.__dict__.get(key)
+        if t is None:
+            t = self.__dict__[key] = torch.zeros_like(self.plain)
+        return t
+
+    @property
+    def exp_avg(self):
+        """Adam's first moment of adam_step: float32, laid out like `plain` (zeros, allocated on first use)."""
+        return self._moment("_exp_avg")
+
+    @property
+    def exp_avg_sq(self):
+        """Adam's second moment of adam_step, like exp_avg."""
+        return self._moment("_exp_avg_sq")
+
     def tracked(self, n):
         """What torch's training-mode forward does next to the running statistics: num_batches_tracked += 1, on the device."""
         if n > 1:
@@ -127,6 +165,21 @@ def _workspace(n, device):             # refuses n = 0 and n above the maximum
     return torch.empty(ops.ppo_train_workspace_bytes(n), dtype=torch.uint8, device=device)
 
 
+def _norms(n, device):                 # adam_step's two gradient norms
+    return torch.empty(2, dtype=torch.float32, device=device)
+
+
+def _step_workspace(n, device):
+    return torch.empty(ops.ppo_step_workspace_bytes(), dtype=torch.uint8, device=device)
+
+
+def _update_outputs(epochs, device):   # update()'s losses and norms, a row an epoch
+    return torch.empty((epochs, 4), dtype=torch.float32, device=device), torch.empty((epochs, 2), dtype=torch.float32, device=device)
+
+
+WHICH = ("actor", "critic")
+
+
 class DevicePPOLearner:
     """PPOAgent.update()'s networks, loss and gradients on the device (module docstring). The hyper-parameters default to the
     reference agent's. Dropout is ignored.
@@ -141,7 +194,15 @@ class DevicePPOLearner:
       the clamps and the minimum pass a NaN on (torch.relu / clamp / min, not fmaxf / fminf), so each loss part is finite, NaN,
       +inf or -inf where stock float32's is (a NaN or -inf old log-prob with advantage 0, a NaN state: a NaN loss), and a
       gradient tensor holds a non-finite value where stock's does. As in stock torch, old_log_probs = -inf under a positive
-      advantage gives a FINITE loss over NaN actor gradients (exp's backward, 0 x inf): check the gradients, not the loss alone.
+      advantage gives a FINITE loss over NaN actor gradients (exp's backward, 0 x inf): check the gradients, not the loss alone
+      (adam_step does: its second skip rule).
+    adam_step(losses=None, lr=(8e-4, 2e-3), max_norm=0.5, betas=(0.9, 0.999), eps=1e-8) -> float32 (2,) device tensor, the two
+      gradient norms before clipping: the rest of the epoch body (:403-416) for both networks in two launches; the skip rules and
+      opt_counters are in the module docstring.
+    update(states, actions, old_log_probs, rewards, next_states, dones, epochs=8, gamma=0.995, **adam_step's) -> (losses
+      (epochs,4), norms (epochs,2)): the whole of update() after the sampling, without one host read.
+    optimizer_state_dict(which) / load_optimizer_state_dict(which, state_dict), which "actor" or "critic": the moments and the step
+      counter in the format of torch.optim.Adam(module.parameters()).state_dict().
     1 <= N <= 4096; states are float32 (N,16) as RolloutCollector.sample returns them, not packed boards."""
 
     def __init__(self, actor, critic, clip_epsilon=0.3, value_coef=0.4, entropy_coef=0.05):
@@ -154,6 +215,8 @@ class DevicePPOLearner:
             raise ValueError("%s: actor and critic live on different devices" % NAME)
         self.device = self.actor.device
         self._out = OutputCache(NAME, self.device)
+        self.opt_counters = torch.zeros(4, dtype=torch.int64, device=self.device)
+        self._hyper = ((8e-4, 2e-3), (0.9, 0.999), 1e-8)      # the last adam_step's lr, betas, eps: optimizer_state_dict's groups
 
     def refresh(self):
         """Copies the modules' parameters and running statistics into the buffers (a no-op in effect after attach_params())."""
@@ -207,11 +270,121 @@ class DevicePPOLearner:
         return ops.ppo_advantages(values, next_values, rewards, dones, gamma, returns=returns, advantages=adv)
 
     def loss_and_grad(self, states, actions, old_log_probs, advantages, returns):
+        return self._loss_and_grad(states, actions, old_log_probs, advantages, returns, None)
+
+    def _loss_and_grad(self, states, actions, old_log_probs, advantages, returns, losses):
         n = self._rows(states)
         losses, _, _ = ops.ppo_loss_grad(states, actions, old_log_probs, advantages, returns, self.actor.plain, self.critic.plain,
                                          self.actor.running, self.critic.running, self.clip_epsilon, self.value_coef, self.entropy_coef,
-                                         grad_actor=self.actor.grad, grad_critic=self.critic.grad, losses=self._out.get(n, _losses),
-                                         workspace=self._out.get(n, _workspace))
+                                         grad_actor=self.actor.grad, grad_critic=self.critic.grad,
+                                         losses=self._out.get(n, _losses) if losses is None else losses, workspace=self._out.get(n, _workspace))
         self.actor.tracked(n)
         self.critic.tracked(n)
         return losses
+
+    def adam_step(self, losses=None, lr=(8e-4, 2e-3), max_norm=0.5, betas=(0.9, 0.999), eps=1e-8):
+        """The end of an epoch of update() (ppo_agent.py:403-416) on the device, after loss_and_grad: the NaN check on losses[0]
+        (losses: what loss_and_grad returned; None: no check), clip_grad_norm_(max_norm) on each network and an Adam step on each
+        network, in two launches over both (g2048_ppo_adam_step). plain is updated IN PLACE from grad (left clipped, as
+        clip_grad_norm_ leaves it), the moments are each network's exp_avg and exp_avg_sq. lr and eps are a scalar or an (actor,
+        critic) pair, the defaults the reference agent's; max_norm None: no clipping. A NaN loss, or a gradient norm of EITHER
+        network that is not finite, skips the call: no buffer of either network changes, and opt_counters[2] or [3] counts it;
+        otherwise opt_counters[0] and [1] go up by one, and they are the step numbers of Adam's bias correction, read on the
+        device (a skipped call does not advance them). Returns the two norms before clipping, float32 (2,) (the learner's own,
+        one per stream; written on a skipped call too), without synchronising. If attach_params() did not make the modules'
+        parameters views of the buffers, the call ends with write_back(): the modules equal the buffers bit for bit either way."""
+        norms = self._adam_step(losses, lr, max_norm, betas, eps, self._out.get(0, _norms))
+        self._plain_changed()
+        return norms
+
+    def _adam_step(self, losses, lr, max_norm, betas, eps, norms):
+        a, c = self.actor, self.critic
+        ops.ppo_adam_step(a.plain, a.grad, a.exp_avg, a.exp_avg_sq, c.plain, c.grad, c.exp_avg, c.exp_avg_sq, self.opt_counters,
+                          losses=losses, lr=lr, betas=betas, eps=eps, max_norm=max_norm, norms=norms,
+                          workspace=self._out.get(0, _step_workspace))
+        self._hyper = (lr, betas, eps)          # as given (ppo_adam_step accepted them); optimizer_state_dict reads them
+        return norms
+
+    def _plain_changed(self):
+        if not (self.actor.params_attached and self.critic.params_attached):
+            self.write_back()
+
+    def update(self, states, actions, old_log_probs, rewards, next_states, dones, epochs=8, gamma=0.995, **adam):
+        """PPOAgent.update() after its sampling (ppo_agent.py:357-416) on the device: advantages(states, next_states, rewards,
+        dones, gamma), then `epochs` times loss_and_grad and adam_step on that epoch's losses (**adam: adam_step's lr, max_norm,
+        betas, eps). A sequence of launches with no host decision and no host read: an epoch whose loss is a NaN or whose
+        gradients are not finite is skipped on the device (adam_step) and shows in opt_counters and in the returned rows. Returns
+        (losses float32 (epochs,4), norms float32 (epochs,2)), device tensors the learner owns (one pair per (epochs, stream)):
+        row e is epoch e's loss_and_grad result and its gradient norms before clipping. DevicePolicy.refresh() stays with the
+        caller."""
+        epochs = int(epochs)
+        if epochs < 1:
+            raise ValueError("%s: update needs at least one epoch" % NAME)
+        unknown = set(adam) - {"lr", "max_norm", "betas", "eps"}
+        if unknown:
+            raise TypeError("%s: update got unexpected arguments %s" % (NAME, sorted(unknown)))
+        adam = dict(dict(lr=(8e-4, 2e-3), max_norm=0.5, betas=(0.9, 0.999), eps=1e-8), **adam)
+        returns, adv = self.advantages(states, next_states, rewards, dones, gamma)
+        losses, norms = self._out.get(epochs, _update_outputs)
+        for e in range(epochs):
+            self._loss_and_grad(states, actions, old_log_probs, adv, returns, losses[e])
+            self._adam_step(losses[e], adam["lr"], adam["max_norm"], adam["betas"], adam["eps"], norms[e])
+        self._plain_changed()
+        return losses, norms
+
+    def _net(self, which):
+        if which not in WHICH:
+            raise ValueError("%s: which must be 'actor' or 'critic', got %r" % (NAME, which))
+        return (self.actor, self.critic)[WHICH.index(which)], WHICH.index(which)
+
+    def optimizer_state_dict(self, which):
+        """The state of `which` network's Adam in the format torch.optim.Adam(module.parameters()).state_dict() has: 12 entries in
+        named_parameters() order (the plain order), each {step, exp_avg, exp_avg_sq} (copies, shaped like the parameter; step is
+        opt_counters' applied-step count), and one parameter group holding the last adam_step's lr, betas and eps for that network
+        (the reference agent's before the first call). Before the first applied step the state is empty, as a fresh optimiser's
+        is. A stock optimiser's load_state_dict and the reference's save() take it as it is. Synchronises (it reads the
+        counter)."""
+        net, k = self._net(which)
+        lr, betas, eps = self._hyper
+        group = torch.optim.Adam([torch.nn.Parameter(torch.zeros(()))], lr=ops.ppo_pair(lr, "lr")[k], betas=(float(betas[0]), float(betas[1])),
+                                 eps=ops.ppo_pair(eps, "eps")[k]).state_dict()["param_groups"][0]
+        group["params"] = list(range(len(net.params)))
+        step, state = int(self.opt_counters[k]), {}
+        if step > 0:
+            for i, (p, (_, o, _)) in enumerate(zip(net.params, net.offsets)):
+                state[i] = dict(step=torch.tensor(float(step)), exp_avg=net.exp_avg[o:o + p.numel()].view(p.shape).clone(),
+                                exp_avg_sq=net.exp_avg_sq[o:o + p.numel()].view(p.shape).clone())
+        return dict(state=state, param_groups=[group])
+
+    @torch.no_grad()
+    def load_optimizer_state_dict(self, which, state_dict):
+        """Takes what torch.optim.Adam(module.parameters()).state_dict() (or optimizer_state_dict) gave for `which` network, e.g.
+        out of a checkpoint the reference's save() wrote: the moments into exp_avg and exp_avg_sq, the step into opt_counters (the
+        skip counts stay). An empty state resets moments and step to 0. The group's lr, betas and eps are NOT taken: they are
+        adam_step's arguments. amsgrad, maximize and a weight decay are refused: adam_step is plain Adam."""
+        net, k = self._net(which)
+        groups, state = state_dict["param_groups"], state_dict["state"]
+        if len(groups) != 1 or len(groups[0]["params"]) != len(net.params):
+            raise ValueError("%s: expected one parameter group of %d parameters (torch.optim.Adam(module.parameters()))" % (NAME, len(net.params)))
+        g = groups[0]
+        if g.get("amsgrad") or g.get("maximize") or g.get("weight_decay", 0) != 0:
+            raise ValueError("%s: amsgrad, maximize and weight_decay are not what adam_step computes" % NAME)
+        if not state:
+            net.exp_avg.zero_()
+            net.exp_avg_sq.zero_()
+            self.opt_counters[k] = 0
+            return
+        keys = list(g["params"])
+        if set(state) != set(keys):
+            raise ValueError("%s: the state must hold all %d parameters or none" % (NAME, len(keys)))
+        steps = {int(state[key]["step"]) for key in keys}
+        if len(steps) != 1 or min(steps) < 0:
+            raise ValueError("%s: the parameters' step counts differ or are negative: %s" % (NAME, sorted(steps)))
+        for key, p in zip(keys, net.params):
+            for name in ("exp_avg", "exp_avg_sq"):
+                if tuple(state[key][name].shape) != tuple(p.shape):
+                    raise ValueError("%s: %s of parameter %s has shape %s, the parameter %s" % (NAME, name, key, tuple(state[key][name].shape), tuple(p.shape)))
+        for key, p, (_, o, _) in zip(keys, net.params, net.offsets):
+            net.exp_avg[o:o + p.numel()].copy_(state[key]["exp_avg"].reshape(-1))
+            net.exp_avg_sq[o:o + p.numel()].copy_(state[key]["exp_avg_sq"].reshape(-1))
+        self.opt_counters[k] = steps.pop()

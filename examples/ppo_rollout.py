@@ -2,7 +2,7 @@
 """Collect a PPO rollout (BASELINE config 4: 65,536 envs x 128 steps) entirely on the GPU.
 
     python examples/ppo_rollout.py [--envs 65536] [--steps 128] [--policy torch|device-f32|device-bf16|transformer|transformer-bf16]
-                                   [--learner torch|device]
+                                   [--learner torch|device] [--optimizer torch|device]
 
 The policy is any torch module mapping float32 (N,16) observations to action probabilities (N,4) -- or
 (probs, value); here a small MLP. Everything between the policy's outputs and its next inputs (masked sampling,
@@ -17,7 +17,9 @@ tokens, d_model 64, 4 heads, 2 layers) and runs its forward pass as one HIP laun
 --learner device swaps the MLP for the reference's own actor and critic (fc1..fc4, bn1, bn2) and runs PPOAgent.update() with the
 reference's hyper-parameters (batch 256, 8 epochs, clip 0.3, Adam 8e-4 / 2e-3): the advantages block and every epoch's
 training-mode forwards, loss and gradients are g2048.DevicePPOLearner's HIP launches, clip_grad_norm_(0.5) and stock
-torch.optim.Adam run on views of its buffers. Dropout is left out, as everywhere in this library."""
+torch.optim.Adam run on views of its buffers. --optimizer device (with --learner device) makes the epoch loop one learner.update()
+call: the NaN check on the loss, the clipping and both Adam steps are two more launches an epoch, and nothing is read on the host
+until the loss is printed. Dropout is left out, as everywhere in this library."""
 import argparse
 import os
 import sys
@@ -37,7 +39,11 @@ ap.add_argument("--epochs", type=int, default=4)
 ap.add_argument("--policy", choices=("torch", "device-f32", "device-bf16", "transformer", "transformer-bf16"), default="torch")
 ap.add_argument("--dim-ff", type=int, default=128, help="feed-forward width of the transformer (the reference's default is 2048)")
 ap.add_argument("--learner", choices=("torch", "device"), default="torch")
+ap.add_argument("--optimizer", choices=("torch", "device"), default="torch",
+                help="with --learner device: stock clip_grad_norm_ + Adam on the views, or the learner's own update()")
 a = ap.parse_args()
+if a.optimizer == "device" and a.learner != "device":
+    ap.error("--optimizer device needs --learner device")
 if a.learner == "device" and a.policy.startswith("transformer"):
     ap.error("--learner device trains the reference's MLP actor and critic; use --policy torch, device-f32 or device-bf16")
 
@@ -121,15 +127,20 @@ def device_update():
     """PPOAgent.update() (agents/ppo_agent.py:336-420) with its own settings; everything that needs the networks is a HIP launch."""
     learner = g2048.DevicePPOLearner(net.actor, net.critic, clip_epsilon=0.3, value_coef=0.4, entropy_coef=0.05)
     learner.attach_params()
-    learner.attach_grads()
-    opts = [torch.optim.Adam(net.actor.parameters(), lr=8e-4), torch.optim.Adam(net.critic.parameters(), lr=2e-3)]
     mb = rc.sample(256)
-    returns, adv = learner.advantages(mb["states"], mb["next_states"], mb["rewards"], mb["dones"], gamma=0.995)
-    for epoch in range(8):
-        losses = learner.loss_and_grad(mb["states"], mb["actions"], mb["old_log_probs"], adv, returns)
-        for module, opt in zip((net.actor, net.critic), opts):        # the reference's NaN check would synchronise; left to the caller
-            torch.nn.utils.clip_grad_norm_(module.parameters(), 0.5)
-            opt.step()
+    if a.optimizer == "device":         # the whole of update() in one call: the NaN check, clipping and Adam are launches too
+        all_losses, norms = learner.update(mb["states"], mb["actions"], mb["old_log_probs"], mb["rewards"], mb["next_states"], mb["dones"],
+                                           epochs=8, gamma=0.995, lr=(8e-4, 2e-3), max_norm=0.5)
+        losses = all_losses[-1]
+    else:
+        learner.attach_grads()          # stock clipping and stock Adam read .grad: views of the learner's gradient buffers
+        opts = [torch.optim.Adam(net.actor.parameters(), lr=8e-4), torch.optim.Adam(net.critic.parameters(), lr=2e-3)]
+        returns, adv = learner.advantages(mb["states"], mb["next_states"], mb["rewards"], mb["dones"], gamma=0.995)
+        for epoch in range(8):
+            losses = learner.loss_and_grad(mb["states"], mb["actions"], mb["old_log_probs"], adv, returns)
+            for module, opt in zip((net.actor, net.critic), opts):        # the reference's NaN check would synchronise; left to the caller
+                torch.nn.utils.clip_grad_norm_(module.parameters(), 0.5)
+                opt.step()
     if policy is not net:
         policy.refresh()    # the modules are in eval mode and ARE the learner's buffers: re-fold, re-pack, replay
         rc.collect()
@@ -137,6 +148,11 @@ def device_update():
     loss, actor_loss, value_loss, entropy = losses.tolist()
     print("device update on 256 sampled transitions (of %d): loss %.4f (actor %.4f, value %.4f, entropy %.4f) after 8 epochs"
           % (a.envs * a.steps, loss, actor_loss, value_loss, entropy))
+    if a.optimizer == "device":
+        applied_actor, applied_critic, nan_loss, bad_norm = learner.opt_counters.tolist()
+        print("device optimizer: %d / %d Adam steps applied (actor / critic), %d epochs skipped for a NaN loss, %d for a gradient norm "
+              "that is not finite; last gradient norms before clipping %.4g / %.4g"
+              % (applied_actor, applied_critic, nan_loss, bad_norm, float(norms[-1, 0]), float(norms[-1, 1])))
 
 
 if a.learner == "device":

@@ -55,7 +55,7 @@ extern "C" {
                                       _update_priorities / _update_workspace, g2048_dqn_shape_rewards, g2048_qnet_forward_batch,
                                       g2048_qnet_batch_workspace, g2048_dqn_targets, g2048_qnet_loss_grad / _grad_workspace,
                                       g2048_qnet_adamw_step / _step_workspace, g2048_ppo_train_workspace / _forward_train /
-                                      _advantages / _loss_grad)
+                                      _advantages / _loss_grad, g2048_ppo_adam_step / _step_workspace)
                                       4: round 5 (export table = this header + g2048_testing.h exactly: test / measurement hooks moved there,
                                       internal symbols hidden; g2048_replay_games also clamps a game's length to actions_stride)
                                       3: round 4 (actions_out of the g2048_play_games family, g2048_replay_games, g2048_env_step,
@@ -914,6 +914,53 @@ G2048_API int g2048_ppo_loss_grad(const float *states, const int64_t *actions, c
                         const float *returns, const float *plain_actor, const float *plain_critic, float *running_actor_or_null,
                         float *running_critic_or_null, float clip_epsilon, float value_coef, float entropy_coef, size_t n,
                         float *grad_actor_out, float *grad_critic_out, float *loss_out, void *workspace, void *stream);
+
+/* ---- the PPO update's loss gate, gradient clipping and Adam step (agents/ppo_agent.py:403-416) ------------------------------
+ * What an epoch of PPOAgent.update() does after backward(), for the actor and the critic TOGETHER: `if torch.isnan(loss):
+ * continue`, clip_grad_norm_(parameters, max_norm) on each network and torch.optim.Adam.step() on each network. The parameters
+ * are the two PLAIN f32 buffers (layout above: 46532 floats for the actor, 46337 for the critic), the gradients the buffers
+ * g2048_ppo_loss_grad fills, the moment estimates two more buffers per network of the same layout that start as zeros. All eight
+ * are 16-byte aligned; the critic's count is 1 mod 4, so its buffers end in a 16-byte group of one float.
+ * `counters` is four int64 on the device, 8-byte aligned, that start as zeros and belong to the pair of networks:
+ *     {actor steps applied, critic steps applied, calls skipped for a NaN loss, calls skipped for a gradient norm that is not finite}
+ *
+ *   g2048_ppo_adam_step   two launches on `stream`, no host synchronisation and no host decision:
+ *       1. prepare: ONE block of 1,024 threads. Each network's gradient norm: thread t adds grad[i]^2 over the 16-byte groups t,
+ *          t + 1,024, .. in order, then the wavefront's butterfly and the sixteen wavefronts' sums pairwise, all in f64, in an order
+ *          that depends on the float count alone; norms_out = {(float)sqrt(actor's sum), (float)sqrt(critic's sum)}, written on
+ *          EVERY call, a skipped one included. Then one thread decides. The call is SKIPPED if
+ *            - loss_or_null is given and loss_or_null[0] is a NaN (the reference's rule, isnan only: a +inf loss over finite
+ *              gradients is applied; loss_or_null[1..] is never read): counters[2] += 1; or else
+ *            - EITHER network's norm is not finite (an inf or a NaN in a gradient; stock torch would write NaN into every weight
+ *              of that network, and an update that reaches one network and not the other is of no use): counters[3] += 1.
+ *          A skipped call writes nothing else: all eight buffers keep their bits and counters[0], counters[1] stay. Otherwise
+ *          counters[0] and counters[1] go up by one, and for each network, with t = its counter's new value, the thread forms in
+ *          f64 bc1 = 1 - beta1^t and bc2 = 1 - beta2^t, and passes on lr / bc1, sqrt(bc2) (rounded to f32) and the clip coefficient
+ *          c = min(1, max_norm / (norm + 1e-6)), evaluated as torch evaluates it in f32: the reciprocal of norm + 1e-6, times
+ *          max_norm; max_norm = +inf: no clipping. The step number lives on the device because the host never learns of a skipped
+ *          call, and a skipped call must not advance the bias correction (the reference's `continue` does not reach
+ *          optimizer.step()); this is the difference from g2048_qnet_adamw_step, whose caller counts.
+ *       2. update: one grid over both networks; every block reads those scalars and returns at once on a skip. Otherwise, for
+ *          every element, with its network's own lr, eps and c:
+ *              g = grad[i] * c;  grad[i] = g                      (grad is left clipped, as clip_grad_norm_ leaves it)
+ *              m = m + (g - m) * (1 - beta1)
+ *              v = v * beta2 + (g * g) * (1 - beta2)
+ *              p = p - (lr / bc1) * (m / (sqrt(v) / sqrt(bc2) + eps))
+ *          every operation rounded to f32 on its own, in the order of torch's single-tensor Adam (g2048_qnet_adamw_step's lines
+ *          without weight decay). 1 - beta1 and 1 - beta2 are formed on the host in f64 from the shortest decimal that rounds to
+ *          the float given, as there.
+ *       No atomics, no block waits on another; the counters are read and written by the one block of the first launch alone. Two
+ *       calls from the same state give the same bits. Nothing outside the eight buffers, the counters, norms_out[0..1] and the
+ *       workspace is written.
+ *   g2048_ppo_step_workspace   bytes of `workspace` (device memory, 16-byte aligned, contents irrelevant before and meaningless
+ *       after): the prepared scalars.
+ * Arguments are checked before any device call: a null pointer (other than loss_or_null) or a misaligned one, an lr, beta or eps
+ * that is negative or not finite, a beta >= 1, max_norm NaN or <= 0 return G2048_ERR_ARG. */
+G2048_API size_t g2048_ppo_step_workspace(void);
+G2048_API int g2048_ppo_adam_step(float *plain_actor, float *grad_actor, float *exp_avg_actor, float *exp_avg_sq_actor,
+                        float *plain_critic, float *grad_critic, float *exp_avg_critic, float *exp_avg_sq_critic,
+                        const float *loss_or_null, int64_t *counters, float lr_actor, float lr_critic, float beta1, float beta2,
+                        float eps_actor, float eps_critic, float max_norm, float *norms_out, void *workspace, void *stream);
 #ifdef __cplusplus
 }
 #endif

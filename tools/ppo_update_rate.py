@@ -1,8 +1,9 @@
-"""DevicePPOLearner (the gradient half of PPOAgent.update, agents/ppo_agent.py:357-400) against stock torch on the same GPU.
+"""DevicePPOLearner (PPOAgent.update, agents/ppo_agent.py:357-416) against stock torch on the same GPU.
 
     python3 tools/ppo_update_rate.py                      the table
     python3 tools/ppo_update_rate.py --trace N [CALLS]    only CALLS (50) loss_and_grad calls at n = N, for a kernel trace:
         rocprofv3 --kernel-trace --stats --output-format csv -d OUT -- python3 tools/ppo_update_rate.py --trace 256
+    python3 tools/ppo_update_rate.py --trace-step [CALLS] only CALLS (50) adam_step calls after one loss_and_grad, for a kernel trace
 
 The reference's actor and critic (16-256-128-64-{4|1}, BatchNorm1d after the first two ReLUs, torch's default init) in training
 mode with dropout p = 0 on BOTH sides, at n = 256 (the reference's batch) and 4,096 (the limit). Versions, alternating within
@@ -13,16 +14,23 @@ every round:
   torch update          the whole update(): the no-gradient block (two critic forwards, returns, normalised advantages), then 8
                         epochs of the above with clip_grad_norm_(0.5) per network and two torch.optim.Adam steps;
   device update         the same with learner.advantages and learner.loss_and_grad, the clipping and the SAME stock Adam running on
-                        the attached views.
-The reference's `if torch.isnan(loss): continue` is left out on both sides (it is a host synchronisation per epoch).
-A round times REPS back-to-back calls of a version between one event pair and divides; median of 7 rounds after 2 warm-up rounds,
-min - max in brackets. Before timing, the device gradients and stock torch's float32 ones are both compared with the modules'
-float64 autograd on the same GPU, per tensor as max|g - g64| / max|g64|.
-Output: one text table (profiles/r23_ppo_update_rate.txt keeps a run)."""
+                        the attached views;
+  stock tail            what ends an epoch of "device update": clip_grad_norm_(0.5) per network and two stock Adam steps on the
+                        attached views (the gradients are those of one loss_and_grad call);
+  device adam_step      the same in two launches, learner.adam_step(losses), the NaN gate included;
+  device update()       learner.update(): "device update" with adam_step for the stock tail, on a learner of its own.
+The reference's `if torch.isnan(loss): continue` is left out of the stock versions (it is a host synchronisation per epoch);
+adam_step decides it on the device.
+A round times REPS back-to-back calls of a version between one event pair and divides (the device clock), and takes the host's
+perf_counter around the same calls before it waits for the device (the host-enqueue clock); median of 7 rounds after 2 warm-up
+rounds, min - max of the device clock in brackets. Before timing, the device gradients and stock torch's float32 ones are both
+compared with the modules' float64 autograd on the same GPU, per tensor as max|g - g64| / max|g64|.
+Output: one text table (profiles/r23_ppo_update_rate.txt and profiles/r25_ppo_step_rate.txt keep runs)."""
 import copy
 import os
 import statistics
 import sys
+import time
 
 import torch
 import torch.nn as nn
@@ -59,17 +67,21 @@ class Net(nn.Module):                   # the reference's structure and forward,
 
 
 def event_time(fn):
+    """(device seconds, host-enqueue seconds) per call."""
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
     e0.record()
     for _ in range(REPS):
         fn()
     e1.record()
+    host = time.perf_counter() - t0
     torch.cuda.synchronize()
-    return e0.elapsed_time(e1) * 1e-3 / REPS
+    return e0.elapsed_time(e1) * 1e-3 / REPS, host / REPS
 
 
 def alternate(versions, warmup, rounds):
-    """{name: [seconds per call and round]}: every round runs each version, in order."""
+    """{name: [(device seconds, host-enqueue seconds) per call and round]}: every round runs each version, in order."""
     times = {name: [] for name, _ in versions}
     for r in range(warmup + rounds):
         for name, fn in versions:
@@ -117,6 +129,12 @@ def device_update(learner, actor, critic, opts, x, nx, actions, old, rewards, do
             opt.step()
 
 
+def stock_tail(actor, critic, opts):
+    for net, opt in zip((actor, critic), opts):
+        nn.utils.clip_grad_norm_(net.parameters(), MAX_NORM)
+        opt.step()
+
+
 def inputs(actor64, critic64, n):
     x = ops.synth_boards(n, seed=3, device=dev).float() / 15.0          # PPOAgent.normalize_state
     nx = ops.synth_boards(n, seed=4, device=dev).float() / 15.0
@@ -149,10 +167,23 @@ if sys.argv[1:2] == ["--trace"]:
     print("%d loss_and_grad calls at n = %d" % (calls, n))
     sys.exit(0)
 
+if sys.argv[1:2] == ["--trace-step"]:
+    calls = int(sys.argv[2]) if len(sys.argv) > 2 else 50
+    actor, critic = fresh()
+    x, nx, actions, old, adv, ret, rewards, dones = inputs(copy.deepcopy(actor).double(), copy.deepcopy(critic).double(), 256)
+    learner = DevicePPOLearner(actor, critic, CLIP, VALUE_COEF, ENTROPY_COEF)
+    learner.attach_params()
+    losses = learner.loss_and_grad(x, actions, old, adv, ret)
+    for _ in range(calls):
+        learner.adam_step(losses, lr=LR, max_norm=MAX_NORM)
+    torch.cuda.synchronize()
+    print("%d adam_step calls; counters %s" % (calls, learner.opt_counters.tolist()))
+    sys.exit(0)
+
 print("# %d calls per event pair; median of 7 rounds after 2 warm-up rounds, the versions alternating; an update is the advantages "
       "block + %d epochs with clip_grad_norm_(%.1f) and stock torch.optim.Adam" % (REPS, EPOCHS, MAX_NORM))
 print("# workspace of the device pass: %s" % ", ".join("n = %d: %.1f MB" % (n, ops.ppo_train_workspace_bytes(n) / 1e6) for n in (256, 4096)))
-print("%-7s %-22s %10s %22s %12s %10s" % ("rows", "version", "us", "[min - max] us", "rows/s", "vs torch"))
+print("%-7s %-22s %10s %22s %10s %12s %10s" % ("rows", "version", "us", "[min - max] us", "host us", "rows/s", "vs"))
 for n in (256, 4096):
     actor, critic = fresh()                                             # stock torch's
     d_actor, d_critic = copy.deepcopy(actor), copy.deepcopy(critic)     # the device learner's
@@ -177,9 +208,35 @@ for n in (256, 4096):
                 ("device loss_and_grad", lambda: learner.loss_and_grad(x, actions, old, adv, ret)),
                 ("torch update", lambda: torch_update(actor, critic, opts, x, nx, actions, old, rewards, dones)),
                 ("device update", lambda: device_update(learner, d_actor, d_critic, d_opts, x, nx, actions, old, rewards, dones))]
+    # the optimiser tail: a second attached learner for the stock tail (its gradients stay those of one call), a third for adam_step,
+    # a fourth for update(), so that no version steps another's weights
+    def attached():
+        mods = copy.deepcopy(actor), copy.deepcopy(critic)
+        le = DevicePPOLearner(*mods, CLIP, VALUE_COEF, ENTROPY_COEF)
+        le.attach_params()
+        le.attach_grads()
+        return le, mods
+    tail, tail_mods = attached()
+    tail.loss_and_grad(x, actions, old, adv, ret)
+    tail_opts = [torch.optim.Adam(net.parameters(), lr=LR) for net in tail_mods]
+    stepper, _ = attached()
+    step_losses = stepper.loss_and_grad(x, actions, old, adv, ret)
+    whole, _ = attached()
+    versions += [("stock tail", lambda: stock_tail(*tail_mods, tail_opts)),
+                 ("device adam_step", lambda: stepper.adam_step(step_losses, lr=LR, max_norm=MAX_NORM)),
+                 ("device update()", lambda: whole.update(x, actions, old, rewards, nx, dones, epochs=EPOCHS, gamma=GAMMA, lr=LR, max_norm=MAX_NORM))]
     times = alternate(versions, 2, 7)
+    against = {"torch update": "torch update", "device update": "torch update", "device update()": "device update",
+               "stock tail": "stock tail", "device adam_step": "stock tail"}
     for name, _ in versions:
-        tt = times[name]
+        tt, hh = [t for t, _ in times[name]], [h for _, h in times[name]]
         med = statistics.median(tt)
-        base = statistics.median(times["torch update" if name.endswith("update") else "torch fwd+loss+bwd"])
-        print("%-7d %-22s %10.1f %22s %12.4g %9.2fx" % (n, name, med * 1e6, "[%.1f - %.1f]" % (min(tt) * 1e6, max(tt) * 1e6), n / med, base / med))
+        other = against.get(name, "torch fwd+loss+bwd")
+        base = statistics.median([t for t, _ in times[other]])
+        print("%-7d %-22s %10.1f %22s %10.1f %12.4g %9.2fx %s" % (n, name, med * 1e6, "[%.1f - %.1f]" % (min(tt) * 1e6, max(tt) * 1e6),
+                                                                 statistics.median(hh) * 1e6, n / med, base / med, other))
+    print("# n = %d: optimiser counters of the adam_step learner %s, of the update() learner %s"
+          % (n, stepper.opt_counters.tolist(), whole.opt_counters.tolist()))
+    med = lambda name, k: statistics.median([t[k] for t in times[name]])      # noqa: E731
+    assert med("device adam_step", 0) < med("stock tail", 0) and med("device adam_step", 1) < med("stock tail", 1), "adam_step is not faster than the stock tail"
+    assert med("device update()", 0) < med("device update", 0), "update() is not faster than the stock-tail update"
