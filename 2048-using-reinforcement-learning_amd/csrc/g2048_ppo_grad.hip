@@ -3,7 +3,8 @@
 // its running statistics moving by momentum 0.1), the returns / advantages block, the clipped-surrogate + value + entropy loss
 // and the backward pass through both networks, the gradients written in the networks' plain parameter layout (include/g2048.h),
 // where a stock torch optimiser reads them through views. C-ABI: g2048_ppo_train_workspace / g2048_ppo_forward_train /
-// g2048_ppo_advantages / g2048_ppo_loss_grad. The reference's live dropout is left out, as everywhere in this library. f32 only.
+// g2048_ppo_advantages / g2048_ppo_loss_grad, and with the reference's live dropout (nn.Dropout after each BatchNorm)
+// g2048_ppo_forward_train_dropout / g2048_ppo_loss_grad_dropout / g2048_ppo_dropout_mask. f32 only.
 //
 // One phase per launch, per network:
 //   fc1       relu(x W^T + b) for K = 16: one chunk of the f32 matrix cores' product, one wavefront a 16-row x 16-feature tile
@@ -16,21 +17,28 @@
 //   bn_bwd    dgamma = sum dy xhat, dbeta = sum dy, dx = gamma rstd (dy - dbeta / n - xhat dgamma / n) x the ReLU mask below it,
 //             the sums as in bn
 //   loss      one block's fixed-order sums of the rows' terms
-// n == 1: the reference skips both BatchNorms; so does this (their gradients are written as 0, the running statistics stay).
+//   dropout   (p > 0 only) the bn launch multiplies its output by m, the bn_bwd launch the incoming dy, m = 1 / (1 - p) or 0 from
+//             one draw of the counter RNG per element (drop_mult): the backward regenerates it, no mask is stored. With p == 0
+//             the kernels launched are the instantiations without it (pg_bn_kernel<> / pg_bn_bwd_kernel<>), whose code is unchanged.
+// n == 1: the reference skips both BatchNorms; so does this (their gradients are written as 0, the running statistics stay). It
+// does not skip the dropout: with p > 0 one elementwise launch each way (pg_drop_kernel / pg_drop_bwd_kernel) applies m.
 // No atomics, no split-K across blocks, no block waits on another; every output element is one fixed-order accumulation, so two
 // calls give the same bits; nothing past row n or past the stated sizes is read or written, and no row past n of the workspace
 // is relied on. The gradient buffers are overwritten, never accumulated into. Compile with -ffp-contract=off.
 // A NaN or an infinity in an input shows in the loss parts and the gradients as it does in stock torch: every ReLU, clamp and
-// minimum of this pass is a comparison that passes a NaN on (relu_nan, clamp_nan, min_nan), not fmaxf / fminf, which drop it.
+// minimum of this pass is a comparison that passes a NaN on (relu_nan, clamp_nan, min_nan), not fmaxf / fminf, which drop it, and
+// a ReLU's backward is torch's threshold_backward, zero where the output is <= 0: where the output is a NaN the gradient passes.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 
 #include "../../include/g2048.h"
+#include "g2048_board.h"             // rng_draw_lo, the per-element draw
 #include "g2048_grad_products.h"
 #include "g2048_host.h"
 #include "g2048_mfma.h"
 #include "g2048_qnet_batch_fwd.h"
+#include "g2048_rng.h"
 
 namespace {
 
@@ -79,6 +87,51 @@ __global__ __launch_bounds__(256) void pg_fc1_kernel(const float *__restrict__ X
     if (live) *reinterpret_cast<f4 *>(Y + (size_t)row * kH1 + 16 * o + 4 * g) = relu_nan(acc);
 }
 
+// ---------------------------------------------------------------------------------------------------------- dropout --
+// One dropout site of one launch (DESIGN.md "RNG", domain kDomDropout): element (row, feature) of site s (0 after bn1, 1 after bn2)
+// of network w (0 actor, 1 critic) in the library call with index c draws h = rng_draw(k0, k1, ((2 w + s) << 32) | (row F + feature), 0),
+// (k0, k1) = rng_keys(seed, kDomDropout, c), and is kept iff h >= T = floor(p 2^32). The id's high word is the launch's, so it is
+// folded into k1h on the host and the lane hashes 32 bits (rng_draw_lo).
+struct Drop {
+    uint32_t k0, k1h, T;
+    float scale;           // (float)(1 / (1 - p))
+};
+
+__device__ inline bool drop_keep(const Drop &d, uint32_t idx) { return rng_draw_lo(d.k0, d.k1h, idx, 0) >= d.T; }
+// the multiplier: a product, not a select, so that a NaN or an infinity in a dropped position becomes NaN as in torch
+__device__ inline float drop_mult(const Drop &d, uint32_t idx) { return drop_keep(d, idx) ? d.scale : 0.0f; }
+
+inline Drop drop_site(uint64_t seed, uint64_t call_index, int net, int site, double p)
+{
+    const Keys k = rng_keys(seed, kDomDropout, call_index);
+    return Drop{k.k0, k.k1 + rng_hi_term((uint64_t)(2 * net + site) << 32), (uint32_t)std::floor(p * 4294967296.0), (float)(1.0 / (1.0 - p))};
+}
+
+inline bool good_drop(double p) { return p >= 0.0 && p < 1.0; }      // a NaN fails both
+
+// keep[i] = the keep bit of element i of a site, i < count
+__global__ __launch_bounds__(256) void pg_drop_mask_kernel(uint8_t *__restrict__ keep, Drop drop, uint32_t count)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i < count) keep[i] = drop_keep(drop, i) ? 1 : 0;
+}
+
+// n == 1, where no BatchNorm launch carries the dropout: Y = X m over count elements of a site
+__global__ __launch_bounds__(256) void pg_drop_kernel(const float *__restrict__ X, float *__restrict__ Y, Drop drop, uint32_t count)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i < count) Y[i] = X[i] * drop_mult(drop, i);
+}
+
+// its backward, in place: D = d loss / d Y leaves as d loss / d H, X = relu(H) (zero where X <= 0)
+__global__ __launch_bounds__(256) void pg_drop_bwd_kernel(float *__restrict__ D, const float *__restrict__ X, Drop drop, uint32_t count)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= count) return;
+    const float v = D[i] * drop_mult(drop, i);
+    D[i] = X[i] <= 0.0f ? 0.0f : v;
+}
+
 // -------------------------------------------------------------------------------------------------------- BatchNorm --
 // A block of 1,024 = 32 features x 32 row groups; thread (group, feature) owns the rows group, group + 32, ..: partial sum u of eight
 // takes every eighth of them (eight independent loads in flight), the eight are combined pairwise, then the 32 groups pairwise
@@ -115,9 +168,11 @@ __device__ inline float bn_block_sum(const float (&a)[kBnParts], float (&red)[kB
 
 // Y = (X - mean) rstd gamma + beta over the n rows of X [n][F] (n >= 2), mean and the biased variance of the batch; stat: mean [F],
 // rstd [F] kept for the backward. running (optional): mean [F], var [F], moved by momentum 0.1 towards the batch mean and the
-// UNBIASED variance, as torch's training-mode BatchNorm1d moves them. grid F / 32.
+// UNBIASED variance, as torch's training-mode BatchNorm1d moves them. grid F / 32. With a Drop, Y is multiplied by the site's m.
+template <class... MaybeDrop>
 __global__ __launch_bounds__(1024) void pg_bn_kernel(const float *__restrict__ X, int F, const float *__restrict__ gamma, const float *__restrict__ beta,
-                                                      float *__restrict__ Y, float *__restrict__ stat, float *__restrict__ running, int n)
+                                                      float *__restrict__ Y, float *__restrict__ stat, float *__restrict__ running, int n,
+                                                      MaybeDrop... drop)
 {
     __shared__ float red[kBnGroups][32];
     const int f = threadIdx.x & 31, grp = threadIdx.x >> 5, feat = (int)blockIdx.x * 32 + f;
@@ -135,7 +190,11 @@ __global__ __launch_bounds__(1024) void pg_bn_kernel(const float *__restrict__ X
     });
     const float ss = bn_block_sum(a, red, grp, f);
     const float rstd = 1.0f / sqrtf(ss / (float)n + kBnEps), ga = gamma[feat], be = beta[feat];
-    for (int i = grp; i < n; i += kBnGroups) Y[(size_t)i * F + feat] = (x[(size_t)i * F] - mean) * rstd * ga + be;
+    for (int i = grp; i < n; i += kBnGroups) {
+        float y = (x[(size_t)i * F] - mean) * rstd * ga + be;
+        if constexpr (sizeof...(MaybeDrop) != 0) y *= drop_mult(drop..., (uint32_t)(i * F + feat));
+        Y[(size_t)i * F + feat] = y;
+    }
     if (grp == 0) {
         stat[feat] = mean;
         stat[F + feat] = rstd;
@@ -147,9 +206,12 @@ __global__ __launch_bounds__(1024) void pg_bn_kernel(const float *__restrict__ X
 }
 
 // The backward of pg_bn_kernel, in place: D [n][F] holds d loss / d Y and leaves as d loss / d H, where X = relu(H) is the
-// BatchNorm's input (zero where X <= 0). dgamma [F] = sum dy xhat, dbeta [F] = sum dy with xhat = (X - mean) rstd from stat.
+// BatchNorm's input (zero where X <= 0; a NaN X passes the gradient, as torch's ReLU backward does). dgamma [F] = sum dy xhat, dbeta [F] = sum dy with xhat = (X - mean) rstd from stat.
+// With a Drop, D holds d loss / d (Y m), the dropped output: every dy is first multiplied by the regenerated m.
+template <class... MaybeDrop>
 __global__ __launch_bounds__(1024) void pg_bn_bwd_kernel(float *__restrict__ D, const float *__restrict__ X, int F, const float *__restrict__ gamma,
-                                                          const float *__restrict__ stat, float *__restrict__ dgamma, float *__restrict__ dbeta, int n)
+                                                          const float *__restrict__ stat, float *__restrict__ dgamma, float *__restrict__ dbeta, int n,
+                                                          MaybeDrop... drop)
 {
     __shared__ float red[kBnGroups][32];
     const int f = threadIdx.x & 31, grp = threadIdx.x >> 5, feat = (int)blockIdx.x * 32 + f;
@@ -160,7 +222,8 @@ __global__ __launch_bounds__(1024) void pg_bn_bwd_kernel(float *__restrict__ D, 
 #pragma unroll
     for (int u = 0; u < kBnParts; ++u) a[u] = b[u] = 0.0f;
     bn_rows(grp, n, [&](int u, int row) {
-        const float dy = d[(size_t)row * F];
+        float dy = d[(size_t)row * F];
+        if constexpr (sizeof...(MaybeDrop) != 0) dy *= drop_mult(drop..., (uint32_t)(row * F + feat));
         a[u] += dy;
         b[u] += dy * ((x[(size_t)row * F] - mean) * rstd);
     });
@@ -168,8 +231,10 @@ __global__ __launch_bounds__(1024) void pg_bn_bwd_kernel(float *__restrict__ D, 
     const float scale = gamma[feat] * rstd, mb = db / (float)n, mg = dg / (float)n;
     for (int i = grp; i < n; i += kBnGroups) {
         const float xv = x[(size_t)i * F];
-        const float v = scale * (d[(size_t)i * F] - mb - (xv - mean) * rstd * mg);
-        d[(size_t)i * F] = xv > 0.0f ? v : 0.0f;
+        float dy = d[(size_t)i * F];
+        if constexpr (sizeof...(MaybeDrop) != 0) dy *= drop_mult(drop..., (uint32_t)(i * F + feat));
+        const float v = scale * (dy - mb - (xv - mean) * rstd * mg);
+        d[(size_t)i * F] = xv <= 0.0f ? 0.0f : v;
     }
     if (grp == 0) {
         dgamma[feat] = dg;
@@ -198,7 +263,7 @@ __device__ inline void fc4_row(const float *__restrict__ h, const float *__restr
     }
 }
 
-// d3[k] = (sum_j dz[j] fc4.weight[j][k]) where h[k] > 0, else 0
+// d3[k] = 0 where h[k] <= 0, else sum_j dz[j] fc4.weight[j][k] (a NaN h[k] passes it, as torch's ReLU backward does)
 template <int O>
 __device__ inline void fc4_row_dx(const float (&dz)[O], const float *__restrict__ W, const float (&hv)[kH3], float *__restrict__ d3)
 {
@@ -210,7 +275,7 @@ __device__ inline void fc4_row_dx(const float (&dz)[O], const float *__restrict_
             float s = dz[0] * W[k + u];
 #pragma unroll
             for (int j = 1; j < O; ++j) s = fmaf(dz[j], W[j * kH3 + k + u], s);
-            v[u] = hv[k + u] > 0.0f ? s : 0.0f;
+            v[u] = hv[k + u] <= 0.0f ? 0.0f : s;
         }
         *reinterpret_cast<f4 *>(d3 + k) = v;
     }
@@ -391,38 +456,54 @@ struct Net {
     float *G;              // gradient buffer, or null (forward only)
     float *ws;             // this network's workspace
     int n_out;
+    bool dropout;          // p > 0: drop[s] is site s's
+    Drop drop[2];
 };
 
-// the training-mode forward up to relu(fc3 ..), the activations kept in net.ws; returns where BN1's and BN2's outputs lie
+// what the dropout entry points add to a network: p, and with p > 0 the two sites' launch scalars
+Net with_dropout(Net net, uint64_t seed, uint64_t call_index, int w, double p)
+{
+    net.dropout = p > 0.0;
+    if (net.dropout)
+        for (int s = 0; s < 2; ++s) net.drop[s] = drop_site(seed, call_index, w, s, p);
+    return net;
+}
+
+// the training-mode forward up to relu(fc3 ..), the activations kept in net.ws. b1 / b2 (BatchNorm's outputs, dropped where the
+// network has dropout) are what fc2 / fc3 and the backward's dW products read; without BatchNorm and dropout they are h1 / h2
 void launch_trunk(const Net &net, const float *states, int n, hipStream_t s)
 {
     const NetWorkspace w((size_t)n);
     const unsigned tiles = (unsigned)(w.np / 16);
-    const bool bn = n > 1;
-    float *h1 = net.ws + w.h1(), *b1 = bn ? net.ws + w.b1() : h1, *h2 = net.ws + w.h2(), *b2 = bn ? net.ws + w.b2() : h2, *h3 = net.ws + w.h3(),
+    const bool bn = n > 1, own = bn || net.dropout;
+    float *h1 = net.ws + w.h1(), *b1 = own ? net.ws + w.b1() : h1, *h2 = net.ws + w.h2(), *b2 = own ? net.ws + w.b2() : h2, *h3 = net.ws + w.h3(),
           *stat = net.ws + w.stat();
+    const auto norm = [&](const float *h, int F, const float *gamma, const float *beta, float *b, float *st, float *running, const Drop &drop) {
+        if (bn && net.dropout)
+            hipLaunchKernelGGL(pg_bn_kernel<Drop>, dim3(F / 32), dim3(1024), 0, s, h, F, gamma, beta, b, st, running, n, drop);
+        else if (bn)
+            hipLaunchKernelGGL(pg_bn_kernel<>, dim3(F / 32), dim3(1024), 0, s, h, F, gamma, beta, b, st, running, n);
+        else if (net.dropout)
+            hipLaunchKernelGGL(pg_drop_kernel, dim3(blocks_for((size_t)n * F, 256)), dim3(256), 0, s, h, b, drop, (uint32_t)(n * F));
+    };
     hipLaunchKernelGGL(pg_fc1_kernel, dim3(kH1 / 64, tiles), dim3(256), 0, s, states, net.P + kFc1W, net.P + kFc1B, h1, n);
-    if (bn)
-        hipLaunchKernelGGL(pg_bn_kernel, dim3(kH1 / 32), dim3(1024), 0, s, static_cast<const float *>(h1), kH1, net.P + kBn1W, net.P + kBn1B, b1, stat,
-                           net.running ? net.running + kRun1 : nullptr, n);
+    norm(h1, kH1, net.P + kBn1W, net.P + kBn1B, b1, stat, net.running ? net.running + kRun1 : nullptr, net.drop[0]);
     hipLaunchKernelGGL((qb_linear_kernel<true, true>), dim3(kH2 / 64, tiles), dim3(256), 0, s, static_cast<const float *>(b1), kH1, net.P + kFc2W,
                        net.P + kFc2B, h2, kH2, n);
-    if (bn)
-        hipLaunchKernelGGL(pg_bn_kernel, dim3(kH2 / 32), dim3(1024), 0, s, static_cast<const float *>(h2), kH2, net.P + kBn2W, net.P + kBn2B, b2,
-                           stat + 2 * kH1, net.running ? net.running + kRun2 : nullptr, n);
+    norm(h2, kH2, net.P + kBn2W, net.P + kBn2B, b2, stat + 2 * kH1, net.running ? net.running + kRun2 : nullptr, net.drop[1]);
     hipLaunchKernelGGL((qb_linear_kernel<true, true>), dim3(kH3 / 64, tiles), dim3(256), 0, s, static_cast<const float *>(b2), kH2, net.P + kFc3W,
                        net.P + kFc3B, h3, kH3, n);
 }
 
 // from dz [n][n_out] and d3 [n][64] (the head's) to every gradient of the network
-int launch_backward(const Net &net, const float *states, int n, hipStream_t s)
+int launch_backward(const Net &net, const float *states, int n, hipStream_t s, const char *entry)
 {
     const NetWorkspace w((size_t)n);
     const unsigned tiles = (unsigned)(w.np / 16);
-    const bool bn = n > 1;
+    const bool bn = n > 1, own = bn || net.dropout;
     const float *P = net.P, *none = nullptr;
     float *G = net.G;
-    const float *h1 = net.ws + w.h1(), *b1 = bn ? net.ws + w.b1() : h1, *h2 = net.ws + w.h2(), *b2 = bn ? net.ws + w.b2() : h2, *h3 = net.ws + w.h3(),
+    const float *h1 = net.ws + w.h1(), *b1 = own ? net.ws + w.b1() : h1, *h2 = net.ws + w.h2(), *b2 = own ? net.ws + w.b2() : h2, *h3 = net.ws + w.h3(),
                 *stat = net.ws + w.stat(), *dz = net.ws + w.dz();
     float *d3 = net.ws + w.d3(), *d2 = net.ws + w.d2(), *d1 = net.ws + w.d1();
     const int O = net.n_out;
@@ -432,25 +513,109 @@ int launch_backward(const Net &net, const float *states, int n, hipStream_t s)
     const auto dw = [&](const float *dY, int ldy, int M, const float *X, int K, float *dW, float *db) {
         hipLaunchKernelGGL(qg_dw_kernel, dim3((unsigned)(K + 63) / 64, (unsigned)(M + 15) / 16), dim3(256), 0, s, dY, ldy, M, X, K, dW, db, n);
     };
+    // d [n][F] = d loss / d b (the BatchNorm's, dropped, output) to d loss / d (fc's output before its ReLU), in place
+    const auto norm_bwd = [&](float *d, const float *h, int F, const float *gamma, const float *st, float *dgamma, float *dbeta, const Drop &drop) {
+        if (bn && net.dropout)
+            hipLaunchKernelGGL(pg_bn_bwd_kernel<Drop>, dim3(F / 32), dim3(1024), 0, s, d, h, F, gamma, st, dgamma, dbeta, n, drop);
+        else if (bn)
+            hipLaunchKernelGGL(pg_bn_bwd_kernel<>, dim3(F / 32), dim3(1024), 0, s, d, h, F, gamma, st, dgamma, dbeta, n);
+        else if (net.dropout)
+            hipLaunchKernelGGL(pg_drop_bwd_kernel, dim3(blocks_for((size_t)n * F, 256)), dim3(256), 0, s, d, h, drop, (uint32_t)(n * F));
+    };
     dw(dz, O, O, h3, kH3, G + kFc4W, G + kFc4W + O * kH3);
     dw(d3, kH3, kH3, b2, kH2, G + kFc3W, G + kFc3B);
-    dx(d3, kH3, P + kFc3W, kH2, bn ? none : h2, d2);
-    if (bn)
-        hipLaunchKernelGGL(pg_bn_bwd_kernel, dim3(kH2 / 32), dim3(1024), 0, s, d2, h2, kH2, P + kBn2W, stat + 2 * kH1, G + kBn2W, G + kBn2B, n);
+    dx(d3, kH3, P + kFc3W, kH2, own ? none : h2, d2);
+    norm_bwd(d2, h2, kH2, P + kBn2W, stat + 2 * kH1, G + kBn2W, G + kBn2B, net.drop[1]);
     dw(d2, kH2, kH2, b1, kH1, G + kFc2W, G + kFc2B);
-    dx(d2, kH2, P + kFc2W, kH1, bn ? none : h1, d1);
-    if (bn)
-        hipLaunchKernelGGL(pg_bn_bwd_kernel, dim3(kH1 / 32), dim3(1024), 0, s, d1, h1, kH1, P + kBn1W, stat, G + kBn1W, G + kBn1B, n);
+    dx(d2, kH2, P + kFc2W, kH1, own ? none : h1, d1);
+    norm_bwd(d1, h1, kH1, P + kBn1W, stat, G + kBn1W, G + kBn1B, net.drop[0]);
     dw(d1, kH1, kH1, states, kIn, G + kFc1W, G + kFc1B);
     if (!bn) {                                       // the reference's forward skips both BatchNorms for one row: no gradient
         hipError_t e = hipMemsetAsync(G + kBn1W, 0, 2 * kH1 * sizeof(float), s);
         if (e == hipSuccess) e = hipMemsetAsync(G + kBn2W, 0, 2 * kH2 * sizeof(float), s);
-        if (e != hipSuccess) return fail(G2048_ERR_HIP, "g2048_ppo_loss_grad: hipMemsetAsync: %s", hipGetErrorString(e));
+        if (e != hipSuccess) return fail(G2048_ERR_HIP, "%s: hipMemsetAsync: %s", entry, hipGetErrorString(e));
     }
     return G2048_OK;
 }
 
 inline bool good_coef(float v) { return v >= 0.0f && std::isfinite(v); }
+
+// g2048_ppo_forward_train and g2048_ppo_forward_train_dropout (`entry`: whose messages); the first is net 0, p 0
+int forward_train(const char *entry, const float *states, const float *plain, float *running_or_null, int n_out, int net_index, double p,
+                  uint64_t seed, uint64_t call_index, float *out, size_t n, void *workspace, void *stream)
+{
+    if (n == 0) return G2048_OK;
+    if (!states || !plain || !out || !workspace) return fail(G2048_ERR_ARG, "%s: null pointer", entry);
+    if (!aligned(states, 16) || !aligned(plain, 16) || !aligned(workspace, 16) || !aligned(running_or_null, 4) ||
+        !aligned(out, n_out == 4 ? 16 : 4))
+        return fail(G2048_ERR_ARG, "%s: misaligned pointer (states, plain weights, workspace, probabilities: 16 bytes; the rest: 4)", entry);
+    if (n_out != 4 && n_out != 1) return fail(G2048_ERR_ARG, "%s: n_out must be 4 (actor) or 1 (critic)", entry);
+    if (net_index != 0 && net_index != 1) return fail(G2048_ERR_ARG, "%s: net must be 0 (the actor's masks) or 1 (the critic's)", entry);
+    if (!good_drop(p)) return fail(G2048_ERR_ARG, "%s: the dropout probability must be finite, 0 <= p < 1", entry);
+    if (n > G2048_PPO_BATCH_MAX)
+        return fail(G2048_ERR_ARG, "%s: n must not exceed G2048_PPO_BATCH_MAX = %d (the batch statistics are the whole batch's; a larger "
+                                   "batch is not truncated)", entry, G2048_PPO_BATCH_MAX);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int ni = (int)n;
+    const Net net = with_dropout(Net{plain, running_or_null, nullptr, static_cast<float *>(workspace), n_out, false, {}}, seed, call_index,
+                                 net_index, p);
+    const float *h3 = net.ws + NetWorkspace(n).h3();
+    launch_trunk(net, states, ni, s);
+    if (n_out == 4)
+        hipLaunchKernelGGL(pg_actor_head_kernel, dim3(blocks_for(n, 64)), dim3(64), 0, s, h3, plain + kFc4W, reinterpret_cast<float4 *>(out),
+                           static_cast<const long long *>(nullptr), static_cast<const float *>(nullptr), static_cast<const float *>(nullptr), 0.0f,
+                           0.0f, static_cast<float *>(nullptr), static_cast<float *>(nullptr), static_cast<float4 *>(nullptr),
+                           static_cast<float *>(nullptr), ni);
+    else
+        hipLaunchKernelGGL(pg_critic_head_kernel, dim3(blocks_for(n, 64)), dim3(64), 0, s, h3, plain + kFc4W, out, static_cast<const float *>(nullptr),
+                           0.0f, static_cast<float *>(nullptr), static_cast<float *>(nullptr), static_cast<float *>(nullptr), ni);
+    return check_launch(entry);
+}
+
+// g2048_ppo_loss_grad and g2048_ppo_loss_grad_dropout; the first is p 0 for both networks
+int loss_grad(const char *entry, const float *states, const int64_t *actions, const float *old_log_probs, const float *advantages,
+              const float *returns, const float *plain_actor, const float *plain_critic, float *running_actor_or_null,
+              float *running_critic_or_null, float clip_epsilon, float value_coef, float entropy_coef, double p_actor, double p_critic,
+              uint64_t seed, uint64_t call_index, size_t n, float *grad_actor_out, float *grad_critic_out, float *loss_out, void *workspace,
+              void *stream)
+{
+    if (n == 0) return G2048_OK;
+    if (!states || !actions || !old_log_probs || !advantages || !returns || !plain_actor || !plain_critic || !grad_actor_out ||
+        !grad_critic_out || !loss_out || !workspace)
+        return fail(G2048_ERR_ARG, "%s: null pointer", entry);
+    if (!aligned(states, 16) || !aligned(plain_actor, 16) || !aligned(plain_critic, 16) || !aligned(grad_actor_out, 16) ||
+        !aligned(grad_critic_out, 16) || !aligned(workspace, 16) || !aligned(actions, 8) || !aligned(old_log_probs, 4) ||
+        !aligned(advantages, 4) || !aligned(returns, 4) || !aligned(running_actor_or_null, 4) || !aligned(running_critic_or_null, 4) ||
+        !aligned(loss_out, 4))
+        return fail(G2048_ERR_ARG, "%s: misaligned pointer (states, plain weights, gradients, workspace: 16 bytes; actions: 8; the rest: 4)",
+                    entry);
+    if (!good_coef(clip_epsilon) || !good_coef(value_coef) || !good_coef(entropy_coef))
+        return fail(G2048_ERR_ARG, "%s: clip_epsilon, value_coef and entropy_coef must be finite and not negative", entry);
+    if (!good_drop(p_actor) || !good_drop(p_critic))
+        return fail(G2048_ERR_ARG, "%s: the dropout probabilities must be finite, 0 <= p < 1", entry);
+    if (n > G2048_PPO_BATCH_MAX)
+        return fail(G2048_ERR_ARG, "%s: n must not exceed G2048_PPO_BATCH_MAX = %d (the batch statistics are the whole batch's; a larger "
+                                   "batch is not truncated)", entry, G2048_PPO_BATCH_MAX);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int ni = (int)n;
+    const NetWorkspace w(n);
+    float *base = static_cast<float *>(workspace), *terms = base + 2 * w.floats();
+    const Net actor = with_dropout(Net{plain_actor, running_actor_or_null, grad_actor_out, base, 4, false, {}}, seed, call_index, 0, p_actor);
+    const Net critic = with_dropout(Net{plain_critic, running_critic_or_null, grad_critic_out, base + w.floats(), 1, false, {}}, seed, call_index,
+                                    1, p_critic);
+    launch_trunk(actor, states, ni, s);
+    launch_trunk(critic, states, ni, s);
+    hipLaunchKernelGGL(pg_actor_head_kernel, dim3(blocks_for(n, 64)), dim3(64), 0, s, static_cast<const float *>(actor.ws + w.h3()),
+                       plain_actor + kFc4W, reinterpret_cast<float4 *>(actor.ws + w.out()), reinterpret_cast<const long long *>(actions),
+                       old_log_probs, advantages, clip_epsilon, entropy_coef, terms, terms + 2 * w.np, reinterpret_cast<float4 *>(actor.ws + w.dz()),
+                       actor.ws + w.d3(), ni);
+    hipLaunchKernelGGL(pg_critic_head_kernel, dim3(blocks_for(n, 64)), dim3(64), 0, s, static_cast<const float *>(critic.ws + w.h3()),
+                       plain_critic + kFc4W, critic.ws + w.out(), returns, value_coef, terms + w.np, critic.ws + w.dz(), critic.ws + w.d3(), ni);
+    hipLaunchKernelGGL(pg_loss_kernel, dim3(1), dim3(256), 0, s, static_cast<const float *>(terms), w.np, value_coef, entropy_coef, loss_out, ni);
+    int rc = launch_backward(actor, states, ni, s, entry);
+    if (rc == G2048_OK) rc = launch_backward(critic, states, ni, s, entry);
+    return rc == G2048_OK ? check_launch(entry) : rc;
+}
 
 }  // namespace
 
@@ -465,30 +630,29 @@ size_t g2048_ppo_train_workspace(size_t n)
 int g2048_ppo_forward_train(const float *states, const float *plain, float *running_or_null, int n_out, float *out, size_t n, void *workspace,
                             void *stream)
 {
+    return forward_train("g2048_ppo_forward_train", states, plain, running_or_null, n_out, 0, 0.0, 0, 0, out, n, workspace, stream);
+}
+
+int g2048_ppo_forward_train_dropout(const float *states, const float *plain, float *running_or_null, int n_out, int net, double p, uint64_t seed,
+                                    uint64_t call_index, float *out, size_t n, void *workspace, void *stream)
+{
+    return forward_train("g2048_ppo_forward_train_dropout", states, plain, running_or_null, n_out, net, p, seed, call_index, out, n, workspace,
+                         stream);
+}
+
+int g2048_ppo_dropout_mask(uint64_t seed, uint64_t call_index, int net, int site, double p, uint8_t *keep_out, size_t n, void *stream)
+{
     if (n == 0) return G2048_OK;
-    if (!states || !plain || !out || !workspace) return fail(G2048_ERR_ARG, "g2048_ppo_forward_train: null pointer");
-    if (!aligned(states, 16) || !aligned(plain, 16) || !aligned(workspace, 16) || !aligned(running_or_null, 4) ||
-        !aligned(out, n_out == 4 ? 16 : 4))
-        return fail(G2048_ERR_ARG, "g2048_ppo_forward_train: misaligned pointer (states, plain weights, workspace, probabilities: 16 bytes; "
-                                   "the rest: 4)");
-    if (n_out != 4 && n_out != 1) return fail(G2048_ERR_ARG, "g2048_ppo_forward_train: n_out must be 4 (actor) or 1 (critic)");
-    if (n > G2048_PPO_BATCH_MAX)
-        return fail(G2048_ERR_ARG, "g2048_ppo_forward_train: n must not exceed G2048_PPO_BATCH_MAX = %d (the batch statistics are the "
-                                   "whole batch's; a larger batch is not truncated)", G2048_PPO_BATCH_MAX);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int ni = (int)n;
-    const Net net{plain, running_or_null, nullptr, static_cast<float *>(workspace), n_out};
-    const float *h3 = net.ws + NetWorkspace(n).h3();
-    launch_trunk(net, states, ni, s);
-    if (n_out == 4)
-        hipLaunchKernelGGL(pg_actor_head_kernel, dim3(blocks_for(n, 64)), dim3(64), 0, s, h3, plain + kFc4W, reinterpret_cast<float4 *>(out),
-                           static_cast<const long long *>(nullptr), static_cast<const float *>(nullptr), static_cast<const float *>(nullptr), 0.0f,
-                           0.0f, static_cast<float *>(nullptr), static_cast<float *>(nullptr), static_cast<float4 *>(nullptr),
-                           static_cast<float *>(nullptr), ni);
-    else
-        hipLaunchKernelGGL(pg_critic_head_kernel, dim3(blocks_for(n, 64)), dim3(64), 0, s, h3, plain + kFc4W, out, static_cast<const float *>(nullptr),
-                           0.0f, static_cast<float *>(nullptr), static_cast<float *>(nullptr), static_cast<float *>(nullptr), ni);
-    return check_launch("g2048_ppo_forward_train");
+    if (!keep_out) return fail(G2048_ERR_ARG, "g2048_ppo_dropout_mask: null pointer");
+    if ((net != 0 && net != 1) || (site != 0 && site != 1))
+        return fail(G2048_ERR_ARG, "g2048_ppo_dropout_mask: net must be 0 (actor) or 1 (critic), site 0 (after bn1, 256 features) or 1 (after "
+                                   "bn2, 128)");
+    if (!good_drop(p)) return fail(G2048_ERR_ARG, "g2048_ppo_dropout_mask: the dropout probability must be finite, 0 <= p < 1");
+    if (n > G2048_PPO_BATCH_MAX) return fail(G2048_ERR_ARG, "g2048_ppo_dropout_mask: n must not exceed G2048_PPO_BATCH_MAX = %d", G2048_PPO_BATCH_MAX);
+    const uint32_t count = (uint32_t)n * (uint32_t)(site == 0 ? kH1 : kH2);
+    hipLaunchKernelGGL(pg_drop_mask_kernel, dim3(blocks_for(count, 256)), dim3(256), 0, static_cast<hipStream_t>(stream), keep_out,
+                       drop_site(seed, call_index, net, site, p), count);
+    return check_launch("g2048_ppo_dropout_mask");
 }
 
 int g2048_ppo_advantages(const float *values, const float *next_values, const float *rewards, const float *dones, float gamma,
@@ -513,39 +677,20 @@ int g2048_ppo_loss_grad(const float *states, const int64_t *actions, const float
                         float clip_epsilon, float value_coef, float entropy_coef, size_t n, float *grad_actor_out, float *grad_critic_out,
                         float *loss_out, void *workspace, void *stream)
 {
-    if (n == 0) return G2048_OK;
-    if (!states || !actions || !old_log_probs || !advantages || !returns || !plain_actor || !plain_critic || !grad_actor_out ||
-        !grad_critic_out || !loss_out || !workspace)
-        return fail(G2048_ERR_ARG, "g2048_ppo_loss_grad: null pointer");
-    if (!aligned(states, 16) || !aligned(plain_actor, 16) || !aligned(plain_critic, 16) || !aligned(grad_actor_out, 16) ||
-        !aligned(grad_critic_out, 16) || !aligned(workspace, 16) || !aligned(actions, 8) || !aligned(old_log_probs, 4) ||
-        !aligned(advantages, 4) || !aligned(returns, 4) || !aligned(running_actor_or_null, 4) || !aligned(running_critic_or_null, 4) ||
-        !aligned(loss_out, 4))
-        return fail(G2048_ERR_ARG, "g2048_ppo_loss_grad: misaligned pointer (states, plain weights, gradients, workspace: 16 bytes; actions: 8; "
-                                   "the rest: 4)");
-    if (!good_coef(clip_epsilon) || !good_coef(value_coef) || !good_coef(entropy_coef))
-        return fail(G2048_ERR_ARG, "g2048_ppo_loss_grad: clip_epsilon, value_coef and entropy_coef must be finite and not negative");
-    if (n > G2048_PPO_BATCH_MAX)
-        return fail(G2048_ERR_ARG, "g2048_ppo_loss_grad: n must not exceed G2048_PPO_BATCH_MAX = %d (the batch statistics are the whole "
-                                   "batch's; a larger batch is not truncated)", G2048_PPO_BATCH_MAX);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int ni = (int)n;
-    const NetWorkspace w(n);
-    float *base = static_cast<float *>(workspace), *terms = base + 2 * w.floats();
-    const Net actor{plain_actor, running_actor_or_null, grad_actor_out, base, 4};
-    const Net critic{plain_critic, running_critic_or_null, grad_critic_out, base + w.floats(), 1};
-    launch_trunk(actor, states, ni, s);
-    launch_trunk(critic, states, ni, s);
-    hipLaunchKernelGGL(pg_actor_head_kernel, dim3(blocks_for(n, 64)), dim3(64), 0, s, static_cast<const float *>(actor.ws + w.h3()),
-                       plain_actor + kFc4W, reinterpret_cast<float4 *>(actor.ws + w.out()), reinterpret_cast<const long long *>(actions),
-                       old_log_probs, advantages, clip_epsilon, entropy_coef, terms, terms + 2 * w.np, reinterpret_cast<float4 *>(actor.ws + w.dz()),
-                       actor.ws + w.d3(), ni);
-    hipLaunchKernelGGL(pg_critic_head_kernel, dim3(blocks_for(n, 64)), dim3(64), 0, s, static_cast<const float *>(critic.ws + w.h3()),
-                       plain_critic + kFc4W, critic.ws + w.out(), returns, value_coef, terms + w.np, critic.ws + w.dz(), critic.ws + w.d3(), ni);
-    hipLaunchKernelGGL(pg_loss_kernel, dim3(1), dim3(256), 0, s, static_cast<const float *>(terms), w.np, value_coef, entropy_coef, loss_out, ni);
-    int rc = launch_backward(actor, states, ni, s);
-    if (rc == G2048_OK) rc = launch_backward(critic, states, ni, s);
-    return rc == G2048_OK ? check_launch("g2048_ppo_loss_grad") : rc;
+    return loss_grad("g2048_ppo_loss_grad", states, actions, old_log_probs, advantages, returns, plain_actor, plain_critic, running_actor_or_null,
+                     running_critic_or_null, clip_epsilon, value_coef, entropy_coef, 0.0, 0.0, 0, 0, n, grad_actor_out, grad_critic_out, loss_out,
+                     workspace, stream);
+}
+
+int g2048_ppo_loss_grad_dropout(const float *states, const int64_t *actions, const float *old_log_probs, const float *advantages,
+                                const float *returns, const float *plain_actor, const float *plain_critic, float *running_actor_or_null,
+                                float *running_critic_or_null, float clip_epsilon, float value_coef, float entropy_coef, double p_actor,
+                                double p_critic, uint64_t seed, uint64_t call_index, size_t n, float *grad_actor_out, float *grad_critic_out,
+                                float *loss_out, void *workspace, void *stream)
+{
+    return loss_grad("g2048_ppo_loss_grad_dropout", states, actions, old_log_probs, advantages, returns, plain_actor, plain_critic,
+                     running_actor_or_null, running_critic_or_null, clip_epsilon, value_coef, entropy_coef, p_actor, p_critic, seed, call_index, n,
+                     grad_actor_out, grad_critic_out, loss_out, workspace, stream);
 }
 
 }  // extern "C"

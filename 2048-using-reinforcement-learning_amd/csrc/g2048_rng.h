@@ -23,6 +23,10 @@ G2048_RNG_HD uint64_t splitmix64(uint64_t x)
     return x ^ (x >> 31);
 }
 
+// RNG domain 11 (DESIGN.md "RNG"): the dropout masks of the PPO update's training-mode forwards (g2048_ppo_grad.hip, its only
+// user; the domains 1 .. 10 of the game kernels are the enum of g2048_board.h)
+constexpr uint32_t kDomDropout = 11;
+
 struct Keys { uint32_t k0, k1; };
 
 G2048_RNG_HD Keys rng_keys(uint64_t seed, uint32_t domain, uint64_t index)

@@ -129,6 +129,9 @@ SIGNATURES = {
     "g2048_ppo_forward_train": (_int, [_vp, _vp, _vp, _int, _vp, _sz, _vp, _vp]),
     "g2048_ppo_advantages": (_int, [_vp] * 4 + [C.c_float, _vp, _vp, _sz, _vp]),
     "g2048_ppo_loss_grad": (_int, [_vp] * 9 + [C.c_float] * 3 + [_sz] + [_vp] * 5),
+    "g2048_ppo_forward_train_dropout": (_int, [_vp, _vp, _vp, _int, _int, C.c_double, _u64, _u64, _vp, _sz, _vp, _vp]),
+    "g2048_ppo_loss_grad_dropout": (_int, [_vp] * 9 + [C.c_float] * 3 + [C.c_double] * 2 + [_u64, _u64, _sz] + [_vp] * 5),
+    "g2048_ppo_dropout_mask": (_int, [_u64, _u64, _int, _int, C.c_double, _vp, _sz, _vp]),
     "g2048_ppo_step_workspace": (_sz, []),
     "g2048_ppo_adam_step": (_int, [_vp] * 10 + [C.c_float] * 7 + [_vp] * 3),
 }

@@ -1575,11 +1575,52 @@ def _ppo_flat(t, floats, name):
     return t
 
 
-def ppo_forward_train(states, plain, n_out, running=None, out=None, workspace=None):
-    """One PPO network's TRAINING-mode forward (g2048_ppo_forward_train): BatchNorm on batch statistics (skipped for one row, as
-    the reference's forward skips it), no dropout. states float32 (n,16); plain: the network's plain float32 parameter buffer
+def ppo_pair(v, name):
+    """(actor's, critic's) of a hyper-parameter given as a scalar or a pair."""
+    if isinstance(v, (tuple, list)):
+        if len(v) != 2:
+            raise ValueError("g2048: %s must be a scalar or an (actor, critic) pair" % name)
+        return float(v[0]), float(v[1])
+    return float(v), float(v)
+
+
+def ppo_dropout_p(p, name="dropout"):
+    """A dropout probability as the library takes it: a finite float, 0 <= p < 1."""
+    p = float(p)
+    if not 0.0 <= p < 1.0:              # a NaN fails both comparisons
+        raise ValueError("g2048: %s must be finite, 0 <= p < 1 (got %r)" % (name, p))
+    return p
+
+
+def ppo_dropout_mask(n, net, site, p, seed=0, call_index=0, device="cuda", out=None):
+    """The keep bits of one dropout site of one call (g2048_ppo_dropout_mask), written through the function the training passes
+    draw them with: uint8 (n, F), F = 256 for site 0 (after bn1) and 128 for site 1 (after bn2), net 0 the actor's and 1 the
+    critic's, 1 where the element is kept. Element (row, feature) is kept iff rng_draw(rng_keys(seed, 11, call_index),
+    ((2 net + site) << 32) | (row F + feature), 0) >= floor(p 2^32); a kept element is multiplied by float32(1 / (1 - p)), a
+    dropped one by 0. No synchronisation."""
+    if net not in (0, 1) or site not in (0, 1):
+        raise ValueError("g2048: net must be 0 (actor) or 1 (critic), site 0 (after bn1) or 1 (after bn2)")
+    p, n = ppo_dropout_p(p), int(n)
+    if not 0 <= n <= L.PPO_BATCH_MAX:
+        raise ValueError("g2048: a dropout mask has 0 .. %d rows (the PPO training pass's batch limit); got n = %d" % (L.PPO_BATCH_MAX, n))
+    dev = torch.device(device)
+    out = _output(out, n, torch.uint8, (256 if site == 0 else 128,), "out", dev)
+    if n:
+        L.call(out.device, L.lib().g2048_ppo_dropout_mask, L.u64(seed), L.u64(call_index), net, site, p, out.data_ptr(), n,
+               L.stream_ptr(out.device))
+    return out
+
+
+def ppo_forward_train(states, plain, n_out, running=None, out=None, workspace=None, dropout=0.0, seed=0, call_index=0, net=0):
+    """One PPO network's TRAINING-mode forward (g2048_ppo_forward_train, with dropout g2048_ppo_forward_train_dropout): BatchNorm
+    on batch statistics (skipped for one row, as the reference's forward skips it), then dropout with probability `dropout` after
+    each BatchNorm (for one row too), the masks those of ppo_dropout_mask(n, net, site, dropout, seed, call_index); dropout = 0
+    is the pass without it, bit for bit. states float32 (n,16); plain: the network's plain float32 parameter buffer
     (ppo_plain_floats(n_out)); running: the 768-float running-statistics buffer, moved by momentum 0.1 when given, untouched
     when None. Returns probabilities float32 (n,4) for n_out 4, values float32 (n,1) for n_out 1. No synchronisation."""
+    p = ppo_dropout_p(dropout)
+    if net not in (0, 1):
+        raise ValueError("g2048: net must be 0 (the actor's masks) or 1 (the critic's)")
     L.require_device_tensor(states, torch.float32, (16,), "states")
     _ppo_flat(plain, ppo_plain_floats(n_out), "plain")
     if running is not None:
@@ -1589,8 +1630,13 @@ def ppo_forward_train(states, plain, n_out, running=None, out=None, workspace=No
     if n == 0:
         return out
     workspace = _ppo_workspace(workspace, n, dev)
-    L.call(dev, L.lib().g2048_ppo_forward_train, states.data_ptr(), plain.data_ptr(), running.data_ptr() if running is not None else None,
-           int(n_out), out.data_ptr(), n, workspace.data_ptr(), L.stream_ptr(dev))
+    run = running.data_ptr() if running is not None else None
+    if p == 0.0:
+        L.call(dev, L.lib().g2048_ppo_forward_train, states.data_ptr(), plain.data_ptr(), run, int(n_out), out.data_ptr(), n,
+               workspace.data_ptr(), L.stream_ptr(dev))
+    else:
+        L.call(dev, L.lib().g2048_ppo_forward_train_dropout, states.data_ptr(), plain.data_ptr(), run, int(n_out), net, p, L.u64(seed),
+               L.u64(call_index), out.data_ptr(), n, workspace.data_ptr(), L.stream_ptr(dev))
     return out
 
 
@@ -1614,13 +1660,17 @@ def ppo_advantages(values, next_values, rewards, dones, gamma=0.995, returns=Non
 
 
 def ppo_loss_grad(states, actions, old_log_probs, advantages, returns, plain_actor, plain_critic, running_actor=None, running_critic=None,
-                  clip_epsilon=0.3, value_coef=0.4, entropy_coef=0.05, grad_actor=None, grad_critic=None, losses=None, workspace=None):
-    """One epoch body of PPOAgent.update (agents/ppo_agent.py:378-400) up to backward() on the device (g2048_ppo_loss_grad): both
-    networks' training-mode forwards (running statistics moved where a buffer is given), the clipped-surrogate, value and entropy
-    loss and d loss / d parameter of both networks in their plain layouts, OVERWRITTEN, never accumulated into. states float32
-    (n,16), actions int64 (n,), old_log_probs, advantages, returns float32 (n,). No dropout, f32 only. An action outside 0..3 is
-    the caller's error (the kernel reads actions & 3). No synchronisation. Returns (losses float32 (4,) = loss, actor_loss,
-    value_loss, entropy; grad_actor; grad_critic)."""
+                  clip_epsilon=0.3, value_coef=0.4, entropy_coef=0.05, grad_actor=None, grad_critic=None, losses=None, workspace=None,
+                  dropout=0.0, seed=0, call_index=0):
+    """One epoch body of PPOAgent.update (agents/ppo_agent.py:378-400) up to backward() on the device (g2048_ppo_loss_grad, with
+    dropout g2048_ppo_loss_grad_dropout): both networks' training-mode forwards (running statistics moved where a buffer is
+    given), the clipped-surrogate, value and entropy loss and d loss / d parameter of both networks in their plain layouts,
+    OVERWRITTEN, never accumulated into. states float32 (n,16), actions int64 (n,), old_log_probs, advantages, returns float32
+    (n,). dropout: a probability or an (actor, critic) pair, applied after each BatchNorm as in ppo_forward_train, both networks'
+    masks those of (seed, call_index), the backward regenerating them; 0 is the pass without it, bit for bit. f32 only. An action
+    outside 0..3 is the caller's error (the kernel reads actions & 3). No synchronisation. Returns (losses float32 (4,) = loss,
+    actor_loss, value_loss, entropy; grad_actor; grad_critic)."""
+    p_actor, p_critic = (ppo_dropout_p(p) for p in ppo_pair(dropout, "dropout"))
     L.require_device_tensor(states, torch.float32, (16,), "states")
     L.require_device_tensor(actions, torch.int64, (), "actions")
     for t, name in ((old_log_probs, "old_log_probs"), (advantages, "advantages"), (returns, "returns")):
@@ -1645,25 +1695,20 @@ def ppo_loss_grad(states, actions, old_log_probs, advantages, returns, plain_act
     if n == 0:
         return losses, grad_actor, grad_critic
     workspace = _ppo_workspace(workspace, n, dev)
-    L.call(dev, L.lib().g2048_ppo_loss_grad, states.data_ptr(), actions.data_ptr(), old_log_probs.data_ptr(), advantages.data_ptr(),
-           returns.data_ptr(), plain_actor.data_ptr(), plain_critic.data_ptr(), running_actor.data_ptr() if running_actor is not None else None,
-           running_critic.data_ptr() if running_critic is not None else None, float(clip_epsilon), float(value_coef), float(entropy_coef), n,
-           grad_actor.data_ptr(), grad_critic.data_ptr(), losses.data_ptr(), workspace.data_ptr(), L.stream_ptr(dev))
+    head = (states.data_ptr(), actions.data_ptr(), old_log_probs.data_ptr(), advantages.data_ptr(), returns.data_ptr(), plain_actor.data_ptr(),
+            plain_critic.data_ptr(), running_actor.data_ptr() if running_actor is not None else None,
+            running_critic.data_ptr() if running_critic is not None else None, float(clip_epsilon), float(value_coef), float(entropy_coef))
+    tail = (n, grad_actor.data_ptr(), grad_critic.data_ptr(), losses.data_ptr(), workspace.data_ptr(), L.stream_ptr(dev))
+    if p_actor == 0.0 and p_critic == 0.0:
+        L.call(dev, L.lib().g2048_ppo_loss_grad, *head, *tail)
+    else:
+        L.call(dev, L.lib().g2048_ppo_loss_grad_dropout, *head, p_actor, p_critic, L.u64(seed), L.u64(call_index), *tail)
     return losses, grad_actor, grad_critic
 
 
 def ppo_step_workspace_bytes():
     """Bytes of the workspace ppo_adam_step needs (g2048_ppo_step_workspace): the scalars its first launch prepares."""
     return L.lib().g2048_ppo_step_workspace()
-
-
-def ppo_pair(v, name):
-    """(actor's, critic's) of a hyper-parameter given as a scalar or a pair."""
-    if isinstance(v, (tuple, list)):
-        if len(v) != 2:
-            raise ValueError("g2048: %s must be a scalar or an (actor, critic) pair" % name)
-        return float(v[0]), float(v[1])
-    return float(v), float(v)
 
 
 def ppo_adam_step(plain_actor, grad_actor, exp_avg_actor, exp_avg_sq_actor, plain_critic, grad_critic, exp_avg_critic, exp_avg_sq_critic,

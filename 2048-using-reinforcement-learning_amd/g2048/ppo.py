@@ -1,10 +1,25 @@
 """The reference's PPOAgent.update() (agents/ppo_agent.py:357-416) on the device.
 
-`DevicePPOLearner(actor, critic, clip_epsilon=0.3, value_coef=0.4, entropy_coef=0.05)` takes the reference's ActorNetwork /
+`DevicePPOLearner(actor, critic, clip_epsilon=0.3, value_coef=0.4, entropy_coef=0.05, dropout=0.0, dropout_seed=0)` takes the reference's ActorNetwork /
 CriticNetwork layout (attributes fc1..fc4 Linear 16-256-128-64-{4|1}, bn1, bn2 BatchNorm1d, in either mode; anything else raises
 ValueError) and evaluates the function update() trains: both networks in TRAINING mode, BatchNorm on batch statistics with its
-running statistics moving on every forward (skipped for a batch of one row, as the reference's forward skips it). The modules'
-Dropout layers are IGNORED, as everywhere in this library: the device pass is update() with dropout p = 0.
+running statistics moving on every forward (skipped for a batch of one row, as the reference's forward skips it).
+
+Dropout. The reference's networks apply nn.Dropout(0.2) after each BatchNorm (for one row, where the BatchNorms are skipped, after
+the two ReLUs), and update() runs them in training mode, the two critic forwards of its no-gradient block included. `dropout`
+says what the device pass does with those layers: with 0.0 (the default) they are IGNORED, which is update() with p = 0 and what this
+class computed before it knew dropout, bit for bit; a probability, or an (actor, critic) pair, applies it; "module" takes each
+module's own `dropout.p` (the reference's 0.2). The masks are not torch's: element (row, feature) of site s (0 after bn1, 1
+after bn2) of network w (0 actor, 1 critic) is kept iff one draw of the library's counter RNG (DESIGN.md "RNG", domain 11), a pure
+function of (dropout_seed, call index, w, s, row, feature), is at least floor(p 2^32), and a kept element is multiplied by
+float32(1 / (1 - p)): the same distribution as torch's, reproducible from the seed and the index (ops.ppo_dropout_mask writes the
+keep bits), regenerated in the backward pass instead of stored. `dropout_index` is the call index of the NEXT training-mode
+forward, a Python int counted on the host: probs, values and loss_and_grad take one each (both networks of loss_and_grad share it),
+advantages two (states, then next states), so update(epochs=E) takes 2 + E. No forward is ever skipped (the NaN gate skips only
+the optimiser step), so the count needs nothing from the device. dropout_state() / set_dropout_state() carry (seed, index) through
+a checkpoint. The index is a launch scalar: a captured graph of update() replays the SAME masks on every replay. Out of scope:
+DevicePolicy and the rollout kernels are eval mode, as get_action uses the networks; the hybrid Q-network's eight dropout sites;
+bf16.
 
 Each network lives in three flat float32 buffers on the modules' device: `plain` (the parameters, layout of include/g2048.h =
 the module's named_parameters() order), `grad` (same layout, overwritten by loss_and_grad) and `running` (bn1.running_mean,
@@ -63,6 +78,22 @@ def parse(module, n_out):
     for key in ("fc1", "bn1", "fc2", "bn2", "fc3", "fc4"):
         params += [names[key].weight, names[key].bias]
     return params, [names["bn1"], names["bn2"]]
+
+
+def dropout_of(actor, critic, dropout):
+    """(actor's p, critic's p) of DevicePPOLearner's `dropout`: a probability, an (actor, critic) pair, or "module" for each
+    module's own `dropout.p`. Raises ValueError for a module without such a layer and for a p outside 0 <= p < 1."""
+    if isinstance(dropout, str):
+        if dropout != "module":
+            raise ValueError("%s: dropout must be a probability, an (actor, critic) pair or \"module\", got %r" % (NAME, dropout))
+        layers = [getattr(m, "dropout", None) for m in (actor, critic)]
+        if not all(isinstance(d, nn.Dropout) for d in layers):
+            raise ValueError("%s: dropout=\"module\" needs an nn.Dropout attribute `dropout` on both modules (the reference's layout)" % NAME)
+        dropout = (layers[0].p, layers[1].p)
+    try:
+        return tuple(ops.ppo_dropout_p(p) for p in ops.ppo_pair(dropout, "dropout"))
+    except ValueError as e:
+        raise ValueError(str(e).replace("g2048:", NAME + ":")) from None
 
 
 class _TrainNet:
@@ -182,7 +213,7 @@ WHICH = ("actor", "critic")
 
 class DevicePPOLearner:
     """PPOAgent.update()'s networks, loss and gradients on the device (module docstring). The hyper-parameters default to the
-    reference agent's. Dropout is ignored.
+    reference agent's. dropout, dropout_seed, dropout_index, dropout_state(), set_dropout_state(): the module docstring.
 
     probs(states) / values(states): one network's training-mode forward on float32 (N,16) observations; the running statistics move
       and num_batches_tracked counts, as in torch.
@@ -205,11 +236,13 @@ class DevicePPOLearner:
       counter in the format of torch.optim.Adam(module.parameters()).state_dict().
     1 <= N <= 4096; states are float32 (N,16) as RolloutCollector.sample returns them, not packed boards."""
 
-    def __init__(self, actor, critic, clip_epsilon=0.3, value_coef=0.4, entropy_coef=0.05):
+    def __init__(self, actor, critic, clip_epsilon=0.3, value_coef=0.4, entropy_coef=0.05, dropout=0.0, dropout_seed=0):
         for v, name in ((clip_epsilon, "clip_epsilon"), (value_coef, "value_coef"), (entropy_coef, "entropy_coef")):
             if not (float(v) >= 0.0 and float(v) != float("inf")):
                 raise ValueError("%s: %s must be finite and not negative" % (NAME, name))
         self.clip_epsilon, self.value_coef, self.entropy_coef = float(clip_epsilon), float(value_coef), float(entropy_coef)
+        self.dropout = dropout_of(actor, critic, dropout)           # (actor's p, critic's p)
+        self.dropout_seed, self.dropout_index = ops.L.u64(dropout_seed), 0
         self.actor, self.critic = _TrainNet(actor, 4), _TrainNet(critic, 1)
         if self.actor.device != self.critic.device:
             raise ValueError("%s: actor and critic live on different devices" % NAME)
@@ -250,10 +283,27 @@ class DevicePPOLearner:
             raise ValueError("%s: states on %s, weights on %s" % (NAME, states.device, self.device))
         return states.shape[0]
 
+    def dropout_state(self):
+        """(dropout_seed, dropout_index): with the weights, what reproduces the masks of every later call."""
+        return self.dropout_seed, self.dropout_index
+
+    def set_dropout_state(self, state):
+        seed, index = state
+        if int(index) < 0:
+            raise ValueError("%s: the dropout index must not be negative" % NAME)
+        self.dropout_seed, self.dropout_index = ops.L.u64(seed), int(index)
+
+    def _next_index(self):
+        index = self.dropout_index
+        self.dropout_index = index + 1
+        return index
+
     def _forward(self, net, states, make):
         n = self._rows(states)
+        w = 0 if net is self.actor else 1
         out = ops.ppo_forward_train(states, net.plain, net.n_out, running=net.running, out=self._out.get(n, make),
-                                    workspace=self._out.get(n, _workspace))
+                                    workspace=self._out.get(n, _workspace), dropout=self.dropout[w], seed=self.dropout_seed,
+                                    call_index=self._next_index(), net=w)
         net.tracked(n)
         return out
 
@@ -277,7 +327,8 @@ class DevicePPOLearner:
         losses, _, _ = ops.ppo_loss_grad(states, actions, old_log_probs, advantages, returns, self.actor.plain, self.critic.plain,
                                          self.actor.running, self.critic.running, self.clip_epsilon, self.value_coef, self.entropy_coef,
                                          grad_actor=self.actor.grad, grad_critic=self.critic.grad,
-                                         losses=self._out.get(n, _losses) if losses is None else losses, workspace=self._out.get(n, _workspace))
+                                         losses=self._out.get(n, _losses) if losses is None else losses, workspace=self._out.get(n, _workspace),
+                                         dropout=self.dropout, seed=self.dropout_seed, call_index=self._next_index())
         self.actor.tracked(n)
         self.critic.tracked(n)
         return losses

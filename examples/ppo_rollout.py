@@ -2,7 +2,7 @@
 """Collect a PPO rollout (BASELINE config 4: 65,536 envs x 128 steps) entirely on the GPU.
 
     python examples/ppo_rollout.py [--envs 65536] [--steps 128] [--policy torch|device-f32|device-bf16|transformer|transformer-bf16]
-                                   [--learner torch|device] [--optimizer torch|device]
+                                   [--learner torch|device] [--optimizer torch|device] [--dropout P]
 
 The policy is any torch module mapping float32 (N,16) observations to action probabilities (N,4) -- or
 (probs, value); here a small MLP. Everything between the policy's outputs and its next inputs (masked sampling,
@@ -19,7 +19,9 @@ reference's hyper-parameters (batch 256, 8 epochs, clip 0.3, Adam 8e-4 / 2e-3): 
 training-mode forwards, loss and gradients are g2048.DevicePPOLearner's HIP launches, clip_grad_norm_(0.5) and stock
 torch.optim.Adam run on views of its buffers. --optimizer device (with --learner device) makes the epoch loop one learner.update()
 call: the NaN check on the loss, the clipping and both Adam steps are two more launches an epoch, and nothing is read on the host
-until the loss is printed. Dropout is left out, as everywhere in this library."""
+until the loss is printed. --dropout P (with --learner device; the reference's networks have 0.2) trains with the reference's live
+dropout on the device, the masks drawn from the learner's counter RNG; the default 0 leaves the Dropout layers out, and the torch
+learner keeps its own."""
 import argparse
 import os
 import sys
@@ -41,9 +43,13 @@ ap.add_argument("--dim-ff", type=int, default=128, help="feed-forward width of t
 ap.add_argument("--learner", choices=("torch", "device"), default="torch")
 ap.add_argument("--optimizer", choices=("torch", "device"), default="torch",
                 help="with --learner device: stock clip_grad_norm_ + Adam on the views, or the learner's own update()")
+ap.add_argument("--dropout", type=float, default=0.0,
+                help="with --learner device: the dropout probability of the training-mode forwards (the reference's networks: 0.2)")
 a = ap.parse_args()
 if a.optimizer == "device" and a.learner != "device":
     ap.error("--optimizer device needs --learner device")
+if a.dropout and a.learner != "device":
+    ap.error("--dropout is the device learner's; the torch learner's modules keep their own")
 if a.learner == "device" and a.policy.startswith("transformer"):
     ap.error("--learner device trains the reference's MLP actor and critic; use --policy torch, device-f32 or device-bf16")
 
@@ -125,7 +131,8 @@ print("obs", tuple(traj["obs"].shape), "rewards mean %.3f" % float(traj["rewards
 
 def device_update():
     """PPOAgent.update() (agents/ppo_agent.py:336-420) with its own settings; everything that needs the networks is a HIP launch."""
-    learner = g2048.DevicePPOLearner(net.actor, net.critic, clip_epsilon=0.3, value_coef=0.4, entropy_coef=0.05)
+    learner = g2048.DevicePPOLearner(net.actor, net.critic, clip_epsilon=0.3, value_coef=0.4, entropy_coef=0.05, dropout=a.dropout,
+                                     dropout_seed=1)
     learner.attach_params()
     mb = rc.sample(256)
     if a.optimizer == "device":         # the whole of update() in one call: the NaN check, clipping and Adam are launches too
@@ -148,6 +155,8 @@ def device_update():
     loss, actor_loss, value_loss, entropy = losses.tolist()
     print("device update on 256 sampled transitions (of %d): loss %.4f (actor %.4f, value %.4f, entropy %.4f) after 8 epochs"
           % (a.envs * a.steps, loss, actor_loss, value_loss, entropy))
+    if a.dropout:
+        print("dropout p = %g: %d training-mode forwards drew masks (dropout_state %s)" % (a.dropout, learner.dropout_index, learner.dropout_state()))
     if a.optimizer == "device":
         applied_actor, applied_critic, nan_loss, bad_norm = learner.opt_counters.tolist()
         print("device optimizer: %d / %d Adam steps applied (actor / critic), %d epochs skipped for a NaN loss, %d for a gradient norm "

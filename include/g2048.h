@@ -55,7 +55,8 @@ extern "C" {
                                       _update_priorities / _update_workspace, g2048_dqn_shape_rewards, g2048_qnet_forward_batch,
                                       g2048_qnet_batch_workspace, g2048_dqn_targets, g2048_qnet_loss_grad / _grad_workspace,
                                       g2048_qnet_adamw_step / _step_workspace, g2048_ppo_train_workspace / _forward_train /
-                                      _advantages / _loss_grad, g2048_ppo_adam_step / _step_workspace)
+                                      _advantages / _loss_grad, g2048_ppo_adam_step / _step_workspace,
+                                      g2048_ppo_forward_train_dropout / _loss_grad_dropout / g2048_ppo_dropout_mask)
                                       4: round 5 (export table = this header + g2048_testing.h exactly: test / measurement hooks moved there,
                                       internal symbols hidden; g2048_replay_games also clamps a game's length to actions_stride)
                                       3: round 4 (actions_out of the g2048_play_games family, g2048_replay_games, g2048_env_step,
@@ -869,8 +870,9 @@ G2048_API int g2048_qnet_adamw_step(float *plain, float *grad, float *exp_avg, f
  * BatchNorms use the batch mean and the biased variance over the n rows (eps 1e-5); given a running-statistics buffer they move
  * it by momentum 0.1 towards the batch mean and the UNBIASED variance, as torch does. For n == 1 the reference's forward skips
  * both BatchNorms, and so does this: their gradients are written as 0 and the running statistics are untouched. The reference
- * runs these lines with its dropout live; that is left out, as everywhere in this library. f32 only. The inputs are the float
- * observations PPOAgent.update builds (states float32 [n][16], 16-byte aligned), not packed boards.
+ * runs these lines with its dropout live (nn.Dropout(0.2) on b1 and b2); g2048_ppo_forward_train and g2048_ppo_loss_grad leave
+ * it out (p = 0), the *_dropout entry points below apply it. f32 only. The inputs are the float observations PPOAgent.update
+ * builds (states float32 [n][16], 16-byte aligned), not packed boards.
  *
  * One network's parameters are one PLAIN f32 buffer of 46272 + 65 * n_out floats (n_out 4: actor, 1: critic), torch's row-major
  * [out][in], back to back:
@@ -901,9 +903,34 @@ G2048_API int g2048_qnet_adamw_step(float *plain, float *grad, float *exp_avg, f
  *       and backward and the heads (fc4, the loss, its derivative) on the VALU. No atomics, no split-K across blocks: every
  *       output element is one fixed-order accumulation, so two calls give the same bits. Nothing past row n or past the stated
  *       sizes is read or written.
+ *
+ * Dropout (the reference's training-mode forwards; RNG domain 11 of DESIGN.md "RNG"). With probability p, b1 and b2 (for n == 1,
+ * where the BatchNorms are skipped: h1 and h2) are multiplied element by element by m before fc2 / fc3 read them. For the library
+ * call with index `call_index`, (k0, k1) = rng_keys(seed, 11, call_index); element (row, feature) of site s (0: b1, F = 256; 1: b2,
+ * F = 128) of network w (0 actor, 1 critic) draws h = rng_draw(k0, k1, id, 0), id = ((uint64)(2 w + s) << 32) | (row * F + feature),
+ * and is kept iff h >= T, T = (uint32) floor(p * 2^32) formed in double; m = (float)(1.0 / (1.0 - p)) if kept, else 0.0f. It is a
+ * multiplication both ways (y = x * m, dx = dy * m), as in torch: a NaN or an infinity in a dropped position becomes NaN. The
+ * backward regenerates m; no mask is stored and the workspace is the same. p is a double, 0 <= p < 1 and finite.
+ *   g2048_ppo_forward_train_dropout   g2048_ppo_forward_train with dropout p on the masks of network `net` (0 or 1, whatever
+ *       n_out is: the critic's forwards of the advantages block pass 1).
+ *   g2048_ppo_loss_grad_dropout   g2048_ppo_loss_grad with p_actor on the actor (w = 0) and p_critic on the critic (w = 1); both
+ *       networks share call_index. Still one fixed-order accumulation per output element: two calls with the same seed and
+ *       index give the same bits.
+ *   g2048_ppo_dropout_mask   keep_out uint8 [n][F] = 1 where the element of (net, site) is kept, written through the function the
+ *       two passes draw with; for callers who reproduce a step, and for tests. 1 <= n <= G2048_PPO_BATCH_MAX.
+ *   With p == 0 (p_actor == p_critic == 0) the two passes launch exactly the kernels of the entry points without dropout and give
+ *   their bits. A network with p == 0 next to one with p > 0 is the pass without dropout for that network.
+ *
+ * A ReLU's backward, in all of these passes, is torch's threshold_backward: the gradient is zeroed where the ReLU's output is <= 0,
+ * so it passes where the output is a NaN (a non-finite row of `states`), and each gradient tensor is then non-finite where stock
+ * torch's is. One exception: n == 1 in a network WITHOUT dropout. There the two hidden ReLUs' backward is the mask of the shared dX
+ * product (the Q-network's kernel), which keeps the gradient where the output is > 0 and so zeroes it at a NaN; the loss parts are
+ * NaN all the same, which is what the optimiser's gate reads. n == 1 with p > 0 and every n > 1 follow torch.
+ *
  * 1 <= n <= G2048_PPO_BATCH_MAX (the batch statistics are the whole batch's: a larger n is refused, not truncated); n == 0
  * returns G2048_OK and does nothing. Arguments are checked before any device call: a null or misaligned pointer, n too large,
- * n_out other than 4 or 1, a clip_epsilon, value_coef or entropy_coef that is negative or not finite return G2048_ERR_ARG. */
+ * n_out other than 4 or 1, net or site other than 0 or 1, a clip_epsilon, value_coef or entropy_coef that is negative or not
+ * finite, a p that is negative, >= 1 or not finite return G2048_ERR_ARG. */
 #define G2048_PPO_BATCH_MAX 4096
 G2048_API size_t g2048_ppo_train_workspace(size_t n);
 G2048_API int g2048_ppo_forward_train(const float *states, const float *plain, float *running_or_null, int n_out, float *out, size_t n,
@@ -914,6 +941,15 @@ G2048_API int g2048_ppo_loss_grad(const float *states, const int64_t *actions, c
                         const float *returns, const float *plain_actor, const float *plain_critic, float *running_actor_or_null,
                         float *running_critic_or_null, float clip_epsilon, float value_coef, float entropy_coef, size_t n,
                         float *grad_actor_out, float *grad_critic_out, float *loss_out, void *workspace, void *stream);
+G2048_API int g2048_ppo_forward_train_dropout(const float *states, const float *plain, float *running_or_null, int n_out, int net, double p,
+                                    uint64_t seed, uint64_t call_index, float *out, size_t n, void *workspace, void *stream);
+G2048_API int g2048_ppo_loss_grad_dropout(const float *states, const int64_t *actions, const float *old_log_probs, const float *advantages,
+                                const float *returns, const float *plain_actor, const float *plain_critic, float *running_actor_or_null,
+                                float *running_critic_or_null, float clip_epsilon, float value_coef, float entropy_coef, double p_actor,
+                                double p_critic, uint64_t seed, uint64_t call_index, size_t n, float *grad_actor_out,
+                                float *grad_critic_out, float *loss_out, void *workspace, void *stream);
+G2048_API int g2048_ppo_dropout_mask(uint64_t seed, uint64_t call_index, int net, int site, double p, uint8_t *keep_out, size_t n,
+                           void *stream);
 
 /* ---- the PPO update's loss gate, gradient clipping and Adam step (agents/ppo_agent.py:403-416) ------------------------------
  * What an epoch of PPOAgent.update() does after backward(), for the actor and the critic TOGETHER: `if torch.isnan(loss):

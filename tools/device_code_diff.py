@@ -1,10 +1,12 @@
 #!/usr/bin/env python3
-"""(host) Is the device code of two builds of the library the same?   python tools/device_code_diff.py A.so B.so
+"""(host) Is the device code of two builds of the library the same?   python tools/device_code_diff.py A.so B.so [A_KERNEL=B_KERNEL ...]
 
 Unbundles both with `llvm-objdump --offloading` and compares, per gfx950 code object (one per .hip file, in link order), the set
 of kernels and the bytes of .text and .rodata (the kernel descriptors live there). Where a whole section differs -- e.g. the
 same kernels emitted in another order -- every kernel is compared on its own: the function's bytes and its 64-byte descriptor
-`<kernel>.kd` (without its entry offset, which moves when a kernel is added); the ones that differ are printed. Exit status 0 only if everything matches. What a host-side refactor has to show."""
+`<kernel>.kd` (without its entry offset, which moves when a kernel is added); the ones that differ are printed. A_KERNEL=B_KERNEL (mangled names) compares a kernel of A with the kernel of B that took its place
+under another name, e.g. one that became the instantiation of a template; kernels only B has are then listed, not counted. Exit
+status 0 only if everything else matches. What a host-side refactor has to show."""
 import glob
 import os
 import shutil
@@ -58,7 +60,8 @@ def without_entry_offset(kd):
     return kd[:KD_ENTRY_OFFSET.start] + kd[KD_ENTRY_OFFSET.stop:]
 
 
-def main(a, b):
+def main(a, b, renamed=()):
+    to_b = dict(pair.split("=") for pair in renamed)
     with tempfile.TemporaryDirectory() as tmp:
         objs_a, objs_b = code_objects(a, os.path.join(tmp, "a")), code_objects(b, os.path.join(tmp, "b"))
     same = len(objs_a) == len(objs_b) and len(objs_a) > 0
@@ -69,10 +72,17 @@ def main(a, b):
         whole = {s: sec_a.get(s, (0, b""))[1] == sec_b.get(s, (0, b""))[1] for s in (".text", ".rodata")}
         print("code object %d: %d kernels; " % (i, len(kern_a)) + "; ".join(
             "%s %d bytes %s" % (s, len(sec_a.get(s, (0, b""))[1]), "identical" if ok else "DIFFERS") for s, ok in whole.items()))
+        here = {k: v for k, v in to_b.items() if k in kern_a and v in kern_b}
+        if here:
+            print("  compared under another name: " + ", ".join("%s = %s" % kv for kv in sorted(here.items())))
+            if kern_b - set(here.values()) - kern_a:
+                print("  kernels only in %s: %s" % (b, sorted(kern_b - set(here.values()) - kern_a)))
+            kern_b = (kern_b - set(here.values())) & kern_a | set(here)
+            sym_b = dict(sym_b, **{k + tail: sym_b[v + tail] for k, v in here.items() for tail in ("", ".kd")})
         if kern_a != kern_b:
             same = False
             print("  kernels only in %s: %s\n  kernels only in %s: %s" % (a, sorted(kern_a - kern_b), b, sorted(kern_b - kern_a)))
-        if not all(whole.values()):
+        if not all(whole.values()) or here:
             # a descriptor holds the offset from itself to the kernel's entry (KD_ENTRY_OFFSET), which moves with every kernel added
             # to or taken from the code object: compared with that field left out, and reported apart from the function's bytes
             def parts(k):
@@ -97,6 +107,6 @@ def main(a, b):
 
 
 if __name__ == "__main__":
-    if len(sys.argv) != 3:
+    if len(sys.argv) < 3 or not all("=" in pair for pair in sys.argv[3:]):
         sys.exit(__doc__)
-    sys.exit(main(sys.argv[1], sys.argv[2]))
+    sys.exit(main(sys.argv[1], sys.argv[2], sys.argv[3:]))

@@ -4,6 +4,9 @@
     python3 tools/ppo_update_rate.py --trace N [CALLS]    only CALLS (50) loss_and_grad calls at n = N, for a kernel trace:
         rocprofv3 --kernel-trace --stats --output-format csv -d OUT -- python3 tools/ppo_update_rate.py --trace 256
     python3 tools/ppo_update_rate.py --trace-step [CALLS] only CALLS (50) adam_step calls after one loss_and_grad, for a kernel trace
+    python3 tools/ppo_update_rate.py --dropout [PARENT.so] the dropout table: loss_and_grad and update() with p = 0 and p = 0.2 next to
+        stock torch's modules with dropout.p 0 and 0.2, and, given another build of the library (e.g. the parent commit's, python -m
+        g2048._build -o PARENT.so in its tree), the same p = 0 calls through that build, all alternating in one run
 
 The reference's actor and critic (16-256-128-64-{4|1}, BatchNorm1d after the first two ReLUs, torch's default init) in training
 mode with dropout p = 0 on BOTH sides, at n = 256 (the reference's batch) and 4,096 (the limit). Versions, alternating within
@@ -25,7 +28,8 @@ A round times REPS back-to-back calls of a version between one event pair and di
 perf_counter around the same calls before it waits for the device (the host-enqueue clock); median of 7 rounds after 2 warm-up
 rounds, min - max of the device clock in brackets. Before timing, the device gradients and stock torch's float32 ones are both
 compared with the modules' float64 autograd on the same GPU, per tensor as max|g - g64| / max|g64|.
-Output: one text table (profiles/r23_ppo_update_rate.txt and profiles/r25_ppo_step_rate.txt keep runs)."""
+Output: one text table (profiles/r23_ppo_update_rate.txt, profiles/r25_ppo_step_rate.txt and profiles/r26_ppo_dropout_rate.txt keep
+runs)."""
 import copy
 import os
 import statistics
@@ -178,6 +182,103 @@ if sys.argv[1:2] == ["--trace-step"]:
         learner.adam_step(losses, lr=LR, max_norm=MAX_NORM)
     torch.cuda.synchronize()
     print("%d adam_step calls; counters %s" % (calls, learner.opt_counters.tolist()))
+    sys.exit(0)
+
+def other_build(path):
+    """Another build of the C-ABI next to the product's: the entry points it has, bound as g2048._lib binds them."""
+    import ctypes
+    from g2048 import _lib
+    lib = ctypes.CDLL(path)
+    for name, (res, args) in _lib.SIGNATURES.items():
+        fn = getattr(lib, name, None)           # a parent build lacks what this tree adds
+        if fn is not None:
+            fn.restype, fn.argtypes = res, args
+    return lib
+
+
+def through(lib, fn):
+    """fn with every C-ABI call of the package going to `lib`: the same Python path, the other build's host code and kernels."""
+    from g2048 import _lib
+
+    def run():
+        mine, _lib._lib = _lib.lib(), lib
+        try:
+            return fn()
+        finally:
+            _lib._lib = mine
+    return run
+
+
+def report(n, versions, times, against):
+    for name, _ in versions:
+        tt, hh = [t for t, _ in times[name]], [h for _, h in times[name]]
+        med = statistics.median(tt)
+        other = against.get(name, versions[0][0])
+        base = statistics.median([t for t, _ in times[other]])
+        print("%-7d %-26s %10.1f %22s %10.1f %12.4g %9.2fx %s" % (n, name, med * 1e6, "[%.1f - %.1f]" % (min(tt) * 1e6, max(tt) * 1e6),
+                                                                 statistics.median(hh) * 1e6, n / med, base / med, other))
+
+
+if sys.argv[1:2] == ["--dropout"]:
+    parent = other_build(sys.argv[2]) if len(sys.argv) > 2 else None
+    P = 0.2
+    print("# %d calls per event pair; median of 7 rounds after 2 warm-up rounds, the versions alternating; update() is the advantages block "
+          "+ %d epochs, adam_step included; torch update: clip_grad_norm_(%.1f) and stock torch.optim.Adam" % (REPS, EPOCHS, MAX_NORM))
+    print("%-7s %-26s %10s %22s %10s %12s %10s" % ("rows", "version", "us", "[min - max] us", "host us", "rows/s", "vs"))
+    for n in (256, 4096):
+        actor, critic = fresh()
+        x, nx, actions, old, adv, ret, rewards, dones = inputs(copy.deepcopy(actor).double(), copy.deepcopy(critic).double(), n)
+
+        def learner_with(p):
+            le = DevicePPOLearner(copy.deepcopy(actor), copy.deepcopy(critic), CLIP, VALUE_COEF, ENTROPY_COEF, dropout=p)
+            le.attach_params()
+            return le
+
+        def torch_with(p):
+            mods = copy.deepcopy(actor), copy.deepcopy(critic)
+            for m in mods:
+                m.dropout.p = p
+            return mods, [torch.optim.Adam(m.parameters(), lr=LR) for m in mods]
+        grad0, grad2, upd0, upd2 = learner_with(0.0), learner_with(P), learner_with(0.0), learner_with(P)
+        (t0, o0), (t2, o2), (u0, uo0), (u2, uo2) = torch_with(0.0), torch_with(P), torch_with(0.0), torch_with(P)
+        update = lambda le: le.update(x, actions, old, rewards, nx, dones, epochs=EPOCHS, gamma=GAMMA, lr=LR, max_norm=MAX_NORM)      # noqa: E731
+        versions, against = [], {}
+        if parent is not None:
+            grad_p, upd_p = learner_with(0.0), learner_with(0.0)
+            mine = [t.clone() for t in (grad0.loss_and_grad(x, actions, old, adv, ret), grad0.actor.grad, grad0.critic.grad)]
+            theirs = [through(parent, lambda: grad_p.loss_and_grad(x, actions, old, adv, ret))(), grad_p.actor.grad, grad_p.critic.grad]
+            print("# n = %d: p = 0 through this build and through %s: losses and both gradient buffers %s" % (
+                n, os.path.basename(sys.argv[2]), "bit for bit the same" if all(torch.equal(a.view(torch.int32), b.view(torch.int32))
+                                                                              for a, b in zip(mine, theirs)) else "DIFFER"))
+            versions += [("parent loss_and_grad", through(parent, lambda: grad_p.loss_and_grad(x, actions, old, adv, ret)))]
+            against.update({"device loss_and_grad p=0": "parent loss_and_grad", "device update() p=0": "parent update()",
+                            "parent update()": "parent update()"})
+        versions += [("device loss_and_grad p=0", lambda: grad0.loss_and_grad(x, actions, old, adv, ret)),
+                     ("device loss_and_grad p=0.2", lambda: grad2.loss_and_grad(x, actions, old, adv, ret)),
+                     ("torch fwd+loss+bwd p=0", lambda: torch_step(*t0, x, actions, old, adv, ret)),
+                     ("torch fwd+loss+bwd p=0.2", lambda: torch_step(*t2, x, actions, old, adv, ret)),
+                     ] + ([("parent update()", through(parent, lambda: update(upd_p)))] if parent is not None else []) + [
+                     ("device update() p=0", lambda: update(upd0)), ("device update() p=0.2", lambda: update(upd2)),
+                     ("torch update p=0", lambda: torch_update(*u0, uo0, x, nx, actions, old, rewards, dones)),
+                     ("torch update p=0.2", lambda: torch_update(*u2, uo2, x, nx, actions, old, rewards, dones))]
+        against.update({"device loss_and_grad p=0.2": "device loss_and_grad p=0", "torch fwd+loss+bwd p=0.2": "torch fwd+loss+bwd p=0",
+                        "device update() p=0.2": "device update() p=0", "torch update p=0.2": "torch update p=0",
+                        "torch fwd+loss+bwd p=0": "device loss_and_grad p=0", "torch update p=0": "device update() p=0"})
+        against.setdefault("device loss_and_grad p=0", "device loss_and_grad p=0")
+        against.setdefault("device update() p=0", "device update() p=0")
+        times = alternate(versions, 2, 7)
+        report(n, versions, times, against)
+        med = lambda name: statistics.median([t for t, _ in times[name]]) * 1e6      # noqa: E731
+        for what, a, b in (("loss_and_grad", "device loss_and_grad p=0.2", "device loss_and_grad p=0"),
+                           ("torch fwd+loss+bwd", "torch fwd+loss+bwd p=0.2", "torch fwd+loss+bwd p=0"),
+                           ("update()", "device update() p=0.2", "device update() p=0"), ("torch update", "torch update p=0.2", "torch update p=0")):
+            print("# n = %d: %s, p = 0.2 over p = 0: %+.1f us (%+.1f %%)" % (n, what, med(a) - med(b), 100 * (med(a) / med(b) - 1)))
+        if parent is not None:
+            for mine, theirs in (("device loss_and_grad p=0", "parent loss_and_grad"), ("device update() p=0", "parent update()")):
+                tt = [t * 1e6 for t, _ in times[theirs]]
+                print("# n = %d: %s against %s: %+.1f us; the parent's own rounds span %.1f us" % (n, mine, theirs, med(mine) - med(theirs),
+                                                                                                 max(tt) - min(tt)))
+        print("# n = %d: dropout_index of the p = 0.2 update() learner %d, its optimiser counters %s" % (n, upd2.dropout_index, upd2.opt_counters.tolist()))
     sys.exit(0)
 
 print("# %d calls per event pair; median of 7 rounds after 2 warm-up rounds, the versions alternating; an update is the advantages "
