@@ -1,12 +1,14 @@
 // g2048_grad_products.h -- the two general products of a gradient pass on the f32 matrix cores, shared by g2048_qnet_grad.hip
 // (the Q-network's backward) and g2048_ppo_grad.hip (the PPO actor's and critic's): the data gradient dX = dY . W and the
 // weight gradient dW = dY^T . X with db = sum dY, for row-major f32 operands as they lie in a plain parameter buffer and a
-// workspace. Device code, included by those two files and nothing else; every kernel is per translation unit. The rules are
+// workspace. Device code, included by those two files and g2048_qnet_train.hip (through g2048_qnet_grad_bwd.h) and nothing else; every
+// kernel is per translation unit. The rules are
 // g2048_qnet_grad.hip's: every output element is one wavefront's fixed-order accumulation, nothing past row n is read or written.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "g2048_mfma.h"
+#include "g2048_qnet_drop.h"
 
 namespace {
 
@@ -35,9 +37,13 @@ __device__ inline void dx_chunks(const float *__restrict__ wcol, size_t K, const
         for (int c = 0; c < N; ++c) acc[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[c][r], y[c][r], acc[c], 0, 0, 0);
 }
 
-// four wavefronts a block = four feature tiles of one board tile; grid (K / 64 up, board tiles). M is a multiple of 32.
+// four wavefronts a block = four feature tiles of one board tile; grid (K / 64 up, board tiles). M is a multiple of 32. With a
+// QDrop (the Q-network's training pass, site 2) dX is the gradient at a dropped layer's input: after the ReLU mask it is multiplied
+// by the site's regenerated m, element board K + feature.
+template <class... MaybeDrop>
 __global__ __launch_bounds__(256) void qg_dx_kernel(const float *__restrict__ dY, int M, const float *__restrict__ W, int K,
-                                                     const float *__restrict__ res, const float *__restrict__ mask, float *__restrict__ dX, int n)
+                                                     const float *__restrict__ res, const float *__restrict__ mask, float *__restrict__ dX, int n,
+                                                     MaybeDrop... drop)
 {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4, col = lane & 15;
     const int o = (int)blockIdx.x * 4 + wave;
@@ -59,6 +65,10 @@ __global__ __launch_bounds__(256) void qg_dx_kernel(const float *__restrict__ dY
         const f4 a = load_f4(mask + at);
 #pragma unroll
         for (int r = 0; r < 4; ++r) v[r] = a[r] > 0.0f ? v[r] : 0.0f;
+    }
+    if constexpr (sizeof...(MaybeDrop) != 0) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) v[r] *= qdrop_mult(drop..., (uint32_t)at + (uint32_t)r);
     }
     *reinterpret_cast<f4 *>(dX + at) = v;
 }

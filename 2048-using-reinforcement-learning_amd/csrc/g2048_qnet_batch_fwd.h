@@ -1,7 +1,9 @@
 // g2048_qnet_batch_fwd.h -- the forward kernels of the hybrid agent's Q-network on a BATCH of boards (one sequence of n tokens), shared
 // by g2048_qnet_batch.hip (the forward alone) and g2048_qnet_grad.hip (the forward that keeps its activations, then the gradient
-// pass); g2048_ppo_grad.hip takes qb_linear_kernel from here for the PPO networks' fc2 and fc3. Device code, included by those
-// three files and nothing else; every kernel is per translation unit. What the phases are and
+// pass); g2048_ppo_grad.hip takes qb_linear_kernel from here for the PPO networks' fc2 and fc3, and g2048_qnet_train.hip (the training
+// library) instantiates the attention, proj_norm and linear kernels a second time with a QDrop (g2048_qnet_drop.h) as their trailing
+// argument: the reference's live dropout. The instantiations without one keep the parameter lists and the statements they had as
+// plain kernels. Device code, included by those four files and nothing else; every kernel is per translation unit. What the phases are and
 // why the weights are read from the plain buffer: the head of g2048_qnet_batch.hip. The outputs the gradient pass needs on top
 // (conv1's output, the attention rows' maximum and sum, the sums before the LayerNorms) are optional pointers that the forward
 // alone passes as null; they change no arithmetic.
@@ -10,6 +12,7 @@
 
 #include "../../include/g2048.h"
 #include "g2048_mfma.h"
+#include "g2048_qnet_drop.h"
 
 namespace {
 
@@ -128,10 +131,11 @@ __device__ inline f4 tile_product(const float *__restrict__ wrow, const float *_
 }
 
 // Y [n][M] = act(X [n][K] W^T + b): four wavefronts a block = four feature tiles of one board tile; grid (M / 64 up, board tiles).
-// KEEP_NAN: the ReLU passes a NaN on, as torch.relu does (the PPO update, whose NaN loss is its caller's signal).
-template <bool RELU, bool KEEP_NAN = false>
+// KEEP_NAN: the ReLU passes a NaN on, as torch.relu does (the PPO update, whose NaN loss is its caller's signal). With a QDrop
+// (the Q-network's training forward, site 2: the ReLU'd hidden layer) Y is multiplied by the site's m, element board M + feature.
+template <bool RELU, bool KEEP_NAN = false, class... MaybeDrop>
 __global__ __launch_bounds__(256) void qb_linear_kernel(const float *__restrict__ X, int K, const float *__restrict__ W,
-                                                         const float *__restrict__ bias, float *__restrict__ Y, int M, int n)
+                                                         const float *__restrict__ bias, float *__restrict__ Y, int M, int n, MaybeDrop... drop)
 {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4, col = lane & 15;
     const int o = (int)blockIdx.x * 4 + wave;
@@ -141,6 +145,11 @@ __global__ __launch_bounds__(256) void qb_linear_kernel(const float *__restrict_
     f4 acc = load_w(bias + 16 * o + 4 * g);
     acc = tile_product(W + (size_t)(16 * o + col) * K + 4 * g, X + (size_t)board * K + 4 * g, live, K, acc);
     if (RELU) acc = KEEP_NAN ? relu_nan(acc) : relu(acc);
+    if constexpr (sizeof...(MaybeDrop) != 0) {
+        const uint32_t e = (uint32_t)board * (uint32_t)M + (uint32_t)(16 * o + 4 * g);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acc[r] *= qdrop_mult(drop..., e + r);
+    }
     if (live) *reinterpret_cast<f4 *>(Y + (size_t)board * M + 16 * o + 4 * g) = acc;
 }
 
@@ -149,9 +158,12 @@ __global__ __launch_bounds__(256) void qb_linear_kernel(const float *__restrict_
 // lane (query col, g) holds the scores of keys 4 g .. 4 g + 3 of the tile for its query: the maximum and the sum over a tile's
 // keys are the toolkit's cross-lane reductions, and the probabilities are, as they stand, the B operand of P.V (A = V^T, lane
 // (feature col, g) reading V[key 4 g + r][col]). The next tile's K and V are loaded before this tile's arithmetic. max_out, sum_out
-// (optional, [query][head]): the row's final maximum and sum, from which the gradient pass recomputes the probabilities.
+// (optional, [query][head]): the row's final maximum and sum, from which the gradient pass recomputes the probabilities. With a
+// QDrop (the training forward, site 0) the probabilities are multiplied by the site's m before P.V, element (head n + query) n + key;
+// the row's maximum and sum are of the unmasked scores.
+template <class... MaybeDrop>
 __global__ __launch_bounds__(64) void qb_attention_kernel(const float *__restrict__ qkv, float *__restrict__ att, int n,
-                                                          float *__restrict__ max_out, float *__restrict__ sum_out)
+                                                          float *__restrict__ max_out, float *__restrict__ sum_out, MaybeDrop... drop)
 {
     const int lane = threadIdx.x, g = lane >> 4, col = lane & 15, head = blockIdx.y;
     const int query = (int)blockIdx.x * 16 + col;
@@ -190,6 +202,11 @@ __global__ __launch_bounds__(64) void qb_attention_kernel(const float *__restric
         for (int r = 0; r < 4; ++r) p[r] = expf(s[r] - mn);
         l = l * scale + lanes_sum((p[0] + p[1]) + (p[2] + p[3]));
         acc = acc * splat(scale);
+        if constexpr (sizeof...(MaybeDrop) != 0) {
+            const uint32_t e = ((uint32_t)head * (uint32_t)n + (uint32_t)query) * (uint32_t)n + (uint32_t)(16 * t + 4 * g);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) p[r] *= qdrop_mult(drop..., e + r);
+        }
 #pragma unroll
         for (int r = 0; r < 4; ++r) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(v[r], p[r], acc, 0, 0, 0);
         m = mn;
@@ -205,7 +222,8 @@ __global__ __launch_bounds__(64) void qb_attention_kernel(const float *__restric
 // x = LayerNorm(x + H W^T + b) for one tile of 16 boards; norm: weight[128] bias[128]; eps: one float on the device. With fc
 // (fc.weight [4][128], fc.bias [4]) Q = fc(x) goes to q_out. The residual rows are read from x, the normalised rows go to x_out
 // (which may be x: a row is read and written by its own block only; null: not stored) and the sum before the norm to pre_out
-// (optional; the gradient pass keeps it).
+// (optional; the gradient pass keeps it). With a QDrop (the training forward, sites 1 and 3: dropout1 / dropout2) H W^T + b is
+// multiplied by the site's m before the residual add, element board 128 + feature.
 constexpr int kTileStride = kD + 4;
 __device__ inline float half_sum(float v)            // over the 32 lanes of the wavefront's half, the same on all of them
 {
@@ -214,10 +232,11 @@ __device__ inline float half_sum(float v)            // over the 32 lanes of the
     return v;
 }
 
+template <class... MaybeDrop>
 __global__ __launch_bounds__(512) void qb_proj_norm_kernel(const float *__restrict__ H, int K, const float *__restrict__ W,
                                                            const float *__restrict__ bias, const float *__restrict__ norm,
                                                            const float *__restrict__ eps, const float *x, float *x_out, float *__restrict__ pre_out,
-                                                           const float *__restrict__ fc, float4 *__restrict__ q_out, int n)
+                                                           const float *__restrict__ fc, float4 *__restrict__ q_out, int n, MaybeDrop... drop)
 {
     __shared__ __attribute__((aligned(16))) float tile[16][kTileStride];
     const int lane = threadIdx.x & 63, o = threadIdx.x >> 6, g = lane >> 4, col = lane & 15;
@@ -226,6 +245,11 @@ __global__ __launch_bounds__(512) void qb_proj_norm_kernel(const float *__restri
         const bool live = board < n;
         f4 acc = load_w(bias + 16 * o + 4 * g);
         acc = tile_product(W + (size_t)(16 * o + col) * K + 4 * g, H + (size_t)board * K + 4 * g, live, K, acc);
+        if constexpr (sizeof...(MaybeDrop) != 0) {
+            const uint32_t e = (uint32_t)board * (uint32_t)kD + (uint32_t)(16 * o + 4 * g);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) acc[r] *= qdrop_mult(drop..., e + r);
+        }
         const f4 res = live ? load_f4(x + (size_t)board * kD + 16 * o + 4 * g) : splat(0.0f);
         *reinterpret_cast<f4 *>(&tile[col][16 * o + 4 * g]) = res + acc;
         if (pre_out && live) *reinterpret_cast<f4 *>(pre_out + (size_t)board * kD + 16 * o + 4 * g) = res + acc;

@@ -26,6 +26,8 @@ G2048_RNG_HD uint64_t splitmix64(uint64_t x)
 // RNG domain 11 (DESIGN.md "RNG"): the dropout masks of the PPO update's training-mode forwards (g2048_ppo_grad.hip, its only
 // user; the domains 1 .. 10 of the game kernels are the enum of g2048_board.h)
 constexpr uint32_t kDomDropout = 11;
+// RNG domain 12: the dropout masks of the Q-network's training-mode forwards (g2048_qnet_drop.h, g2048_qnet_train.hip)
+constexpr uint32_t kDomQnetDropout = 12;
 
 struct Keys { uint32_t k0, k1; };
 

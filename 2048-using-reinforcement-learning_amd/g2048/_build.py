@@ -1,10 +1,14 @@
-"""Builds csrc/libg2048_hip.so for gfx950 with hipcc (cross-compiles without a GPU).
+"""Builds csrc/libg2048_hip.so and csrc/libg2048_train_hip.so for gfx950 with hipcc (cross-compiles without a GPU).
 
     python -m g2048._build [-o LIBRARY] [extra compiler flags ...]           (from the package directory)
+    python -m g2048._build --train [-o LIBRARY] [extra compiler flags ...]   (the training library alone)
 
-The library is built in-tree so that it travels with the source snapshot; it is
+The libraries are built in-tree so that they travel with the source snapshot; they are
 git-ignored. -ffp-contract=off is REQUIRED: the reward / heuristic kernels follow
 the reference's f64 operation order (mul then add, never fma).
+
+libg2048_train_hip.so (include/g2048_train.h) holds the Q-network's training-mode entry points: the main library's export
+table is closed (ABI 5), so they live in a second library with the same flags and the same version script.
 """
 import os
 import shutil
@@ -12,11 +16,13 @@ import subprocess
 
 CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "csrc")
 LIB = os.environ.get("G2048_LIB") or os.path.join(CSRC, "libg2048_hip.so")     # G2048_LIB: A/B builds only (tools/)
+TRAIN_LIB = os.environ.get("G2048_TRAIN_LIB") or os.path.join(CSRC, "libg2048_train_hip.so")     # G2048_TRAIN_LIB: A/B builds only
 SOURCES = ["g2048_kernels.hip", "g2048_beam.hip", "g2048_rollout.hip", "g2048_policy.hip", "g2048_tpolicy.hip",
            "g2048_qnet.hip", "g2048_qnet_batch.hip", "g2048_qnet_grad.hip", "g2048_qnet_step.hip", "g2048_per.hip", "g2048_ppo_grad.hip",
            "g2048_ppo_step.hip"]
+TRAIN_SOURCES = ["g2048_qnet_train.hip"]
 INCLUDE = os.path.join(CSRC, "..", "..", "include")
-PUBLIC_HEADERS = [os.path.join(INCLUDE, "g2048.h"), os.path.join(INCLUDE, "g2048_testing.h")]
+PUBLIC_HEADERS = [os.path.join(INCLUDE, "g2048.h"), os.path.join(INCLUDE, "g2048_testing.h"), os.path.join(INCLUDE, "g2048_train.h")]
 # -fvisibility=hidden: the export table is exactly what the two headers declare with G2048_API (tests/test_abi_and_host.py)
 # -amdgpu-kernarg-preload-count: the first kernel-argument dwords arrive in SGPRs with the wavefront instead of through s_load +
 # s_waitcnt at its head (gfx950 takes up to 14 next to the kernarg pointer; the short kernels order their arguments for it:
@@ -26,31 +32,55 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp
          "-Wl,--version-script=" + os.path.join(CSRC, "g2048_exports.map"), "-Wall", "-Wno-unused-function"]
 
 
-def needs_build():
-    if not os.path.exists(LIB):
+def _stale(lib):
+    if not os.path.exists(lib):
         return True
-    t = os.path.getmtime(LIB)
-    # every file a source can include is a dependency: whatever lies in csrc/ (sources, headers, .inc) + the public header
+    t = os.path.getmtime(lib)
+    # every file a source can include is a dependency: whatever lies in csrc/ (sources, headers, .inc) + the public headers
     deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h", ".inc", ".hpp", ".map"))] + PUBLIC_HEADERS
     return any(os.path.exists(d) and os.path.getmtime(d) > t for d in deps)
 
 
-def build(force=False, verbose=False, lib=None, extra_flags=()):
-    """lib / extra_flags: A/B and measurement builds next to the product's (tools/build_ab.sh); such a build is always made."""
-    if lib is None and not force and not needs_build():
-        return LIB
+def needs_build():
+    return _stale(LIB) or _stale(TRAIN_LIB)
+
+
+def _compile(sources, out, extra_flags, verbose):
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    srcs = [os.path.join(CSRC, f) for f in SOURCES if os.path.exists(os.path.join(CSRC, f))]
-    cmd = [hipcc] + FLAGS + list(extra_flags) + ["-o", lib or LIB] + srcs
+    srcs = [os.path.join(CSRC, f) for f in sources if os.path.exists(os.path.join(CSRC, f))]
+    cmd = [hipcc] + FLAGS + list(extra_flags) + ["-o", out] + srcs
     if verbose:
         print(" ".join(cmd))
     subprocess.check_call(cmd)
-    return lib or LIB
+    return out
 
 
-if __name__ == "__main__":          # [-o LIBRARY] [extra compiler flags ...]
+def build(force=False, verbose=False, lib=None, extra_flags=()):
+    """Both product libraries, each only if it is stale. lib / extra_flags: an A/B or measurement build of the MAIN library next to
+    the product's (tools/build_ab.sh); such a build is always made, and the training library is left alone."""
+    if lib is not None:
+        return _compile(SOURCES, lib, extra_flags, verbose)
+    if force or _stale(LIB):
+        _compile(SOURCES, LIB, extra_flags, verbose)
+    if force or _stale(TRAIN_LIB):
+        _compile(TRAIN_SOURCES, TRAIN_LIB, extra_flags, verbose)
+    return LIB
+
+
+def build_train(lib=None, extra_flags=(), verbose=False):
+    """The training library alone, always made: the product's, or an A/B build at `lib` (loaded through G2048_TRAIN_LIB)."""
+    return _compile(TRAIN_SOURCES, lib or TRAIN_LIB, extra_flags, verbose)
+
+
+if __name__ == "__main__":          # [--train] [-o LIBRARY] [extra compiler flags ...]
     import sys
     out, args = None, sys.argv[1:]
+    train = args[:1] == ["--train"]
+    if train:
+        args = args[1:]
     if args[:1] == ["-o"]:
         out, args = args[1], args[2:]
-    print(build(force=True, verbose=True, lib=out, extra_flags=args))
+    if train:
+        print(build_train(lib=out, extra_flags=args, verbose=True))
+    else:
+        print(build(force=True, verbose=True, lib=out, extra_flags=args))

@@ -176,6 +176,64 @@ def check(rc):
         raise RuntimeError("g2048: %s (status %d)" % (lib().g2048_last_error().decode(), rc))
 
 
+# ---- the training library (include/g2048_train.h, csrc/libg2048_train_hip.so): its own table, loader, error string and version
+TRAIN_ABI_VERSION = 1
+_p4 = C.POINTER(C.c_double)
+TRAIN_SIGNATURES = {
+    "g2048_train_last_error": (C.c_char_p, []),
+    "g2048_train_abi_version": (_int, []),
+    "g2048_qnet_train_workspace": (_sz, [_sz, _int, _int]),
+    "g2048_qnet_forward_batch_dropout": (_int, [_vp, _vp, _vp, _sz, _int, _int, _p4, _u64, _u64, _vp, _vp]),
+    "g2048_qnet_loss_grad_dropout": (_int, [_vp] * 5 + [_sz, _int, _int, _p4, _u64, _u64] + [_vp] * 6),
+    "g2048_qnet_dropout_mask": (_int, [_u64, _u64, _int, _int, C.c_double, _sz, _int, _sz, _sz, _vp, _vp]),
+}
+_train_lib = None
+
+
+def train_library_path():
+    return _build.TRAIN_LIB
+
+
+def train_lib():
+    """The loaded training library. Raises if it has not been built (python __graft_entry__.py); as loud as lib()."""
+    global _train_lib
+    if _train_lib is None:
+        path = train_library_path()
+        if not os.path.exists(path):
+            raise RuntimeError("g2048: %s is missing -- build it with `python __graft_entry__.py` "
+                               "(hipcc --offload-arch=gfx950); there is no CPU fallback and no training pass without it" % path)
+        if os.environ.get("G2048_TRAIN_LIB"):      # A/B builds are only ever loaded on request, and say so
+            import sys
+            print("g2048: loading the A/B build %s (G2048_TRAIN_LIB is set)" % path, file=sys.stderr)
+        elif os.path.basename(path) != "libg2048_train_hip.so":
+            raise RuntimeError("g2048: refusing to load %s: only csrc/libg2048_train_hip.so is the product's training library" % path)
+        T = C.CDLL(path)
+        for name, (res, args) in TRAIN_SIGNATURES.items():
+            fn = getattr(T, name)   # AttributeError here = ABI mismatch, deliberately loud
+            fn.restype, fn.argtypes = res, args
+        if T.g2048_train_abi_version() != TRAIN_ABI_VERSION:
+            raise RuntimeError("g2048: training library ABI version mismatch (library %d, binding %d)"
+                               % (T.g2048_train_abi_version(), TRAIN_ABI_VERSION))
+        _train_lib = T
+    return _train_lib
+
+
+def train_check(rc):
+    if rc != OK:
+        raise RuntimeError("g2048: %s (status %d)" % (train_lib().g2048_train_last_error().decode(), rc))
+
+
+def train_call(device, fn, *args):
+    """call() for an entry point of the training library: its status is read from that library's own error string."""
+    idx = device.index if device.index is not None else torch.cuda.current_device()
+    if torch.cuda.current_device() == idx:
+        rc = fn(*args)
+    else:
+        with torch.cuda.device(idx):
+            rc = fn(*args)
+    train_check(rc)
+
+
 def stream_ptr(device):
     return torch.cuda.current_stream(device).cuda_stream
 

@@ -3,6 +3,8 @@
 Boards are torch.uint8 tensors of shape (n, 16) holding log2 codes (0 = empty), on a ROCm device.
 Every call is enqueued on torch's current stream of the boards' device and returns immediately.
 """
+import ctypes as C
+
 import torch
 
 from . import _lib as L
@@ -577,12 +579,79 @@ def qnet_batch_workspace_bytes(n, dim_ff):
     return nb
 
 
-def qnet_forward_batch(boards, plain, dim_ff, n_layers, q=None, workspace=None):
+QNET_DROPOUT_SITES = ("attention", "dropout1", "dropout", "dropout2")       # the order torch's training-mode layer draws in
+
+
+def qnet_dropout_p(dropout, name="dropout"):
+    """The four dropout probabilities of an encoder layer as the training library takes them, in the order of
+    QNET_DROPOUT_SITES: None or one probability for all four sites, or a 4-tuple; each finite, 0 <= p < 1. Returns None when
+    every site is off (the passes are then the main library's, bit for bit)."""
+    if dropout is None:
+        return None
+    if isinstance(dropout, (tuple, list)):
+        if len(dropout) != 4:
+            raise ValueError("g2048: %s must be a probability or a 4-tuple %s" % (name, QNET_DROPOUT_SITES))
+        p = tuple(float(v) for v in dropout)
+    else:
+        p = (float(dropout),) * 4
+    for v in p:
+        if not 0.0 <= v < 1.0:              # a NaN fails both comparisons
+            raise ValueError("g2048: %s must be finite, 0 <= p < 1 (got %r)" % (name, v))
+    return p if any(p) else None
+
+
+def _p4(p):
+    return (C.c_double * 4)(*p)
+
+
+def qnet_dropout_mask(n, layer, site, p, dim_ff=2048, seed=0, call_index=0, first_row=0, rows=None, device="cuda", out=None):
+    """The keep bits of rows [first_row, first_row + rows) of one dropout site of one call (g2048_qnet_dropout_mask), written
+    through the function the training passes draw them with: uint8 (rows, columns), 1 where the element is kept. The site's
+    matrix is (8 n, n) for site 0 (row = head n + query, column = key), (n, 128) for sites 1 and 3 and (n, dim_ff) for site 2;
+    rows None: down to the matrix's last row. Element e = row columns + column of site s of encoder layer `layer` is kept iff
+    rng_draw(rng_keys(seed, 12, call_index), ((4 layer + s) << 32) | e, 0) >= floor(p 2^32); a kept element is multiplied by
+    float32(1 / (1 - p)), a dropped one by 0. No synchronisation."""
+    n, layer, site, first_row = int(n), int(layer), int(site), int(first_row)
+    if site not in (0, 1, 2, 3):
+        raise ValueError("g2048: site must be 0 .. 3 %s" % (QNET_DROPOUT_SITES,))
+    if not 0 <= layer < 64:
+        raise ValueError("g2048: layer must be 0 .. 63")
+    p = float(p)
+    if not 0.0 <= p < 1.0:
+        raise ValueError("g2048: p must be finite, 0 <= p < 1 (got %r)" % p)
+    if not 0 <= n <= L.QNET_BATCH_MAX:
+        raise ValueError("g2048: a dropout mask is of 0 .. %d boards (the batch passes' limit); got n = %d" % (L.QNET_BATCH_MAX, n))
+    height, width = (8 * n, n) if site == 0 else (n, int(dim_ff) if site == 2 else 128)
+    rows = height - first_row if rows is None else int(rows)
+    if first_row < 0 or rows < 0 or first_row + rows > height:
+        raise ValueError("g2048: rows %d .. %d lie past the site's matrix of %d rows" % (first_row, first_row + rows, height))
+    dev = torch.device(device)
+    out = _output(out, rows, torch.uint8, (width,), "out", dev)
+    if n and rows:
+        L.train_call(out.device, L.train_lib().g2048_qnet_dropout_mask, L.u64(seed), L.u64(call_index), layer, site, p, n, int(dim_ff),
+                     first_row, rows, out.data_ptr(), L.stream_ptr(out.device))
+    return out
+
+
+def qnet_train_workspace_bytes(n, dim_ff, n_layers):
+    """Bytes of the workspace qnet_loss_grad needs for n boards with dropout (g2048_qnet_train_workspace)."""
+    nb = L.train_lib().g2048_qnet_train_workspace(int(n), int(dim_ff), int(n_layers))
+    if nb == 0:
+        raise ValueError("g2048: qnet_loss_grad takes 1 .. %d boards (they are one sequence; a larger batch is refused, not "
+                         "truncated), a dim_ff that is a multiple of 32 and 1 .. 64 layers (got n = %d, dim_ff = %d, n_layers = %d)"
+                         % (L.QNET_BATCH_MAX, int(n), int(dim_ff), int(n_layers)))
+    return nb
+
+
+def qnet_forward_batch(boards, plain, dim_ff, n_layers, q=None, workspace=None, dropout=None, seed=0, call_index=0):
     """The hybrid agent's Q-network on n boards as ONE call of the reference's module (g2048_qnet_forward_batch): the boards are
     one sequence of n tokens that attend to each other, as in DQNAgent.train_step. plain: the PLAIN float32 parameter buffer
     (qnet_plain_floats; qnet.flatten), read directly; f32 only. 2 + 5 n_layers launches on the current stream, no
     synchronisation. workspace: a uint8 device tensor of at least qnet_batch_workspace_bytes(n, dim_ff) (allocated when None).
-    Returns q float32 (n,4)."""
+    dropout: None, 0 or all zeros: the eval-mode function through the main library, as ever. A probability or a 4-tuple
+    (qnet_dropout_p): the module's TRAINING-mode call with the masks of (seed, call_index) (qnet_dropout_mask), through the
+    training library's g2048_qnet_forward_batch_dropout; same launches, same workspace. Returns q float32 (n,4)."""
+    p = qnet_dropout_p(dropout)
     L.require_device_tensor(boards, torch.uint8, (16,), "boards")
     L.require_device_tensor(plain, torch.float32, None, "plain")
     n, dev = boards.shape[0], boards.device
@@ -597,8 +666,12 @@ def qnet_forward_batch(boards, plain, dim_ff, n_layers, q=None, workspace=None):
     L.require_device_tensor(workspace, torch.uint8, None, "workspace")
     if workspace.numel() < nb:
         raise ValueError("g2048: workspace must hold at least %d bytes" % nb)
-    L.call(dev, L.lib().g2048_qnet_forward_batch, boards.data_ptr(), plain.data_ptr(), q.data_ptr(), n, int(dim_ff), int(n_layers),
-           workspace.data_ptr(), L.stream_ptr(dev))
+    if p is None:
+        L.call(dev, L.lib().g2048_qnet_forward_batch, boards.data_ptr(), plain.data_ptr(), q.data_ptr(), n, int(dim_ff), int(n_layers),
+               workspace.data_ptr(), L.stream_ptr(dev))
+    else:
+        L.train_call(dev, L.train_lib().g2048_qnet_forward_batch_dropout, boards.data_ptr(), plain.data_ptr(), q.data_ptr(), n, int(dim_ff),
+                     int(n_layers), _p4(p), L.u64(seed), L.u64(call_index), workspace.data_ptr(), L.stream_ptr(dev))
     return q
 
 
@@ -612,13 +685,18 @@ def qnet_grad_workspace_bytes(n, dim_ff, n_layers):
     return nb
 
 
-def qnet_loss_grad(boards, plain, actions, targets, weights, dim_ff, n_layers, grad=None, td=None, loss=None, q=None, workspace=None):
+def qnet_loss_grad(boards, plain, actions, targets, weights, dim_ff, n_layers, grad=None, td=None, loss=None, q=None, workspace=None,
+                   dropout=None, seed=0, call_index=0):
     """The gradient half of DQNAgent.train_step (agents/hybrid.py:1038, :1049-1055) on the device (g2048_qnet_loss_grad): q =
     the batch forward of qnet_forward_batch (the same bits), td = the Huber error of q[i, actions[i]] against targets[i], loss =
     mean(weights * td) and grad = d loss / d parameter in the layout of `plain` (the LayerNorm-eps slots 0), overwritten, never
     accumulated into. boards uint8 (n,16), actions int64 (n,), targets and weights float32 (n,), plain the PLAIN float32
-    parameter buffer. Eval mode (no dropout), f32 only. An action outside 0..3 is the caller's error (the kernel reads
-    actions & 3). No synchronisation. Returns (loss float32 (), td float32 (n,), q float32 (n,4), grad float32 (plain.numel(),))."""
+    parameter buffer. f32 only. An action outside 0..3 is the caller's error (the kernel reads actions & 3). dropout: None, 0
+    or all zeros: eval mode through the main library, as ever. A probability or a 4-tuple (qnet_dropout_p): the reference's
+    TRAINING-mode pass with the masks of (seed, call_index), regenerated in the backward (the training library's
+    g2048_qnet_loss_grad_dropout; the workspace is then qnet_train_workspace_bytes'). No synchronisation. Returns (loss float32 (),
+    td float32 (n,), q float32 (n,4), grad float32 (plain.numel(),))."""
+    p = qnet_dropout_p(dropout)
     L.require_device_tensor(boards, torch.uint8, (16,), "boards")
     L.require_device_tensor(plain, torch.float32, None, "plain")
     L.require_device_tensor(actions, torch.int64, (), "actions")
@@ -644,15 +722,20 @@ def qnet_loss_grad(boards, plain, actions, targets, weights, dim_ff, n_layers, g
         raise ValueError("g2048: loss must hold one float32")
     if n == 0:
         return loss, td, q, grad
-    nb = qnet_grad_workspace_bytes(n, dim_ff, n_layers)
+    nb = qnet_grad_workspace_bytes(n, dim_ff, n_layers) if p is None else qnet_train_workspace_bytes(n, dim_ff, n_layers)
     if workspace is None:
         workspace = torch.empty(nb, dtype=torch.uint8, device=dev)
     L.require_device_tensor(workspace, torch.uint8, None, "workspace")
     if workspace.numel() < nb:
         raise ValueError("g2048: workspace must hold at least %d bytes" % nb)
-    L.call(dev, L.lib().g2048_qnet_loss_grad, boards.data_ptr(), plain.data_ptr(), actions.data_ptr(), targets.data_ptr(),
-           weights.data_ptr(), n, int(dim_ff), int(n_layers), grad.data_ptr(), td.data_ptr(), loss.data_ptr(), q.data_ptr(),
-           workspace.data_ptr(), L.stream_ptr(dev))
+    if p is None:
+        L.call(dev, L.lib().g2048_qnet_loss_grad, boards.data_ptr(), plain.data_ptr(), actions.data_ptr(), targets.data_ptr(),
+               weights.data_ptr(), n, int(dim_ff), int(n_layers), grad.data_ptr(), td.data_ptr(), loss.data_ptr(), q.data_ptr(),
+               workspace.data_ptr(), L.stream_ptr(dev))
+    else:
+        L.train_call(dev, L.train_lib().g2048_qnet_loss_grad_dropout, boards.data_ptr(), plain.data_ptr(), actions.data_ptr(),
+                     targets.data_ptr(), weights.data_ptr(), n, int(dim_ff), int(n_layers), _p4(p), L.u64(seed), L.u64(call_index),
+                     grad.data_ptr(), td.data_ptr(), loss.data_ptr(), q.data_ptr(), workspace.data_ptr(), L.stream_ptr(dev))
     return loss, td, q, grad
 
 

@@ -18,8 +18,8 @@ forward, a Python int counted on the host: probs, values and loss_and_grad take 
 advantages two (states, then next states), so update(epochs=E) takes 2 + E. No forward is ever skipped (the NaN gate skips only
 the optimiser step), so the count needs nothing from the device. dropout_state() / set_dropout_state() carry (seed, index) through
 a checkpoint. The index is a launch scalar: a captured graph of update() replays the SAME masks on every replay. Out of scope:
-DevicePolicy and the rollout kernels are eval mode, as get_action uses the networks; the hybrid Q-network's eight dropout sites;
-bf16.
+DevicePolicy and the rollout kernels are eval mode, as get_action uses the networks; bf16. (The hybrid Q-network's eight dropout
+sites are DeviceQNetwork(dropout=...)'s, g2048/qnet.py.)
 
 Each network lives in three flat float32 buffers on the modules' device: `plain` (the parameters, layout of include/g2048.h =
 the module's named_parameters() order), `grad` (same layout, overwritten by loss_and_grad) and `running` (bn1.running_mean,

@@ -9,13 +9,25 @@ Per-board semantics. The reference's encoder layer is not batch_first and is fed
 boards is ONE sequence of B tokens that attend to each other; the reference only ever calls it with one board. Row i here is
 model(x[i:i+1]): every board is a sequence of one token, the attention softmax is exactly 1.0 and the attention block is
 out_proj(W_v x + b_v). Q, K, the head count and batch_first cannot influence that and are not constrained. The reference never
-calls .eval() (its dropout is live even in select_action); this is the eval-mode function.
+calls .eval() (its dropout is live even in select_action); acting here -- __call__, act, act_beam, the play kernels -- is the
+eval-mode function, dropout in select_action being an accident of the reference.
+
+Training. DQNAgent.train_step's three forwards (hybrid.py:1038, :1042, :1044) run nn.TransformerEncoderLayer's four dropout sites
+live, and so do the training forwards here when the network is built with `dropout`: DeviceQNetwork(model, dropout=0.1 | (p_attention,
+p_dropout1, p_dropout, p_dropout2) | "module", dropout_seed=s). loss_and_grad applies it, forward_batch(boards, training=True) and
+dqn_targets(..., training=True) apply it; forward_batch(boards) stays eval mode. The masks are counter-RNG draws (include/g2048_train.h;
+ops.qnet_dropout_mask writes a site's keep bits), regenerated in the backward pass instead of stored. `dropout_index` is the call
+index of the NEXT training forward, a Python int counted on the host (it counts with dropout 0 too); dropout_state() /
+set_dropout_state() carry (seed, index) through a checkpoint. The index is a launch scalar: a captured graph replays the SAME masks
+on every replay. sync_from copies weights only: give the online and the target network different seeds, as the reference's two
+modules draw independently; with the same seed and index their masks coincide. With dropout 0, the default, every call goes
+through the main library's entry points and gives the bits it always gave.
 
 The module is recognised by structure, not by attribute names: two Conv2d (1->32 and 32->64, kernel 2, stride 1, paddings 1 and
 0), exactly one nn.TransformerEncoder (post-norm ReLU layers, d_model 128, no final norm, dim_feedforward a multiple of 32) and,
 outside it, two Linears told apart by shape: 1024->128 (embedding) and 128->4 (fc). ReLU / Sequential containers around them are
-ignored. Anything else raises ValueError with the reason; a module in training mode is refused (dropout has no device
-counterpart).
+ignored. Anything else raises ValueError with the reason; a module in training mode is refused at construction and in
+refresh() (what the training forwards apply is the `dropout` argument's business, not the module's mode).
 """
 import torch
 import torch.nn.functional as F
@@ -126,6 +138,26 @@ def forward_batch_reference(p, boards, dtype=torch.float64):
         prob = torch.softmax(q @ k.transpose(1, 2) / (head ** 0.5), dim=-1)
         x = E.post_norm_tail(lay, x, (prob @ v).transpose(0, 1).reshape(n, D_MODEL), w)
     return x @ w(p.fc.weight).T + w(p.fc.bias)
+
+
+def dropout_of(p, dropout):
+    """The four dropout probabilities (attention, dropout1, dropout, dropout2) of DeviceQNetwork's `dropout` for the parsed module
+    p: a probability for all four sites, a 4-tuple, or "module" for the layers' own self_attn.dropout, dropout1.p, dropout.p and
+    dropout2.p, which must agree from layer to layer (the masks differ per layer, the probabilities are shared). Raises ValueError
+    for anything else and for a probability outside 0 <= p < 1."""
+    if isinstance(dropout, str):
+        if dropout != "module":
+            E._refuse(NAME, "dropout must be a probability, a 4-tuple %s or \"module\", got %r" % (ops.QNET_DROPOUT_SITES, dropout))
+        per_layer = [(float(lay.self_attn.dropout), float(lay.dropout1.p), float(lay.dropout.p), float(lay.dropout2.p)) for lay in p.layers]
+        for i, t in enumerate(per_layer):
+            if t != per_layer[0]:
+                E._refuse(NAME, "dropout=\"module\": encoder layer %d has dropout %s, layer 0 has %s; the device pass shares one set of "
+                                "probabilities among the layers" % (i, t, per_layer[0]))
+        dropout = per_layer[0]
+    try:
+        return ops.qnet_dropout_p(dropout) or (0.0, 0.0, 0.0, 0.0)
+    except (TypeError, ValueError) as e:
+        E._refuse(NAME, str(e)[7:] if str(e).startswith("g2048: ") else "dropout: " + str(e))
 
 
 def _check_loss_inputs(n, actions, targets, weights):
@@ -245,35 +277,65 @@ class DeviceQNetwork(E.PackedNet):
     refresh() re-flattens and re-packs the weights IN PLACE on the current stream (call it after an optimizer step; the module
     must be back in eval mode); after attach_params() the module IS the plain buffer and refresh() only packs.
     The learner's tail on the device: adamw_step(lr) (gradient clipping and AdamW over net.plain from net.grad) and
-    sync_from(other) (the target-network update)."""
+    sync_from(other) (the target-network update).
+    dropout, dropout_seed: what the TRAINING forwards apply (loss_and_grad, forward_batch(training=True)); the module docstring.
+    0.0, the default: none, through the entry points and with the bits of a network built without the argument."""
 
     name, parse = NAME, staticmethod(parse)
     plain_floats, packed_bytes, pack = map(staticmethod, (ops.qnet_plain_floats, ops.qnet_packed_bytes, ops.qnet_pack))
+
+    def __init__(self, model, precision="f32", dropout=0.0, dropout_seed=0):
+        self.dropout = dropout_of(parse(model), dropout)           # (attention, dropout1, dropout, dropout2)
+        self.dropout_seed, self.dropout_index = ops.L.u64(dropout_seed), 0
+        super().__init__(model, precision)
+
+    def dropout_state(self):
+        """(dropout_seed, dropout_index): with the weights, what reproduces the masks of every later training forward."""
+        return self.dropout_seed, self.dropout_index
+
+    def set_dropout_state(self, state):
+        seed, index = state
+        if int(index) < 0:
+            raise ValueError("%s: the dropout index must not be negative" % NAME)
+        self.dropout_seed, self.dropout_index = ops.L.u64(seed), int(index)
+
+    def _next_index(self):
+        index = self.dropout_index
+        self.dropout_index = index + 1
+        return index
 
     def __call__(self, boards):
         q, _ = self._out.get(self._out.rows(boards), _outputs)
         return ops.qnet_forward(boards, self.packed, self.dim_ff, self.n_layers, self.precision, q=q)
 
-    def forward_batch(self, boards):
-        """q float32 (N,4) of the module's own eval-mode BATCH call on uint8 (N,16) boards, as DQNAgent.train_step makes it
+    def forward_batch(self, boards, training=False):
+        """q float32 (N,4) of the module's own BATCH call on uint8 (N,16) boards, as DQNAgent.train_step makes it
         (hybrid.py:1038-1044): the N boards are one sequence of N tokens that attend to each other, so a row depends on every
         board of the call (g2048_qnet_forward_batch; 2 + 5 n_layers launches, no synchronisation). 1 <= N <= 4096. The weights
         are this network's plain buffer, so refresh() refreshes this path too. f32 only: the first layer's attention logits
         reach 1e9 and bf16 logits would pick keys at random. The output buffer and the workspace are the network's (one of each
-        per (N, stream))."""
+        per (N, stream)). training=False: eval mode. training=True: the reference's training-mode call, net.dropout applied with
+        the masks of (net.dropout_seed, net.dropout_index); the index then counts on (with dropout 0 too)."""
         if self.precision != "f32":
             raise ValueError("%s.forward_batch: precision 'bf16' is refused: the attention logits reach 1e9 on raw tile values, and "
                              "bf16 logits would pick keys at random; build the network with precision='f32'" % NAME)
         check_batch_layers(self.parsed)
         n = self._out.rows(boards)
+        if not training:
+            return ops.qnet_forward_batch(boards, self.plain, self.dim_ff, self.n_layers, q=self._out.get(n, _q_only),
+                                          workspace=self._out.get(n, self._batch_workspace))
         return ops.qnet_forward_batch(boards, self.plain, self.dim_ff, self.n_layers, q=self._out.get(n, _q_only),
-                                      workspace=self._out.get(n, self._batch_workspace))
+                                      workspace=self._out.get(n, self._batch_workspace), dropout=self.dropout, seed=self.dropout_seed,
+                                      call_index=self._next_index())
 
     def _batch_workspace(self, n, device):          # refuses n = 0 and n above the maximum
         return torch.empty(ops.qnet_batch_workspace_bytes(n, self.dim_ff), dtype=torch.uint8, device=device)
 
     def _grad_workspace(self, n, device):           # refuses n = 0 and n above the maximum
         return torch.empty(ops.qnet_grad_workspace_bytes(n, self.dim_ff, self.n_layers), dtype=torch.uint8, device=device)
+
+    def _train_workspace(self, n, device):          # loss_and_grad's with dropout: one more array
+        return torch.empty(ops.qnet_train_workspace_bytes(n, self.dim_ff, self.n_layers), dtype=torch.uint8, device=device)
 
     @property
     def grad(self):
@@ -288,8 +350,9 @@ class DeviceQNetwork(E.PackedNet):
         :1049-1055) on uint8 (N,16) boards, int64 (N,) actions, float32 (N,) targets and weights: q = forward_batch(boards) (the
         same bits), td = the Huber error of q[i, actions[i]] against targets[i], loss = mean(weights * td); net.grad is
         OVERWRITTEN with d loss / d parameter in the layout of net.plain (g2048_qnet_loss_grad: the forward with its activations
-        kept, then the backward, one phase per launch; no host synchronisation). Eval mode: the reference's live dropout is left
-        out. f32 only, for forward_batch's reason. An action outside 0..3 is the caller's error (the kernel reads actions & 3).
+        kept, then the backward, one phase per launch; no host synchronisation). This is a training forward: net.dropout is
+        applied with the masks of (net.dropout_seed, net.dropout_index), regenerated in the backward, and the index counts on;
+        with dropout 0 it is g2048_qnet_loss_grad's eval-mode pass, bit for bit. f32 only, for forward_batch's reason. An action outside 0..3 is the caller's error (the kernel reads actions & 3).
         The outputs and the workspace are the network's (one set per (N, stream))."""
         if self.precision != "f32":
             raise ValueError("%s.loss_and_grad: precision 'bf16' is refused: the attention logits reach 1e9 on raw tile values, and "
@@ -301,7 +364,8 @@ class DeviceQNetwork(E.PackedNet):
         n = self._out.rows(boards)
         loss, td, q = self._out.get(n, _loss_outputs)
         ops.qnet_loss_grad(boards, self.plain, actions, targets, weights, self.dim_ff, self.n_layers, grad=self.grad, td=td, loss=loss,
-                           q=q, workspace=self._out.get(n, self._grad_workspace))
+                           q=q, workspace=self._out.get(n, self._train_workspace if any(self.dropout) else self._grad_workspace),
+                           dropout=self.dropout, seed=self.dropout_seed, call_index=self._next_index())
         return loss, td, q
 
     def attach_grads(self):
@@ -405,7 +469,10 @@ class DeviceQNetwork(E.PackedNet):
     def sync_from(self, other):
         """The target-network update (DQNAgent.update_target_model, hybrid.py:811, :1073) without a state_dict round: ONE device
         copy of other.plain into net.plain, net.packed packed again at this network's own precision, and the module's
-        parameters loaded from net.plain unless attach_params() made them views of it. Raises ValueError when dim_ff,
+        parameters loaded from net.plain unless attach_params() made them views of it. Weights only: dropout, dropout_seed and
+        dropout_index stay this network's own. The two networks of a learner are built with different seeds, e.g.
+        DeviceQNetwork(online_model, dropout=p, dropout_seed=s) and DeviceQNetwork(target_model, dropout=p, dropout_seed=s + 1);
+        with the same seed and index their masks coincide. Raises ValueError when dim_ff,
         n_layers, the LayerNorm eps or the device differ."""
         if not isinstance(other, DeviceQNetwork):
             raise TypeError("%s.sync_from: expected a %s, got %s" % (NAME, NAME, type(other).__name__))
@@ -453,15 +520,16 @@ class DeviceQNetwork(E.PackedNet):
         return actions, q
 
 
-def dqn_targets(online, target, next_boards, shaped_rewards, dones, gamma=0.99):
+def dqn_targets(online, target, next_boards, shaped_rewards, dones, gamma=0.99, training=False):
     """The no-gradient block of DQNAgent.train_step (agents/hybrid.py:1041-1046) on the device: (targets float32 (N,),
     next_actions int64 (N,)) with next_actions = online.forward_batch(next_boards).argmax(1) (unmasked, first maximum), next_q
     = target.forward_batch(next_boards) at those actions and targets = shaped_rewards + (1 - dones) * gamma * next_q. online,
     target: DeviceQNetwork; next_boards uint8 (N,16); shaped_rewards, dones float32 (N,) as DeviceReplayBuffer.sample returns
     them. Three launch groups on the current stream, no host synchronisation; the outputs are buffers of `online` (one pair per
-    (N, stream))."""
-    q_online = online.forward_batch(next_boards)
-    q_target = target.forward_batch(next_boards)
+    (N, stream)). training=True: both forwards are training forwards, as the reference's are (neither module is ever put in eval
+    mode): each network applies its own dropout with its own seed and index."""
+    q_online = online.forward_batch(next_boards, training=training)
+    q_target = target.forward_batch(next_boards, training=training)
     targets, next_actions = online._out.get(next_boards.shape[0], _targets)
     return ops.dqn_targets(q_online, q_target, shaped_rewards, dones, gamma, targets=targets, next_actions=next_actions)
 

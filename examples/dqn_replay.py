@@ -2,7 +2,7 @@
 """The data side of the hybrid agent's training loop (reference agents/hybrid.py:955-1074) entirely on the GPU.
 
     python examples/dqn_replay.py [--envs 4096] [--steps 200] [--capacity 200000] [--batch 256] [--every 4] [--dim-ff 2048] [--train]
-                                  [--device-step]
+                                  [--device-step] [--dropout 0.1 | module]
 
 A VecGame2048 batch is played by DeviceQNetwork.act(epsilon=...) (DQNAgent.select_action); every step of every env is pushed
 into a g2048.DeviceReplayBuffer (PrioritizedReplayBuffer.push); every --every steps a batch is sampled -- sample(), the float32
@@ -17,7 +17,11 @@ Without --train there is no optimiser here and no claim about learning; the scri
 prioritised Huber loss and the backward pass on the device, the gradients landing in the views attach_grads() gave the module's
 parameters), then stock torch for the elementwise rest -- clip_grad_norm_ at 10, AdamW(lr 1e-3, weight_decay 1e-4),
 CosineAnnealingLR --, update_priorities(indices, td + 1e-5), online.refresh(), and the target network synchronised every 250
-training steps. Eval mode throughout: the reference's live dropout is left out. Still no claim about learning curves.
+training steps. Still no claim about learning curves.
+
+--train --dropout P (or --dropout module, the layers' own 0.1): the three forwards of train_step -- both networks' in dqn_targets and
+the one loss_and_grad keeps -- run the encoder layers' four dropout sites live, as the reference's do (it never calls .eval()); the
+online and the target network draw from different seeds. Acting stays eval mode. Without --dropout: eval mode throughout.
 
 --train --device-step keeps that tail on the device too: attach_params() makes both modules views of their plain buffers,
 online.adamw_step(g2048.cosine_lr(round)) is the clipping, the AdamW update and the re-pack in two launches plus the pack, and
@@ -45,9 +49,13 @@ ap.add_argument("--dim-ff", type=int, default=2048)
 ap.add_argument("--precision", choices=("f32", "bf16"), default="f32")
 ap.add_argument("--train", action="store_true", help="the full train_step: loss_and_grad, clip, AdamW, cosine schedule, target sync")
 ap.add_argument("--device-step", action="store_true", help="with --train: clipping, AdamW and the target sync on the device (adamw_step, sync_from)")
+ap.add_argument("--dropout", default="0", help="with --train: a probability for the encoder layers' four dropout sites in the training forwards, or 'module'")
 a = ap.parse_args()
 if a.device_step and not a.train:
     sys.exit("--device-step needs --train")
+dropout = a.dropout if a.dropout == "module" else float(a.dropout)
+if dropout != 0 and not a.train:
+    sys.exit("--dropout needs --train")
 if a.envs > a.capacity:
     sys.exit("--envs must not exceed --capacity: a push holds one transition per env")
 
@@ -65,8 +73,8 @@ class HybridDQN(nn.Module):             # the reference's layout (agents/hybrid.
 
 dev, seed, gamma = torch.device("cuda"), 1, 0.99
 torch.manual_seed(0)
-online = g2048.DeviceQNetwork(HybridDQN(a.dim_ff).to(dev).eval())
-target = g2048.DeviceQNetwork(HybridDQN(a.dim_ff).to(dev).eval())
+online = g2048.DeviceQNetwork(HybridDQN(a.dim_ff).to(dev).eval(), dropout=dropout, dropout_seed=seed)
+target = g2048.DeviceQNetwork(HybridDQN(a.dim_ff).to(dev).eval(), dropout=dropout, dropout_seed=seed + 1)     # its own masks
 actor = online if a.precision == "f32" else g2048.DeviceQNetwork(online.model, precision=a.precision)     # the same module
 env = g2048.VecGame2048(a.envs, device=dev, seed=seed)
 buf = g2048.DeviceReplayBuffer(a.capacity, alpha=0.6, device=dev, seed=seed)
@@ -96,7 +104,7 @@ def learn(round_index):
     beta = 0.4 + 0.6 * min(round_index / 1000.0, 1.0)
     (states, actions, rewards, next_states, dones), indices, weights, shaped = buf.sample(a.batch, beta=beta)
     boards, next_boards = buf.boards(indices)              # the same batch as uint8 codes, the form DeviceQNetwork reads
-    targets, _ = g2048.dqn_targets(online, target, next_boards, shaped, dones, gamma)
+    targets, _ = g2048.dqn_targets(online, target, next_boards, shaped, dones, gamma, training=a.train)
     if a.train:
         return train(round_index, boards, actions, targets, weights, indices)
     q = online.forward_batch(boards).gather(1, actions.unsqueeze(1)).squeeze(1)
@@ -155,5 +163,8 @@ print("%d envs x %d steps: %d transitions pushed in %.3f s = %.3g transitions/s,
 prio = buf.logical_priorities()
 print("buffer: %d of %d entries, priorities %.3g .. %.3g, last weighted Huber loss %s"
       % (len(buf), a.capacity, float(prio.min()), float(prio.max()), "%.4g" % float(loss) if loss is not None else "none"))
+if a.train:
+    print("dropout %s: %d training forwards of the online network, %d of the target network"
+          % (online.dropout, online.dropout_index, target.dropout_index))
 if last_norm is not None:
     print("device step: %d updates, last gradient norm before clipping %.4g" % (online.opt_step, float(last_norm)))

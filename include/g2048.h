@@ -795,7 +795,10 @@ G2048_API int g2048_dqn_targets(const float *q_online_next, const float *q_targe
 
 /* ---- the Q-network's loss and gradient pass (agents/hybrid.py:1038, :1049-1055) ------------------------------------------
  * The lines of train_step that need gradients, for the module of g2048_qnet_forward_batch (eval mode, f32, 8 heads, the n boards
- * ONE sequence). The reference runs them with its dropout live; that is left out, as everywhere in this library.
+ * ONE sequence). The reference runs them with its dropout live. These entry points are the eval-mode function; the same passes
+ * with the dropout are the training entry points of the second library (include/g2048_train.h: g2048_qnet_forward_batch_dropout,
+ * g2048_qnet_loss_grad_dropout), whose p = 0 is this function bit for bit. Acting (g2048_qnet_forward, g2048_qnet_select_actions, the
+ * play entry points) has no dropout in either library.
  *
  *   g2048_qnet_loss_grad   given boards (uint8 n x 16), actions (int64 [n]), targets and weights (float32 [n]):
  *         q_out (float32 n x 4)  = the bits of g2048_qnet_forward_batch on the same boards and weights;

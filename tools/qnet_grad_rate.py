@@ -5,6 +5,8 @@ torch on the same GPU.
     python3 tools/qnet_grad_rate.py --trace N [CALLS]     only CALLS (50) loss_and_grad calls at n = N, for a kernel trace:
         rocprofv3 --kernel-trace --stats --output-format csv -d OUT -- python3 tools/qnet_grad_rate.py --trace 256
         python3 tools/qnet_grad_rate.py --phases OUT      that trace as one line per phase (the kernels in launch order)
+    python3 tools/qnet_grad_rate.py --dropout             what the training library's live dropout costs (dropout_table below;
+                                                          profiles/r28_qnet_dropout_rate.txt keeps a run)
 
 The reference's shape (dim_ff 2048, 2 layers, torch's default init) at n = 64, 256 and 1,024 boards; 256 is the batch train_step
 uses. Versions, alternating within every round:
@@ -132,6 +134,112 @@ torch.manual_seed(0)
 model = QNet().to(dev).eval()
 net = DeviceQNetwork(model)
 model64 = copy.deepcopy(model).double()
+
+def dropout_table():
+    """--dropout: what the reference's live dropout costs (docs/LOG.md R28.1). At n = 256 and 4,096, the rows alternating within every
+    round, median of 7 rounds after 2 warm-up rounds; per row the device clock (an event pair round REPS calls) and the host clock (the
+    time the same REPS calls take to enqueue). Before timing, p = 0 through the training library is checked to give the main library's
+    bits."""
+    import ctypes as C
+    import time
+
+    import g2048
+    from g2048 import _lib as L
+    p1 = 0.1
+    target_model = QNet().to(dev).eval()
+    nets = {p: DeviceQNetwork(copy.deepcopy(model), dropout=p, dropout_seed=1) for p in (0.0, p1)}
+    targets_of = {p: DeviceQNetwork(copy.deepcopy(target_model), dropout=p, dropout_seed=2) for p in (0.0, p1)}
+    for d in (nets, targets_of):
+        for v in d.values():
+            v.attach_params()
+    single = {s: tuple(p1 if k == s else 0.0 for k in range(4)) for s in range(4)}
+    train = copy.deepcopy(model).train()
+    zeros = (C.c_double * 4)(0.0, 0.0, 0.0, 0.0)
+
+    def set_p(m, p):
+        for lay in m.transformer.layers:
+            lay.self_attn.dropout, lay.dropout1.p, lay.dropout.p, lay.dropout2.p = p, p, p, p
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        h0 = time.perf_counter()
+        e0.record()
+        for _ in range(REPS):
+            fn()
+        e1.record()
+        h1 = time.perf_counter()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) * 1e-3 / REPS, (h1 - h0) / REPS
+
+    print("# --dropout: dim_ff %d, %d layers, p = %g; %d calls per event pair; median of 7 rounds after 2 warm-up rounds, the rows alternating"
+          % (DIM_FF, LAYERS, p1, REPS))
+    print("%-7s %-56s %10s %22s %10s" % ("boards", "version", "device us", "[min - max] us", "host us"))
+    for n in (256, 4096):
+        boards = ops.synth_boards(n, seed=3, device=dev)
+        nxt = ops.synth_boards(n, seed=4, device=dev)
+        x = tile_values(boards)
+        a, t, w = inputs(model64, boards)
+        shaped, dones = torch.zeros(n, device=dev), torch.zeros(n, device=dev)
+        net0 = nets[0.0]
+        floats = net0.plain.numel()
+        grad, td, q, loss = (torch.empty(s, device=dev) for s in ((floats,), (n,), (n, 4), ()))
+        ws = torch.empty(ops.qnet_train_workspace_bytes(n, DIM_FF, LAYERS), dtype=torch.uint8, device=dev)
+
+        def main_lib():
+            ops.qnet_loss_grad(boards, net0.plain, a, t, w, DIM_FF, LAYERS, grad=grad, td=td, loss=loss, q=q, workspace=ws)
+
+        def train_lib_p0():
+            L.train_call(dev, L.train_lib().g2048_qnet_loss_grad_dropout, boards.data_ptr(), net0.plain.data_ptr(), a.data_ptr(), t.data_ptr(),
+                         w.data_ptr(), n, DIM_FF, LAYERS, zeros, 1, 2, grad.data_ptr(), td.data_ptr(), loss.data_ptr(), q.data_ptr(),
+                         ws.data_ptr(), L.stream_ptr(dev))
+
+        main_lib()
+        want = grad.clone()
+        train_lib_p0()
+        assert torch.equal(grad, want), "p = 0 through the training library does not give the main library's bits"
+
+        def site_row(p4):
+            return lambda: ops.qnet_loss_grad(boards, net0.plain, a, t, w, DIM_FF, LAYERS, grad=grad, td=td, loss=loss, q=q, workspace=ws,
+                                              dropout=p4, seed=1, call_index=2)
+
+        def torch_row(p):
+            def fn():
+                set_p(train, p)
+                torch_step(train, x, a, t, w)
+            return fn
+
+        def round_row(p):
+            online, target = nets[p], targets_of[p]
+
+            def fn():
+                tg, _ = g2048.dqn_targets(online, target, nxt, shaped, dones, 0.99, training=True)
+                online.loss_and_grad(boards, a, tg, w)
+                online.adamw_step(1e-4)
+            return fn
+
+        rows = ([("main library g2048_qnet_loss_grad", main_lib), ("training library, p = 0", train_lib_p0),
+                 ("training library, p = %g on all four sites" % p1, site_row((p1,) * 4))]
+                + [("training library, p = %g on site %d (%s) alone" % (p1, s, ops.QNET_DROPOUT_SITES[s]), site_row(single[s])) for s in range(4)]
+                + [("torch training-mode fwd+bwd, p = 0", torch_row(0.0)), ("torch training-mode fwd+bwd, p = %g" % p1, torch_row(p1)),
+                   ("round: targets + loss_and_grad + adamw_step, p = 0", round_row(0.0)),
+                   ("round: targets + loss_and_grad + adamw_step, p = %g" % p1, round_row(p1))])
+        times = {name: [] for name, _ in rows}
+        for r in range(9):
+            for name, fn in rows:
+                dt = timed(fn)
+                if r >= 2:
+                    times[name].append(dt)
+        for name, _ in rows:
+            devs, hosts = [d for d, _ in times[name]], [h for _, h in times[name]]
+            print("%-7d %-56s %10.1f %22s %10.1f" % (n, name, statistics.median(devs) * 1e6, "[%.1f - %.1f]" % (min(devs) * 1e6, max(devs) * 1e6),
+                                                    statistics.median(hosts) * 1e6))
+        train.zero_grad(set_to_none=True)
+
+
+if sys.argv[1:2] == ["--dropout"]:
+    dropout_table()
+    sys.exit(0)
 
 if sys.argv[1:2] == ["--trace"]:
     n, calls = int(sys.argv[2]), int(sys.argv[3]) if len(sys.argv) > 3 else 50
