@@ -1,7 +1,8 @@
 // g2048_grad_products.h -- the two general products of a gradient pass on the f32 matrix cores, shared by g2048_qnet_grad.hip
 // (the Q-network's backward) and g2048_ppo_grad.hip (the PPO actor's and critic's): the data gradient dX = dY . W and the
 // weight gradient dW = dY^T . X with db = sum dY, for row-major f32 operands as they lie in a plain parameter buffer and a
-// workspace. Device code, included by those two files and g2048_qnet_train.hip (through g2048_qnet_grad_bwd.h) and nothing else; every
+// workspace. Device code, included by those two files, g2048_qnet_train.hip (through g2048_qnet_grad_bwd.h) and g2048_tpolicy_grad.hip
+// (the transformer policy's backward over n boards) and nothing else; every
 // kernel is per translation unit. The rules are
 // g2048_qnet_grad.hip's: every output element is one wavefront's fixed-order accumulation, nothing past row n is read or written.
 #pragma once

@@ -37,6 +37,7 @@
 #include "g2048_grad_products.h"
 #include "g2048_host.h"
 #include "g2048_mfma.h"
+#include "g2048_ppo_head.h"
 #include "g2048_qnet_batch_fwd.h"
 #include "g2048_rng.h"
 
@@ -281,11 +282,6 @@ __device__ inline void fc4_row_dx(const float (&dz)[O], const float *__restrict_
     }
 }
 
-// torch.clamp and torch.min: a NaN operand gives NaN, where fminf / fmaxf return the operand that is none. Plain comparisons; for
-// finite operands (lo <= hi) the values are fminf(fmaxf(x, lo), hi) and fminf(a, b).
-__device__ inline float clamp_nan(float x, float lo, float hi) { return x < lo ? lo : x > hi ? hi : x; }
-__device__ inline float min_nan(float a, float b) { return (a < b || a != a) ? a : b; }
-
 // The actor's head, a thread a row: p = softmax(fc4 h3) to probs. With `actions` (the loss asked for):
 //   q = p / sum(p); l = log(clamp(q, eps, 1 - eps)), eps = 2^-23 (Categorical(probs=p) in f32); ratio = exp(l[a] - old);
 //   term = min(ratio A, clamp(ratio, 1 - clip, 1 + clip) A); ent = -sum l q; loss share = -term / n - ent_coef ent / n
@@ -304,40 +300,8 @@ __global__ __launch_bounds__(64) void pg_actor_head_kernel(const float *__restri
     probs[i] = p4;
     if (!actions) return;
     const float p[4] = {p4.x, p4.y, p4.z, p4.w};
-    const float eps = 1.1920928955078125e-07f, inv_n = 1.0f / (float)n;
-    const float s = ((p[0] + p[1]) + p[2]) + p[3];
-    const int a = (int)(actions[i] & 3);
-    float q[4], l[4], e = 0.0f;
-    bool open[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        q[j] = p[j] / s;
-        open[j] = q[j] >= eps && q[j] <= 1.0f - eps;
-        l[j] = logf(clamp_nan(q[j], eps, 1.0f - eps));
-        e += l[j] * q[j];
-    }
-    const float A = adv[i], ratio = expf(l[a] - old_log_probs[i]), lo = 1.0f - clip, hi = 1.0f + clip;
-    const float s1 = ratio * A, s2 = clamp_nan(ratio, lo, hi) * A;
-    term[i] = min_nan(s1, s2);
-    ent[i] = -e;
-    const float g1 = s1 < s2 ? 1.0f : s1 == s2 ? 0.5f : 0.0f, g2 = s2 < s1 ? 1.0f : s1 == s2 ? 0.5f : 0.0f;
-    const float dratio = -inv_n * (g1 * A + (ratio >= lo && ratio <= hi ? g2 * A : 0.0f));
-    const float dla = dratio * ratio, ce = ent_coef * inv_n;
-    float gq[4], gp[4], dz[4], dot = 0.0f;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const float dl = ce * q[j] + (j == a ? dla : 0.0f);                 // d loss / d l[j]: the entropy's l q, the taken action's ratio
-        gq[j] = ce * l[j] + (open[j] ? dl / q[j] : 0.0f);
-        dot += gq[j] * p[j];
-    }
-    float dot2 = 0.0f;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        gp[j] = gq[j] / s - dot / (s * s);
-        dot2 += gp[j] * p[j];
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) dz[j] = p[j] * (gp[j] - dot2);
+    float dz[4];
+    ppo_actor_row(p, (int)(actions[i] & 3), old_log_probs[i], adv[i], clip, ent_coef, 1.0f / (float)n, term[i], ent[i], dz);
     dz_out[i] = make_float4(dz[0], dz[1], dz[2], dz[3]);
     fc4_row_dx<4>(dz, W, hv, d3 + (size_t)i * kH3);
 }
@@ -353,48 +317,12 @@ __global__ __launch_bounds__(64) void pg_critic_head_kernel(const float *__restr
     fc4_row<1>(h3 + (size_t)i * kH3, W, hv, z);
     values[i] = z[0];
     if (!returns) return;
-    const float d = z[0] - returns[i];
-    term[i] = d * d;
-    const float dz[1] = {value_coef * (2.0f * d) / (float)n};
+    const float dz[1] = {ppo_critic_row(z[0], returns[i], value_coef, n, term[i])};
     dz_out[i] = dz[0];
     fc4_row_dx<1>(dz, W, hv, d3 + (size_t)i * kH3);
 }
 
-// One block's fixed-order sums: thread t adds its rows t, t + 256, .. in order, then a fixed tree over the 256 threads, for each
-// of K arrays of n floats, `stride` apart; the sums are left in red[k][0].
-template <int K>
-__device__ inline void block_sums(const float *__restrict__ terms, size_t stride, int n, float (&red)[K][256])
-{
-    const int t = threadIdx.x;
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        float v = 0.0f;
-        for (int i = t; i < n; i += 256) v += terms[k * stride + i];
-        red[k][t] = v;
-    }
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (t < s)
-#pragma unroll
-            for (int k = 0; k < K; ++k) red[k][t] += red[k][t + s];
-        __syncthreads();
-    }
-}
-
-// terms: the actor's min(..) [n], the critic's squared errors, the entropies. out = {loss, actor_loss, value_loss, entropy}
-__global__ __launch_bounds__(256) void pg_loss_kernel(const float *__restrict__ terms, size_t stride, float value_coef, float ent_coef,
-                                                       float *__restrict__ out, int n)
-{
-    __shared__ float red[3][256];
-    block_sums<3>(terms, stride, n, red);
-    if (threadIdx.x == 0) {
-        const float actor = -(red[0][0] / (float)n), value = red[1][0] / (float)n, entropy = red[2][0] / (float)n;
-        out[0] = actor + value_coef * value - ent_coef * entropy;
-        out[1] = actor;
-        out[2] = value;
-        out[3] = entropy;
-    }
-}
+// (the rows' terms to the four loss parts: block_sums and pg_loss_kernel, g2048_ppo_head.h)
 
 // ------------------------------------------------------------------------------------------------------- advantages --
 // ppo_agent.py:368-373 in one block of 256: thread t keeps its rows t, t + 256, .. (at most 16) in registers. The mean and the

@@ -41,24 +41,14 @@
 #include "g2048_mfma.h"
 #include "g2048_play.h"
 #include "g2048_rng.h"
+#include "g2048_tpolicy_layout.h"
 
 namespace {
 
 using namespace g2048;
 
 // ------------------------------------------------------------------------------------------------ shapes and layouts --
-constexpr int kD = 64, kHeads = 4, kTok = 16, kFc1 = 128, kFc2 = 64, kFlat = kTok * kD;
-
-// plain f32 layout (g2048_tpolicy_pack's input; include/g2048.h)
-constexpr int kPlainEmb = 0, kPlainLayer0 = 2 * kD;
-constexpr int kPlInW = 0, kPlInB = kPlInW + 3 * kD * kD, kPlOutW = kPlInB + 3 * kD, kPlOutB = kPlOutW + kD * kD, kPlW1 = kPlOutB + kD;
-__host__ __device__ constexpr int pl_b1(int ff) { return kPlW1 + ff * kD; }
-__host__ __device__ constexpr int pl_w2(int ff) { return pl_b1(ff) + ff; }
-__host__ __device__ constexpr int pl_b2(int ff) { return pl_w2(ff) + kD * ff; }
-__host__ __device__ constexpr int pl_norm(int ff) { return pl_b2(ff) + kD; }             // norm1.w norm1.b norm2.w norm2.b eps1 eps2
-__host__ __device__ constexpr int pl_layer(int ff) { return pl_norm(ff) + 4 * kD + 2; }
-constexpr int kPlFc1W = 0, kPlFc1B = kPlFc1W + kFc1 * kFlat, kPlFc2W = kPlFc1B + kFc1, kPlFc2B = kPlFc2W + kFc2 * kFc1,
-              kPlActW = kPlFc2B + kFc2, kPlActB = kPlActW + 4 * kD, kPlCriW = kPlActB + 4, kPlCriB = kPlCriW + kD, kPlTail = kPlCriB + 1;
+// the shapes (kD, kHeads, kTok, kFc1, kFc2, kFlat) and the plain f32 layout (kPl*, pl_*): g2048_tpolicy_layout.h
 
 // packed layout: per layer the fragments of in_proj (12 row tiles), out_proj (4), linear1 (dim_ff / 16), linear2 (4); then fc1
 // (8), fc2 (4), the head tile (1); then the f32 section. A matrix's fragments are ordered [row tile o][chunk c]; a chunk is 16

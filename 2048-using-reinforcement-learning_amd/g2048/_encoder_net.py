@@ -197,8 +197,10 @@ class OutputCache:
 
 class PackedNet:
     """Base of DeviceTransformerPolicy and DeviceQNetwork: the module parsed, its parameters flattened into `plain` and packed
-    into `packed` on its device, refresh() to redo both IN PLACE on the current stream, and the output buffers. A subclass gives
-    name and, as staticmethods, parse and ops' plain_floats, packed_bytes and pack of its network."""
+    into `packed` on its device, refresh() to redo both IN PLACE on the current stream, the output buffers, and the learner's side
+    of both networks: `grad` (a buffer laid out like `plain`, filled by the subclass's loss_and_grad), attach_grads() and
+    attach_params() (the module's gradients and parameters as views of the two buffers). A subclass gives name and, as
+    staticmethods, parse and ops' plain_floats, packed_bytes and pack of its network."""
 
     name = parse = plain_floats = packed_bytes = pack = None
 
@@ -219,5 +221,58 @@ class PackedNet:
     def refresh(self):
         if any(m.training for m in self.model.modules()):
             raise ValueError("%s.refresh: %s is in training mode; call .eval() first" % (self.name, type(self.model).__name__))
-        flatten(self.parsed, self.plain)
+        if not self.params_attached:
+            flatten(self.parsed, self.plain)
         self.pack(self.plain, self.dim_ff, self.n_layers, self.precision, out=self.packed)
+
+    # ---- the learner's side: a gradient buffer in plain's layout, and the module's parameters and gradients as views
+    @property
+    def grad(self):
+        """The gradient buffer loss_and_grad fills: float32 of plain.numel(), laid out like `plain` (allocated on first use)."""
+        g = self.__dict__.get("_grad")
+        if g is None:
+            g = self.__dict__["_grad"] = torch.zeros_like(self.plain)
+        return g
+
+    def attach_grads(self):
+        """Sets every parameter's .grad of the module to a view into net.grad, at the offsets of flatten: from then on
+        loss_and_grad, clip_grad_norm_(model.parameters(), ..), optimizer.step() and net.refresh() form a whole update with no
+        gradient copy. Keep the optimizer's zero_grad(set_to_none=False), or call attach_grads() again after it."""
+        o = 0
+        for t in self.parsed.plain_tensors():
+            if isinstance(t, torch.Tensor):
+                t.grad = self.grad[o:o + t.numel()].view(t.shape)
+                o += t.numel()
+            else:
+                o += 1
+        return self.grad
+
+    _attached = None        # attach_params(): (parameter, offset in floats) of the first and the last parameter
+
+    @property
+    def params_attached(self):
+        """True while the module's parameters are the views attach_params() made (the first and the last are looked at)."""
+        if self._attached is None:
+            return False
+        base = self.plain.data_ptr()
+        return all(t.data_ptr() == base + 4 * o for t, o in self._attached)
+
+    @torch.no_grad()
+    def attach_params(self):
+        """Rebinds the storage of every parameter of net.model to a view into net.plain, at the offsets of flatten (the
+        counterpart of attach_grads): from then on the module IS the plain buffer. load_state_dict and an optimizer write
+        through, a device-side update of net.plain needs no copy back into the module, and refresh() skips the re-flatten and only
+        packs. The parameters' current values are kept. model.to(...), .float() or anything else that gives the parameters
+        new storage undoes the attachment (refresh() then re-flattens again, as before); call attach_params() again after
+        it. Returns net.plain."""
+        flatten(self.parsed, self.plain)
+        pairs, o = [], 0
+        for t in self.parsed.plain_tensors():
+            if isinstance(t, torch.Tensor):
+                t.data = self.plain[o:o + t.numel()].view(t.shape)
+                pairs.append((t, o))
+                o += t.numel()
+            else:
+                o += 1
+        self._attached = (pairs[0], pairs[-1])
+        return self.plain

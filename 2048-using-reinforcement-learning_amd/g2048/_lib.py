@@ -234,6 +234,61 @@ def train_call(device, fn, *args):
     train_check(rc)
 
 
+# ---- the transformer policy's learner library (include/g2048_tlearn.h, csrc/libg2048_tlearn_hip.so): again its own table, loader,
+# error string and version
+TLEARN_ABI_VERSION = 1
+TLEARN_BATCH_MAX = 1024
+_f = C.c_float
+TLEARN_SIGNATURES = {
+    "g2048_tlearn_last_error": (C.c_char_p, []),
+    "g2048_tlearn_abi_version": (_int, []),
+    "g2048_tpolicy_grad_workspace": (_sz, [_sz, _int, _int]),
+    "g2048_tpolicy_loss_grad": (_int, [_vp] * 6 + [_sz, _int, _int, _f, _f, _f] + [_vp] * 5 + [_sz, _vp]),
+}
+_tlearn_lib = None
+
+
+def tlearn_library_path():
+    return _build.TLEARN_LIB
+
+
+def tlearn_lib():
+    """The loaded learner library of the transformer policy. Raises if it has not been built (python __graft_entry__.py); as loud
+    as train_lib()."""
+    global _tlearn_lib
+    if _tlearn_lib is None:
+        path = tlearn_library_path()
+        if not os.path.exists(path):
+            raise RuntimeError("g2048: %s is missing -- build it with `python __graft_entry__.py` "
+                               "(hipcc --offload-arch=gfx950); there is no CPU fallback and no gradient pass without it" % path)
+        if os.environ.get("G2048_TLEARN_LIB"):      # A/B builds are only ever loaded on request, and say so
+            import sys
+            print("g2048: loading the A/B build %s (G2048_TLEARN_LIB is set)" % path, file=sys.stderr)
+        elif os.path.basename(path) != "libg2048_tlearn_hip.so":
+            raise RuntimeError("g2048: refusing to load %s: only csrc/libg2048_tlearn_hip.so is the product's learner library" % path)
+        T = C.CDLL(path)
+        for name, (res, args) in TLEARN_SIGNATURES.items():
+            fn = getattr(T, name)   # AttributeError here = ABI mismatch, deliberately loud
+            fn.restype, fn.argtypes = res, args
+        if T.g2048_tlearn_abi_version() != TLEARN_ABI_VERSION:
+            raise RuntimeError("g2048: learner library ABI version mismatch (library %d, binding %d)"
+                               % (T.g2048_tlearn_abi_version(), TLEARN_ABI_VERSION))
+        _tlearn_lib = T
+    return _tlearn_lib
+
+
+def tlearn_call(device, fn, *args):
+    """call() for an entry point of the learner library: its status is read from that library's own error string."""
+    idx = device.index if device.index is not None else torch.cuda.current_device()
+    if torch.cuda.current_device() == idx:
+        rc = fn(*args)
+    else:
+        with torch.cuda.device(idx):
+            rc = fn(*args)
+    if rc != OK:
+        raise RuntimeError("g2048: %s (status %d)" % (tlearn_lib().g2048_tlearn_last_error().decode(), rc))
+
+
 def stream_ptr(device):
     return torch.cuda.current_stream(device).cuda_stream
 

@@ -542,6 +542,64 @@ def tpolicy_forward(boards, packed, dim_ff, n_layers, precision="f32", probs=Non
     return probs if value is None else (probs, value)
 
 
+def tpolicy_grad_workspace_bytes(n, dim_ff, n_layers):
+    """Bytes of the workspace tpolicy_loss_grad needs for n boards (g2048_tpolicy_grad_workspace, the learner library)."""
+    nb = L.tlearn_lib().g2048_tpolicy_grad_workspace(int(n), int(dim_ff), int(n_layers))
+    if nb == 0:
+        raise ValueError("g2048: tpolicy_loss_grad takes 1 .. %d boards (16 tokens each; a larger batch is refused, not truncated), a "
+                         "dim_ff that is a multiple of 32 and 1 .. 64 layers (got n = %d, dim_ff = %d, n_layers = %d)"
+                         % (L.TLEARN_BATCH_MAX, int(n), int(dim_ff), int(n_layers)))
+    return nb
+
+
+def tpolicy_loss_grad(boards, plain, actions, old_log_probs, advantages, returns, dim_ff, n_layers, clip_epsilon=0.3, value_coef=0.4,
+                      entropy_coef=0.05, grad=None, losses=None, probs=None, value=None, workspace=None):
+    """PPOAgent.update()'s loss (agents/ppo_agent.py:378-400) on the transformer policy's two heads and its gradient, on the device
+    (g2048_tpolicy_loss_grad, the learner library): probs, value = the eval-mode module on boards / 15; loss = actor + value_coef
+    value_loss - entropy_coef entropy with the clipped surrogate of exp(log probs[i, actions[i]] - old_log_probs[i]) against
+    advantages, the squared error of value against returns, and Categorical(probs)'s entropy; grad = d loss / d parameter in the
+    layout of `plain` (the LayerNorm-eps slots 0), overwritten, never accumulated into. boards uint8 (n,16), actions int64 (n,),
+    old_log_probs, advantages, returns float32 (n,), plain the PLAIN float32 parameter buffer (tpolicy_plain_floats). f32 only. An
+    action outside 0..3 is the caller's error (the kernel reads actions & 3). A sequence of launches on the current stream, no
+    synchronisation. Returns (losses float32 (4,) = loss, actor, value, entropy; probs float32 (n,4); value float32 (n,1); grad)."""
+    L.require_device_tensor(boards, torch.uint8, (16,), "boards")
+    L.require_device_tensor(plain, torch.float32, None, "plain")
+    L.require_device_tensor(actions, torch.int64, (), "actions")
+    for t, name in ((old_log_probs, "old_log_probs"), (advantages, "advantages"), (returns, "returns")):
+        L.require_device_tensor(t, torch.float32, (), name)
+    n, dev = boards.shape[0], boards.device
+    floats = tpolicy_plain_floats(dim_ff, n_layers)
+    if plain.dim() != 1 or plain.numel() != floats:
+        raise ValueError("g2048: plain must be a flat float32 tensor of %d parameters" % floats)
+    if not (actions.shape[0] == old_log_probs.shape[0] == advantages.shape[0] == returns.shape[0] == n):
+        raise ValueError("g2048: actions, old_log_probs, advantages and returns must have one entry per board")
+    if grad is None:
+        grad = torch.empty(floats, dtype=torch.float32, device=dev)
+    L.require_device_tensor(grad, torch.float32, None, "grad")
+    if grad.dim() != 1 or grad.numel() != floats:
+        raise ValueError("g2048: grad must be a flat float32 tensor of %d floats" % floats)
+    if losses is None:
+        losses = torch.empty(4, dtype=torch.float32, device=dev)
+    L.require_device_tensor(losses, torch.float32, None, "losses")
+    if losses.numel() != 4:
+        raise ValueError("g2048: losses must hold four float32")
+    probs = _output(probs, n, torch.float32, (4,), "probs", dev)
+    value = _output(value, n, torch.float32, (1,), "value", dev)
+    if n == 0:
+        return losses, probs, value, grad
+    nb = tpolicy_grad_workspace_bytes(n, dim_ff, n_layers)
+    if workspace is None:
+        workspace = torch.empty(nb, dtype=torch.uint8, device=dev)
+    L.require_device_tensor(workspace, torch.uint8, None, "workspace")
+    if workspace.numel() < nb:
+        raise ValueError("g2048: workspace must hold at least %d bytes" % nb)
+    L.tlearn_call(dev, L.tlearn_lib().g2048_tpolicy_loss_grad, boards.data_ptr(), plain.data_ptr(), actions.data_ptr(),
+                  old_log_probs.data_ptr(), advantages.data_ptr(), returns.data_ptr(), n, int(dim_ff), int(n_layers), float(clip_epsilon),
+                  float(value_coef), float(entropy_coef), grad.data_ptr(), losses.data_ptr(), probs.data_ptr(), value.data_ptr(),
+                  workspace.data_ptr(), workspace.numel(), L.stream_ptr(dev))
+    return losses, probs, value, grad
+
+
 def qnet_packed_bytes(precision="f32", dim_ff=2048, n_layers=2):
     """Bytes of the packed hybrid Q-network (g2048_qnet_packed_bytes)."""
     return _net_packed_bytes("qnet", precision, dim_ff, n_layers)

@@ -337,14 +337,6 @@ class DeviceQNetwork(E.PackedNet):
     def _train_workspace(self, n, device):          # loss_and_grad's with dropout: one more array
         return torch.empty(ops.qnet_train_workspace_bytes(n, self.dim_ff, self.n_layers), dtype=torch.uint8, device=device)
 
-    @property
-    def grad(self):
-        """The gradient buffer loss_and_grad fills: float32 of plain.numel(), laid out like `plain` (allocated on first use)."""
-        g = self.__dict__.get("_grad")
-        if g is None:
-            g = self.__dict__["_grad"] = torch.zeros_like(self.plain)
-        return g
-
     def loss_and_grad(self, boards, actions, targets, weights):
         """(loss float32 (), td_errors float32 (N,), q float32 (N,4)) of DQNAgent.train_step's gradient half (hybrid.py:1038,
         :1049-1055) on uint8 (N,16) boards, int64 (N,) actions, float32 (N,) targets and weights: q = forward_batch(boards) (the
@@ -368,19 +360,6 @@ class DeviceQNetwork(E.PackedNet):
                            dropout=self.dropout, seed=self.dropout_seed, call_index=self._next_index())
         return loss, td, q
 
-    def attach_grads(self):
-        """Sets every parameter's .grad of the module to a view into net.grad, at the offsets of flatten: from then on
-        loss_and_grad, clip_grad_norm_(model.parameters(), ..), optimizer.step() and net.refresh() form a whole update with no
-        gradient copy. Keep the optimizer's zero_grad(set_to_none=False), or call attach_grads() again after it."""
-        o = 0
-        for t in self.parsed.plain_tensors():
-            if isinstance(t, torch.Tensor):
-                t.grad = self.grad[o:o + t.numel()].view(t.shape)
-                o += t.numel()
-            else:
-                o += 1
-        return self.grad
-
     def _step_workspace(self, n, device):
         return torch.empty(ops.qnet_step_workspace_bytes(self.dim_ff, self.n_layers), dtype=torch.uint8, device=device)
 
@@ -401,43 +380,6 @@ class DeviceQNetwork(E.PackedNet):
         return self._moment("_exp_avg_sq")
 
     opt_step = 0            # the number of adamw_step calls so far
-    _attached = None        # attach_params(): (parameter, offset in floats) of the first and the last parameter
-
-    @property
-    def params_attached(self):
-        """True while the module's parameters are the views attach_params() made (the first and the last are looked at)."""
-        if self._attached is None:
-            return False
-        base = self.plain.data_ptr()
-        return all(t.data_ptr() == base + 4 * o for t, o in self._attached)
-
-    @torch.no_grad()
-    def attach_params(self):
-        """Rebinds the storage of every parameter of net.model to a view into net.plain, at the offsets of flatten (the
-        counterpart of attach_grads): from then on the module IS the plain buffer. load_state_dict and an optimizer write
-        through, adamw_step and sync_from need no copy back into the module, and refresh() skips the re-flatten and only
-        packs. The parameters' current values are kept. model.to(...), .float() or anything else that gives the parameters
-        new storage undoes the attachment (refresh() then re-flattens again, as before); call attach_params() again after
-        it. Returns net.plain."""
-        flatten(self.parsed, self.plain)
-        pairs, o = [], 0
-        for t in self.parsed.plain_tensors():
-            if isinstance(t, torch.Tensor):
-                t.data = self.plain[o:o + t.numel()].view(t.shape)
-                pairs.append((t, o))
-                o += t.numel()
-            else:
-                o += 1
-        self._attached = (pairs[0], pairs[-1])
-        return self.plain
-
-    def refresh(self):
-        if not self.params_attached:
-            return super().refresh()
-        if any(m.training for m in self.model.modules()):
-            raise ValueError("%s.refresh: %s is in training mode; call .eval() first" % (self.name, type(self.model).__name__))
-        self.pack(self.plain, self.dim_ff, self.n_layers, self.precision, out=self.packed)
-
     def _plain_changed(self):
         """After net.plain was written on the device: the packed blob, and the module unless it is the plain buffer."""
         self.pack(self.plain, self.dim_ff, self.n_layers, self.precision, out=self.packed)

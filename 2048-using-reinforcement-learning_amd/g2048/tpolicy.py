@@ -64,6 +64,75 @@ def forward_reference(p, boards, dtype=torch.float64, round_weights=None):
     return torch.softmax(h @ w(p.actor.weight).T + w(p.actor.bias), -1), h @ w(p.critic.weight).T + w(p.critic.bias)
 
 
+def _check_loss_inputs(n, actions, old_log_probs, advantages, returns):
+    for name, t, dtype in (("actions", actions, torch.int64), ("old_log_probs", old_log_probs, torch.float32),
+                           ("advantages", advantages, torch.float32), ("returns", returns, torch.float32)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("%s: %s must be a torch.Tensor" % (NAME, name))
+        if t.dtype != dtype:
+            raise TypeError("%s: %s must be %s (got %s)" % (NAME, name, dtype, t.dtype))
+        if tuple(t.shape) != (n,):
+            raise ValueError("%s: %s must have shape (%d,), one entry per board (got %s)" % (NAME, name, n, tuple(t.shape)))
+
+
+F32_EPS = float(torch.finfo(torch.float32).eps)
+
+
+def loss_grad_reference(p, boards, actions, old_log_probs, advantages, returns, clip_epsilon=0.3, value_coef=0.4, entropy_coef=0.05,
+                        dtype=torch.float64, eps=F32_EPS):
+    """PPOAgent.update()'s loss (agents/ppo_agent.py:378-400) on the parsed module's two heads, in eval mode, with plain torch ops
+    in `dtype` and autograd over the ops of forward_reference:
+        logp = log(probs[i, actions[i]]), ratio = exp(logp - old_log_probs),
+        actor = -mean(min(ratio adv, clamp(ratio, 1 - clip, 1 + clip) adv)), vloss = mean((value[:, 0] - returns)^2),
+        ent = mean(Categorical(probs).entropy()), loss = actor + value_coef vloss - entropy_coef ent.
+    Categorical(probs=probs) renormalises and clamps the probabilities to [eps, 1 - eps]; eps defaults to float32's, which is what
+    the float32 module and the kernel clamp at, whatever `dtype` is. Returns (losses (4,) = loss, actor, vloss, ent; probs (N,4);
+    value (N,1); grad: d loss / d parameter flat in the plain layout, the LayerNorm-eps slots 0). The yardstick of
+    g2048_tpolicy_loss_grad; the module's own .grad fields are not touched."""
+    n = boards.shape[0]
+    _check_loss_inputs(n, actions, old_log_probs, advantages, returns)
+    seq = p.plain_tensors()
+    params = [t for t in seq if isinstance(t, torch.Tensor)]
+    leaf = {id(t): t.detach().to(dtype).requires_grad_(True) for t in params}
+    w = lambda t: leaf[id(t)]       # noqa: E731
+    with torch.enable_grad():
+        x = boards.to(dtype) / 15
+        x = x.reshape(-1, TOKENS, 1) * w(p.embedding.weight).reshape(1, 1, -1) + w(p.embedding.bias)
+        for lay in p.layers:
+            a = lay.self_attn
+            qkv = x @ w(a.in_proj_weight).T + w(a.in_proj_bias)
+            q, k, v = (t.reshape(n, TOKENS, N_HEAD, -1).transpose(1, 2) for t in qkv.split(D_MODEL, -1))
+            s = torch.softmax((q @ k.transpose(-1, -2)) / 4, -1)
+            x = E.post_norm_tail(lay, x, (s @ v).transpose(1, 2).reshape(n, TOKENS, D_MODEL), w)
+        h = torch.relu(x.reshape(n, -1) @ w(p.fc1.weight).T + w(p.fc1.bias))
+        h = torch.relu(h @ w(p.fc2.weight).T + w(p.fc2.bias))
+        probs = torch.softmax(h @ w(p.actor.weight).T + w(p.actor.bias), -1)
+        value = h @ w(p.critic.weight).T + w(p.critic.bias)
+        qn = probs / probs.sum(-1, keepdim=True)
+        logits = torch.log(torch.clamp(qn, min=eps, max=1 - eps))
+        logp = logits.gather(-1, actions.unsqueeze(-1)).squeeze(-1)
+        ent = -(logits * qn).sum(-1).mean()
+        ratio = torch.exp(logp - old_log_probs.to(dtype))
+        adv = advantages.to(dtype)
+        actor = -torch.min(ratio * adv, torch.clamp(ratio, 1 - clip_epsilon, 1 + clip_epsilon) * adv).mean()
+        vloss = ((value[:, 0] - returns.to(dtype)) ** 2).mean()
+        loss = actor + value_coef * vloss - entropy_coef * ent
+        grads = dict(zip((id(t) for t in params), torch.autograd.grad(loss, [leaf[id(t)] for t in params])))
+    flat = torch.cat([grads[id(t)].reshape(-1) if isinstance(t, torch.Tensor) else torch.zeros(1, dtype=dtype, device=boards.device)
+                      for t in seq])
+    return torch.stack([loss, actor, vloss, ent]).detach(), probs.detach(), value.detach(), flat
+
+
+def _loss_outputs(n, device):       # losses, probs, value
+    return (torch.empty(4, dtype=torch.float32, device=device), torch.empty((n, 4), dtype=torch.float32, device=device),
+            torch.empty((n, 1), dtype=torch.float32, device=device))
+
+
+def _advantage_buffers(n, device):  # the two forwards' probabilities (not returned), value, next value, returns, advantages
+    return (torch.empty((n, 4), dtype=torch.float32, device=device),) + tuple(
+        torch.empty(shape, dtype=torch.float32, device=device) for shape in ((n, 1), (n, 1), (n,), (n,)))
+
+
 def _outputs(n, device):
     return torch.empty((n, 4), dtype=torch.float32, device=device), torch.empty((n, 1), dtype=torch.float32, device=device)
 
@@ -77,7 +146,9 @@ class DeviceTransformerPolicy(E.PackedNet):
     precision: "f32" (exact f32 MFMA, the parity path) or "bf16" (bf16 weights and matmul inputs, f32 accumulation, LayerNorm,
     softmax and attention products).
     refresh() re-flattens and re-packs the weights IN PLACE on the current stream (call it after an optimizer step; the module
-    must be back in eval mode): graphs captured earlier replay with the new weights.
+    must be back in eval mode): graphs captured earlier replay with the new weights. After attach_params() the module IS the
+    plain buffer and refresh() only packs.
+    loss_and_grad(...) fills net.grad; attach_grads() / attach_params() hand both buffers to a stock optimizer as views.
 
     takes_boards = True: RolloutCollector hands it the packed boards instead of the float observations."""
 
@@ -88,3 +159,49 @@ class DeviceTransformerPolicy(E.PackedNet):
     def __call__(self, boards):
         probs, value = self._out.get(self._out.rows(boards), _outputs)
         return ops.tpolicy_forward(boards, self.packed, self.dim_ff, self.n_layers, self.precision, probs=probs, value=value)
+
+    def _grad_workspace(self, n, device):           # refuses n = 0 and n above the maximum
+        return torch.empty(ops.tpolicy_grad_workspace_bytes(n, self.dim_ff, self.n_layers), dtype=torch.uint8, device=device)
+
+    def loss_and_grad(self, boards, actions, old_log_probs, advantages, returns, clip_epsilon=0.3, value_coef=0.4, entropy_coef=0.05):
+        """(losses float32 (4,) = loss, actor loss, value loss, entropy; probs float32 (N,4); value float32 (N,1)) of
+        PPOAgent.update()'s loss (agents/ppo_agent.py:378-400; the coefficients default to PPOAgent's) on uint8 (N,16) boards,
+        int64 (N,) actions and float32 (N,) old_log_probs, advantages and returns, the module in eval mode; net.grad is
+        OVERWRITTEN with d loss / d parameter in the layout of net.plain (g2048_tpolicy_loss_grad: the forward with its
+        activations kept, the loss head, the backward, one phase per launch; no host synchronisation). 1 <= N <= 1024. The pass
+        is f32 and reads net.plain, whatever precision the acting blob is packed in. An action outside 0..3 is the caller's
+        error (the kernel reads actions & 3). The outputs and the workspace are the network's (one set per (N, stream)): after
+        the first call per (N, stream) nothing is allocated."""
+        if not isinstance(boards, torch.Tensor) or boards.dim() != 2:
+            raise TypeError("%s.loss_and_grad: boards must be a uint8 (N,16) tensor" % NAME)
+        _check_loss_inputs(boards.shape[0], actions, old_log_probs, advantages, returns)
+        n = self._out.rows(boards)
+        if n > ops.L.TLEARN_BATCH_MAX:
+            raise ValueError("%s.loss_and_grad: takes at most %d boards a call (16,384 tokens), got %d; a larger batch is refused, not "
+                             "truncated" % (NAME, ops.L.TLEARN_BATCH_MAX, n))
+        losses, probs, value = self._out.get(n, _loss_outputs)
+        ops.tpolicy_loss_grad(boards, self.plain, actions, old_log_probs, advantages, returns, self.dim_ff, self.n_layers, clip_epsilon,
+                              value_coef, entropy_coef, grad=self.grad, losses=losses, probs=probs, value=value,
+                              workspace=self._out.get(n, self._grad_workspace) if n else None)
+        return losses, probs, value
+
+    def advantages(self, boards, next_boards, rewards, dones, gamma=0.995):
+        """(returns, advantages) float32 (N,) of PPOAgent.update()'s first block (agents/ppo_agent.py:357-373) with this network's
+        critic head: two f32 forwards (through a blob packed from net.plain at f32: the acting blob when precision is "f32"),
+        returns = rewards + gamma * value(next_boards) * (1 - dones), advantages = returns - value(boards), normalised by their
+        mean and unbiased std (+ 1e-8) when N > 1 (g2048_ppo_advantages). rewards, dones float32 (N,). The outputs are the
+        network's (one pair per (N, stream)); no synchronisation."""
+        n = self._out.rows(boards)
+        if self._out.rows(next_boards) != n:
+            raise ValueError("%s.advantages: boards and next_boards must have the same number of rows" % NAME)
+        packed = self.packed
+        if self.precision != "f32":
+            packed = self._out.get(0, self._f32_blob)
+            self.pack(self.plain, self.dim_ff, self.n_layers, "f32", out=packed)
+        probs, value, next_value, returns, adv = self._out.get(n, _advantage_buffers)
+        ops.tpolicy_forward(boards, packed, self.dim_ff, self.n_layers, "f32", probs=probs, value=value)
+        ops.tpolicy_forward(next_boards, packed, self.dim_ff, self.n_layers, "f32", probs=probs, value=next_value)
+        return ops.ppo_advantages(value, next_value, rewards, dones, gamma, returns=returns, advantages=adv)
+
+    def _f32_blob(self, n, device):
+        return torch.empty(self.packed_bytes("f32", self.dim_ff, self.n_layers), dtype=torch.uint8, device=device)

@@ -1,0 +1,74 @@
+#!/usr/bin/env python3
+"""A PPO update of the reference's transformer policy (models/transformer.py) with its loss and gradient pass on the GPU.
+
+    python examples/tpolicy_update.py [--envs 256] [--updates 5] [--epochs 3] [--dim-ff 2048] [--precision f32|bf16] [--lr 3e-4]
+
+A stock-torch module with the reference's layout, a VecGame2048 batch, one step of every env acted by
+g2048.DeviceTransformerPolicy (the probabilities of one g2048_tpolicy_forward launch, PPOAgent.get_action's masked sampling), then
+per update: net.advantages (agents/ppo_agent.py:357-373 with this network's critic head) and --epochs rounds of
+net.loss_and_grad (:378-400 on the two heads, eval mode: the forward with its activations kept, the loss head and the backward on
+the device, the gradients landing in the views attach_grads() gave the module's parameters), clip_grad_norm_ at 0.5, a stock
+torch.optim.Adam on the views attach_params() made of net.plain, and net.refresh() (which then only packs the acting blob again).
+No gradient copy and no host synchronisation inside an update; the loss parts are read back once per update, to print them.
+--envs is at most 1,024, the pass's limit. The script shows that the pieces fit; it makes no claim about learning.
+"""
+import argparse
+import os
+import sys
+
+import torch
+import torch.nn as nn
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "2048-using-reinforcement-learning_amd"))
+import g2048
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--envs", type=int, default=256)
+ap.add_argument("--updates", type=int, default=5)
+ap.add_argument("--epochs", type=int, default=3)
+ap.add_argument("--dim-ff", type=int, default=2048)
+ap.add_argument("--precision", choices=("f32", "bf16"), default="f32", help="of the acting blob; the gradient pass is f32 either way")
+ap.add_argument("--lr", type=float, default=3e-4)
+a = ap.parse_args()
+if not 1 <= a.envs <= 1024:
+    sys.exit("--envs must be 1 .. 1024: loss_and_grad takes at most 1,024 boards a call")
+
+
+class TransformerModel(nn.Module):      # the reference's layout (models/transformer.py:4-40), stock torch, default init
+    def __init__(self, dim_ff):
+        super().__init__()
+        self.embedding = nn.Linear(1, 64)
+        layer = nn.TransformerEncoderLayer(d_model=64, nhead=4, dim_feedforward=dim_ff, batch_first=True)
+        self.transformer_encoder = nn.TransformerEncoder(layer, num_layers=2)
+        self.fc1, self.fc2 = nn.Linear(1024, 128), nn.Linear(128, 64)
+        self.actor, self.critic = nn.Linear(64, 4), nn.Linear(64, 1)
+
+
+dev, seed = torch.device("cuda"), 1
+torch.manual_seed(0)
+net = g2048.DeviceTransformerPolicy(TransformerModel(a.dim_ff).to(dev).eval(), precision=a.precision)
+net.attach_params()                    # the module's parameters are views of net.plain from here on
+net.attach_grads()                     # and their .grad views of net.grad
+optimizer = torch.optim.Adam(net.model.parameters(), lr=a.lr)
+env = g2048.VecGame2048(a.envs, device=dev, seed=seed)
+gen = torch.Generator(device=dev).manual_seed(seed)
+
+for update in range(a.updates):
+    boards = env.boards.clone()
+    probs, _ = net(boards)
+    actions, old_log_probs = g2048.masked_sample(probs, g2048.ops.valid_moves(boards), generator=gen)
+    next_boards, reward, done, _ = env.step(actions)
+    next_boards, reward, dones = next_boards.clone(), reward.float().clone(), done.float()
+    returns, advantages = net.advantages(boards, next_boards, reward, dones)
+    actions = actions.to(torch.int64)
+    for epoch in range(a.epochs):
+        losses, _, _ = net.loss_and_grad(boards, actions, old_log_probs, advantages, returns)     # fills net.grad
+        torch.nn.utils.clip_grad_norm_(net.model.parameters(), max_norm=0.5)
+        optimizer.step()               # no zero_grad: the next call overwrites
+        net.refresh()                  # attached: packs the acting blob, nothing else
+    loss, actor, value, entropy = losses.tolist()
+    print("update %d: %d boards, last epoch's loss %.4f = actor %.4f + 0.4 x value %.4f - 0.05 x entropy %.4f; mean reward %.2f"
+          % (update, a.envs, loss, actor, value, entropy, float(reward.mean())))
+    fresh, _ = g2048.ops.reset(a.envs, seed, update + 1, 0, device=dev)
+    env.load(torch.where(done[:, None], fresh, env.boards), torch.where(done, torch.zeros_like(env.scores), env.scores))
+print("parameters attached: %s; %d floats of gradient in place" % (net.params_attached, net.grad.numel()))
