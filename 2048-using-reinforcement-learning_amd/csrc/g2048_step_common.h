@@ -1,7 +1,8 @@
 // g2048_step_common.h -- what the optimiser-step kernels share (g2048_qnet_step.hip: the Q-network's clipping and AdamW;
-// g2048_ppo_step.hip: the PPO networks' clipping and Adam): fixed-order f64 sums over a wavefront and over a block of 256
-// threads, the 16-byte groups of a flat f32 buffer with a short last group, and the host's reading of a float hyper-parameter as
-// the decimal its caller wrote. Included by those two files and nothing else.
+// g2048_ppo_step.hip: the PPO networks' clipping and Adam; g2048_tpolicy_step.hip: the transformer policy's, in
+// libg2048_tstep_hip.so): fixed-order f64 sums over a wavefront and over a block of 256 threads, the 16-byte groups of a flat f32
+// buffer with a short last group, and the host's reading of a float hyper-parameter as the decimal its caller wrote. Included by
+// those three files and nothing else.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -199,7 +199,8 @@ class PackedNet:
     """Base of DeviceTransformerPolicy and DeviceQNetwork: the module parsed, its parameters flattened into `plain` and packed
     into `packed` on its device, refresh() to redo both IN PLACE on the current stream, the output buffers, and the learner's side
     of both networks: `grad` (a buffer laid out like `plain`, filled by the subclass's loss_and_grad), attach_grads() and
-    attach_params() (the module's gradients and parameters as views of the two buffers). A subclass gives name and, as
+    attach_params() (the module's gradients and parameters as views of the two buffers), and the optimiser's moments `exp_avg` and
+    `exp_avg_sq` with _plain_changed() for the subclass's device step. A subclass gives name and, as
     staticmethods, parse and ops' plain_floats, packed_bytes and pack of its network."""
 
     name = parse = plain_floats = packed_bytes = pack = None
@@ -233,6 +234,29 @@ class PackedNet:
         if g is None:
             g = self.__dict__["_grad"] = torch.zeros_like(self.plain)
         return g
+
+    def _moment(self, key):
+        t = self.__dict__.get(key)
+        if t is None:
+            t = self.__dict__[key] = torch.zeros_like(self.plain)
+        return t
+
+    @property
+    def exp_avg(self):
+        """The optimiser's first moment of the subclass's device step: float32 of plain.numel(), laid out like `plain` (zeros,
+        allocated on first use)."""
+        return self._moment("_exp_avg")
+
+    @property
+    def exp_avg_sq(self):
+        """The optimiser's second moment, like exp_avg."""
+        return self._moment("_exp_avg_sq")
+
+    def _plain_changed(self):
+        """After net.plain was written on the device: the packed blob, and the module unless it is the plain buffer."""
+        self.pack(self.plain, self.dim_ff, self.n_layers, self.precision, out=self.packed)
+        if not self.params_attached:
+            unflatten(self.parsed, self.plain)
 
     def attach_grads(self):
         """Sets every parameter's .grad of the module to a view into net.grad, at the offsets of flatten: from then on

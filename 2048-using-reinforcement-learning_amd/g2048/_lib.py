@@ -289,6 +289,59 @@ def tlearn_call(device, fn, *args):
         raise RuntimeError("g2048: %s (status %d)" % (tlearn_lib().g2048_tlearn_last_error().decode(), rc))
 
 
+# ---- the transformer policy's optimiser-step library (include/g2048_tstep.h, csrc/libg2048_tstep_hip.so): the fourth table, loader,
+# error string and version
+TSTEP_ABI_VERSION = 1
+TSTEP_SIGNATURES = {
+    "g2048_tstep_last_error": (C.c_char_p, []),
+    "g2048_tstep_abi_version": (_int, []),
+    "g2048_tpolicy_step_workspace": (_sz, [_int, _int]),
+    "g2048_tpolicy_adam_step": (_int, [_vp] * 4 + [_int, _int, _vp, _vp] + [_f] * 5 + [_vp, _vp, _sz, _vp]),
+}
+_tstep_lib = None
+
+
+def tstep_library_path():
+    return _build.TSTEP_LIB
+
+
+def tstep_lib():
+    """The loaded optimiser-step library of the transformer policy. Raises if it has not been built (python __graft_entry__.py); as
+    loud as tlearn_lib()."""
+    global _tstep_lib
+    if _tstep_lib is None:
+        path = tstep_library_path()
+        if not os.path.exists(path):
+            raise RuntimeError("g2048: %s is missing -- build it with `python __graft_entry__.py` "
+                               "(hipcc --offload-arch=gfx950); there is no CPU fallback and no device optimiser step without it" % path)
+        if os.environ.get("G2048_TSTEP_LIB"):      # A/B builds are only ever loaded on request, and say so
+            import sys
+            print("g2048: loading the A/B build %s (G2048_TSTEP_LIB is set)" % path, file=sys.stderr)
+        elif os.path.basename(path) != "libg2048_tstep_hip.so":
+            raise RuntimeError("g2048: refusing to load %s: only csrc/libg2048_tstep_hip.so is the product's step library" % path)
+        T = C.CDLL(path)
+        for name, (res, args) in TSTEP_SIGNATURES.items():
+            fn = getattr(T, name)   # AttributeError here = ABI mismatch, deliberately loud
+            fn.restype, fn.argtypes = res, args
+        if T.g2048_tstep_abi_version() != TSTEP_ABI_VERSION:
+            raise RuntimeError("g2048: step library ABI version mismatch (library %d, binding %d)"
+                               % (T.g2048_tstep_abi_version(), TSTEP_ABI_VERSION))
+        _tstep_lib = T
+    return _tstep_lib
+
+
+def tstep_call(device, fn, *args):
+    """call() for an entry point of the step library: its status is read from that library's own error string."""
+    idx = device.index if device.index is not None else torch.cuda.current_device()
+    if torch.cuda.current_device() == idx:
+        rc = fn(*args)
+    else:
+        with torch.cuda.device(idx):
+            rc = fn(*args)
+    if rc != OK:
+        raise RuntimeError("g2048: %s (status %d)" % (tstep_lib().g2048_tstep_last_error().decode(), rc))
+
+
 def stream_ptr(device):
     return torch.cuda.current_stream(device).cuda_stream
 

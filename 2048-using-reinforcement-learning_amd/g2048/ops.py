@@ -600,6 +600,68 @@ def tpolicy_loss_grad(boards, plain, actions, old_log_probs, advantages, returns
     return losses, probs, value, grad
 
 
+def tpolicy_step_workspace_bytes(dim_ff, n_layers):
+    """Bytes of the workspace tpolicy_adam_step needs (g2048_tpolicy_step_workspace, the step library): one float64 per partial sum
+    of the norm and the scalars its second launch prepares."""
+    nb = L.tstep_lib().g2048_tpolicy_step_workspace(int(dim_ff), int(n_layers))
+    if nb == 0:
+        raise ValueError("g2048: tpolicy_adam_step takes a dim_ff that is a multiple of 32 and 1 .. 64 layers (got dim_ff = %d, "
+                         "n_layers = %d)" % (int(dim_ff), int(n_layers)))
+    return nb
+
+
+def tpolicy_adam_step(plain, grad, exp_avg, exp_avg_sq, dim_ff, n_layers, counters, losses=None, lr=3e-4, betas=(0.9, 0.999), eps=1e-8,
+                      max_norm=0.5, norm=None, workspace=None):
+    """What follows backward() in an epoch of PPOAgent.update (agents/ppo_agent.py:403-416) for the transformer policy in three
+    launches (g2048_tpolicy_adam_step, the step library): the NaN check on losses[0], clip_grad_norm_(max_norm) and an Adam step.
+    plain, grad, exp_avg and exp_avg_sq are flat float32 device tensors of tpolicy_plain_floats(dim_ff, n_layers) in the plain
+    layout, all updated IN PLACE (grad is left clipped); counters is int64 (3,) on the device = {steps applied, calls skipped for a
+    NaN loss, calls skipped for a gradient norm that is not finite}, and the bias correction's step number is taken from it ON THE
+    DEVICE. losses: tpolicy_loss_grad's float32 (4,) (or any float32 tensor whose first element is the loss), None: no loss gate.
+    max_norm None means no clipping. The LayerNorm-eps slots keep their bits in all four buffers. A NaN loss or a norm that is not
+    finite leaves all four buffers and the step counter untouched. No synchronisation. Returns the gradient norm before clipping,
+    float32, written on every call."""
+    floats = tpolicy_plain_floats(dim_ff, n_layers)
+    buffers = (("plain", plain), ("grad", grad), ("exp_avg", exp_avg), ("exp_avg_sq", exp_avg_sq))
+    for name, t in buffers:                 # dtype and length of all four before any device: such a mistake reads the same everywhere
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("g2048: %s must be a torch.Tensor" % name)
+        if t.dtype != torch.float32 or t.dim() != 1 or t.numel() != floats:
+            raise (TypeError if t.dtype != torch.float32 else ValueError)(
+                "g2048: %s must be a flat float32 tensor of %d floats (got %s %s)" % (name, floats, t.dtype, tuple(t.shape)))
+    for name, t in buffers:
+        L.require_device_tensor(t, torch.float32, None, name)
+        if t.device != plain.device:
+            raise ValueError("g2048: %s on %s, plain on %s" % (name, t.device, plain.device))
+    dev = plain.device
+    L.require_device_tensor(counters, torch.int64, None, "counters")
+    if counters.dim() != 1 or counters.numel() != 3:
+        raise ValueError("g2048: counters must be an int64 tensor of 3")
+    if losses is not None:
+        L.require_device_tensor(losses, torch.float32, None, "losses")
+        if losses.numel() < 1:
+            raise ValueError("g2048: losses must hold at least one float32")
+    if norm is None:
+        norm = torch.empty((), dtype=torch.float32, device=dev)
+    L.require_device_tensor(norm, torch.float32, None, "norm")
+    if norm.numel() != 1:
+        raise ValueError("g2048: norm must hold one float32")
+    nb = tpolicy_step_workspace_bytes(dim_ff, n_layers)
+    if workspace is None:
+        workspace = torch.empty(nb, dtype=torch.uint8, device=dev)
+    L.require_device_tensor(workspace, torch.uint8, None, "workspace")
+    if workspace.numel() < nb:
+        raise ValueError("g2048: workspace must hold at least %d bytes" % nb)
+    for t, name in ((counters, "counters"), (losses, "losses"), (norm, "norm"), (workspace, "workspace")):
+        if t is not None and t.device != dev:
+            raise ValueError("g2048: %s on %s, plain on %s" % (name, t.device, dev))
+    L.tstep_call(dev, L.tstep_lib().g2048_tpolicy_adam_step, plain.data_ptr(), grad.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(),
+                 int(dim_ff), int(n_layers), losses.data_ptr() if losses is not None else None, counters.data_ptr(), float(lr),
+                 float(betas[0]), float(betas[1]), float(eps), float("inf") if max_norm is None else float(max_norm), norm.data_ptr(),
+                 workspace.data_ptr(), workspace.numel(), L.stream_ptr(dev))
+    return norm
+
+
 def qnet_packed_bytes(precision="f32", dim_ff=2048, n_layers=2):
     """Bytes of the packed hybrid Q-network (g2048_qnet_packed_bytes)."""
     return _net_packed_bytes("qnet", precision, dim_ff, n_layers)

@@ -363,28 +363,7 @@ class DeviceQNetwork(E.PackedNet):
     def _step_workspace(self, n, device):
         return torch.empty(ops.qnet_step_workspace_bytes(self.dim_ff, self.n_layers), dtype=torch.uint8, device=device)
 
-    def _moment(self, key):
-        t = self.__dict__.get(key)
-        if t is None:
-            t = self.__dict__[key] = torch.zeros_like(self.plain)
-        return t
-
-    @property
-    def exp_avg(self):
-        """AdamW's first moment of adamw_step: float32 of plain.numel(), laid out like `plain` (zeros, allocated on first use)."""
-        return self._moment("_exp_avg")
-
-    @property
-    def exp_avg_sq(self):
-        """AdamW's second moment of adamw_step, like exp_avg."""
-        return self._moment("_exp_avg_sq")
-
     opt_step = 0            # the number of adamw_step calls so far
-    def _plain_changed(self):
-        """After net.plain was written on the device: the packed blob, and the module unless it is the plain buffer."""
-        self.pack(self.plain, self.dim_ff, self.n_layers, self.precision, out=self.packed)
-        if not self.params_attached:
-            unflatten(self.parsed, self.plain)
 
     def adamw_step(self, lr, max_norm=10.0, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-4, step=None):
         """clip_grad_norm_(max_norm) and AdamW.step() of DQNAgent.train_step (hybrid.py:1057-1058) on the device, after

@@ -133,6 +133,14 @@ def _advantage_buffers(n, device):  # the two forwards' probabilities (not retur
         torch.empty(shape, dtype=torch.float32, device=device) for shape in ((n, 1), (n, 1), (n,), (n,)))
 
 
+def _norm_out(n, device):           # adam_step's gradient norm
+    return torch.empty((), dtype=torch.float32, device=device)
+
+
+def _update_outputs(epochs, device):        # update()'s losses and norms, a row an epoch
+    return torch.empty((epochs, 4), dtype=torch.float32, device=device), torch.empty(epochs, dtype=torch.float32, device=device)
+
+
 def _outputs(n, device):
     return torch.empty((n, 4), dtype=torch.float32, device=device), torch.empty((n, 1), dtype=torch.float32, device=device)
 
@@ -149,6 +157,9 @@ class DeviceTransformerPolicy(E.PackedNet):
     must be back in eval mode): graphs captured earlier replay with the new weights. After attach_params() the module IS the
     plain buffer and refresh() only packs.
     loss_and_grad(...) fills net.grad; attach_grads() / attach_params() hand both buffers to a stock optimizer as views.
+    adam_step(losses) is the rest of a PPO epoch on the device (NaN gate, clipping, Adam: net.exp_avg, net.exp_avg_sq,
+    net.opt_counters), update(...) the whole of PPOAgent.update() after its sampling without a host read, and
+    optimizer_state_dict() / load_optimizer_state_dict() exchange the state with torch.optim.Adam(model.parameters()).
 
     takes_boards = True: RolloutCollector hands it the packed boards instead of the float observations."""
 
@@ -172,6 +183,9 @@ class DeviceTransformerPolicy(E.PackedNet):
         is f32 and reads net.plain, whatever precision the acting blob is packed in. An action outside 0..3 is the caller's
         error (the kernel reads actions & 3). The outputs and the workspace are the network's (one set per (N, stream)): after
         the first call per (N, stream) nothing is allocated."""
+        return self._loss_and_grad(boards, actions, old_log_probs, advantages, returns, clip_epsilon, value_coef, entropy_coef, None)
+
+    def _loss_and_grad(self, boards, actions, old_log_probs, advantages, returns, clip_epsilon, value_coef, entropy_coef, losses_row):
         if not isinstance(boards, torch.Tensor) or boards.dim() != 2:
             raise TypeError("%s.loss_and_grad: boards must be a uint8 (N,16) tensor" % NAME)
         _check_loss_inputs(boards.shape[0], actions, old_log_probs, advantages, returns)
@@ -180,6 +194,8 @@ class DeviceTransformerPolicy(E.PackedNet):
             raise ValueError("%s.loss_and_grad: takes at most %d boards a call (16,384 tokens), got %d; a larger batch is refused, not "
                              "truncated" % (NAME, ops.L.TLEARN_BATCH_MAX, n))
         losses, probs, value = self._out.get(n, _loss_outputs)
+        if losses_row is not None:              # update(): the epoch's row of its own losses tensor
+            losses = losses_row
         ops.tpolicy_loss_grad(boards, self.plain, actions, old_log_probs, advantages, returns, self.dim_ff, self.n_layers, clip_epsilon,
                               value_coef, entropy_coef, grad=self.grad, losses=losses, probs=probs, value=value,
                               workspace=self._out.get(n, self._grad_workspace) if n else None)
@@ -205,3 +221,133 @@ class DeviceTransformerPolicy(E.PackedNet):
 
     def _f32_blob(self, n, device):
         return torch.empty(self.packed_bytes("f32", self.dim_ff, self.n_layers), dtype=torch.uint8, device=device)
+
+    # ---- the optimiser's side: the NaN gate, clipping and Adam on the device (g2048_tpolicy_adam_step, the step library)
+    _hyper = (3e-4, (0.9, 0.999), 1e-8)     # the last adam_step's lr, betas, eps: optimizer_state_dict's group
+
+    @property
+    def opt_counters(self):
+        """int64 (3,) on the device: {Adam steps applied, calls skipped for a NaN loss, calls skipped for a gradient norm that is
+        not finite} (zeros, allocated on first use). opt_counters[0] is the step number of Adam's bias correction."""
+        c = self.__dict__.get("_opt_counters")
+        if c is None:
+            c = self.__dict__["_opt_counters"] = torch.zeros(3, dtype=torch.int64, device=self.device)
+        return c
+
+    def _step_workspace(self, n, device):
+        return torch.empty(ops.tpolicy_step_workspace_bytes(self.dim_ff, self.n_layers), dtype=torch.uint8, device=device)
+
+    def _adam_step(self, losses, lr, max_norm, betas, eps, norm):
+        ops.tpolicy_adam_step(self.plain, self.grad, self.exp_avg, self.exp_avg_sq, self.dim_ff, self.n_layers, self.opt_counters,
+                              losses=losses, lr=lr, betas=betas, eps=eps, max_norm=max_norm, norm=norm,
+                              workspace=self._out.get(0, self._step_workspace))
+        self._hyper = (lr, betas, eps)          # as given (tpolicy_adam_step accepted them); optimizer_state_dict reads them
+        return norm
+
+    def adam_step(self, losses=None, lr=3e-4, max_norm=0.5, betas=(0.9, 0.999), eps=1e-8):
+        """The end of an epoch of PPOAgent.update (agents/ppo_agent.py:403-416) on the device, after loss_and_grad: the NaN check
+        on losses[0] (losses: what loss_and_grad returned; None: no check), clip_grad_norm_(max_norm) and an Adam step, in three
+        launches (g2048_tpolicy_adam_step). net.plain is updated IN PLACE from net.grad (left clipped, as clip_grad_norm_ leaves
+        it), the moments are net.exp_avg and net.exp_avg_sq. max_norm None: no clipping. The reference never trains this model,
+        so lr has no reference value: 3e-4 is examples/tpolicy_update.py's default; max_norm, betas and eps are PPOAgent's. A NaN
+        loss, or a gradient norm that is not finite, skips the call: no buffer changes, and opt_counters[1] or [2] counts it;
+        otherwise opt_counters[0] goes up by one and is the step number of Adam's bias correction, read on the device (a skipped
+        call does not advance it). The LayerNorm-eps slots are settings and are not updated. Works for both precisions: the
+        pass and the step are f32 on net.plain. The call ends by packing net.plain into net.packed IN PLACE at the network's
+        precision (a forward captured earlier in a graph replays with the new weights) and loads the module's parameters from
+        net.plain unless attach_params() made them views of it. Returns the norm before clipping as a float32 () device tensor
+        (the network's own, one per stream; written on a skipped call too), without synchronising."""
+        norm = self._adam_step(losses, lr, max_norm, betas, eps, self._out.get(0, _norm_out))
+        self._plain_changed()
+        return norm
+
+    def update(self, boards, actions, old_log_probs, rewards, next_boards, dones, epochs=8, gamma=0.995, **adam):
+        """PPOAgent.update() after its sampling (agents/ppo_agent.py:357-416) for this network on the device: advantages(boards,
+        next_boards, rewards, dones, gamma), then `epochs` times loss_and_grad (PPOAgent's coefficients) and the step on that
+        epoch's losses (**adam: adam_step's lr, max_norm, betas, eps), then ONE pack of net.packed and one write-back of the
+        module. A sequence of launches with no host decision and no host read: an epoch whose loss is a NaN or whose gradient is
+        not finite is skipped on the device and shows in opt_counters and in the returned rows. Returns (losses float32
+        (epochs,4), norms float32 (epochs,)), device tensors the network owns (one pair per (epochs, stream)): row e is epoch e's
+        loss_and_grad result and its gradient norm before clipping."""
+        epochs = int(epochs)
+        if epochs < 1:
+            raise ValueError("%s: update needs at least one epoch" % NAME)
+        unknown = set(adam) - {"lr", "max_norm", "betas", "eps"}
+        if unknown:
+            raise TypeError("%s: update got unexpected arguments %s" % (NAME, sorted(unknown)))
+        adam = dict(dict(lr=3e-4, max_norm=0.5, betas=(0.9, 0.999), eps=1e-8), **adam)
+        returns, adv = self.advantages(boards, next_boards, rewards, dones, gamma)
+        losses, norms = self._out.get(epochs, _update_outputs)
+        for e in range(epochs):
+            self._loss_and_grad(boards, actions, old_log_probs, adv, returns, 0.3, 0.4, 0.05, losses[e])
+            self._adam_step(losses[e], adam["lr"], adam["max_norm"], adam["betas"], adam["eps"], norms[e])
+        self._plain_changed()
+        return losses, norms
+
+    def _param_offsets(self):
+        """[(parameter, offset in floats into net.plain)] in model.parameters() order: the module is recognised by structure, so
+        that order need not be the plain order; each parameter is found in the plain layout by identity."""
+        at, o = {}, 0
+        for t in self.parsed.plain_tensors():
+            if isinstance(t, torch.Tensor):
+                at[id(t)] = o
+                o += t.numel()
+            else:
+                o += 1
+        params = list(self.model.parameters())
+        if len(params) != len(at) or any(id(p) not in at for p in params):
+            raise ValueError("%s: model.parameters() are not the %d tensors of the plain layout" % (NAME, len(at)))
+        return [(p, at[id(p)]) for p in params]
+
+    def optimizer_state_dict(self):
+        """The state of adam_step's Adam in the format torch.optim.Adam(model.parameters()).state_dict() has: an entry per
+        parameter in model.parameters() order, each {step, exp_avg, exp_avg_sq} (copies, shaped like the parameter; step is
+        opt_counters' applied-step count), and one parameter group holding the last adam_step's lr, betas and eps (adam_step's
+        defaults before the first call). Before the first applied step the state is empty, as a fresh optimiser's is. A stock
+        optimiser's load_state_dict takes it as it is. Synchronises (it reads the counter)."""
+        lr, betas, eps = self._hyper
+        group = torch.optim.Adam([torch.nn.Parameter(torch.zeros(()))], lr=float(lr), betas=(float(betas[0]), float(betas[1])),
+                                 eps=float(eps)).state_dict()["param_groups"][0]
+        pairs = self._param_offsets()
+        group["params"] = list(range(len(pairs)))
+        step, state = int(self.opt_counters[0]), {}
+        if step > 0:
+            for i, (p, o) in enumerate(pairs):
+                state[i] = dict(step=torch.tensor(float(step)), exp_avg=self.exp_avg[o:o + p.numel()].view(p.shape).clone(),
+                                exp_avg_sq=self.exp_avg_sq[o:o + p.numel()].view(p.shape).clone())
+        return dict(state=state, param_groups=[group])
+
+    @torch.no_grad()
+    def load_optimizer_state_dict(self, state_dict):
+        """Takes what torch.optim.Adam(model.parameters()).state_dict() (or optimizer_state_dict) gave: the moments into exp_avg
+        and exp_avg_sq at each parameter's place in the plain layout, the step into opt_counters[0] (the skip counts stay). An
+        empty state resets moments and step to 0. The group's lr, betas and eps are NOT taken: they are adam_step's arguments.
+        amsgrad, maximize and a weight decay are refused: adam_step is plain Adam. The LayerNorm-eps slots of the moments are not
+        written."""
+        pairs = self._param_offsets()
+        groups, state = state_dict["param_groups"], state_dict["state"]
+        if len(groups) != 1 or len(groups[0]["params"]) != len(pairs):
+            raise ValueError("%s: expected one parameter group of %d parameters (torch.optim.Adam(model.parameters()))" % (NAME, len(pairs)))
+        g = groups[0]
+        if g.get("amsgrad") or g.get("maximize") or g.get("weight_decay", 0) != 0:
+            raise ValueError("%s: amsgrad, maximize and weight_decay are not what adam_step computes" % NAME)
+        if not state:
+            self.exp_avg.zero_()
+            self.exp_avg_sq.zero_()
+            self.opt_counters[0] = 0
+            return
+        keys = list(g["params"])
+        if set(state) != set(keys):
+            raise ValueError("%s: the state must hold all %d parameters or none" % (NAME, len(keys)))
+        steps = {int(state[key]["step"]) for key in keys}
+        if len(steps) != 1 or min(steps) < 0:
+            raise ValueError("%s: the parameters' step counts differ or are negative: %s" % (NAME, sorted(steps)))
+        for key, (p, _) in zip(keys, pairs):
+            for name in ("exp_avg", "exp_avg_sq"):
+                if tuple(state[key][name].shape) != tuple(p.shape):
+                    raise ValueError("%s: %s of parameter %s has shape %s, the parameter %s"
+                                     % (NAME, name, key, tuple(state[key][name].shape), tuple(p.shape)))
+        for key, (p, o) in zip(keys, pairs):
+            self.exp_avg[o:o + p.numel()].copy_(state[key]["exp_avg"].reshape(-1))
+            self.exp_avg_sq[o:o + p.numel()].copy_(state[key]["exp_avg_sq"].reshape(-1))
+        self.opt_counters[0] = steps.pop()

@@ -1,11 +1,15 @@
 #!/usr/bin/env python3
-"""A PPO update of the reference's transformer policy (models/transformer.py) with its loss and gradient pass on the GPU.
+"""A PPO update of the reference's transformer policy (models/transformer.py) with its loss, gradients and optimiser on the GPU.
 
     python examples/tpolicy_update.py [--envs 256] [--updates 5] [--epochs 3] [--dim-ff 2048] [--precision f32|bf16] [--lr 3e-4]
+                                      [--optimizer device|torch]
 
 A stock-torch module with the reference's layout, a VecGame2048 batch, one step of every env acted by
 g2048.DeviceTransformerPolicy (the probabilities of one g2048_tpolicy_forward launch, PPOAgent.get_action's masked sampling), then
-per update: net.advantages (agents/ppo_agent.py:357-373 with this network's critic head) and --epochs rounds of
+per update, with --optimizer device (the default): ONE net.update() call, which is net.advantages, --epochs rounds of
+net.loss_and_grad and the device's NaN gate, clipping at 0.5 and Adam step on net.plain (g2048_tpolicy_adam_step), and one pack of
+the acting blob at the end; a skipped epoch shows in net.opt_counters. With --optimizer torch the same update from its pieces and
+stock torch: net.advantages (agents/ppo_agent.py:357-373 with this network's critic head) and --epochs rounds of
 net.loss_and_grad (:378-400 on the two heads, eval mode: the forward with its activations kept, the loss head and the backward on
 the device, the gradients landing in the views attach_grads() gave the module's parameters), clip_grad_norm_ at 0.5, a stock
 torch.optim.Adam on the views attach_params() made of net.plain, and net.refresh() (which then only packs the acting blob again).
@@ -29,6 +33,8 @@ ap.add_argument("--epochs", type=int, default=3)
 ap.add_argument("--dim-ff", type=int, default=2048)
 ap.add_argument("--precision", choices=("f32", "bf16"), default="f32", help="of the acting blob; the gradient pass is f32 either way")
 ap.add_argument("--lr", type=float, default=3e-4)
+ap.add_argument("--optimizer", choices=("device", "torch"), default="device",
+                help="device: net.update(), clipping and Adam in the library; torch: clip_grad_norm_ and torch.optim.Adam on attached views")
 a = ap.parse_args()
 if not 1 <= a.envs <= 1024:
     sys.exit("--envs must be 1 .. 1024: loss_and_grad takes at most 1,024 boards a call")
@@ -48,8 +54,9 @@ dev, seed = torch.device("cuda"), 1
 torch.manual_seed(0)
 net = g2048.DeviceTransformerPolicy(TransformerModel(a.dim_ff).to(dev).eval(), precision=a.precision)
 net.attach_params()                    # the module's parameters are views of net.plain from here on
-net.attach_grads()                     # and their .grad views of net.grad
-optimizer = torch.optim.Adam(net.model.parameters(), lr=a.lr)
+if a.optimizer == "torch":
+    net.attach_grads()                 # and their .grad views of net.grad
+    optimizer = torch.optim.Adam(net.model.parameters(), lr=a.lr)
 env = g2048.VecGame2048(a.envs, device=dev, seed=seed)
 gen = torch.Generator(device=dev).manual_seed(seed)
 
@@ -59,16 +66,23 @@ for update in range(a.updates):
     actions, old_log_probs = g2048.masked_sample(probs, g2048.ops.valid_moves(boards), generator=gen)
     next_boards, reward, done, _ = env.step(actions)
     next_boards, reward, dones = next_boards.clone(), reward.float().clone(), done.float()
-    returns, advantages = net.advantages(boards, next_boards, reward, dones)
     actions = actions.to(torch.int64)
-    for epoch in range(a.epochs):
-        losses, _, _ = net.loss_and_grad(boards, actions, old_log_probs, advantages, returns)     # fills net.grad
-        torch.nn.utils.clip_grad_norm_(net.model.parameters(), max_norm=0.5)
-        optimizer.step()               # no zero_grad: the next call overwrites
-        net.refresh()                  # attached: packs the acting blob, nothing else
+    if a.optimizer == "device":
+        rows, _ = net.update(boards, actions, old_log_probs, reward, next_boards, dones, epochs=a.epochs, lr=a.lr)
+        losses = rows[-1]
+    else:
+        returns, advantages = net.advantages(boards, next_boards, reward, dones)
+        for epoch in range(a.epochs):
+            losses, _, _ = net.loss_and_grad(boards, actions, old_log_probs, advantages, returns)     # fills net.grad
+            torch.nn.utils.clip_grad_norm_(net.model.parameters(), max_norm=0.5)
+            optimizer.step()           # no zero_grad: the next call overwrites
+            net.refresh()              # attached: packs the acting blob, nothing else
     loss, actor, value, entropy = losses.tolist()
     print("update %d: %d boards, last epoch's loss %.4f = actor %.4f + 0.4 x value %.4f - 0.05 x entropy %.4f; mean reward %.2f"
           % (update, a.envs, loss, actor, value, entropy, float(reward.mean())))
     fresh, _ = g2048.ops.reset(a.envs, seed, update + 1, 0, device=dev)
     env.load(torch.where(done[:, None], fresh, env.boards), torch.where(done, torch.zeros_like(env.scores), env.scores))
 print("parameters attached: %s; %d floats of gradient in place" % (net.params_attached, net.grad.numel()))
+if a.optimizer == "device":
+    print("device optimizer: %d Adam steps applied, %d epochs skipped for a NaN loss, %d for a gradient that is not finite"
+          % tuple(net.opt_counters.tolist()))
