@@ -2,20 +2,18 @@
 // critic together, on the device: the NaN check on the loss, clip_grad_norm_ per network and an Adam step per network over the two
 // PLAIN parameter buffers (include/g2048.h) and the gradient buffers g2048_ppo_loss_grad fills. C-ABI: g2048_ppo_adam_step /
 // g2048_ppo_step_workspace. Two launches, no host synchronisation and no host decision:
-//   prepare  ONE block of 1,024 threads. Thread t adds grad[i]^2 over the 16-byte groups t, t + 1,024, .. of a buffer in order, one
-//            f64 sum a vector component, combined pairwise; then the butterfly and the sixteen wavefronts' sums, pairwise: the order
-//            depends on the float count alone. Thread 0 reads the loss and the counters, decides whether the call applies, forms
-//            both clip coefficients and, in f64 from the network's OWN applied-step counter, lr / bc1 and sqrt(bc2), writes them
-//            to the workspace, the norms to norms_out and the counters back. Nothing else reads the counters in that launch.
+//   prepare  ONE block of 1,024 threads. Thread t adds grad[i]^2 over the 16-byte groups t, t + 1,024, .. of a buffer in order
+//            (sum_squares); then the butterfly and the sixteen wavefronts' sums, pairwise: the order depends on the float count
+//            alone. Thread 0 reads the loss and the counters, decides whether the call applies, forms both clip coefficients and,
+//            in f64 from the network's OWN applied-step counter, lr / bc1 and sqrt(bc2), writes them to the workspace, the norms
+//            to norms_out and the counters back. Nothing else reads the counters in that launch.
 //   update   both networks in one grid, a 16-byte group a lane. Every block reads the prepared scalars and returns at once on a
-//            skip. Otherwise the lines of the Q-network's update (g2048_qnet_step.hip) without weight decay, every operation
-//            rounded to f32 on its own (-ffp-contract=off):
-//              g = grad c;  m += (g - m)(1 - beta1);  v = v beta2 + (g g)(1 - beta2);  p -= (lr / bc1) (m / (sqrt(v) / sqrt(bc2) + eps))
+//            skip. Otherwise adam_update without weight decay.
 //            The critic's buffers are = 1 mod 4 floats long: their last group is one float.
 // No atomics, no block waits on another, nothing depends on the compute-unit count: two calls give the same bits.
 #include "../../include/g2048.h"
 #include "g2048_host.h"
-#include "g2048_step_common.h"      // wave_sum, load_group, store_group, decimal_of, good_hyper
+#include "g2048_step_common.h"      // the sums, the groups, adam_update, the gates' pieces and the host's scalars
 
 namespace {
 
@@ -41,13 +39,7 @@ struct PrepScalars {
 // sum of grad[i]^2 over one buffer by the whole block, the same on every thread
 __device__ inline double prep_sum(const float *__restrict__ grad, size_t floats, double (&red)[kPrepWaves])
 {
-    double a[4] = {0.0, 0.0, 0.0, 0.0};
-    for (size_t at = 4 * (size_t)threadIdx.x; at < floats; at += 4 * (size_t)kPrepThreads) {
-        const f4 g = load_group(grad, at, floats);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) a[j] += (double)g[j] * (double)g[j];
-    }
-    const double w = wave_sum((a[0] + a[1]) + (a[2] + a[3]));
+    const double w = wave_sum(sum_squares(grad, 4 * (size_t)threadIdx.x, floats, 4 * (size_t)kPrepThreads, floats));
     __syncthreads();                                                   // red may still be read from the buffer before
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = w;
     __syncthreads();
@@ -74,12 +66,7 @@ __global__ __launch_bounds__(kPrepThreads) void ps_prepare_kernel(const float *_
     Prepared out;
     out.apply = 0;
     out.clip[0] = out.clip[1] = out.step_size[0] = out.step_size[1] = out.bc2_sqrt[0] = out.bc2_sqrt[1] = 0.0f;
-    bool nan_loss = false;
-    if (loss_or_null) {
-        const float loss = loss_or_null[0];
-        nan_loss = loss != loss;                                       // isnan only, the reference's rule: +inf is applied
-    }
-    if (nan_loss) {
+    if (nan_loss(loss_or_null)) {
         counters[2] += 1;
     } else if (!__builtin_isfinite(norm_a) || !__builtin_isfinite(norm_c)) {
         counters[3] += 1;
@@ -90,17 +77,18 @@ __global__ __launch_bounds__(kPrepThreads) void ps_prepare_kernel(const float *_
         for (int n = 0; n < 2; ++n) {
             const long long t = counters[n] + 1;                       // this network's step number: skipped calls never counted
             counters[n] = t;
-            const double bc1 = 1.0 - pow(k.beta1, (double)t), bc2 = 1.0 - pow(k.beta2, (double)t);
-            out.clip[n] = fminf(1.0f, (1.0f / (norm[n] + 1e-6f)) * k.max_norm);      // the reciprocal first: how torch evaluates it
-            out.step_size[n] = (float)(k.lr[n] / bc1);
-            out.bc2_sqrt[n] = (float)sqrt(bc2);
+            const BiasCorrections bc = bias_corrections(k.lr[n], k.beta1, k.beta2, (double)t);
+            out.clip[n] = clip_coefficient(norm[n], k.max_norm);
+            out.step_size[n] = bc.step_size;
+            out.bc2_sqrt[n] = bc.bc2_sqrt;
         }
     }
     *prepared = out;
 }
 
 struct UpdateScalars {
-    float one_minus_beta1, beta2, one_minus_beta2, eps[2];
+    AdamBetas betas;
+    float eps[2];
 };
 
 struct NetBuffers {
@@ -117,21 +105,10 @@ __global__ __launch_bounds__(kStepThreads) void ps_update_kernel(NetBuffers acto
     const size_t floats = is_critic ? kCriticFloats : kActorFloats;
     const size_t at = ((size_t)(blockIdx.x - (is_critic ? kActorBlocks : 0u)) * kStepThreads + threadIdx.x) * 4;
     if (at >= floats) return;
-    const float c = prepared->clip[n], step_size = prepared->step_size[n], bc2_sqrt = prepared->bc2_sqrt[n], eps = k.eps[n];
-    const f4 g0 = load_group(b.grad, at, floats), p0 = load_group(b.plain, at, floats);
-    const f4 m0 = load_group(b.exp_avg, at, floats), v0 = load_group(b.exp_avg_sq, at, floats);
-    f4 g, p, m, v;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        g[j] = g0[j] * c;
-        m[j] = m0[j] + (g[j] - m0[j]) * k.one_minus_beta1;
-        v[j] = v0[j] * k.beta2 + (g[j] * g[j]) * k.one_minus_beta2;
-        p[j] = p0[j] - step_size * (m[j] / (sqrtf(v[j]) / bc2_sqrt + eps));
-    }
-    store_group(b.grad, at, floats, g);
-    store_group(b.plain, at, floats, p);
-    store_group(b.exp_avg, at, floats, m);
-    store_group(b.exp_avg_sq, at, floats, v);
+    const float c = prepared->clip[n], eps = k.eps[n];
+    const BiasCorrections bc = {prepared->step_size[n], prepared->bc2_sqrt[n]};
+    const StepGroup in = load_step_group(b.plain, b.grad, b.exp_avg, b.exp_avg_sq, at, floats);
+    store_step_group(b.plain, b.grad, b.exp_avg, b.exp_avg_sq, at, floats, adam_update<false>(in, c, 1.0f, k.betas, bc, eps));
 }
 
 }  // namespace
@@ -153,23 +130,19 @@ int g2048_ppo_adam_step(float *plain_actor, float *grad_actor, float *exp_avg_ac
         !aligned(workspace, 16) || !aligned(counters, 8) || !aligned(norms_out, 4) || !aligned(loss_or_null, 4))
         return fail(G2048_ERR_ARG, "g2048_ppo_adam_step: misaligned pointer (plain weights, grad, exp_avg, exp_avg_sq, workspace: 16 bytes; "
                                    "counters: 8; loss, norms: 4)");
-    if (!good_hyper(lr_actor) || !good_hyper(lr_critic) || !good_hyper(beta1) || !good_hyper(beta2) || !good_hyper(eps_actor) ||
-        !good_hyper(eps_critic))
-        return fail(G2048_ERR_ARG, "g2048_ppo_adam_step: lr, beta1, beta2 and eps must be finite and not negative");
-    if (beta1 >= 1.0f || beta2 >= 1.0f) return fail(G2048_ERR_ARG, "g2048_ppo_adam_step: beta1 and beta2 must be below 1");
-    if (!(max_norm > 0.0f)) return fail(G2048_ERR_ARG, "g2048_ppo_adam_step: max_norm must be above 0 (+inf: no clipping)");
+    const float lr_eps[4] = {lr_actor, lr_critic, eps_actor, eps_critic};
+    if (const char *defect = adam_hyper_defect(lr_eps, 4, beta1, beta2, nullptr, max_norm))
+        return fail(G2048_ERR_ARG, "g2048_ppo_adam_step: %s", defect);
 
-    const double b1 = decimal_of(beta1), b2 = decimal_of(beta2);
+    const BetaScalars b = beta_scalars(beta1, beta2);
     PrepScalars ps;
-    ps.beta1 = b1;
-    ps.beta2 = b2;
+    ps.beta1 = b.beta1;
+    ps.beta2 = b.beta2;
     ps.lr[0] = (double)lr_actor;
     ps.lr[1] = (double)lr_critic;
     ps.max_norm = max_norm;
     UpdateScalars us;
-    us.one_minus_beta1 = (float)(1.0 - b1);
-    us.beta2 = beta2;
-    us.one_minus_beta2 = (float)(1.0 - b2);
+    us.betas = b.update;
     us.eps[0] = eps_actor;
     us.eps[1] = eps_critic;
     hipStream_t s = static_cast<hipStream_t>(stream);

@@ -10,6 +10,7 @@ The libraries are built in-tree so that they travel with the source snapshot; th
 git-ignored. -ffp-contract=off is REQUIRED: the reward / heuristic kernels follow
 the reference's f64 operation order (mul then add, never fma).
 
+LIBRARIES has a row per library; one more library is one more row there and one in g2048/_lib.py.
 libg2048_train_hip.so (include/g2048_train.h) holds the Q-network's training-mode entry points: the main library's export
 table is closed (ABI 5), so they live in a second library with the same flags and the same version script.
 libg2048_tlearn_hip.so (include/g2048_tlearn.h) holds the transformer policy's PPO loss and gradient pass, a third library for
@@ -20,21 +21,27 @@ the learner library's table is closed as well.
 import os
 import shutil
 import subprocess
+import sys
 
 CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "csrc")
-LIB = os.environ.get("G2048_LIB") or os.path.join(CSRC, "libg2048_hip.so")     # G2048_LIB: A/B builds only (tools/)
-TRAIN_LIB = os.environ.get("G2048_TRAIN_LIB") or os.path.join(CSRC, "libg2048_train_hip.so")     # G2048_TRAIN_LIB: A/B builds only
-SOURCES = ["g2048_kernels.hip", "g2048_beam.hip", "g2048_rollout.hip", "g2048_policy.hip", "g2048_tpolicy.hip",
-           "g2048_qnet.hip", "g2048_qnet_batch.hip", "g2048_qnet_grad.hip", "g2048_qnet_step.hip", "g2048_per.hip", "g2048_ppo_grad.hip",
-           "g2048_ppo_step.hip"]
-TLEARN_LIB = os.environ.get("G2048_TLEARN_LIB") or os.path.join(CSRC, "libg2048_tlearn_hip.so")   # G2048_TLEARN_LIB: A/B builds only
-TRAIN_SOURCES = ["g2048_qnet_train.hip"]
-TLEARN_SOURCES = ["g2048_tpolicy_grad.hip"]
-TSTEP_LIB = os.environ.get("G2048_TSTEP_LIB") or os.path.join(CSRC, "libg2048_tstep_hip.so")      # G2048_TSTEP_LIB: A/B builds only
-TSTEP_SOURCES = ["g2048_tpolicy_step.hip"]
 INCLUDE = os.path.join(CSRC, "..", "..", "include")
-PUBLIC_HEADERS = [os.path.join(INCLUDE, "g2048.h"), os.path.join(INCLUDE, "g2048_testing.h"), os.path.join(INCLUDE, "g2048_train.h"),
-                  os.path.join(INCLUDE, "g2048_tlearn.h"), os.path.join(INCLUDE, "g2048_tstep.h")]
+# key: (product file, environment variable that names an A/B build to load in its place (tools/), sources, public headers).
+# The key is the prefix of the module's names for the row: TRAIN_LIB, TRAIN_SOURCES; the main library's are LIB and SOURCES.
+LIBRARIES = {
+    "": ("libg2048_hip.so", "G2048_LIB",
+         ["g2048_kernels.hip", "g2048_beam.hip", "g2048_rollout.hip", "g2048_policy.hip", "g2048_tpolicy.hip", "g2048_qnet.hip",
+          "g2048_qnet_batch.hip", "g2048_qnet_grad.hip", "g2048_qnet_step.hip", "g2048_per.hip", "g2048_ppo_grad.hip", "g2048_ppo_step.hip"],
+         ["g2048.h", "g2048_testing.h"]),
+    "TRAIN_": ("libg2048_train_hip.so", "G2048_TRAIN_LIB", ["g2048_qnet_train.hip"], ["g2048_train.h"]),
+    "TLEARN_": ("libg2048_tlearn_hip.so", "G2048_TLEARN_LIB", ["g2048_tpolicy_grad.hip"], ["g2048_tlearn.h"]),
+    "TSTEP_": ("libg2048_tstep_hip.so", "G2048_TSTEP_LIB", ["g2048_tpolicy_step.hip"], ["g2048_tstep.h"]),
+}
+PUBLIC_HEADERS = [os.path.join(INCLUDE, h) for row in LIBRARIES.values() for h in row[3]]
+# LIB, SOURCES, TRAIN_LIB, TRAIN_SOURCES, ...: what the loader, the tools and the tests read; needs_build() and build() read the
+# paths from here too, so a path that is replaced at run time is the one they look at
+for _key, (_file, _env, _sources, _) in LIBRARIES.items():
+    globals()[_key + "LIB"] = os.environ.get(_env) or os.path.join(CSRC, _file)
+    globals()[_key + "SOURCES"] = _sources
 # -fvisibility=hidden: the export table is exactly what the two headers declare with G2048_API (tests/test_abi_and_host.py)
 # -amdgpu-kernarg-preload-count: the first kernel-argument dwords arrive in SGPRs with the wavefront instead of through s_load +
 # s_waitcnt at its head (gfx950 takes up to 14 next to the kernarg pointer; the short kernels order their arguments for it:
@@ -42,6 +49,10 @@ PUBLIC_HEADERS = [os.path.join(INCLUDE, "g2048.h"), os.path.join(INCLUDE, "g2048
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fvisibility=hidden",
          "-mllvm", "-amdgpu-kernarg-preload-count=16",
          "-Wl,--version-script=" + os.path.join(CSRC, "g2048_exports.map"), "-Wall", "-Wno-unused-function"]
+
+
+def path_of(key):
+    return globals()[key + "LIB"]
 
 
 def _stale(lib):
@@ -54,12 +65,14 @@ def _stale(lib):
 
 
 def needs_build():
-    return _stale(LIB) or _stale(TRAIN_LIB) or _stale(TLEARN_LIB) or _stale(TSTEP_LIB)
+    return any(_stale(path_of(key)) for key in LIBRARIES)
 
 
-def _compile(sources, out, extra_flags, verbose):
+def build_one(key, lib=None, extra_flags=(), verbose=False):
+    """The library of row `key` alone, always made: the product's, or an A/B build at `lib` (loaded through the row's variable)."""
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    srcs = [os.path.join(CSRC, f) for f in sources if os.path.exists(os.path.join(CSRC, f))]
+    out = lib or path_of(key)
+    srcs = [os.path.join(CSRC, f) for f in LIBRARIES[key][2] if os.path.exists(os.path.join(CSRC, f))]
     cmd = [hipcc] + FLAGS + list(extra_flags) + ["-o", out] + srcs
     if verbose:
         print(" ".join(cmd))
@@ -68,51 +81,24 @@ def _compile(sources, out, extra_flags, verbose):
 
 
 def build(force=False, verbose=False, lib=None, extra_flags=()):
-    """The four product libraries, each only if it is stale. lib / extra_flags: an A/B or measurement build of the MAIN library next to
-    the product's (tools/build_ab.sh); such a build is always made, and the other three libraries are left alone."""
+    """The product libraries, each only if it is stale. lib / extra_flags: an A/B or measurement build of the MAIN library next to
+    the product's (tools/build_ab.sh); such a build is always made, and the other libraries are left alone."""
     if lib is not None:
-        return _compile(SOURCES, lib, extra_flags, verbose)
-    if force or _stale(LIB):
-        _compile(SOURCES, LIB, extra_flags, verbose)
-    if force or _stale(TRAIN_LIB):
-        _compile(TRAIN_SOURCES, TRAIN_LIB, extra_flags, verbose)
-    if force or _stale(TLEARN_LIB):
-        _compile(TLEARN_SOURCES, TLEARN_LIB, extra_flags, verbose)
-    if force or _stale(TSTEP_LIB):
-        _compile(TSTEP_SOURCES, TSTEP_LIB, extra_flags, verbose)
-    return LIB
-
-
-def build_train(lib=None, extra_flags=(), verbose=False):
-    """The training library alone, always made: the product's, or an A/B build at `lib` (loaded through G2048_TRAIN_LIB)."""
-    return _compile(TRAIN_SOURCES, lib or TRAIN_LIB, extra_flags, verbose)
-
-
-def build_tlearn(lib=None, extra_flags=(), verbose=False):
-    """The transformer policy's learner library alone, always made: the product's, or an A/B build at `lib` (loaded through
-    G2048_TLEARN_LIB)."""
-    return _compile(TLEARN_SOURCES, lib or TLEARN_LIB, extra_flags, verbose)
-
-
-def build_tstep(lib=None, extra_flags=(), verbose=False):
-    """The transformer policy's optimiser-step library alone, always made: the product's, or an A/B build at `lib` (loaded through
-    G2048_TSTEP_LIB)."""
-    return _compile(TSTEP_SOURCES, lib or TSTEP_LIB, extra_flags, verbose)
+        return build_one("", lib, extra_flags, verbose)
+    for key in LIBRARIES:
+        if force or _stale(path_of(key)):
+            build_one(key, None, extra_flags, verbose)
+    return path_of("")
 
 
 if __name__ == "__main__":          # [--train | --tlearn | --tstep] [-o LIBRARY] [extra compiler flags ...]
-    import sys
     out, args = None, sys.argv[1:]
-    train, tlearn, tstep = args[:1] == ["--train"], args[:1] == ["--tlearn"], args[:1] == ["--tstep"]
-    if train or tlearn or tstep:
+    key = next((k for k in LIBRARIES if k and args[:1] == ["--" + k[:-1].lower()]), None)
+    if key:
         args = args[1:]
     if args[:1] == ["-o"]:
         out, args = args[1], args[2:]
-    if train:
-        print(build_train(lib=out, extra_flags=args, verbose=True))
-    elif tlearn:
-        print(build_tlearn(lib=out, extra_flags=args, verbose=True))
-    elif tstep:
-        print(build_tstep(lib=out, extra_flags=args, verbose=True))
+    if key:
+        print(build_one(key, lib=out, extra_flags=args, verbose=True))
     else:
         print(build(force=True, verbose=True, lib=out, extra_flags=args))

@@ -1,17 +1,18 @@
-"""ctypes binding of the C-ABI in include/g2048.h (csrc/libg2048_hip.so).
+"""ctypes binding of the C-ABI in include/g2048.h (csrc/libg2048_hip.so) and of the three libraries beside it (g2048_train.h,
+g2048_tlearn.h, g2048_tstep.h): one Library per row of _build.LIBRARIES, each with its own table, error string and version.
 
 There is no fallback: if the library is missing or no HIP device is visible, every
 compute call raises. PyTorch is only used for device memory and streams -- tensors
 are passed as data_ptr(), work is enqueued on torch's current stream.
 """
+import contextlib
 import ctypes as C
 import os
+import sys
 
 import torch
 
 from . import _build
-
-_lib = None
 
 OK = 0
 ABI_VERSION = 5
@@ -137,46 +138,6 @@ SIGNATURES = {
 }
 
 
-def library_path():
-    return _build.LIB
-
-
-def lib():
-    """The loaded C-ABI library. Raises if it has not been built (python __graft_entry__.py)."""
-    global _lib
-    if _lib is None:
-        path = library_path()
-        if not os.path.exists(path):
-            raise RuntimeError("g2048: %s is missing -- build it with `python __graft_entry__.py` "
-                               "(hipcc --offload-arch=gfx950); there is no CPU fallback" % path)
-        if os.environ.get("G2048_LIB"):      # A/B builds (tools/build_ab.sh) are only ever loaded on request, and say so
-            import sys
-            print("g2048: loading the A/B build %s (G2048_LIB is set)" % path, file=sys.stderr)
-        elif os.path.basename(path) != "libg2048_hip.so":
-            raise RuntimeError("g2048: refusing to load %s: only csrc/libg2048_hip.so is the product library" % path)
-        L = C.CDLL(path)        # torch is imported above, so libamdhip64 resolves to the runtime torch uses
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(L, name)   # AttributeError here = ABI mismatch, deliberately loud
-            fn.restype, fn.argtypes = res, args
-        if L.g2048_abi_version() != ABI_VERSION:
-            raise RuntimeError("g2048: ABI version mismatch (library %d, binding %d)" % (L.g2048_abi_version(), ABI_VERSION))
-        flags = int(L.g2048_build_flags())
-        if flags and os.environ.get("G2048_ALLOW_INSTRUMENTED") != "1":
-            # a measurement build (csrc/g2048_instrument.h) overwrites real outputs with clock ticks: only the timeline tools,
-            # which set G2048_ALLOW_INSTRUMENTED=1 themselves, may load one
-            raise RuntimeError("g2048: %s is an instrumented measurement build (g2048_build_flags() = 0x%x); its outputs are "
-                               "not results -- refusing to load it (tools/*_timeline.py opt in with G2048_ALLOW_INSTRUMENTED=1)"
-                               % (path, flags))
-        _lib = L
-    return _lib
-
-
-def check(rc):
-    if rc != OK:
-        raise RuntimeError("g2048: %s (status %d)" % (lib().g2048_last_error().decode(), rc))
-
-
-# ---- the training library (include/g2048_train.h, csrc/libg2048_train_hip.so): its own table, loader, error string and version
 TRAIN_ABI_VERSION = 1
 _p4 = C.POINTER(C.c_double)
 TRAIN_SIGNATURES = {
@@ -187,55 +148,7 @@ TRAIN_SIGNATURES = {
     "g2048_qnet_loss_grad_dropout": (_int, [_vp] * 5 + [_sz, _int, _int, _p4, _u64, _u64] + [_vp] * 6),
     "g2048_qnet_dropout_mask": (_int, [_u64, _u64, _int, _int, C.c_double, _sz, _int, _sz, _sz, _vp, _vp]),
 }
-_train_lib = None
 
-
-def train_library_path():
-    return _build.TRAIN_LIB
-
-
-def train_lib():
-    """The loaded training library. Raises if it has not been built (python __graft_entry__.py); as loud as lib()."""
-    global _train_lib
-    if _train_lib is None:
-        path = train_library_path()
-        if not os.path.exists(path):
-            raise RuntimeError("g2048: %s is missing -- build it with `python __graft_entry__.py` "
-                               "(hipcc --offload-arch=gfx950); there is no CPU fallback and no training pass without it" % path)
-        if os.environ.get("G2048_TRAIN_LIB"):      # A/B builds are only ever loaded on request, and say so
-            import sys
-            print("g2048: loading the A/B build %s (G2048_TRAIN_LIB is set)" % path, file=sys.stderr)
-        elif os.path.basename(path) != "libg2048_train_hip.so":
-            raise RuntimeError("g2048: refusing to load %s: only csrc/libg2048_train_hip.so is the product's training library" % path)
-        T = C.CDLL(path)
-        for name, (res, args) in TRAIN_SIGNATURES.items():
-            fn = getattr(T, name)   # AttributeError here = ABI mismatch, deliberately loud
-            fn.restype, fn.argtypes = res, args
-        if T.g2048_train_abi_version() != TRAIN_ABI_VERSION:
-            raise RuntimeError("g2048: training library ABI version mismatch (library %d, binding %d)"
-                               % (T.g2048_train_abi_version(), TRAIN_ABI_VERSION))
-        _train_lib = T
-    return _train_lib
-
-
-def train_check(rc):
-    if rc != OK:
-        raise RuntimeError("g2048: %s (status %d)" % (train_lib().g2048_train_last_error().decode(), rc))
-
-
-def train_call(device, fn, *args):
-    """call() for an entry point of the training library: its status is read from that library's own error string."""
-    idx = device.index if device.index is not None else torch.cuda.current_device()
-    if torch.cuda.current_device() == idx:
-        rc = fn(*args)
-    else:
-        with torch.cuda.device(idx):
-            rc = fn(*args)
-    train_check(rc)
-
-
-# ---- the transformer policy's learner library (include/g2048_tlearn.h, csrc/libg2048_tlearn_hip.so): again its own table, loader,
-# error string and version
 TLEARN_ABI_VERSION = 1
 TLEARN_BATCH_MAX = 1024
 _f = C.c_float
@@ -245,52 +158,7 @@ TLEARN_SIGNATURES = {
     "g2048_tpolicy_grad_workspace": (_sz, [_sz, _int, _int]),
     "g2048_tpolicy_loss_grad": (_int, [_vp] * 6 + [_sz, _int, _int, _f, _f, _f] + [_vp] * 5 + [_sz, _vp]),
 }
-_tlearn_lib = None
 
-
-def tlearn_library_path():
-    return _build.TLEARN_LIB
-
-
-def tlearn_lib():
-    """The loaded learner library of the transformer policy. Raises if it has not been built (python __graft_entry__.py); as loud
-    as train_lib()."""
-    global _tlearn_lib
-    if _tlearn_lib is None:
-        path = tlearn_library_path()
-        if not os.path.exists(path):
-            raise RuntimeError("g2048: %s is missing -- build it with `python __graft_entry__.py` "
-                               "(hipcc --offload-arch=gfx950); there is no CPU fallback and no gradient pass without it" % path)
-        if os.environ.get("G2048_TLEARN_LIB"):      # A/B builds are only ever loaded on request, and say so
-            import sys
-            print("g2048: loading the A/B build %s (G2048_TLEARN_LIB is set)" % path, file=sys.stderr)
-        elif os.path.basename(path) != "libg2048_tlearn_hip.so":
-            raise RuntimeError("g2048: refusing to load %s: only csrc/libg2048_tlearn_hip.so is the product's learner library" % path)
-        T = C.CDLL(path)
-        for name, (res, args) in TLEARN_SIGNATURES.items():
-            fn = getattr(T, name)   # AttributeError here = ABI mismatch, deliberately loud
-            fn.restype, fn.argtypes = res, args
-        if T.g2048_tlearn_abi_version() != TLEARN_ABI_VERSION:
-            raise RuntimeError("g2048: learner library ABI version mismatch (library %d, binding %d)"
-                               % (T.g2048_tlearn_abi_version(), TLEARN_ABI_VERSION))
-        _tlearn_lib = T
-    return _tlearn_lib
-
-
-def tlearn_call(device, fn, *args):
-    """call() for an entry point of the learner library: its status is read from that library's own error string."""
-    idx = device.index if device.index is not None else torch.cuda.current_device()
-    if torch.cuda.current_device() == idx:
-        rc = fn(*args)
-    else:
-        with torch.cuda.device(idx):
-            rc = fn(*args)
-    if rc != OK:
-        raise RuntimeError("g2048: %s (status %d)" % (tlearn_lib().g2048_tlearn_last_error().decode(), rc))
-
-
-# ---- the transformer policy's optimiser-step library (include/g2048_tstep.h, csrc/libg2048_tstep_hip.so): the fourth table, loader,
-# error string and version
 TSTEP_ABI_VERSION = 1
 TSTEP_SIGNATURES = {
     "g2048_tstep_last_error": (C.c_char_p, []),
@@ -298,64 +166,98 @@ TSTEP_SIGNATURES = {
     "g2048_tpolicy_step_workspace": (_sz, [_int, _int]),
     "g2048_tpolicy_adam_step": (_int, [_vp] * 4 + [_int, _int, _vp, _vp] + [_f] * 5 + [_vp, _vp, _sz, _vp]),
 }
-_tstep_lib = None
 
 
-def tstep_library_path():
-    return _build.TSTEP_LIB
+class Library:
+    """One shared object of _build.LIBRARIES (row `key`), loaded on first use and as loud as can be: a missing file, a file under
+    another name than the product's, a missing symbol, another ABI version and a failed call all raise."""
 
+    def __init__(self, key, stem, signatures, version, role="", without="", after_load=None):
+        """stem: the library exports <stem>_abi_version and <stem>_last_error. role: what the messages call the library beside the
+        main one ("training"); without: what the `missing` message says is lost with it. after_load(handle, path): a last check."""
+        self.key, self.stem, self.signatures, self.version = key, stem, signatures, version
+        self.role, self.without, self.after_load = role, without, after_load
+        self.handle = None
 
-def tstep_lib():
-    """The loaded optimiser-step library of the transformer policy. Raises if it has not been built (python __graft_entry__.py); as
-    loud as tlearn_lib()."""
-    global _tstep_lib
-    if _tstep_lib is None:
-        path = tstep_library_path()
-        if not os.path.exists(path):
-            raise RuntimeError("g2048: %s is missing -- build it with `python __graft_entry__.py` "
-                               "(hipcc --offload-arch=gfx950); there is no CPU fallback and no device optimiser step without it" % path)
-        if os.environ.get("G2048_TSTEP_LIB"):      # A/B builds are only ever loaded on request, and say so
-            import sys
-            print("g2048: loading the A/B build %s (G2048_TSTEP_LIB is set)" % path, file=sys.stderr)
-        elif os.path.basename(path) != "libg2048_tstep_hip.so":
-            raise RuntimeError("g2048: refusing to load %s: only csrc/libg2048_tstep_hip.so is the product's step library" % path)
-        T = C.CDLL(path)
-        for name, (res, args) in TSTEP_SIGNATURES.items():
-            fn = getattr(T, name)   # AttributeError here = ABI mismatch, deliberately loud
-            fn.restype, fn.argtypes = res, args
-        if T.g2048_tstep_abi_version() != TSTEP_ABI_VERSION:
-            raise RuntimeError("g2048: step library ABI version mismatch (library %d, binding %d)"
-                               % (T.g2048_tstep_abi_version(), TSTEP_ABI_VERSION))
-        _tstep_lib = T
-    return _tstep_lib
+    def path(self):
+        return _build.path_of(self.key)
 
+    def load(self):
+        """The loaded library. Raises if it has not been built (python __graft_entry__.py)."""
+        if self.handle is None:
+            path, (product, env) = self.path(), _build.LIBRARIES[self.key][:2]
+            if not os.path.exists(path):
+                raise RuntimeError("g2048: %s is missing -- build it with `python __graft_entry__.py` "
+                                   "(hipcc --offload-arch=gfx950); there is no CPU fallback%s" % (path, self.without))
+            if os.environ.get(env):      # A/B builds (tools/build_ab.sh) are only ever loaded on request, and say so
+                print("g2048: loading the A/B build %s (%s is set)" % (path, env), file=sys.stderr)
+            elif os.path.basename(path) != product:
+                raise RuntimeError("g2048: refusing to load %s: only csrc/%s is the product%s library"
+                                   % (path, product, self.role and "'s " + self.role))
+            handle = C.CDLL(path)       # torch is imported above, so libamdhip64 resolves to the runtime torch uses
+            for name, (res, args) in self.signatures.items():
+                fn = getattr(handle, name)   # AttributeError here = ABI mismatch, deliberately loud
+                fn.restype, fn.argtypes = res, args
+            found = getattr(handle, self.stem + "_abi_version")()
+            if found != self.version:
+                raise RuntimeError("g2048: %sABI version mismatch (library %d, binding %d)"
+                                   % (self.role and self.role + " library ", found, self.version))
+            if self.after_load:
+                self.after_load(handle, path)
+            self.handle = handle
+        return self.handle
 
-def tstep_call(device, fn, *args):
-    """call() for an entry point of the step library: its status is read from that library's own error string."""
-    idx = device.index if device.index is not None else torch.cuda.current_device()
-    if torch.cuda.current_device() == idx:
-        rc = fn(*args)
-    else:
-        with torch.cuda.device(idx):
+    def check(self, rc):
+        if rc != OK:
+            raise RuntimeError("g2048: %s (status %d)" % (getattr(self.load(), self.stem + "_last_error")().decode(), rc))
+
+    def call(self, device, fn, *args):
+        """Invoke an entry point with `device` as the calling thread's current HIP device (a launch goes to the current device,
+        which need not be the tensors' device in a one-process multi-GPU program) and check its status against this library's
+        own error string."""
+        idx = device.index if device.index is not None else torch.cuda.current_device()
+        if torch.cuda.current_device() == idx:
             rc = fn(*args)
-    if rc != OK:
-        raise RuntimeError("g2048: %s (status %d)" % (tstep_lib().g2048_tstep_last_error().decode(), rc))
+        else:
+            with torch.cuda.device(idx):
+                rc = fn(*args)
+        self.check(rc)
+
+    @contextlib.contextmanager
+    def swapped(self, handle):
+        """Every call of the package goes to `handle`, another build bound like this one, until the block ends (tools/)."""
+        mine, self.handle = self.load(), handle
+        try:
+            yield
+        finally:
+            self.handle = mine
+
+
+def _refuse_instrumented(handle, path):
+    flags = int(handle.g2048_build_flags())
+    if flags and os.environ.get("G2048_ALLOW_INSTRUMENTED") != "1":
+        # a measurement build (csrc/g2048_instrument.h) overwrites real outputs with clock ticks: only the timeline tools,
+        # which set G2048_ALLOW_INSTRUMENTED=1 themselves, may load one
+        raise RuntimeError("g2048: %s is an instrumented measurement build (g2048_build_flags() = 0x%x); its outputs are "
+                           "not results -- refusing to load it (tools/*_timeline.py opt in with G2048_ALLOW_INSTRUMENTED=1)"
+                           % (path, flags))
+
+
+MAIN = Library("", "g2048", SIGNATURES, ABI_VERSION, after_load=_refuse_instrumented)
+TRAIN = Library("TRAIN_", "g2048_train", TRAIN_SIGNATURES, TRAIN_ABI_VERSION, "training", " and no training pass without it")
+TLEARN = Library("TLEARN_", "g2048_tlearn", TLEARN_SIGNATURES, TLEARN_ABI_VERSION, "learner", " and no gradient pass without it")
+TSTEP = Library("TSTEP_", "g2048_tstep", TSTEP_SIGNATURES, TSTEP_ABI_VERSION, "step", " and no device optimiser step without it")
+LIBRARIES = {"": MAIN, "TRAIN_": TRAIN, "TLEARN_": TLEARN, "TSTEP_": TSTEP}
+
+# the names the package, the tools and the tests call
+library_path, lib, check, call = MAIN.path, MAIN.load, MAIN.check, MAIN.call
+train_library_path, train_lib, train_call = TRAIN.path, TRAIN.load, TRAIN.call
+tlearn_library_path, tlearn_lib, tlearn_call = TLEARN.path, TLEARN.load, TLEARN.call
+tstep_library_path, tstep_lib, tstep_call = TSTEP.path, TSTEP.load, TSTEP.call
 
 
 def stream_ptr(device):
     return torch.cuda.current_stream(device).cuda_stream
-
-
-def call(device, fn, *args):
-    """Invoke a C-ABI entry point with `device` as the calling thread's current HIP device (a launch goes to the
-    current device, which need not be the tensors' device in a one-process multi-GPU program) and check its status."""
-    idx = device.index if device.index is not None else torch.cuda.current_device()
-    if torch.cuda.current_device() == idx:
-        rc = fn(*args)
-    else:
-        with torch.cuda.device(idx):
-            rc = fn(*args)
-    check(rc)
 
 
 def require_device_tensor(t, dtype, shape_tail=None, name="tensor"):

@@ -47,6 +47,57 @@ def _output(t, n, dtype, tail, name, device):
     return t
 
 
+def _workspace(workspace, nb, dev):
+    """The workspace of a call that needs nb bytes: allocated when None, else required to be a uint8 device tensor that holds them."""
+    if workspace is None:
+        workspace = torch.empty(nb, dtype=torch.uint8, device=dev)
+    L.require_device_tensor(workspace, torch.uint8, None, "workspace")
+    if workspace.numel() < nb:
+        raise ValueError("g2048: workspace must hold at least %d bytes" % nb)
+    return workspace
+
+
+def _float_output(t, shape, name, dev):
+    """The small float32 output `name` of an optimiser step, () or (2,): allocated when None, else required to hold as many."""
+    if t is None:
+        t = torch.empty(shape, dtype=torch.float32, device=dev)
+    L.require_device_tensor(t, torch.float32, None, name)
+    if t.numel() != (2 if shape else 1):
+        raise ValueError("g2048: %s must hold %s float32" % (name, "two" if shape else "one"))
+    return t
+
+
+def _step_buffers(buffers):
+    """The flat float32 buffers of an optimiser step, (name, tensor, floats) each: dtype and length of ALL of them before any
+    device, since such a mistake reads the same everywhere; then every one on a device, and on the first one's, which is returned."""
+    for name, t, floats in buffers:
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("g2048: %s must be a torch.Tensor" % name)
+        if t.dtype != torch.float32 or t.dim() != 1 or t.numel() != floats:
+            raise (TypeError if t.dtype != torch.float32 else ValueError)(
+                "g2048: %s must be a flat float32 tensor of %d floats (got %s %s)" % (name, floats, t.dtype, tuple(t.shape)))
+    first, dev = buffers[0][0], buffers[0][1].device
+    for name, t, _ in buffers:
+        L.require_device_tensor(t, torch.float32, None, name)
+        if t.device != dev:
+            raise ValueError("g2048: %s on %s, %s on %s" % (name, t.device, first, dev))
+    return dev
+
+
+def _step_counters(counters, count):
+    L.require_device_tensor(counters, torch.int64, None, "counters")
+    if counters.dim() != 1 or counters.numel() != count:
+        raise ValueError("g2048: counters must be an int64 tensor of %d" % count)
+
+
+def _gate_losses(losses):
+    """The optional float32 tensor whose first element is the loss an optimiser step checks for NaN."""
+    if losses is not None:
+        L.require_device_tensor(losses, torch.float32, None, "losses")
+        if losses.numel() < 1:
+            raise ValueError("g2048: losses must hold at least one float32")
+
+
 def step(boards, actions, scores, seed, step_index, id_base=0, out=None, reward=None, flags=None,
          reward_f64=False, auto_reset=False, tune=0, keyblock=None, noop_actions=False):
     """Game2048Env.step for every board (reference environment/game_2048.py:170-210).
@@ -587,12 +638,7 @@ def tpolicy_loss_grad(boards, plain, actions, old_log_probs, advantages, returns
     value = _output(value, n, torch.float32, (1,), "value", dev)
     if n == 0:
         return losses, probs, value, grad
-    nb = tpolicy_grad_workspace_bytes(n, dim_ff, n_layers)
-    if workspace is None:
-        workspace = torch.empty(nb, dtype=torch.uint8, device=dev)
-    L.require_device_tensor(workspace, torch.uint8, None, "workspace")
-    if workspace.numel() < nb:
-        raise ValueError("g2048: workspace must hold at least %d bytes" % nb)
+    workspace = _workspace(workspace, tpolicy_grad_workspace_bytes(n, dim_ff, n_layers), dev)
     L.tlearn_call(dev, L.tlearn_lib().g2048_tpolicy_loss_grad, boards.data_ptr(), plain.data_ptr(), actions.data_ptr(),
                   old_log_probs.data_ptr(), advantages.data_ptr(), returns.data_ptr(), n, int(dim_ff), int(n_layers), float(clip_epsilon),
                   float(value_coef), float(entropy_coef), grad.data_ptr(), losses.data_ptr(), probs.data_ptr(), value.data_ptr(),
@@ -622,36 +668,11 @@ def tpolicy_adam_step(plain, grad, exp_avg, exp_avg_sq, dim_ff, n_layers, counte
     finite leaves all four buffers and the step counter untouched. No synchronisation. Returns the gradient norm before clipping,
     float32, written on every call."""
     floats = tpolicy_plain_floats(dim_ff, n_layers)
-    buffers = (("plain", plain), ("grad", grad), ("exp_avg", exp_avg), ("exp_avg_sq", exp_avg_sq))
-    for name, t in buffers:                 # dtype and length of all four before any device: such a mistake reads the same everywhere
-        if not isinstance(t, torch.Tensor):
-            raise TypeError("g2048: %s must be a torch.Tensor" % name)
-        if t.dtype != torch.float32 or t.dim() != 1 or t.numel() != floats:
-            raise (TypeError if t.dtype != torch.float32 else ValueError)(
-                "g2048: %s must be a flat float32 tensor of %d floats (got %s %s)" % (name, floats, t.dtype, tuple(t.shape)))
-    for name, t in buffers:
-        L.require_device_tensor(t, torch.float32, None, name)
-        if t.device != plain.device:
-            raise ValueError("g2048: %s on %s, plain on %s" % (name, t.device, plain.device))
-    dev = plain.device
-    L.require_device_tensor(counters, torch.int64, None, "counters")
-    if counters.dim() != 1 or counters.numel() != 3:
-        raise ValueError("g2048: counters must be an int64 tensor of 3")
-    if losses is not None:
-        L.require_device_tensor(losses, torch.float32, None, "losses")
-        if losses.numel() < 1:
-            raise ValueError("g2048: losses must hold at least one float32")
-    if norm is None:
-        norm = torch.empty((), dtype=torch.float32, device=dev)
-    L.require_device_tensor(norm, torch.float32, None, "norm")
-    if norm.numel() != 1:
-        raise ValueError("g2048: norm must hold one float32")
-    nb = tpolicy_step_workspace_bytes(dim_ff, n_layers)
-    if workspace is None:
-        workspace = torch.empty(nb, dtype=torch.uint8, device=dev)
-    L.require_device_tensor(workspace, torch.uint8, None, "workspace")
-    if workspace.numel() < nb:
-        raise ValueError("g2048: workspace must hold at least %d bytes" % nb)
+    dev = _step_buffers((("plain", plain, floats), ("grad", grad, floats), ("exp_avg", exp_avg, floats), ("exp_avg_sq", exp_avg_sq, floats)))
+    _step_counters(counters, 3)
+    _gate_losses(losses)
+    norm = _float_output(norm, (), "norm", dev)
+    workspace = _workspace(workspace, tpolicy_step_workspace_bytes(dim_ff, n_layers), dev)
     for t, name in ((counters, "counters"), (losses, "losses"), (norm, "norm"), (workspace, "workspace")):
         if t is not None and t.device != dev:
             raise ValueError("g2048: %s on %s, plain on %s" % (name, t.device, dev))
@@ -780,12 +801,7 @@ def qnet_forward_batch(boards, plain, dim_ff, n_layers, q=None, workspace=None, 
     q = _output(q, n, torch.float32, (4,), "q", dev)
     if n == 0:
         return q
-    nb = qnet_batch_workspace_bytes(n, dim_ff)
-    if workspace is None:
-        workspace = torch.empty(nb, dtype=torch.uint8, device=dev)
-    L.require_device_tensor(workspace, torch.uint8, None, "workspace")
-    if workspace.numel() < nb:
-        raise ValueError("g2048: workspace must hold at least %d bytes" % nb)
+    workspace = _workspace(workspace, qnet_batch_workspace_bytes(n, dim_ff), dev)
     if p is None:
         L.call(dev, L.lib().g2048_qnet_forward_batch, boards.data_ptr(), plain.data_ptr(), q.data_ptr(), n, int(dim_ff), int(n_layers),
                workspace.data_ptr(), L.stream_ptr(dev))
@@ -835,19 +851,11 @@ def qnet_loss_grad(boards, plain, actions, targets, weights, dim_ff, n_layers, g
         raise ValueError("g2048: grad must be a flat float32 tensor of %d floats" % floats)
     td = _output(td, n, torch.float32, (), "td", dev)
     q = _output(q, n, torch.float32, (4,), "q", dev)
-    if loss is None:
-        loss = torch.empty((), dtype=torch.float32, device=dev)
-    L.require_device_tensor(loss, torch.float32, None, "loss")
-    if loss.numel() != 1:
-        raise ValueError("g2048: loss must hold one float32")
+    loss = _float_output(loss, (), "loss", dev)
     if n == 0:
         return loss, td, q, grad
     nb = qnet_grad_workspace_bytes(n, dim_ff, n_layers) if p is None else qnet_train_workspace_bytes(n, dim_ff, n_layers)
-    if workspace is None:
-        workspace = torch.empty(nb, dtype=torch.uint8, device=dev)
-    L.require_device_tensor(workspace, torch.uint8, None, "workspace")
-    if workspace.numel() < nb:
-        raise ValueError("g2048: workspace must hold at least %d bytes" % nb)
+    workspace = _workspace(workspace, nb, dev)
     if p is None:
         L.call(dev, L.lib().g2048_qnet_loss_grad, boards.data_ptr(), plain.data_ptr(), actions.data_ptr(), targets.data_ptr(),
                weights.data_ptr(), n, int(dim_ff), int(n_layers), grad.data_ptr(), td.data_ptr(), loss.data_ptr(), q.data_ptr(),
@@ -876,29 +884,9 @@ def qnet_adamw_step(plain, grad, exp_avg, exp_avg_sq, dim_ff, n_layers, lr, step
     of this update; max_norm None means no clipping. The LayerNorm-eps slots keep their bits in all four. A gradient norm that
     is not finite leaves all four untouched. No synchronisation. Returns the gradient norm before clipping, float32 ()."""
     floats = qnet_plain_floats(dim_ff, n_layers)
-    buffers = (("plain", plain), ("grad", grad), ("exp_avg", exp_avg), ("exp_avg_sq", exp_avg_sq))
-    for name, t in buffers:                 # dtype and length of all four before any device: such a mistake reads the same everywhere
-        if not isinstance(t, torch.Tensor):
-            raise TypeError("g2048: %s must be a torch.Tensor" % name)
-        if t.dtype != torch.float32 or t.dim() != 1 or t.numel() != floats:
-            raise (TypeError if t.dtype != torch.float32 else ValueError)(
-                "g2048: %s must be a flat float32 tensor of %d floats (got %s %s)" % (name, floats, t.dtype, tuple(t.shape)))
-    for name, t in buffers:
-        L.require_device_tensor(t, torch.float32, None, name)
-        if t.device != plain.device:
-            raise ValueError("g2048: %s on %s, plain on %s" % (name, t.device, plain.device))
-    dev = plain.device
-    if norm is None:
-        norm = torch.empty((), dtype=torch.float32, device=dev)
-    L.require_device_tensor(norm, torch.float32, None, "norm")
-    if norm.numel() != 1:
-        raise ValueError("g2048: norm must hold one float32")
-    nb = qnet_step_workspace_bytes(dim_ff, n_layers)
-    if workspace is None:
-        workspace = torch.empty(nb, dtype=torch.uint8, device=dev)
-    L.require_device_tensor(workspace, torch.uint8, None, "workspace")
-    if workspace.numel() < nb:
-        raise ValueError("g2048: workspace must hold at least %d bytes" % nb)
+    dev = _step_buffers((("plain", plain, floats), ("grad", grad, floats), ("exp_avg", exp_avg, floats), ("exp_avg_sq", exp_avg_sq, floats)))
+    norm = _float_output(norm, (), "norm", dev)
+    workspace = _workspace(workspace, qnet_step_workspace_bytes(dim_ff, n_layers), dev)
     L.call(dev, L.lib().g2048_qnet_adamw_step, plain.data_ptr(), grad.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(),
            int(dim_ff), int(n_layers), float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay),
            float("inf") if max_norm is None else float(max_norm), int(step), norm.data_ptr(), workspace.data_ptr(), L.stream_ptr(dev))
@@ -1761,16 +1749,6 @@ def ppo_train_workspace_bytes(n):
     return nb
 
 
-def _ppo_workspace(workspace, n, dev):
-    nb = ppo_train_workspace_bytes(n)
-    if workspace is None:
-        workspace = torch.empty(nb, dtype=torch.uint8, device=dev)
-    L.require_device_tensor(workspace, torch.uint8, None, "workspace")
-    if workspace.numel() < nb:
-        raise ValueError("g2048: workspace must hold at least %d bytes" % nb)
-    return workspace
-
-
 def _ppo_flat(t, floats, name):
     L.require_device_tensor(t, torch.float32, None, name)
     if t.dim() != 1 or t.numel() != floats:
@@ -1832,7 +1810,7 @@ def ppo_forward_train(states, plain, n_out, running=None, out=None, workspace=No
     out = _output(out, n, torch.float32, (n_out,), "out", dev)
     if n == 0:
         return out
-    workspace = _ppo_workspace(workspace, n, dev)
+    workspace = _workspace(workspace, ppo_train_workspace_bytes(n), dev)
     run = running.data_ptr() if running is not None else None
     if p == 0.0:
         L.call(dev, L.lib().g2048_ppo_forward_train, states.data_ptr(), plain.data_ptr(), run, int(n_out), out.data_ptr(), n,
@@ -1897,7 +1875,7 @@ def ppo_loss_grad(states, actions, old_log_probs, advantages, returns, plain_act
     _ppo_flat(losses, 4, "losses")
     if n == 0:
         return losses, grad_actor, grad_critic
-    workspace = _ppo_workspace(workspace, n, dev)
+    workspace = _workspace(workspace, ppo_train_workspace_bytes(n), dev)
     head = (states.data_ptr(), actions.data_ptr(), old_log_probs.data_ptr(), advantages.data_ptr(), returns.data_ptr(), plain_actor.data_ptr(),
             plain_critic.data_ptr(), running_actor.data_ptr() if running_actor is not None else None,
             running_critic.data_ptr() if running_critic is not None else None, float(clip_epsilon), float(value_coef), float(entropy_coef))
@@ -1925,39 +1903,15 @@ def ppo_adam_step(plain_actor, grad_actor, exp_avg_actor, exp_avg_sq_actor, plai
     first element is the loss), None: no loss gate. lr and eps are a scalar or an (actor, critic) pair; max_norm None means no
     clipping. A NaN loss or a norm of either network that is not finite leaves all eight buffers and both step counters untouched.
     No synchronisation. Returns the two gradient norms before clipping, float32 (2,), written on every call."""
-    buffers = (("plain_actor", plain_actor, 4), ("grad_actor", grad_actor, 4), ("exp_avg_actor", exp_avg_actor, 4),
-               ("exp_avg_sq_actor", exp_avg_sq_actor, 4), ("plain_critic", plain_critic, 1), ("grad_critic", grad_critic, 1),
-               ("exp_avg_critic", exp_avg_critic, 1), ("exp_avg_sq_critic", exp_avg_sq_critic, 1))
-    for name, t, n_out in buffers:          # dtype and length of all eight before any device: such a mistake reads the same everywhere
-        floats = ppo_plain_floats(n_out)
-        if not isinstance(t, torch.Tensor):
-            raise TypeError("g2048: %s must be a torch.Tensor" % name)
-        if t.dtype != torch.float32 or t.dim() != 1 or t.numel() != floats:
-            raise (TypeError if t.dtype != torch.float32 else ValueError)(
-                "g2048: %s must be a flat float32 tensor of %d floats (got %s %s)" % (name, floats, t.dtype, tuple(t.shape)))
-    for name, t, _ in buffers:
-        L.require_device_tensor(t, torch.float32, None, name)
-        if t.device != plain_actor.device:
-            raise ValueError("g2048: %s on %s, plain_actor on %s" % (name, t.device, plain_actor.device))
-    dev = plain_actor.device
-    L.require_device_tensor(counters, torch.int64, None, "counters")
-    if counters.dim() != 1 or counters.numel() != 4:
-        raise ValueError("g2048: counters must be an int64 tensor of 4")
-    if losses is not None:
-        L.require_device_tensor(losses, torch.float32, None, "losses")
-        if losses.numel() < 1:
-            raise ValueError("g2048: losses must hold at least one float32")
-    if norms is None:
-        norms = torch.empty(2, dtype=torch.float32, device=dev)
-    L.require_device_tensor(norms, torch.float32, None, "norms")
-    if norms.numel() != 2:
-        raise ValueError("g2048: norms must hold two float32")
-    nb = ppo_step_workspace_bytes()
-    if workspace is None:
-        workspace = torch.empty(nb, dtype=torch.uint8, device=dev)
-    L.require_device_tensor(workspace, torch.uint8, None, "workspace")
-    if workspace.numel() < nb:
-        raise ValueError("g2048: workspace must hold at least %d bytes" % nb)
+    actor, critic = ppo_plain_floats(4), ppo_plain_floats(1)
+    buffers = (("plain_actor", plain_actor, actor), ("grad_actor", grad_actor, actor), ("exp_avg_actor", exp_avg_actor, actor),
+               ("exp_avg_sq_actor", exp_avg_sq_actor, actor), ("plain_critic", plain_critic, critic), ("grad_critic", grad_critic, critic),
+               ("exp_avg_critic", exp_avg_critic, critic), ("exp_avg_sq_critic", exp_avg_sq_critic, critic))
+    dev = _step_buffers(buffers)
+    _step_counters(counters, 4)
+    _gate_losses(losses)
+    norms = _float_output(norms, (2,), "norms", dev)
+    workspace = _workspace(workspace, ppo_step_workspace_bytes(), dev)
     for t, name in ((counters, "counters"), (losses, "losses"), (norms, "norms"), (workspace, "workspace")):
         if t is not None and t.device != dev:
             raise ValueError("g2048: %s on %s, plain_actor on %s" % (name, t.device, dev))

@@ -159,7 +159,7 @@ def test_dtype_and_shape_checks(built):
 
 def test_missing_library_is_loud(built, monkeypatch, tmp_path):
     from g2048 import _lib, _build
-    monkeypatch.setattr(_lib, "_lib", None)
+    monkeypatch.setattr(_lib.MAIN, "handle", None)
     monkeypatch.setattr(_build, "LIB", str(tmp_path / "nope.so"))
     with pytest.raises(RuntimeError, match="no CPU fallback"):
         _lib.lib()

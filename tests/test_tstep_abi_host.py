@@ -1,28 +1,10 @@
-"""The step library's boundary (csrc/libg2048_tstep_hip.so, include/g2048_tstep.h), the counterpart of
-tests/test_tlearn_abi_host.py for the fourth library: its export table, its header, its binding table and the inventory of bounds
-tests below name the same entry points, no name is shared with the other three libraries, whose tables are still exactly their own,
-the loader is loud, and every argument check of g2048_tpolicy_adam_step happens before any device call (there is no device here)."""
+"""What only the step library has (csrc/libg2048_tstep_hip.so, include/g2048_tstep.h): its workspace arithmetic, every argument
+check of g2048_tpolicy_adam_step before any device call (there is no device here) and the Python layer's refusals. Its export
+table, header, binding table, inventory of bounds tests and loader are checked with the other libraries'
+(tests/test_libraries_abi_host.py)."""
 import ctypes as C
-import os
-import re
-import subprocess
 
 import pytest
-
-from conftest import PKG, REPO
-from test_abi_and_host import declared_symbols
-from test_train_abi_host import exported
-
-GPU = "tests/test_gpu_tpolicy_step.py"
-HOST = "a host function: it writes no device memory"
-
-# per entry point: the GPU test that puts guard bands round what it writes, or (None, the reason it needs none)
-GUARDED_BY = {
-    "g2048_tstep_last_error": (None, HOST),
-    "g2048_tstep_abi_version": (None, HOST),
-    "g2048_tpolicy_step_workspace": (None, "a size query on the host: it writes no device memory"),
-    "g2048_tpolicy_adam_step": GPU + "::test_guard_bands_round_everything_the_entry_point_writes",
-}
 
 
 @pytest.fixture(scope="module")
@@ -31,72 +13,6 @@ def built():
     ge.build()
     from g2048 import _lib
     return _lib
-
-
-def test_step_library_exports_its_header_and_its_binding_table(built):
-    names = declared_symbols("g2048_tstep.h")
-    assert exported(built.tstep_library_path()) == names, (exported(built.tstep_library_path()), names)
-    assert set(names) == set(built.TSTEP_SIGNATURES) == set(GUARDED_BY) and len(names) == 4
-    hdr = open(os.path.join(REPO, "include", "g2048_tstep.h")).read()
-    version = int(re.search(r"#define G2048_TSTEP_ABI_VERSION (\d+)", hdr).group(1))
-    assert version == 1 == built.TSTEP_ABI_VERSION == built.tstep_lib().g2048_tstep_abi_version()
-    assert os.path.basename(built.tstep_library_path()) == "libg2048_tstep_hip.so"
-    assert os.path.dirname(built.tstep_library_path()) == os.path.dirname(built.library_path())
-
-
-def test_the_four_libraries_share_no_entry_point_and_the_other_three_keep_their_tables(built):
-    main, train, tlearn = exported(built.library_path()), exported(built.train_library_path()), exported(built.tlearn_library_path())
-    assert main == declared_symbols() and set(main) == set(built.SIGNATURES), "the main library's export table moved"
-    assert train == declared_symbols("g2048_train.h") and set(train) == set(built.TRAIN_SIGNATURES) and len(train) == 6
-    assert tlearn == declared_symbols("g2048_tlearn.h") and set(tlearn) == set(built.TLEARN_SIGNATURES) and len(tlearn) == 4
-    assert not set(built.TSTEP_SIGNATURES) & (set(main) | set(train) | set(tlearn))
-    assert built.lib().g2048_abi_version() == built.ABI_VERSION == 5
-    assert built.train_lib().g2048_train_abi_version() == built.TRAIN_ABI_VERSION == 1
-    assert built.tlearn_lib().g2048_tlearn_abi_version() == built.TLEARN_ABI_VERSION == 1
-
-
-def test_the_build_counts_the_fourth_library(built):
-    from g2048 import _build
-    assert os.path.basename(_build.TSTEP_LIB) == "libg2048_tstep_hip.so" and _build.TSTEP_SOURCES == ["g2048_tpolicy_step.hip"]
-    assert _build.TLEARN_SOURCES == ["g2048_tpolicy_grad.hip"] and "g2048_tpolicy_step.hip" not in _build.SOURCES + _build.TRAIN_SOURCES
-    assert any(h.endswith("g2048_tstep.h") for h in _build.PUBLIC_HEADERS)
-    assert not _build.needs_build()
-    real = _build.TSTEP_LIB
-    try:
-        _build.TSTEP_LIB = os.path.join(os.path.dirname(real), "absent_tstep.so")
-        assert _build.needs_build(), "needs_build() does not look at the step library"
-    finally:
-        _build.TSTEP_LIB = real
-
-
-def test_every_step_entry_point_has_its_bounds_test_or_a_reason():
-    for name, where in GUARDED_BY.items():
-        if isinstance(where, tuple):
-            none, reason = where
-            assert none is None and isinstance(reason, str) and len(reason.strip()) > 10 and "\n" not in reason, name
-            continue
-        path, _, test = where.partition("::")
-        source = open(os.path.join(REPO, path)).read()
-        assert re.search(r"^def %s\(" % re.escape(test), source, re.M), "%s: %s has no test %s" % (name, path, test)
-        assert "pytest.mark.gpu" in source, "%s: %s is no GPU test file" % (name, path)
-
-
-def test_the_loader_is_loud_and_takes_only_the_product_name(built, tmp_path):
-    """A missing library raises; a library under another name is loaded only through G2048_TSTEP_LIB, and says so."""
-    import shutil
-    import sys
-    code = ("import sys; sys.path.insert(0, %r); from g2048 import _lib\n"
-            "try:\n    print('LOADED', _lib.tstep_lib().g2048_tstep_abi_version())\n"
-            "except RuntimeError as e:\n    print('REFUSED', 'missing' in str(e))\n" % PKG)
-    run = lambda env: subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True)      # noqa: E731
-    out = run(dict(os.environ, G2048_TSTEP_LIB=str(tmp_path / "absent.so")))
-    assert "REFUSED True" in out.stdout, out
-    copy = shutil.copy(built.tstep_library_path(), str(tmp_path / "libab.so"))
-    out = run(dict(os.environ, G2048_TSTEP_LIB=copy))
-    assert "LOADED 1" in out.stdout and "loading the A/B build" in out.stderr, out
-    # without the variable a foreign name is refused: the path is fixed at import, so the refusal is read off the loader's source
-    src = open(os.path.join(PKG, "g2048", "_lib.py")).read()
-    assert 'os.path.basename(path) != "libg2048_tstep_hip.so"' in src
 
 
 def test_workspace_query_refuses_shapes_and_is_a_multiple_of_16(built):

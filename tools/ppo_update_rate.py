@@ -201,11 +201,8 @@ def through(lib, fn):
     from g2048 import _lib
 
     def run():
-        mine, _lib._lib = _lib.lib(), lib
-        try:
+        with _lib.MAIN.swapped(lib):
             return fn()
-        finally:
-            _lib._lib = mine
     return run
 
 
