@@ -61,7 +61,7 @@ struct Sites {
     {
         for (int s = 0; s < 4; ++s) {
             on[s] = p[s] > 0.0;
-            d[s] = qdrop_site(seed, call_index, layer, s, p[s]);
+            d[s] = qdrop_site(kDomQnetDropout, seed, call_index, layer, s, p[s]);
         }
     }
 };
@@ -289,7 +289,7 @@ int g2048_qnet_dropout_mask(uint64_t seed, uint64_t call_index, int layer, int s
         return fail(G2048_ERR_ARG, "%s: rows %zu .. %zu lie past the site's matrix of %zu rows", entry, first_row, first_row + rows, height);
     // at most 32,768 x 4,096 or 4,096 x 65,536 elements: 32 bits hold every index
     hipLaunchKernelGGL(qt_mask_kernel, dim3(blocks_for(rows * width, 256)), dim3(256), 0, static_cast<hipStream_t>(stream), keep_out,
-                       qdrop_site(seed, call_index, layer, site, p), (uint32_t)(first_row * width), (uint32_t)(rows * width));
+                       qdrop_site(kDomQnetDropout, seed, call_index, layer, site, p), (uint32_t)(first_row * width), (uint32_t)(rows * width));
     return check_launch(entry);
 }
 

@@ -28,6 +28,8 @@ G2048_RNG_HD uint64_t splitmix64(uint64_t x)
 constexpr uint32_t kDomDropout = 11;
 // RNG domain 12: the dropout masks of the Q-network's training-mode forwards (g2048_qnet_drop.h, g2048_qnet_train.hip)
 constexpr uint32_t kDomQnetDropout = 12;
+// RNG domain 13: the dropout masks of the transformer policy's training-mode forwards (g2048_tpolicy_train.hip)
+constexpr uint32_t kDomTpolicyDropout = 13;
 
 struct Keys { uint32_t k0, k1; };
 

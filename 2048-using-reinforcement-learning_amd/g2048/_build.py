@@ -1,10 +1,11 @@
-"""Builds csrc/libg2048_hip.so, csrc/libg2048_train_hip.so, csrc/libg2048_tlearn_hip.so and csrc/libg2048_tstep_hip.so for gfx950
-with hipcc (cross-compiles without a GPU).
+"""Builds csrc/libg2048_hip.so, csrc/libg2048_train_hip.so, csrc/libg2048_tlearn_hip.so, csrc/libg2048_tstep_hip.so and
+csrc/libg2048_ttrain_hip.so for gfx950 with hipcc (cross-compiles without a GPU).
 
     python -m g2048._build [-o LIBRARY] [extra compiler flags ...]           (from the package directory)
     python -m g2048._build --train [-o LIBRARY] [extra compiler flags ...]   (the training library alone)
     python -m g2048._build --tlearn [-o LIBRARY] [extra compiler flags ...]  (the transformer policy's learner library alone)
     python -m g2048._build --tstep [-o LIBRARY] [extra compiler flags ...]   (the transformer policy's optimiser-step library alone)
+    python -m g2048._build --ttrain [-o LIBRARY] [extra compiler flags ...]  (the transformer policy's training-mode library alone)
 
 The libraries are built in-tree so that they travel with the source snapshot; they are
 git-ignored. -ffp-contract=off is REQUIRED: the reward / heuristic kernels follow
@@ -17,6 +18,8 @@ libg2048_tlearn_hip.so (include/g2048_tlearn.h) holds the transformer policy's P
 the same reason: the training library's table is closed too.
 libg2048_tstep_hip.so (include/g2048_tstep.h) holds the transformer policy's NaN gate, clipping and Adam step, a fourth library:
 the learner library's table is closed as well.
+libg2048_ttrain_hip.so (include/g2048_ttrain.h) holds the transformer policy's training-mode passes (the encoder's live dropout), a
+fifth library for the same reason; its kernels are the learner library's, shared as csrc/g2048_tpolicy_grad_pass.h.
 """
 import os
 import shutil
@@ -35,6 +38,7 @@ LIBRARIES = {
     "TRAIN_": ("libg2048_train_hip.so", "G2048_TRAIN_LIB", ["g2048_qnet_train.hip"], ["g2048_train.h"]),
     "TLEARN_": ("libg2048_tlearn_hip.so", "G2048_TLEARN_LIB", ["g2048_tpolicy_grad.hip"], ["g2048_tlearn.h"]),
     "TSTEP_": ("libg2048_tstep_hip.so", "G2048_TSTEP_LIB", ["g2048_tpolicy_step.hip"], ["g2048_tstep.h"]),
+    "TTRAIN_": ("libg2048_ttrain_hip.so", "G2048_TTRAIN_LIB", ["g2048_tpolicy_train.hip"], ["g2048_ttrain.h"]),
 }
 PUBLIC_HEADERS = [os.path.join(INCLUDE, h) for row in LIBRARIES.values() for h in row[3]]
 # LIB, SOURCES, TRAIN_LIB, TRAIN_SOURCES, ...: what the loader, the tools and the tests read; needs_build() and build() read the
@@ -91,7 +95,7 @@ def build(force=False, verbose=False, lib=None, extra_flags=()):
     return path_of("")
 
 
-if __name__ == "__main__":          # [--train | --tlearn | --tstep] [-o LIBRARY] [extra compiler flags ...]
+if __name__ == "__main__":          # [--train | --tlearn | --tstep | --ttrain] [-o LIBRARY] [extra compiler flags ...]
     out, args = None, sys.argv[1:]
     key = next((k for k in LIBRARIES if k and args[:1] == ["--" + k[:-1].lower()]), None)
     if key:

@@ -108,6 +108,26 @@ def checked_layers(name, enc, d_model, nhead=None, batch_first=False):
     return layers, dim_ff
 
 
+def dropout_of(name, p, dropout):
+    """The four dropout probabilities (attention, dropout1, dropout, dropout2) of a device network's `dropout` argument for the
+    parsed module p: a probability for all four sites, a 4-tuple, or "module" for the layers' own self_attn.dropout, dropout1.p,
+    dropout.p and dropout2.p, which must agree from layer to layer (the masks differ per layer, the probabilities are shared).
+    Raises ValueError for anything else and for a probability outside 0 <= p < 1."""
+    if isinstance(dropout, str):
+        if dropout != "module":
+            _refuse(name, "dropout must be a probability, a 4-tuple %s or \"module\", got %r" % (ops.QNET_DROPOUT_SITES, dropout))
+        per_layer = [(float(lay.self_attn.dropout), float(lay.dropout1.p), float(lay.dropout.p), float(lay.dropout2.p)) for lay in p.layers]
+        for i, t in enumerate(per_layer):
+            if t != per_layer[0]:
+                _refuse(name, "dropout=\"module\": encoder layer %d has dropout %s, layer 0 has %s; the device pass shares one set of "
+                              "probabilities among the layers" % (i, t, per_layer[0]))
+        dropout = per_layer[0]
+    try:
+        return ops.qnet_dropout_p(dropout) or (0.0, 0.0, 0.0, 0.0)
+    except (TypeError, ValueError) as e:
+        _refuse(name, str(e)[7:] if str(e).startswith("g2048: ") else "dropout: " + str(e))
+
+
 def layer_tensors(layers):
     """The encoder layers' parameters in the plain layout's order: state-dict order, then the two LayerNorm eps as Python floats."""
     seq = []
@@ -163,13 +183,15 @@ def weight_caster(dtype, round_weights=None):
     return w
 
 
-def post_norm_tail(lay, x, attended, w):
+def post_norm_tail(lay, x, attended, w, mult=None):
     """The rest of a post-norm encoder layer after the attention itself: norm1(x + out_proj(attended)), then the feed-forward
-    pair and norm2, with the weights through w."""
+    pair and norm2, with the weights through w. mult: None (eval mode), or a callable (site, shape, dtype) -> the multipliers of
+    dropout site 1 (dropout1), 2 (the hidden layer's) or 3 (dropout2) of this layer, applied where the training-mode layer drops."""
     a, d = lay.self_attn, (x.shape[-1],)
-    x = F.layer_norm(x + attended @ w(a.out_proj.weight).T + w(a.out_proj.bias), d, w(lay.norm1.weight), w(lay.norm1.bias), lay.norm1.eps)
-    h = torch.relu(x @ w(lay.linear1.weight).T + w(lay.linear1.bias))
-    return F.layer_norm(x + h @ w(lay.linear2.weight).T + w(lay.linear2.bias), d, w(lay.norm2.weight), w(lay.norm2.bias), lay.norm2.eps)
+    m = (lambda site, t: t) if mult is None else (lambda site, t: t * mult(site, tuple(t.shape), t.dtype))
+    x = F.layer_norm(x + m(1, attended @ w(a.out_proj.weight).T + w(a.out_proj.bias)), d, w(lay.norm1.weight), w(lay.norm1.bias), lay.norm1.eps)
+    h = m(2, torch.relu(x @ w(lay.linear1.weight).T + w(lay.linear1.bias)))
+    return F.layer_norm(x + m(3, h @ w(lay.linear2.weight).T + w(lay.linear2.bias)), d, w(lay.norm2.weight), w(lay.norm2.bias), lay.norm2.eps)
 
 
 class OutputCache:

@@ -1,5 +1,5 @@
-"""ctypes binding of the C-ABI in include/g2048.h (csrc/libg2048_hip.so) and of the three libraries beside it (g2048_train.h,
-g2048_tlearn.h, g2048_tstep.h): one Library per row of _build.LIBRARIES, each with its own table, error string and version.
+"""ctypes binding of the C-ABI in include/g2048.h (csrc/libg2048_hip.so) and of the four libraries beside it (g2048_train.h,
+g2048_tlearn.h, g2048_tstep.h, g2048_ttrain.h): one Library per row of _build.LIBRARIES, each with its own table, error string and version.
 
 There is no fallback: if the library is missing or no HIP device is visible, every
 compute call raises. PyTorch is only used for device memory and streams -- tensors
@@ -167,6 +167,16 @@ TSTEP_SIGNATURES = {
     "g2048_tpolicy_adam_step": (_int, [_vp] * 4 + [_int, _int, _vp, _vp] + [_f] * 5 + [_vp, _vp, _sz, _vp]),
 }
 
+TTRAIN_ABI_VERSION = 1
+TTRAIN_SIGNATURES = {
+    "g2048_ttrain_last_error": (C.c_char_p, []),
+    "g2048_ttrain_abi_version": (_int, []),
+    "g2048_tpolicy_train_workspace": (_sz, [_sz, _int, _int]),
+    "g2048_tpolicy_loss_grad_dropout": (_int, [_vp] * 6 + [_sz, _int, _int, _p4, _u64, _u64, _f, _f, _f] + [_vp] * 5 + [_sz, _vp]),
+    "g2048_tpolicy_forward_dropout": (_int, [_vp, _vp, _sz, _int, _int, _p4, _u64, _u64, _vp, _vp, _vp, _sz, _vp]),
+    "g2048_tpolicy_dropout_mask": (_int, [_u64, _u64, _int, _int, C.c_double, _sz, _int, _sz, _sz, _vp, _vp]),
+}
+
 
 class Library:
     """One shared object of _build.LIBRARIES (row `key`), loaded on first use and as loud as can be: a missing file, a file under
@@ -247,13 +257,16 @@ MAIN = Library("", "g2048", SIGNATURES, ABI_VERSION, after_load=_refuse_instrume
 TRAIN = Library("TRAIN_", "g2048_train", TRAIN_SIGNATURES, TRAIN_ABI_VERSION, "training", " and no training pass without it")
 TLEARN = Library("TLEARN_", "g2048_tlearn", TLEARN_SIGNATURES, TLEARN_ABI_VERSION, "learner", " and no gradient pass without it")
 TSTEP = Library("TSTEP_", "g2048_tstep", TSTEP_SIGNATURES, TSTEP_ABI_VERSION, "step", " and no device optimiser step without it")
-LIBRARIES = {"": MAIN, "TRAIN_": TRAIN, "TLEARN_": TLEARN, "TSTEP_": TSTEP}
+TTRAIN = Library("TTRAIN_", "g2048_ttrain", TTRAIN_SIGNATURES, TTRAIN_ABI_VERSION, "policy training",
+                 " and no training-mode pass of the transformer policy without it")
+LIBRARIES = {"": MAIN, "TRAIN_": TRAIN, "TLEARN_": TLEARN, "TSTEP_": TSTEP, "TTRAIN_": TTRAIN}
 
 # the names the package, the tools and the tests call
 library_path, lib, check, call = MAIN.path, MAIN.load, MAIN.check, MAIN.call
 train_library_path, train_lib, train_call = TRAIN.path, TRAIN.load, TRAIN.call
 tlearn_library_path, tlearn_lib, tlearn_call = TLEARN.path, TLEARN.load, TLEARN.call
 tstep_library_path, tstep_lib, tstep_call = TSTEP.path, TSTEP.load, TSTEP.call
+ttrain_library_path, ttrain_lib, ttrain_call = TTRAIN.path, TTRAIN.load, TTRAIN.call
 
 
 def stream_ptr(device):

@@ -604,7 +604,7 @@ def tpolicy_grad_workspace_bytes(n, dim_ff, n_layers):
 
 
 def tpolicy_loss_grad(boards, plain, actions, old_log_probs, advantages, returns, dim_ff, n_layers, clip_epsilon=0.3, value_coef=0.4,
-                      entropy_coef=0.05, grad=None, losses=None, probs=None, value=None, workspace=None):
+                      entropy_coef=0.05, grad=None, losses=None, probs=None, value=None, workspace=None, dropout=None, seed=0, call_index=0):
     """PPOAgent.update()'s loss (agents/ppo_agent.py:378-400) on the transformer policy's two heads and its gradient, on the device
     (g2048_tpolicy_loss_grad, the learner library): probs, value = the eval-mode module on boards / 15; loss = actor + value_coef
     value_loss - entropy_coef entropy with the clipped surrogate of exp(log probs[i, actions[i]] - old_log_probs[i]) against
@@ -612,7 +612,11 @@ def tpolicy_loss_grad(boards, plain, actions, old_log_probs, advantages, returns
     layout of `plain` (the LayerNorm-eps slots 0), overwritten, never accumulated into. boards uint8 (n,16), actions int64 (n,),
     old_log_probs, advantages, returns float32 (n,), plain the PLAIN float32 parameter buffer (tpolicy_plain_floats). f32 only. An
     action outside 0..3 is the caller's error (the kernel reads actions & 3). A sequence of launches on the current stream, no
-    synchronisation. Returns (losses float32 (4,) = loss, actor, value, entropy; probs float32 (n,4); value float32 (n,1); grad)."""
+    synchronisation. dropout: None, 0 or all zeros: eval mode through the learner library, as ever. A probability or a 4-tuple
+    (qnet_dropout_p): the module's TRAINING-mode pass with the masks of (seed, call_index) (tpolicy_dropout_mask), regenerated in
+    the backward (the training library's g2048_tpolicy_loss_grad_dropout; the workspace is then tpolicy_train_workspace_bytes').
+    Returns (losses float32 (4,) = loss, actor, value, entropy; probs float32 (n,4); value float32 (n,1); grad)."""
+    p = qnet_dropout_p(dropout)
     L.require_device_tensor(boards, torch.uint8, (16,), "boards")
     L.require_device_tensor(plain, torch.float32, None, "plain")
     L.require_device_tensor(actions, torch.int64, (), "actions")
@@ -638,12 +642,84 @@ def tpolicy_loss_grad(boards, plain, actions, old_log_probs, advantages, returns
     value = _output(value, n, torch.float32, (1,), "value", dev)
     if n == 0:
         return losses, probs, value, grad
-    workspace = _workspace(workspace, tpolicy_grad_workspace_bytes(n, dim_ff, n_layers), dev)
-    L.tlearn_call(dev, L.tlearn_lib().g2048_tpolicy_loss_grad, boards.data_ptr(), plain.data_ptr(), actions.data_ptr(),
-                  old_log_probs.data_ptr(), advantages.data_ptr(), returns.data_ptr(), n, int(dim_ff), int(n_layers), float(clip_epsilon),
-                  float(value_coef), float(entropy_coef), grad.data_ptr(), losses.data_ptr(), probs.data_ptr(), value.data_ptr(),
-                  workspace.data_ptr(), workspace.numel(), L.stream_ptr(dev))
+    nb = tpolicy_grad_workspace_bytes(n, dim_ff, n_layers) if p is None else tpolicy_train_workspace_bytes(n, dim_ff, n_layers)
+    workspace = _workspace(workspace, nb, dev)
+    if p is None:
+        L.tlearn_call(dev, L.tlearn_lib().g2048_tpolicy_loss_grad, boards.data_ptr(), plain.data_ptr(), actions.data_ptr(),
+                      old_log_probs.data_ptr(), advantages.data_ptr(), returns.data_ptr(), n, int(dim_ff), int(n_layers), float(clip_epsilon),
+                      float(value_coef), float(entropy_coef), grad.data_ptr(), losses.data_ptr(), probs.data_ptr(), value.data_ptr(),
+                      workspace.data_ptr(), workspace.numel(), L.stream_ptr(dev))
+    else:
+        L.ttrain_call(dev, L.ttrain_lib().g2048_tpolicy_loss_grad_dropout, boards.data_ptr(), plain.data_ptr(), actions.data_ptr(),
+                      old_log_probs.data_ptr(), advantages.data_ptr(), returns.data_ptr(), n, int(dim_ff), int(n_layers), _p4(p), L.u64(seed),
+                      L.u64(call_index), float(clip_epsilon), float(value_coef), float(entropy_coef), grad.data_ptr(), losses.data_ptr(),
+                      probs.data_ptr(), value.data_ptr(), workspace.data_ptr(), workspace.numel(), L.stream_ptr(dev))
     return losses, probs, value, grad
+
+
+def tpolicy_train_workspace_bytes(n, dim_ff, n_layers):
+    """Bytes of the workspace tpolicy_loss_grad with dropout and tpolicy_forward_train need for n boards
+    (g2048_tpolicy_train_workspace, the training library): tpolicy_grad_workspace_bytes plus one (16 n, 64) float32 array."""
+    nb = L.ttrain_lib().g2048_tpolicy_train_workspace(int(n), int(dim_ff), int(n_layers))
+    if nb == 0:
+        raise ValueError("g2048: the transformer policy's training passes take 1 .. %d boards (16 tokens each; a larger batch is refused, "
+                         "not truncated), a dim_ff that is a multiple of 32 and 1 .. 64 layers (got n = %d, dim_ff = %d, n_layers = %d)"
+                         % (L.TLEARN_BATCH_MAX, int(n), int(dim_ff), int(n_layers)))
+    return nb
+
+
+def tpolicy_forward_train(boards, plain, dim_ff, n_layers, dropout, seed=0, call_index=0, probs=None, value=None, workspace=None):
+    """The transformer policy's TRAINING-mode forward on uint8 (n,16) boards, in f32 from the PLAIN parameter buffer
+    (g2048_tpolicy_forward_dropout, the training library): the forward launches of tpolicy_loss_grad with the masks of (seed,
+    call_index) and the two heads; at equal (seed, call_index) the bits of the probs and value tpolicy_loss_grad returns. dropout:
+    a probability or a 4-tuple (qnet_dropout_p; None, 0 or all zeros run the same launches without a mask). workspace: a uint8
+    device tensor of at least tpolicy_train_workspace_bytes(n, dim_ff, n_layers) (allocated when None). No synchronisation.
+    Returns (probs float32 (n,4), value float32 (n,1))."""
+    p = qnet_dropout_p(dropout) or (0.0, 0.0, 0.0, 0.0)
+    L.require_device_tensor(boards, torch.uint8, (16,), "boards")
+    L.require_device_tensor(plain, torch.float32, None, "plain")
+    n, dev = boards.shape[0], boards.device
+    floats = tpolicy_plain_floats(dim_ff, n_layers)
+    if plain.dim() != 1 or plain.numel() != floats:
+        raise ValueError("g2048: plain must be a flat float32 tensor of %d parameters" % floats)
+    probs = _output(probs, n, torch.float32, (4,), "probs", dev)
+    value = _output(value, n, torch.float32, (1,), "value", dev)
+    if n == 0:
+        return probs, value
+    workspace = _workspace(workspace, tpolicy_train_workspace_bytes(n, dim_ff, n_layers), dev)
+    L.ttrain_call(dev, L.ttrain_lib().g2048_tpolicy_forward_dropout, boards.data_ptr(), plain.data_ptr(), n, int(dim_ff), int(n_layers), _p4(p),
+                  L.u64(seed), L.u64(call_index), probs.data_ptr(), value.data_ptr(), workspace.data_ptr(), workspace.numel(), L.stream_ptr(dev))
+    return probs, value
+
+
+def tpolicy_dropout_mask(n, layer, site, p, dim_ff=2048, seed=0, call_index=0, first_row=0, rows=None, device="cuda", out=None):
+    """The keep bits of rows [first_row, first_row + rows) of one dropout site of one call of the transformer policy's training
+    passes (g2048_tpolicy_dropout_mask), written through the function the kernels draw them with: uint8 (rows, columns), 1 where
+    the element is kept. The site's matrix is (64 n, 16) for site 0 (row = (board 4 + head) 16 + query, column = key), (16 n, 64)
+    for sites 1 and 3 and (16 n, dim_ff) for site 2 (row = token = 16 board + cell); rows None: down to the matrix's last row.
+    Element e = row columns + column of site s of encoder layer `layer` is kept iff rng_draw(rng_keys(seed, 13, call_index),
+    ((4 layer + s) << 32) | e, 0) >= floor(p 2^32); a kept element is multiplied by float32(1 / (1 - p)), a dropped one by 0. No
+    synchronisation."""
+    n, layer, site, first_row = int(n), int(layer), int(site), int(first_row)
+    if site not in (0, 1, 2, 3):
+        raise ValueError("g2048: site must be 0 .. 3 %s" % (QNET_DROPOUT_SITES,))
+    if not 0 <= layer < 64:
+        raise ValueError("g2048: layer must be 0 .. 63")
+    p = float(p)
+    if not 0.0 <= p < 1.0:
+        raise ValueError("g2048: p must be finite, 0 <= p < 1 (got %r)" % p)
+    if not 0 <= n <= L.TLEARN_BATCH_MAX:
+        raise ValueError("g2048: a dropout mask is of 0 .. %d boards (the gradient pass's limit); got n = %d" % (L.TLEARN_BATCH_MAX, n))
+    height, width = (64 * n, 16) if site == 0 else (16 * n, int(dim_ff) if site == 2 else 64)
+    rows = height - first_row if rows is None else int(rows)
+    if first_row < 0 or rows < 0 or first_row + rows > height:
+        raise ValueError("g2048: rows %d .. %d lie past the site's matrix of %d rows" % (first_row, first_row + rows, height))
+    dev = torch.device(device)
+    out = _output(out, rows, torch.uint8, (width,), "out", dev)
+    if n and rows:
+        L.ttrain_call(out.device, L.ttrain_lib().g2048_tpolicy_dropout_mask, L.u64(seed), L.u64(call_index), layer, site, p, n, int(dim_ff),
+                      first_row, rows, out.data_ptr(), L.stream_ptr(out.device))
+    return out
 
 
 def tpolicy_step_workspace_bytes(dim_ff, n_layers):

@@ -141,23 +141,8 @@ def forward_batch_reference(p, boards, dtype=torch.float64):
 
 
 def dropout_of(p, dropout):
-    """The four dropout probabilities (attention, dropout1, dropout, dropout2) of DeviceQNetwork's `dropout` for the parsed module
-    p: a probability for all four sites, a 4-tuple, or "module" for the layers' own self_attn.dropout, dropout1.p, dropout.p and
-    dropout2.p, which must agree from layer to layer (the masks differ per layer, the probabilities are shared). Raises ValueError
-    for anything else and for a probability outside 0 <= p < 1."""
-    if isinstance(dropout, str):
-        if dropout != "module":
-            E._refuse(NAME, "dropout must be a probability, a 4-tuple %s or \"module\", got %r" % (ops.QNET_DROPOUT_SITES, dropout))
-        per_layer = [(float(lay.self_attn.dropout), float(lay.dropout1.p), float(lay.dropout.p), float(lay.dropout2.p)) for lay in p.layers]
-        for i, t in enumerate(per_layer):
-            if t != per_layer[0]:
-                E._refuse(NAME, "dropout=\"module\": encoder layer %d has dropout %s, layer 0 has %s; the device pass shares one set of "
-                                "probabilities among the layers" % (i, t, per_layer[0]))
-        dropout = per_layer[0]
-    try:
-        return ops.qnet_dropout_p(dropout) or (0.0, 0.0, 0.0, 0.0)
-    except (TypeError, ValueError) as e:
-        E._refuse(NAME, str(e)[7:] if str(e).startswith("g2048: ") else "dropout: " + str(e))
+    """The four dropout probabilities of DeviceQNetwork's `dropout` for the parsed module p (_encoder_net.dropout_of)."""
+    return E.dropout_of(NAME, p, dropout)
 
 
 def _check_loss_inputs(n, actions, targets, weights):

@@ -1,4 +1,5 @@
-"""The reference's transformer policy (models/transformer.py:4-40, eval mode) as one HIP launch on the packed boards.
+"""The reference's transformer policy (models/transformer.py:4-40) as one HIP launch on the packed boards, and its PPO update on
+the device.
 
 `DeviceTransformerPolicy(model, precision="f32")` takes a torch module of that structure, flattens its parameters into the
 plain layout of include/g2048.h (state-dict order, plus the two LayerNorm eps per layer), packs them with `g2048_tpolicy_pack`
@@ -79,9 +80,12 @@ F32_EPS = float(torch.finfo(torch.float32).eps)
 
 
 def loss_grad_reference(p, boards, actions, old_log_probs, advantages, returns, clip_epsilon=0.3, value_coef=0.4, entropy_coef=0.05,
-                        dtype=torch.float64, eps=F32_EPS):
+                        dtype=torch.float64, eps=F32_EPS, multipliers=None):
     """PPOAgent.update()'s loss (agents/ppo_agent.py:378-400) on the parsed module's two heads, in eval mode, with plain torch ops
-    in `dtype` and autograd over the ops of forward_reference:
+    in `dtype` and autograd over the ops of forward_reference. multipliers: None, or a callable (layer, site, shape, dtype) -> the
+    dropout multipliers (keep x 1 / (1 - p)) of site 0 (the attention probabilities, (N,4,16,16)), 1 (dropout1, (N,16,64)), 2 (the
+    hidden layer, (N,16,dim_ff)) or 3 (dropout2, (N,16,64)) of encoder layer `layer`: with it the function is the TRAINING-mode
+    module's under those masks.
         logp = log(probs[i, actions[i]]), ratio = exp(logp - old_log_probs),
         actor = -mean(min(ratio adv, clamp(ratio, 1 - clip, 1 + clip) adv)), vloss = mean((value[:, 0] - returns)^2),
         ent = mean(Categorical(probs).entropy()), loss = actor + value_coef vloss - entropy_coef ent.
@@ -98,12 +102,15 @@ def loss_grad_reference(p, boards, actions, old_log_probs, advantages, returns, 
     with torch.enable_grad():
         x = boards.to(dtype) / 15
         x = x.reshape(-1, TOKENS, 1) * w(p.embedding.weight).reshape(1, 1, -1) + w(p.embedding.bias)
-        for lay in p.layers:
+        for i, lay in enumerate(p.layers):
             a = lay.self_attn
+            mult = None if multipliers is None else (lambda site, shape, dt, i=i: multipliers(i, site, shape, dt))
             qkv = x @ w(a.in_proj_weight).T + w(a.in_proj_bias)
             q, k, v = (t.reshape(n, TOKENS, N_HEAD, -1).transpose(1, 2) for t in qkv.split(D_MODEL, -1))
             s = torch.softmax((q @ k.transpose(-1, -2)) / 4, -1)
-            x = E.post_norm_tail(lay, x, (s @ v).transpose(1, 2).reshape(n, TOKENS, D_MODEL), w)
+            if mult is not None:
+                s = s * mult(0, tuple(s.shape), s.dtype)
+            x = E.post_norm_tail(lay, x, (s @ v).transpose(1, 2).reshape(n, TOKENS, D_MODEL), w, mult)
         h = torch.relu(x.reshape(n, -1) @ w(p.fc1.weight).T + w(p.fc1.bias))
         h = torch.relu(h @ w(p.fc2.weight).T + w(p.fc2.bias))
         probs = torch.softmax(h @ w(p.actor.weight).T + w(p.actor.bias), -1)
@@ -160,6 +167,8 @@ class DeviceTransformerPolicy(E.PackedNet):
     adam_step(losses) is the rest of a PPO epoch on the device (NaN gate, clipping, Adam: net.exp_avg, net.exp_avg_sq,
     net.opt_counters), update(...) the whole of PPOAgent.update() after its sampling without a host read, and
     optimizer_state_dict() / load_optimizer_state_dict() exchange the state with torch.optim.Adam(model.parameters()).
+    dropout, dropout_seed: what the TRAINING forwards apply (loss_and_grad, advantages, update); the module docstring. 0.0, the
+    default: none, through the entry points and with the bits of a policy built without the argument.
 
     takes_boards = True: RolloutCollector hands it the packed boards instead of the float observations."""
 
@@ -167,12 +176,35 @@ class DeviceTransformerPolicy(E.PackedNet):
     name, parse = NAME, staticmethod(parse)
     plain_floats, packed_bytes, pack = map(staticmethod, (ops.tpolicy_plain_floats, ops.tpolicy_packed_bytes, ops.tpolicy_pack))
 
+    def __init__(self, model, precision="f32", dropout=0.0, dropout_seed=0):
+        self.dropout = E.dropout_of(NAME, parse(model), dropout)    # (attention, dropout1, dropout, dropout2)
+        self.dropout_seed, self.dropout_index = ops.L.u64(dropout_seed), 0
+        super().__init__(model, precision)
+
+    def dropout_state(self):
+        """(dropout_seed, dropout_index): with the weights, what reproduces the masks of every later training forward."""
+        return self.dropout_seed, self.dropout_index
+
+    def set_dropout_state(self, state):
+        seed, index = state
+        if int(index) < 0:
+            raise ValueError("%s: the dropout index must not be negative" % NAME)
+        self.dropout_seed, self.dropout_index = ops.L.u64(seed), int(index)
+
+    def _next_index(self):
+        index = self.dropout_index
+        self.dropout_index = index + 1
+        return index
+
     def __call__(self, boards):
         probs, value = self._out.get(self._out.rows(boards), _outputs)
         return ops.tpolicy_forward(boards, self.packed, self.dim_ff, self.n_layers, self.precision, probs=probs, value=value)
 
     def _grad_workspace(self, n, device):           # refuses n = 0 and n above the maximum
         return torch.empty(ops.tpolicy_grad_workspace_bytes(n, self.dim_ff, self.n_layers), dtype=torch.uint8, device=device)
+
+    def _train_workspace(self, n, device):          # the training passes': one more array
+        return torch.empty(ops.tpolicy_train_workspace_bytes(n, self.dim_ff, self.n_layers), dtype=torch.uint8, device=device)
 
     def loss_and_grad(self, boards, actions, old_log_probs, advantages, returns, clip_epsilon=0.3, value_coef=0.4, entropy_coef=0.05):
         """(losses float32 (4,) = loss, actor loss, value loss, entropy; probs float32 (N,4); value float32 (N,1)) of
@@ -182,7 +214,9 @@ class DeviceTransformerPolicy(E.PackedNet):
         activations kept, the loss head, the backward, one phase per launch; no host synchronisation). 1 <= N <= 1024. The pass
         is f32 and reads net.plain, whatever precision the acting blob is packed in. An action outside 0..3 is the caller's
         error (the kernel reads actions & 3). The outputs and the workspace are the network's (one set per (N, stream)): after
-        the first call per (N, stream) nothing is allocated."""
+        the first call per (N, stream) nothing is allocated. This is a training forward: with any net.dropout > 0 it is the
+        module's TRAINING-mode pass (g2048_tpolicy_loss_grad_dropout) under the masks of (net.dropout_seed, net.dropout_index),
+        regenerated in the backward; the index counts on either way, and with dropout 0 the call and its bits are as ever."""
         return self._loss_and_grad(boards, actions, old_log_probs, advantages, returns, clip_epsilon, value_coef, entropy_coef, None)
 
     def _loss_and_grad(self, boards, actions, old_log_probs, advantages, returns, clip_epsilon, value_coef, entropy_coef, losses_row):
@@ -198,18 +232,29 @@ class DeviceTransformerPolicy(E.PackedNet):
             losses = losses_row
         ops.tpolicy_loss_grad(boards, self.plain, actions, old_log_probs, advantages, returns, self.dim_ff, self.n_layers, clip_epsilon,
                               value_coef, entropy_coef, grad=self.grad, losses=losses, probs=probs, value=value,
-                              workspace=self._out.get(n, self._grad_workspace) if n else None)
+                              workspace=self._out.get(n, self._train_workspace if any(self.dropout) else self._grad_workspace) if n else None,
+                              dropout=self.dropout, seed=self.dropout_seed, call_index=self._next_index())
         return losses, probs, value
 
-    def advantages(self, boards, next_boards, rewards, dones, gamma=0.995):
+    def advantages(self, boards, next_boards, rewards, dones, gamma=0.995, training=None):
         """(returns, advantages) float32 (N,) of PPOAgent.update()'s first block (agents/ppo_agent.py:357-373) with this network's
         critic head: two f32 forwards (through a blob packed from net.plain at f32: the acting blob when precision is "f32"),
         returns = rewards + gamma * value(next_boards) * (1 - dones), advantages = returns - value(boards), normalised by their
         mean and unbiased std (+ 1e-8) when N > 1 (g2048_ppo_advantages). rewards, dones float32 (N,). The outputs are the
-        network's (one pair per (N, stream)); no synchronisation."""
+        network's (one pair per (N, stream)); no synchronisation. training: None means training iff any net.dropout > 0. Training
+        is the reference's block with the network in training mode: two g2048_tpolicy_forward_dropout calls from net.plain, boards
+        first and then next_boards, with two consecutive dropout indices (1 <= N <= 1024). Otherwise the two fused eval-mode
+        forwards run, and the index stays."""
         n = self._out.rows(boards)
         if self._out.rows(next_boards) != n:
             raise ValueError("%s.advantages: boards and next_boards must have the same number of rows" % NAME)
+        if any(self.dropout) if training is None else training:
+            probs, value, next_value, returns, adv = self._out.get(n, _advantage_buffers)
+            workspace = self._out.get(n, self._train_workspace) if n else None
+            for b, v in ((boards, value), (next_boards, next_value)):
+                ops.tpolicy_forward_train(b, self.plain, self.dim_ff, self.n_layers, self.dropout, self.dropout_seed, self._next_index(),
+                                          probs=probs, value=v, workspace=workspace)
+            return ops.ppo_advantages(value, next_value, rewards, dones, gamma, returns=returns, advantages=adv)
         packed = self.packed
         if self.precision != "f32":
             packed = self._out.get(0, self._f32_blob)
@@ -268,7 +313,9 @@ class DeviceTransformerPolicy(E.PackedNet):
         module. A sequence of launches with no host decision and no host read: an epoch whose loss is a NaN or whose gradient is
         not finite is skipped on the device and shows in opt_counters and in the returned rows. Returns (losses float32
         (epochs,4), norms float32 (epochs,)), device tensors the network owns (one pair per (epochs, stream)): row e is epoch e's
-        loss_and_grad result and its gradient norm before clipping."""
+        loss_and_grad result and its gradient norm before clipping. With dropout one update uses 2 + epochs consecutive dropout
+        indices, in that order (the advantage block's two forwards, then the epochs), still with no host read. A captured graph of
+        update() replays the masks it was captured with: the indices are kernel arguments, as for DevicePPOLearner."""
         epochs = int(epochs)
         if epochs < 1:
             raise ValueError("%s: update needs at least one epoch" % NAME)

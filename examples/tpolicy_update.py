@@ -2,7 +2,7 @@
 """A PPO update of the reference's transformer policy (models/transformer.py) with its loss, gradients and optimiser on the GPU.
 
     python examples/tpolicy_update.py [--envs 256] [--updates 5] [--epochs 3] [--dim-ff 2048] [--precision f32|bf16] [--lr 3e-4]
-                                      [--optimizer device|torch]
+                                      [--optimizer device|torch] [--dropout P|module] [--dropout-seed S]
 
 A stock-torch module with the reference's layout, a VecGame2048 batch, one step of every env acted by
 g2048.DeviceTransformerPolicy (the probabilities of one g2048_tpolicy_forward launch, PPOAgent.get_action's masked sampling), then
@@ -14,7 +14,10 @@ net.loss_and_grad (:378-400 on the two heads, eval mode: the forward with its ac
 the device, the gradients landing in the views attach_grads() gave the module's parameters), clip_grad_norm_ at 0.5, a stock
 torch.optim.Adam on the views attach_params() made of net.plain, and net.refresh() (which then only packs the acting blob again).
 No gradient copy and no host synchronisation inside an update; the loss parts are read back once per update, to print them.
---envs is at most 1,024, the pass's limit. The script shows that the pieces fit; it makes no claim about learning.
+--envs is at most 1,024, the pass's limit. --dropout P (or "module" for the layers' own 0.1) makes the update the reference's: its
+networks stay in training mode through PPOAgent.update(), so the advantage block's two critic forwards and every epoch's forward run
+the encoder's four dropout sites, here with counter-RNG masks keyed by (--dropout-seed, net.dropout_index) and regenerated in the
+backward pass; acting stays eval mode. The script shows that the pieces fit; it makes no claim about learning.
 """
 import argparse
 import os
@@ -35,7 +38,10 @@ ap.add_argument("--precision", choices=("f32", "bf16"), default="f32", help="of 
 ap.add_argument("--lr", type=float, default=3e-4)
 ap.add_argument("--optimizer", choices=("device", "torch"), default="device",
                 help="device: net.update(), clipping and Adam in the library; torch: clip_grad_norm_ and torch.optim.Adam on attached views")
+ap.add_argument("--dropout", default="0", help="a probability for the encoder's four dropout sites, or 'module' for the layers' own; 0: eval mode")
+ap.add_argument("--dropout-seed", type=int, default=0)
 a = ap.parse_args()
+dropout = a.dropout if a.dropout == "module" else float(a.dropout)
 if not 1 <= a.envs <= 1024:
     sys.exit("--envs must be 1 .. 1024: loss_and_grad takes at most 1,024 boards a call")
 
@@ -52,7 +58,8 @@ class TransformerModel(nn.Module):      # the reference's layout (models/transfo
 
 dev, seed = torch.device("cuda"), 1
 torch.manual_seed(0)
-net = g2048.DeviceTransformerPolicy(TransformerModel(a.dim_ff).to(dev).eval(), precision=a.precision)
+net = g2048.DeviceTransformerPolicy(TransformerModel(a.dim_ff).to(dev).eval(), precision=a.precision, dropout=dropout,
+                                    dropout_seed=a.dropout_seed)
 net.attach_params()                    # the module's parameters are views of net.plain from here on
 if a.optimizer == "torch":
     net.attach_grads()                 # and their .grad views of net.grad
@@ -83,6 +90,7 @@ for update in range(a.updates):
     fresh, _ = g2048.ops.reset(a.envs, seed, update + 1, 0, device=dev)
     env.load(torch.where(done[:, None], fresh, env.boards), torch.where(done, torch.zeros_like(env.scores), env.scores))
 print("parameters attached: %s; %d floats of gradient in place" % (net.params_attached, net.grad.numel()))
+print("dropout %s: %d training forwards, seed %d" % (net.dropout, net.dropout_index, net.dropout_seed))
 if a.optimizer == "device":
     print("device optimizer: %d Adam steps applied, %d epochs skipped for a NaN loss, %d for a gradient that is not finite"
           % tuple(net.opt_counters.tolist()))

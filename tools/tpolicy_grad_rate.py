@@ -2,6 +2,7 @@
 g2048_tpolicy_loss_grad) against stock torch on the same GPU.
 
     python3 tools/tpolicy_grad_rate.py                    the table
+    python3 tools/tpolicy_grad_rate.py --dropout          what the encoder's live dropout costs (the training library)
 
 The reference's layout (torch's default init, the heads x 8) with dim_ff 128 (bench.py's config 4) and 2,048 (the reference's), 2
 layers, at N = 64, 256 and 1,024 boards. Versions, alternating within every round:
@@ -12,8 +13,15 @@ A round times REPS back-to-back calls of a version between one event pair and di
 min - max in brackets. Before timing, the device gradients and stock torch's float32 ones are both compared with the module's
 float64 autograd on the same GPU, per tensor as max|g - g64| / max|g64|. The boards are not screened: where a ReLU input lies within
 rounding of zero, either side's gradient shows a sign flip (1e-4 .. 1e-3); tests/tpolicy_grad_ref.py screens its cases for that.
-Output: one text table (profiles/r29_tpolicy_grad_rate.txt keeps a run)."""
+Output: one text table (profiles/r29_tpolicy_grad_rate.txt keeps a run).
+
+--dropout: at N = 256 and 1,024, dim_ff 128 and 2,048, 2 layers, alternating within every round: the learner library's
+g2048_tpolicy_loss_grad; the training library's g2048_tpolicy_loss_grad_dropout at p = 0 (the same kernels in the same order: it must
+lie inside the first row's spread), at p = 0.1 on all four sites and on each site alone; the stock module in .train() mode (forward,
+loss, backward()) at p = 0 and p = 0.1 with torch's own masks; net.update(epochs=8) at p = 0 and p = 0.1
+(profiles/r32_tpolicy_dropout_rate.txt keeps a run)."""
 import copy
+import ctypes as C
 import os
 import statistics
 import sys
@@ -26,6 +34,7 @@ import __graft_entry__ as ge  # noqa: E402
 
 ge.import_package()
 from g2048 import DeviceTransformerPolicy, ops  # noqa: E402
+from g2048 import _lib as L  # noqa: E402
 
 dev = torch.device("cuda")
 LAYERS, REPS = 2, 10
@@ -128,5 +137,80 @@ def main():
         print("workspace at N = 1,024, dim_ff %d, 2 layers: %.1f MiB" % (dim_ff, ops.tpolicy_grad_workspace_bytes(1024, dim_ff, LAYERS) / 2 ** 20))
 
 
+def dropout_table():
+    print("device: %s; torch %s" % (torch.cuda.get_device_name(0), torch.__version__))
+    sites = ("attention", "dropout1", "dropout", "dropout2")
+    for dim_ff in (128, 2048):
+        torch.manual_seed(29)
+        model = TPolicy(dim_ff).to(dev).eval()
+        with torch.no_grad():
+            model.actor.weight.mul_(8.0)
+            model.critic.weight.mul_(8.0)
+        plain = DeviceTransformerPolicy(copy.deepcopy(model))
+        dropped = DeviceTransformerPolicy(copy.deepcopy(model), dropout=0.1)
+        trains = {}
+        for p in (0.0, 0.1):
+            trains[p] = copy.deepcopy(model).train()
+            for lay in trains[p].transformer_encoder.layers:
+                lay.self_attn.dropout, lay.dropout1.p, lay.dropout.p, lay.dropout2.p = p, p, p, p
+        for n in (256, 1024):
+            boards, nxt = ops.synth_boards(n, seed=29 + n, device=dev), ops.synth_boards(n, seed=59 + n, device=dev)
+            x = boards.float() / 15
+            i = torch.arange(n, device=dev)
+            actions = (5 * i + 1) % 4
+            gen = torch.Generator(device=dev).manual_seed(n)
+            with torch.no_grad():
+                p32, v32 = model(x)
+            old = torch.log(p32.gather(1, actions[:, None])[:, 0]) + 0.5 * torch.randn(n, generator=gen, device=dev)
+            adv = (((13 * i) % 17 - 8) / 4.0 + 2.0 * x[:, 0]).float()
+            ret = (v32[:, 0] + 0.5 + ((7 * i) % 11 - 5) / 5.0).float()
+            rewards, dones = ret * 0.5, (i % 5 == 0).float()
+            grad = torch.empty_like(plain.plain)
+            ws = torch.empty(ops.tpolicy_train_workspace_bytes(n, dim_ff, LAYERS), dtype=torch.uint8, device=dev)
+            counter = [0]
+
+            def device(p4):
+                def run():
+                    counter[0] += 1
+                    ops.tpolicy_loss_grad(boards, plain.plain, actions, old, adv, ret, dim_ff, LAYERS, grad=grad, workspace=ws, dropout=p4,
+                                          seed=1, call_index=counter[0])
+                return run
+
+            out = (torch.empty(4, device=dev), torch.empty((n, 4), device=dev), torch.empty((n, 1), device=dev))
+            f, zeros = C.c_float, (C.c_double * 4)(0.0, 0.0, 0.0, 0.0)
+
+            def zero_p():       # the training library's entry point itself at p = 0 (ops would take the learner library's)
+                L.ttrain_call(dev, L.ttrain_lib().g2048_tpolicy_loss_grad_dropout, boards.data_ptr(), plain.plain.data_ptr(), actions.data_ptr(),
+                              old.data_ptr(), adv.data_ptr(), ret.data_ptr(), n, dim_ff, LAYERS, zeros, 1, 1, f(CLIP),
+                              f(VALUE_COEF), f(ENTROPY_COEF), grad.data_ptr(), out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(),
+                              ws.data_ptr(), ws.numel(), L.stream_ptr(dev))
+
+            def stock(p):
+                def run():
+                    trains[p].zero_grad(set_to_none=False)
+                    stock_loss(trains[p], x, actions, old, adv, ret).backward()
+                return run
+
+            def update(net):
+                return lambda: net.update(boards, actions, old, rewards, nxt, dones, epochs=8)
+
+            versions = [("learner library, eval mode", device(None)), ("training library, p = 0", zero_p),
+                        ("training library, p = 0.1 on all four", device(0.1))]
+            versions += [("  p = 0.1 on site %d (%s) alone" % (k, sites[k]), device(tuple(0.1 if j == k else 0.0 for j in range(4)))) for k in range(4)]
+            versions += [("torch .train() fwd+bwd, p = 0", stock(0.0)), ("torch .train() fwd+bwd, p = 0.1", stock(0.1)),
+                         ("update(epochs=8), p = 0", update(plain)), ("update(epochs=8), p = 0.1", update(dropped))]
+            start = [plain.plain.clone(), dropped.plain.clone()]
+            t = alternate(versions)
+            for net, t0 in zip((plain, dropped), start):       # the timed updates moved the weights
+                net.plain.copy_(t0)
+                net._plain_changed()
+            base = statistics.median(t[versions[0][0]])
+            print("dim_ff %d, N = %d" % (dim_ff, n))
+            for name, _ in versions:
+                v = t[name]
+                print("  %-42s %9.1f us [%8.1f - %8.1f]  %5.2f x the first row" % (name, statistics.median(v) * 1e6, min(v) * 1e6, max(v) * 1e6,
+                                                                                   statistics.median(v) / base))
+
+
 if __name__ == "__main__":
-    main()
+    dropout_table() if sys.argv[1:] == ["--dropout"] else main()
