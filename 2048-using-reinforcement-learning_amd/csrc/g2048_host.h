@@ -9,6 +9,7 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <cmath>
 #include <type_traits>
 
 #include "../../include/g2048.h"
@@ -48,6 +49,9 @@ inline bool good_encoder_shape(int dim_ff, int n_layers)
 {
     return dim_ff >= 32 && dim_ff % 32 == 0 && dim_ff <= 65536 && n_layers >= 1 && n_layers <= 64;
 }
+
+// a loss coefficient or the clip range of the two PPO passes (g2048_ppo_grad.hip, g2048_tpolicy_grad_pass.h)
+inline bool good_coef(float v) { return v >= 0.0f && std::isfinite(v); }
 
 // ------------------------------------------------------- the two encoder networks (g2048_tpolicy.hip, g2048_qnet.hip) --
 // precision and encoder shape: G2048_OK, or the error as `entry`'s. precision_arg: what that entry point calls the argument

@@ -1,6 +1,7 @@
-// g2048_mfma.h -- the fragment toolkit of the three network files (g2048_policy.hip, g2048_tpolicy.hip, g2048_qnet.hip): the
-// vector types, the small f32 helpers, the one MFMA step over a packed weight fragment, and the kernel that packs a matrix into
-// such fragments. Device code, included by those files and nothing else.
+// g2048_mfma.h -- the fragment toolkit of the three network files (g2048_policy.hip, g2048_tpolicy.hip, g2048_qnet.hip) and of the
+// batch passes: the vector types, the small f32 helpers, the one MFMA step over a packed weight fragment, the kernel that packs a
+// matrix into such fragments, and for the batch passes the load of a plain weight row (load_w) and the product over it
+// (chunks_product). Device code, included by the library's .hip files and the headers they share.
 //
 // A fragment is 64 lanes x 16 bytes = 1 KiB: the MFMA A operand of one 16-row tile of weights over one chunk of K, a lane's
 // share one 16-byte load. Lane l (g = l >> 4) holds row 16 o + (l & 15) of the matrix. A chunk is
@@ -43,6 +44,9 @@ __device__ inline f4 relu_nan(f4 v)
 __device__ inline f4 load_f4(const void *p) { return *reinterpret_cast<const f4 *>(p); }
 __device__ inline f4 splat(float v) { return f4{v, v, v, v}; }
 
+typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));      // 16 bytes of a plain f32 buffer: 4-byte aligned at worst
+__device__ inline f4 load_w(const float *p) { const f4u v = *reinterpret_cast<const f4u *>(p); return f4{v[0], v[1], v[2], v[3]}; }
+
 // Two result tiles as one bf16 B operand. INT_RNE: by bf16_rne's integer add (g2048_policy.hip, whose forward kernel was
 // written and measured with it); otherwise the float -> __bf16 cast, gfx950's v_cvt_pk_bf16_f32 (round to nearest even, two
 // values per instruction). Finite values round the same either way.
@@ -80,6 +84,27 @@ __device__ inline void chunk_mma(const unsigned char *frag, const f4 (&act)[E][2
                 acc[e] = TRANSPOSED ? __builtin_amdgcn_mfma_f32_16x16x4f32(act[e][0][r], a[r], acc[e], 0, 0, 0)
                                     : __builtin_amdgcn_mfma_f32_16x16x4f32(a[r], act[e][0][r], acc[e], 0, 0, 0);
     }
+}
+
+// The batch passes' product over a plain row-major W (the Q-network's g2048_qnet_batch_fwd.h, the transformer policy's
+// g2048_tpolicy_grad_pass.h): acc (features 16 o + 4 g + r of row `col` of the tile) += W[16 o ..][K] . X[row][K]. Lane (col, g): the
+// A operand is W[16 o + col][16 c + 4 g ..], the B operand X[row][16 c + 4 g ..], four MFMAs a chunk. N chunks at once, every load
+// issued before the first MFMA (K is a multiple of 32: the chunks come in pairs). Chunk c of a group of eight accumulates into
+// acc[c]: eight independent partial sums, so that consecutive MFMAs do not wait on each other and the rounding error of a long K
+// grows like a blocked sum's, not like one serial chain's. The order is fixed all the same.
+template <int N>
+__device__ inline void chunks_product(const float *__restrict__ wrow, const float *__restrict__ xrow, bool live, f4 (&acc)[8])
+{
+    f4 w[N], x[N];
+#pragma unroll
+    for (int c = 0; c < N; ++c) {
+        w[c] = load_w(wrow + 16 * c);
+        x[c] = live ? load_f4(xrow + 16 * c) : splat(0.0f);
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int c = 0; c < N; ++c) acc[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[c][r], x[c][r], acc[c], 0, 0, 0);
 }
 
 __device__ inline float lanes_sum(float v)           // over the four lanes c, c + 16, c + 32, c + 48, the same on all four

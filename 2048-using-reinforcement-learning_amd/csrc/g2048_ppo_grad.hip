@@ -18,7 +18,7 @@
 //             the sums as in bn
 //   loss      one block's fixed-order sums of the rows' terms
 //   dropout   (p > 0 only) the bn launch multiplies its output by m, the bn_bwd launch the incoming dy, m = 1 / (1 - p) or 0 from
-//             one draw of the counter RNG per element (drop_mult): the backward regenerates it, no mask is stored. With p == 0
+//             one draw of the counter RNG per element (qdrop_mult): the backward regenerates it, no mask is stored. With p == 0
 //             the kernels launched are the instantiations without it (pg_bn_kernel<> / pg_bn_bwd_kernel<>), whose code is unchanged.
 // n == 1: the reference skips both BatchNorms; so does this (their gradients are written as 0, the running statistics stay). It
 // does not skip the dropout: with p > 0 one elementwise launch each way (pg_drop_kernel / pg_drop_bwd_kernel) applies m.
@@ -89,47 +89,33 @@ __global__ __launch_bounds__(256) void pg_fc1_kernel(const float *__restrict__ X
 }
 
 // ---------------------------------------------------------------------------------------------------------- dropout --
-// One dropout site of one launch (DESIGN.md "RNG", domain kDomDropout): element (row, feature) of site s (0 after bn1, 1 after bn2)
-// of network w (0 actor, 1 critic) in the library call with index c draws h = rng_draw(k0, k1, ((2 w + s) << 32) | (row F + feature), 0),
-// (k0, k1) = rng_keys(seed, kDomDropout, c), and is kept iff h >= T = floor(p 2^32). The id's high word is the launch's, so it is
-// folded into k1h on the host and the lane hashes 32 bits (rng_draw_lo).
-struct Drop {
-    uint32_t k0, k1h, T;
-    float scale;           // (float)(1 / (1 - p))
-};
-
-__device__ inline bool drop_keep(const Drop &d, uint32_t idx) { return rng_draw_lo(d.k0, d.k1h, idx, 0) >= d.T; }
-// the multiplier: a product, not a select, so that a NaN or an infinity in a dropped position becomes NaN as in torch
-__device__ inline float drop_mult(const Drop &d, uint32_t idx) { return drop_keep(d, idx) ? d.scale : 0.0f; }
-
-inline Drop drop_site(uint64_t seed, uint64_t call_index, int net, int site, double p)
+// One dropout site of one launch is a QDrop (g2048_qnet_drop.h, through g2048_qnet_batch_fwd.h), domain kDomDropout: element
+// (row, feature) of site s (0 after bn1, 1 after bn2) of network w (0 actor, 1 critic) is element row F + feature of stream 2 w + s.
+inline QDrop drop_site(uint64_t seed, uint64_t call_index, int net, int site, double p)
 {
-    const Keys k = rng_keys(seed, kDomDropout, call_index);
-    return Drop{k.k0, k.k1 + rng_hi_term((uint64_t)(2 * net + site) << 32), (uint32_t)std::floor(p * 4294967296.0), (float)(1.0 / (1.0 - p))};
+    return QDrop(kDomDropout, seed, call_index, (uint32_t)(2 * net + site), p);
 }
 
-inline bool good_drop(double p) { return p >= 0.0 && p < 1.0; }      // a NaN fails both
-
 // keep[i] = the keep bit of element i of a site, i < count
-__global__ __launch_bounds__(256) void pg_drop_mask_kernel(uint8_t *__restrict__ keep, Drop drop, uint32_t count)
+__global__ __launch_bounds__(256) void pg_drop_mask_kernel(uint8_t *__restrict__ keep, QDrop drop, uint32_t count)
 {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i < count) keep[i] = drop_keep(drop, i) ? 1 : 0;
+    if (i < count) keep[i] = qdrop_keep(drop, i) ? 1 : 0;
 }
 
 // n == 1, where no BatchNorm launch carries the dropout: Y = X m over count elements of a site
-__global__ __launch_bounds__(256) void pg_drop_kernel(const float *__restrict__ X, float *__restrict__ Y, Drop drop, uint32_t count)
+__global__ __launch_bounds__(256) void pg_drop_kernel(const float *__restrict__ X, float *__restrict__ Y, QDrop drop, uint32_t count)
 {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i < count) Y[i] = X[i] * drop_mult(drop, i);
+    if (i < count) Y[i] = X[i] * qdrop_mult(drop, i);
 }
 
 // its backward, in place: D = d loss / d Y leaves as d loss / d H, X = relu(H) (zero where X <= 0)
-__global__ __launch_bounds__(256) void pg_drop_bwd_kernel(float *__restrict__ D, const float *__restrict__ X, Drop drop, uint32_t count)
+__global__ __launch_bounds__(256) void pg_drop_bwd_kernel(float *__restrict__ D, const float *__restrict__ X, QDrop drop, uint32_t count)
 {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= count) return;
-    const float v = D[i] * drop_mult(drop, i);
+    const float v = D[i] * qdrop_mult(drop, i);
     D[i] = X[i] <= 0.0f ? 0.0f : v;
 }
 
@@ -169,7 +155,7 @@ __device__ inline float bn_block_sum(const float (&a)[kBnParts], float (&red)[kB
 
 // Y = (X - mean) rstd gamma + beta over the n rows of X [n][F] (n >= 2), mean and the biased variance of the batch; stat: mean [F],
 // rstd [F] kept for the backward. running (optional): mean [F], var [F], moved by momentum 0.1 towards the batch mean and the
-// UNBIASED variance, as torch's training-mode BatchNorm1d moves them. grid F / 32. With a Drop, Y is multiplied by the site's m.
+// UNBIASED variance, as torch's training-mode BatchNorm1d moves them. grid F / 32. With a QDrop, Y is multiplied by the site's m.
 template <class... MaybeDrop>
 __global__ __launch_bounds__(1024) void pg_bn_kernel(const float *__restrict__ X, int F, const float *__restrict__ gamma, const float *__restrict__ beta,
                                                       float *__restrict__ Y, float *__restrict__ stat, float *__restrict__ running, int n,
@@ -193,7 +179,7 @@ __global__ __launch_bounds__(1024) void pg_bn_kernel(const float *__restrict__ X
     const float rstd = 1.0f / sqrtf(ss / (float)n + kBnEps), ga = gamma[feat], be = beta[feat];
     for (int i = grp; i < n; i += kBnGroups) {
         float y = (x[(size_t)i * F] - mean) * rstd * ga + be;
-        if constexpr (sizeof...(MaybeDrop) != 0) y *= drop_mult(drop..., (uint32_t)(i * F + feat));
+        if constexpr (sizeof...(MaybeDrop) != 0) y *= qdrop_mult(drop..., (uint32_t)(i * F + feat));
         Y[(size_t)i * F + feat] = y;
     }
     if (grp == 0) {
@@ -208,7 +194,7 @@ __global__ __launch_bounds__(1024) void pg_bn_kernel(const float *__restrict__ X
 
 // The backward of pg_bn_kernel, in place: D [n][F] holds d loss / d Y and leaves as d loss / d H, where X = relu(H) is the
 // BatchNorm's input (zero where X <= 0; a NaN X passes the gradient, as torch's ReLU backward does). dgamma [F] = sum dy xhat, dbeta [F] = sum dy with xhat = (X - mean) rstd from stat.
-// With a Drop, D holds d loss / d (Y m), the dropped output: every dy is first multiplied by the regenerated m.
+// With a QDrop, D holds d loss / d (Y m), the dropped output: every dy is first multiplied by the regenerated m.
 template <class... MaybeDrop>
 __global__ __launch_bounds__(1024) void pg_bn_bwd_kernel(float *__restrict__ D, const float *__restrict__ X, int F, const float *__restrict__ gamma,
                                                           const float *__restrict__ stat, float *__restrict__ dgamma, float *__restrict__ dbeta, int n,
@@ -224,7 +210,7 @@ __global__ __launch_bounds__(1024) void pg_bn_bwd_kernel(float *__restrict__ D, 
     for (int u = 0; u < kBnParts; ++u) a[u] = b[u] = 0.0f;
     bn_rows(grp, n, [&](int u, int row) {
         float dy = d[(size_t)row * F];
-        if constexpr (sizeof...(MaybeDrop) != 0) dy *= drop_mult(drop..., (uint32_t)(row * F + feat));
+        if constexpr (sizeof...(MaybeDrop) != 0) dy *= qdrop_mult(drop..., (uint32_t)(row * F + feat));
         a[u] += dy;
         b[u] += dy * ((x[(size_t)row * F] - mean) * rstd);
     });
@@ -233,7 +219,7 @@ __global__ __launch_bounds__(1024) void pg_bn_bwd_kernel(float *__restrict__ D, 
     for (int i = grp; i < n; i += kBnGroups) {
         const float xv = x[(size_t)i * F];
         float dy = d[(size_t)i * F];
-        if constexpr (sizeof...(MaybeDrop) != 0) dy *= drop_mult(drop..., (uint32_t)(i * F + feat));
+        if constexpr (sizeof...(MaybeDrop) != 0) dy *= qdrop_mult(drop..., (uint32_t)(i * F + feat));
         const float v = scale * (dy - mb - (xv - mean) * rstd * mg);
         d[(size_t)i * F] = xv <= 0.0f ? 0.0f : v;
     }
@@ -385,7 +371,7 @@ struct Net {
     float *ws;             // this network's workspace
     int n_out;
     bool dropout;          // p > 0: drop[s] is site s's
-    Drop drop[2];
+    QDrop drop[2];
 };
 
 // what the dropout entry points add to a network: p, and with p > 0 the two sites' launch scalars
@@ -406,9 +392,9 @@ void launch_trunk(const Net &net, const float *states, int n, hipStream_t s)
     const bool bn = n > 1, own = bn || net.dropout;
     float *h1 = net.ws + w.h1(), *b1 = own ? net.ws + w.b1() : h1, *h2 = net.ws + w.h2(), *b2 = own ? net.ws + w.b2() : h2, *h3 = net.ws + w.h3(),
           *stat = net.ws + w.stat();
-    const auto norm = [&](const float *h, int F, const float *gamma, const float *beta, float *b, float *st, float *running, const Drop &drop) {
+    const auto norm = [&](const float *h, int F, const float *gamma, const float *beta, float *b, float *st, float *running, const QDrop &drop) {
         if (bn && net.dropout)
-            hipLaunchKernelGGL(pg_bn_kernel<Drop>, dim3(F / 32), dim3(1024), 0, s, h, F, gamma, beta, b, st, running, n, drop);
+            hipLaunchKernelGGL(pg_bn_kernel<QDrop>, dim3(F / 32), dim3(1024), 0, s, h, F, gamma, beta, b, st, running, n, drop);
         else if (bn)
             hipLaunchKernelGGL(pg_bn_kernel<>, dim3(F / 32), dim3(1024), 0, s, h, F, gamma, beta, b, st, running, n);
         else if (net.dropout)
@@ -442,9 +428,9 @@ int launch_backward(const Net &net, const float *states, int n, hipStream_t s, c
         hipLaunchKernelGGL(qg_dw_kernel, dim3((unsigned)(K + 63) / 64, (unsigned)(M + 15) / 16), dim3(256), 0, s, dY, ldy, M, X, K, dW, db, n);
     };
     // d [n][F] = d loss / d b (the BatchNorm's, dropped, output) to d loss / d (fc's output before its ReLU), in place
-    const auto norm_bwd = [&](float *d, const float *h, int F, const float *gamma, const float *st, float *dgamma, float *dbeta, const Drop &drop) {
+    const auto norm_bwd = [&](float *d, const float *h, int F, const float *gamma, const float *st, float *dgamma, float *dbeta, const QDrop &drop) {
         if (bn && net.dropout)
-            hipLaunchKernelGGL(pg_bn_bwd_kernel<Drop>, dim3(F / 32), dim3(1024), 0, s, d, h, F, gamma, st, dgamma, dbeta, n, drop);
+            hipLaunchKernelGGL(pg_bn_bwd_kernel<QDrop>, dim3(F / 32), dim3(1024), 0, s, d, h, F, gamma, st, dgamma, dbeta, n, drop);
         else if (bn)
             hipLaunchKernelGGL(pg_bn_bwd_kernel<>, dim3(F / 32), dim3(1024), 0, s, d, h, F, gamma, st, dgamma, dbeta, n);
         else if (net.dropout)
@@ -466,7 +452,6 @@ int launch_backward(const Net &net, const float *states, int n, hipStream_t s, c
     return G2048_OK;
 }
 
-inline bool good_coef(float v) { return v >= 0.0f && std::isfinite(v); }
 
 // g2048_ppo_forward_train and g2048_ppo_forward_train_dropout (`entry`: whose messages); the first is net 0, p 0
 int forward_train(const char *entry, const float *states, const float *plain, float *running_or_null, int n_out, int net_index, double p,
@@ -479,7 +464,7 @@ int forward_train(const char *entry, const float *states, const float *plain, fl
         return fail(G2048_ERR_ARG, "%s: misaligned pointer (states, plain weights, workspace, probabilities: 16 bytes; the rest: 4)", entry);
     if (n_out != 4 && n_out != 1) return fail(G2048_ERR_ARG, "%s: n_out must be 4 (actor) or 1 (critic)", entry);
     if (net_index != 0 && net_index != 1) return fail(G2048_ERR_ARG, "%s: net must be 0 (the actor's masks) or 1 (the critic's)", entry);
-    if (!good_drop(p)) return fail(G2048_ERR_ARG, "%s: the dropout probability must be finite, 0 <= p < 1", entry);
+    if (!good_qdrop(p)) return fail(G2048_ERR_ARG, "%s: the dropout probability must be finite, 0 <= p < 1", entry);
     if (n > G2048_PPO_BATCH_MAX)
         return fail(G2048_ERR_ARG, "%s: n must not exceed G2048_PPO_BATCH_MAX = %d (the batch statistics are the whole batch's; a larger "
                                    "batch is not truncated)", entry, G2048_PPO_BATCH_MAX);
@@ -519,7 +504,7 @@ int loss_grad(const char *entry, const float *states, const int64_t *actions, co
                     entry);
     if (!good_coef(clip_epsilon) || !good_coef(value_coef) || !good_coef(entropy_coef))
         return fail(G2048_ERR_ARG, "%s: clip_epsilon, value_coef and entropy_coef must be finite and not negative", entry);
-    if (!good_drop(p_actor) || !good_drop(p_critic))
+    if (!good_qdrop(p_actor) || !good_qdrop(p_critic))
         return fail(G2048_ERR_ARG, "%s: the dropout probabilities must be finite, 0 <= p < 1", entry);
     if (n > G2048_PPO_BATCH_MAX)
         return fail(G2048_ERR_ARG, "%s: n must not exceed G2048_PPO_BATCH_MAX = %d (the batch statistics are the whole batch's; a larger "
@@ -575,7 +560,7 @@ int g2048_ppo_dropout_mask(uint64_t seed, uint64_t call_index, int net, int site
     if ((net != 0 && net != 1) || (site != 0 && site != 1))
         return fail(G2048_ERR_ARG, "g2048_ppo_dropout_mask: net must be 0 (actor) or 1 (critic), site 0 (after bn1, 256 features) or 1 (after "
                                    "bn2, 128)");
-    if (!good_drop(p)) return fail(G2048_ERR_ARG, "g2048_ppo_dropout_mask: the dropout probability must be finite, 0 <= p < 1");
+    if (!good_qdrop(p)) return fail(G2048_ERR_ARG, "g2048_ppo_dropout_mask: the dropout probability must be finite, 0 <= p < 1");
     if (n > G2048_PPO_BATCH_MAX) return fail(G2048_ERR_ARG, "g2048_ppo_dropout_mask: n must not exceed G2048_PPO_BATCH_MAX = %d", G2048_PPO_BATCH_MAX);
     const uint32_t count = (uint32_t)n * (uint32_t)(site == 0 ? kH1 : kH2);
     hipLaunchKernelGGL(pg_drop_mask_kernel, dim3(blocks_for(count, 256)), dim3(256), 0, static_cast<hipStream_t>(stream), keep_out,

@@ -3,7 +3,9 @@
 // are ONE sequence of n tokens that attend to each other (8 heads of 16, scores q.k / 4, softmax over all n keys). This is a
 // different function from g2048_qnet_forward's (every board its own sequence of one token); they agree at n = 1. With it, the
 // no-gradient block of train_step: the online network's argmax, the target network's Q at it and the Double-DQN target
-// (g2048_dqn_targets). C-ABI: include/g2048.h, g2048_qnet_forward_batch / g2048_qnet_batch_workspace / g2048_dqn_targets.
+// (g2048_dqn_targets). C-ABI: include/g2048.h, g2048_qnet_forward_batch / g2048_qnet_batch_workspace / g2048_dqn_targets. The kernels,
+// the workspace (FwdWorkspace) and the launch sequence (qb_forward_pass<kDrop>) are g2048_qnet_batch_fwd.h's, shared with the gradient
+// pass and the training library; this file keeps the entry points and g2048_dqn_targets.
 //
 // Shape of the work. n is small (the reference's batch is 256), so the pass is a short sequence of launches, one phase each,
 // every phase's grid spread over board tiles x feature tiles (or query tiles x heads); between phases the activations lie
@@ -35,17 +37,6 @@
 
 namespace {
 
-// workspace, in floats: x [np][128], qkv [np][384], att [np][128], h [np][max(1024, dim_ff)] (feat, then the hidden layer)
-struct Workspace {
-    size_t np, hw;
-    Workspace(size_t n, int ff) : np((n + 15) / 16 * 16), hw((size_t)(ff > kFlat ? ff : kFlat)) {}
-    size_t x() const { return 0; }
-    size_t qkv() const { return np * kD; }
-    size_t att() const { return qkv() + np * kQkv; }
-    size_t h() const { return att() + np * kD; }
-    size_t floats() const { return h() + np * hw; }
-};
-
 // ------------------------------------------------------------------------------------------------------ dqn targets --
 // hybrid.py:1042-1046 on given Q: next_action = argmax of the online Q (unmasked, first maximum), next_q = the target Q at it,
 // target = shaped + (1 - done) * gamma * next_q in torch's order of operations, every step rounded to f32, no contraction.
@@ -75,48 +66,14 @@ extern "C" {
 size_t g2048_qnet_batch_workspace(size_t n, int dim_ff)
 {
     if (n == 0 || n > G2048_QNET_BATCH_MAX || !good_encoder_shape(dim_ff, 1)) return 0;
-    return Workspace(n, dim_ff).floats() * sizeof(float);
+    return FwdWorkspace(n, dim_ff).floats() * sizeof(float);
 }
 
 int g2048_qnet_forward_batch(const void *boards, const float *plain_f32, float *q_out, size_t n, int dim_ff, int n_layers,
                              void *workspace, void *stream)
 {
-    if (n == 0) return G2048_OK;
-    if (!boards || !plain_f32 || !q_out || !workspace) return fail(G2048_ERR_ARG, "g2048_qnet_forward_batch: null pointer");
-    if (!aligned(boards, 16) || !aligned(plain_f32, 16) || !aligned(q_out, 16) || !aligned(workspace, 16))
-        return fail(G2048_ERR_ARG, "g2048_qnet_forward_batch: misaligned pointer (boards, plain weights, q, workspace: 16 bytes)");
-    if (n > G2048_QNET_BATCH_MAX)
-        return fail(G2048_ERR_ARG, "g2048_qnet_forward_batch: n must not exceed G2048_QNET_BATCH_MAX = %d (the boards are one sequence; "
-                                   "a larger batch is not truncated)", G2048_QNET_BATCH_MAX);
-    if (!good_encoder_shape(dim_ff, n_layers))
-        return fail(G2048_ERR_ARG, "g2048_qnet_forward_batch: dim_ff must be a multiple of 32 (32 .. 65536) and n_layers 1 .. 64");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const Workspace ws(n, dim_ff);
-    float *base = static_cast<float *>(workspace), *x = base + ws.x(), *qkv = base + ws.qkv(), *att = base + ws.att(), *h = base + ws.h();
-    const float *P = plain_f32;
-    const int ni = (int)n, ff = dim_ff;
-    const unsigned tiles = (unsigned)(ws.np / 16);
-    const auto linear = [&](auto RELU, const float *X, int K, const float *W, const float *b, float *Y, int M) {
-        hipLaunchKernelGGL(qb_linear_kernel<decltype(RELU)::value>, dim3((unsigned)(M + 63) / 64, tiles), dim3(256), 0, s, X, K, W, b, Y, M, ni);
-    };
-    hipLaunchKernelGGL(qb_conv_kernel, dim3((unsigned)n), dim3(256), 0, s, static_cast<const uint8_t *>(boards), P, h, static_cast<float *>(nullptr));
-    linear(std::false_type{}, h, kFlat, P + kPlEmbW, P + kPlEmbB, x, kD);
-    for (int l = 0; l < n_layers; ++l) {
-        const float *L = P + kPlLayer0 + (size_t)l * pl_layer(ff), *norms = L + pl_norm(ff);
-        const bool last = l == n_layers - 1;
-        linear(std::false_type{}, x, kD, L + kPlInW, L + kPlInB, qkv, kQkv);
-        hipLaunchKernelGGL(qb_attention_kernel, dim3(tiles, kHeads), dim3(64), 0, s, qkv, att, ni, static_cast<float *>(nullptr),
-                           static_cast<float *>(nullptr));
-        hipLaunchKernelGGL(qb_proj_norm_kernel, dim3(tiles), dim3(512), 0, s, att, kD, L + kPlOutW, L + kPlOutB, norms, norms + 4 * kD,
-                           static_cast<const float *>(x), x, static_cast<float *>(nullptr), static_cast<const float *>(nullptr),
-                           static_cast<float4 *>(nullptr), ni);
-        linear(std::true_type{}, x, kD, L + kPlW1, L + pl_b1(ff), h, ff);
-        hipLaunchKernelGGL(qb_proj_norm_kernel, dim3(tiles), dim3(512), 0, s, h, ff, L + pl_w2(ff), L + pl_b2(ff), norms + 2 * kD,
-                           norms + 4 * kD + 1, static_cast<const float *>(x), last ? static_cast<float *>(nullptr) : x, static_cast<float *>(nullptr),
-                           last ? P + kPlLayer0 + (size_t)n_layers * pl_layer(ff) : static_cast<const float *>(nullptr),
-                           reinterpret_cast<float4 *>(q_out), ni);
-    }
-    return check_launch("g2048_qnet_forward_batch");
+    return qb_forward_pass<false>("g2048_qnet_forward_batch", QbCall{boards, plain_f32, nullptr, nullptr, nullptr, n, dim_ff, n_layers, nullptr,
+                                                                     nullptr, nullptr, q_out, workspace, stream, false, nullptr, 0, 0});
 }
 
 int g2048_dqn_targets(const float *q_online_next, const float *q_target_next, const float *shaped, const float *dones, float gamma,

@@ -1,9 +1,10 @@
-// g2048_qnet_batch_fwd.h -- the forward kernels of the hybrid agent's Q-network on a BATCH of boards (one sequence of n tokens), shared
+// g2048_qnet_batch_fwd.h -- the forward kernels of the hybrid agent's Q-network on a BATCH of boards (one sequence of n tokens), and below
+// them the host side of its four batch passes (one call description, one check, one forward launch sequence: qb_forward<kDrop>), shared
 // by g2048_qnet_batch.hip (the forward alone) and g2048_qnet_grad.hip (the forward that keeps its activations, then the gradient
 // pass); g2048_ppo_grad.hip takes qb_linear_kernel from here for the PPO networks' fc2 and fc3, and g2048_qnet_train.hip (the training
 // library) instantiates the attention, proj_norm and linear kernels a second time with a QDrop (g2048_qnet_drop.h) as their trailing
 // argument: the reference's live dropout. The instantiations without one keep the parameter lists and the statements they had as
-// plain kernels. Device code, included by those four files and nothing else; every kernel is per translation unit. What the phases are and
+// plain kernels. Device and host code, included by those four files and nothing else; every kernel is per translation unit. What the phases are and
 // why the weights are read from the plain buffer: the head of g2048_qnet_batch.hip. The outputs the gradient pass needs on top
 // (conv1's output, the attention rows' maximum and sum, the sums before the LayerNorms) are optional pointers that the forward
 // alone passes as null; they change no arithmetic.
@@ -11,6 +12,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/g2048.h"
+#include "g2048_host.h"
 #include "g2048_mfma.h"
 #include "g2048_qnet_drop.h"
 
@@ -29,9 +31,6 @@ constexpr size_t pl_w2(size_t ff) { return pl_b1(ff) + ff; }
 constexpr size_t pl_b2(size_t ff) { return pl_w2(ff) + kD * ff; }
 constexpr size_t pl_norm(size_t ff) { return pl_b2(ff) + kD; }          // norm1.w norm1.b norm2.w norm2.b eps1 eps2
 constexpr size_t pl_layer(size_t ff) { return pl_norm(ff) + 4 * kD + 2; }
-
-typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));      // a weight row's 16 bytes: 4-byte aligned at worst
-__device__ inline f4 load_w(const float *p) { const f4u v = *reinterpret_cast<const f4u *>(p); return f4{v[0], v[1], v[2], v[3]}; }
 
 // ------------------------------------------------------------------------------------------------------------- conv --
 // One block a board. conv1 (32 x 5 x 5 from the zero-padded 6 x 6 grid of tile values) into LDS, then thread t computes conv2's
@@ -101,26 +100,7 @@ __global__ __launch_bounds__(256) void qb_conv_kernel(const uint8_t *__restrict_
 }
 
 // ----------------------------------------------------------------------------------------------------------- linear --
-// acc (features 16 o + 4 g + r of board `col` of the tile) += W[16 o ..][K] . X[board][K]; W row-major as it lies in `plain`.
-// Lane (col, g): the A operand is W[16 o + col][16 c + 4 g ..], the B operand X[board][16 c + 4 g ..], four MFMAs a chunk.
-// N chunks at once, every load issued before the first MFMA (K is a multiple of 32: the chunks come in pairs). Chunk c of a
-// group of eight accumulates into acc[c]: eight independent partial sums, so that consecutive MFMAs do not wait on each other and
-// the rounding error of a long K grows like a blocked sum's, not like one serial chain's. The order is fixed all the same.
-template <int N>
-__device__ inline void chunks_product(const float *__restrict__ wrow, const float *__restrict__ xrow, bool live, f4 (&acc)[8])
-{
-    f4 w[N], x[N];
-#pragma unroll
-    for (int c = 0; c < N; ++c) {
-        w[c] = load_w(wrow + 16 * c);
-        x[c] = live ? load_f4(xrow + 16 * c) : splat(0.0f);
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-        for (int c = 0; c < N; ++c) acc[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[c][r], x[c][r], acc[c], 0, 0, 0);
-}
-
+// the whole K of one tile through chunks_product (g2048_mfma.h): groups of eight chunks, then pairs
 __device__ inline f4 tile_product(const float *__restrict__ wrow, const float *__restrict__ xrow, bool live, int K, f4 bias)
 {
     f4 acc[8] = {bias, splat(0.0f), splat(0.0f), splat(0.0f), splat(0.0f), splat(0.0f), splat(0.0f), splat(0.0f)};
@@ -271,6 +251,119 @@ __global__ __launch_bounds__(512) void qb_proj_norm_kernel(const float *__restri
         out[a] = half_sum(fmaf(w[3], v[3], fmaf(w[2], v[2], fmaf(w[1], v[1], w[0] * v[0]))));
     }
     if (j == 0 && board < n) q_out[board] = make_float4(out[0] + fc[4 * kD], out[1] + fc[4 * kD + 1], out[2] + fc[4 * kD + 2], out[3] + fc[4 * kD + 3]);
+}
+
+// ------------------------------------------------------------------------------------------------------------- host --
+// One call of any of the Q-network's four batch passes (g2048_qnet_forward_batch, g2048_qnet_loss_grad and their _dropout forms).
+// backward false: the forward alone; actions, targets, weights, grad, td and loss are then not looked at. p4, seed, call_index: the
+// training-mode passes' (kDrop true), else unused.
+struct QbCall {
+    const void *boards;
+    const float *plain;
+    const int64_t *actions;
+    const float *targets, *weights;
+    size_t n;
+    int dim_ff, n_layers;
+    float *grad, *td, *loss, *q;
+    void *workspace, *stream;
+    bool backward;
+    const double *p4;
+    uint64_t seed, call_index;
+};
+
+// the argument checks of the four passes, all before any device call
+template <bool kDrop>
+int qb_check(const char *entry, const QbCall &c)
+{
+    if (!c.boards || !c.plain || !c.q || !c.workspace ||
+        (c.backward && (!c.actions || !c.targets || !c.weights || !c.grad || !c.td || !c.loss)))
+        return fail(G2048_ERR_ARG, "%s: null pointer", entry);
+    if (!aligned(c.boards, 16) || !aligned(c.plain, 16) || !aligned(c.grad, 16) || !aligned(c.q, 16) || !aligned(c.workspace, 16) ||
+        !aligned(c.actions, 8) || !aligned(c.targets, 4) || !aligned(c.weights, 4) || !aligned(c.td, 4) || !aligned(c.loss, 4))
+        return c.backward ? fail(G2048_ERR_ARG, "%s: misaligned pointer (boards, plain weights, grad, q, workspace: 16 bytes; actions: 8; "
+                                                "the rest: 4)", entry)
+                          : fail(G2048_ERR_ARG, "%s: misaligned pointer (boards, plain weights, q, workspace: 16 bytes)", entry);
+    if (c.n > G2048_QNET_BATCH_MAX)
+        return fail(G2048_ERR_ARG, "%s: n must not exceed G2048_QNET_BATCH_MAX = %d (the boards are one sequence; a larger batch is not "
+                                   "truncated)", entry, G2048_QNET_BATCH_MAX);
+    if (!good_encoder_shape(c.dim_ff, c.n_layers))
+        return fail(G2048_ERR_ARG, "%s: dim_ff must be a multiple of 32 (32 .. 65536) and n_layers 1 .. 64", entry);
+    if constexpr (kDrop)
+        if (const int rc = check_p(entry, c.p4)) return rc;
+    return G2048_OK;
+}
+
+// the forward-only passes' workspace, in floats: x [np][128], qkv [np][384], att [np][128], h [np][max(1024, dim_ff)] (feat, then
+// the hidden layer); every layer works in place
+struct FwdWorkspace {
+    size_t np, hw;
+    FwdWorkspace(size_t n, int ff) : np((n + 15) / 16 * 16), hw((size_t)(ff > kFlat ? ff : kFlat)) {}
+    size_t x() const { return 0; }
+    size_t qkv() const { return np * kD; }
+    size_t att() const { return qkv() + np * kQkv; }
+    size_t h() const { return att() + np * kD; }
+    size_t floats() const { return h() + np * hw; }
+};
+
+// one encoder layer's arrays: from x0 into x_next (null: not stored, as on the last layer of a forward-only pass); att and h are the
+// DROPPED ones in a training pass. pre1, pre2, amax, asum: what the gradient pass keeps on top, null in a forward-only pass.
+struct LayerBuffers {
+    float *x0, *qkv, *att, *x1, *pre1, *h, *x_next, *pre2, *amax, *asum;
+};
+
+// layer l's five launches; fc_or_null: fc on the last layer, which then writes q_out
+template <bool kDrop>
+void qb_forward_layer(hipStream_t s, const float *L, int ff, const DropSites &st, const LayerBuffers &b, const float *fc_or_null, float *q_out,
+                      int ni, unsigned tiles)
+{
+    const float *norms = L + pl_norm(ff), *none = nullptr;
+    hipLaunchKernelGGL((qb_linear_kernel<false>), dim3((unsigned)(kQkv + 63) / 64, tiles), dim3(256), 0, s, static_cast<const float *>(b.x0), kD,
+                       L + kPlInW, L + kPlInB, b.qkv, kQkv, ni);
+    launch_site<kDrop>(st.at(0), [](auto... d) { return qb_attention_kernel<decltype(d)...>; }, dim3(tiles, kHeads), dim3(64), s,
+                       static_cast<const float *>(b.qkv), b.att, ni, b.amax, b.asum);
+    launch_site<kDrop>(st.at(1), [](auto... d) { return qb_proj_norm_kernel<decltype(d)...>; }, dim3(tiles), dim3(512), s,
+                       static_cast<const float *>(b.att), kD, L + kPlOutW, L + kPlOutB, norms, norms + 4 * kD, static_cast<const float *>(b.x0),
+                       b.x1, b.pre1, none, static_cast<float4 *>(nullptr), ni);
+    launch_site<kDrop>(st.at(2), [](auto... d) { return qb_linear_kernel<true, false, decltype(d)...>; }, dim3((unsigned)(ff + 63) / 64, tiles),
+                       dim3(256), s, static_cast<const float *>(b.x1), kD, L + kPlW1, L + pl_b1(ff), b.h, ff, ni);
+    launch_site<kDrop>(st.at(3), [](auto... d) { return qb_proj_norm_kernel<decltype(d)...>; }, dim3(tiles), dim3(512), s,
+                       static_cast<const float *>(b.h), ff, L + pl_w2(ff), L + pl_b2(ff), norms + 2 * kD, norms + 4 * kD + 1,
+                       static_cast<const float *>(b.x1), b.x_next, b.pre2, fc_or_null, reinterpret_cast<float4 *>(q_out), ni);
+}
+
+// The forward of all four passes, 2 + 5 n_layers launches: conv into feat (and c1 where it is kept), the embedding into layer 0's
+// x0, the layers, Q from the last. buffers(l, last): layer l's LayerBuffers. kDrop true: site s of a layer is live where p4[s] > 0
+// and then launches the QDrop instantiation; with all four 0 the sequence and the bits are the eval-mode pass's.
+template <bool kDrop, class Buffers>
+void qb_forward(const QbCall &c, unsigned tiles, float *feat, float *c1, Buffers buffers)
+{
+    hipStream_t s = static_cast<hipStream_t>(c.stream);
+    const float *P = c.plain;
+    const int ni = (int)c.n, ff = c.dim_ff;
+    hipLaunchKernelGGL(qb_conv_kernel, dim3((unsigned)c.n), dim3(256), 0, s, static_cast<const uint8_t *>(c.boards), P, feat, c1);
+    hipLaunchKernelGGL((qb_linear_kernel<false>), dim3((unsigned)(kD + 63) / 64, tiles), dim3(256), 0, s, static_cast<const float *>(feat), kFlat,
+                       P + kPlEmbW, P + kPlEmbB, buffers(0, c.n_layers == 1).x0, kD, ni);
+    for (int l = 0; l < c.n_layers; ++l) {
+        const bool last = l == c.n_layers - 1;
+        qb_forward_layer<kDrop>(s, P + kPlLayer0 + (size_t)l * pl_layer(ff), ff,
+                                DropSites(kDomQnetDropout, c.seed, c.call_index, l, kDrop ? c.p4 : nullptr), buffers(l, last),
+                                last ? P + kPlLayer0 + (size_t)c.n_layers * pl_layer(ff) : nullptr, c.q, ni, tiles);
+    }
+}
+
+// a forward-only pass: g2048_qnet_forward_batch (kDrop false) or g2048_qnet_forward_batch_dropout
+template <bool kDrop>
+int qb_forward_pass(const char *entry, const QbCall &c)
+{
+    if (c.n == 0) return G2048_OK;
+    if (const int rc = qb_check<kDrop>(entry, c)) return rc;
+    const FwdWorkspace ws(c.n, c.dim_ff);
+    float *base = static_cast<float *>(c.workspace), *x = base + ws.x(), *qkv = base + ws.qkv(), *att = base + ws.att(), *h = base + ws.h();
+    float *nowhere = nullptr;
+    qb_forward<kDrop>(c, (unsigned)(ws.np / 16), h, nowhere, [&](int, bool last) {
+        return LayerBuffers{x, qkv, att, x, nowhere, h, last ? nowhere : x, nowhere, nowhere, nowhere};
+    });
+    return check_launch(entry);
 }
 
 }  // namespace

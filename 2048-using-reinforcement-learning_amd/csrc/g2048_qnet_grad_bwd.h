@@ -1,5 +1,6 @@
-// g2048_qnet_grad_bwd.h -- the backward kernels of the hybrid agent's Q-network and the workspace they share with the forward that
-// keeps its activations: shared by g2048_qnet_grad.hip (g2048_qnet_loss_grad, eval mode) and g2048_qnet_train.hip (the same pass with
+// g2048_qnet_grad_bwd.h -- the backward kernels of the hybrid agent's Q-network, the workspace they share with the forward that
+// keeps its activations, and the one launch sequence of the loss and gradient pass (qg_pass<kDrop>; its forward is qb_forward of
+// g2048_qnet_batch_fwd.h): shared by g2048_qnet_grad.hip (g2048_qnet_loss_grad, eval mode) and g2048_qnet_train.hip (the same pass with
 // the reference's live dropout, libg2048_train_hip.so). Device code, included by those two files and nothing else; every kernel is
 // per translation unit. What the phases are and the rules they keep: the head of g2048_qnet_grad.hip. The two attention kernels
 // take a QDrop (g2048_qnet_drop.h) as a trailing argument in the training pass: each hashes the tile it recomputes; the instantiation
@@ -7,7 +8,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "g2048_grad_products.h"
+#include "g2048_host.h"
 #include "g2048_mfma.h"
 #include "g2048_qnet_batch_fwd.h"
 #include "g2048_qnet_drop.h"
@@ -365,6 +369,110 @@ __global__ __launch_bounds__(256) void qg_conv_dw1_kernel(const float *__restric
     }
     if (t < 4) dW[ch * 4 + t] = red[t][0];
     if (t == 4) db[ch] = red[4][0];
+}
+
+// ------------------------------------------------------------------------------------------------------------- host --
+// the training pass's workspace: GradWorkspace, then dsm [np][128], the LayerNorm backward's ds x a site's multipliers
+struct TrainWorkspace : GradWorkspace {
+    using GradWorkspace::GradWorkspace;
+    size_t dsm() const { return GradWorkspace::floats(); }
+    size_t floats() const { return dsm() + np * kD; }
+};
+
+// A loss and gradient pass: g2048_qnet_loss_grad (kDrop false, GradWorkspace) or g2048_qnet_loss_grad_dropout (TrainWorkspace). The
+// forward is qb_forward with every layer's activations kept, so q has the bits of the forward-only pass; then the loss and the
+// backward, one phase a launch (the head of g2048_qnet_grad.hip). kDrop true: where the masks go is in the head of
+// g2048_qnet_train.hip; a site with p4[s] == 0 launches the instantiation without a QDrop.
+template <bool kDrop>
+int qg_pass(const char *entry, const QbCall &c)
+{
+    if (c.n == 0) return G2048_OK;
+    if (const int rc = qb_check<kDrop>(entry, c)) return rc;
+    hipStream_t s = static_cast<hipStream_t>(c.stream);
+    const size_t n = c.n, nl = (size_t)c.n_layers;
+    const std::conditional_t<kDrop, TrainWorkspace, GradWorkspace> ws(n, c.dim_ff, c.n_layers);
+    float *base = static_cast<float *>(c.workspace);
+    const float *P = c.plain;
+    float *G = c.grad;
+    const int ni = (int)n, ff = c.dim_ff;
+    const unsigned tiles = (unsigned)(ws.np / 16);
+    const float *none = nullptr;
+    float *nowhere = nullptr;
+    const float *fc = P + kPlLayer0 + nl * pl_layer(ff);
+
+    // ---- the forward, its activations kept
+    float *feat = base + ws.feat(), *c1 = base + ws.c1();
+    qb_forward<kDrop>(c, tiles, feat, c1, [&](size_t l, bool) {
+        return LayerBuffers{base + ws.x(l), base + ws.qkv(l), base + ws.att(l), base + ws.x1(l), base + ws.pre1(l), base + ws.h(l),
+                            base + ws.x(l + 1), base + ws.pre2(l), base + ws.amax(l), base + ws.asum(l)};
+    });
+
+    // ---- the loss and the backward
+    const auto dx = [&](const float *dY, int M, const float *W, int K, const float *res, const float *mask, float *dX) {
+        hipLaunchKernelGGL(qg_dx_kernel<>, dim3((unsigned)(K + 63) / 64, tiles), dim3(256), 0, s, dY, M, W, K, res, mask, dX, ni);
+    };
+    const auto dw = [&](const float *dY, int ldy, int M, const float *X, int K, float *dW, float *db) {
+        hipLaunchKernelGGL(qg_dw_kernel, dim3((unsigned)(K + 63) / 64, (unsigned)(M + 15) / 16), dim3(256), 0, s, dY, ldy, M, X, K, dW, db, ni);
+    };
+    float *part = base + ws.part();
+    const auto ln = [&](const float *g, const float *pre, const float *norm, const float *eps, float *ds, float *dnorm, float *zero) {
+        hipLaunchKernelGGL(qg_ln_kernel, dim3(tiles), dim3(512), 0, s, g, pre, norm, eps, ds, part, ni);
+        hipLaunchKernelGGL(qg_tiles_kernel, dim3(1), dim3(256), 0, s, static_cast<const float *>(part), (int)tiles, dnorm, zero);
+    };
+    float *ga = base + ws.ga(), *gb = base + ws.gb(), *ds = base + ws.ds(), *datt = base + ws.datt(), *dqkv = base + ws.dqkv(),
+          *dh = base + ws.dh(), *dz1 = base + ws.dz1(), *dd = base + ws.dd(), *dq = base + ws.dq(), *term = base + ws.term();
+    // ds x the multipliers of site 1 or 3: what enters the dropped projection's dW and dX (ds itself where the site is off)
+    const auto scaled = [&](const QDrop *d) -> const float * {
+        if constexpr (kDrop) {
+            if (d) {
+                float *dsm = base + ws.dsm();
+                hipLaunchKernelGGL(qt_scale_kernel<QDrop>, dim3(blocks_for(n * kD, 256)), dim3(256), 0, s, static_cast<const float *>(ds), dsm, *d,
+                                   (uint32_t)(n * kD));
+                return dsm;
+            }
+        }
+        return ds;
+    };
+    hipLaunchKernelGGL(qg_head_kernel, dim3((unsigned)n), dim3(128), 0, s, reinterpret_cast<const float4 *>(c.q),
+                       reinterpret_cast<const long long *>(c.actions), c.targets, c.weights, fc, c.td, reinterpret_cast<float4 *>(dq), term, ga, ni);
+    hipLaunchKernelGGL(qg_sum_kernel, dim3(1), dim3(256), 0, s, static_cast<const float *>(term), c.loss, ni);
+    {
+        float *Gfc = G + kPlLayer0 + nl * pl_layer(ff);
+        dw(dq, 4, 4, base + ws.x(nl), kD, Gfc, Gfc + 4 * kD);
+    }
+    for (size_t l = nl; l-- > 0;) {
+        const size_t lo = kPlLayer0 + l * pl_layer(ff);
+        const float *L = P + lo, *norms = L + pl_norm(ff);
+        float *GL = G + lo, *gnorms = GL + pl_norm(ff);
+        const float *x0 = base + ws.x(l), *qkv = base + ws.qkv(l), *att = base + ws.att(l), *x1 = base + ws.x1(l), *h = base + ws.h(l);
+        const float *amax = base + ws.amax(l), *asum = base + ws.asum(l);
+        const DropSites st(kDomQnetDropout, c.seed, c.call_index, (int)l, kDrop ? c.p4 : nullptr);
+        ln(ga, base + ws.pre2(l), norms + 2 * kD, norms + 4 * kD + 1, ds, gnorms + 2 * kD, gnorms + 4 * kD);
+        const float *d3 = scaled(st.at(3));
+        dw(d3, kD, kD, h, ff, GL + pl_w2(ff), GL + pl_b2(ff));
+        launch_site<kDrop>(st.at(2), [](auto... d) { return qg_dx_kernel<decltype(d)...>; }, dim3((unsigned)(ff + 63) / 64, tiles), dim3(256), s, d3,
+                           kD, L + pl_w2(ff), ff, none, h, dh, ni);
+        dw(dh, ff, ff, x1, kD, GL + kPlW1, GL + pl_b1(ff));
+        dx(dh, ff, L + kPlW1, kD, ds, none, gb);
+        ln(gb, base + ws.pre1(l), norms, norms + 4 * kD, ds, gnorms, nowhere);
+        const float *d1 = scaled(st.at(1));
+        dw(d1, kD, kD, att, kD, GL + kPlOutW, GL + kPlOutB);
+        dx(d1, kD, L + kPlOutW, kD, none, none, datt);
+        launch_site<kDrop>(st.at(0), [](auto... d) { return qg_att_dq_kernel<decltype(d)...>; }, dim3(tiles, kHeads), dim3(64), s, qkv, att,
+                           static_cast<const float *>(datt), amax, asum, dqkv, dd, ni);
+        launch_site<kDrop>(st.at(0), [](auto... d) { return qg_att_dkv_kernel<decltype(d)...>; }, dim3(tiles, kHeads), dim3(64), s, qkv,
+                           static_cast<const float *>(datt), amax, asum, static_cast<const float *>(dd), dqkv, ni);
+        dw(dqkv, kQkv, kQkv, x0, kD, GL + kPlInW, GL + kPlInB);
+        dx(dqkv, kQkv, L + kPlInW, kD, ds, none, ga);
+    }
+    dw(ga, kD, kD, feat, kFlat, G + kPlEmbW, G + kPlEmbB);
+    dx(ga, kD, P + kPlEmbW, kFlat, none, feat, dh);
+    hipLaunchKernelGGL(qg_conv_dw2_kernel, dim3(kC2), dim3(512), 0, s, static_cast<const float *>(dh), static_cast<const float *>(c1),
+                       G + kPlC2W, G + kPlC2B, ni);
+    hipLaunchKernelGGL(qg_conv_dz1_kernel, dim3((unsigned)n), dim3(256), 0, s, static_cast<const float *>(dh), static_cast<const float *>(c1), P, dz1);
+    hipLaunchKernelGGL(qg_conv_dw1_kernel, dim3(kC1), dim3(256), 0, s, static_cast<const float *>(dz1), static_cast<const uint8_t *>(c.boards),
+                       G + kPlC1W, G + kPlC1B, ni);
+    return check_launch(entry);
 }
 
 }  // namespace

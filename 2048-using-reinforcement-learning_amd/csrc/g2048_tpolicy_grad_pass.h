@@ -13,7 +13,7 @@
 //             s = 1  tg_linear_kernel<false> (out_proj): (X W^T + b) x m + res      s = 3  the same on linear2
 //             s = 2  tg_linear_kernel<true> (linear1): relu(..) x m; the backward's recomputation of the hidden layer passes the
 //                    same QDrop and is bit for bit the forward's
-//   backward  s = 3, 1  the gradient ds leaving the LayerNorm backward goes to the residual path as it is and x m (tg_scale_kernel,
+//   backward  s = 3, 1  the gradient ds leaving the LayerNorm backward goes to the residual path as it is and x m (qt_scale_kernel,
 //                    one elementwise launch into the one extra array dsm [16 n][64]) into the dW / dX products of linear2 / out_proj
 //             s = 2  qg_dx_kernel<QDrop> through linear2: x m next to the ReLU mask; linear2's dW reads the dropped hidden layer
 //             s = 0  tg_attention_bwd_kernel, with M the multipliers and P the kept unmasked probabilities:
@@ -84,9 +84,6 @@ struct Workspace {
     size_t train_floats() const { return dsm() + T * kD; }
 };
 
-typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));      // 16 bytes of the plain buffer: 4-byte aligned at worst
-__device__ inline f4 load_w(const float *p) { const f4u v = *reinterpret_cast<const f4u *>(p); return f4{v[0], v[1], v[2], v[3]}; }
-
 __device__ inline float sum16(float v)               // over the 16 lanes that share lane >> 4, the same on all of them
 {
 #pragma unroll
@@ -144,23 +141,8 @@ __global__ __launch_bounds__(256) void tg_embed_bwd_kernel(const float *__restri
 // ----------------------------------------------------------------------------------------------------------- linear --
 // Y [n][M] = act(X [n][K] W^T + b (+ RES)): the tile is D[feature 16 o + 4 g + r][row col]; lane (col, g): the A operand
 // W[16 o + col][16 c + 4 g ..], the B operand X[row][16 c + 4 g ..], four MFMAs a chunk of 16; K is a multiple of 32. Chunk c of a
-// group of eight accumulates into acc[c], combined pairwise: the order is fixed. Four wavefronts a block = four feature tiles of
-// one row tile; grid (M / 64 up, row tiles).
-template <int N>
-__device__ inline void linear_chunks(const float *__restrict__ wrow, const float *__restrict__ xrow, bool live, f4 (&acc)[8])
-{
-    f4 w[N], x[N];
-#pragma unroll
-    for (int c = 0; c < N; ++c) {
-        w[c] = load_w(wrow + 16 * c);
-        x[c] = live ? load_f4(xrow + 16 * c) : splat(0.0f);
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-        for (int c = 0; c < N; ++c) acc[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[c][r], x[c][r], acc[c], 0, 0, 0);
-}
-
+// group of eight accumulates into acc[c] (chunks_product, g2048_mfma.h), combined pairwise: the order is fixed. Four wavefronts a
+// block = four feature tiles of one row tile; grid (M / 64 up, row tiles).
 // With a QDrop the product is a dropout site's, element row M + feature (at most 16,384 x 65,536 = 2^30): sites 1 and 3 (no ReLU)
 // (X W^T + b) x m + RES, site 2 relu(..) x m.
 template <bool RELU, class... MaybeDrop>
@@ -176,8 +158,8 @@ __global__ __launch_bounds__(256) void tg_linear_kernel(const float *__restrict_
     const float *wrow = W + (size_t)(16 * o + col) * K + 4 * g, *xrow = X + (size_t)row * K + 4 * g;
     f4 acc[8] = {load_w(bias + 16 * o + 4 * g), splat(0.0f), splat(0.0f), splat(0.0f), splat(0.0f), splat(0.0f), splat(0.0f), splat(0.0f)};
     int k = 0;
-    for (; k + 128 <= K; k += 128) linear_chunks<8>(wrow + k, xrow + k, live, acc);
-    for (; k < K; k += 32) linear_chunks<2>(wrow + k, xrow + k, live, acc);
+    for (; k + 128 <= K; k += 128) chunks_product<8>(wrow + k, xrow + k, live, acc);
+    for (; k < K; k += 32) chunks_product<2>(wrow + k, xrow + k, live, acc);
     if (!live) return;
     f4 v = sum8(acc);
     const size_t at = (size_t)row * M + 16 * o + 4 * g;
@@ -466,15 +448,6 @@ __global__ __launch_bounds__(64) void tg_head_kernel(const float *__restrict__ H
     }
 }
 
-// Y[i] = X[i] m_i over the 16 n x 64 elements of site 1 or 3 (element token 64 + feature = i); a template so that only the
-// library that launches it holds it
-template <class Drop>
-__global__ __launch_bounds__(256) void tg_scale_kernel(const float *__restrict__ X, float *__restrict__ Y, Drop drop, uint32_t count)
-{
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i < count) Y[i] = X[i] * qdrop_mult(drop, i);
-}
-
 // out[0 .. N) = 0: the training-mode pass clears a layer's two LayerNorm-eps slots of grad with a launch, not with a memset node
 // (a captured graph of update() replayed a memset node of the pass with another byte on the MI355X's runtime: docs/LOG.md R32)
 template <int N>
@@ -484,8 +457,6 @@ __global__ __launch_bounds__(64) void tg_zero_kernel(float *__restrict__ out)
 }
 
 // ------------------------------------------------------------------------------------------------------------- host --
-inline bool good_coef(float v) { return v >= 0.0f && std::isfinite(v); }
-
 inline bool good_shape(size_t n, int dim_ff, int n_layers)
 {
     return n >= 1 && n <= G2048_TLEARN_BATCH_MAX && good_encoder_shape(dim_ff, n_layers);
@@ -533,20 +504,6 @@ inline int tg_check(const char *entry, const TgCall &c, size_t needed, const cha
     return G2048_OK;
 }
 
-template <bool kDrop, bool RELU>
-void tg_linear(hipStream_t s, const QDrop *d, const float *X, int K, const float *W, const float *b, const float *res, float *Y, int M, int rows,
-               unsigned tiles)
-{
-    const dim3 grid((unsigned)(M + 63) / 64, tiles);
-    if constexpr (kDrop) {
-        if (d) {
-            hipLaunchKernelGGL((tg_linear_kernel<RELU, QDrop>), grid, dim3(256), 0, s, X, K, W, b, res, Y, M, rows, *d);
-            return;
-        }
-    }
-    hipLaunchKernelGGL((tg_linear_kernel<RELU>), grid, dim3(256), 0, s, X, K, W, b, res, Y, M, rows);
-}
-
 // The launch sequence, after tg_check. kDrop false: the eval-mode pass. kDrop true: site s of layer l is live where p4[s] > 0 and
 // then launches the QDrop instantiation; with all four 0 the sequence and the bits are the eval-mode pass's.
 template <bool kDrop>
@@ -568,28 +525,15 @@ int tg_pass(const char *entry, const TgCall &c, uint32_t domain = 0)
     const float *Pt = P + tail;
     float *Gt = G + tail;
 
-    // site s of layer l: at(s) is its QDrop where it is live, else null
-    struct Live {
-        QDrop d[4];
-        bool on[4] = {false, false, false, false};
-        const QDrop *at(int k) const { return on[k] ? &d[k] : nullptr; }
-    };
-    const auto sites = [&](size_t l) {
-        Live v;
-        if constexpr (kDrop) {
-            for (int k = 0; k < 4; ++k) {
-                v.on[k] = c.p4[k] > 0.0;
-                if (v.on[k]) v.d[k] = qdrop_site(domain, c.seed, c.call_index, (int)l, k, c.p4[k]);
-            }
-        }
-        return v;
-    };
+    // site k of layer l: at(k) is its QDrop where it is live, else null
+    const auto sites = [&](size_t l) { return DropSites(domain, c.seed, c.call_index, (int)l, kDrop ? c.p4 : nullptr); };
     const auto linear = [&](bool relu_out, const QDrop *d, const float *X, int K, const float *W, const float *b, const float *res, float *Y, int M,
                             int rows, unsigned tiles) {
+        const dim3 grid((unsigned)(M + 63) / 64, tiles);
         if (relu_out)
-            tg_linear<kDrop, true>(s, d, X, K, W, b, res, Y, M, rows, tiles);
+            launch_site<kDrop>(d, [](auto... q) { return tg_linear_kernel<true, decltype(q)...>; }, grid, dim3(256), s, X, K, W, b, res, Y, M, rows);
         else
-            tg_linear<kDrop, false>(s, d, X, K, W, b, res, Y, M, rows, tiles);
+            launch_site<kDrop>(d, [](auto... q) { return tg_linear_kernel<false, decltype(q)...>; }, grid, dim3(256), s, X, K, W, b, res, Y, M, rows);
     };
     const auto norm = [&](const float *S, const float *np, const float *eps, float *Y, float *stat) {
         hipLaunchKernelGGL(tg_ln_kernel, dim3(ttiles), dim3(256), 0, s, S, np, eps, Y, reinterpret_cast<float2 *>(stat), T);
@@ -603,17 +547,10 @@ int tg_pass(const char *entry, const TgCall &c, uint32_t domain = 0)
         const float *x0 = base + ws.x(l);
         float *qkv = base + ws.qkv(l), *prob = base + ws.prob(l), *att = base + ws.att(l), *pre1 = base + ws.pre1(l), *x1 = base + ws.x1(l),
               *pre2 = base + ws.pre2(l), *stat = base + ws.stat(l);
-        const Live st = sites(l);
+        const DropSites st = sites(l);
         linear(false, nullptr, x0, kD, L + kPlInW, L + kPlInB, none, qkv, kQkv, T, ttiles);
-        bool hashed = false;
-        if constexpr (kDrop) {
-            if (st.at(0)) {
-                hipLaunchKernelGGL(tg_attention_kernel<QDrop>, dim3((unsigned)n), dim3(256), 0, s, static_cast<const float *>(qkv), att, prob,
-                                   *st.at(0));
-                hashed = true;
-            }
-        }
-        if (!hashed) hipLaunchKernelGGL(tg_attention_kernel<>, dim3((unsigned)n), dim3(256), 0, s, static_cast<const float *>(qkv), att, prob);
+        launch_site<kDrop>(st.at(0), [](auto... q) { return tg_attention_kernel<decltype(q)...>; }, dim3((unsigned)n), dim3(256), s,
+                           static_cast<const float *>(qkv), att, prob);
         linear(false, st.at(1), att, kD, L + kPlOutW, L + kPlOutB, x0, pre1, kD, T, ttiles);
         norm(pre1, norms, norms + 4 * kD, x1, stat);
         linear(true, st.at(2), x1, kD, L + kPlW1, L + pl_b1(ff), none, h, ff, T, ttiles);
@@ -644,14 +581,8 @@ int tg_pass(const char *entry, const TgCall &c, uint32_t domain = 0)
           *wpart = base + ws.wpart(), *bpart = base + ws.bpart(), *cpart = base + ws.cpart();
     const auto dx = [&](const QDrop *d, const float *dY, int M, const float *W, int K, const float *res, const float *mask, float *dX, int rows,
                         unsigned tiles) {
-        const dim3 grid((unsigned)(K + 63) / 64, tiles);
-        if constexpr (kDrop) {
-            if (d) {
-                hipLaunchKernelGGL(qg_dx_kernel<QDrop>, grid, dim3(256), 0, s, dY, M, W, K, res, mask, dX, rows, *d);
-                return;
-            }
-        }
-        hipLaunchKernelGGL(qg_dx_kernel<>, grid, dim3(256), 0, s, dY, M, W, K, res, mask, dX, rows);
+        launch_site<kDrop>(d, [](auto... q) { return qg_dx_kernel<decltype(q)...>; }, dim3((unsigned)(K + 63) / 64, tiles), dim3(256), s, dY, M, W, K,
+                           res, mask, dX, rows);
     };
     const auto dw = [&](const float *dY, int ldy, int M, const float *X, int K, float *dW, float *db) {      // over the n boards
         hipLaunchKernelGGL(qg_dw_kernel, dim3((unsigned)(K + 63) / 64, (unsigned)(M + 15) / 16), dim3(256), 0, s, dY, ldy, M, X, K, dW, db, ni);
@@ -675,7 +606,7 @@ int tg_pass(const char *entry, const TgCall &c, uint32_t domain = 0)
         if constexpr (kDrop) {
             if (d) {
                 float *dsm = base + ws.dsm();
-                hipLaunchKernelGGL(tg_scale_kernel<QDrop>, dim3(blocks_for((size_t)T * kD, 256)), dim3(256), 0, s, static_cast<const float *>(ds),
+                hipLaunchKernelGGL(qt_scale_kernel<QDrop>, dim3(blocks_for((size_t)T * kD, 256)), dim3(256), 0, s, static_cast<const float *>(ds),
                                    dsm, *d, (uint32_t)((size_t)T * kD));
                 return dsm;
             }
@@ -694,7 +625,7 @@ int tg_pass(const char *entry, const TgCall &c, uint32_t domain = 0)
         float *GL = G + lo, *gnorms = GL + pl_norm(ff);
         const float *x0 = base + ws.x(l), *qkv = base + ws.qkv(l), *prob = base + ws.prob(l), *att = base + ws.att(l), *x1 = base + ws.x1(l),
                     *stat = base + ws.stat(l);
-        const Live st = sites(l);
+        const DropSites st = sites(l);
         linear(true, st.at(2), x1, kD, L + kPlW1, L + pl_b1(ff), none, h, ff, T, ttiles);      // the hidden layer again, the same mask
         norm_bwd(ga, base + ws.pre2(l), stat + 2 * (size_t)T, norms + 2 * kD, gnorms + 2 * kD);
         const float *d3 = scaled(st.at(3));
@@ -706,16 +637,8 @@ int tg_pass(const char *entry, const TgCall &c, uint32_t domain = 0)
         const float *d1o = scaled(st.at(1));
         dw_split(d1o, kD, att, kD, GL + kPlOutW, GL + kPlOutB);
         dx(nullptr, d1o, kD, L + kPlOutW, kD, none, none, datt, T, ttiles);
-        bool hashed = false;
-        if constexpr (kDrop) {
-            if (st.at(0)) {
-                hipLaunchKernelGGL(tg_attention_bwd_kernel<QDrop>, dim3((unsigned)n), dim3(256), 0, s, qkv, prob, static_cast<const float *>(datt),
-                                   dqkv, *st.at(0));
-                hashed = true;
-            }
-        }
-        if (!hashed)
-            hipLaunchKernelGGL(tg_attention_bwd_kernel<>, dim3((unsigned)n), dim3(256), 0, s, qkv, prob, static_cast<const float *>(datt), dqkv);
+        launch_site<kDrop>(st.at(0), [](auto... q) { return tg_attention_bwd_kernel<decltype(q)...>; }, dim3((unsigned)n), dim3(256), s, qkv, prob,
+                           static_cast<const float *>(datt), dqkv);
         dw_split(dqkv, kQkv, x0, kD, GL + kPlInW, GL + kPlInB);
         dx(nullptr, dqkv, kQkv, L + kPlInW, kD, ds, none, ga, T, ttiles);
         if constexpr (kDrop)                                                                                            // the eps slots

@@ -8,7 +8,7 @@
 // as their trailing argument. Acting has no dropout: the fused kernel of g2048_tpolicy.hip is not here.
 //
 // Where the masks go, what is kept (the UNMASKED attention probabilities and nothing of any mask) and the identity the attention's
-// backward uses are in that header's head comment. Sites 1 and 3 in the backward are one elementwise launch (tg_scale_kernel) into
+// backward uses are in that header's head comment. Sites 1 and 3 in the backward are one elementwise launch (qt_scale_kernel of g2048_qnet_drop.h) into
 // one extra [16 n][64] array, not fused into the dW / dX products, so qg_dx_kernel and tg_dw_split_kernel stay as they are.
 // A site with p == 0 is not hashed: its launch is the instantiation without a QDrop, which is the learner library's kernel. With all
 // four 0 the kernel launches are g2048_tpolicy_loss_grad's in its order and so are the bits; the one difference is that a layer's two
@@ -20,21 +20,6 @@
 #include "g2048_tpolicy_grad_pass.h"
 
 namespace {
-
-// keep[i] = the keep bit of element first + i of a site, i < count
-__global__ __launch_bounds__(256) void tt_mask_kernel(uint8_t *__restrict__ keep, QDrop drop, uint32_t first, uint32_t count)
-{
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i < count) keep[i] = qdrop_keep(drop, first + i) ? 1 : 0;
-}
-
-int check_p(const char *entry, const double *p4)
-{
-    if (!p4) return fail(G2048_ERR_ARG, "%s: null pointer", entry);
-    for (int s = 0; s < 4; ++s)
-        if (!good_qdrop(p4[s])) return fail(G2048_ERR_ARG, "%s: p[%d] must be finite, 0 <= p < 1", entry, s);
-    return G2048_OK;
-}
 
 size_t train_bytes(size_t n, int dim_ff, int n_layers)
 {
@@ -83,22 +68,10 @@ int g2048_tpolicy_forward_dropout(const void *boards, const float *plain_f32, si
 int g2048_tpolicy_dropout_mask(uint64_t seed, uint64_t call_index, int layer, int site, double p, size_t n, int dim_ff, size_t first_row,
                                size_t rows, uint8_t *keep_out, void *stream)
 {
-    const char *entry = "g2048_tpolicy_dropout_mask";
-    if (n == 0 || rows == 0) return G2048_OK;
-    if (!keep_out) return fail(G2048_ERR_ARG, "%s: null pointer", entry);
-    if (n > G2048_TLEARN_BATCH_MAX) return fail(G2048_ERR_ARG, "%s: n must not exceed G2048_TLEARN_BATCH_MAX = %d", entry, G2048_TLEARN_BATCH_MAX);
-    if (!good_encoder_shape(dim_ff, 1)) return fail(G2048_ERR_ARG, "%s: dim_ff must be a multiple of 32 (32 .. 65536)", entry);
-    if (layer < 0 || layer >= 64) return fail(G2048_ERR_ARG, "%s: layer must be 0 .. 63", entry);
-    if (site < 0 || site > 3) return fail(G2048_ERR_ARG, "%s: site must be 0 .. 3", entry);
-    if (!good_qdrop(p)) return fail(G2048_ERR_ARG, "%s: p must be finite, 0 <= p < 1", entry);
-    const size_t height = site == 0 ? (size_t)kHeads * kTok * n : (size_t)kTok * n;
-    const size_t width = site == 0 ? (size_t)kTok : site == 2 ? (size_t)dim_ff : (size_t)kD;
-    if (first_row > height || rows > height - first_row)
-        return fail(G2048_ERR_ARG, "%s: rows %zu .. %zu lie past the site's matrix of %zu rows", entry, first_row, first_row + rows, height);
-    // at most 65,536 x 16 or 16,384 x 65,536 = 2^30 elements: 32 bits hold every index
-    hipLaunchKernelGGL(tt_mask_kernel, dim3(blocks_for(rows * width, 256)), dim3(256), 0, static_cast<hipStream_t>(stream), keep_out,
-                       qdrop_site(kDomTpolicyDropout, seed, call_index, layer, site, p), (uint32_t)(first_row * width), (uint32_t)(rows * width));
-    return check_launch(entry);
+    // at most 65,536 x 16 or 16,384 x 65,536 = 2^30 elements
+    return dropout_mask("g2048_tpolicy_dropout_mask", kDomTpolicyDropout, G2048_TLEARN_BATCH_MAX, "G2048_TLEARN_BATCH_MAX", seed, call_index, layer,
+                        site, p, n, dim_ff, site == 0 ? (size_t)kHeads * kTok * n : (size_t)kTok * n,
+                        site == 0 ? (size_t)kTok : site == 2 ? (size_t)dim_ff : (size_t)kD, first_row, rows, keep_out, stream);
 }
 
 }  // extern "C"

@@ -67,6 +67,30 @@ def _float_output(t, shape, name, dev):
     return t
 
 
+def _flat_plain(plain, floats):
+    """plain: a flat float32 device tensor of `floats` parameters."""
+    L.require_device_tensor(plain, torch.float32, None, "plain")
+    if plain.dim() != 1 or plain.numel() != floats:
+        raise ValueError("g2048: plain must be a flat float32 tensor of %d parameters" % floats)
+
+
+def _grad_output(grad, floats, dev):
+    """grad as given, or allocated: a flat float32 device tensor of `floats` floats."""
+    if grad is None:
+        grad = torch.empty(floats, dtype=torch.float32, device=dev)
+    L.require_device_tensor(grad, torch.float32, None, "grad")
+    if grad.dim() != 1 or grad.numel() != floats:
+        raise ValueError("g2048: grad must be a flat float32 tensor of %d floats" % floats)
+    return grad
+
+
+def _sized(nb, message, *values):
+    """A size query's bytes; 0 is the library's refusal of the arguments: ValueError(message % values)."""
+    if nb == 0:
+        raise ValueError(message % values)
+    return nb
+
+
 def _step_buffers(buffers):
     """The flat float32 buffers of an optimiser step, (name, tensor, floats) each: dtype and length of ALL of them before any
     device, since such a mistake reads the same everywhere; then every one on a device, and on the first one's, which is returned."""
@@ -496,10 +520,7 @@ def _pack(fn, plain, args, nb, out):
 
 def policy_packed_bytes(precision="f32", n_out=4):
     """Bytes of one packed network (g2048_policy_packed_bytes)."""
-    nb = L.lib().g2048_policy_packed_bytes(POLICY_PRECISIONS[precision], int(n_out))
-    if nb == 0:
-        raise ValueError("g2048: n_out must be 4 (actor) or 1 (critic)")
-    return nb
+    return _sized(L.lib().g2048_policy_packed_bytes(POLICY_PRECISIONS[precision], int(n_out)), "g2048: n_out must be 4 (actor) or 1 (critic)")
 
 
 def policy_pack(plain, n_out, precision="f32", out=None):
@@ -553,9 +574,7 @@ def _net_packed_bytes(kind, precision, dim_ff, n_layers):
 def _net_pack(kind, plain, dim_ff, n_layers, precision, out):
     L.require_device_tensor(plain, torch.float32, None, "plain")
     nb = _net_packed_bytes(kind, precision, dim_ff, n_layers)
-    floats = _NETS[kind][0](dim_ff, n_layers)
-    if plain.dim() != 1 or plain.numel() != floats:
-        raise ValueError("g2048: plain must be a flat float32 tensor of %d parameters" % floats)
+    _flat_plain(plain, _NETS[kind][0](dim_ff, n_layers))
     return _pack(getattr(L.lib(), _NETS[kind][2]), plain, (int(dim_ff), int(n_layers), POLICY_PRECISIONS[precision]), nb, out)
 
 
@@ -595,12 +614,10 @@ def tpolicy_forward(boards, packed, dim_ff, n_layers, precision="f32", probs=Non
 
 def tpolicy_grad_workspace_bytes(n, dim_ff, n_layers):
     """Bytes of the workspace tpolicy_loss_grad needs for n boards (g2048_tpolicy_grad_workspace, the learner library)."""
-    nb = L.tlearn_lib().g2048_tpolicy_grad_workspace(int(n), int(dim_ff), int(n_layers))
-    if nb == 0:
-        raise ValueError("g2048: tpolicy_loss_grad takes 1 .. %d boards (16 tokens each; a larger batch is refused, not truncated), a "
-                         "dim_ff that is a multiple of 32 and 1 .. 64 layers (got n = %d, dim_ff = %d, n_layers = %d)"
-                         % (L.TLEARN_BATCH_MAX, int(n), int(dim_ff), int(n_layers)))
-    return nb
+    return _sized(L.tlearn_lib().g2048_tpolicy_grad_workspace(int(n), int(dim_ff), int(n_layers)),
+                  "g2048: tpolicy_loss_grad takes 1 .. %d boards (16 tokens each; a larger batch is refused, not truncated), a "
+                  "dim_ff that is a multiple of 32 and 1 .. 64 layers (got n = %d, dim_ff = %d, n_layers = %d)",
+                  L.TLEARN_BATCH_MAX, int(n), int(dim_ff), int(n_layers))
 
 
 def tpolicy_loss_grad(boards, plain, actions, old_log_probs, advantages, returns, dim_ff, n_layers, clip_epsilon=0.3, value_coef=0.4,
@@ -617,22 +634,16 @@ def tpolicy_loss_grad(boards, plain, actions, old_log_probs, advantages, returns
     the backward (the training library's g2048_tpolicy_loss_grad_dropout; the workspace is then tpolicy_train_workspace_bytes').
     Returns (losses float32 (4,) = loss, actor, value, entropy; probs float32 (n,4); value float32 (n,1); grad)."""
     p = qnet_dropout_p(dropout)
+    floats = tpolicy_plain_floats(dim_ff, n_layers)
     L.require_device_tensor(boards, torch.uint8, (16,), "boards")
-    L.require_device_tensor(plain, torch.float32, None, "plain")
+    _flat_plain(plain, floats)
     L.require_device_tensor(actions, torch.int64, (), "actions")
     for t, name in ((old_log_probs, "old_log_probs"), (advantages, "advantages"), (returns, "returns")):
         L.require_device_tensor(t, torch.float32, (), name)
     n, dev = boards.shape[0], boards.device
-    floats = tpolicy_plain_floats(dim_ff, n_layers)
-    if plain.dim() != 1 or plain.numel() != floats:
-        raise ValueError("g2048: plain must be a flat float32 tensor of %d parameters" % floats)
     if not (actions.shape[0] == old_log_probs.shape[0] == advantages.shape[0] == returns.shape[0] == n):
         raise ValueError("g2048: actions, old_log_probs, advantages and returns must have one entry per board")
-    if grad is None:
-        grad = torch.empty(floats, dtype=torch.float32, device=dev)
-    L.require_device_tensor(grad, torch.float32, None, "grad")
-    if grad.dim() != 1 or grad.numel() != floats:
-        raise ValueError("g2048: grad must be a flat float32 tensor of %d floats" % floats)
+    grad = _grad_output(grad, floats, dev)
     if losses is None:
         losses = torch.empty(4, dtype=torch.float32, device=dev)
     L.require_device_tensor(losses, torch.float32, None, "losses")
@@ -660,12 +671,10 @@ def tpolicy_loss_grad(boards, plain, actions, old_log_probs, advantages, returns
 def tpolicy_train_workspace_bytes(n, dim_ff, n_layers):
     """Bytes of the workspace tpolicy_loss_grad with dropout and tpolicy_forward_train need for n boards
     (g2048_tpolicy_train_workspace, the training library): tpolicy_grad_workspace_bytes plus one (16 n, 64) float32 array."""
-    nb = L.ttrain_lib().g2048_tpolicy_train_workspace(int(n), int(dim_ff), int(n_layers))
-    if nb == 0:
-        raise ValueError("g2048: the transformer policy's training passes take 1 .. %d boards (16 tokens each; a larger batch is refused, "
-                         "not truncated), a dim_ff that is a multiple of 32 and 1 .. 64 layers (got n = %d, dim_ff = %d, n_layers = %d)"
-                         % (L.TLEARN_BATCH_MAX, int(n), int(dim_ff), int(n_layers)))
-    return nb
+    return _sized(L.ttrain_lib().g2048_tpolicy_train_workspace(int(n), int(dim_ff), int(n_layers)),
+                  "g2048: the transformer policy's training passes take 1 .. %d boards (16 tokens each; a larger batch is refused, "
+                  "not truncated), a dim_ff that is a multiple of 32 and 1 .. 64 layers (got n = %d, dim_ff = %d, n_layers = %d)",
+                  L.TLEARN_BATCH_MAX, int(n), int(dim_ff), int(n_layers))
 
 
 def tpolicy_forward_train(boards, plain, dim_ff, n_layers, dropout, seed=0, call_index=0, probs=None, value=None, workspace=None):
@@ -677,11 +686,8 @@ def tpolicy_forward_train(boards, plain, dim_ff, n_layers, dropout, seed=0, call
     Returns (probs float32 (n,4), value float32 (n,1))."""
     p = qnet_dropout_p(dropout) or (0.0, 0.0, 0.0, 0.0)
     L.require_device_tensor(boards, torch.uint8, (16,), "boards")
-    L.require_device_tensor(plain, torch.float32, None, "plain")
+    _flat_plain(plain, tpolicy_plain_floats(dim_ff, n_layers))
     n, dev = boards.shape[0], boards.device
-    floats = tpolicy_plain_floats(dim_ff, n_layers)
-    if plain.dim() != 1 or plain.numel() != floats:
-        raise ValueError("g2048: plain must be a flat float32 tensor of %d parameters" % floats)
     probs = _output(probs, n, torch.float32, (4,), "probs", dev)
     value = _output(value, n, torch.float32, (1,), "value", dev)
     if n == 0:
@@ -700,36 +706,16 @@ def tpolicy_dropout_mask(n, layer, site, p, dim_ff=2048, seed=0, call_index=0, f
     Element e = row columns + column of site s of encoder layer `layer` is kept iff rng_draw(rng_keys(seed, 13, call_index),
     ((4 layer + s) << 32) | e, 0) >= floor(p 2^32); a kept element is multiplied by float32(1 / (1 - p)), a dropped one by 0. No
     synchronisation."""
-    n, layer, site, first_row = int(n), int(layer), int(site), int(first_row)
-    if site not in (0, 1, 2, 3):
-        raise ValueError("g2048: site must be 0 .. 3 %s" % (QNET_DROPOUT_SITES,))
-    if not 0 <= layer < 64:
-        raise ValueError("g2048: layer must be 0 .. 63")
-    p = float(p)
-    if not 0.0 <= p < 1.0:
-        raise ValueError("g2048: p must be finite, 0 <= p < 1 (got %r)" % p)
-    if not 0 <= n <= L.TLEARN_BATCH_MAX:
-        raise ValueError("g2048: a dropout mask is of 0 .. %d boards (the gradient pass's limit); got n = %d" % (L.TLEARN_BATCH_MAX, n))
-    height, width = (64 * n, 16) if site == 0 else (16 * n, int(dim_ff) if site == 2 else 64)
-    rows = height - first_row if rows is None else int(rows)
-    if first_row < 0 or rows < 0 or first_row + rows > height:
-        raise ValueError("g2048: rows %d .. %d lie past the site's matrix of %d rows" % (first_row, first_row + rows, height))
-    dev = torch.device(device)
-    out = _output(out, rows, torch.uint8, (width,), "out", dev)
-    if n and rows:
-        L.ttrain_call(out.device, L.ttrain_lib().g2048_tpolicy_dropout_mask, L.u64(seed), L.u64(call_index), layer, site, p, n, int(dim_ff),
-                      first_row, rows, out.data_ptr(), L.stream_ptr(out.device))
-    return out
+    return _encoder_dropout_mask("tpolicy", n, layer, site, p, dim_ff, seed, call_index, first_row, rows, device, out)
 
 
 def tpolicy_step_workspace_bytes(dim_ff, n_layers):
     """Bytes of the workspace tpolicy_adam_step needs (g2048_tpolicy_step_workspace, the step library): one float64 per partial sum
     of the norm and the scalars its second launch prepares."""
-    nb = L.tstep_lib().g2048_tpolicy_step_workspace(int(dim_ff), int(n_layers))
-    if nb == 0:
-        raise ValueError("g2048: tpolicy_adam_step takes a dim_ff that is a multiple of 32 and 1 .. 64 layers (got dim_ff = %d, "
-                         "n_layers = %d)" % (int(dim_ff), int(n_layers)))
-    return nb
+    return _sized(L.tstep_lib().g2048_tpolicy_step_workspace(int(dim_ff), int(n_layers)),
+                  "g2048: tpolicy_adam_step takes a dim_ff that is a multiple of 32 and 1 .. 64 layers (got dim_ff = %d, "
+                  "n_layers = %d)",
+                  int(dim_ff), int(n_layers))
 
 
 def tpolicy_adam_step(plain, grad, exp_avg, exp_avg_sq, dim_ff, n_layers, counters, losses=None, lr=3e-4, betas=(0.9, 0.999), eps=1e-8,
@@ -789,11 +775,10 @@ def qnet_forward(boards, packed, dim_ff, n_layers, precision="f32", q=None, acti
 
 def qnet_batch_workspace_bytes(n, dim_ff):
     """Bytes of the workspace qnet_forward_batch needs for n boards (g2048_qnet_batch_workspace)."""
-    nb = L.lib().g2048_qnet_batch_workspace(int(n), int(dim_ff))
-    if nb == 0:
-        raise ValueError("g2048: qnet_forward_batch takes 1 .. %d boards (they are one sequence; a larger batch is refused, not "
-                         "truncated) and a dim_ff that is a multiple of 32 (got n = %d, dim_ff = %d)" % (L.QNET_BATCH_MAX, int(n), int(dim_ff)))
-    return nb
+    return _sized(L.lib().g2048_qnet_batch_workspace(int(n), int(dim_ff)),
+                  "g2048: qnet_forward_batch takes 1 .. %d boards (they are one sequence; a larger batch is refused, not "
+                  "truncated) and a dim_ff that is a multiple of 32 (got n = %d, dim_ff = %d)",
+                  L.QNET_BATCH_MAX, int(n), int(dim_ff))
 
 
 QNET_DROPOUT_SITES = ("attention", "dropout1", "dropout", "dropout2")       # the order torch's training-mode layer draws in
@@ -817,6 +802,39 @@ def qnet_dropout_p(dropout, name="dropout"):
     return p if any(p) else None
 
 
+# what differs between the two encoder networks' dropout masks: the batch limit, what the message calls it, the site's matrix
+# (rows, columns) of n boards, and the library and entry point that write it
+_MASKS = {"qnet": (L.QNET_BATCH_MAX, "the batch passes' limit", lambda site, n, dim_ff: (8 * n, n) if site == 0 else (n, dim_ff if site == 2 else 128),
+                   L.TRAIN, "g2048_qnet_dropout_mask"),
+          "tpolicy": (L.TLEARN_BATCH_MAX, "the gradient pass's limit",
+                      lambda site, n, dim_ff: (64 * n, 16) if site == 0 else (16 * n, dim_ff if site == 2 else 64),
+                      L.TTRAIN, "g2048_tpolicy_dropout_mask")}
+
+
+def _encoder_dropout_mask(kind, n, layer, site, p, dim_ff, seed, call_index, first_row, rows, device, out):
+    limit, limit_name, site_shape, library, entry = _MASKS[kind]
+    n, layer, site, first_row = int(n), int(layer), int(site), int(first_row)
+    if site not in (0, 1, 2, 3):
+        raise ValueError("g2048: site must be 0 .. 3 %s" % (QNET_DROPOUT_SITES,))
+    if not 0 <= layer < 64:
+        raise ValueError("g2048: layer must be 0 .. 63")
+    p = float(p)
+    if not 0.0 <= p < 1.0:
+        raise ValueError("g2048: p must be finite, 0 <= p < 1 (got %r)" % p)
+    if not 0 <= n <= limit:
+        raise ValueError("g2048: a dropout mask is of 0 .. %d boards (%s); got n = %d" % (limit, limit_name, n))
+    height, width = site_shape(site, n, int(dim_ff))
+    rows = height - first_row if rows is None else int(rows)
+    if first_row < 0 or rows < 0 or first_row + rows > height:
+        raise ValueError("g2048: rows %d .. %d lie past the site's matrix of %d rows" % (first_row, first_row + rows, height))
+    dev = torch.device(device)
+    out = _output(out, rows, torch.uint8, (width,), "out", dev)
+    if n and rows:
+        library.call(out.device, getattr(library.load(), entry), L.u64(seed), L.u64(call_index), layer, site, p, n, int(dim_ff), first_row, rows,
+                     out.data_ptr(), L.stream_ptr(out.device))
+    return out
+
+
 def _p4(p):
     return (C.c_double * 4)(*p)
 
@@ -828,36 +846,15 @@ def qnet_dropout_mask(n, layer, site, p, dim_ff=2048, seed=0, call_index=0, firs
     rows None: down to the matrix's last row. Element e = row columns + column of site s of encoder layer `layer` is kept iff
     rng_draw(rng_keys(seed, 12, call_index), ((4 layer + s) << 32) | e, 0) >= floor(p 2^32); a kept element is multiplied by
     float32(1 / (1 - p)), a dropped one by 0. No synchronisation."""
-    n, layer, site, first_row = int(n), int(layer), int(site), int(first_row)
-    if site not in (0, 1, 2, 3):
-        raise ValueError("g2048: site must be 0 .. 3 %s" % (QNET_DROPOUT_SITES,))
-    if not 0 <= layer < 64:
-        raise ValueError("g2048: layer must be 0 .. 63")
-    p = float(p)
-    if not 0.0 <= p < 1.0:
-        raise ValueError("g2048: p must be finite, 0 <= p < 1 (got %r)" % p)
-    if not 0 <= n <= L.QNET_BATCH_MAX:
-        raise ValueError("g2048: a dropout mask is of 0 .. %d boards (the batch passes' limit); got n = %d" % (L.QNET_BATCH_MAX, n))
-    height, width = (8 * n, n) if site == 0 else (n, int(dim_ff) if site == 2 else 128)
-    rows = height - first_row if rows is None else int(rows)
-    if first_row < 0 or rows < 0 or first_row + rows > height:
-        raise ValueError("g2048: rows %d .. %d lie past the site's matrix of %d rows" % (first_row, first_row + rows, height))
-    dev = torch.device(device)
-    out = _output(out, rows, torch.uint8, (width,), "out", dev)
-    if n and rows:
-        L.train_call(out.device, L.train_lib().g2048_qnet_dropout_mask, L.u64(seed), L.u64(call_index), layer, site, p, n, int(dim_ff),
-                     first_row, rows, out.data_ptr(), L.stream_ptr(out.device))
-    return out
+    return _encoder_dropout_mask("qnet", n, layer, site, p, dim_ff, seed, call_index, first_row, rows, device, out)
 
 
 def qnet_train_workspace_bytes(n, dim_ff, n_layers):
     """Bytes of the workspace qnet_loss_grad needs for n boards with dropout (g2048_qnet_train_workspace)."""
-    nb = L.train_lib().g2048_qnet_train_workspace(int(n), int(dim_ff), int(n_layers))
-    if nb == 0:
-        raise ValueError("g2048: qnet_loss_grad takes 1 .. %d boards (they are one sequence; a larger batch is refused, not "
-                         "truncated), a dim_ff that is a multiple of 32 and 1 .. 64 layers (got n = %d, dim_ff = %d, n_layers = %d)"
-                         % (L.QNET_BATCH_MAX, int(n), int(dim_ff), int(n_layers)))
-    return nb
+    return _sized(L.train_lib().g2048_qnet_train_workspace(int(n), int(dim_ff), int(n_layers)),
+                  "g2048: qnet_loss_grad takes 1 .. %d boards (they are one sequence; a larger batch is refused, not "
+                  "truncated), a dim_ff that is a multiple of 32 and 1 .. 64 layers (got n = %d, dim_ff = %d, n_layers = %d)",
+                  L.QNET_BATCH_MAX, int(n), int(dim_ff), int(n_layers))
 
 
 def qnet_forward_batch(boards, plain, dim_ff, n_layers, q=None, workspace=None, dropout=None, seed=0, call_index=0):
@@ -870,10 +867,8 @@ def qnet_forward_batch(boards, plain, dim_ff, n_layers, q=None, workspace=None, 
     training library's g2048_qnet_forward_batch_dropout; same launches, same workspace. Returns q float32 (n,4)."""
     p = qnet_dropout_p(dropout)
     L.require_device_tensor(boards, torch.uint8, (16,), "boards")
-    L.require_device_tensor(plain, torch.float32, None, "plain")
+    _flat_plain(plain, qnet_plain_floats(dim_ff, n_layers))
     n, dev = boards.shape[0], boards.device
-    if plain.dim() != 1 or plain.numel() != qnet_plain_floats(dim_ff, n_layers):
-        raise ValueError("g2048: plain must be a flat float32 tensor of %d parameters" % qnet_plain_floats(dim_ff, n_layers))
     q = _output(q, n, torch.float32, (4,), "q", dev)
     if n == 0:
         return q
@@ -889,12 +884,10 @@ def qnet_forward_batch(boards, plain, dim_ff, n_layers, q=None, workspace=None, 
 
 def qnet_grad_workspace_bytes(n, dim_ff, n_layers):
     """Bytes of the workspace qnet_loss_grad needs for n boards (g2048_qnet_grad_workspace)."""
-    nb = L.lib().g2048_qnet_grad_workspace(int(n), int(dim_ff), int(n_layers))
-    if nb == 0:
-        raise ValueError("g2048: qnet_loss_grad takes 1 .. %d boards (they are one sequence; a larger batch is refused, not "
-                         "truncated), a dim_ff that is a multiple of 32 and 1 .. 64 layers (got n = %d, dim_ff = %d, n_layers = %d)"
-                         % (L.QNET_BATCH_MAX, int(n), int(dim_ff), int(n_layers)))
-    return nb
+    return _sized(L.lib().g2048_qnet_grad_workspace(int(n), int(dim_ff), int(n_layers)),
+                  "g2048: qnet_loss_grad takes 1 .. %d boards (they are one sequence; a larger batch is refused, not "
+                  "truncated), a dim_ff that is a multiple of 32 and 1 .. 64 layers (got n = %d, dim_ff = %d, n_layers = %d)",
+                  L.QNET_BATCH_MAX, int(n), int(dim_ff), int(n_layers))
 
 
 def qnet_loss_grad(boards, plain, actions, targets, weights, dim_ff, n_layers, grad=None, td=None, loss=None, q=None, workspace=None,
@@ -909,22 +902,16 @@ def qnet_loss_grad(boards, plain, actions, targets, weights, dim_ff, n_layers, g
     g2048_qnet_loss_grad_dropout; the workspace is then qnet_train_workspace_bytes'). No synchronisation. Returns (loss float32 (),
     td float32 (n,), q float32 (n,4), grad float32 (plain.numel(),))."""
     p = qnet_dropout_p(dropout)
+    floats = qnet_plain_floats(dim_ff, n_layers)
     L.require_device_tensor(boards, torch.uint8, (16,), "boards")
-    L.require_device_tensor(plain, torch.float32, None, "plain")
+    _flat_plain(plain, floats)
     L.require_device_tensor(actions, torch.int64, (), "actions")
     L.require_device_tensor(targets, torch.float32, (), "targets")
     L.require_device_tensor(weights, torch.float32, (), "weights")
     n, dev = boards.shape[0], boards.device
-    floats = qnet_plain_floats(dim_ff, n_layers)
-    if plain.dim() != 1 or plain.numel() != floats:
-        raise ValueError("g2048: plain must be a flat float32 tensor of %d parameters" % floats)
     if not (actions.shape[0] == targets.shape[0] == weights.shape[0] == n):
         raise ValueError("g2048: actions, targets and weights must have one entry per board")
-    if grad is None:
-        grad = torch.empty(floats, dtype=torch.float32, device=dev)
-    L.require_device_tensor(grad, torch.float32, None, "grad")
-    if grad.dim() != 1 or grad.numel() != floats:
-        raise ValueError("g2048: grad must be a flat float32 tensor of %d floats" % floats)
+    grad = _grad_output(grad, floats, dev)
     td = _output(td, n, torch.float32, (), "td", dev)
     q = _output(q, n, torch.float32, (4,), "q", dev)
     loss = _float_output(loss, (), "loss", dev)
@@ -945,11 +932,10 @@ def qnet_loss_grad(boards, plain, actions, targets, weights, dim_ff, n_layers, g
 
 def qnet_step_workspace_bytes(dim_ff, n_layers):
     """Bytes of the workspace qnet_adamw_step needs (g2048_qnet_step_workspace): one float64 per partial sum of the norm."""
-    nb = L.lib().g2048_qnet_step_workspace(int(dim_ff), int(n_layers))
-    if nb == 0:
-        raise ValueError("g2048: qnet_adamw_step takes a dim_ff that is a multiple of 32 and 1 .. 64 layers (got dim_ff = %d, "
-                         "n_layers = %d)" % (int(dim_ff), int(n_layers)))
-    return nb
+    return _sized(L.lib().g2048_qnet_step_workspace(int(dim_ff), int(n_layers)),
+                  "g2048: qnet_adamw_step takes a dim_ff that is a multiple of 32 and 1 .. 64 layers (got dim_ff = %d, "
+                  "n_layers = %d)",
+                  int(dim_ff), int(n_layers))
 
 
 def qnet_adamw_step(plain, grad, exp_avg, exp_avg_sq, dim_ff, n_layers, lr, step, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-4,
@@ -1818,11 +1804,10 @@ PPO_RUNNING_OFFSETS = [("bn1.running_mean", 0, 256), ("bn1.running_var", 256, 25
 
 def ppo_train_workspace_bytes(n):
     """Bytes of the workspace the PPO training calls need for n rows (g2048_ppo_train_workspace)."""
-    nb = L.lib().g2048_ppo_train_workspace(int(n))
-    if nb == 0:
-        raise ValueError("g2048: the PPO training pass takes 1 .. %d rows (the batch statistics are the whole batch's; a larger batch "
-                         "is refused, not truncated); got n = %d" % (L.PPO_BATCH_MAX, int(n)))
-    return nb
+    return _sized(L.lib().g2048_ppo_train_workspace(int(n)),
+                  "g2048: the PPO training pass takes 1 .. %d rows (the batch statistics are the whole batch's; a larger batch "
+                  "is refused, not truncated); got n = %d",
+                  L.PPO_BATCH_MAX, int(n))
 
 
 def _ppo_flat(t, floats, name):

@@ -17,7 +17,6 @@ max|got - f64| / max|f64| <= 8 x the float32 run's worst such ratio over the gra
 tests/test_gpu_qnet_grad.py), and that ratio itself must lie in (0, FAIR_F32] (tests/test_qnet_dropout_host.py asserts it for every
 case below, on the CPU). DROPOUT_SEED is the first seed from 0 upwards for which that holds in every case; the host test checks it.
 """
-import contextlib
 import copy
 import functools
 
@@ -25,8 +24,9 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
+import encoder_dropout_ref as E
 import qnet_grad_ref as R
-from ppo_dropout_ref import rng_draws, rng_keys, scale32, scale64, threshold
+from ppo_dropout_ref import scale32  # noqa: F401  (tests/test_qnet_dropout_host.py reads it from here)
 
 DOMAIN = 12
 DROPOUT_SEED = 0                      # the online network's; the target network's is DROPOUT_SEED + 1
@@ -58,70 +58,10 @@ def site_shape(site, n, dim_ff):
     return (8 * n, n) if site == 0 else (n, dim_ff if site == 2 else 128)
 
 
-def keep_mask(seed, call_index, layer, site, p, n, dim_ff, rows=None):
-    """bool (rows, columns): which elements of rows [first, first + count) (rows = (first, count); None: all) of site `site` of
-    encoder layer `layer` the call keeps."""
-    height, width = site_shape(site, n, dim_ff)
-    first, count = (0, height) if rows is None else rows
-    assert 0 <= first and first + count <= height
-    k0, k1 = rng_keys(seed, DOMAIN, call_index)
-    e = np.arange(first * width, (first + count) * width, dtype=np.uint64).astype(np.uint32)
-    return (rng_draws(k0, k1, 4 * layer + site, e) >= np.uint32(threshold(p))).reshape(count, width)
-
-
-@functools.lru_cache(maxsize=512)
-def _whole_mask(seed, call_index, layer, site, p, n, dim_ff):
-    return keep_mask(seed, call_index, layer, site, p, n, dim_ff)
-
-
-def multiplier(seed, call_index, layer, site, p, n, dim_ff, dtype):
-    """keep x scale as a tensor in dtype: the double scale in float64, the project's float32(1 / (1 - p)) in float32."""
-    scale = scale64(p) if dtype == torch.float64 else float(scale32(p))
-    return torch.from_numpy(_whole_mask(seed, call_index, layer, site, float(p), n, dim_ff)).to(dtype) * scale
-
-
-# ------------------------------------------------------------------------------------------- the stock module, masked --
-@contextlib.contextmanager
-def feeding(seed, call_index, p4, n, dim_ff):
-    """While it is open, the training-mode encoder layers draw no random numbers: scaled_dot_product_attention is
-    softmax(q k^T / 4) x the site-0 multipliers, then . v, and dropout is input x the site's multipliers, the sites told by the
-    order of the calls. Yields the call counter (a list of one int)."""
-    calls = [0]
-    real_dropout, real_sdpa = F.dropout, F.scaled_dot_product_attention
-
-    def mult(site, shape, dtype):
-        layer, s = divmod(calls[0], 4)
-        assert s == site, "call %d of the layer is site %d, expected %d" % (calls[0], s, site)
-        calls[0] += 1
-        return multiplier(seed, call_index, layer, site, p4[site], n, dim_ff, dtype).reshape(shape)
-
-    def sdpa(q, k, v, attn_mask=None, dropout_p=0.0, is_causal=False, **kw):
-        assert tuple(q.shape) == (1, 8, n, 16) and attn_mask is None and not is_causal and dropout_p == p4[0], (q.shape, dropout_p)
-        prob = torch.softmax(q @ k.transpose(-1, -2) / 4.0, dim=-1)
-        return (prob * mult(0, prob.shape, q.dtype)) @ v
-
-    def dropout(x, p=0.5, training=True, inplace=False):
-        site = calls[0] % 4
-        assert site != 0 and training and p == p4[site] and tuple(x.shape) == (n, 1, dim_ff if site == 2 else 128), (site, p, x.shape)
-        return x * mult(site, x.shape, x.dtype)
-
-    F.dropout, F.scaled_dot_product_attention = dropout, sdpa
-    try:
-        yield calls
-    finally:
-        F.dropout, F.scaled_dot_product_attention = real_dropout, real_sdpa
-
-
-def training_copy(model, p4, dtype):
-    """A deep copy of the module in dtype and .train() mode whose layers carry the four probabilities."""
-    m = copy.deepcopy(model).to(dtype).train()
-    for lay in m.transformer.layers:
-        lay.self_attn.dropout, lay.dropout1.p, lay.dropout.p, lay.dropout2.p = p4
-    return m
-
-
-def dims(model):
-    return model.transformer.layers[0].linear1.out_features, len(model.transformer.layers)
+ENCODER = E.Encoder(DOMAIN, site_shape, lambda n: (1, 8, n, 16), lambda n, width: (n, 1, width), lambda model: model.transformer.layers)
+# the mask rule and the stock module, masked (encoder_dropout_ref.py)
+keep_mask, multiplier, feeding, training_copy, dims = (ENCODER.keep_mask, ENCODER.multiplier, ENCODER.feeding, ENCODER.training_copy,
+                                                       ENCODER.dims)
 
 
 def masked_loss_grad(model, p4, seed, call_index, codes, actions, targets, weights):
