@@ -17,13 +17,13 @@
 #include "g2048_board.h"
 #include "g2048_host.h"
 #include "g2048_per.h"
+#include "g2048_per_max.h"
 #include "g2048_rng.h"
 
 using namespace g2048;
 
 namespace {
 
-constexpr int kPerBlock = 256;                        // threads of the kernels that walk the buffer
 constexpr int kPerTile = G2048_PER_SCAN_TILE;         // entries per block of the scan: one per thread
 static_assert(kPerTile == kPerBlock, "the scan takes one entry per thread");
 constexpr int kPerSearchBlock = 64;                   // samples per block of the search: a batch of 256 spreads over four CUs
@@ -92,18 +92,7 @@ __device__ __forceinline__ double block_scan(double v, double *s_wave)
 }
 
 // ---- push -----------------------------------------------------------------------------------------------------------------
-// *max_bits (zeroed before the launch) <- the bits of the largest live priority; priorities are positive, so their bits order
-// as they do
-__global__ __launch_bounds__(kPerBlock) void per_max_kernel(const float *__restrict__ priorities, size_t capacity, size_t size, size_t head,
-                                                           uint32_t *max_bits)
-{
-    uint32_t m = 0u;
-    for (size_t i = (size_t)blockIdx.x * kPerBlock + threadIdx.x; i < size; i += (size_t)gridDim.x * kPerBlock)
-        m = max(m, __float_as_uint(priorities[per_slot(head, i, capacity)]));
-    for (int off = 32; off > 0; off >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, off));
-    if ((threadIdx.x & 63u) == 0u && m != 0u) atomicMax(max_bits, m);
-}
-
+// (per_max_kernel, the maximum of the live priorities, and the two stream operations that run it: g2048_per_max.h)
 template <bool REWARD_F64>
 __global__ __launch_bounds__(kPerBlock) void per_push_kernel(uint4 *__restrict__ states, uint4 *__restrict__ next_states, uint8_t *__restrict__ actions,
                                                             float *__restrict__ rewards, uint8_t *__restrict__ dones, float *__restrict__ priorities,
@@ -330,10 +319,8 @@ int g2048_per_push(void *states, void *next_states, uint8_t *actions, float *rew
     hipStream_t s = static_cast<hipStream_t>(stream);
     uint32_t *max_bits = static_cast<uint32_t *>(workspace);
     if (size) {
-        const int rc = check_hip(hipMemsetAsync(max_bits, 0, sizeof(uint32_t), s), "g2048_per_push: hipMemsetAsync");
+        const int rc = per_max_enqueue("g2048_per_push: hipMemsetAsync", priorities, capacity, size, head, max_bits, s);
         if (rc != G2048_OK) return rc;
-        const unsigned blocks = blocks_for(size, kPerBlock);
-        hipLaunchKernelGGL(per_max_kernel, dim3(blocks < 256u ? blocks : 256u), dim3(kPerBlock), 0, s, priorities, capacity, size, head, max_bits);
     }
     with_bool(rewards_f64 != 0u, [&](auto F) {
         hipLaunchKernelGGL((per_push_kernel<decltype(F)::value>), dim3(blocks_for(m, kPerBlock)), dim3(kPerBlock), 0, s, static_cast<uint4 *>(states),

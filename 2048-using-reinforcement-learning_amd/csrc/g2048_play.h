@@ -1,7 +1,7 @@
 // g2048_play.h -- the game-slot core of the kernels that play complete games of a network in one launch (policy_play_kernel,
 // tpolicy_play_kernel, qnet_play_kernel): what a launch's games need, one slot's state, how idle slots take the next games from
 // the ticket counter, and everything that happens to a slot once its action is chosen. Device code, included by those three
-// files and nothing else. The kernels differ in the forward pass before it, in how many slots a wavefront owns, and in where a
+// files (and, for the direction table alone, by g2048_qnet_collect.hip). The kernels differ in the forward pass before it, in how many slots a wavefront owns, and in where a
 // slot's state lives between moves: policy_play_kernel keeps a Game in registers, the other two have none to spare and park it
 // in LDS (PlaySlots), loading and storing it around the move.
 //

@@ -14,8 +14,9 @@ from .policy import DevicePolicy  # noqa: F401
 from .tpolicy import DeviceTransformerPolicy  # noqa: F401
 from .qnet import DeviceQNetwork, dqn_targets, cosine_lr, dqn_epsilon  # noqa: F401
 from .replay_buffer import DeviceReplayBuffer  # noqa: F401
+from .collector import DQNCollector  # noqa: F401
 from .ppo import DevicePPOLearner  # noqa: F401
 
 __all__ = ["ops", "VecGame2048", "BatchedBeamSearch", "evaluate_beam_search", "evaluate_beam_search_sharded", "evaluate_policy", "evaluate_qnet", "save_moveset",
            "save_game_data", "RolloutCollector", "masked_sample", "DevicePolicy", "DeviceTransformerPolicy", "DeviceQNetwork",
-           "DeviceReplayBuffer", "DevicePPOLearner", "dqn_targets", "cosine_lr", "dqn_epsilon"]
+           "DeviceReplayBuffer", "DQNCollector", "DevicePPOLearner", "dqn_targets", "cosine_lr", "dqn_epsilon"]

@@ -1,5 +1,6 @@
 """ctypes binding of the C-ABI in include/g2048.h (csrc/libg2048_hip.so) and of the four libraries beside it (g2048_train.h,
-g2048_tlearn.h, g2048_tstep.h, g2048_ttrain.h): one Library per row of _build.LIBRARIES, each with its own table, error string and version.
+g2048_tlearn.h, g2048_tstep.h, g2048_ttrain.h): one Library per row of _build.LIBRARIES, each with its own table, error string and version;
+and of the extension libg2048_collect_hip.so (g2048_collect.h), the one row of _build.EXTENSIONS, bound by the same Library class.
 
 There is no fallback: if the library is missing or no HIP device is visible, every
 compute call raises. PyTorch is only used for device memory and streams -- tensors
@@ -177,9 +178,18 @@ TTRAIN_SIGNATURES = {
     "g2048_tpolicy_dropout_mask": (_int, [_u64, _u64, _int, _int, C.c_double, _sz, _int, _sz, _sz, _vp, _vp]),
 }
 
+COLLECT_ABI_VERSION = 1
+COLLECT_SIGNATURES = {
+    "g2048_collect_last_error": (C.c_char_p, []),
+    "g2048_collect_abi_version": (_int, []),
+    "g2048_qnet_collect_workspace": (_sz, [_sz]),
+    "g2048_qnet_collect": (_int, [_vp] * 4 + [_int, _int, _u32, _f, _int, _int, _int, _u64, _u64, _u64, _sz, _int, _int] + [_vp] * 6 +
+                           [_sz, _sz, _sz, _vp, _vp, _vp]),
+}
+
 
 class Library:
-    """One shared object of _build.LIBRARIES (row `key`), loaded on first use and as loud as can be: a missing file, a file under
+    """One shared object of _build.LIBRARIES or _build.EXTENSIONS (row `key`), loaded on first use and as loud as can be: a missing file, a file under
     another name than the product's, a missing symbol, another ABI version and a failed call all raise."""
 
     def __init__(self, key, stem, signatures, version, role="", without="", after_load=None):
@@ -195,7 +205,7 @@ class Library:
     def load(self):
         """The loaded library. Raises if it has not been built (python __graft_entry__.py)."""
         if self.handle is None:
-            path, (product, env) = self.path(), _build.LIBRARIES[self.key][:2]
+            path, (product, env) = self.path(), _build.ROWS[self.key][:2]
             if not os.path.exists(path):
                 raise RuntimeError("g2048: %s is missing -- build it with `python __graft_entry__.py` "
                                    "(hipcc --offload-arch=gfx950); there is no CPU fallback%s" % (path, self.without))
@@ -260,6 +270,10 @@ TSTEP = Library("TSTEP_", "g2048_tstep", TSTEP_SIGNATURES, TSTEP_ABI_VERSION, "s
 TTRAIN = Library("TTRAIN_", "g2048_ttrain", TTRAIN_SIGNATURES, TTRAIN_ABI_VERSION, "policy training",
                  " and no training-mode pass of the transformer policy without it")
 LIBRARIES = {"": MAIN, "TRAIN_": TRAIN, "TLEARN_": TLEARN, "TSTEP_": TSTEP, "TTRAIN_": TTRAIN}
+# the second table (_build.EXTENSIONS has the reason for the split): the same class, bound the same way
+COLLECT = Library("COLLECT_", "g2048_collect", COLLECT_SIGNATURES, COLLECT_ABI_VERSION, "collector",
+                  " and no experience collection in one launch without it")
+EXTENSIONS = {"COLLECT_": COLLECT}
 
 # the names the package, the tools and the tests call
 library_path, lib, check, call = MAIN.path, MAIN.load, MAIN.check, MAIN.call
@@ -267,6 +281,7 @@ train_library_path, train_lib, train_call = TRAIN.path, TRAIN.load, TRAIN.call
 tlearn_library_path, tlearn_lib, tlearn_call = TLEARN.path, TLEARN.load, TLEARN.call
 tstep_library_path, tstep_lib, tstep_call = TSTEP.path, TSTEP.load, TSTEP.call
 ttrain_library_path, ttrain_lib, ttrain_call = TTRAIN.path, TTRAIN.load, TTRAIN.call
+collect_library_path, collect_lib, collect_call = COLLECT.path, COLLECT.load, COLLECT.call
 
 
 def stream_ptr(device):

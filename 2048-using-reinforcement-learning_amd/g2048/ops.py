@@ -1775,6 +1775,62 @@ def per_update_priorities(priorities, size, head, indices, td_errors, workspace=
            td_errors.data_ptr(), indices.shape[0], workspace.data_ptr(), L.stream_ptr(dev))
 
 
+# ---- the hybrid agent's experience collection in one launch (include/g2048_collect.h, libg2048_collect_hip.so) ----------------
+def qnet_collect_workspace_bytes(n):
+    return int(L.collect_lib().g2048_qnet_collect_workspace(int(n)))
+
+
+def qnet_collect(boards, scores, moves, packed, dim_ff, n_layers, states, next_states, actions, rewards, dones, priorities, size, head,
+                 steps, precision="f32", epsilon=0.0, beam_width=0, search_depth=30, threshold=64, seed=0x2048, step_index0=0, id_base=0,
+                 max_episode_steps=0, flags=None, workspace=None):
+    """`steps` moves of the n environments (boards uint8 (n,16), scores 32-bit, moves int32: the episodes' move counts, all three
+    updated in place) played by the Q-network in ONE launch (g2048_qnet_collect; train_agent's acting loop, hybrid.py:1098-1127),
+    every transition written into the replay ring as per_push writes a push of steps x n rows. Per step and environment:
+    qnet_forward, qnet_select_actions at `epsilon` (beam_width 0) or qnet_beam_actions at (beam_width, search_depth >= 2,
+    threshold), step() without options, the ring entry, and a fresh board (step(auto_reset=True)'s) when the step ended the game
+    or the episode reached max_episode_steps (0: no cap; the stored done stays 0 then). packed: the blob of qnet_pack for
+    (precision, dim_ff, n_layers). flags: uint8 (steps, n), every step's flags byte. Returns (size, head, flags): the ring's size
+    and head after the call."""
+    _check_play_blob("qnet", packed, precision, dim_ff, n_layers)
+    if precision not in POLICY_PRECISIONS:
+        raise ValueError("g2048: precision must be 'f32' or 'bf16'")
+    epsilon, steps, beam_width = float(epsilon), int(steps), int(beam_width)
+    if not 0.0 <= epsilon <= 1.0:
+        raise ValueError("g2048: epsilon must lie in [0, 1]")
+    if beam_width:
+        _check_beam_settings(beam_width, search_depth, threshold)
+        if int(search_depth) == 1:
+            raise ValueError("g2048: search_depth 1 asks the network about every candidate and is not collected in one launch "
+                             "(DQNCollector.collect(fused=False))")
+    if steps < 1:
+        raise ValueError("g2048: steps must be at least 1")
+    if int(max_episode_steps) < 0:
+        raise ValueError("g2048: max_episode_steps must be 0 (no cap) or positive")
+    capacity = _require_per_buffer(states, next_states, actions, rewards, dones, priorities)
+    _require_games(boards, scores, packed)
+    L.require_device_tensor(moves, torch.int32, None, "moves")
+    n, dev = boards.shape[0], boards.device
+    if scores.shape[0] != n or moves.shape[0] != n:
+        raise ValueError("g2048: scores and moves must have one entry per board")
+    size, head = int(size), int(head)
+    if steps * n > capacity:
+        raise ValueError("g2048: steps x n = %d x %d transitions exceed the buffer's capacity of %d" % (steps, n, capacity))
+    if flags is None:
+        flags = torch.empty((steps, n), dtype=torch.uint8, device=dev)
+    L.require_device_tensor(flags, torch.uint8, None, "flags")
+    if tuple(flags.shape) != (steps, n):
+        raise ValueError("g2048: flags must have shape (steps, n)")
+    workspace = _per_workspace(workspace, qnet_collect_workspace_bytes(n), dev)
+    L.collect_call(dev, L.collect_lib().g2048_qnet_collect, boards.data_ptr(), scores.data_ptr(), moves.data_ptr(), packed.data_ptr(),
+                   int(dim_ff), int(n_layers), POLICY_PRECISIONS[precision], epsilon, beam_width, int(search_depth), int(threshold),
+                   L.u64(seed), L.u64(step_index0), L.u64(id_base), n, steps, int(max_episode_steps), states.data_ptr(),
+                   next_states.data_ptr(), actions.data_ptr(), rewards.data_ptr(), dones.data_ptr(), priorities.data_ptr(), capacity, size,
+                   head, flags.data_ptr(), workspace.data_ptr(), L.stream_ptr(dev))
+    m = steps * n
+    evicted = max(0, size + m - capacity)
+    return min(size + m, capacity), (head + evicted) % capacity, flags
+
+
 PPO_TRUNK_FLOATS, PPO_RUNNING_FLOATS = 46272, 768
 
 

@@ -2,7 +2,7 @@
 """The data side of the hybrid agent's training loop (reference agents/hybrid.py:955-1074) entirely on the GPU.
 
     python examples/dqn_replay.py [--envs 4096] [--steps 200] [--capacity 200000] [--batch 256] [--every 4] [--dim-ff 2048] [--train]
-                                  [--device-step] [--dropout 0.1 | module]
+                                  [--device-step] [--dropout 0.1 | module] [--collector legacy|fused|stepwise] [--collect-steps 16]
 
 A VecGame2048 batch is played by DeviceQNetwork.act(epsilon=...) (DQNAgent.select_action); every step of every env is pushed
 into a g2048.DeviceReplayBuffer (PrioritizedReplayBuffer.push); every --every steps a batch is sampled -- sample(), the float32
@@ -22,6 +22,11 @@ training steps. Still no claim about learning curves.
 --train --dropout P (or --dropout module, the layers' own 0.1): the three forwards of train_step -- both networks' in dqn_targets and
 the one loss_and_grad keeps -- run the encoder layers' four dropout sites live, as the reference's do (it never calls .eval()); the
 online and the target network draw from different seeds. Acting stays eval mode. Without --dropout: eval mode throughout.
+
+--collector fused | stepwise hands the acting side to g2048.DQNCollector (train_agent's loop, :1098-1127: the reference's reset rule
+and its max_steps of 2000): `fused` plays --collect-steps moves of every env and writes their transitions into the ring in ONE kernel
+launch, `stepwise` is the same function made of the older entry points, one env step at a time; the sample + update rounds that
+fall into a chunk follow it. `legacy`, the default, is the loop below (play()) as it always was.
 
 --train --device-step keeps that tail on the device too: attach_params() makes both modules views of their plain buffers,
 online.adamw_step(g2048.cosine_lr(round)) is the clipping, the AdamW update and the re-pack in two launches plus the pack, and
@@ -50,6 +55,8 @@ ap.add_argument("--precision", choices=("f32", "bf16"), default="f32")
 ap.add_argument("--train", action="store_true", help="the full train_step: loss_and_grad, clip, AdamW, cosine schedule, target sync")
 ap.add_argument("--device-step", action="store_true", help="with --train: clipping, AdamW and the target sync on the device (adamw_step, sync_from)")
 ap.add_argument("--dropout", default="0", help="with --train: a probability for the encoder layers' four dropout sites in the training forwards, or 'module'")
+ap.add_argument("--collector", choices=("legacy", "fused", "stepwise"), default="legacy", help="who plays: the loop of this script, or g2048.DQNCollector")
+ap.add_argument("--collect-steps", type=int, default=16, help="with --collector fused | stepwise: env steps per collect call")
 a = ap.parse_args()
 if a.device_step and not a.train:
     sys.exit("--device-step needs --train")
@@ -58,6 +65,8 @@ if dropout != 0 and not a.train:
     sys.exit("--dropout needs --train")
 if a.envs > a.capacity:
     sys.exit("--envs must not exceed --capacity: a push holds one transition per env")
+if a.collector != "legacy" and (a.collect_steps < 1 or a.collect_steps * a.envs > a.capacity):
+    sys.exit("--collect-steps x --envs must lie in 1 .. --capacity: a collect call holds that many transitions")
 
 
 class HybridDQN(nn.Module):             # the reference's layout (agents/hybrid.py:700-727), stock torch, default init
@@ -78,6 +87,7 @@ target = g2048.DeviceQNetwork(HybridDQN(a.dim_ff).to(dev).eval(), dropout=dropou
 actor = online if a.precision == "f32" else g2048.DeviceQNetwork(online.model, precision=a.precision)     # the same module
 env = g2048.VecGame2048(a.envs, device=dev, seed=seed)
 buf = g2048.DeviceReplayBuffer(a.capacity, alpha=0.6, device=dev, seed=seed)
+collector = g2048.DQNCollector(actor, buf, a.envs, seed=seed, device=dev) if a.collector != "legacy" else None
 huber = nn.SmoothL1Loss(reduction="none")
 TARGET_SYNC = 250
 last_norm = None
@@ -141,7 +151,22 @@ def device_step(round_index, loss, td, indices):
     return loss
 
 
+def run_collected(steps, t0):
+    rounds, loss, t = 0, None, t0
+    while t < t0 + steps:
+        k = min(a.collect_steps, t0 + steps - t)
+        collector.collect(k, a.epsilon, fused=a.collector == "fused")
+        for u in range(t, t + k):
+            if len(buf) >= a.batch and (u + 1) % a.every == 0:
+                loss = learn(rounds)
+                rounds += 1
+        t += k
+    return rounds, loss
+
+
 def run(steps, t0):
+    if collector is not None:
+        return run_collected(steps, t0)
     rounds, loss = 0, None
     for t in range(t0, t0 + steps):
         play(t)
