@@ -86,38 +86,7 @@ __global__ __launch_bounds__(kRolloutBlock) void rollout_step_kernel(
     else static_cast<float *>(reward_out)[i] = (float)o.reward;
     flags_out[i] = (uint8_t)o.flags;
     if (mask_next) mask_next[i] = (uint8_t)valid_mask_env(cur);
-    if (obs_next) {
-        const uint32_t kind = (opts >> G2048_ROLLOUT_OBS_SHIFT) & 3u;
-        float v[16];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-#pragma unroll
-            for (int c = 0; c < 4; ++c) v[4 * r + c] = s_obs[(cur.w[r] >> (8 * c)) & 31u];
-        }
-        if (kind == G2048_OBS_F32) {
-            float4 *dst = static_cast<float4 *>(obs_next) + 4 * i;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) dst[r] = make_float4(v[4 * r], v[4 * r + 1], v[4 * r + 2], v[4 * r + 3]);
-        } else {
-            uint32_t h[8];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                uint32_t lo, hi;
-                if (kind == G2048_OBS_BF16) {       // finite non-negative values: round to nearest even by integer add
-                    const uint32_t u0 = __float_as_uint(v[2 * k]), u1 = __float_as_uint(v[2 * k + 1]);
-                    lo = (u0 + 0x7fffu + ((u0 >> 16) & 1u)) >> 16;
-                    hi = (u1 + 0x7fffu + ((u1 >> 16) & 1u)) >> 16;
-                } else {
-                    lo = (uint32_t)__half_as_ushort(__float2half_rn(v[2 * k]));
-                    hi = (uint32_t)__half_as_ushort(__float2half_rn(v[2 * k + 1]));
-                }
-                h[k] = lo | (hi << 16);
-            }
-            uint4 *dst = static_cast<uint4 *>(obs_next) + 2 * i;
-            dst[0] = make_uint4(h[0], h[1], h[2], h[3]);
-            dst[1] = make_uint4(h[4], h[5], h[6], h[7]);
-        }
-    }
+    if (obs_next) store_observation(obs_next, i, cur, (opts >> G2048_ROLLOUT_OBS_SHIFT) & 3u, s_obs);
 }
 
 // ---------------------------------------------------------------- minibatch ---------

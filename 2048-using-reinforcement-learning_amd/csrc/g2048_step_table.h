@@ -39,6 +39,42 @@ struct TenthFromLds {
     __device__ __forceinline__ double crowded(double r, uint32_t empty_after) const { return r + t->crowded[empty_after]; }
 };
 
+// The observation of board `cur` (PPOAgent.normalize_state) as row i of `obs`, whose dtype is `kind` (G2048_OBS_F32 / F16 / BF16):
+// 64 or 32 bytes a board, the values from the LDS copy's obs entries. What rollout_step_kernel and ppo_collect_kernel store; the
+// including file includes <hip/hip_fp16.h> at file scope.
+__device__ __forceinline__ void store_observation(void *__restrict__ obs, size_t i, const Board &cur, uint32_t kind, const float *s_obs)
+{
+    float v[16];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) v[4 * r + c] = s_obs[(cur.w[r] >> (8 * c)) & 31u];
+    }
+    if (kind == G2048_OBS_F32) {
+        float4 *dst = static_cast<float4 *>(obs) + 4 * i;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) dst[r] = make_float4(v[4 * r], v[4 * r + 1], v[4 * r + 2], v[4 * r + 3]);
+    } else {
+        uint32_t h[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            uint32_t lo, hi;
+            if (kind == G2048_OBS_BF16) {       // finite non-negative values: round to nearest even by integer add
+                const uint32_t u0 = __float_as_uint(v[2 * k]), u1 = __float_as_uint(v[2 * k + 1]);
+                lo = (u0 + 0x7fffu + ((u0 >> 16) & 1u)) >> 16;
+                hi = (u1 + 0x7fffu + ((u1 >> 16) & 1u)) >> 16;
+            } else {
+                lo = (uint32_t)__half_as_ushort(__float2half_rn(v[2 * k]));
+                hi = (uint32_t)__half_as_ushort(__float2half_rn(v[2 * k + 1]));
+            }
+            h[k] = lo | (hi << 16);
+        }
+        uint4 *dst = static_cast<uint4 *>(obs) + 2 * i;
+        dst[0] = make_uint4(h[0], h[1], h[2], h[3]);
+        dst[1] = make_uint4(h[4], h[5], h[6], h[7]);
+    }
+}
+
 // The fill in two halves, so that a kernel can put its own loads BETWEEN the table words' load and their LDS write: the write has
 // to wait for the words, and loads issued only after it would start a second memory round trip at the head of every wavefront
 // (the compiler does not move a global load up across the write). Every lane of the wavefront must run both halves.

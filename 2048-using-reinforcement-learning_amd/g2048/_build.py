@@ -1,5 +1,6 @@
 """Builds csrc/libg2048_hip.so, csrc/libg2048_train_hip.so, csrc/libg2048_tlearn_hip.so, csrc/libg2048_tstep_hip.so and
-csrc/libg2048_ttrain_hip.so, and the extension csrc/libg2048_collect_hip.so, for gfx950 with hipcc (cross-compiles without a GPU).
+csrc/libg2048_ttrain_hip.so, and the extensions csrc/libg2048_collect_hip.so and csrc/libg2048_ppo_collect_hip.so, for gfx950 with
+hipcc (cross-compiles without a GPU).
 
     python -m g2048._build [-o LIBRARY] [extra compiler flags ...]           (from the package directory)
     python -m g2048._build --train [-o LIBRARY] [extra compiler flags ...]   (the training library alone)
@@ -7,6 +8,7 @@ csrc/libg2048_ttrain_hip.so, and the extension csrc/libg2048_collect_hip.so, for
     python -m g2048._build --tstep [-o LIBRARY] [extra compiler flags ...]   (the transformer policy's optimiser-step library alone)
     python -m g2048._build --ttrain [-o LIBRARY] [extra compiler flags ...]  (the transformer policy's training-mode library alone)
     python -m g2048._build --collect [-o LIBRARY] [extra compiler flags ...] (the experience collector's library alone)
+    python -m g2048._build --ppo-collect [-o LIBRARY] [extra compiler flags ...]   (the PPO experience collector's library alone)
 
 The libraries are built in-tree so that they travel with the source snapshot; they are
 git-ignored. -ffp-contract=off is REQUIRED: the reward / heuristic kernels follow
@@ -23,7 +25,9 @@ libg2048_ttrain_hip.so (include/g2048_ttrain.h) holds the transformer policy's t
 fifth library for the same reason; its kernels are the learner library's, shared as csrc/g2048_tpolicy_grad_pass.h.
 EXTENSIONS is a second table of the same row shape, and libg2048_collect_hip.so (include/g2048_collect.h: the hybrid agent's
 experience collection in one launch) is its one row. The split says nothing about the library: the tests pin LIBRARIES at five
-rows, so the sixth shared object is counted here, and everything below reads both tables (ROWS).
+rows, so the sixth shared object is counted here, and everything below reads every table (ROWS).
+PPO_EXTENSIONS is a third table of that row shape, and libg2048_ppo_collect_hip.so (include/g2048_ppo_collect.h: the PPO agent's
+experience collection in one launch) is its one row, for the same reason once more: the tests pin EXTENSIONS at that one row.
 """
 import os
 import shutil
@@ -47,7 +51,10 @@ LIBRARIES = {
 EXTENSIONS = {
     "COLLECT_": ("libg2048_collect_hip.so", "G2048_COLLECT_LIB", ["g2048_qnet_collect.hip"], ["g2048_collect.h"]),
 }
-ROWS = {**LIBRARIES, **EXTENSIONS}                    # every shared object of the build, whichever table counts it
+PPO_EXTENSIONS = {
+    "PPO_COLLECT_": ("libg2048_ppo_collect_hip.so", "G2048_PPO_COLLECT_LIB", ["g2048_ppo_collect.hip"], ["g2048_ppo_collect.h"]),
+}
+ROWS = {**LIBRARIES, **EXTENSIONS, **PPO_EXTENSIONS}  # every shared object of the build, whichever table counts it
 PUBLIC_HEADERS = [os.path.join(INCLUDE, h) for row in ROWS.values() for h in row[3]]
 # LIB, SOURCES, TRAIN_LIB, TRAIN_SOURCES, ...: what the loader, the tools and the tests read; needs_build() and build() read the
 # paths from here too, so a path that is replaced at run time is the one they look at
@@ -103,9 +110,9 @@ def build(force=False, verbose=False, lib=None, extra_flags=()):
     return path_of("")
 
 
-if __name__ == "__main__":          # [--train | --tlearn | --tstep | --ttrain | --collect] [-o LIBRARY] [extra compiler flags ...]
+if __name__ == "__main__":          # [--train | --tlearn | --tstep | --ttrain | --collect | --ppo-collect] [-o LIBRARY] [extra compiler flags ...]
     out, args = None, sys.argv[1:]
-    key = next((k for k in ROWS if k and args[:1] == ["--" + k[:-1].lower()]), None)
+    key = next((k for k in ROWS if k and args[:1] == ["--" + k[:-1].lower().replace("_", "-")]), None)
     if key:
         args = args[1:]
     if args[:1] == ["-o"]:

@@ -1,6 +1,7 @@
 """ctypes binding of the C-ABI in include/g2048.h (csrc/libg2048_hip.so) and of the four libraries beside it (g2048_train.h,
 g2048_tlearn.h, g2048_tstep.h, g2048_ttrain.h): one Library per row of _build.LIBRARIES, each with its own table, error string and version;
-and of the extension libg2048_collect_hip.so (g2048_collect.h), the one row of _build.EXTENSIONS, bound by the same Library class.
+and of the extensions libg2048_collect_hip.so (g2048_collect.h), the one row of _build.EXTENSIONS, and libg2048_ppo_collect_hip.so
+(g2048_ppo_collect.h), the one row of _build.PPO_EXTENSIONS, bound by the same Library class.
 
 There is no fallback: if the library is missing or no HIP device is visible, every
 compute call raises. PyTorch is only used for device memory and streams -- tensors
@@ -187,9 +188,17 @@ COLLECT_SIGNATURES = {
                            [_sz, _sz, _sz, _vp, _vp, _vp]),
 }
 
+PPO_COLLECT_ABI_VERSION = 1
+PPO_COLLECT_PRECISION_SHIFT = 8
+PPO_COLLECT_SIGNATURES = {
+    "g2048_ppo_collect_last_error": (C.c_char_p, []),
+    "g2048_ppo_collect_abi_version": (_int, []),
+    "g2048_ppo_collect": (_int, [_vp] * 13 + [_u64, _u64, _vp, _u64, _sz, _int, _u32, _vp]),
+}
+
 
 class Library:
-    """One shared object of _build.LIBRARIES or _build.EXTENSIONS (row `key`), loaded on first use and as loud as can be: a missing file, a file under
+    """One shared object of _build.ROWS (row `key`, of whichever table), loaded on first use and as loud as can be: a missing file, a file under
     another name than the product's, a missing symbol, another ABI version and a failed call all raise."""
 
     def __init__(self, key, stem, signatures, version, role="", without="", after_load=None):
@@ -274,6 +283,10 @@ LIBRARIES = {"": MAIN, "TRAIN_": TRAIN, "TLEARN_": TLEARN, "TSTEP_": TSTEP, "TTR
 COLLECT = Library("COLLECT_", "g2048_collect", COLLECT_SIGNATURES, COLLECT_ABI_VERSION, "collector",
                   " and no experience collection in one launch without it")
 EXTENSIONS = {"COLLECT_": COLLECT}
+# the third table (_build.PPO_EXTENSIONS), for the same reason
+PPO_COLLECT = Library("PPO_COLLECT_", "g2048_ppo_collect", PPO_COLLECT_SIGNATURES, PPO_COLLECT_ABI_VERSION, "PPO collector",
+                      " and no PPO experience collection in one launch without it")
+PPO_EXTENSIONS = {"PPO_COLLECT_": PPO_COLLECT}
 
 # the names the package, the tools and the tests call
 library_path, lib, check, call = MAIN.path, MAIN.load, MAIN.check, MAIN.call
@@ -282,6 +295,7 @@ tlearn_library_path, tlearn_lib, tlearn_call = TLEARN.path, TLEARN.load, TLEARN.
 tstep_library_path, tstep_lib, tstep_call = TSTEP.path, TSTEP.load, TSTEP.call
 ttrain_library_path, ttrain_lib, ttrain_call = TTRAIN.path, TTRAIN.load, TTRAIN.call
 collect_library_path, collect_lib, collect_call = COLLECT.path, COLLECT.load, COLLECT.call
+ppo_collect_library_path, ppo_collect_lib, ppo_collect_call = PPO_COLLECT.path, PPO_COLLECT.load, PPO_COLLECT.call
 
 
 def stream_ptr(device):

@@ -8,6 +8,7 @@ mapping float32 (N, 16) observations to action probabilities (N, 4) -- or (probs
 reference's `TransformerModel` (models/transformer.py) -- and stays stock PyTorch-ROCm: it is the consumer; or a
 `g2048.DevicePolicy` (takes_boards = True), the reference's MLP actor / critic as one HIP launch on the boards; or a
 `g2048.DeviceTransformerPolicy` (takes_boards = True), that `TransformerModel` as one HIP launch on the boards.
+With a `g2048.DevicePolicy`, sampler="collect" plays the whole collect -- forward, sampling and env step of every step -- in ONE launch.
 """
 import warnings
 
@@ -15,6 +16,7 @@ import torch
 
 from . import _lib as L
 from . import ops
+from .policy import DevicePolicy
 from .vec import VecGame2048
 
 
@@ -43,7 +45,13 @@ class RolloutCollector:
     needs no host-side arguments. shaping=True also produces PPOAgent.remember's shaped reward (agents/ppo_agent.py:234-269)
     for the trajectory in (step, env) order, stateful terms included (`ops.remember_shaping`).
 
-    sampler="torch" keeps the unfused reference-style path (torch masked_sample + one launch per piece)."""
+    sampler="torch" keeps the unfused reference-style path (torch masked_sample + one launch per piece).
+
+    sampler="collect" (a `g2048.DevicePolicy` only) runs the T steps of a collect() as ONE `g2048_ppo_collect` launch: the actor's
+    (and critic's) forward, the sampling and the env step of every step inside one kernel, the boards in registers between the
+    steps. It fills the same buffers with the same bits as sampler="fused" with that policy, rows 0 of obs / masks included, so it
+    takes no graph and no priming launch; the step index is the device counter, so a collect() captured in a graph of the caller's
+    replays as the next collect. The sampler is fixed for the collector's life. Where each of the two is the faster: DESIGN.md."""
 
     def __init__(self, n_envs, n_steps, policy, device="cuda", seed=0x2048, id_base=0, shaping=False,
                  generator=None, sampler="fused", obs_dtype=torch.float32, use_graph=True, seen_capacity_log2=20,
@@ -53,12 +61,15 @@ class RolloutCollector:
         self.policy = policy
         self.shaping = bool(shaping)
         self.generator = generator
-        if sampler not in ("fused", "torch"):
-            raise ValueError("sampler must be 'fused' (g2048_rollout_step, counter RNG) or 'torch' (masked_sample)")
-        if shaping and sampler != "fused":
-            raise ValueError("shaping=True needs sampler='fused' (the fused step records what remember() consumes)")
-        if minibatches and sampler != "fused":
-            raise ValueError("minibatches=True needs sampler='fused' (the fused step records the next states sample() gathers)")
+        if sampler not in ("fused", "torch", "collect"):
+            raise ValueError("sampler must be 'fused' (g2048_rollout_step, counter RNG), 'torch' (masked_sample) or 'collect' "
+                             "(g2048_ppo_collect: the whole collect in one launch)")
+        if sampler == "collect" and not isinstance(policy, DevicePolicy):
+            raise ValueError("sampler='collect' needs a g2048.DevicePolicy (the forward pass runs inside the collecting kernel)")
+        if shaping and sampler == "torch":
+            raise ValueError("shaping=True needs sampler='fused' or 'collect' (they record what remember() consumes)")
+        if minibatches and sampler == "torch":
+            raise ValueError("minibatches=True needs sampler='fused' or 'collect' (they record the next states sample() gathers)")
         self.minibatches = bool(minibatches) or self.shaping     # sample() needs the next states before auto-reset, as shaping does
         self._samples = 0           # sample() calls so far (RNG index of the minibatch permutation)
         self._seed = int(seed)
@@ -91,7 +102,8 @@ class RolloutCollector:
         self.env_steps = 0
         self.use_graph = bool(use_graph) and sampler == "fused"
         self._graph = None
-        self._counter = torch.zeros(1, dtype=torch.int64, device=d)     # device copy of env.t at the start of a collect
+        # device copy of env.t at the start of a collect: the graph's step index, and sampler="collect"'s in every collect
+        self._counter = torch.zeros(1, dtype=torch.int64, device=d)
         self._primed = False
 
     # -- one env step, fused (1 g2048 launch) or reference-style (obs / mask / sample / step launches) --------------------
@@ -173,9 +185,21 @@ class RolloutCollector:
         if graph is None:
             self.use_graph = False
 
-    @torch.no_grad()
-    def collect(self):
-        """T steps of every env. Returns the buffers (views, overwritten by the next collect)."""
+    def _collect_one_launch(self):
+        """The T steps as one g2048_ppo_collect launch; the blobs by the batch size, as DevicePolicy.__call__ takes them (the
+        reference's BatchNorm rule for a batch of one row). Step index = the device counter, advanced behind the launch."""
+        env, pol, n = self.env, self.policy, self.n
+        ops.ppo_collect(env.boards, env.scores, pol.actor.blob(n), pol.critic.blob(n) if pol.critic is not None else None, self.T,
+                        pol.precision, env.seed, 0, env.id_base, actions=self.actions, prob=self.logp,
+                        reward=self.rewards64 if self.shaping else self.rewards, flags=self.flags,
+                        value=self.values if pol.critic is not None else None, obs=self._obs, mask=self._masks,
+                        next_boards=self.next_boards, state_maxcode=self.state_maxcode, step_counter=self._counter)
+        self._counter.add_(self.T)
+        env.t += self.T
+        torch.log_(self.logp)                   # the kernel stores the probability; the reference keeps its log
+
+    def _collect_stepwise(self):
+        """The T steps one by one (sampler "fused": replayed from the graph where there is one; sampler "torch")."""
         env = self.env
         if not self._primed:
             self._prime()
@@ -199,6 +223,14 @@ class RolloutCollector:
                 env.t = base
             env.t += self.T
             torch.log_(self.logp)               # the kernel stores the probability; the reference keeps its log
+
+    @torch.no_grad()
+    def collect(self):
+        """T steps of every env. Returns the buffers (views, overwritten by the next collect)."""
+        if self.sampler == "collect":           # rows 0 of obs / masks come from the kernel
+            self._collect_one_launch()
+        else:
+            self._collect_stepwise()
         if self.shaping:
             self.rewards.copy_(self.rewards64)
             T, n = self.T, self.n

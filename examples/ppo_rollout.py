@@ -2,7 +2,7 @@
 """Collect a PPO rollout (BASELINE config 4: 65,536 envs x 128 steps) entirely on the GPU.
 
     python examples/ppo_rollout.py [--envs 65536] [--steps 128] [--policy torch|device-f32|device-bf16|transformer|transformer-bf16]
-                                   [--learner torch|device] [--optimizer torch|device] [--dropout P]
+                                   [--learner torch|device] [--optimizer torch|device] [--dropout P] [--sampler fused|collect]
 
 The policy is any torch module mapping float32 (N,16) observations to action probabilities (N,4) -- or
 (probs, value); here a small MLP. Everything between the policy's outputs and its next inputs (masked sampling,
@@ -21,7 +21,10 @@ torch.optim.Adam run on views of its buffers. --optimizer device (with --learner
 call: the NaN check on the loss, the clipping and both Adam steps are two more launches an epoch, and nothing is read on the host
 until the loss is printed. --dropout P (with --learner device; the reference's networks have 0.2) trains with the reference's live
 dropout on the device, the masks drawn from the learner's counter RNG; the default 0 leaves the Dropout layers out, and the torch
-learner keeps its own."""
+learner keeps its own.
+--sampler collect (with --policy device-f32 / device-bf16) plays the whole collect -- forward, sampling and env step of every step --
+as ONE launch (g2048_ppo_collect) instead of two launches a step replayed from a graph; the trajectory is the same bits.
+DESIGN.md "PPO collect in one launch" says where each is the faster."""
 import argparse
 import os
 import sys
@@ -45,7 +48,11 @@ ap.add_argument("--optimizer", choices=("torch", "device"), default="torch",
                 help="with --learner device: stock clip_grad_norm_ + Adam on the views, or the learner's own update()")
 ap.add_argument("--dropout", type=float, default=0.0,
                 help="with --learner device: the dropout probability of the training-mode forwards (the reference's networks: 0.2)")
+ap.add_argument("--sampler", choices=("fused", "collect"), default="fused",
+                help="collect (with --policy device-f32 / device-bf16): the whole collect in one launch")
 a = ap.parse_args()
+if a.sampler == "collect" and not a.policy.startswith("device-"):
+    ap.error("--sampler collect runs the MLP's forward inside the collecting kernel; use --policy device-f32 or device-bf16")
 if a.optimizer == "device" and a.learner != "device":
     ap.error("--optimizer device needs --learner device")
 if a.dropout and a.learner != "device":
@@ -119,7 +126,7 @@ elif a.policy != "torch" and a.learner == "device":
 elif a.policy != "torch":     # the same modules, 16-256-128-64-{4|1}: actor = body + pi, critic = body + v
     policy = g2048.DevicePolicy(nn.Sequential(net.body, net.pi).eval(), nn.Sequential(net.body, net.v).eval(),
                                 precision=a.policy[len("device-"):])
-rc = g2048.RolloutCollector(a.envs, a.steps, policy, seed=1, shaping=True)
+rc = g2048.RolloutCollector(a.envs, a.steps, policy, seed=1, shaping=True, sampler=a.sampler)
 rc.collect()
 torch.cuda.synchronize(); t0 = time.perf_counter()
 traj = rc.collect()
