@@ -1,7 +1,8 @@
 // g2048_tpolicy_layout.h -- the transformer policy's shapes and its PLAIN f32 parameter layout (g2048_tpolicy_pack's input;
 // include/g2048.h), written down once for the three files that read it: g2048_tpolicy.hip (pack, forward, complete games),
 // g2048_tpolicy_grad.hip (the loss and gradient pass, libg2048_tlearn_hip.so) and g2048_tpolicy_step.hip (clipping and Adam,
-// libg2048_tstep_hip.so). Constants only, included by those three files and nothing else; per translation unit.
+// libg2048_tstep_hip.so), and for g2048_tpolicy_forward.h, through which g2048_tpolicy_collect.hip reads it too. Constants only;
+// per translation unit.
 #pragma once
 
 namespace {

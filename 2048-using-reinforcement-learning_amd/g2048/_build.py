@@ -1,6 +1,6 @@
 """Builds csrc/libg2048_hip.so, csrc/libg2048_train_hip.so, csrc/libg2048_tlearn_hip.so, csrc/libg2048_tstep_hip.so and
-csrc/libg2048_ttrain_hip.so, and the extensions csrc/libg2048_collect_hip.so and csrc/libg2048_ppo_collect_hip.so, for gfx950 with
-hipcc (cross-compiles without a GPU).
+csrc/libg2048_ttrain_hip.so, and the extensions csrc/libg2048_collect_hip.so, csrc/libg2048_ppo_collect_hip.so and
+csrc/libg2048_tpolicy_collect_hip.so, for gfx950 with hipcc (cross-compiles without a GPU).
 
     python -m g2048._build [-o LIBRARY] [extra compiler flags ...]           (from the package directory)
     python -m g2048._build --train [-o LIBRARY] [extra compiler flags ...]   (the training library alone)
@@ -9,6 +9,7 @@ hipcc (cross-compiles without a GPU).
     python -m g2048._build --ttrain [-o LIBRARY] [extra compiler flags ...]  (the transformer policy's training-mode library alone)
     python -m g2048._build --collect [-o LIBRARY] [extra compiler flags ...] (the experience collector's library alone)
     python -m g2048._build --ppo-collect [-o LIBRARY] [extra compiler flags ...]   (the PPO experience collector's library alone)
+    python -m g2048._build --tpolicy-collect [-o LIBRARY] [extra compiler flags ...]   (the transformer policy's collector alone)
 
 The libraries are built in-tree so that they travel with the source snapshot; they are
 git-ignored. -ffp-contract=off is REQUIRED: the reward / heuristic kernels follow
@@ -25,9 +26,13 @@ libg2048_ttrain_hip.so (include/g2048_ttrain.h) holds the transformer policy's t
 fifth library for the same reason; its kernels are the learner library's, shared as csrc/g2048_tpolicy_grad_pass.h.
 EXTENSIONS is a second table of the same row shape, and libg2048_collect_hip.so (include/g2048_collect.h: the hybrid agent's
 experience collection in one launch) is its one row. The split says nothing about the library: the tests pin LIBRARIES at five
-rows, so the sixth shared object is counted here, and everything below reads every table (ROWS).
+rows, so the sixth shared object is counted here.
 PPO_EXTENSIONS is a third table of that row shape, and libg2048_ppo_collect_hip.so (include/g2048_ppo_collect.h: the PPO agent's
 experience collection in one launch) is its one row, for the same reason once more: the tests pin EXTENSIONS at that one row.
+EXTRA_ROWS is the fourth and LAST table of that row shape: the tests pin ROWS, the union of the three above, at seven keys, and
+nothing pins this one's size, so the next library is one more row here and not a fifth table. Its first row is
+libg2048_tpolicy_collect_hip.so (include/g2048_tpolicy_collect.h: the transformer policy's experience collection in one launch).
+Everything below reads ALL_ROWS, every table.
 """
 import os
 import shutil
@@ -54,11 +59,16 @@ EXTENSIONS = {
 PPO_EXTENSIONS = {
     "PPO_COLLECT_": ("libg2048_ppo_collect_hip.so", "G2048_PPO_COLLECT_LIB", ["g2048_ppo_collect.hip"], ["g2048_ppo_collect.h"]),
 }
-ROWS = {**LIBRARIES, **EXTENSIONS, **PPO_EXTENSIONS}  # every shared object of the build, whichever table counts it
-PUBLIC_HEADERS = [os.path.join(INCLUDE, h) for row in ROWS.values() for h in row[3]]
+ROWS = {**LIBRARIES, **EXTENSIONS, **PPO_EXTENSIONS}  # the seven shared objects the older tests count, whichever table counts them
+EXTRA_ROWS = {
+    "TPOLICY_COLLECT_": ("libg2048_tpolicy_collect_hip.so", "G2048_TPOLICY_COLLECT_LIB", ["g2048_tpolicy_collect.hip"],
+                         ["g2048_tpolicy_collect.h"]),
+}
+ALL_ROWS = {**ROWS, **EXTRA_ROWS}  # every shared object of the build
+PUBLIC_HEADERS = [os.path.join(INCLUDE, h) for row in ALL_ROWS.values() for h in row[3]]
 # LIB, SOURCES, TRAIN_LIB, TRAIN_SOURCES, ...: what the loader, the tools and the tests read; needs_build() and build() read the
 # paths from here too, so a path that is replaced at run time is the one they look at
-for _key, (_file, _env, _sources, _) in ROWS.items():
+for _key, (_file, _env, _sources, _) in ALL_ROWS.items():
     globals()[_key + "LIB"] = os.environ.get(_env) or os.path.join(CSRC, _file)
     globals()[_key + "SOURCES"] = _sources
 # -fvisibility=hidden: the export table is exactly what the two headers declare with G2048_API (tests/test_abi_and_host.py)
@@ -84,14 +94,14 @@ def _stale(lib):
 
 
 def needs_build():
-    return any(_stale(path_of(key)) for key in ROWS)
+    return any(_stale(path_of(key)) for key in ALL_ROWS)
 
 
 def build_one(key, lib=None, extra_flags=(), verbose=False):
     """The library of row `key` alone, always made: the product's, or an A/B build at `lib` (loaded through the row's variable)."""
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     out = lib or path_of(key)
-    srcs = [os.path.join(CSRC, f) for f in ROWS[key][2] if os.path.exists(os.path.join(CSRC, f))]
+    srcs = [os.path.join(CSRC, f) for f in ALL_ROWS[key][2] if os.path.exists(os.path.join(CSRC, f))]
     cmd = [hipcc] + FLAGS + list(extra_flags) + ["-o", out] + srcs
     if verbose:
         print(" ".join(cmd))
@@ -104,15 +114,15 @@ def build(force=False, verbose=False, lib=None, extra_flags=()):
     the product's (tools/build_ab.sh); such a build is always made, and the other libraries are left alone."""
     if lib is not None:
         return build_one("", lib, extra_flags, verbose)
-    for key in ROWS:
+    for key in ALL_ROWS:
         if force or _stale(path_of(key)):
             build_one(key, None, extra_flags, verbose)
     return path_of("")
 
 
-if __name__ == "__main__":          # [--train | --tlearn | --tstep | --ttrain | --collect | --ppo-collect] [-o LIBRARY] [extra compiler flags ...]
+if __name__ == "__main__":          # [--train | --tlearn | --tstep | --ttrain | --collect | --ppo-collect | --tpolicy-collect] [-o LIBRARY] [extra compiler flags ...]
     out, args = None, sys.argv[1:]
-    key = next((k for k in ROWS if k and args[:1] == ["--" + k[:-1].lower().replace("_", "-")]), None)
+    key = next((k for k in ALL_ROWS if k and args[:1] == ["--" + k[:-1].lower().replace("_", "-")]), None)
     if key:
         args = args[1:]
     if args[:1] == ["-o"]:

@@ -1,7 +1,8 @@
 """ctypes binding of the C-ABI in include/g2048.h (csrc/libg2048_hip.so) and of the four libraries beside it (g2048_train.h,
 g2048_tlearn.h, g2048_tstep.h, g2048_ttrain.h): one Library per row of _build.LIBRARIES, each with its own table, error string and version;
 and of the extensions libg2048_collect_hip.so (g2048_collect.h), the one row of _build.EXTENSIONS, and libg2048_ppo_collect_hip.so
-(g2048_ppo_collect.h), the one row of _build.PPO_EXTENSIONS, bound by the same Library class.
+(g2048_ppo_collect.h), the one row of _build.PPO_EXTENSIONS, bound by the same Library class; and of the rows of _build.EXTRA_ROWS, the
+open-ended fourth table: libg2048_tpolicy_collect_hip.so (g2048_tpolicy_collect.h).
 
 There is no fallback: if the library is missing or no HIP device is visible, every
 compute call raises. PyTorch is only used for device memory and streams -- tensors
@@ -196,9 +197,17 @@ PPO_COLLECT_SIGNATURES = {
     "g2048_ppo_collect": (_int, [_vp] * 13 + [_u64, _u64, _vp, _u64, _sz, _int, _u32, _vp]),
 }
 
+TPOLICY_COLLECT_ABI_VERSION = 1
+TPOLICY_COLLECT_PRECISION_SHIFT = 8
+TPOLICY_COLLECT_SIGNATURES = {
+    "g2048_tpolicy_collect_last_error": (C.c_char_p, []),
+    "g2048_tpolicy_collect_abi_version": (_int, []),
+    "g2048_tpolicy_collect": (_int, [_vp] * 3 + [_int, _int] + [_vp] * 9 + [_u64, _u64, _vp, _u64, _sz, _int, _u32, _vp]),
+}
+
 
 class Library:
-    """One shared object of _build.ROWS (row `key`, of whichever table), loaded on first use and as loud as can be: a missing file, a file under
+    """One shared object of _build.ALL_ROWS (row `key`, of whichever table), loaded on first use and as loud as can be: a missing file, a file under
     another name than the product's, a missing symbol, another ABI version and a failed call all raise."""
 
     def __init__(self, key, stem, signatures, version, role="", without="", after_load=None):
@@ -214,7 +223,7 @@ class Library:
     def load(self):
         """The loaded library. Raises if it has not been built (python __graft_entry__.py)."""
         if self.handle is None:
-            path, (product, env) = self.path(), _build.ROWS[self.key][:2]
+            path, (product, env) = self.path(), _build.ALL_ROWS[self.key][:2]
             if not os.path.exists(path):
                 raise RuntimeError("g2048: %s is missing -- build it with `python __graft_entry__.py` "
                                    "(hipcc --offload-arch=gfx950); there is no CPU fallback%s" % (path, self.without))
@@ -287,6 +296,10 @@ EXTENSIONS = {"COLLECT_": COLLECT}
 PPO_COLLECT = Library("PPO_COLLECT_", "g2048_ppo_collect", PPO_COLLECT_SIGNATURES, PPO_COLLECT_ABI_VERSION, "PPO collector",
                       " and no PPO experience collection in one launch without it")
 PPO_EXTENSIONS = {"PPO_COLLECT_": PPO_COLLECT}
+# the fourth table (_build.EXTRA_ROWS): no test pins its size, so the next library is one more row here
+TPOLICY_COLLECT = Library("TPOLICY_COLLECT_", "g2048_tpolicy_collect", TPOLICY_COLLECT_SIGNATURES, TPOLICY_COLLECT_ABI_VERSION,
+                          "transformer policy collector", " and no experience collection of the transformer policy in one launch without it")
+EXTRA_ROWS = {"TPOLICY_COLLECT_": TPOLICY_COLLECT}
 
 # the names the package, the tools and the tests call
 library_path, lib, check, call = MAIN.path, MAIN.load, MAIN.check, MAIN.call
@@ -296,6 +309,7 @@ tstep_library_path, tstep_lib, tstep_call = TSTEP.path, TSTEP.load, TSTEP.call
 ttrain_library_path, ttrain_lib, ttrain_call = TTRAIN.path, TTRAIN.load, TTRAIN.call
 collect_library_path, collect_lib, collect_call = COLLECT.path, COLLECT.load, COLLECT.call
 ppo_collect_library_path, ppo_collect_lib, ppo_collect_call = PPO_COLLECT.path, PPO_COLLECT.load, PPO_COLLECT.call
+tpolicy_collect_library_path, tpolicy_collect_lib, tpolicy_collect_call = TPOLICY_COLLECT.path, TPOLICY_COLLECT.load, TPOLICY_COLLECT.call
 
 
 def stream_ptr(device):

@@ -1898,6 +1898,67 @@ def ppo_collect(boards, scores, actor_packed, critic_packed=None, steps=1, preci
     return actions, prob, reward, flags, value
 
 
+# ---- the transformer policy's experience collection in one launch (include/g2048_tpolicy_collect.h, libg2048_tpolicy_collect_hip.so)
+def tpolicy_collect(boards, scores, packed, dim_ff, n_layers, steps=1, precision="f32", seed=0x2048, step_index0=0, id_base=0, *,
+                    actions=None, prob=None, reward=None, flags=None, value=None, obs=None, mask=None, next_boards=None,
+                    state_maxcode=None, step_counter=None, want_value=True):
+    """`steps` moves of the n environments (boards uint8 (n,16) and scores 32-bit, both updated in place) played by the transformer
+    policy in ONE launch (g2048_tpolicy_collect). Per step t and environment: tpolicy_forward of the board it holds with `packed`
+    (the blob of tpolicy_pack for dim_ff, n_layers and `precision`), then rollout_step(auto_reset=True) without a mask input, at
+    step index step_index0 (+ step_counter, an int64 device tensor read inside the kernel) + t. actions, prob (the probability,
+    not its log), reward (float32 or float64), flags and value are (steps, n), allocated when None; with want_value=False and no
+    value tensor the values are not written and None is returned in their place. The optional outputs are written only when
+    given: obs (steps + 1, n, 16) float32 / float16 / bfloat16 and mask uint8 (steps + 1, n), whose row t is the observation and
+    the env valid-move mask of the board step t acts in (row `steps`: the board the call ends on); next_boards uint8 (steps, n,
+    16), the boards before any reset; state_maxcode uint8 (steps, n).
+    Returns (actions, prob, reward, flags, value)."""
+    if precision not in POLICY_PRECISIONS:
+        raise ValueError("g2048: precision must be 'f32' or 'bf16'")
+    steps = int(steps)
+    if steps < 1:
+        raise ValueError("g2048: steps must be at least 1")
+    L.require_device_tensor(boards, torch.uint8, (16,), "boards")
+    _require_scores(scores)
+    n, dev = boards.shape[0], boards.device
+    if scores.shape[0] != n:
+        raise ValueError("g2048: scores must have one entry per board")
+    _check_blob("tpolicy", packed, precision, dim_ff, n_layers)
+
+    def rows(t, dtype, name, tail=(), extra=0, optional=False):
+        shape = (steps + extra, n) + tail
+        if t is None:
+            return None if optional else torch.empty(shape, dtype=dtype, device=dev)
+        L.require_device_tensor(t, dtype, None, name)
+        if tuple(t.shape) != shape:
+            raise ValueError("g2048: %s must have shape %s (got %s)" % (name, shape, tuple(t.shape)))
+        return t
+
+    actions = rows(actions, torch.uint8, "actions")
+    prob = rows(prob, torch.float32, "prob")
+    if reward is not None and reward.dtype not in (torch.float32, torch.float64):
+        raise TypeError("g2048: reward must be float32 or float64")
+    reward = rows(reward, torch.float32 if reward is None else reward.dtype, "reward")
+    flags = rows(flags, torch.uint8, "flags")
+    value = rows(value, torch.float32, "value", optional=not want_value)
+    if obs is not None and obs.dtype not in _OBS_KIND:
+        raise TypeError("g2048: obs must be float32, float16 or bfloat16")
+    obs = rows(obs, None if obs is None else obs.dtype, "obs", (16,), 1, optional=True)
+    mask = rows(mask, torch.uint8, "mask", (), 1, optional=True)
+    next_boards = rows(next_boards, torch.uint8, "next_boards", (16,), optional=True)
+    state_maxcode = rows(state_maxcode, torch.uint8, "state_maxcode", optional=True)
+    if step_counter is not None:
+        L.require_device_tensor(step_counter, torch.int64, None, "step_counter")
+    opts = (L.STEP_REWARD_F64 if reward.dtype == torch.float64 else 0) | L.STEP_AUTO_RESET
+    opts |= (_OBS_KIND[obs.dtype] << L.ROLLOUT_OBS_SHIFT) if obs is not None else 0
+    opts |= POLICY_PRECISIONS[precision] << L.TPOLICY_COLLECT_PRECISION_SHIFT
+    ptr = lambda t: t.data_ptr() if t is not None else None      # noqa: E731
+    L.tpolicy_collect_call(dev, L.tpolicy_collect_lib().g2048_tpolicy_collect, boards.data_ptr(), scores.data_ptr(), packed.data_ptr(),
+                           int(dim_ff), int(n_layers), actions.data_ptr(), prob.data_ptr(), reward.data_ptr(), flags.data_ptr(), ptr(value),
+                           ptr(obs), ptr(mask), ptr(next_boards), ptr(state_maxcode), L.u64(seed), L.u64(step_index0), ptr(step_counter),
+                           L.u64(id_base), n, steps, opts, L.stream_ptr(dev))
+    return actions, prob, reward, flags, value
+
+
 PPO_TRUNK_FLOATS, PPO_RUNNING_FLOATS = 46272, 768
 
 

@@ -8,7 +8,7 @@ mapping float32 (N, 16) observations to action probabilities (N, 4) -- or (probs
 reference's `TransformerModel` (models/transformer.py) -- and stays stock PyTorch-ROCm: it is the consumer; or a
 `g2048.DevicePolicy` (takes_boards = True), the reference's MLP actor / critic as one HIP launch on the boards; or a
 `g2048.DeviceTransformerPolicy` (takes_boards = True), that `TransformerModel` as one HIP launch on the boards.
-With a `g2048.DevicePolicy`, sampler="collect" plays the whole collect -- forward, sampling and env step of every step -- in ONE launch.
+With either of the two, sampler="collect" plays the whole collect -- forward, sampling and env step of every step -- in ONE launch.
 """
 import warnings
 
@@ -17,7 +17,15 @@ import torch
 from . import _lib as L
 from . import ops
 from .policy import DevicePolicy
+from .tpolicy import DeviceTransformerPolicy
 from .vec import VecGame2048
+
+
+def boards_from_observations(x):
+    """The packed boards (uint8, the shape of x) that normalized observations x = code / 15 were encoded from: round(15 x). Exact
+    for float32, float16 and bfloat16 observations: a code is at most 17, and 15 times a 16-bit rounding of code / 15 misses the
+    code by less than 17 * 2^-9 < 1 / 2. What DeviceTransformerPolicy.update() takes (RolloutCollector.sample(as_boards=True))."""
+    return torch.round(x.float() * 15).to(torch.uint8)
 
 
 def masked_sample(probs, mask4, generator=None):
@@ -47,11 +55,13 @@ class RolloutCollector:
 
     sampler="torch" keeps the unfused reference-style path (torch masked_sample + one launch per piece).
 
-    sampler="collect" (a `g2048.DevicePolicy` only) runs the T steps of a collect() as ONE `g2048_ppo_collect` launch: the actor's
-    (and critic's) forward, the sampling and the env step of every step inside one kernel, the boards in registers between the
-    steps. It fills the same buffers with the same bits as sampler="fused" with that policy, rows 0 of obs / masks included, so it
-    takes no graph and no priming launch; the step index is the device counter, so a collect() captured in a graph of the caller's
-    replays as the next collect. The sampler is fixed for the collector's life. Where each of the two is the faster: DESIGN.md."""
+    sampler="collect" (a `g2048.DevicePolicy` or a `g2048.DeviceTransformerPolicy` only) runs the T steps of a collect() as ONE
+    launch, `g2048_ppo_collect` or `g2048_tpolicy_collect`: the network's forward, the sampling and the env step of every step
+    inside one kernel, the boards on the chip between the steps. It fills the same buffers with the same bits as sampler="fused"
+    with that policy, rows 0 of obs / masks included, so it takes no graph and no priming launch; the step index is the device
+    counter, so a collect() captured in a graph of the caller's replays as the next collect, and the kernel reads the policy's blob,
+    so after the policy's refresh() the next collect or replay acts with the new weights. The sampler is fixed for the collector's
+    life. Where each of the two is the faster: DESIGN.md."""
 
     def __init__(self, n_envs, n_steps, policy, device="cuda", seed=0x2048, id_base=0, shaping=False,
                  generator=None, sampler="fused", obs_dtype=torch.float32, use_graph=True, seen_capacity_log2=20,
@@ -63,9 +73,10 @@ class RolloutCollector:
         self.generator = generator
         if sampler not in ("fused", "torch", "collect"):
             raise ValueError("sampler must be 'fused' (g2048_rollout_step, counter RNG), 'torch' (masked_sample) or 'collect' "
-                             "(g2048_ppo_collect: the whole collect in one launch)")
-        if sampler == "collect" and not isinstance(policy, DevicePolicy):
-            raise ValueError("sampler='collect' needs a g2048.DevicePolicy (the forward pass runs inside the collecting kernel)")
+                             "(g2048_ppo_collect / g2048_tpolicy_collect: the whole collect in one launch)")
+        if sampler == "collect" and not isinstance(policy, (DevicePolicy, DeviceTransformerPolicy)):
+            raise ValueError("sampler='collect' needs a g2048.DevicePolicy or a g2048.DeviceTransformerPolicy (the forward pass runs "
+                             "inside the collecting kernel)")
         if shaping and sampler == "torch":
             raise ValueError("shaping=True needs sampler='fused' or 'collect' (they record what remember() consumes)")
         if minibatches and sampler == "torch":
@@ -186,14 +197,19 @@ class RolloutCollector:
             self.use_graph = False
 
     def _collect_one_launch(self):
-        """The T steps as one g2048_ppo_collect launch; the blobs by the batch size, as DevicePolicy.__call__ takes them (the
-        reference's BatchNorm rule for a batch of one row). Step index = the device counter, advanced behind the launch."""
+        """The T steps as one launch, by the policy's type. g2048_ppo_collect: the blobs by the batch size, as DevicePolicy.__call__
+        takes them (the reference's BatchNorm rule for a batch of one row). g2048_tpolicy_collect: the policy's blob, the values
+        always written. Step index = the device counter, advanced behind the launch."""
         env, pol, n = self.env, self.policy, self.n
-        ops.ppo_collect(env.boards, env.scores, pol.actor.blob(n), pol.critic.blob(n) if pol.critic is not None else None, self.T,
-                        pol.precision, env.seed, 0, env.id_base, actions=self.actions, prob=self.logp,
-                        reward=self.rewards64 if self.shaping else self.rewards, flags=self.flags,
-                        value=self.values if pol.critic is not None else None, obs=self._obs, mask=self._masks,
-                        next_boards=self.next_boards, state_maxcode=self.state_maxcode, step_counter=self._counter)
+        out = dict(actions=self.actions, prob=self.logp, reward=self.rewards64 if self.shaping else self.rewards, flags=self.flags,
+                   obs=self._obs, mask=self._masks, next_boards=self.next_boards, state_maxcode=self.state_maxcode,
+                   step_counter=self._counter)
+        if isinstance(pol, DeviceTransformerPolicy):
+            ops.tpolicy_collect(env.boards, env.scores, pol.packed, pol.dim_ff, pol.n_layers, self.T, pol.precision, env.seed, 0,
+                                env.id_base, value=self.values, **out)
+        else:
+            ops.ppo_collect(env.boards, env.scores, pol.actor.blob(n), pol.critic.blob(n) if pol.critic is not None else None, self.T,
+                            pol.precision, env.seed, 0, env.id_base, value=self.values if pol.critic is not None else None, **out)
         self._counter.add_(self.T)
         env.t += self.T
         torch.log_(self.logp)                   # the kernel stores the probability; the reference keeps its log
@@ -258,7 +274,7 @@ class RolloutCollector:
         if self.seen is not None:
             self.seen.assert_ok()
 
-    def sample(self, batch_size, generator=None, want_indices=False, out=None):
+    def sample(self, batch_size, generator=None, want_indices=False, out=None, as_boards=False):
         """PPOMemory.sample(batch_size) (agents/ppo_agent.py:21-50) over the transitions of the last collect(), as the tensors
         PPOAgent.update builds from it (:342-354): dict(states float32 (B,16) normalized, actions int64 (B,), old_log_probs
         float32 (B,), rewards float32 (B,) -- the shaped reward remember() stores when shaping=True, else the env's --,
@@ -266,7 +282,11 @@ class RolloutCollector:
         B distinct transitions (without replacement; a batch larger than the buffer is the whole buffer), drawn and gathered
         by ONE launch (g2048_minibatch_gather), no host synchronisation. The draw is keyed by (the collector's seed, the number
         of sample() calls so far); generator: a CPU torch.Generator to take the key from instead; out: the dict a previous call
-        of the same batch size returned, to be overwritten instead of allocating six tensors again."""
+        of the same batch size returned, to be overwritten instead of allocating six tensors again. as_boards=True: `states` and
+        `next_states` are the uint8 (B,16) packed boards instead (boards_from_observations, exact for every obs dtype), the tensors
+        DeviceTransformerPolicy.update() takes; the rest of the dict is the same. `out` is then not taken: it is the float dict."""
+        if as_boards and out is not None:
+            raise ValueError("RolloutCollector.sample: out= is the dict of a call with as_boards=False")
         if not self.minibatches:
             raise RuntimeError("RolloutCollector.sample needs minibatches=True (or shaping=True): the next states are not recorded")
         if not self._filled:
@@ -282,4 +302,6 @@ class RolloutCollector:
                                    rewards.view(T * n), self.next_boards.view(T * n, 16), self.flags.view(T * n),
                                    batch_size, seed, self._samples, want_indices=want_indices, out=out)
         self._samples += 1
+        if as_boards:
+            out = dict(out, states=boards_from_observations(out["states"]), next_states=boards_from_observations(out["next_states"]))
         return out

@@ -22,9 +22,10 @@ call: the NaN check on the loss, the clipping and both Adam steps are two more l
 until the loss is printed. --dropout P (with --learner device; the reference's networks have 0.2) trains with the reference's live
 dropout on the device, the masks drawn from the learner's counter RNG; the default 0 leaves the Dropout layers out, and the torch
 learner keeps its own.
---sampler collect (with --policy device-f32 / device-bf16) plays the whole collect -- forward, sampling and env step of every step --
-as ONE launch (g2048_ppo_collect) instead of two launches a step replayed from a graph; the trajectory is the same bits.
-DESIGN.md "PPO collect in one launch" says where each is the faster."""
+--sampler collect (with any --policy but torch) plays the whole collect -- forward, sampling and env step of every step -- as ONE
+launch (g2048_ppo_collect for the MLP, g2048_tpolicy_collect for the transformer) instead of two launches a step replayed from a
+graph; the trajectory is the same bits. DESIGN.md "PPO collect in one launch" and "Transformer-policy collect in one launch" say
+where each is the faster."""
 import argparse
 import os
 import sys
@@ -49,10 +50,11 @@ ap.add_argument("--optimizer", choices=("torch", "device"), default="torch",
 ap.add_argument("--dropout", type=float, default=0.0,
                 help="with --learner device: the dropout probability of the training-mode forwards (the reference's networks: 0.2)")
 ap.add_argument("--sampler", choices=("fused", "collect"), default="fused",
-                help="collect (with --policy device-f32 / device-bf16): the whole collect in one launch")
+                help="collect (with any --policy but torch): the whole collect in one launch")
 a = ap.parse_args()
-if a.sampler == "collect" and not a.policy.startswith("device-"):
-    ap.error("--sampler collect runs the MLP's forward inside the collecting kernel; use --policy device-f32 or device-bf16")
+if a.sampler == "collect" and a.policy == "torch":
+    ap.error("--sampler collect runs the forward inside the collecting kernel; use one of the device policies "
+             "(device-f32, device-bf16, transformer, transformer-bf16)")
 if a.optimizer == "device" and a.learner != "device":
     ap.error("--optimizer device needs --learner device")
 if a.dropout and a.learner != "device":

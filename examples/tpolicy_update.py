@@ -3,6 +3,7 @@
 
     python examples/tpolicy_update.py [--envs 256] [--updates 5] [--epochs 3] [--dim-ff 2048] [--precision f32|bf16] [--lr 3e-4]
                                       [--optimizer device|torch] [--dropout P|module] [--dropout-seed S]
+                                      [--collector single|fused|collect] [--steps 8]
 
 A stock-torch module with the reference's layout, a VecGame2048 batch, one step of every env acted by
 g2048.DeviceTransformerPolicy (the probabilities of one g2048_tpolicy_forward launch, PPOAgent.get_action's masked sampling), then
@@ -17,7 +18,13 @@ No gradient copy and no host synchronisation inside an update; the loss parts ar
 --envs is at most 1,024, the pass's limit. --dropout P (or "module" for the layers' own 0.1) makes the update the reference's: its
 networks stay in training mode through PPOAgent.update(), so the advantage block's two critic forwards and every epoch's forward run
 the encoder's four dropout sites, here with counter-RNG masks keyed by (--dropout-seed, net.dropout_index) and regenerated in the
-backward pass; acting stays eval mode. The script shows that the pieces fit; it makes no claim about learning.
+backward pass; acting stays eval mode.
+--collector single (the default) is the hand-written loop above: one step of every env, torch's masked_sample. --collector fused
+and --collector collect take the experience from g2048.RolloutCollector(--envs, --steps, net, sampler=..., minibatches=True)
+instead: per update one collect() of --steps steps (fused: a forward and a rollout step per env step, replayed from a graph;
+collect: ONE g2048_tpolicy_collect launch), then sample(B, as_boards=True), B = min(1,024, --envs x --steps) distinct transitions
+as the packed boards net.update() takes. The update packs the acting blob in place, so the next collect acts with the new weights.
+The script shows that the pieces fit; it makes no claim about learning.
 """
 import argparse
 import os
@@ -40,6 +47,9 @@ ap.add_argument("--optimizer", choices=("device", "torch"), default="device",
                 help="device: net.update(), clipping and Adam in the library; torch: clip_grad_norm_ and torch.optim.Adam on attached views")
 ap.add_argument("--dropout", default="0", help="a probability for the encoder's four dropout sites, or 'module' for the layers' own; 0: eval mode")
 ap.add_argument("--dropout-seed", type=int, default=0)
+ap.add_argument("--collector", choices=("single", "fused", "collect"), default="single",
+                help="single: one env step by torch's masked_sample; fused / collect: g2048.RolloutCollector with that sampler")
+ap.add_argument("--steps", type=int, default=8, help="with --collector fused / collect: env steps per collect")
 a = ap.parse_args()
 dropout = a.dropout if a.dropout == "module" else float(a.dropout)
 if not 1 <= a.envs <= 1024:
@@ -64,16 +74,28 @@ net.attach_params()                    # the module's parameters are views of ne
 if a.optimizer == "torch":
     net.attach_grads()                 # and their .grad views of net.grad
     optimizer = torch.optim.Adam(net.model.parameters(), lr=a.lr)
-env = g2048.VecGame2048(a.envs, device=dev, seed=seed)
-gen = torch.Generator(device=dev).manual_seed(seed)
+if a.collector == "single":
+    env = g2048.VecGame2048(a.envs, device=dev, seed=seed)
+    gen = torch.Generator(device=dev).manual_seed(seed)
+else:
+    if a.steps < 1:
+        sys.exit("--steps must be at least 1")
+    rc = g2048.RolloutCollector(a.envs, a.steps, net, device=dev, seed=seed, sampler=a.collector, minibatches=True)
+    batch = min(1024, a.envs * a.steps)
 
 for update in range(a.updates):
-    boards = env.boards.clone()
-    probs, _ = net(boards)
-    actions, old_log_probs = g2048.masked_sample(probs, g2048.ops.valid_moves(boards), generator=gen)
-    next_boards, reward, done, _ = env.step(actions)
-    next_boards, reward, dones = next_boards.clone(), reward.float().clone(), done.float()
-    actions = actions.to(torch.int64)
+    if a.collector == "single":
+        boards = env.boards.clone()
+        probs, _ = net(boards)
+        actions, old_log_probs = g2048.masked_sample(probs, g2048.ops.valid_moves(boards), generator=gen)
+        next_boards, reward, done, _ = env.step(actions)
+        next_boards, reward, dones = next_boards.clone(), reward.float().clone(), done.float()
+        actions = actions.to(torch.int64)
+    else:
+        rc.collect()
+        mb = rc.sample(batch, as_boards=True)      # states / next_states as packed boards
+        boards, actions, old_log_probs, reward, next_boards, dones = (mb[k] for k in ("states", "actions", "old_log_probs", "rewards",
+                                                                                     "next_states", "dones"))
     if a.optimizer == "device":
         rows, _ = net.update(boards, actions, old_log_probs, reward, next_boards, dones, epochs=a.epochs, lr=a.lr)
         losses = rows[-1]
@@ -86,9 +108,12 @@ for update in range(a.updates):
             net.refresh()              # attached: packs the acting blob, nothing else
     loss, actor, value, entropy = losses.tolist()
     print("update %d: %d boards, last epoch's loss %.4f = actor %.4f + 0.4 x value %.4f - 0.05 x entropy %.4f; mean reward %.2f"
-          % (update, a.envs, loss, actor, value, entropy, float(reward.mean())))
-    fresh, _ = g2048.ops.reset(a.envs, seed, update + 1, 0, device=dev)
-    env.load(torch.where(done[:, None], fresh, env.boards), torch.where(done, torch.zeros_like(env.scores), env.scores))
+          % (update, boards.shape[0], loss, actor, value, entropy, float(reward.mean())))
+    if a.collector == "single":
+        fresh, _ = g2048.ops.reset(a.envs, seed, update + 1, 0, device=dev)
+        env.load(torch.where(done[:, None], fresh, env.boards), torch.where(done, torch.zeros_like(env.scores), env.scores))
+if a.collector != "single":
+    print("collector %s: %d collects of %d envs x %d steps, %d transitions sampled per update" % (a.collector, a.updates, a.envs, a.steps, batch))
 print("parameters attached: %s; %d floats of gradient in place" % (net.params_attached, net.grad.numel()))
 print("dropout %s: %d training forwards, seed %d" % (net.dropout, net.dropout_index, net.dropout_seed))
 if a.optimizer == "device":
