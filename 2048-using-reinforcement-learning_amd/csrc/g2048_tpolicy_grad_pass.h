@@ -23,6 +23,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <type_traits>
 
 #include "../../include/g2048_tlearn.h"
 #include "g2048_grad_products.h"
@@ -30,6 +31,7 @@
 #include "g2048_mfma.h"
 #include "g2048_ppo_head.h"
 #include "g2048_qnet_drop.h"
+#include "g2048_tpolicy_bf16.h"
 #include "g2048_tpolicy_layout.h"
 
 namespace {
@@ -45,9 +47,13 @@ inline size_t row_chunks(size_t rows) { return (rows + kRowChunk - 1) / kRowChun
 inline size_t col_chunks(size_t rows) { return (rows + kColRows - 1) / kColRows; }
 
 // workspace, in floats; T = 16 n tokens. Every array's size is a multiple of four floats, so every array is 16-byte aligned.
+// half (the bf16 feed-forward mode, g2048_tbf16.h): h and dh hold bf16, two elements a float, and wb follows the training array.
 struct Workspace {
     size_t n, T, ff, layers;
-    Workspace(size_t n_, int dim_ff, int n_layers) : n(n_), T(16 * n_), ff((size_t)dim_ff), layers((size_t)n_layers) {}
+    bool half;
+    Workspace(size_t n_, int dim_ff, int n_layers, bool half_ = false)
+        : n(n_), T(16 * n_), ff((size_t)dim_ff), layers((size_t)n_layers), half(half_) {}
+    size_t hidden() const { return half ? T * ff / 2 : T * ff; }                      // floats of h, and of dh
     // kept by the forward
     size_t x(size_t l) const { return l * T * kD; }                                   // l = 0 .. layers: layer l's input
     size_t layer(size_t l) const { return x(layers + 1) + l * T * (kQkv + 5 * kD + 4); }
@@ -59,7 +65,7 @@ struct Workspace {
     size_t pre2(size_t l) const { return x1(l) + T * kD; }
     size_t stat(size_t l) const { return pre2(l) + T * kD; }                          // [2][T][2]: norm1's, norm2's (mean, rstd)
     size_t h() const { return layer(layers); }                                        // [T][dim_ff], one for all layers
-    size_t a1() const { return h() + T * ff; }
+    size_t a1() const { return h() + hidden(); }
     size_t a2() const { return a1() + n * kFc1; }
     // the backward's own
     size_t dz() const { return a2() + n * kFc2; }                                     // [n][8]: logits 0..3, value 4
@@ -73,7 +79,7 @@ struct Workspace {
     size_t datt() const { return ds() + T * kD; }
     size_t dqkv() const { return datt() + T * kD; }
     size_t dh() const { return dqkv() + T * kQkv; }
-    size_t wpart() const { return dh() + T * ff; }                                    // [row chunks][the largest M K]
+    size_t wpart() const { return dh() + hidden(); }                                    // [row chunks][the largest M K]
     size_t wmax() const { return (size_t)kD * (ff > (size_t)kQkv ? ff : (size_t)kQkv); }
     size_t bpart() const { return wpart() + row_chunks(T) * wmax(); }                 // [row chunks][the largest M]
     size_t bmax() const { return ff > (size_t)kQkv ? ff : (size_t)kQkv; }
@@ -82,6 +88,9 @@ struct Workspace {
     // the training-mode pass's one array more: ds x the multipliers of site 1 or 3
     size_t dsm() const { return floats(); }
     size_t train_floats() const { return dsm() + T * kD; }
+    // the bf16 mode's: per layer the packed bf16 weights W1 [ff][64], its transpose [64][ff], W2 [64][ff], its transpose [ff][64]
+    size_t wb() const { return train_floats(); }
+    size_t bf16_floats() const { return wb() + layers * 4 * (size_t)kD * ff / 2; }
 };
 
 __device__ inline float sum16(float v)               // over the 16 lanes that share lane >> 4, the same on all of them
@@ -506,12 +515,14 @@ inline int tg_check(const char *entry, const TgCall &c, size_t needed, const cha
 
 // The launch sequence, after tg_check. kDrop false: the eval-mode pass. kDrop true: site s of layer l is live where p4[s] > 0 and
 // then launches the QDrop instantiation; with all four 0 the sequence and the bits are the eval-mode pass's.
-template <bool kDrop>
+// kBf16: the bf16 feed-forward mode (g2048_tbf16.h). A layer's seven products with dim_ff as an extent are g2048_tpolicy_bf16.h's, h and dh
+// are bf16, and the forward packs every layer's bf16 weight copies once, before that layer's linear1.
+template <bool kDrop, bool kBf16 = false>
 int tg_pass(const char *entry, const TgCall &c, uint32_t domain = 0)
 {
     const size_t n = c.n;
     const int dim_ff = c.dim_ff;
-    const Workspace ws(n, dim_ff, c.n_layers);
+    const Workspace ws(n, dim_ff, c.n_layers, kBf16);
     hipStream_t s = static_cast<hipStream_t>(c.stream);
     float *base = static_cast<float *>(c.workspace);
     const float *P = c.plain, *none = nullptr;
@@ -539,6 +550,23 @@ int tg_pass(const char *entry, const TgCall &c, uint32_t domain = 0)
         hipLaunchKernelGGL(tg_ln_kernel, dim3(ttiles), dim3(256), 0, s, S, np, eps, Y, reinterpret_cast<float2 *>(stat), T);
     };
 
+    // the bf16 mode's feed-forward launches: a layer's packed weights (once a call, in the forward; the backward reads them again),
+    // linear1 (+ ReLU, site 2) into the bf16 h, linear2 (site 3). Copy k of layer l: 0 W1, 1 its transpose, 2 W2, 3 its transpose.
+    __bf16 *hb = reinterpret_cast<__bf16 *>(base + ws.h()), *dhb = reinterpret_cast<__bf16 *>(base + ws.dh());
+    const __bf16 *nomask = nullptr;
+    const auto packed = [&](size_t l, int k) {
+        return reinterpret_cast<__bf16 *>(base + (kBf16 ? ws.wb() : 0)) + (4 * l + (size_t)k) * (size_t)kD * ff;
+    };
+    const auto pack_ff = [&](const auto *L, size_t l) {  // generic, as the two below: only the bf16 mode instantiates their kernels
+        hipLaunchKernelGGL(tb_pack_kernel<>, dim3(blocks_for((size_t)kD * ff, 256), 2), dim3(256), 0, s, L + kPlW1, ff, kD, packed(l, 0), packed(l, 1),
+                           L + pl_w2(ff), kD, ff, packed(l, 2), packed(l, 3));
+    };
+    const auto linear1_bf = [&](const QDrop *d, const float *L, size_t l, const auto *x1) {
+        launch_site<kDrop>(d, [](auto... q) { return tb_linear_kernel<false, true, float, __bf16, decltype(q)...>; },
+                           dim3((unsigned)(ff + 63) / 64, ttiles), dim3(256), s, x1, kD, static_cast<const __bf16 *>(packed(l, 0)), L + pl_b1(ff), none,
+                           nomask, hb, ff, T);
+    };
+
     // ---- the forward, its activations kept
     float *h = base + ws.h(), *a1 = base + ws.a1(), *a2 = base + ws.a2();
     hipLaunchKernelGGL(tg_embed_kernel, dim3(ttiles), dim3(256), 0, s, cells, P, base + ws.x(0), T);
@@ -553,8 +581,16 @@ int tg_pass(const char *entry, const TgCall &c, uint32_t domain = 0)
                            static_cast<const float *>(qkv), att, prob);
         linear(false, st.at(1), att, kD, L + kPlOutW, L + kPlOutB, x0, pre1, kD, T, ttiles);
         norm(pre1, norms, norms + 4 * kD, x1, stat);
-        linear(true, st.at(2), x1, kD, L + kPlW1, L + pl_b1(ff), none, h, ff, T, ttiles);
-        linear(false, st.at(3), h, ff, L + pl_w2(ff), L + pl_b2(ff), x1, pre2, kD, T, ttiles);
+        if constexpr (kBf16) {
+            pack_ff(L, l);
+            linear1_bf(st.at(2), L, l, x1);
+            launch_site<kDrop>(st.at(3), [](auto... q) { return tb_linear_kernel<false, false, __bf16, float, decltype(q)...>; }, dim3(1, ttiles),
+                               dim3(256), s, static_cast<const __bf16 *>(hb), ff, static_cast<const __bf16 *>(packed(l, 2)), L + pl_b2(ff),
+                               static_cast<const float *>(x1), nomask, pre2, kD, T);
+        } else {
+            linear(true, st.at(2), x1, kD, L + kPlW1, L + pl_b1(ff), none, h, ff, T, ttiles);
+            linear(false, st.at(3), h, ff, L + pl_w2(ff), L + pl_b2(ff), x1, pre2, kD, T, ttiles);
+        }
         norm(pre2, norms + 2 * kD, norms + 4 * kD + 1, base + ws.x(l + 1), stat + 2 * (size_t)T);
     }
     const float *xL = base + ws.x(nl);                                      // [n][1024]: the flatten is a view
@@ -596,6 +632,14 @@ int tg_pass(const char *entry, const TgCall &c, uint32_t domain = 0)
         combine(wpart, rchunks, (size_t)M * K, dW);
         combine(bpart, rchunks, (size_t)M, db);
     };
+    const auto dw_split_bf = [&](const auto *dY, int M, const auto *X, int K, float *dW, float *db) {       // the same in the bf16 mode
+        using TA = std::remove_cv_t<std::remove_pointer_t<decltype(dY)>>;
+        using TB = std::remove_cv_t<std::remove_pointer_t<decltype(X)>>;
+        hipLaunchKernelGGL((tb_dw_split_kernel<TA, TB>), dim3((unsigned)(K + 63) / 64, (unsigned)(M + 63) / 64, (unsigned)rchunks), dim3(256), 0, s, dY,
+                           M, X, K, wpart, bpart, T, kRowChunk);
+        combine(wpart, rchunks, (size_t)M * K, dW);
+        combine(bpart, rchunks, (size_t)M, db);
+    };
     const auto norm_bwd = [&](const float *g, const float *pre, const float *stat, const float *gamma, float *dnorm) {
         hipLaunchKernelGGL(tg_ln_bwd_kernel, dim3((unsigned)cchunks), dim3(256), 0, s, g, pre, reinterpret_cast<const float2 *>(stat), gamma, ds,
                            cpart, T);
@@ -626,13 +670,26 @@ int tg_pass(const char *entry, const TgCall &c, uint32_t domain = 0)
         const float *x0 = base + ws.x(l), *qkv = base + ws.qkv(l), *prob = base + ws.prob(l), *att = base + ws.att(l), *x1 = base + ws.x1(l),
                     *stat = base + ws.stat(l);
         const DropSites st = sites(l);
-        linear(true, st.at(2), x1, kD, L + kPlW1, L + pl_b1(ff), none, h, ff, T, ttiles);      // the hidden layer again, the same mask
-        norm_bwd(ga, base + ws.pre2(l), stat + 2 * (size_t)T, norms + 2 * kD, gnorms + 2 * kD);
-        const float *d3 = scaled(st.at(3));
-        dw_split(d3, kD, h, ff, GL + pl_w2(ff), GL + pl_b2(ff));
-        dx(st.at(2), d3, kD, L + pl_w2(ff), ff, none, h, dh, T, ttiles);
-        dw_split(dh, ff, x1, kD, GL + kPlW1, GL + pl_b1(ff));
-        dx(nullptr, dh, ff, L + kPlW1, kD, ds, none, gb, T, ttiles);
+        if constexpr (kBf16) {
+            linear1_bf(st.at(2), L, l, x1);                                                   // the hidden layer again, the same mask
+            norm_bwd(ga, base + ws.pre2(l), stat + 2 * (size_t)T, norms + 2 * kD, gnorms + 2 * kD);
+            const float *d3 = scaled(st.at(3));
+            dw_split_bf(d3, kD, static_cast<const __bf16 *>(hb), ff, GL + pl_w2(ff), GL + pl_b2(ff));
+            launch_site<kDrop>(st.at(2), [](auto... q) { return tb_linear_kernel<true, false, float, __bf16, decltype(q)...>; },
+                               dim3((unsigned)(ff + 63) / 64, ttiles), dim3(256), s, d3, kD, static_cast<const __bf16 *>(packed(l, 3)), none, none,
+                               static_cast<const __bf16 *>(hb), dhb, ff, T);
+            dw_split_bf(static_cast<const __bf16 *>(dhb), ff, x1, kD, GL + kPlW1, GL + pl_b1(ff));
+            hipLaunchKernelGGL((tb_linear_kernel<true, false, __bf16, float>), dim3(1, ttiles), dim3(256), 0, s, static_cast<const __bf16 *>(dhb), ff,
+                               static_cast<const __bf16 *>(packed(l, 1)), none, static_cast<const float *>(ds), nomask, gb, kD, T);
+        } else {
+            linear(true, st.at(2), x1, kD, L + kPlW1, L + pl_b1(ff), none, h, ff, T, ttiles);  // the hidden layer again, the same mask
+            norm_bwd(ga, base + ws.pre2(l), stat + 2 * (size_t)T, norms + 2 * kD, gnorms + 2 * kD);
+            const float *d3 = scaled(st.at(3));
+            dw_split(d3, kD, h, ff, GL + pl_w2(ff), GL + pl_b2(ff));
+            dx(st.at(2), d3, kD, L + pl_w2(ff), ff, none, h, dh, T, ttiles);
+            dw_split(dh, ff, x1, kD, GL + kPlW1, GL + pl_b1(ff));
+            dx(nullptr, dh, ff, L + kPlW1, kD, ds, none, gb, T, ttiles);
+        }
         norm_bwd(gb, base + ws.pre1(l), stat, norms, gnorms);
         const float *d1o = scaled(st.at(1));
         dw_split(d1o, kD, att, kD, GL + kPlOutW, GL + kPlOutB);

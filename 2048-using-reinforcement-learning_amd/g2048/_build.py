@@ -10,6 +10,7 @@ csrc/libg2048_tpolicy_collect_hip.so, for gfx950 with hipcc (cross-compiles with
     python -m g2048._build --collect [-o LIBRARY] [extra compiler flags ...] (the experience collector's library alone)
     python -m g2048._build --ppo-collect [-o LIBRARY] [extra compiler flags ...]   (the PPO experience collector's library alone)
     python -m g2048._build --tpolicy-collect [-o LIBRARY] [extra compiler flags ...]   (the transformer policy's collector alone)
+    python -m g2048._build --tbf16 [-o LIBRARY] [extra compiler flags ...]   (the transformer policy's bf16 gradient library alone)
 
 The libraries are built in-tree so that they travel with the source snapshot; they are
 git-ignored. -ffp-contract=off is REQUIRED: the reward / heuristic kernels follow
@@ -31,7 +32,9 @@ PPO_EXTENSIONS is a third table of that row shape, and libg2048_ppo_collect_hip.
 experience collection in one launch) is its one row, for the same reason once more: the tests pin EXTENSIONS at that one row.
 EXTRA_ROWS is the fourth and LAST table of that row shape: the tests pin ROWS, the union of the three above, at seven keys, and
 nothing pins this one's size, so the next library is one more row here and not a fifth table. Its first row is
-libg2048_tpolicy_collect_hip.so (include/g2048_tpolicy_collect.h: the transformer policy's experience collection in one launch).
+libg2048_tpolicy_collect_hip.so (include/g2048_tpolicy_collect.h: the transformer policy's experience collection in one launch); its
+second is libg2048_tbf16_hip.so (include/g2048_tbf16.h: the transformer policy's gradient pass with bf16 feed-forward products; the
+kernels are the learner library's plus csrc/g2048_tpolicy_bf16.h).
 Everything below reads ALL_ROWS, every table.
 """
 import os
@@ -63,6 +66,7 @@ ROWS = {**LIBRARIES, **EXTENSIONS, **PPO_EXTENSIONS}  # the seven shared objects
 EXTRA_ROWS = {
     "TPOLICY_COLLECT_": ("libg2048_tpolicy_collect_hip.so", "G2048_TPOLICY_COLLECT_LIB", ["g2048_tpolicy_collect.hip"],
                          ["g2048_tpolicy_collect.h"]),
+    "TBF16_": ("libg2048_tbf16_hip.so", "G2048_TBF16_LIB", ["g2048_tpolicy_bf16.hip"], ["g2048_tbf16.h"]),
 }
 ALL_ROWS = {**ROWS, **EXTRA_ROWS}  # every shared object of the build
 PUBLIC_HEADERS = [os.path.join(INCLUDE, h) for row in ALL_ROWS.values() for h in row[3]]

@@ -183,13 +183,18 @@ def weight_caster(dtype, round_weights=None):
     return w
 
 
-def post_norm_tail(lay, x, attended, w, mult=None):
+def post_norm_tail(lay, x, attended, w, mult=None, feed_forward=None):
     """The rest of a post-norm encoder layer after the attention itself: norm1(x + out_proj(attended)), then the feed-forward
     pair and norm2, with the weights through w. mult: None (eval mode), or a callable (site, shape, dtype) -> the multipliers of
-    dropout site 1 (dropout1), 2 (the hidden layer's) or 3 (dropout2) of this layer, applied where the training-mode layer drops."""
+    dropout site 1 (dropout1), 2 (the hidden layer's) or 3 (dropout2) of this layer, applied where the training-mode layer drops.
+    feed_forward: None, or a callable (x, W1, b1, W2, b2, m2) -> linear2(m2(relu(linear1(x)))) that takes the place of the two plain
+    products (m2 applies the site-2 multipliers): the bf16 restatement of g2048.tpolicy."""
     a, d = lay.self_attn, (x.shape[-1],)
     m = (lambda site, t: t) if mult is None else (lambda site, t: t * mult(site, tuple(t.shape), t.dtype))
     x = F.layer_norm(x + m(1, attended @ w(a.out_proj.weight).T + w(a.out_proj.bias)), d, w(lay.norm1.weight), w(lay.norm1.bias), lay.norm1.eps)
+    if feed_forward is not None:
+        y = feed_forward(x, w(lay.linear1.weight), w(lay.linear1.bias), w(lay.linear2.weight), w(lay.linear2.bias), lambda t: m(2, t))
+        return F.layer_norm(x + m(3, y), d, w(lay.norm2.weight), w(lay.norm2.bias), lay.norm2.eps)
     h = m(2, torch.relu(x @ w(lay.linear1.weight).T + w(lay.linear1.bias)))
     return F.layer_norm(x + m(3, h @ w(lay.linear2.weight).T + w(lay.linear2.bias)), d, w(lay.norm2.weight), w(lay.norm2.bias), lay.norm2.eps)
 

@@ -2,7 +2,7 @@
 g2048_tlearn.h, g2048_tstep.h, g2048_ttrain.h): one Library per row of _build.LIBRARIES, each with its own table, error string and version;
 and of the extensions libg2048_collect_hip.so (g2048_collect.h), the one row of _build.EXTENSIONS, and libg2048_ppo_collect_hip.so
 (g2048_ppo_collect.h), the one row of _build.PPO_EXTENSIONS, bound by the same Library class; and of the rows of _build.EXTRA_ROWS, the
-open-ended fourth table: libg2048_tpolicy_collect_hip.so (g2048_tpolicy_collect.h).
+open-ended fourth table: libg2048_tpolicy_collect_hip.so (g2048_tpolicy_collect.h) and libg2048_tbf16_hip.so (g2048_tbf16.h).
 
 There is no fallback: if the library is missing or no HIP device is visible, every
 compute call raises. PyTorch is only used for device memory and streams -- tensors
@@ -205,6 +205,18 @@ TPOLICY_COLLECT_SIGNATURES = {
     "g2048_tpolicy_collect": (_int, [_vp] * 3 + [_int, _int] + [_vp] * 9 + [_u64, _u64, _vp, _u64, _sz, _int, _u32, _vp]),
 }
 
+TBF16_ABI_VERSION = 1
+TBF16_SIGNATURES = {
+    "g2048_tbf16_last_error": (C.c_char_p, []),
+    "g2048_tbf16_abi_version": (_int, []),
+    "g2048_tpolicy_bf16_workspace": (_sz, [_sz, _int, _int]),
+    "g2048_tpolicy_loss_grad_bf16": (_int, [_vp] * 6 + [_sz, _int, _int, _p4, _u64, _u64, _f, _f, _f] + [_vp] * 5 + [_sz, _vp]),
+    # the header's testing section: the three products on their own
+    "g2048_tbf16_test_linear": (_int, [_vp, _int, _vp, _vp, _vp, _vp, _int, _int, _sz, _int, _int, _vp, _sz, _vp]),
+    "g2048_tbf16_test_dx": (_int, [_vp, _int, _vp, _vp, _vp, _vp, _int, _sz, _int, _int, _vp, _sz, _vp]),
+    "g2048_tbf16_test_dw": (_int, [_vp, _int, _vp, _int, _vp, _vp, _sz, _int, _int, _vp, _sz, _vp]),
+}
+
 
 class Library:
     """One shared object of _build.ALL_ROWS (row `key`, of whichever table), loaded on first use and as loud as can be: a missing file, a file under
@@ -299,7 +311,9 @@ PPO_EXTENSIONS = {"PPO_COLLECT_": PPO_COLLECT}
 # the fourth table (_build.EXTRA_ROWS): no test pins its size, so the next library is one more row here
 TPOLICY_COLLECT = Library("TPOLICY_COLLECT_", "g2048_tpolicy_collect", TPOLICY_COLLECT_SIGNATURES, TPOLICY_COLLECT_ABI_VERSION,
                           "transformer policy collector", " and no experience collection of the transformer policy in one launch without it")
-EXTRA_ROWS = {"TPOLICY_COLLECT_": TPOLICY_COLLECT}
+TBF16 = Library("TBF16_", "g2048_tbf16", TBF16_SIGNATURES, TBF16_ABI_VERSION, "bf16 learner",
+                " and no bf16 gradient pass of the transformer policy without it")
+EXTRA_ROWS = {"TPOLICY_COLLECT_": TPOLICY_COLLECT, "TBF16_": TBF16}
 
 # the names the package, the tools and the tests call
 library_path, lib, check, call = MAIN.path, MAIN.load, MAIN.check, MAIN.call
@@ -310,6 +324,7 @@ ttrain_library_path, ttrain_lib, ttrain_call = TTRAIN.path, TTRAIN.load, TTRAIN.
 collect_library_path, collect_lib, collect_call = COLLECT.path, COLLECT.load, COLLECT.call
 ppo_collect_library_path, ppo_collect_lib, ppo_collect_call = PPO_COLLECT.path, PPO_COLLECT.load, PPO_COLLECT.call
 tpolicy_collect_library_path, tpolicy_collect_lib, tpolicy_collect_call = TPOLICY_COLLECT.path, TPOLICY_COLLECT.load, TPOLICY_COLLECT.call
+tbf16_library_path, tbf16_lib, tbf16_call = TBF16.path, TBF16.load, TBF16.call
 
 
 def stream_ptr(device):

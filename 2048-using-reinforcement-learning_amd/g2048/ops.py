@@ -620,8 +620,28 @@ def tpolicy_grad_workspace_bytes(n, dim_ff, n_layers):
                   L.TLEARN_BATCH_MAX, int(n), int(dim_ff), int(n_layers))
 
 
+GRAD_PRECISIONS = ("f32", "bf16")
+
+
+def check_grad_precision(grad_precision):
+    if grad_precision not in GRAD_PRECISIONS:
+        raise ValueError("g2048: grad_precision must be 'f32' or 'bf16' (got %r)" % (grad_precision,))
+    return grad_precision
+
+
+def tpolicy_bf16_workspace_bytes(n, dim_ff, n_layers):
+    """Bytes of the workspace tpolicy_loss_grad with grad_precision="bf16" needs for n boards (g2048_tpolicy_bf16_workspace, the bf16
+    learner library): tpolicy_train_workspace_bytes with the two (16 n, dim_ff) arrays at 2 bytes an element, plus 512 dim_ff bytes
+    of packed weights a layer."""
+    return _sized(L.tbf16_lib().g2048_tpolicy_bf16_workspace(int(n), int(dim_ff), int(n_layers)),
+                  "g2048: the transformer policy's bf16 gradient pass takes 1 .. %d boards (16 tokens each; a larger batch is refused, "
+                  "not truncated), a dim_ff that is a multiple of 32 and 1 .. 64 layers (got n = %d, dim_ff = %d, n_layers = %d)",
+                  L.TLEARN_BATCH_MAX, int(n), int(dim_ff), int(n_layers))
+
+
 def tpolicy_loss_grad(boards, plain, actions, old_log_probs, advantages, returns, dim_ff, n_layers, clip_epsilon=0.3, value_coef=0.4,
-                      entropy_coef=0.05, grad=None, losses=None, probs=None, value=None, workspace=None, dropout=None, seed=0, call_index=0):
+                      entropy_coef=0.05, grad=None, losses=None, probs=None, value=None, workspace=None, dropout=None, seed=0, call_index=0,
+                      grad_precision="f32"):
     """PPOAgent.update()'s loss (agents/ppo_agent.py:378-400) on the transformer policy's two heads and its gradient, on the device
     (g2048_tpolicy_loss_grad, the learner library): probs, value = the eval-mode module on boards / 15; loss = actor + value_coef
     value_loss - entropy_coef entropy with the clipped surrogate of exp(log probs[i, actions[i]] - old_log_probs[i]) against
@@ -632,7 +652,12 @@ def tpolicy_loss_grad(boards, plain, actions, old_log_probs, advantages, returns
     synchronisation. dropout: None, 0 or all zeros: eval mode through the learner library, as ever. A probability or a 4-tuple
     (qnet_dropout_p): the module's TRAINING-mode pass with the masks of (seed, call_index) (tpolicy_dropout_mask), regenerated in
     the backward (the training library's g2048_tpolicy_loss_grad_dropout; the workspace is then tpolicy_train_workspace_bytes').
+    grad_precision "bf16": the seven feed-forward products of every encoder layer take bf16 operands with f32 accumulation and the
+    hidden layer and its gradient are kept as bf16 (g2048_tpolicy_loss_grad_bf16, the bf16 learner library, include/g2048_tbf16.h has
+    the rounding points; the workspace is then tpolicy_bf16_workspace_bytes', with or without dropout). Not a rounding-level change:
+    gradients move by per cents of their largest element. "f32", the default: the calls above, bit for bit.
     Returns (losses float32 (4,) = loss, actor, value, entropy; probs float32 (n,4); value float32 (n,1); grad)."""
+    bf16 = check_grad_precision(grad_precision) == "bf16"
     p = qnet_dropout_p(dropout)
     floats = tpolicy_plain_floats(dim_ff, n_layers)
     L.require_device_tensor(boards, torch.uint8, (16,), "boards")
@@ -653,9 +678,16 @@ def tpolicy_loss_grad(boards, plain, actions, old_log_probs, advantages, returns
     value = _output(value, n, torch.float32, (1,), "value", dev)
     if n == 0:
         return losses, probs, value, grad
-    nb = tpolicy_grad_workspace_bytes(n, dim_ff, n_layers) if p is None else tpolicy_train_workspace_bytes(n, dim_ff, n_layers)
+    nb = (tpolicy_bf16_workspace_bytes if bf16 else tpolicy_grad_workspace_bytes if p is None else tpolicy_train_workspace_bytes)(
+        n, dim_ff, n_layers)
     workspace = _workspace(workspace, nb, dev)
-    if p is None:
+    if bf16:
+        L.tbf16_call(dev, L.tbf16_lib().g2048_tpolicy_loss_grad_bf16, boards.data_ptr(), plain.data_ptr(), actions.data_ptr(),
+                     old_log_probs.data_ptr(), advantages.data_ptr(), returns.data_ptr(), n, int(dim_ff), int(n_layers),
+                     None if p is None else _p4(p), L.u64(seed), L.u64(call_index), float(clip_epsilon), float(value_coef), float(entropy_coef),
+                     grad.data_ptr(), losses.data_ptr(), probs.data_ptr(), value.data_ptr(), workspace.data_ptr(), workspace.numel(),
+                     L.stream_ptr(dev))
+    elif p is None:
         L.tlearn_call(dev, L.tlearn_lib().g2048_tpolicy_loss_grad, boards.data_ptr(), plain.data_ptr(), actions.data_ptr(),
                       old_log_probs.data_ptr(), advantages.data_ptr(), returns.data_ptr(), n, int(dim_ff), int(n_layers), float(clip_epsilon),
                       float(value_coef), float(entropy_coef), grad.data_ptr(), losses.data_ptr(), probs.data_ptr(), value.data_ptr(),

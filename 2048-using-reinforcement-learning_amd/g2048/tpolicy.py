@@ -79,8 +79,51 @@ def _check_loss_inputs(n, actions, old_log_probs, advantages, returns):
 F32_EPS = float(torch.finfo(torch.float32).eps)
 
 
+def rnd(t):
+    """t as float32 (round to nearest even), then as bfloat16 (round to nearest even), back in t's dtype: the rounding of the bf16
+    gradient pass (include/g2048_tbf16.h)."""
+    return t.to(torch.float32).to(torch.bfloat16).to(t.dtype)
+
+
+class _RoundedLinear(torch.autograd.Function):
+    """y = rnd(x) rnd(W)^T + b as the bf16 pass computes it, forward and backward: dx = rnd(dy) rnd(W), dW = rnd(dy)^T rnd(x), and
+    db = the sum of dy as the pass stores it -- rounded for linear1 (its dy is the bf16 dh), as it arrives for linear2."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, stored_dy_is_bf16):
+        xr, wr = rnd(x), rnd(weight)
+        ctx.save_for_backward(xr, wr)
+        ctx.stored_dy_is_bf16 = stored_dy_is_bf16
+        return xr @ wr.T + bias
+
+    @staticmethod
+    def backward(ctx, dy):
+        xr, wr = ctx.saved_tensors
+        g = rnd(dy)
+        stored = g if ctx.stored_dy_is_bf16 else dy
+        return (g @ wr, g.reshape(-1, g.shape[-1]).T @ xr.reshape(-1, xr.shape[-1]), stored.reshape(-1, stored.shape[-1]).sum(0), None)
+
+
+class _StoredBf16(torch.autograd.Function):
+    """The hidden layer as the bf16 pass keeps it: rnd(v) forward; the gradient passes as it is (it is rounded where linear1's
+    backward reads it, after the ReLU mask and the site-2 multiplier)."""
+
+    @staticmethod
+    def forward(ctx, v):
+        return rnd(v)
+
+    @staticmethod
+    def backward(ctx, g):
+        return g
+
+
+def _feed_forward_bf16(x, w1, b1, w2, b2, m2):
+    h = _StoredBf16.apply(m2(torch.relu(_RoundedLinear.apply(x, w1, b1, True))))
+    return _RoundedLinear.apply(h, w2, b2, False)
+
+
 def loss_grad_reference(p, boards, actions, old_log_probs, advantages, returns, clip_epsilon=0.3, value_coef=0.4, entropy_coef=0.05,
-                        dtype=torch.float64, eps=F32_EPS, multipliers=None):
+                        dtype=torch.float64, eps=F32_EPS, multipliers=None, ff_bf16=False):
     """PPOAgent.update()'s loss (agents/ppo_agent.py:378-400) on the parsed module's two heads, in eval mode, with plain torch ops
     in `dtype` and autograd over the ops of forward_reference. multipliers: None, or a callable (layer, site, shape, dtype) -> the
     dropout multipliers (keep x 1 / (1 - p)) of site 0 (the attention probabilities, (N,4,16,16)), 1 (dropout1, (N,16,64)), 2 (the
@@ -92,7 +135,10 @@ def loss_grad_reference(p, boards, actions, old_log_probs, advantages, returns, 
     Categorical(probs=probs) renormalises and clamps the probabilities to [eps, 1 - eps]; eps defaults to float32's, which is what
     the float32 module and the kernel clamp at, whatever `dtype` is. Returns (losses (4,) = loss, actor, vloss, ent; probs (N,4);
     value (N,1); grad: d loss / d parameter flat in the plain layout, the LayerNorm-eps slots 0). The yardstick of
-    g2048_tpolicy_loss_grad; the module's own .grad fields are not touched."""
+    g2048_tpolicy_loss_grad; the module's own .grad fields are not touched. ff_bf16: the function of the bf16 gradient pass
+    (grad_precision="bf16", include/g2048_tbf16.h) restated in `dtype`: every operand of a layer's feed-forward products rounded by
+    rnd, the hidden layer and its gradient kept rounded, linear1's bias gradient the sum of the rounded dh; it composes with
+    multipliers. False, the default: what the function returned before it had the argument."""
     n = boards.shape[0]
     _check_loss_inputs(n, actions, old_log_probs, advantages, returns)
     seq = p.plain_tensors()
@@ -110,7 +156,7 @@ def loss_grad_reference(p, boards, actions, old_log_probs, advantages, returns, 
             s = torch.softmax((q @ k.transpose(-1, -2)) / 4, -1)
             if mult is not None:
                 s = s * mult(0, tuple(s.shape), s.dtype)
-            x = E.post_norm_tail(lay, x, (s @ v).transpose(1, 2).reshape(n, TOKENS, D_MODEL), w, mult)
+            x = E.post_norm_tail(lay, x, (s @ v).transpose(1, 2).reshape(n, TOKENS, D_MODEL), w, mult, _feed_forward_bf16 if ff_bf16 else None)
         h = torch.relu(x.reshape(n, -1) @ w(p.fc1.weight).T + w(p.fc1.bias))
         h = torch.relu(h @ w(p.fc2.weight).T + w(p.fc2.bias))
         probs = torch.softmax(h @ w(p.actor.weight).T + w(p.actor.bias), -1)
@@ -169,6 +215,9 @@ class DeviceTransformerPolicy(E.PackedNet):
     optimizer_state_dict() / load_optimizer_state_dict() exchange the state with torch.optim.Adam(model.parameters()).
     dropout, dropout_seed: what the TRAINING forwards apply (loss_and_grad, advantages, update); the module docstring. 0.0, the
     default: none, through the entry points and with the bits of a policy built without the argument.
+    grad_precision: "f32" (the default: the gradient pass as ever, bit for bit) or "bf16": loss_and_grad and update run the seven
+    feed-forward products of every encoder layer on the bf16 matrix cores (include/g2048_tbf16.h). advantages(), the acting
+    forward and the optimiser step are the same either way. Any other value raises ValueError.
 
     takes_boards = True: RolloutCollector hands it the packed boards instead of the float observations."""
 
@@ -176,7 +225,8 @@ class DeviceTransformerPolicy(E.PackedNet):
     name, parse = NAME, staticmethod(parse)
     plain_floats, packed_bytes, pack = map(staticmethod, (ops.tpolicy_plain_floats, ops.tpolicy_packed_bytes, ops.tpolicy_pack))
 
-    def __init__(self, model, precision="f32", dropout=0.0, dropout_seed=0):
+    def __init__(self, model, precision="f32", dropout=0.0, dropout_seed=0, grad_precision="f32"):
+        self.grad_precision = ops.check_grad_precision(grad_precision)
         self.dropout = E.dropout_of(NAME, parse(model), dropout)    # (attention, dropout1, dropout, dropout2)
         self.dropout_seed, self.dropout_index = ops.L.u64(dropout_seed), 0
         super().__init__(model, precision)
@@ -206,6 +256,9 @@ class DeviceTransformerPolicy(E.PackedNet):
     def _train_workspace(self, n, device):          # the training passes': one more array
         return torch.empty(ops.tpolicy_train_workspace_bytes(n, self.dim_ff, self.n_layers), dtype=torch.uint8, device=device)
 
+    def _bf16_workspace(self, n, device):           # the bf16 gradient pass's: the hidden layer and its gradient at 2 bytes
+        return torch.empty(ops.tpolicy_bf16_workspace_bytes(n, self.dim_ff, self.n_layers), dtype=torch.uint8, device=device)
+
     def loss_and_grad(self, boards, actions, old_log_probs, advantages, returns, clip_epsilon=0.3, value_coef=0.4, entropy_coef=0.05):
         """(losses float32 (4,) = loss, actor loss, value loss, entropy; probs float32 (N,4); value float32 (N,1)) of
         PPOAgent.update()'s loss (agents/ppo_agent.py:378-400; the coefficients default to PPOAgent's) on uint8 (N,16) boards,
@@ -216,7 +269,10 @@ class DeviceTransformerPolicy(E.PackedNet):
         error (the kernel reads actions & 3). The outputs and the workspace are the network's (one set per (N, stream)): after
         the first call per (N, stream) nothing is allocated. This is a training forward: with any net.dropout > 0 it is the
         module's TRAINING-mode pass (g2048_tpolicy_loss_grad_dropout) under the masks of (net.dropout_seed, net.dropout_index),
-        regenerated in the backward; the index counts on either way, and with dropout 0 the call and its bits are as ever."""
+        regenerated in the backward; the index counts on either way, and with dropout 0 the call and its bits are as ever. With
+        net.grad_precision "bf16" the feed-forward products of every encoder layer take bf16 operands and the hidden layer is kept
+        as bf16 (g2048_tpolicy_loss_grad_bf16, with or without dropout): gradients then differ from the f32 pass's by per cents of
+        their largest element, not by rounding (docs/LOG.md R37); net.plain, net.grad and the step stay f32."""
         return self._loss_and_grad(boards, actions, old_log_probs, advantages, returns, clip_epsilon, value_coef, entropy_coef, None)
 
     def _loss_and_grad(self, boards, actions, old_log_probs, advantages, returns, clip_epsilon, value_coef, entropy_coef, losses_row):
@@ -232,8 +288,9 @@ class DeviceTransformerPolicy(E.PackedNet):
             losses = losses_row
         ops.tpolicy_loss_grad(boards, self.plain, actions, old_log_probs, advantages, returns, self.dim_ff, self.n_layers, clip_epsilon,
                               value_coef, entropy_coef, grad=self.grad, losses=losses, probs=probs, value=value,
-                              workspace=self._out.get(n, self._train_workspace if any(self.dropout) else self._grad_workspace) if n else None,
-                              dropout=self.dropout, seed=self.dropout_seed, call_index=self._next_index())
+                              workspace=self._out.get(n, self._bf16_workspace if self.grad_precision == "bf16" else
+                                                      self._train_workspace if any(self.dropout) else self._grad_workspace) if n else None,
+                              dropout=self.dropout, seed=self.dropout_seed, call_index=self._next_index(), grad_precision=self.grad_precision)
         return losses, probs, value
 
     def advantages(self, boards, next_boards, rewards, dones, gamma=0.995, training=None):

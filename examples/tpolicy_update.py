@@ -2,7 +2,7 @@
 """A PPO update of the reference's transformer policy (models/transformer.py) with its loss, gradients and optimiser on the GPU.
 
     python examples/tpolicy_update.py [--envs 256] [--updates 5] [--epochs 3] [--dim-ff 2048] [--precision f32|bf16] [--lr 3e-4]
-                                      [--optimizer device|torch] [--dropout P|module] [--dropout-seed S]
+                                      [--grad-precision f32|bf16] [--optimizer device|torch] [--dropout P|module] [--dropout-seed S]
                                       [--collector single|fused|collect] [--steps 8]
 
 A stock-torch module with the reference's layout, a VecGame2048 batch, one step of every env acted by
@@ -41,7 +41,9 @@ ap.add_argument("--envs", type=int, default=256)
 ap.add_argument("--updates", type=int, default=5)
 ap.add_argument("--epochs", type=int, default=3)
 ap.add_argument("--dim-ff", type=int, default=2048)
-ap.add_argument("--precision", choices=("f32", "bf16"), default="f32", help="of the acting blob; the gradient pass is f32 either way")
+ap.add_argument("--precision", choices=("f32", "bf16"), default="f32", help="of the acting blob; the gradient pass is --grad-precision's")
+ap.add_argument("--grad-precision", choices=("f32", "bf16"), default="f32",
+                help="bf16: every encoder layer's feed-forward products of the gradient pass on the bf16 matrix cores (not a rounding-level change)")
 ap.add_argument("--lr", type=float, default=3e-4)
 ap.add_argument("--optimizer", choices=("device", "torch"), default="device",
                 help="device: net.update(), clipping and Adam in the library; torch: clip_grad_norm_ and torch.optim.Adam on attached views")
@@ -69,7 +71,7 @@ class TransformerModel(nn.Module):      # the reference's layout (models/transfo
 dev, seed = torch.device("cuda"), 1
 torch.manual_seed(0)
 net = g2048.DeviceTransformerPolicy(TransformerModel(a.dim_ff).to(dev).eval(), precision=a.precision, dropout=dropout,
-                                    dropout_seed=a.dropout_seed)
+                                    dropout_seed=a.dropout_seed, grad_precision=a.grad_precision)
 net.attach_params()                    # the module's parameters are views of net.plain from here on
 if a.optimizer == "torch":
     net.attach_grads()                 # and their .grad views of net.grad

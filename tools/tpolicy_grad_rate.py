@@ -3,6 +3,8 @@ g2048_tpolicy_loss_grad) against stock torch on the same GPU.
 
     python3 tools/tpolicy_grad_rate.py                    the table
     python3 tools/tpolicy_grad_rate.py --dropout          what the encoder's live dropout costs (the training library)
+    python3 tools/tpolicy_grad_rate.py --grad-precision bf16   the f32 pass and the bf16 feed-forward mode side by side, at dropout 0
+                                                          and 0.1 (profiles/r37_tpolicy_bf16_rate.txt keeps a run)
 
 The reference's layout (torch's default init, the heads x 8) with dim_ff 128 (bench.py's config 4) and 2,048 (the reference's), 2
 layers, at N = 64, 256 and 1,024 boards. Versions, alternating within every round:
@@ -212,5 +214,53 @@ def dropout_table():
                                                                                    statistics.median(v) / base))
 
 
+def precision_table():
+    """--grad-precision bf16: the f32 pass and the bf16 feed-forward mode (g2048_tpolicy_loss_grad_bf16) in the same run, each at dropout
+    0 and 0.1, alternating within every round; and how far the bf16 mode's gradients lie from the f32 pass's."""
+    print("device: %s; torch %s" % (torch.cuda.get_device_name(0), torch.__version__))
+    print("%-7s %-5s %-30s %-30s %-8s %-30s %-30s %-8s %s" % ("dim_ff", "N", "f32, p = 0", "bf16, p = 0", "f32/bf16", "f32, p = 0.1", "bf16, p = 0.1",
+                                                             "f32/bf16", "bf16 against f32 gradients (p = 0)"))
+    for dim_ff in (128, 2048):
+        torch.manual_seed(29)
+        model = TPolicy(dim_ff).to(dev).eval()
+        with torch.no_grad():
+            model.actor.weight.mul_(8.0)
+            model.critic.weight.mul_(8.0)
+        nets = {(gp, p): DeviceTransformerPolicy(copy.deepcopy(model), dropout=p, grad_precision=gp) for gp in ("f32", "bf16") for p in (0.0, 0.1)}
+        for n in (64, 256, 1024):
+            boards = ops.synth_boards(n, seed=29 + n, device=dev)
+            x = boards.float() / 15
+            i = torch.arange(n, device=dev)
+            actions = (5 * i + 1) % 4
+            gen = torch.Generator(device=dev).manual_seed(n)
+            with torch.no_grad():
+                p32, v32 = model(x)
+            old = torch.log(p32.gather(1, actions[:, None])[:, 0]) + 0.5 * torch.randn(n, generator=gen, device=dev)
+            adv = (((13 * i) % 17 - 8) / 4.0 + 2.0 * x[:, 0]).float()
+            ret = (v32[:, 0] + 0.5 + ((7 * i) % 11 - 5) / 5.0).float()
+            grads = {}
+            for gp in ("f32", "bf16"):
+                nets[gp, 0.0].loss_and_grad(boards, actions, old, adv, ret)
+                flat, o, grads[gp] = nets[gp, 0.0].grad.double(), 0, []
+                for t in nets[gp, 0.0].parsed.plain_tensors():
+                    k = t.numel() if isinstance(t, torch.Tensor) else 1
+                    if isinstance(t, torch.Tensor):
+                        grads[gp].append(flat[o:o + k])
+                    o += k
+            away = max(float((a - b).abs().max() / b.abs().max()) for a, b in zip(grads["bf16"], grads["f32"]))
+            names = [(gp, p) for p in (0.0, 0.1) for gp in ("f32", "bf16")]
+            t = alternate([(key, (lambda net: lambda: net.loss_and_grad(boards, actions, old, adv, ret))(nets[key])) for key in names])
+            cell = lambda v: "%8.1f us [%7.1f - %7.1f]" % (statistics.median(v) * 1e6, min(v) * 1e6, max(v) * 1e6)      # noqa: E731
+            gain = lambda p: "%.2f x" % (statistics.median(t["f32", p]) / statistics.median(t["bf16", p]))             # noqa: E731
+            print("%-7d %-5d %-30s %-30s %-8s %-30s %-30s %-8s %.3g of the largest element" % (
+                dim_ff, n, cell(t["f32", 0.0]), cell(t["bf16", 0.0]), gain(0.0), cell(t["f32", 0.1]), cell(t["bf16", 0.1]), gain(0.1), away))
+        print("workspace at N = 1,024, dim_ff %d, 2 layers: f32 %.1f MiB, f32 with dropout %.1f MiB, bf16 %.1f MiB" % (
+            dim_ff, ops.tpolicy_grad_workspace_bytes(1024, dim_ff, LAYERS) / 2 ** 20, ops.tpolicy_train_workspace_bytes(1024, dim_ff, LAYERS) / 2 ** 20,
+            ops.tpolicy_bf16_workspace_bytes(1024, dim_ff, LAYERS) / 2 ** 20))
+
+
 if __name__ == "__main__":
-    dropout_table() if sys.argv[1:] == ["--dropout"] else main()
+    if sys.argv[1:] == ["--grad-precision", "bf16"]:
+        precision_table()
+    else:
+        dropout_table() if sys.argv[1:] == ["--dropout"] else main()
