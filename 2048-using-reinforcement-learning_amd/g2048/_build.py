@@ -11,6 +11,7 @@ csrc/libg2048_tpolicy_collect_hip.so, for gfx950 with hipcc (cross-compiles with
     python -m g2048._build --ppo-collect [-o LIBRARY] [extra compiler flags ...]   (the PPO experience collector's library alone)
     python -m g2048._build --tpolicy-collect [-o LIBRARY] [extra compiler flags ...]   (the transformer policy's collector alone)
     python -m g2048._build --tbf16 [-o LIBRARY] [extra compiler flags ...]   (the transformer policy's bf16 gradient library alone)
+    python -m g2048._build --search [-o LIBRARY] [extra compiler flags ...]  (the expectimax agent's library alone)
 
 The libraries are built in-tree so that they travel with the source snapshot; they are
 git-ignored. -ffp-contract=off is REQUIRED: the reward / heuristic kernels follow
@@ -34,7 +35,8 @@ EXTRA_ROWS is the fourth and LAST table of that row shape: the tests pin ROWS, t
 nothing pins this one's size, so the next library is one more row here and not a fifth table. Its first row is
 libg2048_tpolicy_collect_hip.so (include/g2048_tpolicy_collect.h: the transformer policy's experience collection in one launch); its
 second is libg2048_tbf16_hip.so (include/g2048_tbf16.h: the transformer policy's gradient pass with bf16 feed-forward products; the
-kernels are the learner library's plus csrc/g2048_tpolicy_bf16.h).
+kernels are the learner library's plus csrc/g2048_tpolicy_bf16.h); its third is libg2048_search_hip.so (include/g2048_search.h: the
+expectimax agent's decisions and complete games; csrc/g2048_expectimax.hip with the value function in csrc/g2048_expectimax.h).
 Everything below reads ALL_ROWS, every table.
 """
 import os
@@ -67,6 +69,7 @@ EXTRA_ROWS = {
     "TPOLICY_COLLECT_": ("libg2048_tpolicy_collect_hip.so", "G2048_TPOLICY_COLLECT_LIB", ["g2048_tpolicy_collect.hip"],
                          ["g2048_tpolicy_collect.h"]),
     "TBF16_": ("libg2048_tbf16_hip.so", "G2048_TBF16_LIB", ["g2048_tpolicy_bf16.hip"], ["g2048_tbf16.h"]),
+    "SEARCH_": ("libg2048_search_hip.so", "G2048_SEARCH_LIB", ["g2048_expectimax.hip"], ["g2048_search.h"]),
 }
 ALL_ROWS = {**ROWS, **EXTRA_ROWS}  # every shared object of the build
 PUBLIC_HEADERS = [os.path.join(INCLUDE, h) for row in ALL_ROWS.values() for h in row[3]]
@@ -124,7 +127,7 @@ def build(force=False, verbose=False, lib=None, extra_flags=()):
     return path_of("")
 
 
-if __name__ == "__main__":          # [--train | --tlearn | --tstep | --ttrain | --collect | --ppo-collect | --tpolicy-collect] [-o LIBRARY] [extra compiler flags ...]
+if __name__ == "__main__":          # [--train | --tlearn | --tstep | --ttrain | --collect | --ppo-collect | --tpolicy-collect | --tbf16 | --search] [-o LIBRARY] [extra compiler flags ...]
     out, args = None, sys.argv[1:]
     key = next((k for k in ALL_ROWS if k and args[:1] == ["--" + k[:-1].lower().replace("_", "-")]), None)
     if key:

@@ -2,7 +2,8 @@
 g2048_tlearn.h, g2048_tstep.h, g2048_ttrain.h): one Library per row of _build.LIBRARIES, each with its own table, error string and version;
 and of the extensions libg2048_collect_hip.so (g2048_collect.h), the one row of _build.EXTENSIONS, and libg2048_ppo_collect_hip.so
 (g2048_ppo_collect.h), the one row of _build.PPO_EXTENSIONS, bound by the same Library class; and of the rows of _build.EXTRA_ROWS, the
-open-ended fourth table: libg2048_tpolicy_collect_hip.so (g2048_tpolicy_collect.h) and libg2048_tbf16_hip.so (g2048_tbf16.h).
+open-ended fourth table: libg2048_tpolicy_collect_hip.so (g2048_tpolicy_collect.h), libg2048_tbf16_hip.so (g2048_tbf16.h) and
+libg2048_search_hip.so (g2048_search.h).
 
 There is no fallback: if the library is missing or no HIP device is visible, every
 compute call raises. PyTorch is only used for device memory and streams -- tensors
@@ -217,6 +218,16 @@ TBF16_SIGNATURES = {
     "g2048_tbf16_test_dw": (_int, [_vp, _int, _vp, _int, _vp, _vp, _sz, _int, _int, _vp, _sz, _vp]),
 }
 
+SEARCH_ABI_VERSION = 1
+EXPECTIMAX_MAX_DEPTH = 3
+SEARCH_SIGNATURES = {
+    "g2048_search_last_error": (C.c_char_p, []),
+    "g2048_search_abi_version": (_int, []),
+    "g2048_expectimax_actions": (_int, [_vp, _vp, _vp, _vp, _int, _int, _int, _sz, _vp]),
+    "g2048_play_expectimax_workspace": (_sz, [_sz]),
+    "g2048_play_expectimax_games": (_int, [_vp, _vp, _int, _int, _int] + [_vp] * 7 + [_int, _u64, _u64, _sz, _u32, _vp, _sz, _vp]),
+}
+
 
 class Library:
     """One shared object of _build.ALL_ROWS (row `key`, of whichever table), loaded on first use and as loud as can be: a missing file, a file under
@@ -313,7 +324,8 @@ TPOLICY_COLLECT = Library("TPOLICY_COLLECT_", "g2048_tpolicy_collect", TPOLICY_C
                           "transformer policy collector", " and no experience collection of the transformer policy in one launch without it")
 TBF16 = Library("TBF16_", "g2048_tbf16", TBF16_SIGNATURES, TBF16_ABI_VERSION, "bf16 learner",
                 " and no bf16 gradient pass of the transformer policy without it")
-EXTRA_ROWS = {"TPOLICY_COLLECT_": TPOLICY_COLLECT, "TBF16_": TBF16}
+SEARCH = Library("SEARCH_", "g2048_search", SEARCH_SIGNATURES, SEARCH_ABI_VERSION, "search", " and no expectimax agent without it")
+EXTRA_ROWS = {"TPOLICY_COLLECT_": TPOLICY_COLLECT, "TBF16_": TBF16, "SEARCH_": SEARCH}
 
 # the names the package, the tools and the tests call
 library_path, lib, check, call = MAIN.path, MAIN.load, MAIN.check, MAIN.call
@@ -325,6 +337,7 @@ collect_library_path, collect_lib, collect_call = COLLECT.path, COLLECT.load, CO
 ppo_collect_library_path, ppo_collect_lib, ppo_collect_call = PPO_COLLECT.path, PPO_COLLECT.load, PPO_COLLECT.call
 tpolicy_collect_library_path, tpolicy_collect_lib, tpolicy_collect_call = TPOLICY_COLLECT.path, TPOLICY_COLLECT.load, TPOLICY_COLLECT.call
 tbf16_library_path, tbf16_lib, tbf16_call = TBF16.path, TBF16.load, TBF16.call
+search_library_path, search_lib, search_call = SEARCH.path, SEARCH.load, SEARCH.call
 
 
 def stream_ptr(device):

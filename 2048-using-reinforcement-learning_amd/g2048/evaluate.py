@@ -294,6 +294,38 @@ def evaluate_qnet(qnet, num_games=4096, max_moves=2000, epsilon=0.0, seed=0x2048
         params, game_id_base, histories)
 
 
+def evaluate_expectimax(num_games=4096, depth=2, max_moves=5000, seed=0x2048, game_id_base=0, fused=True, device=None,
+                        early_game_threshold=512, mid_game_threshold=1024, histories=None, max_waves=0):
+    """Complete games of the expectimax agent (ops.expectimax_actions: the expectation over all spawn successors, `depth` plies,
+    1..3, the beam agent's leaf heuristic): decide -> env step until the game is over or max_moves moves were made. Game g starts
+    from VecGame2048's reset of global id game_id_base + g; the agent draws nothing, so `seed` is the env's alone.
+
+    fused=True: every game is played to the end in ONE launch (g2048_play_expectimax_games; max_waves = its wavefront count,
+    one game in flight each, 0 = as many as the chip holds). fused=False: the move-by-move loop of the launches that exist apart
+    from it -- expectimax_actions, step, track_episodes -- over the whole batch until every game has ended: the yardstick; the
+    games are identical. Returns evaluate_policy's result dict, episode_rewards included; "parameters" holds depth, the two
+    thresholds, max_moves, num_games and seed. histories: as in evaluate_beam_search (fused driver only)."""
+    n, depth, max_moves = int(num_games), int(depth), int(max_moves)
+    early, mid = int(early_game_threshold), int(mid_game_threshold)
+    ops._check_expectimax(depth, early, mid)
+    if max_moves < 1:
+        raise ValueError("g2048.evaluate_expectimax: max_moves must be at least 1")
+    if histories is not None and not fused:
+        raise ValueError("g2048.evaluate_expectimax: histories need the fused driver (fused=True)")
+    dev = torch.device("cuda" if device is None else device)
+
+    def act(boards, t):
+        return ops.expectimax_actions(boards, depth, None, False, early, mid)
+
+    return _evaluate_net(
+        dev, fused,
+        lambda env, want_actions: ops.play_expectimax_games(env.boards, env.scores, depth, max_moves, early, mid, seed, game_id_base,
+                                                            want_rewards=True, want_actions=want_actions, max_waves=max_waves),
+        lambda env: _play_policy_stepwise(env, None, None, max_moves, None, seed, game_id_base, act=act),
+        {"depth": depth, "early_game_threshold": early, "mid_game_threshold": mid, "max_moves": max_moves, "num_games": n, "seed": seed},
+        game_id_base, histories)
+
+
 BEAM_GAMMA = 0.99           # DQNAgent's gamma (hybrid.py:769); it enters the search only at search_depth 1
 
 

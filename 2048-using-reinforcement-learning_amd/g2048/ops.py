@@ -1600,6 +1600,63 @@ def play_qnet_beam_games(boards, scores, packed, dim_ff, n_layers, precision="f3
                             boards.shape[0], POLICY_PRECISIONS[precision], int(max_waves)))
 
 
+def _check_expectimax(depth, early_threshold, mid_threshold):
+    if not 1 <= int(depth) <= L.EXPECTIMAX_MAX_DEPTH:
+        raise ValueError("g2048: expectimax depth must be 1 .. %d" % L.EXPECTIMAX_MAX_DEPTH)
+    if int(early_threshold) < 0 or int(mid_threshold) < 0:
+        raise ValueError("g2048: the phase thresholds are tile values and cannot be negative")
+
+
+def expectimax_actions(boards, depth=2, mask=None, want_values=False, early_threshold=512, mid_threshold=1024, actions=None, values=None):
+    """The expectimax agent's decision for every board (g2048_expectimax_actions, include/g2048_search.h): the valid action with
+    the largest expectation over ALL spawn successors (tile 2 with 0.9, tile 4 with 0.1) of the value `depth` plies down, the
+    leaves valued by the beam agent's heuristic; env moves, ties to the lowest action, 0 where no move is left. mask: optional
+    uint8 (n,), bit a = action a may be chosen (ANDed with the env's valid moves). Returns actions (uint8 (n,)), or with
+    want_values (or a `values` tensor) the pair (actions, values): float64 (n,4), -inf for a move that is invalid or masked out.
+    One launch, one wavefront per board; the f64 sums are taken in a fixed order, so the bits do not depend on the launch."""
+    L.require_device_tensor(boards, torch.uint8, (16,), "boards")
+    _check_expectimax(depth, early_threshold, mid_threshold)
+    n, dev = boards.shape[0], boards.device
+    if mask is not None:
+        L.require_device_tensor(mask, torch.uint8, None, "mask")
+        if mask.numel() != n:
+            raise ValueError("g2048: mask must have one byte per board")
+    actions = _output(actions, n, torch.uint8, (), "actions", dev)
+    if want_values or values is not None:
+        values = _output(values, n, torch.float64, (4,), "values", dev)
+    L.search_call(dev, L.search_lib().g2048_expectimax_actions, boards.data_ptr(), mask.data_ptr() if mask is not None else None,
+                  actions.data_ptr(), values.data_ptr() if values is not None else None, int(depth), int(early_threshold),
+                  int(mid_threshold), n, L.stream_ptr(dev))
+    return (actions, values) if values is not None else actions
+
+
+def play_expectimax_games(boards, scores, depth=2, max_moves=5000, early_threshold=512, mid_threshold=1024, seed=0x2048, game_id_base=0,
+                          want_rewards=True, want_actions=False, max_waves=0):
+    """Every game played to the end by the expectimax agent in ONE launch (g2048_play_expectimax_games): per move the decision of
+    expectimax_actions at `depth` (no mask), then the env step. boards / scores are updated in place. Returns
+    play_policy_games' dict of per-game tensors: moves, valid_moves, invalid_moves (int32), milestone_move (int32 (n,8), -1 =
+    never), alive (uint8), with want_rewards "reward_sum" (float64) and with want_actions "actions" (uint8 (n, max_moves), 0xFF
+    from a game's end on: the input of `replay_games`). max_waves: the number of wavefronts (one game in flight each), 0 = as
+    many as the chip holds (the games are the same for every value)."""
+    L.require_device_tensor(boards, torch.uint8, (16,), "boards")
+    _require_scores(scores)
+    _check_expectimax(depth, early_threshold, mid_threshold)
+    out = _net_game_results(boards, scores, max_moves, max_waves, "max_waves", want_rewards, want_actions)
+    n, dev = boards.shape[0], boards.device
+    lib = L.search_lib()
+    need = int(lib.g2048_play_expectimax_workspace(n))
+    ptr = lambda k: out[k].data_ptr() if k in out else None      # noqa: E731
+    box = _PLAY_NET_WS.get((_dev_index(dev), L.stream_ptr(dev)), _ScratchBox)
+    with box.lock:          # grow-if-needed and enqueue as one step (see beam_get_action)
+        if box.buf is None or box.buf.numel() < need:
+            box.buf = torch.empty(need, dtype=torch.uint8, device=dev)
+        L.search_call(dev, lib.g2048_play_expectimax_games, boards.data_ptr(), scores.data_ptr(), int(depth), int(early_threshold),
+                      int(mid_threshold), out["moves"].data_ptr(), out["valid_moves"].data_ptr(), out["invalid_moves"].data_ptr(),
+                      out["milestone_move"].data_ptr(), ptr("reward_sum"), out["alive"].data_ptr(), ptr("actions"), int(max_moves),
+                      L.u64(seed), L.u64(game_id_base), n, int(max_waves), box.buf.data_ptr(), need, L.stream_ptr(dev))
+    return out
+
+
 def replay_games(boards0, actions, n_moves, seed, game_ids=None, game_id_base=0, scores0=None, longest=None):
     """Recorded games replayed into their per-move histories (g2048_replay_games; reference evaluate_beam_search.py:44-50,
     :72-75: board_history / scores_history / max_tiles_history of run_game). boards0 uint8 (k,16): where each game started;

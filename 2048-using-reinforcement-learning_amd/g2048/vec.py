@@ -260,3 +260,23 @@ class BatchedBeamSearch:
                                   want_expanded, history=self._history)
         self.decisions += 1
         return res
+
+
+class BatchedExpectimax:
+    """The expectimax agent for many games at once: per board the valid move with the largest expectation over all spawn
+    successors, `depth` plies deep (1..3), leaves valued by BeamSearchAgent._evaluate_state (ops.expectimax_actions). It draws
+    nothing, so it has no seed; env moves, no DOWN quirk."""
+
+    def __init__(self, depth=2, early_game_threshold=512, mid_game_threshold=1024):
+        if not 1 <= int(depth) <= L.EXPECTIMAX_MAX_DEPTH:
+            raise ValueError("g2048: expectimax depth must be 1 .. %d" % L.EXPECTIMAX_MAX_DEPTH)
+        self.depth = int(depth)
+        self.early_game_threshold, self.mid_game_threshold = int(early_game_threshold), int(mid_game_threshold)
+        self.decisions = 0
+
+    def get_actions(self, boards, valid_mask=None, want_values=False):
+        """boards uint8 (n,16); valid_mask: optional uint8 (n,), ANDed with the env's valid moves. Returns actions uint8 (n,), or
+        (actions, values float64 (n,4)) with want_values."""
+        res = ops.expectimax_actions(boards, self.depth, valid_mask, want_values, self.early_game_threshold, self.mid_game_threshold)
+        self.decisions += 1
+        return res
